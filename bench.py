@@ -6,7 +6,13 @@ image/caption pairs already resident in HBM, the RCCL all-gather of the L2-norma
 N > 1, and the fused InfoNCE on the local [b, N*b] logit strips.  Pure data parallelism, weak scaling
 (per-GPU batch fixed).  Prints ONE JSON line on rank 0.
 
+A plain run only sets up, warms up, times the K steps and prints the headline.  `--full` adds the rest, as one run: the in-situ
+roofline of the vision c_fc GEMM (HIP events around its launches inside the timed region), the CPU baseline (`--cpu-seconds`) and
+the per-class `breakdown` step.  `--dump-outputs DIR` writes what the last timed step returned (L2-normalised image and text
+embeddings, logit scale, loss) as float32 .npy files, for comparing two builds on the same seeded inputs.
+
     python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full --dump-outputs out/
     python bench.py --gpus N --steps K --warmup W          # launches its own N ranks (one process per GPU) and relays rank 0's line
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W             # the same, under an external launcher
@@ -40,8 +46,12 @@ def parse():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=256, help="per-GPU batch (images = captions)")
     ap.add_argument("--model", default="vit-large-patch14-224")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline budget (0 = skip)")
-    ap.add_argument("--breakdown", action="store_true", help="extra untimed step timing every kernel class")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: in-situ c_fc roofline, CPU baseline, per-class breakdown")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (rank 0) as DIR/<name>.npy, float32")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="with --full: CPU baseline budget (0 = skip)")
+    ap.add_argument("--breakdown", action="store_true", help="extra untimed step timing every kernel class (implied by --full)")
     ap.add_argument("--micro-batches", type=int, default=1,
                     help="encode this many micro-batches of --batch pairs per step, one InfoNCE over all of them "
                          "(config #5: 16 x 256 per GPU = 32k pairs on 8 GPUs)")
@@ -50,7 +60,26 @@ def parse():
     ap.add_argument("--dry-run-gloo", action="store_true",
                     help="CPU rehearsal of the multi-rank plumbing (launcher, rendezvous, rank-ordered all-gather, barrier-fenced "
                          "timing, max over ranks) on the gloo backend: runs no kernel and reports no throughput")
-    return ap.parse_args()
+    a = ap.parse_args()
+    a.breakdown = a.breakdown or a.full
+    return a
+
+
+DUMP_BUDGET = 64 << 20      # bytes of .npy data --dump-outputs may write
+
+
+def dump_outputs(d: str, feats: dict, scalars: dict) -> None:
+    """The arrays a caller of the timed path receives, as float32 .npy files.  Feature matrices that together exceed DUMP_BUDGET
+    are cut to the same evenly strided rows (row 0, s, 2s, ...), so that two builds dump the same sample."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    rows = next(iter(feats.values())).shape[0]
+    row_bytes = sum(v.shape[1] * 4 for v in feats.values())
+    stride = max(1, -(-rows * row_bytes // (DUMP_BUDGET - 4096)))
+    for name, v in feats.items():
+        np.save(os.path.join(d, name + ".npy"), v[::stride].float().cpu().numpy())
+    for name, v in scalars.items():
+        np.save(os.path.join(d, name + ".npy"), np.asarray(float(v), dtype=np.float32))
 
 
 def launch_ranks(n: int) -> int:
@@ -280,15 +309,17 @@ def main():
     mb = max(1, a.micro_batches)
 
     def step():
+        """-> (image features, text features, logit scale, loss): what a caller of the step receives."""
         if mb == 1:
             ni, nt, s = model(images, tokens)
-            return loss_fn(ni, nt, s)
+            return ni, nt, s, loss_fn(ni, nt, s)
         fi, ft = [], []
         for _ in range(mb):                    # the same resident micro-batch each time: synthetic data, full arithmetic
             ni, nt, s = model(images, tokens)
             fi.append(ni)
             ft.append(nt)
-        return loss_fn(torch.cat(fi), torch.cat(ft), s)
+        ni, nt = torch.cat(fi), torch.cat(ft)
+        return ni, nt, s, loss_fn(ni, nt, s)
 
     def fence():
         torch.cuda.synchronize()
@@ -297,32 +328,37 @@ def main():
         torch.cuda.synchronize()
 
     for _ in range(a.warmup):
-        loss = step()
+        res = step()
     if a.precision != "bf16" and a.warmup > 0 and os.environ.get("OVHIP_FP8_DYNAMIC", "0") != "1":
         model.freeze_fp8_scales()              # static scales of the MLP hidden, calibrated on the warm-up steps
-        loss = step()
-    # in-situ timing of the dominant kernel (the vision MLP c_fc GEMM) during the timed region
-    nrec = a.steps * max(1, a.micro_batches) * cfg["vision_cfg"]["layers"] + 8
-    _lib.check(lib.ov_profile_enable(1 << PROF_CLASSES["gemm_fc"], nrec), "ov_profile_enable")
+        res = step()
+    if a.full:
+        # in-situ timing of the dominant kernel (the vision MLP c_fc GEMM) during the timed region
+        nrec = a.steps * max(1, a.micro_batches) * cfg["vision_cfg"]["layers"] + 8
+        _lib.check(lib.ov_profile_enable(1 << PROF_CLASSES["gemm_fc"], nrec), "ov_profile_enable")
     comm_log = []
     record_comm(comm_log if world > 1 else None)
     fence()
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        loss = step()
+        res = step()
     fence()
     dt = time.perf_counter() - t0
     record_comm(None)
     comm = comm_summary(comm_log, dt, a.steps, b * mb * 2 * cfg["embed_dim"] * 4, world, dev)
-    tot, cnt, rows = C.c_double(0), C.c_int(0), C.c_double(0)
-    _lib.check(lib.ov_profile_read(PROF_CLASSES["gemm_fc"], C.byref(tot), C.byref(cnt), C.byref(rows)), "ov_profile_read")
-    _lib.check(lib.ov_profile_enable(0, 0), "ov_profile_enable")
+    if a.full:
+        tot, cnt, rows = C.c_double(0), C.c_int(0), C.c_double(0)
+        _lib.check(lib.ov_profile_read(PROF_CLASSES["gemm_fc"], C.byref(tot), C.byref(cnt), C.byref(rows)), "ov_profile_read")
+        _lib.check(lib.ov_profile_enable(0, 0), "ov_profile_enable")
     if world > 1:
         tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
     model.check_token_range()
+    ni, nt, scale, loss = res
     loss_val = float(loss)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"image_features": ni, "text_features": nt}, {"logit_scale": scale, "loss": loss})
 
     # per-class breakdown (diagnostic, untimed)
     breakdown = None
@@ -352,27 +388,38 @@ def main():
     if rank == 0:
         flops = synth.model_flops(cfg)
         vl, tl = cfg["vision_cfg"]["layers"], cfg["text_cfg"]["layers"]
-        # dominant kernel: gemm_bf16_256x256<GELU> (c_fc).  Algorithmic FLOP per launch = 2*M*N*K.
-        g = S // cfg["vision_cfg"]["patch_size"]
-        Lv, Dv, Dt = g * g + 1, cfg["vision_cfg"]["width"], cfg["text_cfg"]["width"]
-        launches = max(cnt.value, 1)
-        # M of the timed launches comes from the library (the tower may peel tail images onto a side stream)
-        flop_per_launch = 2.0 * (rows.value / launches) * Dv * int(Dv * cfg["vision_cfg"]["mlp_ratio"])
-        avg_ms = tot.value / launches
-        achieved = flop_per_launch / (avg_ms * 1e-3) / 1e12 if avg_ms > 0 else 0.0
-        traffic = None
-        tp = os.path.join(ROOT, "profiles", "traffic.json")
-        if os.path.exists(tp):
-            try:
-                tj = json.load(open(tp))
-                if tj.get("model", "vit-large-patch14-224") == a.model and tj.get("batch", 256) == b:
-                    traffic = tj.get("gemm_fc_bytes_per_launch")
-            except Exception:
-                traffic = None
         from openvision_amd.model import fp8_mixed_mask
         eff_mask = 0 if a.precision == "bf16" else (a.fp8_mask if a.fp8_mask >= 0 else (15 if a.precision == "fp8" else fp8_mixed_mask(1)[0]))
-        fc_fp8 = bool(eff_mask & 4)                      # the roofline kernel (vision c_fc) runs on the fp8 MFMA
-        peak_tf = PEAK_FP8_TFLOPS if fc_fp8 else PEAK_BF16_TFLOPS
+        roofline = None
+        if a.full:
+            # dominant kernel: gemm_bf16_256x256<GELU> (c_fc).  Algorithmic FLOP per launch = 2*M*N*K.
+            Dv = cfg["vision_cfg"]["width"]
+            launches = max(cnt.value, 1)
+            # M of the timed launches comes from the library (the tower may peel tail images onto a side stream)
+            flop_per_launch = 2.0 * (rows.value / launches) * Dv * int(Dv * cfg["vision_cfg"]["mlp_ratio"])
+            avg_ms = tot.value / launches
+            achieved = flop_per_launch / (avg_ms * 1e-3) / 1e12 if avg_ms > 0 else 0.0
+            traffic = None
+            tp = os.path.join(ROOT, "profiles", "traffic.json")
+            if os.path.exists(tp):
+                try:
+                    tj = json.load(open(tp))
+                    if tj.get("model", "vit-large-patch14-224") == a.model and tj.get("batch", 256) == b:
+                        traffic = tj.get("gemm_fc_bytes_per_launch")
+                except Exception:
+                    traffic = None
+            fc_fp8 = bool(eff_mask & 4)                      # the roofline kernel (vision c_fc) runs on the fp8 MFMA
+            peak_tf = PEAK_FP8_TFLOPS if fc_fp8 else PEAK_BF16_TFLOPS
+            roofline = {"bound": "mfma", "kernel": (fc_kernel_name(int(rows.value / launches), int(Dv * cfg['vision_cfg']['mlp_ratio'])) if not fc_fp8
+                                                    else "gemm_fp8_persist<1> (dequantise + bias + erf-GELU)")
+                                  + f" = vision mlp.c_fc, N={int(Dv * cfg['vision_cfg']['mlp_ratio'])} K={Dv}, "
+                                  f"M={int(rows.value / launches)} rows per launch",
+                        "achieved": round(achieved, 1), "peak": peak_tf, "unit": "TFLOP/s",
+                        "frac": round(achieved / peak_tf, 4), "traffic": traffic if a.precision == "bf16" else None,
+                        "traffic_source": ("profiles/traffic.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of an earlier run of this "
+                                           "command, NOT measured in this run") if (traffic is not None and a.precision == "bf16") else None,
+                        "avg_launch_ms": round(avg_ms, 4), "launches": cnt.value,
+                        "flop_per_launch": flop_per_launch}
         out = {
             "metric": "images/sec (node) ViT-L/14@224 fwd+InfoNCE" if a.model == "vit-large-patch14-224"
                       else f"images/sec (node) {a.model} fwd+InfoNCE",
@@ -389,21 +436,12 @@ def main():
                        "gflop_per_pair": round(flops["pair"] / 1e9, 2),
                        "model_tflops_per_gpu": round(flops["pair"] * b * mb * a.steps / dt / 1e12, 1)},
             "loss": round(loss_val, 5),
-            "roofline": {"bound": "mfma", "kernel": (fc_kernel_name(int(rows.value / launches), int(Dv * cfg['vision_cfg']['mlp_ratio'])) if not fc_fp8
-                                                     else "gemm_fp8_persist<1> (dequantise + bias + erf-GELU)")
-                                   + f" = vision mlp.c_fc, N={int(Dv * cfg['vision_cfg']['mlp_ratio'])} K={Dv}, "
-                                   f"M={int(rows.value / launches)} rows per launch",
-                         "achieved": round(achieved, 1), "peak": peak_tf, "unit": "TFLOP/s",
-                         "frac": round(achieved / peak_tf, 4), "traffic": traffic if a.precision == "bf16" else None,
-                         "traffic_source": ("profiles/traffic.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of an earlier run of this "
-                                            "command, NOT measured in this run") if (traffic is not None and a.precision == "bf16") else None,
-                         "avg_launch_ms": round(avg_ms, 4), "launches": cnt.value,
-                         "flop_per_launch": flop_per_launch},
+            "roofline": roofline,
         }
         out["comm"] = comm
         if breakdown:
             out["breakdown"] = breakdown
-        if world == 1 and a.cpu_seconds > 0:
+        if a.full and world == 1 and a.cpu_seconds > 0:
             out["cpu_baseline"] = cpu_baseline(cfg, sd, a.cpu_seconds)
         else:
             out["cpu_baseline"] = None

@@ -1,4 +1,4 @@
-"""CPU: bench.py's bookkeeping (no GPU): per-class algorithmic work adds up to the model FLOP count, host core detection."""
+"""CPU: bench.py's bookkeeping (no GPU): per-class algorithmic work adds up to the model FLOP count, host core detection, output dumps."""
 import importlib.util
 import os
 
@@ -32,6 +32,26 @@ def test_class_work_matches_model_flops(bench, name):
 def test_host_cores_is_sane(bench):
     n = bench.host_cores()
     assert 1 <= n <= 16
+
+
+def test_dump_outputs_float32_within_budget(bench, tmp_path, monkeypatch):
+    """--dump-outputs: one float32 .npy per output; feature rows beyond the byte budget are cut to the same strided sample."""
+    import numpy as np
+    import torch
+    g = torch.Generator().manual_seed(0)
+    fi, ft = torch.randn(1000, 96, generator=g), torch.randn(1000, 96, generator=g).double()
+    scalars = {"logit_scale": torch.tensor(14.25), "loss": torch.tensor(5.5, dtype=torch.float64)}
+    bench.dump_outputs(str(tmp_path / "all"), {"image_features": fi, "text_features": ft}, scalars)
+    a = {p.stem: np.load(p) for p in (tmp_path / "all").iterdir()}
+    assert set(a) == {"image_features", "text_features", "logit_scale", "loss"} and all(v.dtype == np.float32 for v in a.values())
+    assert np.array_equal(a["image_features"], fi.numpy()) and a["text_features"].shape == (1000, 96) and a["loss"] == 5.5
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 200 * 1024)
+    bench.dump_outputs(str(tmp_path / "cut"), {"image_features": fi, "text_features": ft}, scalars)
+    files = list((tmp_path / "cut").iterdir())
+    assert sum(p.stat().st_size for p in files) <= 200 * 1024
+    i, t = np.load(tmp_path / "cut" / "image_features.npy"), np.load(tmp_path / "cut" / "text_features.npy")
+    # 1000 rows of 2 x 96 x 4 bytes = 768 000 bytes against a 200 KiB budget: every 4th row
+    assert len(i) == len(t) == 250 and np.array_equal(i, fi.numpy()[::4]) and np.array_equal(t, ft.float().numpy()[::4])
 
 
 def test_bench_launches_its_own_ranks_gloo_dry_run():

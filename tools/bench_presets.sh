@@ -5,6 +5,6 @@ mkdir -p $OUT
 : > $OUT/presets.jsonl
 for spec in "$@"; do
   model=${spec%%:*}; batch=${spec##*:}
-  timeout -k 10 280 python bench.py --model $model --batch $batch --steps 8 --warmup 3 --cpu-seconds 0 2>/dev/null | tail -1 >> $OUT/presets.jsonl || echo "{\"model\": \"$model\", \"failed\": true}" >> $OUT/presets.jsonl
+  timeout -k 10 280 python bench.py --model $model --batch $batch --steps 8 --warmup 3 --full --cpu-seconds 0 2>/dev/null | tail -1 >> $OUT/presets.jsonl || echo "{\"model\": \"$model\", \"failed\": true}" >> $OUT/presets.jsonl
 done
 echo done

@@ -444,6 +444,36 @@ size_t ov_tower_backward_workspace_bytes(const ov_tower* t, int B, int L);
 int    ov_tower_backward(const ov_tower* t, const ov_bf16* saved, ov_bf16* dx, const ov_block_grads* grads, int B, int L,
                          void* workspace, size_t workspace_bytes, ov_stream_t stream);
 
+/* Input gradients only (frozen weights: feature visualisation, gradient ascent on the inputs): ov_tower_backward over the same saved
+ * activations without any parameter-gradient work (no dW products, bias or LayerNorm parameter sums).  dx is bitwise the dx of
+ * ov_tower_backward. */
+size_t ov_tower_backward_input_workspace_bytes(const ov_tower* t, int B, int L);
+int    ov_tower_backward_input(const ov_tower* t, const ov_bf16* saved, ov_bf16* dx, int B, int L, void* workspace, size_t workspace_bytes,
+                               ov_stream_t stream);
+
+/* ---- MLP-feature objective (feature visualisation: a forward hook on resblocks[layer].mlp.gelu, ov-feature-visualization.py:211) --
+ * The attention half of one block, x1 = x + out_proj(attn(ln_1(x))) (transformer.py:263), keeping qkv [B*L, 3D], attn_out [B*L, D],
+ * x1 [B*L, D] and, where the resident attention backward reads it (head_dim 64, L <= 288), lse [B*heads][L rounded up to 32] fp32
+ * (NULL = not kept).  `w` holds the module's own weights; only ln_1, in_proj and out_proj are read. */
+int ov_block_attn_forward_saving(const ov_tower_cfg* cfg, const ov_block_weights* w, const ov_bf16* x, ov_bf16* qkv, ov_bf16* attn_out,
+                                 ov_bf16* x1, float* lse, int B, int L, ov_stream_t stream);
+/* Its input gradient: dx = dx1 + (out_proj, attention, in_proj, ln_1 backward of dx1); no parameter gradients. */
+size_t ov_block_attn_backward_input_workspace_bytes(const ov_tower_cfg* cfg, int B, int L);
+int ov_block_attn_backward_input(const ov_tower_cfg* cfg, const ov_block_weights* w, const ov_bf16* x, const ov_bf16* qkv,
+                                 const ov_bf16* attn_out, const float* lse /* or NULL */, const ov_bf16* dx1, ov_bf16* dx, int B, int L,
+                                 void* workspace, size_t workspace_bytes, ov_stream_t stream);
+/* pre[r] = ln_2(x1[r]) . fc_w[feature] + fc_b[feature] (fp32 [B*L]; fc_b may be NULL), mean[b] = mean over tokens 1 .. L-1 of
+ * gelu(pre[b*L + t]) (fp32 [B]; erf or tanh GELU, exact).  0 <= feature < mlp (the true hidden width, not the padded one); L >= 2;
+ * D % 8 == 0, D <= 4096.  Deterministic (fixed-order reduction), no workspace. */
+int ov_mlp_feature_forward(const ov_bf16* x1, int64_t ldx, const float* ln2_w, const float* ln2_b, const ov_bf16* fc_w, int64_t ldw,
+                           const float* fc_b, int feature, int mlp, int gelu_tanh, int B, int L, int D, float eps, float* pre, float* mean,
+                           ov_stream_t stream);
+/* dx1[r] = ln_2-backward(x1[r], g_t * fc_w[feature]) with g_t = dmean[b] / (L-1) * gelu'(pre[r]) for t >= 1 and 0 for the CLS row:
+ * d sum_b dmean[b] mean[b] / d x1, bf16 [B*L, D].  dmean: DEVICE fp32 [B]. */
+int ov_mlp_feature_backward(const ov_bf16* x1, int64_t ldx, const float* ln2_w, const ov_bf16* fc_w, int64_t ldw, int feature, int mlp,
+                            int gelu_tanh, const float* pre, const float* dmean, ov_bf16* dx1, int64_t lddx, int B, int L, int D, float eps,
+                            ov_stream_t stream);
+
 typedef struct {      /* VisionTransformer front/back ends (OpenVision: no ln_pre, no conv bias) */
     int image_size, patch_size, kpad;              /* kpad = roundup(3*P*P, 64) */
     int pool_avg;                                  /* 1 = 'avg' (skip cls), 0 = 'tok' */

@@ -129,6 +129,16 @@ SIGNATURES = {
     "ov_block_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_size_t,
                                   c_void_p]),
     "ov_tower_saved_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "ov_tower_backward_input_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "ov_tower_backward_input": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "ov_block_attn_forward_saving": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "ov_block_attn_backward_input_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "ov_block_attn_backward_input": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                             c_void_p, c_size_t, c_void_p]),
+    "ov_mlp_feature_forward": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                       c_int, c_float, c_void_p, c_void_p, c_void_p]),
+    "ov_mlp_feature_backward": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                        c_int64, c_int, c_int, c_int, c_float, c_void_p]),
     "ov_clip_loss_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p,
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "ov_adamw_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float, c_float, c_int, c_float,

@@ -172,8 +172,9 @@ __global__ __launch_bounds__(256) void splitk_sum(const ov_bf16* __restrict__ pa
 }
 
 // LayerNorm backward, wave per row (row in registers, like the forward).  dgamma / dbeta partial sums stay in the wave's
-// registers across the rows it owns and are written once: part[wave_global][2][D].
-template <int NCH>
+// registers across the rows it owns and are written once: part[wave_global][2][D].  PARAMS = false: dx only (the input-only
+// backward of frozen weights); the dx arithmetic is the same instruction for instruction.
+template <int NCH, bool PARAMS = true>
 __global__ __launch_bounds__(256) void layernorm_bwd_rows(const ov_bf16* __restrict__ x, int64_t ldx, const float* __restrict__ gamma,
                                                           const ov_bf16* __restrict__ dy, int64_t lddy, const ov_bf16* __restrict__ dres,
                                                           int64_t lddres, ov_bf16* __restrict__ dx, int64_t lddx, int64_t rows, int D,
@@ -225,8 +226,10 @@ __global__ __launch_bounds__(256) void layernorm_bwd_rows(const ov_bf16* __restr
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     const float xh = (v[c][e] - mean) * rstd;
-                    ag[c][e] = fmaf(q[c][e], xh, ag[c][e]);          // dgamma += dy * xhat
-                    ab[c][e] += q[c][e];                             // dbeta  += dy
+                    if (PARAMS) {
+                        ag[c][e] = fmaf(q[c][e], xh, ag[c][e]);      // dgamma += dy * xhat
+                        ab[c][e] += q[c][e];                         // dbeta  += dy
+                    }
                     v[c][e] = xh;
                     q[c][e] *= g[e];                                 // q = dy * gamma
                     sq += q[c][e];
@@ -252,6 +255,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_rows(const ov_bf16* __restr
             }
         }
     }
+    if (!PARAMS) return;
     float* pg = part + ((int64_t)blockIdx.x * 4 + wave) * 2 * D;
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
@@ -613,4 +617,113 @@ extern "C" int ov_block_backward(const ov_tower_cfg* cfg, const ov_block_weights
     OV_TRY(ov_layernorm_backward(x, D, w->ln1_w, b.t1, D, b.dx1, D, dx, D, g->ln1_w, g->ln1_b, M, D, eps, b.ln, b.ln_bytes, stream));
 #undef OV_TRY
     return OV_OK;
+}
+
+// ---- input-only backward (frozen weights: feature visualisation, gradient ascent on the inputs) -----------------------------------
+// The dX chain of ov_block_backward and nothing else: no weight-gradient products, bias sums or LayerNorm parameter sums.  Every step
+// is the launch ov_block_backward makes for the same quantity (the same transposes, GEMMs, epilogues and LayerNorm-backward rows), so
+// dx comes out bitwise the same.
+namespace {
+// dX[M, K] = epi(dY[M, N] . W[N, K]): linear_backward's dX route (W^T staged in Wt [K, N], then ov_gemm contracting over N)
+int linear_dx(const ov_bf16* dY, int64_t lddy, const ov_bf16* W, int64_t ldw, int64_t M, int N, int K, ov_bf16* dX, int64_t lddx,
+              ov_bf16* Wt, ov_stream_t stream, int epi = OV_EPI_BIAS, const ov_bf16* R = nullptr, int64_t ldr = 0) {
+    int rc;
+    if ((rc = launch_transpose(W, ldw, N, N, K, Wt, N, (hipStream_t)stream)) != OV_OK) return rc;
+    return ov_gemm(dY, lddy, Wt, N, nullptr, dX, lddx, M, K, N, epi, R, ldr, 0, 0, 0, stream);
+}
+
+// dx = LN-backward(x, gamma, dy) (+ dres): ov_layernorm_backward's rows without the parameter sums
+int layernorm_dx(const ov_bf16* x, int64_t ldx, const float* gamma, const ov_bf16* dy, int64_t lddy, const ov_bf16* dres, int64_t lddres,
+                 ov_bf16* dx, int64_t lddx, int64_t rows, int D, float eps, ov_stream_t stream) {
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)lnb_blocks(rows)), blk(256);
+    const int nch = (D / 8 + 63) / 64;
+    float* np = nullptr;
+    if (nch <= 1) hipLaunchKernelGGL((layernorm_bwd_rows<1, false>), grid, blk, 0, st, x, ldx, gamma, dy, lddy, dres, lddres, dx, lddx, rows, D, eps, np);
+    else if (nch <= 2) hipLaunchKernelGGL((layernorm_bwd_rows<2, false>), grid, blk, 0, st, x, ldx, gamma, dy, lddy, dres, lddres, dx, lddx, rows, D, eps, np);
+    else if (nch <= 3) hipLaunchKernelGGL((layernorm_bwd_rows<3, false>), grid, blk, 0, st, x, ldx, gamma, dy, lddy, dres, lddres, dx, lddx, rows, D, eps, np);
+    else if (nch <= 4) hipLaunchKernelGGL((layernorm_bwd_rows<4, false>), grid, blk, 0, st, x, ldx, gamma, dy, lddy, dres, lddres, dx, lddx, rows, D, eps, np);
+    else hipLaunchKernelGGL((layernorm_bwd_rows<8, false>), grid, blk, 0, st, x, ldx, gamma, dy, lddy, dres, lddres, dx, lddx, rows, D, eps, np);
+    OV_LAUNCH_CHECK();
+    return OV_OK;
+}
+
+struct InputBufs { ov_bf16 *wt, *dh, *t1, *dx1, *dqkv; char* att; size_t att_bytes, total; };
+// mlp = false: the attention half only (no dh, no dx1)
+inline InputBufs plan_input(const ov_tower_cfg* c, int B, int L, bool mlp, char* base) {
+    const int64_t M = (int64_t)B * L;
+    const int D = c->width, F = c->mlp_pad;
+    InputBufs b;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += align256(bytes); return p; };
+    const int64_t wn = mlp && F > 3 * D ? F : 3 * D;              // widest W^T: [D, 3D] (QKV) or [F, D] / [D, F] (c_proj / c_fc)
+    b.wt = (ov_bf16*)take((size_t)wn * D * 2);
+    b.dh = mlp ? (ov_bf16*)take((size_t)M * F * 2) : nullptr;
+    b.dx1 = mlp ? (ov_bf16*)take((size_t)M * D * 2) : nullptr;
+    b.t1 = (ov_bf16*)take((size_t)M * D * 2);
+    b.dqkv = (ov_bf16*)take((size_t)M * 3 * D * 2);
+    b.att_bytes = ov_attention_backward_workspace_bytes(B, L, c->heads, c->width / c->heads);
+    b.att = take(b.att_bytes + 256);
+    b.total = off;
+    return b;
+}
+
+inline const float* lse_if_used(const ov_tower_cfg* c, int L, const float* lse) {   // ov_tower_forward_saving's rule
+    return (c->width / c->heads == 64 && (L + 31) / 32 * 32 <= 288) ? lse : nullptr;
+}
+
+// the attention half: dx = dx1 + d(x + out_proj(attn(ln_1(x))))/dx . dx1
+int attn_backward_input(const ov_tower_cfg* cfg, const ov_block_weights* w, const ov_bf16* x, const ov_bf16* qkv, const ov_bf16* attn_out,
+                        const float* lse, const ov_bf16* dx1, ov_bf16* dx, int B, int L, const InputBufs& b, ov_stream_t stream) {
+    const int D = cfg->width, H = cfg->heads, hd = D / H;
+    const int64_t M = (int64_t)B * L;
+    const float scale = 1.0f / sqrtf((float)hd);
+    int rc;
+    if ((rc = linear_dx(dx1, D, w->out_w, D, M, D, D, b.t1, D, b.wt, stream))) return rc;                                   // t1 = d attention out
+    if ((rc = ov_attention_backward_saved(qkv, 3 * D, attn_out, D, b.t1, D, b.dqkv, 3 * D, lse_if_used(cfg, L, lse), B, L, H, hd, scale, b.att,
+                                          b.att_bytes, stream)))
+        return rc;
+    if ((rc = linear_dx(b.dqkv, 3 * D, w->qkv_w, D, M, 3 * D, D, b.t1, D, b.wt, stream))) return rc;                        // t1 = d ln_1 out
+    return layernorm_dx(x, D, w->ln1_w, b.t1, D, dx1, D, dx, D, M, D, cfg->ln_eps, stream);
+}
+}  // namespace
+
+extern "C" size_t ov_block_attn_backward_input_workspace_bytes(const ov_tower_cfg* cfg, int B, int L) {
+    if (!block_cfg_ok(cfg) || B <= 0 || L <= 0) return 0;
+    return plan_input(cfg, B, L, false, nullptr).total;
+}
+
+extern "C" int ov_block_attn_backward_input(const ov_tower_cfg* cfg, const ov_block_weights* w, const ov_bf16* x, const ov_bf16* qkv,
+                                            const ov_bf16* attn_out, const float* lse, const ov_bf16* dx1, ov_bf16* dx, int B, int L,
+                                            void* workspace, size_t workspace_bytes, ov_stream_t stream) {
+    if (!cfg || !w || !x || !qkv || !attn_out || !dx1 || !dx || !workspace || B <= 0 || L <= 0) return OV_ERR_INVALID;
+    if (!block_cfg_ok(cfg)) return OV_ERR_UNSUPPORTED;
+    if (!w->ln1_w || !w->qkv_w || !w->out_w) return OV_ERR_INVALID;
+    if (w->qkv_colsum || w->fc_colsum) return OV_ERR_UNSUPPORTED;
+    if (workspace_bytes < ov_block_attn_backward_input_workspace_bytes(cfg, B, L)) return OV_ERR_WORKSPACE;
+    if (((uintptr_t)workspace | (uintptr_t)x | (uintptr_t)qkv | (uintptr_t)attn_out | (uintptr_t)dx1 | (uintptr_t)dx | (uintptr_t)lse) & 15)
+        return OV_ERR_INVALID;
+    const InputBufs b = plan_input(cfg, B, L, false, (char*)workspace);
+    return attn_backward_input(cfg, w, x, qkv, attn_out, lse, dx1, dx, B, L, b, stream);
+}
+
+// One block's input gradient from the activations ov_tower_forward_saving kept (qkv, attention out, x1, c_fc pre-activation, lse):
+// ov_tower_backward_input (tower.hip) runs it over the layers in reverse.  Arguments are checked there.
+size_t block_backward_input_workspace_bytes(const ov_tower_cfg* cfg, int B, int L) {
+    if (!block_cfg_ok(cfg) || B <= 0 || L <= 0) return 0;
+    return plan_input(cfg, B, L, true, nullptr).total;
+}
+int block_backward_input(const ov_tower_cfg* cfg, const ov_block_weights* w, const ov_bf16* x, const ov_block_saved* s, const ov_bf16* dy,
+                         ov_bf16* dx, int B, int L, void* workspace, ov_stream_t stream) {
+    const int D = cfg->width, F = cfg->mlp_pad;
+    const int64_t M = (int64_t)B * L;
+    const InputBufs b = plan_input(cfg, B, L, true, (char*)workspace);
+    int rc;
+    // MLP branch: dh = (dy Wproj) * gelu'(a) in the product's epilogue, d ln_2 out = dh Wfc, dx1 = dy + LN_2-backward
+    if ((rc = linear_dx(dy, D, w->proj_w, F, M, D, F, b.dh, F, b.wt, stream, cfg->gelu_tanh ? OV_EPI_GELU_GRAD_TANH : OV_EPI_GELU_GRAD_ERF,
+                        s->fc_pre, F)))
+        return rc;
+    if ((rc = linear_dx(b.dh, F, w->fc_w, D, M, F, D, b.t1, D, b.wt, stream))) return rc;
+    if ((rc = layernorm_dx(s->x1, D, w->ln2_w, b.t1, D, dy, D, b.dx1, D, M, D, cfg->ln_eps, stream))) return rc;
+    return attn_backward_input(cfg, w, x, s->qkv, s->attn_out, s->attn_lse, b.dx1, dx, B, L, b, stream);
 }

@@ -617,6 +617,46 @@ extern "C" int ov_tower_backward(const ov_tower* t, const ov_bf16* saved, ov_bf1
     return OV_OK;
 }
 
+// Input gradients only (frozen weights): the same layers in reverse over the same saved activations, with the dX chain of each block
+// and no parameter-gradient work (backward.hip: block_backward_input).  dx comes out bitwise equal to ov_tower_backward's.
+size_t block_backward_input_workspace_bytes(const ov_tower_cfg* cfg, int B, int L);
+int block_backward_input(const ov_tower_cfg* cfg, const ov_block_weights* w, const ov_bf16* x, const ov_block_saved* s, const ov_bf16* dy,
+                         ov_bf16* dx, int B, int L, void* workspace, ov_stream_t stream);
+
+extern "C" size_t ov_tower_backward_input_workspace_bytes(const ov_tower* t, int B, int L) {
+    if (!t) return 0;
+    return block_backward_input_workspace_bytes(&t->cfg, B, L);
+}
+
+extern "C" int ov_tower_backward_input(const ov_tower* t, const ov_bf16* saved, ov_bf16* dx, int B, int L, void* workspace,
+                                       size_t workspace_bytes, ov_stream_t stream) {
+    if (!t || !saved || !dx || !workspace || B <= 0 || L <= 0) return OV_ERR_INVALID;
+    const ov_tower_cfg& c = t->cfg;
+    const size_t need = ov_tower_backward_input_workspace_bytes(t, B, L);
+    if (need == 0) return OV_ERR_UNSUPPORTED;                       // block_cfg_ok: width % 64, head_dim % 8 and <= 96, mlp_pad % 64
+    if (workspace_bytes < need) return OV_ERR_WORKSPACE;
+    if (((uintptr_t)saved | (uintptr_t)dx | (uintptr_t)workspace) & 15) return OV_ERR_INVALID;
+    for (int i = 0; i < c.layers; ++i)
+        if (!t->set[i] || t->blocks[i].qkv_colsum || t->blocks[i].fc_colsum) return OV_ERR_INVALID;
+    const int D = c.width;
+    const int64_t M = (int64_t)B * L;
+    for (int i = c.layers - 1; i >= 0; --i) {                     // dx holds d(block output) on entry and d(block input) on exit
+        const ov_bf16* sx = saved + (size_t)i * saved_per_layer(c, B, L);
+        ov_block_saved sv;
+        sv.qkv = sx + (size_t)M * D;
+        sv.attn_out = sv.qkv + (size_t)M * 3 * D;
+        sv.x1 = sv.attn_out + (size_t)M * D;
+        sv.ln1_out = sv.x1 + (size_t)M * D;
+        sv.ln2_out = sv.ln1_out + (size_t)M * D;
+        sv.fc_pre = sv.ln2_out + (size_t)M * D;
+        sv.fc_act = sv.fc_pre + (size_t)M * c.mlp_pad;
+        sv.attn_lse = saved_lse_used(c, L) ? (const float*)(sv.fc_act + (size_t)M * c.mlp_pad) : nullptr;
+        const int rc = block_backward_input(&c, &t->blocks[i], sx, &sv, dx, dx, B, L, workspace, stream);
+        if (rc) return rc;
+    }
+    return OV_OK;
+}
+
 extern "C" size_t ov_vision_workspace_bytes(const ov_tower* t, const ov_vision_head* h, int B) {
     if (!t || !h || B <= 0 || h->patch_size <= 0) return 0;
     return vision_ws(t, h, B).total;

@@ -1316,7 +1316,13 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_bf16_persist(const GemmArgs 
                 const u32x4_t v = *(const u32x4_t*)(smem + IMG_OFF + row * 64 + qd * 16);
                 const int64_t m = m0 + row;
                 const int grp = (n0 >> 5) + qd * 2;
-                if (m < g.M && grp * 32 < g.N) *(u32x4_t*)(g.rowpart + (m * (g.N >> 5) + grp) * 2) = v;
+                // N / 32 odd (N = 96, 160, 1120, ...): the last group has no partner -- store its 8 bytes only, or the second half
+                // lands on the next row's group 0 (past the buffer's end for the last row)
+                float* const dst = g.rowpart + (m * (g.N >> 5) + grp) * 2;
+                if (m < g.M && grp * 32 < g.N) {
+                    if ((grp + 1) * 32 < g.N) *(u32x4_t*)dst = v;
+                    else *(u32x2_t*)dst = u32x2_t{v[0], v[1]};
+                }
             }
         };
         if (!has_next) {

@@ -7,6 +7,10 @@ from openvision_amd import _lib
 from openvision_amd._lib import ptr, stream_ptr, check, OV_BF16, OV_F32
 
 
+LOG2E = 1.4426950408889634
+REL = 2.0 ** -8                  # the attention bound's relative terms (bound() below)
+
+
 def _flag(t):
     return OV_F32 if t.dtype == torch.float32 else OV_BF16
 
@@ -43,9 +47,11 @@ def gemm_keep(a, w, bias, epi, ldc=None, ldc2=None):
     return out, pre
 
 
-def attention(qkv, B, L, H, hd=64):
+def attention(qkv, B, L, H, hd=64, out=None):
+    """out (optional): a caller-owned [B*L, >= H*hd] bf16 tensor; its row pitch is passed as ld_out (qkv's as ld_qkv)."""
     lib = _lib.load()
-    out = torch.empty(B * L, H * hd, dtype=torch.bfloat16, device=qkv.device)
+    if out is None:
+        out = torch.empty(B * L, H * hd, dtype=torch.bfloat16, device=qkv.device)
     check(lib.ov_attention(ptr(qkv), qkv.stride(0), ptr(out), out.stride(0), B, L, H, hd, hd ** -0.5, stream_ptr()))
     return out
 
@@ -87,14 +93,17 @@ def rowstats_finalize(parts, eps=1e-6):
     return st
 
 
-def gemm_rowparts(a, w, bias, resid, out=None):
-    """Residual GEMM that also leaves the partial sums of its output rows (ov_gemm_rowparts)."""
+def gemm_rowparts(a, w, bias, resid, out=None, parts=None):
+    """Residual GEMM that also leaves the partial sums of its output rows (ov_gemm_rowparts).  parts (optional): a caller-owned
+    contiguous [M, N / 32, 2] fp32 tensor (e.g. a view of a larger buffer, to watch what lies behind it)."""
     lib = _lib.load()
     m, k = a.shape
     n = w.shape[0]
     if out is None:
         out = torch.zeros(m, n, dtype=torch.bfloat16, device=a.device)
-    parts = torch.full((m, n // 32, 2), float("nan"), dtype=torch.float32, device=a.device)
+    if parts is None:
+        parts = torch.full((m, n // 32, 2), float("nan"), dtype=torch.float32, device=a.device)
+    assert parts.shape == (m, n // 32, 2) and parts.is_contiguous()
     check(lib.ov_gemm_rowparts(ptr(a), a.stride(0), ptr(w), w.stride(0), ptr(bias), ptr(out), out.stride(0), m, n, k,
                                ptr(resid), resid.stride(0), ptr(parts), stream_ptr()))
     return out, parts
@@ -326,3 +335,65 @@ def gemm_tn_batched(p, q, chunk, sums=False):
     check(lib.ov_gemm_tn_batched(ptr(p), p.stride(0), ptr(q), q.stride(0), ptr(out), nj, ni * nj, mc, ni, nj, chunk, batch, ptr(ps),
                                  stream_ptr()), "ov_gemm_tn_batched")
     return (out, ps) if sums else out
+
+
+# ---- attention: an fp64 reference with a per-element bound that sees a single mis-handled key (test_gpu_attention_edges.py)
+
+
+def rnd(*shape, seed=0):
+    g = torch.Generator().manual_seed(seed)
+    return torch.randn(*shape, generator=g)
+
+
+def _split(qkv, B, L, Hh, hd):
+    """[B*L, >= 3 Hh hd] -> q, k, v as [B, Hh, L, hd] fp64."""
+    D = Hh * hd
+    x = qkv[:, :3 * D].double().view(B, L, 3, Hh, hd)
+    return [x[:, :, j].transpose(1, 2) for j in range(3)]
+
+
+def attn_ref64(qkv, B, L, Hh, hd):
+    """Softmax attention in fp64 on the (bf16) inputs: (ref, pv), both [B*L, Hh*hd] fp64; pv = P.|V|."""
+    q, k, v = _split(qkv, B, L, Hh, hd)
+    p = torch.softmax(q @ k.transpose(-1, -2) * hd ** -0.5, dim=-1)
+    back = lambda t: t.transpose(1, 2).reshape(B * L, Hh * hd)
+    return back(p @ v), back(p @ v.abs())
+
+
+def bound(ref, pv):
+    """Per-element bound: bf16 output rounding + P rounded to bf16 before P.V (each <= 2^-9 of its term; 2x headroom)."""
+    return REL * ref.abs() + REL * pv + 1e-6
+
+
+def err_ratio(got, ref, pv):
+    """max |got - ref| / bound (<= 1: inside)."""
+    return float(((got.double() - ref).abs() / bound(ref, pv)).max())
+
+
+def spiked_qkv(B, L, Hh, hd, seed, deltas=(4.0, 20.0)):
+    """Random bf16 qkv in which, for head j = b * Hh + h, the lone (last) key is K[L-1] = alpha Q[i] with alpha chosen in fp64 so that
+    row i's logit of that key exceeds its maximum over the other keys by deltas[j % 2] (log2 units): about 4 leaves the running max
+    where it is (the fold's no-rescale branch, p > 1 accumulated), about 20 forces the fold's rescale.  Returns (qkv, [(b, h, i, delta
+    realised after rounding K to bf16)])."""
+    D = Hh * hd
+    qkv = rnd(B * L, 3 * D, seed=seed).to(torch.bfloat16)
+    x = qkv.view(B, L, 3, Hh, hd)
+    c = hd ** -0.5 * LOG2E
+    spikes = []
+    for b in range(B):
+        for h in range(Hh):
+            j = b * Hh + h
+            i = (97 * j + 5) % (L - 1)
+            qi = x[b, i, 0, h].double()
+            m_other = float((x[b, :L - 1, 1, h].double() @ qi).max()) * c
+            alpha = (m_other + deltas[j % len(deltas)]) / (float(qi @ qi) * c)
+            x[b, L - 1, 1, h] = (alpha * qi).to(torch.bfloat16)
+            got = float(x[b, L - 1, 1, h].double() @ qi) * c - m_other
+            spikes.append((b, h, i, got))
+    for (_, _, _, got), want in zip(spikes, [deltas[j % len(deltas)] for j in range(B * Hh)]):
+        assert abs(got - want) < 0.5, (got, want)                   # landed in the intended band after the bf16 rounding
+    return qkv, spikes
+
+
+# the spiked shapes: hd 64 persistent (257), hd 64 streaming (321, 2305), generic chunked (321 at hd 72, 577 at hd 80)
+LONE_SPIKED = [(1, 257, 2, 64), (1, 321, 2, 64), (1, 2305, 2, 64), (1, 321, 2, 72), (1, 577, 2, 80)]

@@ -400,6 +400,25 @@ def test_head_dims_of_h14_and_so400m(width, head_width, variant):
     assert one_minus_cos(ni, ri) < COS_TOL and one_minus_cos(nt, rt) < COS_TOL
 
 
+@pytest.mark.parametrize("variant", ["v1", "sharp"])
+@pytest.mark.parametrize("width,head_width,image_size", [(320, 80, 336), (576, 72, 378)])
+def test_head_dims_of_h14_and_so400m_at_long_sequences(width, head_width, image_size, variant):
+    """As test_head_dims_of_h14_and_so400m, at the image geometry of H/14 at 336 px (L = 577) and of So400m's 27 x 27 patches
+    (378 px, L = 730): the generic head_dim attention's 256-key chunked branch inside the tower."""
+    from oracle import clip_ref as R
+    cfg = preset("vit-tiny-patch16-160")
+    cfg["vision_cfg"] = dict(cfg["vision_cfg"], width=width, head_width=head_width, layers=2, mlp_ratio=3.7362, image_size=image_size,
+                             patch_size=14)
+    cfg["text_cfg"] = dict(cfg["text_cfg"], width=width, heads=width // head_width, layers=2, mlp_ratio=3.7362)
+    sd = synth.make_state_dict(cfg, 0, variant)
+    m = create_model(cfg, device=DEV, state_dict=sd)
+    img = synth.make_images(3, image_size, seed=4) if variant == "v1" else synth.make_structured_images(3, image_size, seed=4)
+    tok = synth.make_captions(3, seed=4)
+    ni, nt, s = m(img.to(DEV), tok.to(DEV))
+    ri, rt, rs = R.clip_forward(img, tok, sd, cfg)
+    assert one_minus_cos(ni, ri) < COS_TOL and one_minus_cos(nt, rt) < COS_TOL
+
+
 def test_zero_shot_and_retrieval_evaluators(tiny):
     """SURVEY.md §8f row 3 on device: classifier weights, top-k (bit-exact indices on the SAME logits) and recall@k
     against the numpy oracle (oracle/eval_ref.py)."""

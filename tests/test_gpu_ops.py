@@ -429,9 +429,12 @@ def test_attention_keeps_the_row_lse_for_the_backward(B, L, H):
         H_.attention_lse(bf(rnd(2 * 300, 3 * 64, seed=1)).to(DEV), 2, 300, 1)          # beyond the resident backward's L
 
 
-@pytest.mark.parametrize("B,L,H,hd", [(2, 257, 4, 72), (2, 257, 3, 80), (1, 40, 2, 72), (1, 300, 2, 80), (1, 65, 2, 32)])
+@pytest.mark.parametrize("B,L,H,hd", [(2, 257, 4, 72), (2, 257, 3, 80), (1, 40, 2, 72), (1, 300, 2, 80), (1, 65, 2, 32),
+                                        # long sequences: three or four 256-row chunks, NDH = 3 (72, 80, 96) and NDH = 2 (48);
+                                        # 769 and 513 end in a chunk of one row
+                                        (1, 577, 2, 80), (1, 730, 2, 72), (1, 769, 1, 96), (2, 513, 2, 48)])
 def test_attention_backward_other_head_dims(B, L, H, hd):
-    """Head dims 72 (So400m) and 80 (H/14) go through the streaming kernels with the d axis zero-padded to 96 in LDS."""
+    """Head dims 72 (So400m) and 80 (H/14) go through the streaming kernels with the d axis zero-padded to 96 in LDS; deterministic."""
     qkv = bf(rnd(B * L, 3 * H * hd, seed=52))
     dout = bf(rnd(B * L, H * hd, seed=53))
     out = H_.attention(qkv.to(DEV), B, L, H, hd)
@@ -443,6 +446,8 @@ def test_attention_backward_other_head_dims(B, L, H, hd):
         got, want = dqkv[:, sl], ref[:, sl]
         tol = 2e-2 * float(want.abs().max()) + 1e-3
         assert float((got - want).abs().max()) < tol, (name, float((got - want).abs().max()), tol)
+    again = H_.attention_backward(qkv.to(DEV), out, dout.to(DEV), B, L, H, hd).float().cpu()
+    assert torch.equal(again, dqkv)                                       # deterministic
 
 
 def test_attention_backward_golden_reference():
@@ -765,8 +770,9 @@ def test_gemm_rowparts_are_the_row_partial_sums_of_the_output(M, N, K):
 def test_gemm_kernel_variants_agree_bitwise_with_the_default(variant):
     """OVHIP_GEMM_VARIANT (read once per process, so each variant runs in a child process): the simple two-stage kernel (1), the
     non-persistent ping-pong kernel (2), the four-wave prototype (3) and the skinny small-M kernel forced onto every shape (4: by
-    default it serves M <= 512, the batch-1 path) accumulate the same products in the same order and share the epilogue arithmetic:
-    every epilogue's output must equal the default persistent kernel's bit for bit, on ragged shapes too."""
+    default it serves grids of <= 96 of the big kernels' tiles, OVHIP_GEMM_SKINNY_TILES) accumulate the same products in the same
+    order and share the epilogue arithmetic: every epilogue's output must equal the default persistent kernel's bit for bit, on
+    ragged shapes too."""
     import subprocess, sys, tempfile
     code = r"""
 import os, sys, torch

@@ -10,8 +10,8 @@
 // is [B*L, H*64] with heads merged -- exactly the operand layout of the out-proj GEMM, so no head
 // split/merge kernels exist.
 //
-// One workgroup = one (batch, head) x NW query tiles of 32 rows (one tile per wave).  K and V of the
-// (batch, head) are staged once per key chunk into LDS and shared by all waves:
+// A wave owns a query tile of 32 rows.  K and V of the (batch, head) are staged into LDS and shared by all waves of
+// the workgroup:
 //   K image  [key][64 d]   128-B rows, 16-B chunk index ^= (key >> 1) & 7  -> conflict-free ds_read_b128
 //   V image  [d half][key][32 d] 64-B rows                                  -> conflict-free ds_read_b64_tr_b16
 // Per 32-key tile and wave (v_mfma_f32_32x32x16_bf16 throughout):
@@ -29,7 +29,6 @@ struct AttnArgs {
     ov_bf16* out; int64_t ldo;
     int B, L, H, nqt, KC;
     float scale_log2;
-    int mode;      // diagnostics only (OVHIP_ATTN_MODE): 0 = full, 1 = staging only, 2 = compute only
 };
 
 typedef __attribute__((address_space(3))) s16x4_t* lds_s16x4_ptr;
@@ -44,155 +43,8 @@ __device__ __forceinline__ bf16x8_t tr_pair(const char* p0, const char* p1) {
     return __builtin_bit_cast(bf16x8_t, c);
 }
 
-// <= 96 VGPRs: 5 waves per SIMD, so two 9-wave workgroups (L = 257) are co-resident per CU (LDS 2 x 72 KiB)
-__global__ __launch_bounds__(576, 5) void attn_fwd_hd64(const AttnArgs a) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x, nthreads = blockDim.x;
-    const int lane = tid & 63, wave = tid >> 6, nw = nthreads >> 6;
-    const int r = lane & 31, h2 = lane >> 5;
-    const int bh = blockIdx.x, b = bh / a.H, h = bh - b * a.H;
-    const int L = a.L, KC = a.KC;
-    const int HD = a.H * 64;
-    char* ks = smem;                         // K image: KC * 128 B
-    char* vs = smem + KC * 128;              // V image: 2 halves * KC * 64 B
-    const ov_bf16* base = a.qkv + (int64_t)b * L * a.ldq + h * 64;
-
-    const int qt = blockIdx.y * nw + wave;
-    const bool active = qt < a.nqt;
-    const int q0 = qt * 32;
-
-    bf16x8_t qf[4];
-    {
-        int qrow = q0 + r;
-        qrow = (active && qrow < L) ? qrow : L - 1;
-        const ov_bf16* qp = base + (int64_t)qrow * a.ldq + 8 * h2;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) qf[s] = *(const bf16x8_t*)(qp + 16 * s);
-    }
-    float m = -INFINITY, lsum = 0.f;
-    f32x16_t o0, o1;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) { o0[i] = 0.f; o1[i] = 0.f; }
-
-    // per-lane LDS offsets
-    const int k_row_off = r * 128;                                   // + tile*4096
-    const int k_sw = (r >> 1) & 7;
-    const int vi = lane & 15, vg = (lane >> 4) & 1;
-    const int v_lane_off = (4 * h2 + (vi >> 2)) * 64 + (16 * vg + 4 * (vi & 3)) * 2;
-
-    for (int kc0 = 0; kc0 < L; kc0 += KC) {
-        if (kc0) __syncthreads();
-        // ---- stage K and V rows [kc0, kc0+KC) of this (batch, head): LDS-DMA, every piece in flight at once ----
-        // LDS 16-B chunk q of the K image holds key q>>3, d-chunk (q&7) ^ ((key>>1)&7); chunk q of V half dh holds key q>>2,
-        // d-chunk dh*4 + (q&3).  The DMA writes LDS lane-linearly, so the permutation sits on the per-lane SOURCE address.
-        // Keys >= L are clamped to L-1: finite data (their scores are masked to -inf, their P is exactly 0).
-        {
-            const int nchunk = KC * 8;                                   // per image (K) and for both V halves together
-            for (int q0c = wave * 64; q0c < nchunk && a.mode != 2; q0c += nthreads) {   // wave-uniform trip count (64 | KC*8)
-                const int q = q0c + lane;
-                {
-                    const int key = q >> 3;
-                    int row = kc0 + key;
-                    row = row < L ? row : L - 1;
-                    const int c = (q & 7) ^ ((key >> 1) & 7);
-                    __builtin_amdgcn_global_load_lds((gptr_t)(base + (int64_t)row * a.ldq + HD + c * 8), (lptr_t)(ks + q0c * 16),
-                                                     16, 0, 0);
-                }
-                {
-                    const int dh = q0c >= KC * 4 ? 1 : 0;                // wave-uniform (64 | KC*4)
-                    const int qq = q - dh * KC * 4;
-                    int row = kc0 + (qq >> 2);
-                    row = row < L ? row : L - 1;
-                    __builtin_amdgcn_global_load_lds((gptr_t)(base + (int64_t)row * a.ldq + 2 * HD + (dh * 4 + (qq & 3)) * 8),
-                                                     (lptr_t)(vs + q0c * 16), 16, 0, 0);
-                }
-            }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        __syncthreads();
-        if (!active) continue;
-        const int nk = (L - kc0) < KC ? (L - kc0) : KC;
-        const int ntile = a.mode == 1 ? 0 : (nk + 31) >> 5;
-        for (int kt = 0; kt < ntile; ++kt) {
-            // ---- S^T = K . Q^T ----
-            f32x16_t s;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) s[i] = 0.f;
-            const char* kp = ks + kt * 4096 + k_row_off;
-#pragma unroll
-            for (int st = 0; st < 4; ++st) {
-                const bf16x8_t kf = *(const bf16x8_t*)(kp + (((2 * st + h2) ^ k_sw) << 4));
-                s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[st], s, 0, 0, 0);
-            }
-            // s[i] <-> key kt*32 + (i&3) + 8*(i>>2) + 4*h2, query r   (raw q.k; the softmax scale rides in the exp2 FMA)
-            if (kt * 32 + 32 > nk) {
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const int key = kt * 32 + (i & 3) + 8 * (i >> 2) + 4 * h2;
-                    if (key >= nk) s[i] = -INFINITY;
-                }
-            }
-            float mx = fmaxf(fmaxf(fmaxf(s[0], s[1]), fmaxf(s[2], s[3])), fmaxf(fmaxf(s[4], s[5]), fmaxf(s[6], s[7])));
-            mx = fmaxf(mx, fmaxf(fmaxf(fmaxf(s[8], s[9]), fmaxf(s[10], s[11])), fmaxf(fmaxf(s[12], s[13]), fmaxf(s[14], s[15]))));
-            mx = fmaxf(mx, __shfl_xor(mx, 32, 64)) * a.scale_log2;
-            // deferred rescale (bpt.py:108-124 recurrence, rescale only when the running max grows by more than 2^8):
-            // P stays <= 2^8, exact in fp32 sums and scale-free in bf16; wave-uniform branch.
-            if (!__all(mx - m <= 8.0f)) {
-                const float mn = fmaxf(m, mx);
-                const float alpha = __builtin_amdgcn_exp2f(m - mn);
-                m = mn;
-                lsum *= alpha;
-#pragma unroll
-                for (int i = 0; i < 16; ++i) { o0[i] *= alpha; o1[i] *= alpha; }
-            }
-            const float nm = -m;
-            float ps = 0.f;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                s[i] = __builtin_amdgcn_exp2f(fmaf(s[i], a.scale_log2, nm));
-                ps += s[i];
-            }
-            lsum += ps;
-            // ---- P^T as the B operand of the two k-steps ----
-            bf16x8_t pf[2];
-#pragma unroll
-            for (int st = 0; st < 2; ++st) {
-                u32x4_t w = {pack_bf16x2(s[8 * st + 0], s[8 * st + 1]), pack_bf16x2(s[8 * st + 2], s[8 * st + 3]),
-                             pack_bf16x2(s[8 * st + 4], s[8 * st + 5]), pack_bf16x2(s[8 * st + 6], s[8 * st + 7])};
-                pf[st] = __builtin_bit_cast(bf16x8_t, w);
-            }
-            // ---- O^T += V^T . P^T ----
-            const char* vp = vs + kt * 32 * 64 + v_lane_off;
-#pragma unroll
-            for (int st = 0; st < 2; ++st) {
-                const char* v0 = vp + st * 16 * 64;
-                const bf16x8_t vf0 = tr_pair(v0, v0 + 8 * 64);
-                const bf16x8_t vf1 = tr_pair(v0 + KC * 64, v0 + KC * 64 + 8 * 64);
-                o0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf0, pf[st], o0, 0, 0, 0);
-                o1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf1, pf[st], o1, 0, 0, 0);
-            }
-        }
-    }
-    if (!active) return;
-    const float l = lsum + __shfl_xor(lsum, 32, 64);
-    const float inv = 1.0f / l;
-    const int q = q0 + r;
-    if (q < L) {
-        ov_bf16* op = a.out + ((int64_t)b * L + q) * a.ldo + h * 64 + 4 * h2;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            u32x2_t w0 = {pack_bf16x2(o0[4 * g] * inv, o0[4 * g + 1] * inv),
-                          pack_bf16x2(o0[4 * g + 2] * inv, o0[4 * g + 3] * inv)};
-            u32x2_t w1 = {pack_bf16x2(o1[4 * g] * inv, o1[4 * g + 1] * inv),
-                          pack_bf16x2(o1[4 * g + 2] * inv, o1[4 * g + 3] * inv)};
-            *(u32x2_t*)(op + 8 * g) = w0;
-            *(u32x2_t*)(op + 32 + 8 * g) = w1;
-        }
-    }
-}
-
 // =====================================================================================================
-// Persistent variant (default when two heads' K/V fit in LDS, i.e. padded L <= 320): a workgroup of nqt waves (one per
+// Persistent kernel (head_dim 64 when two heads' K/V fit in LDS, i.e. padded L <= 320): a workgroup of nqt waves (one per
 // 32-row query tile) walks heads bh = blockIdx.x, blockIdx.x + gridDim.x, ...  K/V of head j live in LDS slot j & 1.
 // Per head: vmcnt(0) + ONE barrier (head j has landed for everybody, and everybody has left head j-1), then the LDS-DMA
 // of head j+1 into the other slot is issued and runs under the MFMAs/softmax of head j -- HBM reads overlap compute.
@@ -1138,6 +990,12 @@ extern "C" int ov_attention_fp8out(const ov_bf16* qkv, int64_t ld_qkv, unsigned 
 }
 
 namespace {
+// OVHIP_ATTN_LONEKEY=0: a single-key last tile / chunk takes a tile step instead of the VALU fold (the tests run both branches)
+int attn_lone_valu() {
+    static const int v = [] { const char* e = getenv("OVHIP_ATTN_LONEKEY"); return (e && e[0] == '0') ? 0 : 1; }();
+    return v;
+}
+
 int attention_impl(const ov_bf16* qkv, int64_t ld_qkv, ov_bf16* out, int64_t ld_out, int B, int L, int H, int hd, float scale,
                    const float* out_amax, float* amax_next, float* lse, ov_stream_t stream) {
     if (!qkv || !out || B <= 0 || L <= 0 || H <= 0) return OV_ERR_INVALID;
@@ -1146,46 +1004,16 @@ int attention_impl(const ov_bf16* qkv, int64_t ld_qkv, ov_bf16* out, int64_t ld_
     if (((uintptr_t)qkv | (uintptr_t)out) & 15) return OV_ERR_INVALID;
     const bool out8 = out_amax != nullptr;
     if (lse != nullptr && (hd != 64 || (L + 31) / 32 * 32 > 288 || out8)) return OV_ERR_UNSUPPORTED;   // the resident backward's shapes only
-    if (hd != 64) {                                      // So400m (72) / H (80): generic padded-head kernel
-        AttnArgs g;
-        g.qkv = qkv; g.ldq = ld_qkv; g.out = out; g.ldo = ld_out;
-        g.B = B; g.L = L; g.H = H; g.nqt = (L + 31) / 32; g.mode = 0;
-        g.scale_log2 = scale * 1.4426950408889634f;
-        const int lpad = g.nqt * 32;
-        // up to 320 (padded) keys: the whole head resident in LDS (123 KB at 320) and one wave per query tile (<= 10), so a head is
-        // staged once by one workgroup (L = 257 used to take two 256-key chunks and a second workgroup for the 257th query row: So400m's
-        // attention 8.0 ms per step); longer sequences: 256-key chunks, 8 waves
-        const bool resident = lpad <= 320;
-        g.KC = resident ? lpad : 256;
-        const int nwg = resident ? g.nqt : 8;
-        const size_t smem = (size_t)g.KC * 96 * 4;       // K (KC x 192 B) + V (3 x KC x 64 B)
-        static OvPerDeviceOnce attr3;
-        const int dev_attr3 = ov_current_device();
-        if (attr3.need(dev_attr3)) {
-            hipError_t e = hipFuncSetAttribute((const void*)attn_fwd_generic<96>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               160 * 1024);
-            if (e != hipSuccess) return OV_ERR_HIP - (int)e;
-            attr3.mark(dev_attr3);
-        }
-        hipLaunchKernelGGL(attn_fwd_generic<96>, dim3((unsigned)(B * H), (unsigned)((g.nqt + nwg - 1) / nwg)), dim3(nwg * 64), smem,
-                           (hipStream_t)stream, g, hd);
-        OV_LAUNCH_CHECK();
-        return OV_OK;
-    }
-    AttnArgs a;
-    a.qkv = qkv; a.ldq = ld_qkv; a.out = out; a.ldo = ld_out;
-    a.B = B; a.L = L; a.H = H;
-    a.nqt = (L + 31) / 32;
-    a.scale_log2 = scale * 1.4426950408889634f;
-    { static int mode = -1; if (mode < 0) { const char* e = getenv("OVHIP_ATTN_MODE"); mode = e ? atoi(e) : 0; } a.mode = mode; }
-    const int lp = a.nqt * 32;
-    static int force_v1 = -1;
-    if (force_v1 < 0) { const char* e = getenv("OVHIP_ATTN_V1"); force_v1 = (e && e[0] == '1') ? 1 : 0; }
-    if (lp <= 320 && (!force_v1 || lse) && (int64_t)L * ld_qkv * 2 < 0x7fffffffLL && (int64_t)L * ld_out * 2 < 0x7fffffffLL) {   // (lse: only this kernel keeps it)
+    const int nqt = (L + 31) / 32, lp = nqt * 32;
+    const float scale_log2 = scale * 1.4426950408889634f;
+    // the persistent kernel's row offsets are 32-bit: an image spanning 2 GiB of rows or more (a caller's huge row pitch) goes to the
+    // generic kernel below
+    const bool narrow = (int64_t)L * ld_qkv * 2 < 0x7fffffffLL && (int64_t)L * ld_out * 2 < 0x7fffffffLL;
+    if (hd == 64 && lp <= 320 && narrow) {
         AttnPArgs p;
         p.qkv = qkv; p.ldq = ld_qkv; p.out = out; p.ldo = ld_out;
-        p.L = L; p.H = H; p.nqt = a.nqt; p.KC = lp; p.nheads = B * H; p.scale_log2 = a.scale_log2; p.out_amax = out_amax; p.amax_next = amax_next; p.lse = lse;
-        { static int lk = -1; if (lk < 0) { const char* e = getenv("OVHIP_ATTN_LONEKEY"); lk = (e && e[0] == '0') ? 0 : 1; } p.lone_valu = lk; }
+        p.L = L; p.H = H; p.nqt = nqt; p.KC = lp; p.nheads = B * H; p.scale_log2 = scale_log2; p.out_amax = out_amax; p.amax_next = amax_next; p.lse = lse;
+        p.lone_valu = attn_lone_valu();
         static OvPerDeviceOnce attr2;
         const int dev_attr2 = ov_current_device();
         if (attr2.need(dev_attr2)) {
@@ -1207,13 +1035,13 @@ int attention_impl(const ov_bf16* qkv, int64_t ld_qkv, ov_bf16* out, int64_t ld_
         const int ncu = ov_num_cus();
         const size_t smem = (size_t)2 * lp * 256;
         int per_cu = (int)((160 * 1024) / smem);                  // workgroups per CU by LDS ...
-        const int by_waves = (a.nqt <= 8 ? 8 : 12) / a.nqt;       // ... and by waves (2 per SIMD for the DEEP variant, else 3)
+        const int by_waves = (nqt <= 8 ? 8 : 12) / nqt;           // ... and by waves (2 per SIMD for the DEEP variant, else 3)
         if (per_cu > by_waves) per_cu = by_waves;
         if (per_cu < 1) per_cu = 1;
         const int cap = ncu * per_cu;
         const int grid = p.nheads < cap ? p.nheads : cap;
-        const dim3 pg((unsigned)grid), pb(a.nqt * 64);
-        if (a.nqt <= 8) {
+        const dim3 pg((unsigned)grid), pb(nqt * 64);
+        if (nqt <= 8) {
             if (out8) hipLaunchKernelGGL((attn_fwd_hd64_persist<true, true>), pg, pb, smem, (hipStream_t)stream, p);
             else if (lse) hipLaunchKernelGGL((attn_fwd_hd64_persist<true, false, true>), pg, pb, smem, (hipStream_t)stream, p);
             else hipLaunchKernelGGL((attn_fwd_hd64_persist<true, false>), pg, pb, smem, (hipStream_t)stream, p);
@@ -1225,15 +1053,14 @@ int attention_impl(const ov_bf16* qkv, int64_t ld_qkv, ov_bf16* out, int64_t ld_
         OV_LAUNCH_CHECK();
         return OV_OK;
     }
-    if (lse != nullptr) return OV_ERR_UNSUPPORTED;       // (OVHIP_ATTN_V1 / row pitches beyond 2 GiB: no kept lse)
-    if (lp > 320 && !force_v1) {
+    if (hd == 64 && lp > 320) {
         AttnSArgs sa;
         sa.qkv = qkv; sa.ldq = ld_qkv; sa.out = out; sa.ldo = ld_out;
-        sa.L = L; sa.H = H; sa.nqt = a.nqt; sa.nqb = (a.nqt + 7) / 8; sa.nheads = B * H; sa.nchunks = (L + 63) / 64;
-        sa.scale_log2 = a.scale_log2;
+        sa.L = L; sa.H = H; sa.nqt = nqt; sa.nqb = (nqt + 7) / 8; sa.nheads = B * H; sa.nchunks = (L + 63) / 64;
+        sa.scale_log2 = scale_log2;
         sa.out_amax = out_amax;
         sa.amax_next = amax_next;
-        { static int lk = -1; if (lk < 0) { const char* e = getenv("OVHIP_ATTN_LONEKEY"); lk = (e && e[0] == '0') ? 0 : 1; } sa.lone_valu = lk; }
+        sa.lone_valu = attn_lone_valu();
         static OvPerDeviceOnce attr4;
         const int dev_attr4 = ov_current_device();
         if (attr4.need(dev_attr4)) {
@@ -1251,22 +1078,29 @@ int attention_impl(const ov_bf16* qkv, int64_t ld_qkv, ov_bf16* out, int64_t ld_
         OV_LAUNCH_CHECK();
         return OV_OK;
     }
-    if (out8) return OV_ERR_UNSUPPORTED;                // the fallback kernel has no e4m3 epilogue
-    int nw;
-    if (lp <= 320) { a.KC = lp; nw = a.nqt; }          // whole K/V of a head resident: one chunk
-    else { a.KC = 256; nw = 8; }
-    const int gy = (a.nqt + nw - 1) / nw;
-    const size_t smem = (size_t)a.KC * 256;
-    static OvPerDeviceOnce attr_set;
-        const int dev_attr_set = ov_current_device();
-    if (attr_set.need(dev_attr_set)) {
-        hipError_t e = hipFuncSetAttribute((const void*)attn_fwd_hd64, hipFuncAttributeMaxDynamicSharedMemorySize,
+    // Generic padded-head kernel: head_dim 72 (So400m) / 80 (H/14), and head_dim 64 images beyond the persistent kernel's 2 GiB.
+    if (lse != nullptr || out8) return OV_ERR_UNSUPPORTED;   // (no kept lse, no e4m3 epilogue in this kernel)
+    AttnArgs g;
+    g.qkv = qkv; g.ldq = ld_qkv; g.out = out; g.ldo = ld_out;
+    g.B = B; g.L = L; g.H = H; g.nqt = nqt;
+    g.scale_log2 = scale_log2;
+    // up to 320 (padded) keys: the whole head resident in LDS (123 KB at 320) and one wave per query tile (<= 10), so a head is
+    // staged once by one workgroup (L = 257 used to take two 256-key chunks and a second workgroup for the 257th query row: So400m's
+    // attention 8.0 ms per step); longer sequences: 256-key chunks, 8 waves
+    const bool resident = lp <= 320;
+    g.KC = resident ? lp : 256;
+    const int nwg = resident ? g.nqt : 8;
+    const size_t smem = (size_t)g.KC * 96 * 4;       // K (KC x 192 B) + V (3 x KC x 64 B)
+    static OvPerDeviceOnce attr3;
+    const int dev_attr3 = ov_current_device();
+    if (attr3.need(dev_attr3)) {
+        hipError_t e = hipFuncSetAttribute((const void*)attn_fwd_generic<96>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                            160 * 1024);
         if (e != hipSuccess) return OV_ERR_HIP - (int)e;
-        attr_set.mark(dev_attr_set);
+        attr3.mark(dev_attr3);
     }
-    hipLaunchKernelGGL(attn_fwd_hd64, dim3((unsigned)(B * H), (unsigned)gy), dim3(nw * 64), smem,
-                       (hipStream_t)stream, a);
+    hipLaunchKernelGGL(attn_fwd_generic<96>, dim3((unsigned)(B * H), (unsigned)((g.nqt + nwg - 1) / nwg)), dim3(nwg * 64), smem,
+                       (hipStream_t)stream, g, hd);
     OV_LAUNCH_CHECK();
     return OV_OK;
 }

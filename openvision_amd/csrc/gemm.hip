@@ -12,9 +12,10 @@
 //   * each wave owns a 128(m) x 64(n) sub-tile = 8 x 4 v_mfma_f32_16x16x32_bf16 accumulators;
 //     W is fed as the MFMA A operand so a lane ends up holding 4 consecutive n for one m;
 //   * epilogue: bias / LN fold / GELU in fp32 on the accumulators, bf16 pack, then either a transposition through a (swizzled)
-//     wave-local LDS image and row-contiguous 16-byte stores (bias epilogue of the persistent kernel, every epilogue of the
-//     non-persistent kernels) or a v_permlane16_swap exchange and row-per-lane 16-byte stores (GELU and residual epilogues of the
-//     persistent kernel); the residual is added on the way out.  All forms perform the same arithmetic in the same order;
+//     wave-local LDS image and row-contiguous 16-byte stores (every epilogue of the non-persistent kernels; in the persistent
+//     kernel the bias epilogue, the LN-folded GELU epilogue with a streamed output, and the residual and GELU-gradient epilogues
+//     without row maps or row statistics) or a v_permlane16_swap exchange and row-per-lane 16-byte stores (the persistent
+//     kernel's other epilogues); the residual is added on the way out.  All forms perform the same arithmetic in the same order;
 //   * workgroup id -> tile map is XCD-aware: each XCD's L2 sees a contiguous run of tiles that walk n
 //     fastest, so the 32 tiles resident on an XCD share A row-panels and the whole of W.
 #include "common.h"
@@ -28,28 +29,26 @@ constexpr int TILE_BYTES = BM * BK * 2;        // one operand tile: 32 KiB
 constexpr int STAGE_BYTES = 2 * TILE_BYTES;    // A + W
 constexpr int SMEM_BYTES = 2 * STAGE_BYTES;    // double buffered: 128 KiB
 
+// Kernel argument block.  Every field has a default; the host entry points assign the fields they use by name.
 struct GemmArgs {
-    const ov_bf16* A; const ov_bf16* W; const float* bias; ov_bf16* C; const ov_bf16* R;
-    int64_t lda, ldw, ldc, ldr, M;
-    int N, K, tiles_m, tiles_n, out_group, resid_mod, resid_off;
-    const float* colsum;            // LN fold: column sums of W' (NULL = plain GEMM)
-    const float* rowstats;          // LN fold: {mean, rstd} per row of A
-    unsigned long long* stamps;     // diagnostics only (ov_debug_gemm_stamps): [block][tile slot][4] s_memtime values
-    int stamp_slots;
-    unsigned long long* wstamps;    // diagnostics only: per-wave epilogue timeline [block][tile slot][wave][8]
-    int ngroup;                     // persistent kernel: n-tiles per group of the XCD tile walk (== tiles_n: plain n-fastest walk)
-    int64_t batch_a, batch_w, batch_c;   // gemm_bf16_pp with gridDim.y > 1: element strides of A, W, C per batch entry (split-K partials)
-    int stagger, stagger_classes;        // persistent kernel: start delay (shader cycles) per class (bid >> 3) % classes (0 = off)
-    int epi_prio;                        // persistent kernel: n > 0: waves 4-7 (the arbitration losers) run epilogue passes < n at s_setprio 1
-    ov_bf16* C2; int64_t ldc2;           // ov_gemm_keep: second output = the GELU epilogue's pre-activation (acc + bias), bf16
-    float* psum;                         // gemm_bf16_pp_tn: [gridDim.y][M] column sums of P over the split's rows (NULL = off)
-    int st_plain;                        // persistent kernel, bias / GELU epilogues: plain instead of streaming output stores (small outputs)
-    int half_ok;                         // persistent kernel: half tiles allowed (OVHIP_GEMM_HALF=0 switches them off)
-    int rev;                             // persistent kernel: walk the row tiles from the last to the first (launcher: c_proj)
-    int rotmask;                         // persistent kernel, plain walk, half last n-tile (see HALF TILES): tiles_n - 1 when the workgroup
+    const ov_bf16* A = nullptr; const ov_bf16* W = nullptr; const float* bias = nullptr; ov_bf16* C = nullptr; const ov_bf16* R = nullptr;
+    int64_t lda = 0, ldw = 0, ldc = 0, ldr = 0, M = 0;
+    int N = 0, K = 0, tiles_m = 0, tiles_n = 0, out_group = 0, resid_mod = 0, resid_off = 0;
+    const float* colsum = nullptr;       // LN fold: column sums of W' (NULL = plain GEMM)
+    const float* rowstats = nullptr;     // LN fold: {mean, rstd} per row of A
+    unsigned long long* stamps = nullptr;     // diagnostics only (ov_debug_gemm_stamps): [block][tile slot][4] s_memtime values
+    int stamp_slots = 0;
+    unsigned long long* wstamps = nullptr;    // diagnostics only: per-wave epilogue timeline [block][tile slot][wave][8]
+    int ngroup = 0;                      // persistent kernel: n-tiles per group of the XCD tile walk (== tiles_n: plain n-fastest walk)
+    int64_t batch_a = 0, batch_w = 0, batch_c = 0;   // gemm_bf16_pp with gridDim.y > 1: element strides of A, W, C per batch entry (split-K partials)
+    ov_bf16* C2 = nullptr; int64_t ldc2 = 0;   // ov_gemm_keep: second output = the GELU epilogue's pre-activation (acc + bias), bf16
+    float* psum = nullptr;               // gemm_bf16_pp_tn: [gridDim.y][M] column sums of P over the split's rows (NULL = off)
+    int st_plain = 0;                    // persistent kernel, bias / GELU epilogues: plain instead of streaming output stores (small outputs)
+    int rev = 0;                         // persistent kernel: walk the row tiles from the last to the first (launcher: c_proj)
+    int rotmask = 0;                     // persistent kernel, plain walk, half last n-tile (see HALF TILES): tiles_n - 1 when the workgroup
                                          // stride is a multiple of tiles_n -- the n index is then rotated by the workgroup's tile count, so
                                          // that every workgroup alternates between full and half tiles (0 = off)
-    float* rowpart;                      // residual epilogue (persistent direct form, skinny kernel): {sum, sum of squares} of every
+    float* rowpart = nullptr;            // residual epilogue (persistent direct form, skinny kernel): {sum, sum of squares} of every
                                          // 32-column group of every OUTPUT row, [M][N / 32][2] fp32 (common.h: row statistics); NULL = off
 };
 
@@ -142,207 +141,9 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, f32x4_t (&acc)[
     }
 }
 
-template <int EPI>
-__global__ __launch_bounds__(NTHREADS, 2) void gemm_bf16_256x256(const GemmArgs g) {
-    __shared__ __attribute__((aligned(16))) char smem[SMEM_BYTES];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-
-    // ---- XCD-aware, bijective workgroup -> tile map (blocks are dealt round-robin over 8 XCDs) ----
-    const int nwg = g.tiles_m * g.tiles_n;
-    const int bid = blockIdx.x;
-    const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    const int wgid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
-    const int tm = wgid / g.tiles_n, tn = wgid - tm * g.tiles_n;
-    const int64_t m0 = (int64_t)tm * BM;
-    const int n0 = tn * BN;
-
-    // ---- per-thread staging sources: 4 x 16 B of A and of W per K-tile ------------------------------
-    // LDS chunk q = j*512 + tid holds tile row q>>3, logical 16-B chunk (q&7) ^ (row&7).
-    const int srow = tid >> 3;
-    const int schunk = (tid & 7) ^ (srow & 7);
-    const ov_bf16* asrc[4];
-    const ov_bf16* wsrc[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        int64_t ar = m0 + j * 64 + srow;
-        ar = ar < g.M ? ar : g.M - 1;                 // clamp: tail rows load a valid row, never stored
-        int wr = n0 + j * 64 + srow;
-        wr = wr < g.N ? wr : g.N - 1;
-        asrc[j] = g.A + ar * g.lda + schunk * 8;
-        wsrc[j] = g.W + (int64_t)wr * g.ldw + schunk * 8;
-    }
-    auto stage = [&](int buf, int k0) {
-        char* sa = smem + buf * STAGE_BYTES + wave * 1024;
-        char* sw = sa + TILE_BYTES;
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            __builtin_amdgcn_global_load_lds((gptr_t)(asrc[j] + k0), (lptr_t)(sa + j * 8192), 16, 0, 0);
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            __builtin_amdgcn_global_load_lds((gptr_t)(wsrc[j] + k0), (lptr_t)(sw + j * 8192), 16, 0, 0);
-    };
-
-    // ---- fragment addressing ------------------------------------------------------------------------
-    const int wm = wave >> 2, wn = wave & 3;
-    const int fr = lane & 15, fq = lane >> 4;
-    const int a_off = (wm * 128 + fr) * 128;
-    const int w_off = TILE_BYTES + (wn * 64 + fr) * 128;
-    const int sw0 = ((fq) ^ (fr & 7)) << 4;
-    const int sw1 = ((4 + fq) ^ (fr & 7)) << 4;
-
-    f32x4_t acc[8][4];
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-
-    const int nt = g.K / BK;
-    stage(0, 0);
-    for (int t = 0; t < nt; ++t) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's pieces of tile t have landed
-        __syncthreads();                                    // everyone's have; buffer (t+1)&1 is free
-        if (t + 1 < nt) stage((t + 1) & 1, (t + 1) * BK);
-        const char* s = smem + (t & 1) * STAGE_BYTES;
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-            const int sw = kk ? sw1 : sw0;
-            bf16x8_t af[8], wf[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) wf[j] = *(const bf16x8_t*)(s + w_off + j * 2048 + sw);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) af[i] = *(const bf16x8_t*)(s + a_off + i * 2048 + sw);
-#pragma unroll
-            for (int i = 0; i < 8; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j], af[i], acc[i][j], 0, 0, 0);
-        }
-    }
-
-    gemm_epilogue<EPI>(g, acc, smem, m0, n0, wave, lane);
-}
-
 // =====================================================================================================
-// Experimental (OVHIP_GEMM_VARIANT=3): FOUR waves per workgroup, one per SIMD, each owning a 128 x 128 quarter of the 256 x 256 tile
-// (8 x 8 accumulator fragments = 256 registers; launch bound 1 wave per SIMD = 512 registers).  Per K-tile a wave reads 32
-// fragments for 128 MFMAs where the ping-pong kernels read 24 for 64: a third less LDS traffic per flop, no partner wave whose
-// load segment interferes with the MFMA stream, ONE barrier per K-tile.  The wave software-pipelines its own operands: while the
-// 64 MFMAs of k-half 0 run it issues the 16 LDS-DMAs of the next K-tile (whole 128-byte lines, 8 rows per instruction: v1's LDS
-// image) and the 16 fragment reads of k-half 1; half-way through k-half 1 it waits for its DMAs, meets the other waves at the
-// barrier and reads the next K-tile's k-half 0 fragments under the remaining MFMAs.  Non-persistent prototype with the shared
-// epilogue (each wave plays two of the epilogue's "waves"); measures what the main loop is worth before anything is built on it.
-template <int EPI>
-__global__ __launch_bounds__(256, 1) void gemm_bf16_w4(const GemmArgs g) {
-    __shared__ __attribute__((aligned(16))) char smem[SMEM_BYTES];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int nwg = g.tiles_m * g.tiles_n;
-    const int bid = blockIdx.x;
-    const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    const int wgid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
-    const int tm = wgid / g.tiles_n, tn = wgid - tm * g.tiles_n;
-    const int64_t m0 = (int64_t)tm * BM;
-    const int n0 = tn * BN;
-
-    // staging: instruction j (0..7) of this wave fills rows (4 j + wave) * 8 + (lane >> 3), stored chunk lane & 7 = logical chunk
-    // (lane & 7) ^ (row & 7) (v1's image: 128-byte rows, conflict-free for the 16x16x32 operand reads)
-    const ov_bf16* asrc[8];
-    const ov_bf16* wsrc[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int row = (4 * j + wave) * 8 + (lane >> 3);
-        const int ch = (lane & 7) ^ (row & 7);
-        int64_t ar = m0 + row;
-        ar = ar < g.M ? ar : g.M - 1;
-        int wr = n0 + row;
-        wr = wr < g.N ? wr : g.N - 1;
-        asrc[j] = g.A + ar * g.lda + ch * 8;
-        wsrc[j] = g.W + (int64_t)wr * g.ldw + ch * 8;
-    }
-    char* const sdst = smem + wave * 1024;
-    auto dma = [&](int buf, int q, int k0) {      // q 0..7: A rows block q; 8..15: W
-        char* d = sdst + buf * STAGE_BYTES + (q >> 3) * TILE_BYTES + (q & 7) * 4096;
-        const ov_bf16* src = (q < 8 ? asrc[q & 7] : wsrc[q & 7]) + k0;
-        __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)d, 16, 0, 0);
-    };
-    const int wm = wave >> 1, wn = wave & 1;
-    const int fr = lane & 15, fq = lane >> 4;
-    const int a_off = (wm * 128 + fr) * 128;
-    const int w_off = TILE_BYTES + (wn * 128 + fr) * 128;
-    const int sw0 = (fq ^ (fr & 7)) << 4, sw1 = ((4 + fq) ^ (fr & 7)) << 4;
-    auto frag = [&](const char* st, int f, int kh) {      // f 0..7: A fragment i = f; 8..15: W fragment j = f - 8
-        return *(const bf16x8_t*)(st + (f < 8 ? a_off : w_off) + (f & 7) * 2048 + (kh ? sw1 : sw0));
-    };
-
-    f32x4_t acc0[8][4], acc1[8][4];               // columns j 0-3 / 4-7 of the wave's 8 x 8 fragment grid
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { acc0[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f}; acc1[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f}; }
-
-    const int nt = g.K / BK;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) dma(0, q, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    bf16x8_t cur[16], nxt[16];
-#pragma unroll
-    for (int f = 0; f < 16; ++f) cur[f] = frag(smem, f, 0);
-
-    // accumulators pinned to AGPRs ("+a"): left to itself hipcc keeps them in VGPRs and parks the FRAGMENTS in AGPRs, which MFMA
-    // operands cannot come from -- 170 v_accvgpr moves and their s_nops per K-tile
-    auto mma = [&](f32x4_t& c, const bf16x8_t& wfrag, const bf16x8_t& afrag) {
-        asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(c) : "v"(wfrag), "v"(afrag));
-    };
-    auto ktile = [&](int t, auto morec) {
-        constexpr bool MORE = decltype(morec)::value;
-        const char* st = smem + (t & 1) * STAGE_BYTES;
-        // ---- k-half 0: 64 MFMAs; under them the next K-tile's 16 DMAs and this K-tile's k-half 1 fragments
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            nxt[q] = frag(st, q, 1);
-            if (MORE && q < 8) { dma((t + 1) & 1, 2 * q, (t + 1) * BK); dma((t + 1) & 1, 2 * q + 1, (t + 1) * BK); }   // all out in the first half
-            const int i = q >> 1;
-#pragma unroll
-            for (int jj = 0; jj < 4; ++jj) {
-                if (q & 1) mma(acc1[i][jj], cur[12 + jj], cur[i]);
-                else mma(acc0[i][jj], cur[8 + jj], cur[i]);
-            }
-        }
-        // ---- k-half 1: 64 MFMAs; half-way the DMAs have landed for everybody, then the next K-tile's k-half 0 fragments
-        const char* sn = smem + ((t + 1) & 1) * STAGE_BYTES;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            if (MORE && q == 10) {                                 // as late as the fragment reads below allow: the DMAs get >= 1.1 k cycles
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __builtin_amdgcn_s_barrier();
-            }
-            if (MORE && q >= 10) {                                 // 16 reads over six groups: 3 3 3 3 2 2
-                const int f0 = q < 14 ? 3 * (q - 10) : 12 + 2 * (q - 14), nf = q < 14 ? 3 : 2;
-#pragma unroll
-                for (int f = 0; f < 3; ++f)
-                    if (f < nf) cur[f0 + f] = frag(sn, f0 + f, 0);
-            }
-            const int i = q >> 1;
-#pragma unroll
-            for (int jj = 0; jj < 4; ++jj) {
-                if (q & 1) mma(acc1[i][jj], nxt[12 + jj], nxt[i]);
-                else mma(acc0[i][jj], nxt[8 + jj], nxt[i]);
-            }
-        }
-    };
-    for (int t = 0; t + 1 < nt; ++t) ktile(t, IntC<1>{});
-    ktile(nt - 1, IntC<0>{});
-    // each wave plays the epilogue's waves (wm, 2 wn) and (wm, 2 wn + 1): same images, same arithmetic
-    gemm_epilogue<EPI>(g, acc0, smem, m0, n0, wm * 4 + wn * 2, lane);
-    gemm_epilogue<EPI>(g, acc1, smem, m0, n0, wm * 4 + wn * 2 + 1, lane);
-}
-
-// =====================================================================================================
-// Ping-pong kernel (default).  Same tile and epilogue as above, different main loop:
+// Ping-pong kernel: the non-persistent launch (grids smaller than the chip, the batched launch, the tower's tail images).  One
+// workgroup = 8 waves = one 256 x 256 output tile, finished by the shared epilogue above.  Main loop:
 //   * each K-tile (BK = 64) is staged as FOUR 16-KiB pieces -- (A,k 0-31) (W,k 0-31) (A,k 32-63) (W,k 32-63) --
 //     one piece per phase, one K-tile ahead, with a COUNTED s_waitcnt vmcnt(4) at phases 1 and 3 (never 0 in the
 //     loop) and raw s_barrier, so two pieces stay in flight across every barrier;
@@ -375,6 +176,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_bf16_pp(const GemmArgs g_in)
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
+    // ---- XCD-aware, bijective workgroup -> tile map (blocks are dealt round-robin over 8 XCDs) ----
     const int nwg = g.tiles_m * g.tiles_n;
     const int bid = blockIdx.x;
     const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7, idx = bid >> 3;
@@ -640,7 +442,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_bf16_pp_tn(const GemmArgs g_
 }
 
 // =====================================================================================================
-// Persistent ping-pong kernel (default).  One workgroup per CU walks a static, XCD-contiguous list of output tiles.
+// Persistent ping-pong kernel (grids of at least one tile per CU).  One workgroup per CU walks a static, XCD-contiguous list of
+// output tiles.
 // On top of the ping-pong main loop above:
 //   * the LAST K-tile of a tile stages K-tile 0 of the NEXT tile into the free LDS buffer, and the epilogue opens by
 //     staging K-tile 1 of the next tile into the buffer that has just been consumed -- so every LDS-DMA the next main
@@ -669,6 +472,11 @@ constexpr int SMEM_PERSIST = IMG_OFF + 8 * 2048;     // 152 KiB of the CU's 160 
 // `g.out_group ? m + m / g.out_group + 1 : m` and computes the software division on every store), and row pointers are one
 // 64-bit multiply per lane, stepped by whole rows, instead of one per store -- ~250 of the ~500 (bias) to ~1200 (residual) VALU
 // instructions of the epilogue were such address arithmetic.
+// Waves 4-7 (younger, they lose every VALU / LDS arbitration against waves 0-3 and finish the epilogue 1.4 k cycles later, while
+// waves 0-3 wait at the tile barrier) run the first EPI_PRIO passes of the epilogue at priority 1: both groups then finish together.
+// Measured in the model: QKV 9.59 -> 9.41 ms, c_fc 12.55 -> 12.24 ms per step (-2 %); all eight passes at priority 1 just swaps the
+// roles (no gain).
+constexpr int EPI_PRIO = 4;
 template <int N> __device__ __forceinline__ void wait_vmcnt() {          // literal counts only (the hand-counted waits of the epilogues)
     static_assert(N == 8 || N == 14 || N == 22 || N == 24 || N == 26 || N == 28, "add the literal");
     if (N == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
@@ -798,7 +606,7 @@ __device__ __forceinline__ void epilogue_stream(const GemmArgs& g, f32x4_t (&acc
     } while (0)
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
-        if (wm == 1 && g.epi_prio > 0 && i == g.epi_prio) __builtin_amdgcn_s_setprio(0);
+        if (wm == 1 && i == EPI_PRIO) __builtin_amdgcn_s_setprio(0);
         if (EPI >= OV_EPI_BIAS_RESIDUAL && i == 4) {
 #pragma unroll
             for (int k = 4; k < 8; ++k) load_resid(k);
@@ -951,7 +759,7 @@ __device__ __forceinline__ void epilogue_stream_lds(const GemmArgs& g, f32x4_t (
     };
 #pragma unroll
     for (int i = 0; i <= 8; ++i) {
-        if (wm == 1 && g.epi_prio > 0 && i == g.epi_prio) __builtin_amdgcn_s_setprio(0);
+        if (wm == 1 && i == EPI_PRIO) __builtin_amdgcn_s_setprio(0);
         if (EPI >= OV_EPI_BIAS_RESIDUAL && i == 4) {
 #pragma unroll
             for (int k = 4; k < 8; ++k) load_resid(k);
@@ -1037,16 +845,6 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_bf16_persist(const GemmArgs 
     const int nper = (G - xcd + 7) >> 3;
     int tcur = li;
     if (tcur >= xcnt) return;
-    if (g.stagger > 0) {
-        // De-synchronise the CUs of an XCD: in lockstep every CU reaches its epilogue at the same moment and the 4 MB an XCD then
-        // writes at once queue on its fabric link; classes start a fraction of a tile period apart so the bursts interleave.
-        const int cls = li % g.stagger_classes;
-        if (cls) {
-            const unsigned long long t0 = __builtin_amdgcn_s_memtime();
-            const unsigned long long want = (unsigned long long)cls * (unsigned)g.stagger;
-            while (__builtin_amdgcn_s_memtime() - t0 < want) __builtin_amdgcn_s_sleep(16);
-        }
-    }
 
     TileSrc cur, nxt;
     int64_t m0, nm0 = 0;
@@ -1152,7 +950,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_bf16_persist(const GemmArgs 
     bool htile;
     int a_lane, w_lane;
     auto set_lanes = [&](int nn) {
-        htile = g.half_ok && g.N - nn <= 128;
+        htile = g.N - nn <= 128;
         const int lf = fresh_lane();
         const int fr = lf & 15, fq = lf >> 4;
         const int lsw = (fq ^ swz4(fr)) << 4;
@@ -1289,7 +1087,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_bf16_persist(const GemmArgs 
         __builtin_amdgcn_sched_barrier(0);
         const bool edge = (m0 + BM > g.M) || (n0 + BN > g.N);      // an edge tile issues fewer than 16 stores per wave
         if (wst != nullptr && lane == 0) wst[1] = __builtin_amdgcn_s_memtime();
-        if (g.epi_prio && wm == 1) __builtin_amdgcn_s_setprio(1);
+        if (wm == 1) __builtin_amdgcn_s_setprio(1);               // until pass EPI_PRIO
         // Store policy by the size of the output (launcher): streaming (nt) stores keep a wide activation (qkv, hidden: 0.4-0.9 GB at
         // the benchmark shapes) from displacing the operands in L2; an output that fits the 256 MB Infinity Cache is stored plainly so
         // that its consumer finds it there (Ti/16: 6.68 -> 6.42 ms per step).  The residual forms always store plainly (x is re-read
@@ -1302,7 +1100,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_bf16_persist(const GemmArgs 
             if (DUAL && g.st_plain) epilogue_stream_lds<EPI, FOLD, MAPPED, 0>(g, acc, smem + IMG_OFF + wave * 2048, smem + PRM_OFF + pslot * 4096, m0, n0, wave, lane, edge, wst, htile);
             else epilogue_stream_lds<EPI, FOLD, MAPPED, OVHIP_ST_LDS>(g, acc, smem + IMG_OFF + wave * 2048, smem + PRM_OFF + pslot * 4096, m0, n0, wave, lane, edge, wst, htile);
         }
-        if (g.epi_prio && wm == 1) __builtin_amdgcn_s_setprio(0);
+        if (wm == 1) __builtin_amdgcn_s_setprio(0);
         stamp(3);
         ++titer;
         auto flush_stats = [&]() {
@@ -1354,7 +1152,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_bf16_persist(const GemmArgs 
 // the A operand, k 0-31 then 32-63 of each K-tile), as in the 256 x 256 kernels, and the epilogue applies the same functions -- a
 // row's result is bitwise the same whichever kernel computed it (batch 1 against batch 9: test_batch_invariance...).
 // LDS image of a stage: [A 64 rows x 128 B][W 64 rows x 128 B], 16-byte chunk c of row r stored at chunk c ^ (r & 7) (on the DMA source
-// side and on the read side), conflict-free for the 16x16x32 operand reads (the v1 kernel's image).
+// side and on the read side), conflict-free for the 16x16x32 operand reads.
 constexpr int SK_BM = 64, SK_BN = 64, SK_STAGES = 4;
 constexpr int SK_STAGE_BYTES = (SK_BM + SK_BN) * 128;            // 16 KiB
 
@@ -1495,14 +1293,10 @@ __global__ __launch_bounds__(256) void gemm_bf16_skinny(const GemmArgs g) {
     }
 }
 
-// The skinny kernel takes over while the shape gives the 256 x 256 kernels at most this many tiles (OVHIP_GEMM_SKINNY_TILES; 0 =
-// never).  Measured crossover on the four L/14 block shapes (tools/dbg/skinny_cross.py): QKV / c_fc win with the skinny kernel up to
-// 60 / 80 big tiles (M = 1028) and lose at 108 / 144 (M = 2056), out_proj / c_proj win at 68 (M = 4112) and lose at 132 (M = 8224).
-int gemm_skinny_tiles() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("OVHIP_GEMM_SKINNY_TILES"); v = e ? atoi(e) : 96; }
-    return v;
-}
+// The skinny kernel takes over while the shape gives the 256 x 256 kernels at most this many tiles.  Measured crossover on the four
+// L/14 block shapes (profiles/r03_skinny_cross.log): QKV / c_fc win with the skinny kernel up to 60 / 80 big tiles (M = 1028) and lose
+// at 108 / 144 (M = 2056), out_proj / c_proj win at 68 (M = 4112) and lose at 132 (M = 8224).
+constexpr int SKINNY_TILES = 96;
 
 int num_cus() { return ov_num_cus(); }
 
@@ -1515,85 +1309,49 @@ unsigned long long* g_stamps = nullptr;
 unsigned long long* g_wstamps = nullptr;
 int g_stamp_slots = 0;
 
-int gemm_variant() {       // 0 = default (persistent ping-pong; skinny kernel for small M), 1 = v1 two-stage, 2 = non-persistent ping-pong,
-    static int v = -1;     // 3 = four-wave prototype, 4 = skinny kernel for EVERY shape (tests: bitwise against the default)
+int gemm_variant() {       // 0 = default (persistent ping-pong; skinny kernel for small M), 2 = non-persistent ping-pong for every shape,
+    static int v = -1;     // 4 = skinny kernel for EVERY shape (tests: bitwise against the default); any other value = 0
     if (v < 0) {
         const char* e = getenv("OVHIP_GEMM_VARIANT");
-        v = (e && e[0] >= '0' && e[0] <= '4') ? e[0] - '0' : 0;
+        v = (e && (e[0] == '2' || e[0] == '4')) ? e[0] - '0' : 0;
     }
     return v;
 }
 
 // n-tiles per group of the persistent walk: groups of 4 once W no longer fits an XCD's L2 next to the streaming A panels
-// (OVHIP_GEMM_NGROUP: 0 = never group, n = force groups of n where tiles_n is a multiple)
 int gemm_ngroup(int tiles_m, int tiles_n, int K) {
-    static int force = -2;
-    if (force == -2) {
-        const char* e = getenv("OVHIP_GEMM_NGROUP");
-        force = e ? atoi(e) : -1;
-    }
-    int gsz = 4;
-    if (force == 0) return tiles_n;
-    if (force > 0) gsz = force;
     const int64_t wbytes = (int64_t)tiles_n * BN * K * 2;
-    if (force < 0 && wbytes <= (3 << 20)) return tiles_n;
-    if (tiles_n <= gsz || tiles_n % gsz || tiles_m < 16) return tiles_n;
-    return gsz;
+    if (wbytes <= (3 << 20) || tiles_n <= 4 || tiles_n % 4 || tiles_m < 16) return tiles_n;
+    return 4;
 }
 
-// start stagger of the persistent kernel, cycles per class (OVHIP_GEMM_STAGGER; experiment knob, 0 = off)
-int gemm_stagger(int K) {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("OVHIP_GEMM_STAGGER"); v = e ? atoi(e) : 0; }
-    (void)K;
-    return v;
-}
-int gemm_stagger_classes() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("OVHIP_GEMM_STAGGER_CLASSES"); v = e ? atoi(e) : 4; if (v < 1) v = 1; }
-    return v;
-}
-
-int gemm_epi_prio() {
-    static int v = -1;
-    // default 4: waves 4-7 (younger, they lose every VALU / LDS arbitration against waves 0-3 and finish the epilogue 1.4 k cycles
-    // later, while waves 0-3 wait at the tile barrier) run the first four passes at priority 1: both groups then finish together.
-    // Measured in the model: QKV 9.59 -> 9.41 ms, c_fc 12.55 -> 12.24 ms per step (-2 %); all eight passes at priority 1 just swaps
-    // the roles (no gain).
-    if (v < 0) { const char* e = getenv("OVHIP_GEMM_EPI_PRIO"); v = e ? atoi(e) : 4; }
-    return v;
-}
-
-// Per-launch policy of the persistent kernel: half tiles and the rotated walk, store policy by output size, reverse row walk.
-inline int env_flag(const char* name, int dflt) {                 // "0" / "1" (anything else: the default)
-    const char* e = getenv(name);
-    return (e && (e[0] == '0' || e[0] == '1')) ? e[0] - '0' : dflt;
-}
+// Per-launch policy of the persistent kernel: the rotated walk, store policy by output size, reverse row walk.
 template <int EPI>
 void persist_policy(GemmArgs& a, int grid_x) {
-    static const int rot_env = env_flag("OVHIP_GEMM_ROTATE", 1), half_env = env_flag("OVHIP_GEMM_HALF", 1), rev_env = env_flag("OVHIP_GEMM_REVERSE", 1);
     static const int64_t nt_min = [] { const char* e = getenv("OVHIP_GEMM_NT_MIN_MB"); return (int64_t)(e ? atoi(e) : 192) << 20; }();
-    a.half_ok = half_env;
     // outputs of at least OVHIP_GEMM_NT_MIN_MB (192) MB are streamed, smaller ones stored plainly: their consumer finds them in the
     // 256 MB Infinity Cache (gemm_bf16_persist, "Store policy")
     a.st_plain = (int64_t)a.M * a.N * 2 < nt_min ? 1 : 0;
     // Row tiles from the last to the first for the residual GEMM that reads a wide hidden activation (c_proj: K >= 2 N): its
     // producer (c_fc) wrote the rows in ascending order, so the ones it wrote last are those the Infinity Cache still holds.
     // S/8@384 (906 MB hidden per layer) 35.03 -> 34.80 ms per step, L/14 (537 MB) 44.78 -> 44.70: small, free, bitwise the same
-    // results.  OVHIP_GEMM_REVERSE=0 switches it off.
-    a.rev = (rev_env && EPI == OV_EPI_BIAS_RESIDUAL && a.K >= 2 * a.N && a.out_group == 0 && a.resid_mod == 0) ? 1 : 0;
+    // results.
+    a.rev = (EPI == OV_EPI_BIAS_RESIDUAL && a.K >= 2 * a.N && a.out_group == 0 && a.resid_mod == 0) ? 1 : 0;
     // a half last n-tile under the plain walk with a workgroup stride that is a multiple of tiles_n: rotate (GemmArgs::rotmask)
     const int rem = a.N % BN, nper = grid_x >> 3;
     a.rotmask = 0;
-    if (rot_env && half_env && rem > 0 && rem <= 128 && a.ngroup >= a.tiles_n && a.tiles_n > 1 && (a.tiles_n & (a.tiles_n - 1)) == 0 &&
+    if (rem > 0 && rem <= 128 && a.ngroup >= a.tiles_n && a.tiles_n > 1 && (a.tiles_n & (a.tiles_n - 1)) == 0 &&
         grid_x % 8 == 0 && nper % a.tiles_n == 0)
         a.rotmask = a.tiles_n - 1;
 }
 
 template <int EPI>
 int launch(GemmArgs a, hipStream_t st) {
-    int var = gemm_variant();
-    if (a.C2 == nullptr && (var == 4 || (var == 0 && (int64_t)a.tiles_m * a.tiles_n <= gemm_skinny_tiles()))) {
+    const int var = gemm_variant();
+    const int nwg = a.tiles_m * a.tiles_n;
+    const bool mapped = a.out_group != 0 || a.resid_mod != 0;          // row maps: the patch embedding's GEMM only
+    // ---- skinny: small M (or every shape under OVHIP_GEMM_VARIANT=4); never with a kept pre-activation
+    if (a.C2 == nullptr && (var == 4 || (var == 0 && nwg <= SKINNY_TILES))) {
         GemmArgs b = a;
         b.tiles_m = (int)((a.M + SK_BM - 1) / SK_BM);
         b.tiles_n = (a.N + SK_BN - 1) / SK_BN;
@@ -1602,88 +1360,66 @@ int launch(GemmArgs a, hipStream_t st) {
         OV_LAUNCH_CHECK();
         return OV_OK;
     }
-    if (var == 4) var = 0;
     // row-statistic partial sums: fused into the persistent kernel's direct residual epilogue; every other kernel is followed by the
     // stand-alone pass over its output (the same arithmetic, common.h: bitwise the same sums)
     float* const rowpart = a.rowpart;
     bool stats_fused = false;
-    const int nwg = a.tiles_m * a.tiles_n;
-    // fewer tiles than CUs (pooled heads, the tower's tail images): persistence buys nothing, use the plain launch
-    // the persistent kernel also wins on grids somewhat smaller than the chip (one tile per workgroup, but its epilogue starts
-    // without global round trips); tiny grids (the tower's tail images) stay on the plain launch
-    static int min_persist_env = -2;
-    if (min_persist_env == -2) { const char* e = getenv("OVHIP_GEMM_MINPERSIST"); min_persist_env = e ? atoi(e) : -1; }
-    const int min_persist = min_persist_env >= 0 ? min_persist_env : num_cus();
-    if (var == 0 && (nwg < min_persist || a.K < 3 * BK)) var = 2;
-    // row maps (the patch embedding's GEMM) exist in the persistent kernel for the bias and residual epilogues only
-    if (var == 0 && (a.out_group != 0 || a.resid_mod != 0) && EPI != OV_EPI_BIAS && EPI != OV_EPI_BIAS_RESIDUAL) var = 2;
-    if (a.C2 != nullptr && var != 0) {
-        // grids below the persistent kernel's threshold (the tower's tail images): the pre-activation from a second, bias-only
-        // product -- the same fp32 accumulators and the same rounding as the fused form
-        GemmArgs b = a;
-        b.C = a.C2; b.ldc = a.ldc2; b.C2 = nullptr;
-        hipLaunchKernelGGL(gemm_bf16_pp<OV_EPI_BIAS>, dim3(nwg), dim3(NTHREADS), 0, st, b);
-        OV_LAUNCH_CHECK();
-        a.C2 = nullptr;
-        var = 2;
-    }
-    if (var == 3) {
-        hipLaunchKernelGGL(gemm_bf16_w4<EPI>, dim3(nwg), dim3(256), 0, st, a);
-    } else if (var == 1) {
-        hipLaunchKernelGGL(gemm_bf16_256x256<EPI>, dim3(nwg), dim3(NTHREADS), 0, st, a);
-    } else if (var == 2) {
+    // ---- plain (gemm_bf16_pp): fewer tiles than CUs (pooled heads, the tower's tail images), where persistence buys nothing; fewer
+    // than 3 K-tiles; row maps with an epilogue other than bias / residual (the only ones with a MAPPED persistent form)
+    if (var == 2 || nwg < num_cus() || a.K < 3 * BK || (mapped && EPI != OV_EPI_BIAS && EPI != OV_EPI_BIAS_RESIDUAL)) {
+        if (a.C2 != nullptr) {
+            // the pre-activation from a second, bias-only product -- the same fp32 accumulators and the same rounding as the fused form
+            GemmArgs b = a;
+            b.C = a.C2; b.ldc = a.ldc2; b.C2 = nullptr;
+            hipLaunchKernelGGL(gemm_bf16_pp<OV_EPI_BIAS>, dim3(nwg), dim3(NTHREADS), 0, st, b);
+            OV_LAUNCH_CHECK();
+            a.C2 = nullptr;
+        }
         hipLaunchKernelGGL(gemm_bf16_pp<EPI>, dim3(nwg), dim3(NTHREADS), 0, st, a);
     } else {
-        const int ncu = num_cus();
-        const dim3 grid(nwg < ncu ? nwg : ncu), blk(NTHREADS);
+        // ---- persistent: one workgroup per CU.  The instantiation follows from the epilogue and the operands:
+        // FOLD = LN-folded weights (colsum), DIRECT = the v_permlane16_swap epilogue instead of the LDS-transposed one,
+        // MAPPED = row maps, KEEP = the kept pre-activation, STATS = fused row statistics.
+        const dim3 grid(num_cus()), blk(NTHREADS);
         persist_policy<EPI>(a, (int)grid.x);
-        // Epilogue form.  Bias-only epilogue (QKV, projections): LDS-transposed coalesced stores measure faster in the model (9.5-9.8
-        // against 10.0-10.3 ms per step for the QKV GEMMs); OVHIP_GEMM_EPI_DIRECT=1 selects the direct form there too.  GELU (LN-folded
-        // c_fc): by store policy, below.  Residual: LDS-transposed (below); with row maps, kept pre-activations or row statistics: direct.
-        constexpr bool CAN_FOLD = EPI < OV_EPI_BIAS_RESIDUAL;
-        const bool mapped = a.out_group != 0 || a.resid_mod != 0;          // row maps: the patch embedding's GEMM only
-        if (EPI == OV_EPI_BIAS) {
-            static int direct0 = -1;
-            if (direct0 < 0) { const char* e = getenv("OVHIP_GEMM_EPI_DIRECT"); direct0 = (e && e[0] == '1') ? 1 : 0; }
-            if (a.colsum != nullptr) {          // LN fold: never with row maps
-                if (direct0) hipLaunchKernelGGL((gemm_bf16_persist<OV_EPI_BIAS, true, true, false>), grid, blk, 0, st, a);
-                else hipLaunchKernelGGL((gemm_bf16_persist<OV_EPI_BIAS, true, false, false>), grid, blk, 0, st, a);
-            } else if (mapped) {
+        if constexpr (EPI == OV_EPI_BIAS) {
+            // LDS-transposed coalesced stores measure faster in the model than the direct form (9.5-9.8 against 10.0-10.3 ms per step
+            // for the QKV GEMMs)
+            if (a.colsum != nullptr)            // LN fold: never with row maps
+                hipLaunchKernelGGL((gemm_bf16_persist<OV_EPI_BIAS, true, false, false>), grid, blk, 0, st, a);
+            else if (mapped)
                 hipLaunchKernelGGL((gemm_bf16_persist<OV_EPI_BIAS, false, false, true>), grid, blk, 0, st, a);
-            } else {
-                if (direct0) hipLaunchKernelGGL((gemm_bf16_persist<OV_EPI_BIAS, false, true, false>), grid, blk, 0, st, a);
-                else hipLaunchKernelGGL((gemm_bf16_persist<OV_EPI_BIAS, false, false, false>), grid, blk, 0, st, a);
-            }
-        } else if (a.C2 != nullptr) {             // ov_gemm_keep (GELU epilogues, unfolded weights: checked by the caller)
-            constexpr int E = (EPI == OV_EPI_BIAS_GELU_ERF || EPI == OV_EPI_BIAS_GELU_TANH) ? EPI : OV_EPI_BIAS_GELU_ERF;
-            hipLaunchKernelGGL((gemm_bf16_persist<E, false, true, false, true>), grid, blk, 0, st, a);
-        } else if (CAN_FOLD && a.colsum != nullptr) {
-            // GELU with the LN fold (vision / text c_fc): OVHIP_GEMM_GELU_LDS=1 selects the LDS-transposed form (whole-line stores)
-            // Default: the LDS-transposed form when the output is streamed (whole 128-byte lines leave L2; the direct form's 16-byte
-            // streaming stores leave as partial lines: WRITE_SIZE 0.69 against 0.54 GB per L/14 launch) -- L/14 45.1 -> 44.9 ms, S/8
-            // 35.7 -> 35.4; the direct form for small, plainly stored outputs (Ti/16: 0.71 against 0.73 ms).  OVHIP_GEMM_GELU_LDS=0|1 forces.
-            static int gelu_env = -2;
-            if (gelu_env == -2) { const char* e = getenv("OVHIP_GEMM_GELU_LDS"); gelu_env = e ? (e[0] == '1' ? 1 : 0) : -1; }
-            const int gelu_lds = gelu_env >= 0 ? gelu_env : (a.st_plain ? 0 : 1);
-            constexpr int EF = CAN_FOLD ? EPI : OV_EPI_BIAS_GELU_ERF;      // (the residual epilogues never come here: not instantiated)
-            if (gelu_lds) hipLaunchKernelGGL((gemm_bf16_persist<EF, true, false, false>), grid, blk, 0, st, a);
-            else hipLaunchKernelGGL((gemm_bf16_persist<EF, true, true, false>), grid, blk, 0, st, a);
-        } else if (EPI == OV_EPI_BIAS_RESIDUAL && mapped) {
-            hipLaunchKernelGGL((gemm_bf16_persist<OV_EPI_BIAS_RESIDUAL, false, true, true>), grid, blk, 0, st, a);
-        } else if (EPI == OV_EPI_BIAS_RESIDUAL && rowpart != nullptr) {
-            hipLaunchKernelGGL((gemm_bf16_persist<OV_EPI_BIAS_RESIDUAL, false, true, false, false, true>), grid, blk, 0, st, a);
-            stats_fused = true;
-        } else {
-            // Residual epilogue: the LDS-transposed form (whole-line stores, 16 instead of ~70 TA cycles per store instruction) since the
-            // register diet of round 3 made it fit (246 VGPRs, zero scratch): out-proj 4.26 -> 4.10 ms per L/14 step, step -0.5 %
-            // (Ti/16 -1.8 %); OVHIP_GEMM_RESID_LDS=0 selects the direct form again.
-            static const int resid_lds = env_flag("OVHIP_GEMM_RESID_LDS", 1);
-            if constexpr (EPI >= OV_EPI_BIAS_RESIDUAL) {       // (residual and GELU-gradient epilogues: both read a second operand row-wise)
-                if (resid_lds) hipLaunchKernelGGL((gemm_bf16_persist<EPI, false, false, false>), grid, blk, 0, st, a);
-                else hipLaunchKernelGGL((gemm_bf16_persist<EPI, false, true, false>), grid, blk, 0, st, a);
+            else
+                hipLaunchKernelGGL((gemm_bf16_persist<OV_EPI_BIAS, false, false, false>), grid, blk, 0, st, a);
+        } else if constexpr (EPI == OV_EPI_BIAS_GELU_ERF || EPI == OV_EPI_BIAS_GELU_TANH) {
+            if (a.C2 != nullptr) {              // ov_gemm_keep (unfolded weights: checked by the caller)
+                hipLaunchKernelGGL((gemm_bf16_persist<EPI, false, true, false, true>), grid, blk, 0, st, a);
+            } else if (a.colsum != nullptr) {
+                // GELU with the LN fold (vision / text c_fc).  Default: the LDS-transposed form when the output is streamed (whole
+                // 128-byte lines leave L2; the direct form's 16-byte streaming stores leave as partial lines: WRITE_SIZE 0.69 against
+                // 0.54 GB per L/14 launch) -- L/14 45.1 -> 44.9 ms, S/8 35.7 -> 35.4; the direct form for small, plainly stored outputs
+                // (Ti/16: 0.71 against 0.73 ms).  OVHIP_GEMM_GELU_LDS=0|1 forces.
+                static int gelu_env = -2;
+                if (gelu_env == -2) { const char* e = getenv("OVHIP_GEMM_GELU_LDS"); gelu_env = e ? (e[0] == '1' ? 1 : 0) : -1; }
+                const int gelu_lds = gelu_env >= 0 ? gelu_env : (a.st_plain ? 0 : 1);
+                if (gelu_lds) hipLaunchKernelGGL((gemm_bf16_persist<EPI, true, false, false>), grid, blk, 0, st, a);
+                else hipLaunchKernelGGL((gemm_bf16_persist<EPI, true, true, false>), grid, blk, 0, st, a);
             } else {
                 hipLaunchKernelGGL((gemm_bf16_persist<EPI, false, true, false>), grid, blk, 0, st, a);
             }
+        } else if constexpr (EPI == OV_EPI_BIAS_RESIDUAL) {
+            if (mapped) {
+                hipLaunchKernelGGL((gemm_bf16_persist<OV_EPI_BIAS_RESIDUAL, false, true, true>), grid, blk, 0, st, a);
+            } else if (rowpart != nullptr) {
+                hipLaunchKernelGGL((gemm_bf16_persist<OV_EPI_BIAS_RESIDUAL, false, true, false, false, true>), grid, blk, 0, st, a);
+                stats_fused = true;
+            } else {
+                // the LDS-transposed form (whole-line stores, 16 instead of ~70 TA cycles per store instruction) since the register diet
+                // of round 3 made it fit (246 VGPRs, zero scratch): out-proj 4.26 -> 4.10 ms per L/14 step, step -0.5 % (Ti/16 -1.8 %)
+                hipLaunchKernelGGL((gemm_bf16_persist<OV_EPI_BIAS_RESIDUAL, false, false, false>), grid, blk, 0, st, a);
+            }
+        } else {                                // GELU gradient: ov_gemm admits no fold, row maps, kept pre-activation or statistics
+            hipLaunchKernelGGL((gemm_bf16_persist<EPI, false, false, false>), grid, blk, 0, st, a);
         }
     }
     OV_LAUNCH_CHECK();
@@ -1711,9 +1447,16 @@ extern "C" int ov_gemm(const ov_bf16* A, int64_t lda, const ov_bf16* W, int64_t 
     const int64_t tiles_m = (M + BM - 1) / BM;
     const int64_t tiles_n = (N + BN - 1) / BN;
     if (tiles_m * tiles_n > 0x7fffffffLL || M > 0x7fff0000LL) return OV_ERR_UNSUPPORTED;    // 32-bit row indices in the kernels
-    GemmArgs a{A, W, bias, C, R, lda, ldw, ldc, ldr, M, N, K, (int)tiles_m, (int)tiles_n,
-               out_group, resid_mod, resid_off, g_colsum, g_rowstats, g_stamps, g_stamp_slots, g_wstamps, gemm_ngroup((int)tiles_m, (int)tiles_n, K), 0, 0, 0,
-               gemm_stagger(K), gemm_stagger_classes(), gemm_epi_prio(), g_keep, g_ldkeep, nullptr, 0, 1, 0, 0, g_rowpart};
+    GemmArgs a;
+    a.A = A; a.W = W; a.bias = bias; a.C = C; a.R = R;
+    a.lda = lda; a.ldw = ldw; a.ldc = ldc; a.ldr = ldr; a.M = M; a.N = N; a.K = K;
+    a.tiles_m = (int)tiles_m; a.tiles_n = (int)tiles_n;
+    a.out_group = out_group; a.resid_mod = resid_mod; a.resid_off = resid_off;
+    a.colsum = g_colsum; a.rowstats = g_rowstats;
+    a.stamps = g_stamps; a.stamp_slots = g_stamp_slots; a.wstamps = g_wstamps;
+    a.ngroup = gemm_ngroup((int)tiles_m, (int)tiles_n, K);
+    a.C2 = g_keep; a.ldc2 = g_ldkeep;
+    a.rowpart = g_rowpart;
     hipStream_t st = (hipStream_t)stream;
     switch (epilogue) {
         case OV_EPI_BIAS: return launch<OV_EPI_BIAS>(a, st);
@@ -1760,8 +1503,11 @@ extern "C" int ov_gemm_batched(const ov_bf16* A, int64_t lda, int64_t stride_a, 
     if (((uintptr_t)A | (uintptr_t)W | (uintptr_t)C) & 15) return OV_ERR_INVALID;
     const int64_t tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
     if (tiles_m * tiles_n > 0x7fffffffLL || M > 0x7fff0000LL) return OV_ERR_UNSUPPORTED;
-    GemmArgs a{A, W, nullptr, C, nullptr, lda, ldw, ldc, 0, M, N, K, (int)tiles_m, (int)tiles_n, 0, 0, 0, nullptr, nullptr, nullptr, 0, nullptr,
-               (int)tiles_n, stride_a, stride_w, stride_c, 0, 1, 0};
+    GemmArgs a;
+    a.A = A; a.W = W; a.C = C;
+    a.lda = lda; a.ldw = ldw; a.ldc = ldc; a.M = M; a.N = N; a.K = K;
+    a.tiles_m = (int)tiles_m; a.tiles_n = (int)tiles_n; a.ngroup = (int)tiles_n;
+    a.batch_a = stride_a; a.batch_w = stride_w; a.batch_c = stride_c;
     hipLaunchKernelGGL(gemm_bf16_pp<OV_EPI_BIAS>, dim3((unsigned)(tiles_m * tiles_n), (unsigned)batch), dim3(NTHREADS), 0,
                        (hipStream_t)stream, a);
     OV_LAUNCH_CHECK();
@@ -1780,11 +1526,12 @@ extern "C" int ov_gemm_tn_batched(const ov_bf16* P, int64_t ldp, const ov_bf16* 
     if (((uintptr_t)P | (uintptr_t)Q | (uintptr_t)C) & 15) return OV_ERR_INVALID;
     const int64_t tiles_m = (NI + BM - 1) / BM, tiles_n = (NJ + BN - 1) / BN;
     if (tiles_m * tiles_n > 0x7fffffffLL) return OV_ERR_UNSUPPORTED;
-    GemmArgs a{P, Q, nullptr, C, nullptr, ldp, ldq, ldc, 0, NI, NJ, 0, (int)tiles_m, (int)tiles_n, 0, 0, 0, nullptr, nullptr, nullptr, 0, nullptr,
-               (int)tiles_n, chunk, 0, stride_c, 0, 1, 0};
-    a.K = 0;                    // (int field: the contraction length does not fit the struct's K for huge M; carried below)
-    if (Mc > 0x7fffffffLL) return OV_ERR_UNSUPPORTED;
-    a.K = (int)Mc;
+    if (Mc > 0x7fffffffLL) return OV_ERR_UNSUPPORTED;          // (int field: the contraction length is carried in K)
+    GemmArgs a;
+    a.A = P; a.W = Q; a.C = C;
+    a.lda = ldp; a.ldw = ldq; a.ldc = ldc; a.M = NI; a.N = NJ; a.K = (int)Mc;
+    a.tiles_m = (int)tiles_m; a.tiles_n = (int)tiles_n; a.ngroup = (int)tiles_n;
+    a.batch_a = chunk; a.batch_c = stride_c;
     a.psum = psum;
     hipLaunchKernelGGL(gemm_bf16_pp_tn, dim3((unsigned)(tiles_m * tiles_n), (unsigned)batch), dim3(NTHREADS), 0, (hipStream_t)stream, a);
     OV_LAUNCH_CHECK();

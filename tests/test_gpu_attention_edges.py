@@ -84,6 +84,24 @@ def test_attention_padded_row_pitches(B, L, Hh, hd):
     assert torch.equal(got, H.attention(dense.to(DEV), B, L, Hh, hd).cpu())          # the pitch changes nothing else
 
 
+def test_attention_huge_row_pitch():
+    """head_dim 64, padded L <= 320, but the qkv image spans more than 2 GiB of rows (L * ld * 2 > 2^31, a C-API caller's pitch): the
+    persistent kernel's 32-bit row offsets cannot reach it, so the generic kernel (64-bit offsets) computes it.  Pad columns hold NaN."""
+    B, L, Hh, hd, ld = 2, 257, 2, 64, 1 << 22
+    D = Hh * hd
+    assert L * ld * 2 > 2 ** 31
+    dense = rnd(B * L, 3 * D, seed=L + hd + 11).to(torch.bfloat16)
+    qkv = torch.full((B * L, ld), float("nan"), dtype=torch.bfloat16, device=DEV)       # 4.3 GB
+    qkv[:, :3 * D] = dense.to(DEV)
+    got = H.attention(qkv[:, :3 * D], B, L, Hh, hd).cpu()
+    del qkv
+    torch.cuda.empty_cache()
+    ref, pv = attn_ref64(dense, B, L, Hh, hd)
+    r = err_ratio(got, ref, pv)
+    print(f"attention row pitch 2^22 B={B} L={L} H={Hh} hd={hd}: max err / bound {r:.3f}")
+    assert r <= 1.0, r
+
+
 # ------------------------------------------------------------------------------------------------------------------------------
 # C. the lone key as the row maximum, with the fold (default) and with the tile step (OVHIP_ATTN_LONEKEY=0, read once per process)
 

@@ -14,4 +14,4 @@ for _ in range(20):
     H.attention(qkv, B, L, Hh)
 e1.record(); torch.cuda.synchronize()
 ms = e0.elapsed_time(e1) / 20
-print("mode", os.environ.get("OVHIP_ATTN_MODE", "0"), "B", B, "L", L, "H", Hh, "ms/launch", ms, "TFLOP/s", 4.0 * B * Hh * L * L * 64 / (ms * 1e-3) / 1e12)
+print("B", B, "L", L, "H", Hh, "ms/launch", ms, "TFLOP/s", 4.0 * B * Hh * L * L * 64 / (ms * 1e-3) / 1e12)

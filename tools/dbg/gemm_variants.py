@@ -1,4 +1,5 @@
-"""Launch time of ov_gemm at the L/14 shapes for one OVHIP_GEMM_VARIANT (run once per variant: the switch is read once)."""
+"""Launch time of ov_gemm at the L/14 shapes for one OVHIP_GEMM_VARIANT: 0 (default), 2 (non-persistent ping-pong) or 4 (skinny kernel
+for every shape).  Run once per variant: the switch is read once."""
 import os, sys, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))

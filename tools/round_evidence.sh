@@ -19,7 +19,6 @@ bash tools/profile_pmc.sh > $OUT/profile_pmc.log 2>&1
 echo "profiles done"
 python tools/gemm_stamps.py > $OUT/${TAG}_gemm_stamps.log 2>&1
 python tools/gemm_wave_stamps.py qkv out fc proj > $OUT/${TAG}_gemm_wave_stamps.log 2>&1
-python tools/dbg/skinny_cross.py > $OUT/${TAG}_skinny_cross.log 2>&1
 python tools/train_step_probe.py > $OUT/${TAG}_train_step.log 2>&1
 python tools/optim_probe.py > $OUT/${TAG}_optim.log 2>&1
 python tools/graph_probe.py > $OUT/${TAG}_graph.log 2>&1

@@ -451,6 +451,23 @@ size_t ov_tower_backward_input_workspace_bytes(const ov_tower* t, int B, int L);
 int    ov_tower_backward_input(const ov_tower* t, const ov_bf16* saved, ov_bf16* dx, int B, int L, void* workspace, size_t workspace_bytes,
                                ov_stream_t stream);
 
+/* Frozen parameters (LiT: a locked image tower; gradient ascent through a frozen text tower).  ov_tower_forward_saving_from runs the
+ * layers below `first` with exactly the operators of ov_tower_forward_saving, x in place and their intermediates in the workspace
+ * (ov_tower_forward_saving_from_workspace_bytes, 0 when first == 0), and keeps the slots of layers [first, layers) in `saved` (slot 0 =
+ * layer `first`; ov_tower_saved_bytes_from; NULL iff first == layers).  x and every kept slot are bitwise ov_tower_forward_saving's.
+ * ov_tower_backward_partial walks layers layers-1 .. first over those slots: grads[layers - first] requests (weight, bias) pairs, a NULL
+ * pair is frozen; a pair with one NULL pointer, or a pointer that is not 16-byte aligned, is OV_ERR_INVALID.  dx holds d(output) on
+ * entry; with want_dx it holds d(input of layer `first`) on return, otherwise its contents are unspecified and nothing runs below the
+ * lowest block with a requested pair.  Every gradient computed is bitwise ov_tower_backward's (all pairs NULL, first = 0, want_dx = 1:
+ * ov_tower_backward_input's dx). */
+size_t ov_tower_saved_bytes_from(const ov_tower* t, int first, int B, int L);
+size_t ov_tower_forward_saving_from_workspace_bytes(const ov_tower* t, int first, int B, int L);
+int    ov_tower_forward_saving_from(const ov_tower* t, int first, ov_bf16* x, ov_bf16* saved, int B, int L, void* workspace,
+                                    size_t workspace_bytes, ov_stream_t stream);
+size_t ov_tower_backward_partial_workspace_bytes(const ov_tower* t, int B, int L);
+int    ov_tower_backward_partial(const ov_tower* t, int first, const ov_bf16* saved, ov_bf16* dx, const ov_block_grads* grads, int want_dx,
+                                 int B, int L, void* workspace, size_t workspace_bytes, ov_stream_t stream);
+
 /* ---- MLP-feature objective (feature visualisation: a forward hook on resblocks[layer].mlp.gelu, ov-feature-visualization.py:211) --
  * The attention half of one block, x1 = x + out_proj(attn(ln_1(x))) (transformer.py:263), keeping qkv [B*L, 3D], attn_out [B*L, D],
  * x1 [B*L, D] and, where the resident attention backward reads it (head_dim 64, L <= 288), lse [B*heads][L rounded up to 32] fp32

@@ -131,6 +131,12 @@ SIGNATURES = {
     "ov_tower_saved_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "ov_tower_backward_input_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "ov_tower_backward_input": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "ov_tower_saved_bytes_from": (c_size_t, [c_void_p, c_int, c_int, c_int]),
+    "ov_tower_forward_saving_from_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
+    "ov_tower_forward_saving_from": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "ov_tower_backward_partial_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "ov_tower_backward_partial": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t,
+                                          c_void_p]),
     "ov_block_attn_forward_saving": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "ov_block_attn_backward_input_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "ov_block_attn_backward_input": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,

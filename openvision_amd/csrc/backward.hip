@@ -173,12 +173,14 @@ __global__ __launch_bounds__(256) void splitk_sum(const ov_bf16* __restrict__ pa
 
 // LayerNorm backward, wave per row (row in registers, like the forward).  dgamma / dbeta partial sums stay in the wave's
 // registers across the rows it owns and are written once: part[wave_global][2][D].  PARAMS = false: dx only (the input-only
-// backward of frozen weights); the dx arithmetic is the same instruction for instruction.
-template <int NCH, bool PARAMS = true>
+// backward of frozen weights); DX = false: the parameter partials only (a trainable LayerNorm whose input gradient nobody needs).
+// Either way the arithmetic that is kept is the same instruction for instruction, with the same rows per wave.
+template <int NCH, bool PARAMS = true, bool DX = true>
 __global__ __launch_bounds__(256) void layernorm_bwd_rows(const ov_bf16* __restrict__ x, int64_t ldx, const float* __restrict__ gamma,
                                                           const ov_bf16* __restrict__ dy, int64_t lddy, const ov_bf16* __restrict__ dres,
                                                           int64_t lddres, ov_bf16* __restrict__ dx, int64_t lddx, int64_t rows, int D,
                                                           float eps, float* __restrict__ part) {
+    static_assert(PARAMS || DX, "nothing to compute");
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int nchunk = D >> 3;
     const float invD = 1.0f / (float)D;
@@ -230,13 +232,16 @@ __global__ __launch_bounds__(256) void layernorm_bwd_rows(const ov_bf16* __restr
                         ag[c][e] = fmaf(q[c][e], xh, ag[c][e]);      // dgamma += dy * xhat
                         ab[c][e] += q[c][e];                         // dbeta  += dy
                     }
-                    v[c][e] = xh;
-                    q[c][e] *= g[e];                                 // q = dy * gamma
-                    sq += q[c][e];
-                    sqx = fmaf(q[c][e], xh, sqx);
+                    if (DX) {
+                        v[c][e] = xh;
+                        q[c][e] *= g[e];                             // q = dy * gamma
+                        sq += q[c][e];
+                        sqx = fmaf(q[c][e], xh, sqx);
+                    }
                 }
             }
         }
+        if (!DX) continue;
         const float mq = wave_sum(sq) * invD, mqx = wave_sum(sqx) * invD;
 #pragma unroll
         for (int c = 0; c < NCH; ++c) {
@@ -648,6 +653,27 @@ int layernorm_dx(const ov_bf16* x, int64_t ldx, const float* gamma, const ov_bf1
     return OV_OK;
 }
 
+// dgamma / dbeta alone (a trainable LayerNorm whose input gradient is not wanted): ov_layernorm_backward's rows without dx, then the
+// same column sums -- bitwise its dgamma / dbeta.  `workspace`: ov_layernorm_backward_workspace_bytes(rows, D).
+int layernorm_params(const ov_bf16* x, int64_t ldx, const float* gamma, const ov_bf16* dy, int64_t lddy, float* dgamma, float* dbeta,
+                     int64_t rows, int D, float eps, void* workspace, ov_stream_t stream) {
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t blocks = lnb_blocks(rows);
+    const dim3 grid((unsigned)blocks), blk(256);
+    float* part = (float*)workspace;
+    const int nch = (D / 8 + 63) / 64;
+    const ov_bf16* nr = nullptr;
+    ov_bf16* nx = nullptr;
+    if (nch <= 1) hipLaunchKernelGGL((layernorm_bwd_rows<1, true, false>), grid, blk, 0, st, x, ldx, gamma, dy, lddy, nr, 0, nx, 0, rows, D, eps, part);
+    else if (nch <= 2) hipLaunchKernelGGL((layernorm_bwd_rows<2, true, false>), grid, blk, 0, st, x, ldx, gamma, dy, lddy, nr, 0, nx, 0, rows, D, eps, part);
+    else if (nch <= 3) hipLaunchKernelGGL((layernorm_bwd_rows<3, true, false>), grid, blk, 0, st, x, ldx, gamma, dy, lddy, nr, 0, nx, 0, rows, D, eps, part);
+    else if (nch <= 4) hipLaunchKernelGGL((layernorm_bwd_rows<4, true, false>), grid, blk, 0, st, x, ldx, gamma, dy, lddy, nr, 0, nx, 0, rows, D, eps, part);
+    else hipLaunchKernelGGL((layernorm_bwd_rows<8, true, false>), grid, blk, 0, st, x, ldx, gamma, dy, lddy, nr, 0, nx, 0, rows, D, eps, part);
+    OV_LAUNCH_CHECK();
+    float* scratch = part + (size_t)blocks * 4 * 2 * D;
+    return launch_rows_sum(part, blocks * 4, 2 * D, (int64_t)2 * D, scratch, dgamma, st, dbeta, D);
+}
+
 struct InputBufs { ov_bf16 *wt, *dh, *t1, *dx1, *dqkv; char* att; size_t att_bytes, total; };
 // mlp = false: the attention half only (no dh, no dx1)
 inline InputBufs plan_input(const ov_tower_cfg* c, int B, int L, bool mlp, char* base) {
@@ -726,4 +752,79 @@ int block_backward_input(const ov_tower_cfg* cfg, const ov_block_weights* w, con
     if ((rc = linear_dx(b.dh, F, w->fc_w, D, M, F, D, b.t1, D, b.wt, stream))) return rc;
     if ((rc = layernorm_dx(s->x1, D, w->ln2_w, b.t1, D, dy, D, b.dx1, D, M, D, cfg->ln_eps, stream))) return rc;
     return attn_backward_input(cfg, w, x, s->qkv, s->attn_out, s->attn_lse, b.dx1, dx, B, L, b, stream);
+}
+
+// ---- partial backward (frozen parameters: LiT, a frozen text tower) ----------------------------------------------------------------
+// The six (weight, bias) pairs of ov_block_grads, bit k = pair k in declaration order (ln_1, in_proj, out_proj, ln_2, c_fc, c_proj):
+// the requested ones, 0 for g == NULL, -1 when a pair has exactly one NULL pointer or a pointer is not 16-byte aligned (the dW / db
+// products require it; checked here so that the tower rejects it before its first launch).
+int block_grad_pairs(const ov_block_grads* g) {
+    if (!g) return 0;
+    const void* p[12] = {g->ln1_w, g->ln1_b, g->qkv_w, g->qkv_b, g->out_w, g->out_b, g->ln2_w, g->ln2_b, g->fc_w, g->fc_b, g->proj_w, g->proj_b};
+    int m = 0;
+    for (int k = 0; k < 6; ++k) {
+        if ((p[2 * k] == nullptr) != (p[2 * k + 1] == nullptr)) return -1;
+        if (((uintptr_t)p[2 * k] | (uintptr_t)p[2 * k + 1]) & 15) return -1;
+        if (p[2 * k]) m |= 1 << k;
+    }
+    return m;
+}
+
+// One block's backward over the activations ov_tower_forward_saving kept (every field of `s` set; the tower checks the arguments),
+// computing only the requested pairs of `g` and, when dx != NULL, the block input's gradient (dx may alias dy).  Nothing is launched
+// that no requested output needs, and each launch that is made is the one ov_block_backward makes for that quantity (a dX-only,
+// dW-only or combined linear_backward; the full, dx-only or parameter-only LayerNorm rows), so what comes out is bitwise its result.
+// Workspace: ov_block_backward_workspace_bytes.
+int block_backward_partial(const ov_tower_cfg* cfg, const ov_block_weights* w, const ov_bf16* x, const ov_block_saved* s,
+                           const ov_bf16* dy, ov_bf16* dx, const ov_block_grads* g, int B, int L, void* workspace, size_t workspace_bytes,
+                           ov_stream_t stream) {
+    const int pairs = block_grad_pairs(g);
+    if (pairs < 0) return OV_ERR_INVALID;
+    const bool p_ln1 = pairs & 1, p_qkv = pairs & 2, p_out = pairs & 4, p_ln2 = pairs & 8, p_fc = pairs & 16, p_proj = pairs & 32;
+    // what each intermediate gradient is needed for, from the bottom of the block up
+    const bool need_dln1 = p_ln1 || dx;                   // d ln_1 out (QKV dX)
+    const bool need_dqkv = p_qkv || need_dln1;            // attention backward (reads d attention out: out_proj dX)
+    const bool need_dx1 = p_out || need_dqkv;             // LN_2 backward's dx (plus dy) = d x1
+    const bool need_dln2 = p_ln2 || need_dx1;             // d ln_2 out (c_fc dX)
+    const bool need_dh = p_fc || need_dln2;               // d c_fc pre-activation (c_proj dX with the GELU derivative)
+    const int D = cfg->width, F = cfg->mlp_pad, H = cfg->heads, hd = D / H;
+    const int64_t M = (int64_t)B * L;
+    const float eps = cfg->ln_eps, scale = 1.0f / sqrtf((float)hd);
+    BlockBufs b = plan_block(cfg, B, L, (char*)workspace);
+    if (workspace_bytes < b.total) return OV_ERR_WORKSPACE;
+    int rc;
+#define OV_TRY(call) do { if ((rc = (call)) != OV_OK) return rc; } while (0)
+    // ---- MLP branch: y = x1 + c_proj(gelu(a))
+    if (need_dh)
+        OV_TRY(linear_backward(dy, D, nullptr, 0, w->proj_w, F, M, D, F, b.dh, F, nullptr, 0, nullptr, b.lin, b.lin_bytes, stream,
+                               cfg->gelu_tanh ? OV_EPI_GELU_GRAD_TANH : OV_EPI_GELU_GRAD_ERF, s->fc_pre, F));
+    if (p_proj)
+        OV_TRY(ov_linear_backward(dy, D, s->fc_act, F, w->proj_w, F, M, D, F, nullptr, 0, g->proj_w, F, g->proj_b, b.lin, b.lin_bytes, stream));
+    if (p_fc || need_dln2)
+        OV_TRY(ov_linear_backward(b.dh, F, s->ln2_out, D, w->fc_w, D, M, F, D, need_dln2 ? b.t1 : nullptr, D, p_fc ? g->fc_w : nullptr, D,
+                                  p_fc ? g->fc_b : nullptr, b.lin, b.lin_bytes, stream));
+    if (p_ln2 && need_dx1)
+        OV_TRY(ov_layernorm_backward(s->x1, D, w->ln2_w, b.t1, D, dy, D, b.dx1, D, g->ln2_w, g->ln2_b, M, D, eps, b.ln, b.ln_bytes, stream));
+    else if (need_dx1)
+        OV_TRY(layernorm_dx(s->x1, D, w->ln2_w, b.t1, D, dy, D, b.dx1, D, M, D, eps, stream));
+    else if (p_ln2)
+        OV_TRY(layernorm_params(s->x1, D, w->ln2_w, b.t1, D, g->ln2_w, g->ln2_b, M, D, eps, b.ln, stream));
+    // ---- attention branch: x1 = x + out_proj(attn(qkv))
+    if (p_out || need_dqkv)
+        OV_TRY(ov_linear_backward(b.dx1, D, s->attn_out, D, w->out_w, D, M, D, D, need_dqkv ? b.t1 : nullptr, D, p_out ? g->out_w : nullptr,
+                                  D, p_out ? g->out_b : nullptr, b.lin, b.lin_bytes, stream));
+    if (need_dqkv)
+        OV_TRY(ov_attention_backward_saved(s->qkv, 3 * D, s->attn_out, D, b.t1, D, b.dqkv, 3 * D, s->attn_lse, B, L, H, hd, scale, b.att,
+                                           b.att_bytes, stream));
+    if (p_qkv || need_dln1)
+        OV_TRY(ov_linear_backward(b.dqkv, 3 * D, s->ln1_out, D, w->qkv_w, D, M, 3 * D, D, need_dln1 ? b.t1 : nullptr, D,
+                                  p_qkv ? g->qkv_w : nullptr, D, p_qkv ? g->qkv_b : nullptr, b.lin, b.lin_bytes, stream));
+    if (p_ln1 && dx)
+        OV_TRY(ov_layernorm_backward(x, D, w->ln1_w, b.t1, D, b.dx1, D, dx, D, g->ln1_w, g->ln1_b, M, D, eps, b.ln, b.ln_bytes, stream));
+    else if (dx)
+        OV_TRY(layernorm_dx(x, D, w->ln1_w, b.t1, D, b.dx1, D, dx, D, M, D, eps, stream));
+    else if (p_ln1)
+        OV_TRY(layernorm_params(x, D, w->ln1_w, b.t1, D, g->ln1_w, g->ln1_b, M, D, eps, b.ln, stream));
+#undef OV_TRY
+    return OV_OK;
 }

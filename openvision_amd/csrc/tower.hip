@@ -541,50 +541,111 @@ extern "C" size_t ov_tower_saved_bytes(const ov_tower* t, int B, int L) {
     return (size_t)t->cfg.layers * saved_per_layer(t->cfg, B, L) * sizeof(ov_bf16);
 }
 
+namespace {
+// one layer's slot: [x | qkv | attention out | x1 | ln_1 out | ln_2 out | c_fc pre-activation | c_fc activation | lse]; `rest` = where
+// the part after x starts (sx + M D in `saved`; elsewhere for the layers ov_tower_forward_saving_from does not keep)
+struct Slot { ov_bf16 *x, *qkv, *o, *x1, *n1, *n2, *pre, *act; float* lse; };
+inline Slot slot_at(const ov_tower_cfg& c, ov_bf16* sx, ov_bf16* rest, int64_t M) {
+    Slot s;
+    s.x = sx;
+    s.qkv = rest;
+    s.o = s.qkv + (size_t)M * 3 * c.width;
+    s.x1 = s.o + (size_t)M * c.width;
+    s.n1 = s.x1 + (size_t)M * c.width;
+    s.n2 = s.n1 + (size_t)M * c.width;
+    s.pre = s.n2 + (size_t)M * c.width;
+    s.act = s.pre + (size_t)M * c.mlp_pad;
+    s.lse = (float*)(s.act + (size_t)M * c.mlp_pad);
+    return s;
+}
+inline ov_block_saved block_saved_at(const ov_tower_cfg& c, const ov_bf16* sx, int B, int L) {
+    const int64_t M = (int64_t)B * L;
+    const Slot s = slot_at(c, const_cast<ov_bf16*>(sx), const_cast<ov_bf16*>(sx) + (size_t)M * c.width, M);
+    ov_block_saved sv;
+    sv.qkv = s.qkv; sv.attn_out = s.o; sv.x1 = s.x1; sv.ln1_out = s.n1; sv.ln2_out = s.n2; sv.fc_pre = s.pre; sv.fc_act = s.act;
+    sv.attn_lse = saved_lse_used(c, L) ? s.lse : nullptr;
+    return sv;
+}
+
+// One block of the saving forward: the same operator sequence as run_block, with qkv / attention output / x1 / ... written where the
+// backward will read them, the input read from s.x and the output written to y (y may be s.x: nothing reads the input after out_proj)
+int forward_saving_layer(const ov_tower_cfg& c, const ov_block_weights& w, const Slot& s, ov_bf16* y, int B, int L, ov_stream_t stream) {
+    const int D = c.width, H = c.heads, hd = D / H;
+    const int64_t M = (int64_t)B * L;
+    const float scale = 1.0f / sqrtf((float)hd);
+    const int gelu = c.gelu_tanh ? OV_EPI_BIAS_GELU_TANH : OV_EPI_BIAS_GELU_ERF;
+    int rc;
+    if ((rc = ov_layernorm(s.x, OV_BF16, D, w.ln1_w, w.ln1_b, s.n1, OV_BF16, D, M, D, c.ln_eps, stream))) return rc;
+    if ((rc = ov_gemm(s.n1, D, w.qkv_w, D, w.qkv_b, s.qkv, 3 * D, M, 3 * D, D, OV_EPI_BIAS, nullptr, 0, 0, 0, 0, stream))) return rc;
+    rc = saved_lse_used(c, L) ? ov_attention_lse(s.qkv, 3 * D, s.o, D, s.lse, B, L, H, hd, scale, stream)
+                              : ov_attention(s.qkv, 3 * D, s.o, D, B, L, H, hd, scale, stream);
+    if (rc) return rc;
+    if ((rc = ov_gemm(s.o, D, w.out_w, D, w.out_b, s.x1, D, M, D, D, OV_EPI_BIAS_RESIDUAL, s.x, D, 0, 0, 0, stream))) return rc;
+    if ((rc = ov_layernorm(s.x1, OV_BF16, D, w.ln2_w, w.ln2_b, s.n2, OV_BF16, D, M, D, c.ln_eps, stream))) return rc;
+    if ((rc = ov_gemm_keep(s.n2, D, w.fc_w, D, w.fc_b, s.act, c.mlp_pad, s.pre, c.mlp_pad, M, c.mlp_pad, D, gelu, stream))) return rc;
+    return ov_gemm(s.act, c.mlp_pad, w.proj_w, c.mlp_pad, w.proj_b, y, D, M, D, c.mlp_pad, OV_EPI_BIAS_RESIDUAL, s.x1, D, 0, 0, 0, stream);
+}
+
+// layers [first, layers) keep their slots in `saved` (slot 0 = layer first); layer i reads its input from its own slot and writes its
+// output straight into the next slot (the last one into x): one copy for the kept part of the tower
+int forward_saving_kept(const ov_tower* t, int first, ov_bf16* x, ov_bf16* saved, int B, int L, ov_stream_t stream) {
+    const ov_tower_cfg& c = t->cfg;
+    const int64_t M = (int64_t)B * L;
+    const size_t spl = saved_per_layer(c, B, L);
+    hipError_t e = hipMemcpyAsync(saved, x, (size_t)M * c.width * 2, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+    if (e != hipSuccess) return OV_ERR_HIP - (int)e;
+    for (int i = first; i < c.layers; ++i) {
+        ov_bf16* sx = saved + (size_t)(i - first) * spl;
+        ov_bf16* y = i + 1 < c.layers ? sx + spl : x;
+        const int rc = forward_saving_layer(c, t->blocks[i], slot_at(c, sx, sx + (size_t)M * c.width, M), y, B, L, stream);
+        if (rc) return rc;
+    }
+    return OV_OK;
+}
+}  // namespace
+
 extern "C" int ov_tower_forward_saving(const ov_tower* t, ov_bf16* x, ov_bf16* saved, int B, int L, void* workspace,
                                        size_t workspace_bytes, ov_stream_t stream) {
     if (!t || !x || !saved || !workspace || B <= 0 || L <= 0) return OV_ERR_INVALID;
     if (tower_fp8(t)) return OV_ERR_UNSUPPORTED;                   // the backward differentiates the bf16 path
     if (workspace_bytes < ov_tower_workspace_bytes(t, B, L)) return OV_ERR_WORKSPACE;
     if (((uintptr_t)x | (uintptr_t)saved | (uintptr_t)workspace) & 15) return OV_ERR_INVALID;
-    const ov_tower_cfg& c = t->cfg;
-    const int D = c.width, H = c.heads, hd = D / H;
-    const int64_t M = (int64_t)B * L;
-    const float scale = 1.0f / sqrtf((float)hd);              // (every intermediate lands in `saved`: the workspace stays unused)
-    const int gelu = c.gelu_tanh ? OV_EPI_BIAS_GELU_TANH : OV_EPI_BIAS_GELU_ERF;
-    const size_t spl = saved_per_layer(c, B, L);
-    const bool keep_lse = saved_lse_used(c, L);
+    const ov_tower_cfg& c = t->cfg;                            // (every intermediate lands in `saved`: the workspace stays unused)
     for (int i = 0; i < c.layers; ++i)
         if (!t->set[i] || t->blocks[i].qkv_colsum || t->blocks[i].fc_colsum) return OV_ERR_INVALID;   // the module's own weights
-    // layer i reads its input from its own saved slot and writes its output straight into layer i+1's slot (the last one into x):
-    // one copy for the whole tower
-    hipError_t e = hipMemcpyAsync(saved, x, (size_t)M * D * 2, hipMemcpyDeviceToDevice, (hipStream_t)stream);
-    if (e != hipSuccess) return OV_ERR_HIP - (int)e;
-    for (int i = 0; i < c.layers; ++i) {
-        const ov_block_weights& w = t->blocks[i];
-        ov_bf16* sx = saved + (size_t)i * spl;
-        ov_bf16* sqkv = sx + (size_t)M * D;
-        ov_bf16* so = sqkv + (size_t)M * 3 * D;
-        ov_bf16* sx1 = so + (size_t)M * D;
-        ov_bf16* sn1 = sx1 + (size_t)M * D;
-        ov_bf16* sn2 = sn1 + (size_t)M * D;
-        ov_bf16* spre = sn2 + (size_t)M * D;
-        ov_bf16* sact = spre + (size_t)M * c.mlp_pad;
-        float* slse = (float*)(sact + (size_t)M * c.mlp_pad);
-        ov_bf16* y = i + 1 < c.layers ? saved + (size_t)(i + 1) * spl : x;
-        int rc;
-        // the same operator sequence as run_block, with qkv / attention output / x1 written where the backward will read them
-        if ((rc = ov_layernorm(sx, OV_BF16, D, w.ln1_w, w.ln1_b, sn1, OV_BF16, D, M, D, c.ln_eps, stream))) return rc;
-        if ((rc = ov_gemm(sn1, D, w.qkv_w, D, w.qkv_b, sqkv, 3 * D, M, 3 * D, D, OV_EPI_BIAS, nullptr, 0, 0, 0, 0, stream))) return rc;
-        rc = keep_lse ? ov_attention_lse(sqkv, 3 * D, so, D, slse, B, L, H, hd, scale, stream) : ov_attention(sqkv, 3 * D, so, D, B, L, H, hd, scale, stream);
+    return forward_saving_kept(t, 0, x, saved, B, L, stream);
+}
+
+// ---- frozen lower layers: keep only layers [first, layers) ----------------------------------------------------------------------------
+extern "C" size_t ov_tower_saved_bytes_from(const ov_tower* t, int first, int B, int L) {
+    if (!t || B <= 0 || L <= 0 || first < 0 || first > t->cfg.layers) return 0;
+    return (size_t)(t->cfg.layers - first) * saved_per_layer(t->cfg, B, L) * sizeof(ov_bf16);
+}
+
+// the layers below `first` run in place on x with their intermediates in one slot's worth of workspace (all but its x part); 0 = none
+extern "C" size_t ov_tower_forward_saving_from_workspace_bytes(const ov_tower* t, int first, int B, int L) {
+    if (!t || B <= 0 || L <= 0 || first <= 0 || first > t->cfg.layers) return 0;
+    return (saved_per_layer(t->cfg, B, L) - (size_t)B * L * t->cfg.width) * sizeof(ov_bf16);
+}
+
+extern "C" int ov_tower_forward_saving_from(const ov_tower* t, int first, ov_bf16* x, ov_bf16* saved, int B, int L, void* workspace,
+                                            size_t workspace_bytes, ov_stream_t stream) {
+    if (!t || !x || B <= 0 || L <= 0 || first < 0 || first > t->cfg.layers) return OV_ERR_INVALID;
+    const ov_tower_cfg& c = t->cfg;
+    if (first < c.layers && !saved) return OV_ERR_INVALID;
+    const size_t need = ov_tower_forward_saving_from_workspace_bytes(t, first, B, L);
+    if (need > 0 && !workspace) return OV_ERR_INVALID;
+    if (tower_fp8(t)) return OV_ERR_UNSUPPORTED;
+    if (workspace_bytes < need) return OV_ERR_WORKSPACE;
+    if (((uintptr_t)x | (uintptr_t)saved | (uintptr_t)workspace) & 15) return OV_ERR_INVALID;
+    for (int i = 0; i < c.layers; ++i)
+        if (!t->set[i] || t->blocks[i].qkv_colsum || t->blocks[i].fc_colsum) return OV_ERR_INVALID;
+    const int64_t M = (int64_t)B * L;
+    for (int i = 0; i < first; ++i) {                                // x -> x in place, the same operators on the same values
+        const int rc = forward_saving_layer(c, t->blocks[i], slot_at(c, x, (ov_bf16*)workspace, M), x, B, L, stream);
         if (rc) return rc;
-        if ((rc = ov_gemm(so, D, w.out_w, D, w.out_b, sx1, D, M, D, D, OV_EPI_BIAS_RESIDUAL, sx, D, 0, 0, 0, stream))) return rc;
-        if ((rc = ov_layernorm(sx1, OV_BF16, D, w.ln2_w, w.ln2_b, sn2, OV_BF16, D, M, D, c.ln_eps, stream))) return rc;
-        if ((rc = ov_gemm_keep(sn2, D, w.fc_w, D, w.fc_b, sact, c.mlp_pad, spre, c.mlp_pad, M, c.mlp_pad, D, gelu, stream))) return rc;
-        if ((rc = ov_gemm(sact, c.mlp_pad, w.proj_w, c.mlp_pad, w.proj_b, y, D, M, D, c.mlp_pad, OV_EPI_BIAS_RESIDUAL, sx1, D, 0, 0, 0, stream)))
-            return rc;
     }
-    return OV_OK;
+    return first < c.layers ? forward_saving_kept(t, first, x, saved, B, L, stream) : OV_OK;
 }
 
 extern "C" size_t ov_tower_backward_workspace_bytes(const ov_tower* t, int B, int L) {
@@ -596,21 +657,11 @@ extern "C" int ov_tower_backward(const ov_tower* t, const ov_bf16* saved, ov_bf1
                                  void* workspace, size_t workspace_bytes, ov_stream_t stream) {
     if (!t || !saved || !dx || !grads || !workspace || B <= 0 || L <= 0) return OV_ERR_INVALID;
     const ov_tower_cfg& c = t->cfg;
-    const int D = c.width;
-    const int64_t M = (int64_t)B * L;
     for (int i = 0; i < c.layers; ++i)
         if (!t->set[i]) return OV_ERR_INVALID;
     for (int i = c.layers - 1; i >= 0; --i) {                     // dx holds d(block output) on entry and d(block input) on exit
         const ov_bf16* sx = saved + (size_t)i * saved_per_layer(c, B, L);
-        ov_block_saved sv;
-        sv.qkv = sx + (size_t)M * D;
-        sv.attn_out = sv.qkv + (size_t)M * 3 * D;
-        sv.x1 = sv.attn_out + (size_t)M * D;
-        sv.ln1_out = sv.x1 + (size_t)M * D;
-        sv.ln2_out = sv.ln1_out + (size_t)M * D;
-        sv.fc_pre = sv.ln2_out + (size_t)M * D;
-        sv.fc_act = sv.fc_pre + (size_t)M * c.mlp_pad;
-        sv.attn_lse = saved_lse_used(c, L) ? (const float*)(sv.fc_act + (size_t)M * c.mlp_pad) : nullptr;
+        const ov_block_saved sv = block_saved_at(c, sx, B, L);
         const int rc = ov_block_backward(&c, &t->blocks[i], sx, &sv, dx, dx, &grads[i], B, L, workspace, workspace_bytes, stream);
         if (rc) return rc;
     }
@@ -638,20 +689,50 @@ extern "C" int ov_tower_backward_input(const ov_tower* t, const ov_bf16* saved, 
     if (((uintptr_t)saved | (uintptr_t)dx | (uintptr_t)workspace) & 15) return OV_ERR_INVALID;
     for (int i = 0; i < c.layers; ++i)
         if (!t->set[i] || t->blocks[i].qkv_colsum || t->blocks[i].fc_colsum) return OV_ERR_INVALID;
-    const int D = c.width;
-    const int64_t M = (int64_t)B * L;
     for (int i = c.layers - 1; i >= 0; --i) {                     // dx holds d(block output) on entry and d(block input) on exit
         const ov_bf16* sx = saved + (size_t)i * saved_per_layer(c, B, L);
-        ov_block_saved sv;
-        sv.qkv = sx + (size_t)M * D;
-        sv.attn_out = sv.qkv + (size_t)M * 3 * D;
-        sv.x1 = sv.attn_out + (size_t)M * D;
-        sv.ln1_out = sv.x1 + (size_t)M * D;
-        sv.ln2_out = sv.ln1_out + (size_t)M * D;
-        sv.fc_pre = sv.ln2_out + (size_t)M * D;
-        sv.fc_act = sv.fc_pre + (size_t)M * c.mlp_pad;
-        sv.attn_lse = saved_lse_used(c, L) ? (const float*)(sv.fc_act + (size_t)M * c.mlp_pad) : nullptr;
+        const ov_block_saved sv = block_saved_at(c, sx, B, L);
         const int rc = block_backward_input(&c, &t->blocks[i], sx, &sv, dx, dx, B, L, workspace, stream);
+        if (rc) return rc;
+    }
+    return OV_OK;
+}
+
+// Partial backward (frozen parameters): the layers [first, layers) that ov_tower_forward_saving_from kept, in reverse, each through
+// block_backward_partial (backward.hip) with the pairs grads[i - first] requests.  Frozen blocks above the lowest trainable one run
+// input-only; with want_dx = 0 nothing runs below it.  Every gradient computed is bitwise ov_tower_backward's.
+int block_grad_pairs(const ov_block_grads* g);
+int block_backward_partial(const ov_tower_cfg* cfg, const ov_block_weights* w, const ov_bf16* x, const ov_block_saved* s, const ov_bf16* dy,
+                           ov_bf16* dx, const ov_block_grads* g, int B, int L, void* workspace, size_t workspace_bytes, ov_stream_t stream);
+
+extern "C" size_t ov_tower_backward_partial_workspace_bytes(const ov_tower* t, int B, int L) {
+    if (!t) return 0;
+    return ov_block_backward_workspace_bytes(&t->cfg, B, L);
+}
+
+extern "C" int ov_tower_backward_partial(const ov_tower* t, int first, const ov_bf16* saved, ov_bf16* dx, const ov_block_grads* grads,
+                                         int want_dx, int B, int L, void* workspace, size_t workspace_bytes, ov_stream_t stream) {
+    if (!t || !dx || B <= 0 || L <= 0 || first < 0 || first > t->cfg.layers) return OV_ERR_INVALID;
+    const ov_tower_cfg& c = t->cfg;
+    if (first == c.layers) return OV_OK;                          // nothing kept: d(input of layer `first`) = d(output), already in dx
+    if (!saved || !grads || !workspace) return OV_ERR_INVALID;
+    int lo = want_dx ? first : c.layers;                          // the lowest layer that runs
+    for (int i = c.layers - 1; i >= first; --i) {
+        const int p = block_grad_pairs(&grads[i - first]);
+        if (p < 0) return OV_ERR_INVALID;                          // a pair with one NULL pointer, or a misaligned one
+        if (p && i < lo) lo = i;
+    }
+    const size_t need = ov_tower_backward_partial_workspace_bytes(t, B, L);
+    if (need == 0) return OV_ERR_UNSUPPORTED;                       // block_cfg_ok: width % 64, head_dim % 8 and <= 96, mlp_pad % 64
+    if (workspace_bytes < need) return OV_ERR_WORKSPACE;
+    if (((uintptr_t)saved | (uintptr_t)dx | (uintptr_t)workspace) & 15) return OV_ERR_INVALID;
+    for (int i = 0; i < c.layers; ++i)
+        if (!t->set[i] || t->blocks[i].qkv_colsum || t->blocks[i].fc_colsum) return OV_ERR_INVALID;
+    for (int i = c.layers - 1; i >= lo; --i) {                    // dx holds d(block output) on entry and d(block input) on exit
+        const ov_bf16* sx = saved + (size_t)(i - first) * saved_per_layer(c, B, L);
+        const ov_block_saved sv = block_saved_at(c, sx, B, L);
+        const int rc = block_backward_partial(&c, &t->blocks[i], sx, &sv, dx, (i > lo || want_dx) ? dx : nullptr, &grads[i - first], B, L,
+                                              workspace, workspace_bytes, stream);
         if (rc) return rc;
     }
     return OV_OK;

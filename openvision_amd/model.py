@@ -583,6 +583,24 @@ class VisionTransformer(nn.Module):
         return self._pk.get((self.conv1.weight, self.class_embedding, self.positional_embedding, self.ln_post.weight,
                              self.ln_post.bias, self.proj), build)
 
+    def lock(self, unlocked_groups: int = 0, freeze_bn_stats: bool = False) -> None:
+        """LiT locking (transformer.py:542-572): freeze the whole tower, then train again the last ``unlocked_groups`` of its
+        parameter groups (``_lock_groups``).  ``freeze_bn_stats`` is accepted and has no effect, as in the reference (there is no
+        BatchNorm).  Frozen parameters get no gradient from ``openvision_amd.training``, which then skips their work."""
+        self.requires_grad_(False)
+        if unlocked_groups:
+            for group in self._lock_groups()[-unlocked_groups:]:
+                for p in group:
+                    p.requires_grad_(True)
+
+    def _lock_groups(self):
+        """Parameters of the locking groups, input side first: the patch embedding with class / positional embeddings and ln_pre,
+        one group per block, the last block together with ln_post, and the output projection."""
+        blocks = list(self.transformer.resblocks)
+        embed = [*self.conv1.parameters(), self.class_embedding, self.positional_embedding, *self.ln_pre.parameters()]
+        top = [*blocks[-1].parameters(), *self.ln_post.parameters()]
+        return [embed] + [list(b.parameters()) for b in blocks[:-1]] + [top, [self.proj]]
+
     def _check_image(self, x: torch.Tensor):
         _require_cuda(x, "VisionTransformer")
         if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != self.image_size[0] or x.shape[3] != self.image_size[1]:
@@ -821,8 +839,10 @@ class CLIP(nn.Module):
         invalidate_packed()          # copy_ under no_grad bumps _version today; do not depend on it
         return out
 
-    def lock_image_tower(self, *a, **k):
-        raise NotImplementedError("not provided: the training path (openvision_amd.training) differentiates every parameter")
+    def lock_image_tower(self, unlocked_groups: int = 0, freeze_bn_stats: bool = False) -> None:
+        """Lock the image tower as per LiT (model.py:256-258 of the reference); see ``VisionTransformer.lock``.  Build the optimiser
+        afterwards: ``FusedAdamW`` collects the parameters that require grad when it is constructed."""
+        self.visual.lock(unlocked_groups=unlocked_groups, freeze_bn_stats=freeze_bn_stats)
 
     def set_grad_checkpointing(self, enable=True):
         if enable:

@@ -118,7 +118,13 @@ def _packed_blocks(transformer, params, mlp: int, mlp_pad: int, span=(0, -1)):
 
 class _TowerFn(torch.autograd.Function):
     """Transformer.forward (transformer.py:355-366) as one autograd node over the blocks [lo, hi) (all of them by default; several
-    consecutive nodes when ``tower_forward`` is asked for chunks, so that parameter gradients become available chunk by chunk)."""
+    consecutive nodes when ``tower_forward`` is asked for chunks, so that parameter gradients become available chunk by chunk).
+
+    Frozen parameters (``requires_grad=False``: ``lock_image_tower``, a frozen text tower under gradient ascent) are honoured per
+    (weight, bias) pair of a block: a pair is frozen when both of its tensors are.  When x needs no gradient either, the blocks below
+    the lowest trainable one run without keeping anything (``ov_tower_forward_saving_from``) and the backward stops at that block
+    (``ov_tower_backward_partial``); frozen blocks above it run input-only.  Every gradient that is computed is bitwise the one of
+    the all-trainable path; with everything trainable the node makes exactly that path's calls."""
 
     @staticmethod
     def forward(ctx, transformer, lo, hi, x, *params):
@@ -129,27 +135,42 @@ class _TowerFn(torch.autograd.Function):
         if d % 64 or d % heads or (d // heads) % 8 or d // heads > 96:
             raise _lib.OvhipError("training path: width % 64 == 0 and head_dim % 8 == 0, <= 96 are required")
         bsz, seq, _ = x.shape
+        need_x, need_p = ctx.needs_input_grad[3], ctx.needs_input_grad[4:]
+        pairs = [[need_p[12 * i + 2 * k] or need_p[12 * i + 2 * k + 1] for k in range(6)] for i in range(len(blocks))]
+        every = need_x and all(need_p)
+        first = 0 if need_x else next((i for i, pr in enumerate(pairs) if any(pr)), len(blocks))
         cfg = _lib.TowerCfg(d, len(blocks), heads, mlp, mlp_pad, int(b0.gelu_tanh), float(b0.ln_1.eps))
         handle = lib.ov_tower_create(C.byref(cfg))
         if not handle:
             raise _lib.OvhipError("ov_tower_create failed")
         pool = _train_state(transformer)["pool"]
+        saved = None
         try:
             keep = _packed_blocks(transformer, params, mlp, mlp_pad, (lo, hi))
             for i, ts in enumerate(keep):
                 bw = _lib.BlockWeights(*[C.c_void_p(t.data_ptr()) for t in ts], None, None)
                 check(lib.ov_tower_set_block(handle, i, C.byref(bw)), "ov_tower_set_block")
             xb = x.detach().to(torch.bfloat16).contiguous().clone()
-            saved = pool.take(lib.ov_tower_saved_bytes(handle, bsz, seq), x.device, "saved")
-            nbytes = lib.ov_tower_workspace_bytes(handle, bsz, seq)
-            ws = pool.take(nbytes, x.device)
-            check(lib.ov_tower_forward_saving(handle, ptr(xb), ptr(saved), bsz, seq, ptr(ws), nbytes, stream_ptr()),
-                  "ov_tower_forward_saving")
-            pool.give(ws)
+            if every:
+                saved = pool.take(lib.ov_tower_saved_bytes(handle, bsz, seq), x.device, "saved")
+                nbytes = lib.ov_tower_workspace_bytes(handle, bsz, seq)
+                ws = pool.take(nbytes, x.device)
+                check(lib.ov_tower_forward_saving(handle, ptr(xb), ptr(saved), bsz, seq, ptr(ws), nbytes, stream_ptr()),
+                      "ov_tower_forward_saving")
+            else:
+                if first < len(blocks):
+                    saved = pool.take(lib.ov_tower_saved_bytes_from(handle, first, bsz, seq), x.device, "saved")
+                nbytes = lib.ov_tower_forward_saving_from_workspace_bytes(handle, first, bsz, seq)
+                ws = pool.take(nbytes, x.device) if nbytes else None
+                check(lib.ov_tower_forward_saving_from(handle, first, ptr(xb), ptr(saved), bsz, seq, ptr(ws), nbytes, stream_ptr()),
+                      "ov_tower_forward_saving_from")
+            if ws is not None:
+                pool.give(ws)
         finally:
             lib.ov_tower_destroy(handle)
         ctx.cfg, ctx.keep, ctx.saved, ctx.shape, ctx.mlp, ctx.pool = cfg, keep, saved, (bsz, seq, d), mlp, pool
-        ctx.saved_gen = saved._ovhip_gen
+        ctx.every, ctx.first, ctx.pairs, ctx.need = every, first, pairs, (need_x, need_p)
+        ctx.saved_gen = saved._ovhip_gen if saved is not None else None
         ctx.x_dtype, ctx.p_dtypes = x.dtype, [p.dtype for p in params]
         return xb.to(x.dtype)
 
@@ -158,30 +179,47 @@ class _TowerFn(torch.autograd.Function):
         lib = _lib.load()
         bsz, seq, d = ctx.shape
         layers = len(ctx.keep)
-        if ctx.saved._ovhip_gen != ctx.saved_gen:
+        if ctx.saved is None or ctx.saved._ovhip_gen != ctx.saved_gen:
             raise _lib.OvhipError("training path: the saved activations of this graph were recycled by a later forward; a second "
                                   "backward over the same graph must come before the next forward of this tower")
+        need_x, need_p = ctx.need
+        first = ctx.first
         handle = lib.ov_tower_create(C.byref(ctx.cfg))
         try:
             for i, ts in enumerate(ctx.keep):
                 bw = _lib.BlockWeights(*[C.c_void_p(t.data_ptr()) for t in ts], None, None)
                 check(lib.ov_tower_set_block(handle, i, C.byref(bw)), "ov_tower_set_block")
-            grads = [[torch.empty_like(t) for t in ts] for ts in ctx.keep]
-            garr = (_lib.BlockGrads * layers)(*[_lib.BlockGrads(*[C.c_void_p(t.data_ptr()) for t in g]) for g in grads])
             dx = grad_out.detach().to(torch.bfloat16).contiguous().clone()
-            nbytes = lib.ov_tower_backward_workspace_bytes(handle, bsz, seq)
-            ws = ctx.pool.take(nbytes, dx.device)
-            check(lib.ov_tower_backward(handle, ptr(ctx.saved), ptr(dx), garr, bsz, seq, ptr(ws), nbytes, stream_ptr()),
-                  "ov_tower_backward")
+            if ctx.every:
+                grads = [[torch.empty_like(t) for t in ts] for ts in ctx.keep]
+                garr = (_lib.BlockGrads * layers)(*[_lib.BlockGrads(*[C.c_void_p(t.data_ptr()) for t in g]) for g in grads])
+                nbytes = lib.ov_tower_backward_workspace_bytes(handle, bsz, seq)
+                ws = ctx.pool.take(nbytes, dx.device)
+                check(lib.ov_tower_backward(handle, ptr(ctx.saved), ptr(dx), garr, bsz, seq, ptr(ws), nbytes, stream_ptr()),
+                      "ov_tower_backward")
+            else:                     # frozen pairs: NULL in ov_block_grads, no buffers, no work
+                grads = [[None] * 12 for _ in range(first)]
+                grads += [[torch.empty_like(t) if ctx.pairs[i][j // 2] else None for j, t in enumerate(ctx.keep[i])]
+                          for i in range(first, layers)]
+                garr = (_lib.BlockGrads * (layers - first))(*[_lib.BlockGrads(*[ptr(t) for t in g]) for g in grads[first:]])
+                nbytes = lib.ov_tower_backward_partial_workspace_bytes(handle, bsz, seq)
+                ws = ctx.pool.take(nbytes, dx.device)
+                check(lib.ov_tower_backward_partial(handle, first, ptr(ctx.saved), ptr(dx), garr, int(need_x), bsz, seq, ptr(ws), nbytes,
+                                                    stream_ptr()), "ov_tower_backward_partial")
             ctx.pool.give(ws)
             ctx.pool.give(ctx.saved)         # ordered on the stream: the next forward's writes come after this backward's reads
         finally:
             lib.ov_tower_destroy(handle)
         mlp = ctx.mlp                                             # drop the (exactly zero) gradients of the MLP padding
         for gs in grads:
-            gs[8], gs[9], gs[10] = gs[8][:mlp], gs[9][:mlp], gs[10][:, :mlp]
-        flat = [g.to(ctx.p_dtypes[12 * i + j]) for i, gs in enumerate(grads) for j, g in enumerate(gs)]
-        return (None, None, None, dx.view(bsz, seq, d).to(ctx.x_dtype), *flat)
+            if gs[8] is not None:
+                gs[8], gs[9] = gs[8][:mlp], gs[9][:mlp]
+            if gs[10] is not None:
+                gs[10] = gs[10][:, :mlp]
+        # the frozen half of a mixed pair was computed with its partner and is dropped here
+        flat = [g.to(ctx.p_dtypes[12 * i + j]) if g is not None and need_p[12 * i + j] else None
+                for i, gs in enumerate(grads) for j, g in enumerate(gs)]
+        return (None, None, None, dx.view(bsz, seq, d).to(ctx.x_dtype) if need_x else None, *flat)
 
 
 def _round_up(x: int, m: int) -> int:

@@ -147,6 +147,28 @@ int ov_attention_lse(const ov_bf16* qkv, int64_t ld_qkv, ov_bf16* out, int64_t l
 int ov_im2col_patches(const void* image, int img_dtype, ov_bf16* out, int B, int S, int P, int Kpad,
                       ov_stream_t stream);
 
+/* ---- patch dropout (PatchDropout, transformer.py:49-86): image b keeps the G = g*g patches keep[b, 0..K-1] (int32, in that order).
+ * ov_im2col_patches on the kept patches only: out[b*K + j, :] = the operand row of patch keep[b, j] (bitwise ov_im2col_patches' row).
+ * Indices are expected in [0, G) (ov_patch_keep_inverse checks them); any other index is clamped.  1 <= K <= G. */
+int ov_im2col_patches_keep(const void* image, int img_dtype, const int* keep, ov_bf16* out, int B, int S, int P, int K, int Kpad,
+                           ov_stream_t stream);
+/* inv[b, p] = j where keep[b, j] = p, -1 for a dropped patch (int32 [B, G]).  A duplicate or an index outside [0, G) sets *err_flag
+ * (device int, may be NULL) to 1.  1 <= K <= G <= 16384. */
+int ov_patch_keep_inverse(const int* keep, int* inv, int B, int K, int G, int* err_flag, ov_stream_t stream);
+/* The training path's token assembly, fp32 [B, 1+K, D]:  x[b, 0] = cls + pos[0],  x[b, 1+j] = y[b*K + j] + pos[1 + keep[b, j]]
+ * (y bf16 rows of the patch GEMM, cls fp32 [D], pos fp32 [1+G, D]; one fp32 add per element).  D % 8 == 0. */
+int ov_patch_keep_assemble(const ov_bf16* y, int64_t ldy, const float* cls, const float* pos, const int* keep, float* x, int B, int K,
+                           int G, int D, ov_stream_t stream);
+/* Its backward from dx fp32 [B, 1+K, D]:  dpos[p] (fp32 [1+G, D]) = sum over b = 0..B-1, in that order, of the row p fed (exactly 0 for
+ * a patch no image kept), dcls = dpos[0] (fp32 [D]); dy[b*K + j] = bf16(dx[b, 1+j]).  Deterministic (no atomics).  dpos / dcls / dy
+ * may be NULL (skipped). */
+int ov_patch_keep_assemble_backward(const float* dx, const int* inv, int B, int K, int G, int D, float* dpos, float* dcls, ov_bf16* dy,
+                                    int64_t lddy, ov_stream_t stream);
+/* Pixel gradient of ov_im2col_patches_keep: dimg [B,3,S,S] (img_dtype) = the kept patches' rows of dcols [B*K, ldc] (bf16) put back,
+ * 0 in dropped patches (stride = kernel: a permutation, no sums).  S % 4 == 0. */
+int ov_col2im_patches_keep(const ov_bf16* dcols, int64_t ldc, const int* inv, void* dimg, int img_dtype, int B, int S, int P, int K,
+                           ov_stream_t stream);
+
 /* x[b*L + 0, :] = bf16(bf16(cls[:]) + bf16(pos[0,:]))  for every image b. cls/pos fp32. */
 int ov_cls_rows(ov_bf16* x, int64_t ldx, const float* cls, const float* pos0, int B, int L, int D,
                 ov_stream_t stream);
@@ -516,6 +538,19 @@ int ov_vision_head_forward(const ov_tower* t, const ov_vision_head* h, const ov_
 int ov_encode_image(const ov_tower* t, const ov_vision_head* h, const void* image, int img_dtype, int B,
                     float* features, int normalize, void* workspace, size_t workspace_bytes,
                     ov_stream_t stream);
+/* ov_vision_head_forward on tokens x[B*L, D] with L given (patch dropout: L = 1 + K). */
+int ov_vision_head_forward_tokens(const ov_tower* t, const ov_vision_head* h, const ov_bf16* x, int B, int L,
+                                  float* features, int normalize, void* workspace, size_t workspace_bytes,
+                                  ov_stream_t stream);
+/* Patch dropout (transformer.py:619): the same at L' = 1 + K tokens, image b keeping the patches keep[b, 0..K-1] (int32 [B, K], in
+ * that order; see ov_im2col_patches_keep).  Kept tokens are bitwise the matching tokens of ov_vision_embed.  *err_flag (device int,
+ * may be NULL) is set when an index lies outside [0, G).  1 <= K <= G, else OV_ERR_INVALID. */
+size_t ov_vision_keep_workspace_bytes(const ov_tower* t, const ov_vision_head* h, int B, int K);
+int ov_vision_embed_keep(const ov_tower* t, const ov_vision_head* h, const void* image, int img_dtype, const int* keep, int B,
+                         int K, ov_bf16* x, int* err_flag, void* workspace, size_t workspace_bytes, ov_stream_t stream);
+int ov_encode_image_keep(const ov_tower* t, const ov_vision_head* h, const void* image, int img_dtype, const int* keep, int B,
+                         int K, float* features, int normalize, int* err_flag, void* workspace, size_t workspace_bytes,
+                         ov_stream_t stream);
 
 typedef struct {      /* CLIP text front/back ends */
     int context_length, vocab_size;

@@ -87,6 +87,12 @@ SIGNATURES = {
                                  c_void_p, c_void_p]),
     "ov_attention": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_float, c_void_p]),
     "ov_im2col_patches": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "ov_im2col_patches_keep": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "ov_patch_keep_inverse": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "ov_patch_keep_assemble": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "ov_patch_keep_assemble_backward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64,
+                                                c_void_p]),
+    "ov_col2im_patches_keep": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "ov_cls_rows": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "ov_mean_pool": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "ov_text_embed": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p,
@@ -168,6 +174,13 @@ SIGNATURES = {
                                        c_size_t, c_void_p]),
     "ov_encode_image": (c_int, [c_void_p, C.POINTER(VisionHead), c_void_p, c_int, c_int, c_void_p, c_int, c_void_p,
                                 c_size_t, c_void_p]),
+    "ov_vision_head_forward_tokens": (c_int, [c_void_p, C.POINTER(VisionHead), c_void_p, c_int, c_int, c_void_p, c_int, c_void_p,
+                                              c_size_t, c_void_p]),
+    "ov_vision_keep_workspace_bytes": (c_size_t, [c_void_p, C.POINTER(VisionHead), c_int, c_int]),
+    "ov_vision_embed_keep": (c_int, [c_void_p, C.POINTER(VisionHead), c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                     c_void_p, c_size_t, c_void_p]),
+    "ov_encode_image_keep": (c_int, [c_void_p, C.POINTER(VisionHead), c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int,
+                                     c_void_p, c_void_p, c_size_t, c_void_p]),
     "ov_text_workspace_bytes": (c_size_t, [c_void_p, C.POINTER(TextHead), c_int]),
     "ov_encode_text": (c_int, [c_void_p, C.POINTER(TextHead), c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
                                c_size_t, c_void_p]),

@@ -76,9 +76,11 @@ def _from_dict(cls, d: Union[dict, Any]):
 
 def vision_cfg_from(d) -> CLIPVisionCfg:
     c = _from_dict(CLIPVisionCfg, d)
-    if c.timm_model_name or c.attentional_pool or c.ls_init_value is not None or c.patch_dropout:
+    if c.timm_model_name or c.attentional_pool or c.ls_init_value is not None:
         raise ValueError("vision_cfg selects a tower outside the OpenVision ViT path "
-                         "(timm / attentional pool / layer-scale / patch-dropout)")
+                         "(timm / attentional pool / layer-scale)")
+    if not 0 <= float(c.patch_dropout) < 1:                      # PatchDropout's own assertion (transformer.py:56)
+        raise ValueError(f"vision patch_dropout must lie in [0, 1), got {c.patch_dropout!r}")
     if c.pool_type not in ("avg", "tok"):
         raise ValueError(f"vision pool_type {c.pool_type!r} not supported (OpenVision uses 'avg')")
     if c.width % c.head_width:

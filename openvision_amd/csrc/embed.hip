@@ -7,38 +7,211 @@
 //   ov_gather_rows     text_global_pool 'last' / 'first'                  transformer.py:655-658
 //   ov_convert         dtype casts (.to(cast_dtype))
 //   ov_l2norm          F.normalize(x, dim=-1)                             model.py:267,284
+// Patch dropout (PatchDropout, transformer.py:49-86: the image keeps K of its G patch tokens, in the order of keep[b, :]):
+//   ov_im2col_patches_keep         the conv1 operand rows of the kept patches only (+ their pos-emb rows, for ov_vision_embed_keep)
+//   ov_patch_keep_inverse          keep [B, K] -> inv [B, G] (j or -1), duplicate / out-of-range indices raise a device flag
+//   ov_patch_keep_assemble         fp32 tokens [B, 1+K, D]: cls + pos[0], then patch rows + pos[1 + keep]
+//   ov_patch_keep_assemble_backward  dpos / dcls as fixed-order sums over the batch (no atomics), dY rows of the patch GEMM
+//   ov_col2im_patches_keep         pixel gradient: kept patches' rows back into the image, dropped patches 0
 // All are 16-byte-per-lane streaming kernels; none re-reads its input.
 #include "common.h"
 
 namespace {
+
+// columns ch*8 .. ch*8+7 of the conv1 operand row of patch (py, px) of image b: (c, ii, jj) order of the weight's flattening,
+// zero past 3 P^2, rounded to bf16 once
+template <bool IMG_F32>
+__device__ __forceinline__ u32x4_t im2col_chunk(const void* __restrict__ img, int b, int py, int px, int ch, int S, int P) {
+    const int PP = P * P, K = 3 * PP;
+    float v[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const int k = ch * 8 + e;
+        float x = 0.f;
+        if (k < K) {
+            const int c = k / PP, rem = k - c * PP;
+            const int ii = rem / P, jj = rem - ii * P;
+            const int64_t src = (((int64_t)b * 3 + c) * S + (py * P + ii)) * S + (px * P + jj);
+            x = IMG_F32 ? ((const float*)img)[src] : bf16_bits_to_f32(((const ov_bf16*)img)[src]);
+        }
+        v[e] = x;
+    }
+    return u32x4_t{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7])};
+}
 
 template <bool IMG_F32>
 __global__ __launch_bounds__(256) void im2col_kernel(const void* __restrict__ img, ov_bf16* __restrict__ out,
                                                      int B, int S, int P, int g, int Kpad, int64_t total) {
     // one thread per 8 output columns
     const int cpr = Kpad >> 3;
-    const int PP = P * P, K = 3 * PP;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
         const int64_t row = i / cpr;
         const int ch = (int)(i - row * cpr);
         const int b = (int)(row / (g * g));
         const int pr = (int)(row - (int64_t)b * g * g);
         const int py = pr / g, px = pr - py * g;
-        float v[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const int k = ch * 8 + e;
-            float x = 0.f;
-            if (k < K) {
-                const int c = k / PP, rem = k - c * PP;
-                const int ii = rem / P, jj = rem - ii * P;
-                const int64_t src = (((int64_t)b * 3 + c) * S + (py * P + ii)) * S + (px * P + jj);
-                x = IMG_F32 ? ((const float*)img)[src] : bf16_bits_to_f32(((const ov_bf16*)img)[src]);
-            }
-            v[e] = x;
+        *(u32x4_t*)(out + row * Kpad + ch * 8) = im2col_chunk<IMG_F32>(img, b, py, px, ch, S, P);
+    }
+}
+
+// keep index of output row `row` (= b * K + j), clamped into [0, G) so that no read leaves the image; an index outside it raises *err
+__device__ __forceinline__ int keep_index(const int* __restrict__ keep, int64_t row, int G, int* __restrict__ err) {
+    int id = keep[row];
+    if (id < 0 || id >= G) {
+        if (err) *err = 1;
+        id = id < 0 ? 0 : G - 1;
+    }
+    return id;
+}
+
+// Work items [0, ncols): one per 8 operand columns of a kept row (im2col_kernel's arithmetic); [ncols, total): one per 8 columns of the
+// kept row's positional-embedding row pos[1 + keep[b, j]] (bf16, for the patch GEMM's residual epilogue), when posk is given.
+template <bool IMG_F32>
+__global__ __launch_bounds__(256) void im2col_keep_kernel(const void* __restrict__ img, const int* __restrict__ keep, ov_bf16* __restrict__ out,
+                                                          const ov_bf16* __restrict__ pos, ov_bf16* __restrict__ posk, int S, int P, int g,
+                                                          int K, int Kpad, int D, int* __restrict__ err, int64_t ncols, int64_t total) {
+    const int cpr = Kpad >> 3, dpr = D >> 3, G = g * g;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        if (i < ncols) {
+            const int64_t row = i / cpr;
+            const int ch = (int)(i - row * cpr);
+            const int b = (int)(row / K);
+            const int id = keep_index(keep, row, G, err);
+            const int py = id / g, px = id - py * g;
+            *(u32x4_t*)(out + row * Kpad + ch * 8) = im2col_chunk<IMG_F32>(img, b, py, px, ch, S, P);
+        } else {
+            const int64_t k = i - ncols;
+            const int64_t row = k / dpr;
+            const int ch = (int)(k - row * dpr);
+            const int id = keep_index(keep, row, G, nullptr);
+            *(u32x4_t*)(posk + row * D + ch * 8) = *(const u32x4_t*)(pos + (int64_t)(1 + id) * D + ch * 8);
         }
-        u32x4_t w = {pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7])};
-        *(u32x4_t*)(out + row * Kpad + ch * 8) = w;
+    }
+}
+
+// One workgroup per image: inv[b, keep[b, j]] = j, -1 where no j points.  A duplicate leaves one of its writers unconfirmed in the
+// second pass; both cases raise *err.
+__global__ __launch_bounds__(256) void keep_inverse_kernel(const int* __restrict__ keep, int* __restrict__ inv, int K, int G,
+                                                           int* __restrict__ err) {
+    extern __shared__ int sinv[];
+    const int b = blockIdx.x;
+    const int* kb = keep + (int64_t)b * K;
+    int bad = 0;
+    for (int t = threadIdx.x; t < G; t += blockDim.x) sinv[t] = -1;
+    __syncthreads();
+    for (int j = threadIdx.x; j < K; j += blockDim.x) {
+        const int id = kb[j];
+        if (id >= 0 && id < G) sinv[id] = j;
+        else bad = 1;
+    }
+    __syncthreads();
+    for (int j = threadIdx.x; j < K; j += blockDim.x) {
+        const int id = kb[j];
+        if (id >= 0 && id < G && sinv[id] != j) bad = 1;
+    }
+    for (int t = threadIdx.x; t < G; t += blockDim.x) inv[(int64_t)b * G + t] = sinv[t];
+    if (bad && err) *err = 1;
+}
+
+// x[b, 0] = cls + pos[0], x[b, 1 + j] = y[b * K + j] + pos[1 + keep[b, j]]: one fp32 add per element (what
+// torch.cat([cls, y]) + pos computes); one thread per 8 columns of an output row
+__global__ __launch_bounds__(256) void keep_assemble_kernel(const ov_bf16* __restrict__ y, int64_t ldy, const float* __restrict__ cls,
+                                                            const float* __restrict__ pos, const int* __restrict__ keep, float* __restrict__ x,
+                                                            int K, int G, int D, int64_t total) {
+    const int dpr = D >> 3, L = K + 1;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t row = i / dpr;
+        const int ch = (int)(i - row * dpr);
+        const int64_t b = row / L;
+        const int t = (int)(row - b * L);
+        float v[8];
+        if (t == 0) {
+            const float4 c0 = *(const float4*)(cls + ch * 8), c1 = *(const float4*)(cls + ch * 8 + 4);
+            const float4 p0 = *(const float4*)(pos + ch * 8), p1 = *(const float4*)(pos + ch * 8 + 4);
+            v[0] = c0.x + p0.x; v[1] = c0.y + p0.y; v[2] = c0.z + p0.z; v[3] = c0.w + p0.w;
+            v[4] = c1.x + p1.x; v[5] = c1.y + p1.y; v[6] = c1.z + p1.z; v[7] = c1.w + p1.w;
+        } else {
+            const int64_t r = b * K + (t - 1);
+            const int id = keep_index(keep, r, G, nullptr);
+            const u32x4_t w = *(const u32x4_t*)(y + r * ldy + ch * 8);
+            const float* pr = pos + (int64_t)(1 + id) * D + ch * 8;
+            const float4 p0 = *(const float4*)pr, p1 = *(const float4*)(pr + 4);
+            v[0] = bf16lo_to_f32(w[0]) + p0.x; v[1] = bf16hi_to_f32(w[0]) + p0.y;
+            v[2] = bf16lo_to_f32(w[1]) + p0.z; v[3] = bf16hi_to_f32(w[1]) + p0.w;
+            v[4] = bf16lo_to_f32(w[2]) + p1.x; v[5] = bf16hi_to_f32(w[2]) + p1.y;
+            v[6] = bf16lo_to_f32(w[3]) + p1.z; v[7] = bf16hi_to_f32(w[3]) + p1.w;
+        }
+        float4* q = (float4*)(x + row * D + ch * 8);
+        q[0] = make_float4(v[0], v[1], v[2], v[3]);
+        q[1] = make_float4(v[4], v[5], v[6], v[7]);
+    }
+}
+
+// Work items [0, npos): one per 4 columns of a positional row p in [0, 1 + G): dpos[p] = sum over b = 0, 1, ..., B-1 (in that order)
+// of the gradient row that p fed (row 0 for p = 0, row 1 + inv[b, p - 1] when that patch was kept); exactly 0 when no image kept it.
+// dcls = dpos[0].  [npos, total): one per 8 columns of a kept row: dy[b * K + j] = bf16(dx[b, 1 + j]) (the patch GEMM's output gradient).
+__global__ __launch_bounds__(256) void keep_assemble_bwd_kernel(const float* __restrict__ dx, const int* __restrict__ inv, int B, int K, int G,
+                                                                int D, float* __restrict__ dpos, float* __restrict__ dcls,
+                                                                ov_bf16* __restrict__ dy, int64_t lddy, int64_t npos, int64_t total) {
+    const int L = K + 1;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        if (i < npos) {
+            const int qpr = D >> 2;
+            const int p = (int)(i / qpr);
+            const int c = (int)(i - (int64_t)p * qpr) * 4;
+            float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll 4
+            for (int b = 0; b < B; ++b) {
+                const int t = p == 0 ? 0 : 1 + inv[(int64_t)b * G + p - 1];
+                if (t > 0 || p == 0) {
+                    const float4 g = *(const float4*)(dx + ((int64_t)b * L + t) * D + c);
+                    acc.x += g.x; acc.y += g.y; acc.z += g.z; acc.w += g.w;
+                }
+            }
+            if (dpos) *(float4*)(dpos + (int64_t)p * D + c) = acc;
+            if (p == 0 && dcls) *(float4*)(dcls + c) = acc;
+        } else {
+            const int dpr = D >> 3;
+            const int64_t k = i - npos;
+            const int64_t r = k / dpr;
+            const int ch = (int)(k - r * dpr);
+            const int64_t b = r / K;
+            const float* src = dx + (b * L + 1 + (r - b * K)) * D + ch * 8;
+            const float4 g0 = *(const float4*)src, g1 = *(const float4*)(src + 4);
+            *(u32x4_t*)(dy + r * lddy + ch * 8) =
+                u32x4_t{pack_bf16x2(g0.x, g0.y), pack_bf16x2(g0.z, g0.w), pack_bf16x2(g1.x, g1.y), pack_bf16x2(g1.z, g1.w)};
+        }
+    }
+}
+
+// Pixel gradient of the kept-patch im2col (stride = kernel: every pixel belongs to exactly one patch, so a pure gather, no sums):
+// one thread per 4 consecutive pixels of an image row, dimg [B, 3, S, S] fp32 (16-byte stores) or bf16 (8-byte stores).
+template <bool OUT_F32>
+__global__ __launch_bounds__(256) void col2im_keep_kernel(const ov_bf16* __restrict__ dcols, int64_t ldc, const int* __restrict__ inv,
+                                                          void* __restrict__ dimg, int S, int P, int g, int K, int64_t total) {
+    const int G = g * g, PP = P * P;
+    const int qpr = S >> 2;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t line = i / qpr;                 // (b, c, y)
+        const int x0 = (int)(i - line * qpr) * 4;
+        const int y = (int)(line % S);
+        const int64_t bc = line / S;
+        const int c = (int)(bc % 3);
+        const int64_t b = bc / 3;
+        const int py = y / P, ii = y - py * P;
+        float v[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int xx = x0 + e;
+            const int px = xx / P, jj = xx - px * P;
+            const int j = inv[b * G + py * g + px];
+            v[e] = j >= 0 ? bf16_bits_to_f32(dcols[(b * K + j) * ldc + c * PP + ii * P + jj]) : 0.f;
+        }
+        if (OUT_F32) {
+            *(float4*)((float*)dimg + i * 4) = make_float4(v[0], v[1], v[2], v[3]);
+        } else {
+            *(u32x2_t*)((ov_bf16*)dimg + i * 4) = u32x2_t{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
+        }
     }
 }
 
@@ -158,7 +331,35 @@ inline unsigned grid_for(int64_t total, int block) {
     return (unsigned)g;
 }
 
+int im2col_keep_launch(const void* image, int img_dtype, const int* keep, ov_bf16* out, int B, int S, int P, int K, int Kpad,
+                       const ov_bf16* pos, ov_bf16* posk, int D, int* err_flag, hipStream_t st) {
+    if (!image || !keep || !out || B <= 0 || S <= 0 || P <= 0) return OV_ERR_INVALID;
+    if (S % P || Kpad % 8 || Kpad < 3 * P * P || ((uintptr_t)out & 15)) return OV_ERR_INVALID;
+    const int g = S / P;
+    if (K < 1 || K > g * g) return OV_ERR_INVALID;
+    if (posk && (!pos || D <= 0 || D % 8 || (((uintptr_t)pos | (uintptr_t)posk) & 15))) return OV_ERR_INVALID;
+    const int64_t ncols = (int64_t)B * K * (Kpad / 8);
+    const int64_t total = ncols + (posk ? (int64_t)B * K * (D / 8) : 0);
+    if (img_dtype == OV_F32)
+        hipLaunchKernelGGL(im2col_keep_kernel<true>, dim3(grid_for(total, 256)), dim3(256), 0, st, image, keep, out, pos, posk, S, P, g, K,
+                           Kpad, D, err_flag, ncols, total);
+    else if (img_dtype == OV_BF16)
+        hipLaunchKernelGGL(im2col_keep_kernel<false>, dim3(grid_for(total, 256)), dim3(256), 0, st, image, keep, out, pos, posk, S, P, g, K,
+                           Kpad, D, err_flag, ncols, total);
+    else
+        return OV_ERR_INVALID;
+    OV_LAUNCH_CHECK();
+    return OV_OK;
+}
+
 }  // namespace
+
+// ov_im2col_patches_keep with the kept rows' positional-embedding rows gathered in the same launch (ov_vision_embed_keep)
+int ov_im2col_patches_keep_pos(const void* image, int img_dtype, const int* keep, ov_bf16* out, int B, int S, int P, int K, int Kpad,
+                               const ov_bf16* pos, ov_bf16* posk, int D, int* err_flag, ov_stream_t stream) {
+    if (!posk) return OV_ERR_INVALID;
+    return im2col_keep_launch(image, img_dtype, keep, out, B, S, P, K, Kpad, pos, posk, D, err_flag, (hipStream_t)stream);
+}
 
 extern "C" int ov_im2col_patches(const void* image, int img_dtype, ov_bf16* out, int B, int S, int P, int Kpad,
                                  ov_stream_t stream) {
@@ -246,6 +447,64 @@ extern "C" int ov_l2norm(const void* x, int x_dtype, int64_t ldx, float* y, int6
         hipLaunchKernelGGL(l2norm_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, x, ldx, y, ldy, rows, E);
     else if (x_dtype == OV_BF16)
         hipLaunchKernelGGL(l2norm_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, x, ldx, y, ldy, rows, E);
+    else
+        return OV_ERR_INVALID;
+    OV_LAUNCH_CHECK();
+    return OV_OK;
+}
+
+extern "C" int ov_im2col_patches_keep(const void* image, int img_dtype, const int* keep, ov_bf16* out, int B, int S, int P, int K, int Kpad,
+                                      ov_stream_t stream) {
+    return im2col_keep_launch(image, img_dtype, keep, out, B, S, P, K, Kpad, nullptr, nullptr, 0, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int ov_patch_keep_inverse(const int* keep, int* inv, int B, int K, int G, int* err_flag, ov_stream_t stream) {
+    if (!keep || !inv || B <= 0 || G <= 0 || K < 1 || K > G) return OV_ERR_INVALID;
+    if (G > 16384) return OV_ERR_UNSUPPORTED;                 // the map of one image lives in LDS
+    hipLaunchKernelGGL(keep_inverse_kernel, dim3((unsigned)B), dim3(256), (size_t)G * sizeof(int), (hipStream_t)stream, keep, inv, K, G,
+                       err_flag);
+    OV_LAUNCH_CHECK();
+    return OV_OK;
+}
+
+extern "C" int ov_patch_keep_assemble(const ov_bf16* y, int64_t ldy, const float* cls, const float* pos, const int* keep, float* x, int B,
+                                      int K, int G, int D, ov_stream_t stream) {
+    if (!y || !cls || !pos || !keep || !x || B <= 0 || G <= 0 || K < 1 || K > G || D <= 0) return OV_ERR_INVALID;
+    if (D % 8 || ldy % 8 || ldy < D || (((uintptr_t)y | (uintptr_t)cls | (uintptr_t)pos | (uintptr_t)x) & 15)) return OV_ERR_INVALID;
+    const int64_t total = (int64_t)B * (K + 1) * (D / 8);
+    hipLaunchKernelGGL(keep_assemble_kernel, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, y, ldy, cls, pos, keep, x, K, G,
+                       D, total);
+    OV_LAUNCH_CHECK();
+    return OV_OK;
+}
+
+extern "C" int ov_patch_keep_assemble_backward(const float* dx, const int* inv, int B, int K, int G, int D, float* dpos, float* dcls,
+                                               ov_bf16* dy, int64_t lddy, ov_stream_t stream) {
+    if (!dx || !inv || B <= 0 || G <= 0 || K < 1 || K > G || D <= 0) return OV_ERR_INVALID;
+    if (D % 8 || (((uintptr_t)dx | (uintptr_t)dpos | (uintptr_t)dcls | (uintptr_t)dy) & 15)) return OV_ERR_INVALID;
+    if (dy && (lddy % 8 || lddy < D)) return OV_ERR_INVALID;
+    const int64_t npos = (dpos || dcls) ? (int64_t)(1 + G) * (D / 4) : 0;
+    const int64_t total = npos + (dy ? (int64_t)B * K * (D / 8) : 0);
+    if (total == 0) return OV_OK;
+    hipLaunchKernelGGL(keep_assemble_bwd_kernel, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, dx, inv, B, K, G, D, dpos,
+                       dcls, dy, lddy, npos, total);
+    OV_LAUNCH_CHECK();
+    return OV_OK;
+}
+
+extern "C" int ov_col2im_patches_keep(const ov_bf16* dcols, int64_t ldc, const int* inv, void* dimg, int img_dtype, int B, int S, int P,
+                                      int K, ov_stream_t stream) {
+    if (!dcols || !inv || !dimg || B <= 0 || S <= 0 || P <= 0) return OV_ERR_INVALID;
+    if (S % P || S % 4 || ldc < 3 * P * P) return OV_ERR_INVALID;
+    const int g = S / P;
+    if (K < 1 || K > g * g) return OV_ERR_INVALID;
+    if (((uintptr_t)dimg & (img_dtype == OV_F32 ? 15 : 7))) return OV_ERR_INVALID;
+    const int64_t total = (int64_t)B * 3 * S * (S / 4);
+    hipStream_t st = (hipStream_t)stream;
+    if (img_dtype == OV_F32)
+        hipLaunchKernelGGL(col2im_keep_kernel<true>, dim3(grid_for(total, 256)), dim3(256), 0, st, dcols, ldc, inv, dimg, S, P, g, K, total);
+    else if (img_dtype == OV_BF16)
+        hipLaunchKernelGGL(col2im_keep_kernel<false>, dim3(grid_for(total, 256)), dim3(256), 0, st, dcols, ldc, inv, dimg, S, P, g, K, total);
     else
         return OV_ERR_INVALID;
     OV_LAUNCH_CHECK();

@@ -4,6 +4,7 @@
 //   ov_vision_embed         conv1 + cls + pos-emb (ln_pre = Identity)              transformer.py:610-620
 //   ov_vision_head_forward  _global_pool -> ln_post -> @ proj (-> F.normalize)     transformer.py:638-646, model.py:267
 //   ov_encode_image         VisionTransformer.forward                              transformer.py:609-651
+//   ov_vision_embed_keep / ov_encode_image_keep   the same with patch dropout: K kept patches per image, L' = 1 + K  transformer.py:619,60-86
 //   ov_encode_text          CLIP.encode_text                                       model.py:269-284
 //
 // Per block, seven launches on the caller's stream (all asynchronous, nothing allocated):
@@ -102,6 +103,23 @@ inline VisionWs vision_ws(const ov_tower* t, const ov_vision_head* h, int B) {
     size_t off = 0;
     w.x = off;      off += align_up((size_t)B * L * D * 2, 256);
     w.tower = off;  off += align_up(ov_tower_workspace_bytes(t, B, L), 256);
+    w.pooled = off; off += align_up((size_t)B * D * 4, 256);
+    w.lnrow = off;  off += align_up((size_t)B * D * 2, 256);
+    w.feat = off;   off += align_up((size_t)B * h->embed_pad * 2, 256);
+    w.total = off;
+    return w;
+}
+// patch dropout: tokens [B, 1 + K, D]; the im2col rows and their pos-emb rows alias the tower workspace until the blocks run
+inline size_t keep_embed_bytes(const ov_tower* t, const ov_vision_head* h, int B, int K) {
+    return align_up((size_t)B * K * h->kpad * 2, 256) + (size_t)B * K * t->cfg.width * 2;
+}
+inline VisionWs vision_keep_ws(const ov_tower* t, const ov_vision_head* h, int B, int K) {
+    const int L = K + 1, D = t->cfg.width;
+    VisionWs w;
+    size_t off = 0;
+    const size_t tower = ov_tower_workspace_bytes(t, B, L), embed = keep_embed_bytes(t, h, B, K);
+    w.x = off;      off += align_up((size_t)B * L * D * 2, 256);
+    w.tower = off;  off += align_up(tower > embed ? tower : embed, 256);
     w.pooled = off; off += align_up((size_t)B * D * 4, 256);
     w.lnrow = off;  off += align_up((size_t)B * D * 2, 256);
     w.feat = off;   off += align_up((size_t)B * h->embed_pad * 2, 256);
@@ -762,8 +780,15 @@ extern "C" int ov_vision_embed(const ov_tower* t, const ov_vision_head* h, const
 
 extern "C" int ov_vision_head_forward(const ov_tower* t, const ov_vision_head* h, const ov_bf16* x, int B, float* features,
                                       int normalize, void* workspace, size_t workspace_bytes, ov_stream_t stream) {
-    if (!t || !h || !x || !features || !workspace || B <= 0) return OV_ERR_INVALID;
-    const int g = h->image_size / h->patch_size, L = g * g + 1, D = t->cfg.width, E = h->embed_dim, EP = h->embed_pad;
+    if (!t || !h || !x || !features || !workspace || B <= 0 || h->patch_size <= 0) return OV_ERR_INVALID;
+    const int g = h->image_size / h->patch_size;
+    return ov_vision_head_forward_tokens(t, h, x, B, g * g + 1, features, normalize, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ov_vision_head_forward_tokens(const ov_tower* t, const ov_vision_head* h, const ov_bf16* x, int B, int L, float* features,
+                                             int normalize, void* workspace, size_t workspace_bytes, ov_stream_t stream) {
+    if (!t || !h || !x || !features || !workspace || B <= 0 || L < 2) return OV_ERR_INVALID;
+    const int D = t->cfg.width, E = h->embed_dim, EP = h->embed_pad;
     if (EP % 8 || EP < E) return OV_ERR_INVALID;
     if (!h->final_ln_after_pool) return OV_ERR_UNSUPPORTED;       // OpenVision: pool -> LN (transformer.py:638-640)
     const size_t o_pooled = 0, o_ln = align_up((size_t)B * D * 4, 256), o_feat = o_ln + align_up((size_t)B * D * 2, 256);
@@ -799,6 +824,53 @@ extern "C" int ov_encode_image(const ov_tower* t, const ov_vision_head* h, const
     if ((rc = ov_vision_embed(t, h, image, img_dtype, B, x, ws + w.tower, tower_bytes, stream))) return rc;
     if ((rc = ov_tower_forward(t, x, B, L, ws + w.tower, tower_bytes, stream))) return rc;
     return ov_vision_head_forward(t, h, x, B, features, normalize, ws + w.pooled, w.total - w.pooled, stream);
+}
+
+int ov_im2col_patches_keep_pos(const void* image, int img_dtype, const int* keep, ov_bf16* out, int B, int S, int P, int K, int Kpad,
+                               const ov_bf16* pos, ov_bf16* posk, int D, int* err_flag, ov_stream_t stream);
+
+extern "C" size_t ov_vision_keep_workspace_bytes(const ov_tower* t, const ov_vision_head* h, int B, int K) {
+    if (!t || !h || B <= 0 || h->patch_size <= 0) return 0;
+    const int g = h->image_size / h->patch_size;
+    if (K < 1 || K > g * g) return 0;
+    return vision_keep_ws(t, h, B, K).total;
+}
+
+extern "C" int ov_vision_embed_keep(const ov_tower* t, const ov_vision_head* h, const void* image, int img_dtype, const int* keep, int B,
+                                    int K, ov_bf16* x, int* err_flag, void* workspace, size_t workspace_bytes, ov_stream_t stream) {
+    if (!t || !h || !image || !keep || !x || !workspace || B <= 0 || h->patch_size <= 0) return OV_ERR_INVALID;
+    const int g = h->image_size / h->patch_size, D = t->cfg.width;
+    if (K < 1 || K > g * g) return OV_ERR_INVALID;
+    if (h->kpad % 64 || h->kpad < 3 * h->patch_size * h->patch_size) return OV_ERR_INVALID;
+    if (workspace_bytes < keep_embed_bytes(t, h, B, K)) return OV_ERR_WORKSPACE;
+    ov_bf16* patches = (ov_bf16*)workspace;
+    ov_bf16* posk = (ov_bf16*)((char*)workspace + align_up((size_t)B * K * h->kpad * 2, 256));
+    int rc;
+    if ((rc = ov_im2col_patches_keep_pos(image, img_dtype, keep, patches, B, h->image_size, h->patch_size, K, h->kpad, h->pos, posk, D,
+                                         err_flag, stream)))
+        return rc;
+    // the GEMM of ov_vision_embed on the kept rows: the epilogue adds the gathered pos-emb rows one to one and skips a cls row per image
+    if ((rc = ov_gemm(patches, h->kpad, h->conv_w, h->kpad, nullptr, x, D, (int64_t)B * K, D, h->kpad, OV_EPI_BIAS_RESIDUAL, posk, D, K, 0,
+                      0, stream)))
+        return rc;
+    return ov_cls_rows(x, D, h->cls, h->pos_f32, B, K + 1, D, stream);
+}
+
+extern "C" int ov_encode_image_keep(const ov_tower* t, const ov_vision_head* h, const void* image, int img_dtype, const int* keep, int B,
+                                    int K, float* features, int normalize, int* err_flag, void* workspace, size_t workspace_bytes,
+                                    ov_stream_t stream) {
+    if (!t || !h || !image || !keep || !features || !workspace || B <= 0 || h->patch_size <= 0) return OV_ERR_INVALID;
+    const int g = h->image_size / h->patch_size;
+    if (K < 1 || K > g * g) return OV_ERR_INVALID;
+    const VisionWs w = vision_keep_ws(t, h, B, K);
+    if (workspace_bytes < w.total) return OV_ERR_WORKSPACE;
+    const int L = K + 1;
+    char* ws = (char*)workspace;
+    ov_bf16* x = (ov_bf16*)(ws + w.x);
+    int rc;
+    if ((rc = ov_vision_embed_keep(t, h, image, img_dtype, keep, B, K, x, err_flag, ws + w.tower, w.pooled - w.tower, stream))) return rc;
+    if ((rc = ov_tower_forward(t, x, B, L, ws + w.tower, w.pooled - w.tower, stream))) return rc;
+    return ov_vision_head_forward_tokens(t, h, x, B, L, features, normalize, ws + w.pooled, w.total - w.pooled, stream);
 }
 
 extern "C" size_t ov_text_workspace_bytes(const ov_tower* t, const ov_text_head* h, int B) {

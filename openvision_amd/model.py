@@ -538,12 +538,65 @@ class Transformer(nn.Module):
         return _run_blocks(list(self.resblocks), x, self._cache, self._ws)
 
 
+class PatchDropout(nn.Module):
+    """PatchDropout (transformer.py:49-86, FLIP arXiv 2212.00794) with ``exclude_first_token=True``, as VisionTransformer builds it: in
+    training mode each image keeps ``K = max(1, int(G * (1 - prob)))`` of its G patch tokens, those of the K largest entries of
+    ``torch.randn(B, G)`` drawn from the CPU default generator, in ``topk`` order, behind its CLS token.  In eval mode nothing is drawn.
+
+    ``sample`` is that draw on its own (int64 [B, K]); the HIP paths of ``VisionTransformer`` / ``CLIP`` / ``training.encode_image`` take
+    it and run the tower on the kept tokens only.  ``forward`` is the reference module on a token tensor [B, 1 + G, D].  No parameters."""
+
+    def __init__(self, prob: float, exclude_first_token: bool = True):
+        super().__init__()
+        if not 0 <= prob < 1.:
+            raise ValueError(f"patch dropout probability must lie in [0, 1), got {prob!r}")
+        if not exclude_first_token:
+            raise NotImplementedError("VisionTransformer always excludes the CLS token from patch dropout")
+        self.prob = float(prob)
+        self.exclude_first_token = exclude_first_token
+
+    def num_keep(self, num_tokens: int) -> int:
+        return max(1, int(num_tokens * (1 - self.prob)))
+
+    def sample(self, batch: int, num_tokens: int) -> torch.Tensor:
+        """The reference's draw: int64 [batch, K] patch indices on the CPU (consumes the CPU default generator)."""
+        rand = torch.randn(batch, num_tokens)
+        return rand.topk(self.num_keep(num_tokens), dim=-1).indices
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if not self.training or self.prob == 0.:
+            return x
+        cls_tokens, x = x[:, :1], x[:, 1:]
+        keep = self.sample(x.shape[0], x.shape[1]).to(x.device)
+        x = x[torch.arange(x.shape[0], device=x.device)[:, None], keep]
+        return torch.cat((cls_tokens, x), dim=1)
+
+
+def check_keep(keep: torch.Tensor, batch: int, num_patches: int) -> None:
+    """Host-side shape check of a patch-keep table [batch, K], 1 <= K <= num_patches (index values are checked on the device)."""
+    if not isinstance(keep, torch.Tensor) or keep.dim() != 2 or keep.shape[0] != batch:
+        raise ValueError(f"keep must be an integer tensor [{batch}, K], got {getattr(keep, 'shape', type(keep))}")
+    if keep.is_floating_point() or keep.is_complex() or keep.dtype == torch.bool:
+        raise ValueError(f"keep must hold integer patch indices, got {keep.dtype}")
+    if not 1 <= keep.shape[1] <= num_patches:
+        raise ValueError(f"keep: K = {keep.shape[1]} outside [1, {num_patches}]")
+
+
+def keep_to_device(keep: torch.Tensor, device) -> torch.Tensor:
+    """int32 copy of a keep table on `device`.  From the CPU through pinned memory and a non_blocking copy: the host does not wait."""
+    k = keep.detach().to(torch.int32)
+    if k.device.type == "cpu" and torch.device(device).type == "cuda":
+        return k.contiguous().pin_memory().to(device, non_blocking=True)
+    return k.to(device).contiguous()
+
+
 class VisionTransformer(nn.Module):
-    """transformer.py:434-651 restricted to what OpenVision instantiates (no attentional pool, patch_dropout = 0)."""
+    """transformer.py:434-651 restricted to what OpenVision instantiates (no attentional pool)."""
 
     def __init__(self, image_size: int, patch_size: int, width: int, layers: int, heads: int, mlp_ratio: float,
                  output_dim: int, pool_type: str = "avg", final_ln_after_pool: bool = True, no_ln_pre: bool = True,
-                 act_kwargs: Optional[dict] = None, eps: float = 1e-6, output_tokens: bool = False):
+                 act_kwargs: Optional[dict] = None, eps: float = 1e-6, output_tokens: bool = False,
+                 patch_dropout: float = 0.0):
         super().__init__()
         self.output_tokens = output_tokens
         self.image_size = (image_size, image_size)
@@ -555,7 +608,8 @@ class VisionTransformer(nn.Module):
         scale = width ** -0.5
         self.class_embedding = nn.Parameter(scale * torch.randn(width))
         self.positional_embedding = nn.Parameter(scale * torch.randn(self.grid_size[0] * self.grid_size[1] + 1, width))
-        self.patch_dropout = nn.Identity()
+        # transformer.py:481: dropout only when p > 0 (the module has no parameters: the state dict is the same either way)
+        self.patch_dropout = PatchDropout(patch_dropout) if patch_dropout > 0. else nn.Identity()
         self.ln_pre = nn.Identity() if no_ln_pre else LayerNorm(width, eps=eps)
         self.transformer = Transformer(width, layers, heads, mlp_ratio, act_kwargs, eps)
         self.attn_pool = None
@@ -606,8 +660,21 @@ class VisionTransformer(nn.Module):
         if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != self.image_size[0] or x.shape[3] != self.image_size[1]:
             raise ValueError(f"expected [B,3,{self.image_size[0]},{self.image_size[1]}], got {tuple(x.shape)}")
 
+    @property
+    def num_patches(self) -> int:
+        return self.grid_size[0] * self.grid_size[1]
+
+    def dropout_active(self) -> bool:
+        """Patch dropout applies to the next forward: training mode and p > 0 (transformer.py:61)."""
+        return self.training and isinstance(self.patch_dropout, PatchDropout) and self.patch_dropout.prob > 0
+
+    def _draw_keep(self, bsz: int, device) -> torch.Tensor:
+        return keep_to_device(self.patch_dropout.sample(bsz, self.num_patches), device)
+
     def _encode(self, x: torch.Tensor, normalize: bool) -> torch.Tensor:
         self._check_image(x)
+        if self.dropout_active():
+            return self._encode_keep(x, self._draw_keep(x.shape[0], x.device), normalize)
         lib = _lib.load()
         head, _keep = self._head()
         tower = self.transformer.tower()
@@ -629,11 +696,43 @@ class VisionTransformer(nn.Module):
                 out[b0:b0 + nb] = self._head_forward(tok, normalize)
         return out
 
-    def _embed_tokens(self, img: torch.Tensor) -> torch.Tensor:
+    def _encode_keep(self, x: torch.Tensor, keep: torch.Tensor, normalize: bool) -> torch.Tensor:
+        """The tower on the kept patches only (int32 device keep [B, K]): L' = 1 + K tokens per image."""
+        lib = _lib.load()
+        head, _keep = self._head()
+        tower = self.transformer.tower()
+        img = x.detach()
+        img = img.contiguous() if img.dtype in (torch.float32, torch.bfloat16) else img.float().contiguous()
+        bsz, nk = keep.shape
+        out = torch.empty(bsz, self.output_dim, dtype=torch.float32, device=x.device)
+        st = stream_ptr()
+        for b0 in range(0, bsz, MAX_MICRO_BATCH):
+            nb = min(MAX_MICRO_BATCH, bsz - b0)
+            kb = keep[b0:b0 + nb]
+            if isinstance(self.ln_pre, nn.Identity):
+                nbytes = lib.ov_vision_keep_workspace_bytes(tower.handle, C.byref(head), nb, nk)
+                ws = self._ws.get(nbytes, x.device)
+                check(lib.ov_encode_image_keep(tower.handle, C.byref(head), ptr(img[b0:]), _dtype_flag(img), ptr(kb), nb, nk, ptr(out[b0:]),
+                                               int(normalize), None, ptr(ws), nbytes, st), "ov_encode_image_keep")
+            else:
+                tok = self._embed_tokens(img[b0:b0 + nb], kb)
+                tok = self.transformer(self.ln_pre(tok))
+                out[b0:b0 + nb] = self._head_forward(tok, normalize)
+        return out
+
+    def _embed_tokens(self, img: torch.Tensor, keep: Optional[torch.Tensor] = None) -> torch.Tensor:
         lib = _lib.load()
         head, _ = self._head()
         tower = self.transformer.tower()
         bsz = img.shape[0]
+        if keep is not None:                    # patch dropout: the kept patches' tokens, in keep order, behind the CLS token
+            nk = keep.shape[1]
+            tok = torch.empty(bsz, 1 + nk, tower.width, dtype=torch.bfloat16, device=img.device)
+            nbytes = lib.ov_vision_keep_workspace_bytes(tower.handle, C.byref(head), bsz, nk)
+            ws = self._ws.get(nbytes, img.device)
+            check(lib.ov_vision_embed_keep(tower.handle, C.byref(head), ptr(img), _dtype_flag(img), ptr(keep), bsz, nk, ptr(tok), None,
+                                           ptr(ws), nbytes, stream_ptr()), "ov_vision_embed_keep")
+            return tok
         seq = self.grid_size[0] * self.grid_size[1] + 1
         tok = torch.empty(bsz, seq, tower.width, dtype=torch.bfloat16, device=img.device)
         nbytes = bsz * (seq - 1) * self.conv1.kpad * 2
@@ -646,20 +745,21 @@ class VisionTransformer(nn.Module):
         lib = _lib.load()
         head, _ = self._head()
         tower = self.transformer.tower()
-        bsz = tok.shape[0]
+        bsz, seq = tok.shape[0], tok.shape[1]
         tokb = tok.detach().to(torch.bfloat16).contiguous()
         out = torch.empty(bsz, self.output_dim, dtype=torch.float32, device=tok.device)
         nbytes = bsz * tower.width * 8 + bsz * self.output_dim * 2 + 4096
         ws = self._ws.get(nbytes, tok.device)
-        check(lib.ov_vision_head_forward(tower.handle, C.byref(head), ptr(tokb), bsz, ptr(out), int(normalize), ptr(ws),
-                                         nbytes, stream_ptr()), "ov_vision_head_forward")
+        check(lib.ov_vision_head_forward_tokens(tower.handle, C.byref(head), ptr(tokb), bsz, seq, ptr(out), int(normalize), ptr(ws),
+                                                nbytes, stream_ptr()), "ov_vision_head_forward_tokens")
         return out
 
     def forward(self, x: torch.Tensor):
         if self.output_tokens:
             self._check_image(x)
             img = x.detach().contiguous()
-            tok = self._embed_tokens(img if img.dtype in (torch.float32, torch.bfloat16) else img.float())
+            keep = self._draw_keep(x.shape[0], x.device) if self.dropout_active() else None
+            tok = self._embed_tokens(img if img.dtype in (torch.float32, torch.bfloat16) else img.float(), keep)
             tok = self.transformer(self.ln_pre(tok))
             pooled = self._head_forward(tok, False)
             tokens = tok[:, 1:]
@@ -693,7 +793,7 @@ class CLIP(nn.Module):
             image_size=v.image_size, patch_size=v.patch_size, width=v.width, layers=v.layers,
             heads=v.width // v.head_width, mlp_ratio=v.mlp_ratio, output_dim=embed_dim, pool_type=v.pool_type,
             final_ln_after_pool=v.final_ln_after_pool, no_ln_pre=v.no_ln_pre, act_kwargs=v.act_kwargs,
-            eps=ln_eps(v.norm_kwargs), output_tokens=v.output_tokens)
+            eps=ln_eps(v.norm_kwargs), output_tokens=v.output_tokens, patch_dropout=float(v.patch_dropout))
         # text tower parts are adopted at the top level, as the reference does (model.py:239-248)
         self.transformer = Transformer(t.width, t.layers, t.heads, t.mlp_ratio, t.act_kwargs, ln_eps(t.norm_kwargs))
         self.context_length = t.context_length
@@ -757,7 +857,8 @@ class CLIP(nn.Module):
 
     def encode_image(self, image: torch.Tensor, normalize: bool = False) -> torch.Tensor:
         """model.py:265-267.  Returns fp32 [B, embed_dim]."""
-        if 0 < image.shape[0] <= self.graph_max_batch and image.is_cuda and not torch.cuda.is_current_stream_capturing():
+        if (0 < image.shape[0] <= self.graph_max_batch and image.is_cuda and not torch.cuda.is_current_stream_capturing()
+                and not self.visual.dropout_active()):               # a captured graph would replay one draw of kept patches
             self.visual._check_image(image)
             x = image.detach()
             x = x.contiguous() if x.dtype in (torch.float32, torch.bfloat16) else x.float().contiguous()

@@ -304,6 +304,95 @@ class _LayerNormFn(torch.autograd.Function):
         return dx.view(shape).to(xd), dg.to(wd), db.to(bd), None
 
 
+class _PatchKeepFn(torch.autograd.Function):
+    """Patch dropout's front end (transformer.py:610-619 with PatchDropout): the conv1 operand rows of the kept patches only
+    (``ov_im2col_patches_keep``), the patch GEMM over those B K rows (``ov_gemm``, as ``_LinearFn``), and the fp32 token assembly
+    ``x[b, 0] = cls + pos[0]``, ``x[b, 1 + j] = y[b, j] + pos[1 + keep[b, j]]`` (``ov_patch_keep_assemble``) -> x [B, 1 + K, D].
+
+    Backward: ``ov_patch_keep_assemble_backward`` gives dpos / dcls as fixed-order sums over the batch (bitwise reproducible; 0 for a
+    position no image kept) and the GEMM's output gradient; ``ov_linear_backward`` over the K kept rows gives the conv1 weight gradient
+    (from the forward's operand rows) and, when the image needs one, the rows that ``ov_col2im_patches_keep`` puts back into the image
+    (dropped patches 0).  keep / inv: int32 device tensors [B, K] / [B, G] (``ov_patch_keep_inverse``)."""
+
+    @staticmethod
+    def forward(ctx, image, w, cls, pos, keep, inv, patch):
+        lib = _lib.load()
+        bsz, _, s, _ = image.shape
+        g = s // patch
+        nk = keep.shape[1]
+        d = w.shape[0]
+        k, kp, npad = 3 * patch * patch, _round_up(3 * patch * patch, 64), _round_up(d, 64)
+        img = image.detach()
+        img = img.contiguous() if img.dtype in (torch.float32, torch.bfloat16) else img.float().contiguous()
+        st = stream_ptr()
+        m = bsz * nk
+        cols = torch.empty(m, kp, dtype=torch.bfloat16, device=image.device)
+        check(lib.ov_im2col_patches_keep(ptr(img), _lib.OV_F32 if img.dtype == torch.float32 else _lib.OV_BF16, ptr(keep), ptr(cols), bsz,
+                                         s, patch, nk, kp, st), "ov_im2col_patches_keep")
+        wb = torch.zeros(npad, kp, dtype=torch.bfloat16, device=image.device)
+        wb[:d, :k] = w.detach()
+        y = torch.empty(m, npad, dtype=torch.bfloat16, device=image.device)
+        check(lib.ov_gemm(ptr(cols), kp, ptr(wb), kp, None, ptr(y), npad, m, npad, kp, _lib.EPI_BIAS, None, 0, 0, 0, 0, st), "ov_gemm")
+        cls32, pos32 = cls.detach().float().contiguous(), pos.detach().float().contiguous()
+        x = torch.empty(bsz, 1 + nk, d, dtype=torch.float32, device=image.device)
+        check(lib.ov_patch_keep_assemble(ptr(y), npad, ptr(cls32), ptr(pos32), ptr(keep), ptr(x), bsz, nk, g * g, d, st),
+              "ov_patch_keep_assemble")
+        ctx.save_for_backward(cols, wb, keep, inv)
+        ctx.dims = (bsz, s, patch, g * g, nk, d, k, kp, npad, img.dtype, image.dtype, w.dtype, cls.dtype, pos.dtype)
+        return x
+
+    @staticmethod
+    def backward(ctx, dx):
+        lib = _lib.load()
+        cols, wb, keep, inv = ctx.saved_tensors
+        bsz, s, patch, gg, nk, d, k, kp, npad, img_dt, xd, wd, cd, pd = ctx.dims
+        need_img, need_w, need_cls, need_pos = ctx.needs_input_grad[:4]
+        dev = dx.device
+        st = stream_ptr()
+        m = bsz * nk
+        dx = dx.detach().float().contiguous()
+        dpos = torch.empty(1 + gg, d, dtype=torch.float32, device=dev) if need_pos else None
+        dcls = torch.empty(d, dtype=torch.float32, device=dev) if need_cls else None
+        dyb = None
+        if need_img or need_w:
+            dyb = (torch.empty if npad == d else torch.zeros)(m, npad, dtype=torch.bfloat16, device=dev)
+        check(lib.ov_patch_keep_assemble_backward(ptr(dx), ptr(inv), bsz, nk, gg, d, ptr(dpos), ptr(dcls), ptr(dyb), npad, st),
+              "ov_patch_keep_assemble_backward")
+        dimg = dw = None
+        if dyb is not None:
+            dcols = torch.empty(m, kp, dtype=torch.bfloat16, device=dev) if need_img else None
+            dwb = torch.empty(npad, kp, dtype=torch.bfloat16, device=dev) if need_w else None
+            nb = lib.ov_linear_backward_workspace_bytes(m, npad, kp)
+            ws = torch.empty(nb + 256, dtype=torch.uint8, device=dev)
+            check(lib.ov_linear_backward(ptr(dyb), npad, ptr(cols), kp, ptr(wb), kp, m, npad, kp, ptr(dcols), kp, ptr(dwb), kp, None, ptr(ws),
+                                         nb, st), "ov_linear_backward")
+            if need_w:
+                dw = dwb[:d, :k].to(wd)
+            if need_img:
+                dimg = torch.empty(bsz, 3, s, s, dtype=img_dt, device=dev)
+                check(lib.ov_col2im_patches_keep(ptr(dcols), kp, ptr(inv), ptr(dimg), _lib.OV_F32 if img_dt == torch.float32 else _lib.OV_BF16,
+                                                 bsz, s, patch, nk, st), "ov_col2im_patches_keep")
+                dimg = dimg.to(xd)
+        return (dimg, dw, dcls.to(cd) if need_cls else None, dpos.to(pd) if need_pos else None, None, None, None)
+
+
+def patch_keep_tables(model, keep: torch.Tensor, batch: int, device, validate: bool = True):
+    """int32 device copies of a keep table [B, K] of patch indices and its inverse map [B, G] (``ov_patch_keep_inverse``).  With
+    ``validate`` the device's duplicate / range flag is read back (one host synchronisation) and a bad table raises IndexError."""
+    from .model import check_keep, keep_to_device
+    v = model.visual
+    gg = v.num_patches
+    check_keep(keep, batch, gg)
+    lib = _lib.load()
+    kd = keep_to_device(keep, device)
+    inv = torch.empty(batch, gg, dtype=torch.int32, device=device)
+    err = torch.zeros(1, dtype=torch.int32, device=device) if validate else None
+    check(lib.ov_patch_keep_inverse(ptr(kd), ptr(inv), batch, kd.shape[1], gg, ptr(err), stream_ptr()), "ov_patch_keep_inverse")
+    if validate and int(err.item()) != 0:
+        raise IndexError(f"keep: a patch index is repeated within an image or lies outside [0, {gg})")
+    return kd, inv
+
+
 CHUNK_LAYERS = [max(0, int(os.environ.get("OVHIP_TRAIN_CHUNK_LAYERS", "0") or 0))]   # > 0: towers run as consecutive autograd nodes of that many blocks
 
 
@@ -328,22 +417,41 @@ def tower_forward(transformer, x: torch.Tensor) -> torch.Tensor:
     return x
 
 
-def encode_image(model, image: torch.Tensor, normalize: bool = True) -> torch.Tensor:
+def encode_image(model, image: torch.Tensor, normalize: bool = True, keep: torch.Tensor = None) -> torch.Tensor:
     """CLIP.encode_image (model.py:265-267) with gradients.  VisionTransformer.forward, transformer.py:609-651, for the
-    OpenVision configuration (no ln_pre, pool -> ln_post -> proj)."""
+    OpenVision configuration (no ln_pre, pool -> ln_post -> proj).
+
+    Patch dropout (transformer.py:619): when the vision tower is in training mode with ``patch_dropout`` p > 0, the kept patches are
+    drawn as the reference draws them (``PatchDropout.sample``: CPU default generator) and the tower runs on those 1 + K tokens.
+    ``keep`` (integer [B, K], patch indices in [0, G), no repeats within an image) overrides the draw, whatever the mode and p; such
+    a table is checked on the device and the flag read back (one host synchronisation), a bad one raises IndexError."""
     v = model.visual
     if not isinstance(v.ln_pre, torch.nn.Identity):
         raise _lib.OvhipError("training path: ln_pre is Identity for OpenVision towers")
     p = v.patch_size[0]
     w = v.conv1.weight
-    # conv1 (:610-612, stride = kernel, no bias) as patch rows times W^T: the same sums as F.conv2d, and a plain GEMM for autograd
-    # (MIOpen's fp32 convolution path costs tens of ms per step at this shape)
     bsz, _, hh, ww = image.shape
     gh, gw = hh // p, ww // p
-    patches = image.reshape(bsz, 3, gh, p, gw, p).permute(0, 2, 4, 1, 3, 5).reshape(bsz * gh * gw, 3 * p * p)
-    x = _LinearFn.apply(patches, w.reshape(w.shape[0], -1), None).view(bsz, gh * gw, -1)
-    cls = v.class_embedding.float().expand(x.shape[0], 1, -1)
-    x = torch.cat([cls, x], dim=1) + v.positional_embedding.float()                            # :615-617
+    explicit = keep is not None
+    if explicit:
+        from .model import check_keep
+        check_keep(keep, bsz, gh * gw)
+    if keep is None and v.dropout_active():
+        keep = v.patch_dropout.sample(bsz, gh * gw)
+    if keep is not None:
+        if not image.is_cuda:
+            raise _lib.OvhipError("training path: tensors must live on an MI355X device (no CPU fallback)")
+        if hh != ww or hh % p:
+            raise ValueError(f"expected square images of a multiple of the patch size, got {tuple(image.shape)}")
+        kd, inv = patch_keep_tables(model, keep, bsz, image.device, validate=explicit)
+        x = _PatchKeepFn.apply(image, w.reshape(w.shape[0], -1), v.class_embedding, v.positional_embedding, kd, inv, p)
+    else:
+        # conv1 (:610-612, stride = kernel, no bias) as patch rows times W^T: the same sums as F.conv2d, and a plain GEMM for autograd
+        # (MIOpen's fp32 convolution path costs tens of ms per step at this shape)
+        patches = image.reshape(bsz, 3, gh, p, gw, p).permute(0, 2, 4, 1, 3, 5).reshape(bsz * gh * gw, 3 * p * p)
+        x = _LinearFn.apply(patches, w.reshape(w.shape[0], -1), None).view(bsz, gh * gw, -1)
+        cls = v.class_embedding.float().expand(x.shape[0], 1, -1)
+        x = torch.cat([cls, x], dim=1) + v.positional_embedding.float()                            # :615-617
     x = tower_forward(v.transformer, x)
     if v.final_ln_after_pool:
         pooled = x[:, 1:].mean(dim=1) if v.pool_type == "avg" else x[:, 0]
@@ -391,7 +499,8 @@ def encode_text(model, text: torch.Tensor, normalize: bool = True) -> torch.Tens
 
 
 def clip_forward(model, image: torch.Tensor, text: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    """CLIP.forward (model.py:295-315) with gradients: (image_features, text_features, logit_scale.exp())."""
+    """CLIP.forward (model.py:295-315) with gradients: (image_features, text_features, logit_scale.exp()).  Patch dropout as in
+    ``encode_image`` (drawn when the vision tower is in training mode with p > 0)."""
     return encode_image(model, image, True), encode_text(model, text, True), model.logit_scale.exp()
 
 

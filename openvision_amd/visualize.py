@@ -147,6 +147,10 @@ class _FeatureFn(torch.autograd.Function):
 
 
 def _check_args(visual, image, layer: int, feature: int):
+    pd = getattr(visual, "patch_dropout", None)
+    if visual.training and float(getattr(pd, "prob", 0.0)) > 0:
+        raise _lib.OvhipError(f"feature objective: the vision tower is in training mode with patch_dropout = {pd.prob}; the objective reads "
+                              "every patch token and does not drop any -- call model.eval() (or visual.eval()) first")
     if not isinstance(visual.ln_pre, torch.nn.Identity):
         raise _lib.OvhipError("feature objective: ln_pre is Identity for OpenVision towers")
     blocks = list(visual.transformer.resblocks)

@@ -6,9 +6,13 @@
     text_train   text-side gradient-ascent step (ov-gradient-ascent.py) at B = 13, L/14's text tower, parameters trainable
     text_frozen  the same step with model.requires_grad_(False)     (input-only text backward)
 
+--patch-dropout P (image configurations): the vision tower's patch_dropout = P, model in training mode, so that every step keeps
+K = max(1, int(G (1 - P))) patches per image, drawn as the reference draws them (FLIP; FLIP + LiT with image_lit).
+
 Run each configuration as its own step, each under its own time limit, and stop at the first failure:
 
     timeout -k 10 600 python tools/frozen_step_probe.py image_all && timeout -k 10 600 python tools/frozen_step_probe.py image_lit && ...
+    timeout -k 10 600 python tools/frozen_step_probe.py image_all --patch-dropout 0.5 && ...
 
 Prints one JSON line per configuration: ms per step (mean of STEPS timed steps after one warm-up step) and
 torch.cuda.max_memory_allocated over the timed steps (model, optimiser state and the training path's buffer pool included)."""
@@ -29,13 +33,25 @@ CONFIGS = ("image_all", "image_lit", "image_lit2", "text_train", "text_frozen")
 
 
 def main():
-    which = sys.argv[1] if len(sys.argv) > 1 else ""
+    args = sys.argv[1:]
+    which = args[0] if args else ""
+    pdrop = 0.0
+    if len(args) == 3 and args[1] == "--patch-dropout" and which.startswith("image"):
+        pdrop = float(args[2])
+    elif len(args) != 1:
+        which = ""
     if which not in CONFIGS:
-        sys.exit(f"usage: frozen_step_probe.py {{{'|'.join(CONFIGS)}}}")
+        sys.exit(f"usage: frozen_step_probe.py {{{'|'.join(CONFIGS)}}} [--patch-dropout P]")
     name = os.environ.get("MODEL", "vit-large-patch14-224")
     steps = int(os.environ.get("STEPS", "3"))
     cfg = preset(name)
-    m = create_model(cfg, device="cuda", state_dict=synth.make_state_dict(cfg))
+    sd = synth.make_state_dict(cfg)
+    if pdrop > 0:
+        cfg = dict(cfg, vision_cfg=dict(cfg["vision_cfg"], patch_dropout=pdrop))
+    m = create_model(cfg, device="cuda", state_dict=sd)
+    if pdrop > 0:
+        m.train()                                   # patch dropout acts in training mode only
+        torch.manual_seed(0)
     if which.startswith("image"):
         B = int(os.environ.get("BATCH", "256"))
         if which == "image_lit":
@@ -79,7 +95,7 @@ def main():
     torch.cuda.synchronize()
     ms = (time.perf_counter() - t0) / steps * 1e3
     trainable = sum(p.numel() for p in m.parameters() if p.requires_grad)
-    print(json.dumps(dict(config=which, model=name, batch=B, steps=steps, ms_per_step=round(ms, 2),
+    print(json.dumps(dict(config=which, model=name, batch=B, patch_dropout=pdrop, steps=steps, ms_per_step=round(ms, 2),
                           max_memory_allocated_gib=round(torch.cuda.max_memory_allocated() / 2 ** 30, 2),
                           trainable_params=trainable, loss=float(loss.detach()))), flush=True)
 

@@ -17,6 +17,7 @@
  *   ov_l2norm           F.normalize(x, dim=-1)                                model.py:267,284
  *   ov_logits           CLIP.get_logits (scale * img @ txt^T)                 model.py:286-293
  *   ov_clip_loss        ClipLoss.get_logits + cross_entropy both ways         loss.py:102-131
+ *   ov_siglip_loss      SigLipLoss._loss summed over every text block          loss.py:307-414
  *   ov_gemm_fp8         the same nn.Linear on fp8 e4m3 operands (config #5)           transformer.py:225,232-236
  *   ov_preprocess_image transforms.Resize -> ToTensor -> Normalize (Pillow-exact)  ov-zero-shot-test.py:72-77, transform.py:355-392
  *   ov_class_mean_normalize / ov_topk   zero-shot classifier weights, argmax / recall@k ranking   zero_shot_classifier.py:54-57,
@@ -281,6 +282,31 @@ int ov_clip_loss_backward(const float* img, const float* txt, const float* all_i
                           const float* logit_scale, int label_offset, const float* lse_terms, const float* grad_loss, float* d_img,
                           float* d_txt, float* d_all_img, float* d_all_txt, float* d_scale, void* workspace,
                           size_t workspace_bytes, ov_stream_t stream);
+
+/* SigLIP pairwise sigmoid loss on a local strip (SigLipLoss, loss.py:307-414; the neighbour-exchange ring is replaced by one
+ * all-gather of the text features: only the order of the sums differs).
+ *   img           : this rank's L2-normalised image embeddings [b, E] fp32
+ *   all_txt       : gathered text embeddings [N, E] fp32 in rank order (== this rank's text when N == b)
+ *   logit_scale   : DEVICE scalar s, the multiplier exp(CLIP.logit_scale); logit_bias: DEVICE scalar beta (NULL = no bias)
+ *   with z = s img_i . all_txt_j + beta and l = +1 where j == i + label_offset (label_offset = b * rank), -1 elsewhere:
+ *   loss_out[0] = (1 / b) sum_{i < b, j < N} softplus(-l z)                (fp32, device; = -logsigmoid(l z), loss.py:349-358)
+ * 0 <= label_offset, label_offset + b <= N, E % 8 == 0, E <= 1152 (OV_ERR_INVALID / OV_ERR_UNSUPPORTED otherwise).
+ * workspace: ov_siglip_loss_workspace_bytes(b, N) bytes.  Logits are never materialised; deterministic (no atomics). */
+size_t ov_siglip_loss_workspace_bytes(int b, int N);
+int ov_siglip_loss(const float* img, const float* all_txt, int b, int N, int E, const float* logit_scale, const float* logit_bias,
+                   int label_offset, float* loss_out, void* workspace, size_t workspace_bytes, ov_stream_t stream);
+
+/* Backward of ov_siglip_loss: with g = -l sigmoid(-l z) / b * grad_loss (grad_loss a DEVICE scalar, NULL = 1), recomputed tile by
+ * tile and never materialised:
+ *                        d_img     = s g all_txt          (local rows [b, E], always written)
+ *                        d_all_txt = s g^T img            (gathered rows [N, E]; NULL = skip)
+ *                        d_scale   = sum g .* (img . all_txt^T),  d_bias = sum g      (device scalars; NULL = skip)
+ * The caller routes d_all_txt (sum over ranks, own chunk kept).  Same shape limits as ov_siglip_loss.  Deterministic: no atomics,
+ * the scalar sums are fixed-order two-stage sums. */
+size_t ov_siglip_loss_backward_workspace_bytes(int b, int N);
+int ov_siglip_loss_backward(const float* img, const float* all_txt, int b, int N, int E, const float* logit_scale,
+                            const float* logit_bias, int label_offset, const float* grad_loss, float* d_img, float* d_all_txt,
+                            float* d_scale, float* d_bias, void* workspace, size_t workspace_bytes, ov_stream_t stream);
 
 /* ---- operator-level backward of the block (the reference gets these from torch autograd through nn.Linear,
  * nn.LayerNorm and nn.GELU: transformer.py:15-30, 232-236).  bf16 activations and gradients, fp32 arithmetic and parameter-gradient

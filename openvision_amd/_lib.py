@@ -109,6 +109,12 @@ SIGNATURES = {
     "ov_clip_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p,
                              c_void_p, c_void_p, c_size_t, c_void_p]),
     "ov_clip_loss_backward_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "ov_siglip_loss_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "ov_siglip_loss": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_size_t,
+                               c_void_p]),
+    "ov_siglip_loss_backward_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "ov_siglip_loss_backward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "ov_gemm_batched": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int, c_int,
                                 c_int, c_void_p]),
     "ov_gemm_tn_batched": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_int64, c_int,

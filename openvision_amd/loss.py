@@ -10,6 +10,9 @@ HIP kernel behind ``ov_clip_loss_backward`` (d loss / d features and d loss / d 
 carries the gradient on through the towers.  The gathered-side terms are routed as
 ``gather_features`` does (loss.py:19-63): own chunk only, or summed over ranks (reduce-scatter) with ``gather_with_grad``.
 ``use_horovod`` is rejected (RCCL via torch.distributed is the only transport here).
+
+``SigLipLoss`` (loss.py:307-414) is the pairwise sigmoid objective on the same transport: one all-gather of the text features,
+one fused strip kernel (``ov_siglip_loss``), and in the backward the gathered side summed over ranks.
 """
 from __future__ import annotations
 
@@ -47,21 +50,27 @@ def gather_features(image_features: torch.Tensor, text_features: torch.Tensor, l
         raise RuntimeError("world_size > 1 needs an initialised torch.distributed process group (caller owns init)")
     b, e = image_features.shape
     packed = torch.cat([image_features.detach().float(), text_features.detach().float()], dim=1).contiguous()
-    out = torch.empty(world_size * b, 2 * e, dtype=torch.float32, device=packed.device)
+    out = _all_gather_rows(packed, world_size, group)
+    return out[:, :e].contiguous(), out[:, e:].contiguous()
+
+
+def _all_gather_rows(x: torch.Tensor, world_size: int, group=None) -> torch.Tensor:
+    """[b, C] on every rank -> [world_size * b, C] in rank order: one all_gather_into_tensor, bracketed for record_comm."""
+    out = torch.empty(world_size * x.shape[0], x.shape[1], dtype=x.dtype, device=x.device)
     if _COMM_LOG is None:
-        dist.all_gather_into_tensor(out, packed, group=group)
-    elif packed.is_cuda:
+        dist.all_gather_into_tensor(out, x, group=group)
+    elif x.is_cuda:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        dist.all_gather_into_tensor(out, packed, group=group)
+        dist.all_gather_into_tensor(out, x, group=group)
         e1.record()
         _COMM_LOG.append((e0, e1))
     else:
         import time
         t0 = time.perf_counter()
-        dist.all_gather_into_tensor(out, packed, group=group)
+        dist.all_gather_into_tensor(out, x, group=group)
         _COMM_LOG.append((t0, time.perf_counter()))
-    return out[:, :e].contiguous(), out[:, e:].contiguous()
+    return out
 
 
 class ClipLoss(nn.Module):
@@ -204,3 +213,108 @@ class _ClipLossFn(torch.autograd.Function):
             g_img, g_txt = own[:, :e], own[:, e:]
         dt_i, dt_t, dt_s = ctx.in_dtypes
         return None, g_img.to(dt_i), g_txt.to(dt_t), d_scale[0].to(dt_s)
+
+
+class SigLipLoss(nn.Module):
+    """Same constructor and call signature as the reference's SigLIP loss (loss.py:307-414), plus ``group``.
+
+    Each rank holds ``[b, E]`` image and text embeddings.  The reference passes text blocks round a neighbour-exchange ring
+    (loss.py:219-304) and adds one ``[b, b]`` sigmoid loss per block; here ONE all-gather of the text features gives the
+    rank-ordered ``[N, E]`` set and the fused HIP kernel (``ov_siglip_loss``) sums the whole ``[b, N]`` strip, labels ``+1`` at
+    ``i + b*rank`` and ``-1`` elsewhere.  Every rank's loss is the same sum over all text blocks, and the ring's backward hands
+    each block's gradient back to its owner, as the reduce-scatter of the gathered-side gradient does here: only the order of
+    the sums differs.  ``bidir`` only chooses the ring's direction in the reference, so it is accepted and has no effect.
+
+    ``logit_bias`` (a 0-d tensor, a float, or None for no bias) and ``logit_scale`` (the multiplier, already ``exp``'d) stay on the
+    device.  The loss is an autograd node whenever an input requires grad (backward: ``ov_siglip_loss_backward``)."""
+
+    def __init__(self, cache_labels: bool = False, rank: int = 0, world_size: int = 1, bidir: bool = True,
+                 use_horovod: bool = False, group=None):
+        super().__init__()
+        if use_horovod:
+            raise NotImplementedError("horovod transport is not supported; use torch.distributed (RCCL)")
+        self.cache_labels, self.rank, self.world_size, self.bidir, self.use_horovod = cache_labels, rank, world_size, bidir, use_horovod
+        self.group = group
+        self.always_collective = False   # tests only: take the world_size > 1 path (gather / reduce-scatter) in a world of one rank
+        self._ws: Optional[torch.Tensor] = None
+
+    def _gather_text(self, text: torch.Tensor) -> torch.Tensor:
+        if self.world_size == 1 and not self.always_collective:
+            return text
+        if not (dist.is_available() and dist.is_initialized()):
+            raise RuntimeError("world_size > 1 needs an initialised torch.distributed process group (caller owns init)")
+        return _all_gather_rows(text, self.world_size, self.group)
+
+    def _loss_strip(self, img, all_txt, scale: torch.Tensor, bias: Optional[torch.Tensor], label_offset: int) -> torch.Tensor:
+        lib = _lib.load()
+        b, e = img.shape
+        n = all_txt.shape[0]
+        nbytes = lib.ov_siglip_loss_workspace_bytes(b, n)
+        if self._ws is None or self._ws.device != img.device or self._ws.numel() < nbytes:
+            self._ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=img.device)
+        out = torch.empty(1, dtype=torch.float32, device=img.device)
+        check(lib.ov_siglip_loss(ptr(img), ptr(all_txt), b, n, e, ptr(scale), ptr(bias) if bias is not None else None,
+                                 int(label_offset), ptr(out), ptr(self._ws), nbytes, stream_ptr()), "ov_siglip_loss")
+        return out[0]
+
+    def forward(self, image_features, text_features, logit_scale, logit_bias=None, output_dict: bool = False):
+        if not (image_features.is_cuda and text_features.is_cuda):
+            raise _lib.OvhipError("SigLipLoss: features must live on an MI355X device (no CPU fallback)")
+        needs_grad = torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad
+                                                     for t in (image_features, text_features, logit_scale, logit_bias))
+        if needs_grad:
+            dev = image_features.device
+            if not isinstance(logit_scale, torch.Tensor):
+                logit_scale = torch.tensor(float(logit_scale), device=dev)
+            if logit_bias is not None and not isinstance(logit_bias, torch.Tensor):
+                logit_bias = torch.tensor(float(logit_bias), device=dev)
+            loss = _SigLipLossFn.apply(self, image_features, text_features, logit_scale, logit_bias)
+        else:
+            img = image_features.detach().float().contiguous()
+            all_txt = self._gather_text(text_features.detach().float().contiguous())
+            scale = ClipLoss._device_scale(logit_scale, img.device)
+            bias = ClipLoss._device_scale(logit_bias, img.device) if logit_bias is not None else None
+            loss = self._loss_strip(img, all_txt, scale, bias, img.shape[0] * self.rank)
+        return {"contrastive_loss": loss} if output_dict else loss
+
+
+class _SigLipLossFn(torch.autograd.Function):
+    """SigLipLoss as an autograd node.  forward = the fused strip kernel; backward = ov_siglip_loss_backward, then the gathered
+    side's gradient summed over ranks (own chunk kept): what the reference's NeighbourExchange backward returns to each block's
+    owner (loss.py:273-280)."""
+
+    @staticmethod
+    def forward(ctx, mod: "SigLipLoss", image_features, text_features, logit_scale, logit_bias):
+        img, txt = image_features.detach().float().contiguous(), text_features.detach().float().contiguous()
+        b = img.shape[0]
+        ctx.multi = mod.world_size > 1 or mod.always_collective
+        all_txt = mod._gather_text(txt)
+        off = b * mod.rank
+        scale = ClipLoss._device_scale(logit_scale, img.device)
+        bias = ClipLoss._device_scale(logit_bias, img.device) if logit_bias is not None else None
+        loss = mod._loss_strip(img, all_txt, scale, bias, off)
+        ctx.mod, ctx.off, ctx.has_bias = mod, off, bias is not None
+        ctx.in_dtypes = (image_features.dtype, text_features.dtype, logit_scale.dtype,
+                         logit_bias.dtype if logit_bias is not None else None)
+        ctx.save_for_backward(img, all_txt, scale, bias)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        mod: "SigLipLoss" = ctx.mod
+        img, all_txt, scale, bias = ctx.saved_tensors
+        lib = _lib.load()
+        b, e = img.shape
+        n = all_txt.shape[0]
+        d_img, d_all = torch.empty_like(img), torch.empty_like(all_txt)
+        d_sc = torch.empty(2, dtype=torch.float32, device=img.device)            # d scale, d bias
+        grad = grad_out.detach().float().reshape(1).contiguous()                  # device scalar: no host round trip
+        nbytes = lib.ov_siglip_loss_backward_workspace_bytes(b, n)
+        wsb = torch.empty(nbytes + 256, dtype=torch.uint8, device=img.device)
+        check(lib.ov_siglip_loss_backward(ptr(img), ptr(all_txt), b, n, e, ptr(scale), ptr(bias) if ctx.has_bias else None, ctx.off,
+                                          ptr(grad), ptr(d_img), ptr(d_all), ptr(d_sc[0:]), ptr(d_sc[1:]) if ctx.has_bias else None,
+                                          ptr(wsb), nbytes, stream_ptr()), "ov_siglip_loss_backward")
+        # text appears on the gathered side only: at world_size 1 its gradient IS d_all (nothing to add)
+        d_txt = _sum_over_ranks_own_chunk(d_all, b, mod.rank, mod.group) if ctx.multi else d_all
+        dt_i, dt_t, dt_s, dt_b = ctx.in_dtypes
+        return (None, d_img.to(dt_i), d_txt.to(dt_t), d_sc[0].to(dt_s), d_sc[1].to(dt_b) if ctx.has_bias else None)

@@ -783,8 +783,6 @@ class CLIP(nn.Module):
         super().__init__()
         if quick_gelu:
             raise NotImplementedError("quick_gelu is not used by OpenVision configs")
-        if init_logit_bias is not None:
-            raise NotImplementedError("logit_bias (SigLIP) is outside the InfoNCE path")
         self.output_dict = output_dict
         v = vision_cfg_from(vision_cfg)
         t = text_cfg_from(text_cfg)
@@ -807,7 +805,8 @@ class CLIP(nn.Module):
         self.text_pool_type = t.pool_type
         self.register_buffer("attn_mask", None, persistent=False)     # no_causal_mask -> None (transformer.py:722-725)
         self.logit_scale = nn.Parameter(torch.ones([]) * float(init_logit_scale))
-        self.logit_bias = None
+        # SigLIP (model.py:251-254): a learned scalar added to every logit; the loss is openvision_amd.loss.SigLipLoss
+        self.logit_bias = nn.Parameter(torch.ones([]) * float(init_logit_bias)) if init_logit_bias is not None else None
         self._pk = _Packed()
         self._ws = _Workspace()
         self._err = None
@@ -905,6 +904,8 @@ class CLIP(nn.Module):
         i = self.encode_image(image, normalize=True)
         t = self.encode_text(text, normalize=True)
         li = logits(i, t, self.logit_scale.detach().exp())       # the scale stays on the device (model.py:288)
+        if self.logit_bias is not None:
+            li += self.logit_bias.detach()                       # model.py:289-290, also on the device
         return li, li.T
 
     def forward(self, image: Optional[torch.Tensor] = None, text: Optional[torch.Tensor] = None):
@@ -926,8 +927,14 @@ class CLIP(nn.Module):
             image_features = self.encode_image(image, normalize=True) if image is not None else None
             text_features = self.encode_text(text, normalize=True) if text is not None else None
         scale = self.logit_scale.detach().exp()
+        bias = self.logit_bias.detach() if self.logit_bias is not None else None
         if self.output_dict:
-            return {"image_features": image_features, "text_features": text_features, "logit_scale": scale}
+            out = {"image_features": image_features, "text_features": text_features, "logit_scale": scale}
+            if bias is not None:
+                out["logit_bias"] = bias
+            return out
+        if bias is not None:
+            return image_features, text_features, scale, bias
         return image_features, text_features, scale
 
     def invalidate_packed(self) -> None:

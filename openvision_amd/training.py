@@ -498,10 +498,14 @@ def encode_text(model, text: torch.Tensor, normalize: bool = True) -> torch.Tens
     return encode_text_embeddings(model, x, normalize, text.argmax(dim=-1))
 
 
-def clip_forward(model, image: torch.Tensor, text: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    """CLIP.forward (model.py:295-315) with gradients: (image_features, text_features, logit_scale.exp()).  Patch dropout as in
+def clip_forward(model, image: torch.Tensor, text: torch.Tensor) -> Tuple[torch.Tensor, ...]:
+    """CLIP.forward (model.py:295-315) with gradients: (image_features, text_features, logit_scale.exp()), and ``logit_bias`` (the
+    parameter itself, so its gradient flows) as a fourth element when the model has one (SigLIP).  Patch dropout as in
     ``encode_image`` (drawn when the vision tower is in training mode with p > 0)."""
-    return encode_image(model, image, True), encode_text(model, text, True), model.logit_scale.exp()
+    out = (encode_image(model, image, True), encode_text(model, text, True), model.logit_scale.exp())
+    if getattr(model, "logit_bias", None) is not None:
+        return out + (model.logit_bias,)
+    return out
 
 
 # --------------------------------------------------------------------------------------------------------------------------
@@ -509,7 +513,7 @@ def clip_forward(model, image: torch.Tensor, text: torch.Tensor) -> Tuple[torch.
 # --------------------------------------------------------------------------------------------------------------------------
 def default_decay_filter(name: str, p: torch.Tensor) -> bool:
     """The reference decays '.*/kernel$' only (build_optax.py:259: Dense / Conv kernels): here the 2-D (and conv) weight matrices;
-    biases, LayerNorm parameters, class / positional / token embeddings and the logit scale are not decayed."""
+    biases, LayerNorm parameters, class / positional / token embeddings, the logit scale and the logit bias are not decayed."""
     if name.endswith("token_embedding.weight") or "positional_embedding" in name or name.endswith("class_embedding"):
         return False
     return p.dim() >= 2

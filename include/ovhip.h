@@ -480,8 +480,9 @@ int ov_block_backward(const ov_tower_cfg* cfg, const ov_block_weights* w, const 
 
 /* Training-side tower entry points.  ov_tower_forward_saving = the tower forward on the caller's stream that keeps, per layer and
  * token, [x | qkv | attention out | x1 | ln_1 out | ln_2 out | c_fc pre-activation | c_fc activation] (8 D + 2 mlp_pad bf16, plus the
- * attention's fp32 row log-sum-exp per layer; `saved` holds ov_tower_saved_bytes: 52 GB for L/14 at batch 256 — sized for the 288 GB of an MI355X: nothing of the forward is run a second time
- * by the backward).  bf16 path; the blocks must hold
+ * attention's fp32 row log-sum-exp per layer; `saved` holds ov_tower_saved_bytes: 52 GB for L/14 at batch 256; nothing of the forward
+ * is run a second time by the backward -- ov_tower_forward_checkpointed below keeps the block inputs only and recomputes the rest).
+ * bf16 path; the blocks must hold
  * the module's own, unfolded weights.  ov_tower_backward runs ov_block_backward over the layers in reverse: dx [B*L, D] holds
  * d loss / d (tower output) on entry and d loss / d (tower input) on return; grads[layer] receives that block's parameter gradients
  * (written, not accumulated). */
@@ -515,6 +516,24 @@ int    ov_tower_forward_saving_from(const ov_tower* t, int first, ov_bf16* x, ov
 size_t ov_tower_backward_partial_workspace_bytes(const ov_tower* t, int B, int L);
 int    ov_tower_backward_partial(const ov_tower* t, int first, const ov_bf16* saved, ov_bf16* dx, const ov_block_grads* grads, int want_dx,
                                  int B, int L, void* workspace, size_t workspace_bytes, ov_stream_t stream);
+
+/* Activation recomputation (the reference's remat='full' per block; CLIP.set_grad_checkpointing).  ov_tower_forward_checkpointed runs
+ * the layers below `first` as ov_tower_forward_saving_from does (x in place, intermediates in `slot`) and keeps, for each layer
+ * i >= first, only its input in ckpt[i - first] (ov_tower_checkpoint_bytes: (layers - first) B L D bf16; NULL iff first == layers):
+ * layer i reads ckpt[i - first], puts its intermediates in `slot` (ov_tower_slot_bytes: one layer's slot without its x part) and
+ * writes its output into ckpt[i - first + 1], the last one into x.  On return `slot` holds the top layer's slot (first < layers).
+ * ov_tower_backward_checkpointed walks layers layers-1 .. first with ov_tower_backward_partial's grads / want_dx / lowest-layer rules
+ * and workspace (ov_tower_backward_partial_workspace_bytes); before each block backward it recomputes that layer's slot from its
+ * checkpoint with the forward's own launches (c_proj excepted: the backward never reads the block output), except the top layer's
+ * when `slot_holds_top` says `slot` is untouched since the forward.  x, the loss and every gradient are bitwise those of the saving
+ * path.  Same rejections as the saving entry points; a short slot is OV_ERR_WORKSPACE. */
+size_t ov_tower_checkpoint_bytes(const ov_tower* t, int first, int B, int L);
+size_t ov_tower_slot_bytes(const ov_tower* t, int B, int L);
+int    ov_tower_forward_checkpointed(const ov_tower* t, int first, ov_bf16* x, ov_bf16* ckpt, void* slot, size_t slot_bytes, int B, int L,
+                                     ov_stream_t stream);
+int    ov_tower_backward_checkpointed(const ov_tower* t, int first, const ov_bf16* ckpt, void* slot, size_t slot_bytes, int slot_holds_top,
+                                      ov_bf16* dx, const ov_block_grads* grads, int want_dx, int B, int L, void* workspace,
+                                      size_t workspace_bytes, ov_stream_t stream);
 
 /* ---- MLP-feature objective (feature visualisation: a forward hook on resblocks[layer].mlp.gelu, ov-feature-visualization.py:211) --
  * The attention half of one block, x1 = x + out_proj(attn(ln_1(x))) (transformer.py:263), keeping qkv [B*L, 3D], attn_out [B*L, D],

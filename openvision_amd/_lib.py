@@ -149,6 +149,11 @@ SIGNATURES = {
     "ov_tower_backward_partial_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "ov_tower_backward_partial": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t,
                                           c_void_p]),
+    "ov_tower_checkpoint_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
+    "ov_tower_slot_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "ov_tower_forward_checkpointed": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p]),
+    "ov_tower_backward_checkpointed": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_int, c_int,
+                                               c_int, c_void_p, c_size_t, c_void_p]),
     "ov_block_attn_forward_saving": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "ov_block_attn_backward_input_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "ov_block_attn_backward_input": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,

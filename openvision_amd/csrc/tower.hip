@@ -545,7 +545,8 @@ extern "C" int ov_block_backward(const ov_tower_cfg* cfg, const ov_block_weights
 extern "C" size_t ov_block_backward_workspace_bytes(const ov_tower_cfg* cfg, int B, int L);
 
 // saved activations of one layer: [x | qkv | attention out | x1 | ln_1 out | ln_2 out | c_fc pre-activation | c_fc activation],
-// 8 D + 2 mlp_pad bf16 per token (288 GB of HBM: keep, do not recompute)
+// 8 D + 2 mlp_pad bf16 per token (the default keeps them all; ov_tower_forward_checkpointed keeps only x and recomputes the rest
+// per block in the backward)
 // + per layer the attention's row log-sum-exp, fp32 [B * heads][L rounded up to 32] (ov_attention_lse; used by the backward where the
 // resident kernel applies: head_dim 64, L <= 288)
 static inline size_t saved_per_token(const ov_tower_cfg& c) { return (size_t)8 * c.width + 2 * (size_t)c.mlp_pad; }
@@ -576,17 +577,20 @@ inline Slot slot_at(const ov_tower_cfg& c, ov_bf16* sx, ov_bf16* rest, int64_t M
     s.lse = (float*)(s.act + (size_t)M * c.mlp_pad);
     return s;
 }
-inline ov_block_saved block_saved_at(const ov_tower_cfg& c, const ov_bf16* sx, int B, int L) {
-    const int64_t M = (int64_t)B * L;
-    const Slot s = slot_at(c, const_cast<ov_bf16*>(sx), const_cast<ov_bf16*>(sx) + (size_t)M * c.width, M);
+inline ov_block_saved block_saved_of(const ov_tower_cfg& c, const Slot& s, int L) {
     ov_block_saved sv;
     sv.qkv = s.qkv; sv.attn_out = s.o; sv.x1 = s.x1; sv.ln1_out = s.n1; sv.ln2_out = s.n2; sv.fc_pre = s.pre; sv.fc_act = s.act;
     sv.attn_lse = saved_lse_used(c, L) ? s.lse : nullptr;
     return sv;
 }
+inline ov_block_saved block_saved_at(const ov_tower_cfg& c, const ov_bf16* sx, int B, int L) {
+    const int64_t M = (int64_t)B * L;
+    return block_saved_of(c, slot_at(c, const_cast<ov_bf16*>(sx), const_cast<ov_bf16*>(sx) + (size_t)M * c.width, M), L);
+}
 
 // One block of the saving forward: the same operator sequence as run_block, with qkv / attention output / x1 / ... written where the
-// backward will read them, the input read from s.x and the output written to y (y may be s.x: nothing reads the input after out_proj)
+// backward will read them, the input read from s.x and the output written to y (y may be s.x: nothing reads the input after out_proj).
+// y = NULL: the slot only (the backward's recompute), c_proj is not run.
 int forward_saving_layer(const ov_tower_cfg& c, const ov_block_weights& w, const Slot& s, ov_bf16* y, int B, int L, ov_stream_t stream) {
     const int D = c.width, H = c.heads, hd = D / H;
     const int64_t M = (int64_t)B * L;
@@ -601,6 +605,7 @@ int forward_saving_layer(const ov_tower_cfg& c, const ov_block_weights& w, const
     if ((rc = ov_gemm(s.o, D, w.out_w, D, w.out_b, s.x1, D, M, D, D, OV_EPI_BIAS_RESIDUAL, s.x, D, 0, 0, 0, stream))) return rc;
     if ((rc = ov_layernorm(s.x1, OV_BF16, D, w.ln2_w, w.ln2_b, s.n2, OV_BF16, D, M, D, c.ln_eps, stream))) return rc;
     if ((rc = ov_gemm_keep(s.n2, D, w.fc_w, D, w.fc_b, s.act, c.mlp_pad, s.pre, c.mlp_pad, M, c.mlp_pad, D, gelu, stream))) return rc;
+    if (!y) return OV_OK;
     return ov_gemm(s.act, c.mlp_pad, w.proj_w, c.mlp_pad, w.proj_b, y, D, M, D, c.mlp_pad, OV_EPI_BIAS_RESIDUAL, s.x1, D, 0, 0, 0, stream);
 }
 
@@ -640,10 +645,15 @@ extern "C" size_t ov_tower_saved_bytes_from(const ov_tower* t, int first, int B,
     return (size_t)(t->cfg.layers - first) * saved_per_layer(t->cfg, B, L) * sizeof(ov_bf16);
 }
 
+// one layer's slot without its x part
+static inline size_t slot_rest_bytes(const ov_tower_cfg& c, int B, int L) {
+    return (saved_per_layer(c, B, L) - (size_t)B * L * c.width) * sizeof(ov_bf16);
+}
+
 // the layers below `first` run in place on x with their intermediates in one slot's worth of workspace (all but its x part); 0 = none
 extern "C" size_t ov_tower_forward_saving_from_workspace_bytes(const ov_tower* t, int first, int B, int L) {
     if (!t || B <= 0 || L <= 0 || first <= 0 || first > t->cfg.layers) return 0;
-    return (saved_per_layer(t->cfg, B, L) - (size_t)B * L * t->cfg.width) * sizeof(ov_bf16);
+    return slot_rest_bytes(t->cfg, B, L);
 }
 
 extern "C" int ov_tower_forward_saving_from(const ov_tower* t, int first, ov_bf16* x, ov_bf16* saved, int B, int L, void* workspace,
@@ -751,6 +761,87 @@ extern "C" int ov_tower_backward_partial(const ov_tower* t, int first, const ov_
         const ov_block_saved sv = block_saved_at(c, sx, B, L);
         const int rc = block_backward_partial(&c, &t->blocks[i], sx, &sv, dx, (i > lo || want_dx) ? dx : nullptr, &grads[i - first], B, L,
                                               workspace, workspace_bytes, stream);
+        if (rc) return rc;
+    }
+    return OV_OK;
+}
+
+// ---- activation recomputation (the reference's remat='full' per block): keep each kept layer's input only ----------------------------
+extern "C" size_t ov_tower_checkpoint_bytes(const ov_tower* t, int first, int B, int L) {
+    if (!t || B <= 0 || L <= 0 || first < 0 || first > t->cfg.layers) return 0;
+    return (size_t)(t->cfg.layers - first) * B * L * t->cfg.width * sizeof(ov_bf16);
+}
+
+extern "C" size_t ov_tower_slot_bytes(const ov_tower* t, int B, int L) {
+    if (!t || B <= 0 || L <= 0) return 0;
+    return slot_rest_bytes(t->cfg, B, L);
+}
+
+// Layers below `first` as in ov_tower_forward_saving_from (x in place, intermediates in `slot`); layer i >= first reads its input from
+// ckpt[i - first], puts its intermediates in `slot` and writes its output into ckpt[i - first + 1] (the last one into x): the operators
+// of forward_saving_kept on the same values, so `slot` ends up holding exactly the top layer's saved slot (x part: ckpt[layers-1-first]).
+extern "C" int ov_tower_forward_checkpointed(const ov_tower* t, int first, ov_bf16* x, ov_bf16* ckpt, void* slot, size_t slot_bytes, int B,
+                                             int L, ov_stream_t stream) {
+    if (!t || !x || !slot || B <= 0 || L <= 0 || first < 0 || first > t->cfg.layers) return OV_ERR_INVALID;
+    const ov_tower_cfg& c = t->cfg;
+    if (first < c.layers && !ckpt) return OV_ERR_INVALID;
+    if (tower_fp8(t)) return OV_ERR_UNSUPPORTED;
+    if (slot_bytes < ov_tower_slot_bytes(t, B, L)) return OV_ERR_WORKSPACE;
+    if (((uintptr_t)x | (uintptr_t)ckpt | (uintptr_t)slot) & 15) return OV_ERR_INVALID;
+    for (int i = 0; i < c.layers; ++i)
+        if (!t->set[i] || t->blocks[i].qkv_colsum || t->blocks[i].fc_colsum) return OV_ERR_INVALID;
+    const int64_t M = (int64_t)B * L;
+    const size_t xe = (size_t)M * c.width;
+    for (int i = 0; i < first; ++i) {
+        const int rc = forward_saving_layer(c, t->blocks[i], slot_at(c, x, (ov_bf16*)slot, M), x, B, L, stream);
+        if (rc) return rc;
+    }
+    if (first == c.layers) return OV_OK;
+    hipError_t e = hipMemcpyAsync(ckpt, x, xe * sizeof(ov_bf16), hipMemcpyDeviceToDevice, (hipStream_t)stream);
+    if (e != hipSuccess) return OV_ERR_HIP - (int)e;
+    for (int i = first; i < c.layers; ++i) {
+        ov_bf16* sx = ckpt + (size_t)(i - first) * xe;
+        ov_bf16* y = i + 1 < c.layers ? sx + xe : x;
+        const int rc = forward_saving_layer(c, t->blocks[i], slot_at(c, sx, (ov_bf16*)slot, M), y, B, L, stream);
+        if (rc) return rc;
+    }
+    return OV_OK;
+}
+
+// ov_tower_backward_partial over checkpoints: before its block backward, each layer's slot is rebuilt in `slot` from ckpt[i - first]
+// by the forward's own launches (forward_saving_layer without c_proj: the backward never reads the block output), except the top
+// layer's when the caller says `slot` still holds it from ov_tower_forward_checkpointed.  The same grads / want_dx / lowest-layer
+// rules; every gradient is bitwise ov_tower_backward_partial's over ov_tower_forward_saving_from's slots.
+extern "C" int ov_tower_backward_checkpointed(const ov_tower* t, int first, const ov_bf16* ckpt, void* slot, size_t slot_bytes,
+                                              int slot_holds_top, ov_bf16* dx, const ov_block_grads* grads, int want_dx, int B, int L,
+                                              void* workspace, size_t workspace_bytes, ov_stream_t stream) {
+    if (!t || !dx || B <= 0 || L <= 0 || first < 0 || first > t->cfg.layers) return OV_ERR_INVALID;
+    const ov_tower_cfg& c = t->cfg;
+    if (first == c.layers) return OV_OK;                          // nothing kept: d(input of layer `first`) = d(output), already in dx
+    if (!ckpt || !slot || !grads || !workspace) return OV_ERR_INVALID;
+    int lo = want_dx ? first : c.layers;                          // the lowest layer that runs
+    for (int i = c.layers - 1; i >= first; --i) {
+        const int p = block_grad_pairs(&grads[i - first]);
+        if (p < 0) return OV_ERR_INVALID;                          // a pair with one NULL pointer, or a misaligned one
+        if (p && i < lo) lo = i;
+    }
+    if (tower_fp8(t)) return OV_ERR_UNSUPPORTED;                   // the recompute runs the bf16 forward
+    const size_t need = ov_tower_backward_partial_workspace_bytes(t, B, L);
+    if (need == 0) return OV_ERR_UNSUPPORTED;                       // block_cfg_ok: width % 64, head_dim % 8 and <= 96, mlp_pad % 64
+    if (workspace_bytes < need || slot_bytes < ov_tower_slot_bytes(t, B, L)) return OV_ERR_WORKSPACE;
+    if (((uintptr_t)ckpt | (uintptr_t)slot | (uintptr_t)dx | (uintptr_t)workspace) & 15) return OV_ERR_INVALID;
+    for (int i = 0; i < c.layers; ++i)
+        if (!t->set[i] || t->blocks[i].qkv_colsum || t->blocks[i].fc_colsum) return OV_ERR_INVALID;
+    const int64_t M = (int64_t)B * L;
+    const size_t xe = (size_t)M * c.width;
+    for (int i = c.layers - 1; i >= lo; --i) {                    // dx holds d(block output) on entry and d(block input) on exit
+        ov_bf16* sx = const_cast<ov_bf16*>(ckpt) + (size_t)(i - first) * xe;
+        const Slot s = slot_at(c, sx, (ov_bf16*)slot, M);
+        int rc;
+        if (!(slot_holds_top && i == c.layers - 1) && (rc = forward_saving_layer(c, t->blocks[i], s, nullptr, B, L, stream))) return rc;
+        const ov_block_saved sv = block_saved_of(c, s, L);
+        rc = block_backward_partial(&c, &t->blocks[i], sx, &sv, dx, (i > lo || want_dx) ? dx : nullptr, &grads[i - first], B, L,
+                                    workspace, workspace_bytes, stream);
         if (rc) return rc;
     }
     return OV_OK;

@@ -637,6 +637,10 @@ class VisionTransformer(nn.Module):
         return self._pk.get((self.conv1.weight, self.class_embedding, self.positional_embedding, self.ln_post.weight,
                              self.ln_post.bias, self.proj), build)
 
+    def set_grad_checkpointing(self, enable=True):
+        """transformer.py:596: recompute this tower's block intermediates in the training backward (see CLIP.set_grad_checkpointing)."""
+        self.transformer.grad_checkpointing = enable
+
     def lock(self, unlocked_groups: int = 0, freeze_bn_stats: bool = False) -> None:
         """LiT locking (transformer.py:542-572): freeze the whole tower, then train again the last ``unlocked_groups`` of its
         parameter groups (``_lock_groups``).  ``freeze_bn_stats`` is accepted and has no effect, as in the reference (there is no
@@ -953,8 +957,11 @@ class CLIP(nn.Module):
         self.visual.lock(unlocked_groups=unlocked_groups, freeze_bn_stats=freeze_bn_stats)
 
     def set_grad_checkpointing(self, enable=True):
-        if enable:
-            raise NotImplementedError("not needed: openvision_amd.training keeps per-layer activations and recomputes the rest itself")
+        """Activation recomputation on the training path (model.py:261-263 of the reference; its trainer's remat='full' per block):
+        ``openvision_amd.training`` then keeps only each block's input and recomputes the block's intermediates just before its
+        backward, bitwise the same loss and gradients.  The inference entry points ignore the flag."""
+        self.visual.set_grad_checkpointing(enable)
+        self.transformer.grad_checkpointing = enable
 
 
 def logits(a: torch.Tensor, b: torch.Tensor, scale=1.0) -> torch.Tensor:

@@ -11,10 +11,13 @@ Opt-in: the inference entry points of ``openvision_amd.model`` never build a gra
     loss = ClipLoss(...)(img_f, txt_f, scale)                               # openvision_amd.loss.ClipLoss
     loss.backward()                                                         # .grad on every parameter, as with the reference
 
-Activation memory: the tower keeps, per layer and token, the block input, the packed qkv, the attention output, the mid-block
-residual, both LayerNorm outputs and the c_fc pre-activation and activation (8 D + 2 mlp bf16: 52 GB for L/14 at B=256, sized for
-the 288 GB of an MI355X); the backward runs nothing of the forward again.  Every preset is covered: head dims 72 / 80 (So400m, H/14) take the streaming
-attention backward with d zero-padded to 96, an MLP width that is not a multiple of 64 (So400m) is zero-padded.
+Activation memory: by default the tower keeps, per layer and token, the block input, the packed qkv, the attention output, the
+mid-block residual, both LayerNorm outputs and the c_fc pre-activation and activation (8 D + 2 mlp bf16: 52 GB for L/14 at B=256);
+the backward runs nothing of the forward again.  ``model.set_grad_checkpointing()`` (the reference's remat='full' per block) keeps
+only each block's input (D bf16 per layer and token: 3.2 GB) plus one layer's intermediates, and the backward recomputes each
+block's intermediates with the forward's own launches just before that block's backward: the same loss and gradients, bit for bit.
+Every preset is covered: head dims 72 / 80 (So400m, H/14) take the streaming attention backward with d zero-padded to 96, an MLP
+width that is not a multiple of 64 (So400m) is zero-padded.
 """
 from __future__ import annotations
 
@@ -56,8 +59,9 @@ def _pad_mlp(ts: List[torch.Tensor], mlp: int, mlp_pad: int) -> List[torch.Tenso
 
 
 class _Pool:
-    """Grow-only pool of device buffers, one free list per purpose ("saved": the activations a forward keeps for its backward, 19 GB at
-    L/14, B = 256; "ws": kernel workspaces): a step takes what it needs in forward and hands it back at the end of backward, so
+    """Grow-only pool of device buffers, one free list per purpose ("saved": the activations a forward keeps for its backward, or the
+    block inputs under recomputation; "slot": one layer's intermediates under recomputation; "ws": kernel workspaces): a step takes
+    what it needs in forward and hands it back at the end of backward, so
     steady-state training allocates nothing per step.  Retention sizes itself: per purpose the pool keeps as many free buffers as
     were ever outstanding at once (one saved buffer per chunk of `set_backward_chunk_layers`, one workspace), and a request is served
     by the SMALLEST free buffer of its own purpose that fits, so a workspace never takes a saved-activation buffer."""
@@ -66,6 +70,7 @@ class _Pool:
         self.lists = {}                    # purpose -> free buffers, ascending size
         self.out = {}                      # purpose -> buffers currently handed out
         self.peak = {}                     # purpose -> high-water mark of `out`
+        self.out_bytes = {}                # purpose -> bytes requested by the buffers currently handed out
 
     @property
     def free(self) -> List[torch.Tensor]:
@@ -75,13 +80,15 @@ class _Pool:
         lst = self.lists.setdefault(kind, [])
         self.out[kind] = self.out.get(kind, 0) + 1
         self.peak[kind] = max(self.peak.get(kind, 0), self.out[kind])
+        self.out_bytes[kind] = self.out_bytes.get(kind, 0) + int(nbytes)
         for i, t in enumerate(lst):
             if t.device == device and t.numel() >= nbytes:
                 t = lst.pop(i)
                 t._ovhip_gen += 1              # whoever still holds it from an earlier step can tell it was recycled
+                t._ovhip_req = int(nbytes)
                 return t
         t = torch.empty(int(nbytes) + 256, dtype=torch.uint8, device=device)
-        t._ovhip_gen, t._ovhip_kind = 0, kind
+        t._ovhip_gen, t._ovhip_kind, t._ovhip_req = 0, kind, int(nbytes)
         return t
 
     def give(self, t: torch.Tensor) -> None:
@@ -90,6 +97,7 @@ class _Pool:
         if any(u is t for u in lst):
             return
         self.out[kind] = max(0, self.out.get(kind, 0) - 1)
+        self.out_bytes[kind] = max(0, self.out_bytes.get(kind, 0) - getattr(t, "_ovhip_req", 0))
         lst.append(t)
         lst.sort(key=lambda x: x.numel())
         del lst[:-max(1, self.peak.get(kind, 1))]        # too many: the smallest go (a grown request made them useless)
@@ -124,7 +132,12 @@ class _TowerFn(torch.autograd.Function):
     (weight, bias) pair of a block: a pair is frozen when both of its tensors are.  When x needs no gradient either, the blocks below
     the lowest trainable one run without keeping anything (``ov_tower_forward_saving_from``) and the backward stops at that block
     (``ov_tower_backward_partial``); frozen blocks above it run input-only.  Every gradient that is computed is bitwise the one of
-    the all-trainable path; with everything trainable the node makes exactly that path's calls."""
+    the all-trainable path; with everything trainable the node makes exactly that path's calls.
+
+    Recomputation (``transformer.grad_checkpointing``): the same `first` rule, but ``ov_tower_forward_checkpointed`` keeps only the
+    inputs of layers [first, hi - lo) ("saved") and one layer's intermediates ("slot"); ``ov_tower_backward_checkpointed`` rebuilds
+    each block's slot before its backward.  The node holding the tower's last block keeps its slot until its backward (no recompute
+    of that block); every other node hands its slot back after the forward.  Loss and gradients are bitwise those without it."""
 
     @staticmethod
     def forward(ctx, transformer, lo, hi, x, *params):
@@ -144,14 +157,32 @@ class _TowerFn(torch.autograd.Function):
         if not handle:
             raise _lib.OvhipError("ov_tower_create failed")
         pool = _train_state(transformer)["pool"]
-        saved = None
+        remat = bool(getattr(transformer, "grad_checkpointing", False))
+        saved = slot = None
         try:
             keep = _packed_blocks(transformer, params, mlp, mlp_pad, (lo, hi))
             for i, ts in enumerate(keep):
                 bw = _lib.BlockWeights(*[C.c_void_p(t.data_ptr()) for t in ts], None, None)
                 check(lib.ov_tower_set_block(handle, i, C.byref(bw)), "ov_tower_set_block")
             xb = x.detach().to(torch.bfloat16).contiguous().clone()
-            if every:
+            if remat:
+                nslot = lib.ov_tower_slot_bytes(handle, bsz, seq)
+                if first < len(blocks):
+                    saved = pool.take(lib.ov_tower_checkpoint_bytes(handle, first, bsz, seq), x.device, "saved")
+                slot = pool.take(nslot, x.device, "slot")
+                try:
+                    check(lib.ov_tower_forward_checkpointed(handle, first, ptr(xb), ptr(saved), ptr(slot), nslot, bsz, seq, stream_ptr()),
+                          "ov_tower_forward_checkpointed")
+                except BaseException:
+                    for t in (saved, slot):
+                        if t is not None:
+                            pool.give(t)
+                    raise
+                if saved is None or hi < len(transformer.resblocks):   # only the top node keeps its slot for the backward
+                    pool.give(slot)
+                    slot = None
+                ws = None
+            elif every:
                 saved = pool.take(lib.ov_tower_saved_bytes(handle, bsz, seq), x.device, "saved")
                 nbytes = lib.ov_tower_workspace_bytes(handle, bsz, seq)
                 ws = pool.take(nbytes, x.device)
@@ -171,6 +202,7 @@ class _TowerFn(torch.autograd.Function):
         ctx.cfg, ctx.keep, ctx.saved, ctx.shape, ctx.mlp, ctx.pool = cfg, keep, saved, (bsz, seq, d), mlp, pool
         ctx.every, ctx.first, ctx.pairs, ctx.need = every, first, pairs, (need_x, need_p)
         ctx.saved_gen = saved._ovhip_gen if saved is not None else None
+        ctx.remat, ctx.slot = remat, slot
         ctx.x_dtype, ctx.p_dtypes = x.dtype, [p.dtype for p in params]
         return xb.to(x.dtype)
 
@@ -190,7 +222,26 @@ class _TowerFn(torch.autograd.Function):
                 bw = _lib.BlockWeights(*[C.c_void_p(t.data_ptr()) for t in ts], None, None)
                 check(lib.ov_tower_set_block(handle, i, C.byref(bw)), "ov_tower_set_block")
             dx = grad_out.detach().to(torch.bfloat16).contiguous().clone()
-            if ctx.every:
+            if ctx.remat:             # the partial backward's grads rules; with everything trainable every pair is requested
+                grads = [[None] * 12 for _ in range(first)]
+                grads += [[torch.empty_like(t) if ctx.pairs[i][j // 2] else None for j, t in enumerate(ctx.keep[i])]
+                          for i in range(first, layers)]
+                garr = (_lib.BlockGrads * (layers - first))(*[_lib.BlockGrads(*[ptr(t) for t in g]) for g in grads[first:]])
+                nbytes = lib.ov_tower_backward_partial_workspace_bytes(handle, bsz, seq)
+                nslot = lib.ov_tower_slot_bytes(handle, bsz, seq)
+                slot, holds = ctx.slot, ctx.slot is not None
+                ctx.slot = None               # the backward overwrites it: a second backward over this graph recomputes the top block
+                ws = ctx.pool.take(nbytes, dx.device)
+                if slot is None:
+                    slot = ctx.pool.take(nslot, dx.device, "slot")
+                try:
+                    check(lib.ov_tower_backward_checkpointed(handle, first, ptr(ctx.saved), ptr(slot), nslot, int(holds), ptr(dx), garr,
+                                                             int(need_x), bsz, seq, ptr(ws), nbytes, stream_ptr()),
+                          "ov_tower_backward_checkpointed")
+                finally:                      # an error leaves nothing outstanding either
+                    for t in (slot, ws, ctx.saved):
+                        ctx.pool.give(t)
+            elif ctx.every:
                 grads = [[torch.empty_like(t) for t in ts] for ts in ctx.keep]
                 garr = (_lib.BlockGrads * layers)(*[_lib.BlockGrads(*[C.c_void_p(t.data_ptr()) for t in g]) for g in grads])
                 nbytes = lib.ov_tower_backward_workspace_bytes(handle, bsz, seq)
@@ -206,8 +257,9 @@ class _TowerFn(torch.autograd.Function):
                 ws = ctx.pool.take(nbytes, dx.device)
                 check(lib.ov_tower_backward_partial(handle, first, ptr(ctx.saved), ptr(dx), garr, int(need_x), bsz, seq, ptr(ws), nbytes,
                                                     stream_ptr()), "ov_tower_backward_partial")
-            ctx.pool.give(ws)
-            ctx.pool.give(ctx.saved)         # ordered on the stream: the next forward's writes come after this backward's reads
+            if not ctx.remat:
+                ctx.pool.give(ws)
+                ctx.pool.give(ctx.saved)     # ordered on the stream: the next forward's writes come after this backward's reads
         finally:
             lib.ov_tower_destroy(handle)
         mlp = ctx.mlp                                             # drop the (exactly zero) gradients of the MLP padding

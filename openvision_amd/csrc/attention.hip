@@ -1003,7 +1003,7 @@ int attention_impl(const ov_bf16* qkv, int64_t ld_qkv, ov_bf16* out, int64_t ld_
     if (ld_qkv % 8 || ld_out % 8 || ld_qkv < 3 * H * hd || ld_out < H * hd) return OV_ERR_INVALID;
     if (((uintptr_t)qkv | (uintptr_t)out) & 15) return OV_ERR_INVALID;
     const bool out8 = out_amax != nullptr;
-    if (lse != nullptr && (hd != 64 || (L + 31) / 32 * 32 > 288 || out8)) return OV_ERR_UNSUPPORTED;   // the resident backward's shapes only
+    if (lse != nullptr && (!ov_attn_bwd_resident(hd, L) || out8)) return OV_ERR_UNSUPPORTED;   // the resident backward's shapes only
     const int nqt = (L + 31) / 32, lp = nqt * 32;
     const float scale_log2 = scale * 1.4426950408889634f;
     // the persistent kernel's row offsets are 32-bit: an image spanning 2 GiB of rows or more (a caller's huge row pitch) goes to the

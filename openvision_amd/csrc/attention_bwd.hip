@@ -536,7 +536,7 @@ __global__ __launch_bounds__(512) void attn_bwd_stream_kv(const AttnBwdSArgs g) 
 }  // namespace
 
 extern "C" size_t ov_attention_backward_workspace_bytes(int B, int L, int H, int hd) {
-    if (B <= 0 || L <= 0 || H <= 0 || (hd == 64 && L <= 288)) return 0;       // the resident kernel needs none
+    if (B <= 0 || L <= 0 || H <= 0 || ov_attn_bwd_resident(hd, L)) return 0;  // the resident kernel needs none
     const int64_t lpad = (int64_t)(L + CH - 1) / CH * CH;
     return (size_t)2 * B * H * lpad * sizeof(float);
 }
@@ -579,7 +579,7 @@ extern "C" int ov_attention_backward_saved(const ov_bf16* qkv, int64_t ld_qkv, c
     a.L = L; a.H = H; a.KC = (L + 31) / 32 * 32;
     a.scale = scale; a.scale_log2 = scale * 1.4426950408889634f;
     a.lse_in = lse;
-    if (hd == 64 && L <= 288) {                                 // Q, K, V, dO of a head resident in LDS
+    if (ov_attn_bwd_resident(hd, L)) {                          // Q, K, V, dO of a head resident in LDS
         static OvPerDeviceOnce attr;
         const int dev = ov_current_device();
         if (attr.need(dev)) {

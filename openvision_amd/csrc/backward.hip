@@ -695,7 +695,7 @@ inline InputBufs plan_input(const ov_tower_cfg* c, int B, int L, bool mlp, char*
 }
 
 inline const float* lse_if_used(const ov_tower_cfg* c, int L, const float* lse) {   // ov_tower_forward_saving's rule
-    return (c->width / c->heads == 64 && (L + 31) / 32 * 32 <= 288) ? lse : nullptr;
+    return ov_attn_bwd_resident(c->width / c->heads, L) ? lse : nullptr;
 }
 
 // the attention half: dx = dx1 + d(x + out_proj(attn(ln_1(x))))/dx . dx1

@@ -22,6 +22,11 @@ typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
 
 static inline int ov_hip(hipError_t e) { return e == hipSuccess ? OV_OK : OV_ERR_HIP - (int)e; }
 
+// The resident attention backward (attention_bwd.hip: a head's Q, K, V and dO held in LDS) takes head_dim 64 and L <= 288; every other
+// shape goes to the streaming kernels.  Only the resident kernel reads the forward's row log-sum-exp (ov_attention_lse), so this also
+// decides where the training forward keeps it and the backward passes it on.
+static inline bool ov_attn_bwd_resident(int hd, int L) { return hd == 64 && L <= 288; }
+
 // ---- per-device host state: function attributes (hipFuncSetAttribute) and device properties belong to ONE device; a process
 // may drive several (one host thread each).  Device ids beyond OV_MAX_DEVICES - 1 share the last slot's "not yet done" answer
 // (the attribute is then set on every launch: correct, just slower).

@@ -268,7 +268,7 @@ extern "C" int ov_block_attn_forward_saving(const ov_tower_cfg* cfg, const ov_bl
     if (((uintptr_t)x | (uintptr_t)qkv | (uintptr_t)attn_out | (uintptr_t)x1) & 15) return OV_ERR_INVALID;
     const int64_t M = (int64_t)B * L;
     const float scale = 1.0f / sqrtf((float)hd);
-    const bool keep_lse = lse != nullptr && hd == 64 && (L + 31) / 32 * 32 <= 288;
+    const bool keep_lse = lse != nullptr && ov_attn_bwd_resident(hd, L);
     int rc;
     if ((rc = ov_layernorm(x, OV_BF16, D, w->ln1_w, w->ln1_b, attn_out, OV_BF16, D, M, D, cfg->ln_eps, stream))) return rc;
     if ((rc = ov_gemm(attn_out, D, w->qkv_w, D, w->qkv_b, qkv, 3 * D, M, 3 * D, D, OV_EPI_BIAS, nullptr, 0, 0, 0, 0, stream))) return rc;

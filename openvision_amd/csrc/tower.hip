@@ -539,22 +539,26 @@ extern "C" int ov_tower_forward(const ov_tower* t, ov_bf16* x, int B, int L, voi
 }
 
 // ---- training-side entry points: keep every block's input, run the blocks' backward in reverse -------------
-extern "C" int ov_block_backward(const ov_tower_cfg* cfg, const ov_block_weights* w, const ov_bf16* x, const ov_block_saved* saved,
-                                 const ov_bf16* dy, ov_bf16* dx, const ov_block_grads* g, int B, int L, void* workspace,
-                                 size_t workspace_bytes, ov_stream_t stream);
-extern "C" size_t ov_block_backward_workspace_bytes(const ov_tower_cfg* cfg, int B, int L);
+// backward.hip, one block over its kept activations (arguments checked here): block_backward_partial computes the requested pairs of g
+// (block_grad_pairs: bit k = pair k, -1 for a half-NULL or misaligned pair) and dx unless NULL, with ov_block_backward's launches for
+// them; block_backward_input computes dx alone, in a smaller workspace.
+int block_grad_pairs(const ov_block_grads* g);
+int block_backward_partial(const ov_tower_cfg* cfg, const ov_block_weights* w, const ov_bf16* x, const ov_block_saved* s, const ov_bf16* dy,
+                           ov_bf16* dx, const ov_block_grads* g, int B, int L, void* workspace, size_t workspace_bytes, ov_stream_t stream);
+size_t block_backward_input_workspace_bytes(const ov_tower_cfg* cfg, int B, int L);
+int block_backward_input(const ov_tower_cfg* cfg, const ov_block_weights* w, const ov_bf16* x, const ov_block_saved* s, const ov_bf16* dy,
+                         ov_bf16* dx, int B, int L, void* workspace, ov_stream_t stream);
 
 // saved activations of one layer: [x | qkv | attention out | x1 | ln_1 out | ln_2 out | c_fc pre-activation | c_fc activation],
 // 8 D + 2 mlp_pad bf16 per token (the default keeps them all; ov_tower_forward_checkpointed keeps only x and recomputes the rest
 // per block in the backward)
 // + per layer the attention's row log-sum-exp, fp32 [B * heads][L rounded up to 32] (ov_attention_lse; used by the backward where the
-// resident kernel applies: head_dim 64, L <= 288)
+// resident kernel applies: ov_attn_bwd_resident)
 static inline size_t saved_per_token(const ov_tower_cfg& c) { return (size_t)8 * c.width + 2 * (size_t)c.mlp_pad; }
 static inline size_t saved_lse_elems(const ov_tower_cfg& c, int B, int L) {      // in bf16 elements, a multiple of 8 (16-byte sections)
     return ((size_t)2 * B * c.heads * ((L + 31) / 32 * 32) + 7) / 8 * 8;
 }
 static inline size_t saved_per_layer(const ov_tower_cfg& c, int B, int L) { return (size_t)B * L * saved_per_token(c) + saved_lse_elems(c, B, L); }
-static inline bool saved_lse_used(const ov_tower_cfg& c, int L) { return c.width / c.heads == 64 && (L + 31) / 32 * 32 <= 288; }
 extern "C" size_t ov_tower_saved_bytes(const ov_tower* t, int B, int L) {
     if (!t || B <= 0 || L <= 0) return 0;
     return (size_t)t->cfg.layers * saved_per_layer(t->cfg, B, L) * sizeof(ov_bf16);
@@ -562,7 +566,7 @@ extern "C" size_t ov_tower_saved_bytes(const ov_tower* t, int B, int L) {
 
 namespace {
 // one layer's slot: [x | qkv | attention out | x1 | ln_1 out | ln_2 out | c_fc pre-activation | c_fc activation | lse]; `rest` = where
-// the part after x starts (sx + M D in `saved`; elsewhere for the layers ov_tower_forward_saving_from does not keep)
+// the part after x starts (sx + M D in `saved`; elsewhere for the layers a Layout does not keep whole)
 struct Slot { ov_bf16 *x, *qkv, *o, *x1, *n1, *n2, *pre, *act; float* lse; };
 inline Slot slot_at(const ov_tower_cfg& c, ov_bf16* sx, ov_bf16* rest, int64_t M) {
     Slot s;
@@ -580,12 +584,24 @@ inline Slot slot_at(const ov_tower_cfg& c, ov_bf16* sx, ov_bf16* rest, int64_t M
 inline ov_block_saved block_saved_of(const ov_tower_cfg& c, const Slot& s, int L) {
     ov_block_saved sv;
     sv.qkv = s.qkv; sv.attn_out = s.o; sv.x1 = s.x1; sv.ln1_out = s.n1; sv.ln2_out = s.n2; sv.fc_pre = s.pre; sv.fc_act = s.act;
-    sv.attn_lse = saved_lse_used(c, L) ? s.lse : nullptr;
+    sv.attn_lse = ov_attn_bwd_resident(c.width / c.heads, L) ? s.lse : nullptr;
     return sv;
 }
-inline ov_block_saved block_saved_at(const ov_tower_cfg& c, const ov_bf16* sx, int B, int L) {
-    const int64_t M = (int64_t)B * L;
-    return block_saved_of(c, slot_at(c, const_cast<ov_bf16*>(sx), const_cast<ov_bf16*>(sx) + (size_t)M * c.width, M), L);
+
+// Where a kept layer i >= first has its input and the rest of its slot: x + (i - first) x_stride and rest + (i - first) rest_stride.
+// Saving (ov_tower_forward_saving[_from]): a whole slot per layer in `saved`.  Checkpointed: the inputs M D apart in ckpt, and one slot
+// that every layer shares (stride 0).
+struct Layout { ov_bf16* x; size_t x_stride; ov_bf16* rest; size_t rest_stride; };
+inline Layout saving_layout(const ov_tower_cfg& c, const ov_bf16* saved, int B, int L) {
+    ov_bf16* s = const_cast<ov_bf16*>(saved);
+    const size_t spl = saved_per_layer(c, B, L);
+    return {s, spl, s ? s + (size_t)B * L * c.width : nullptr, spl};
+}
+inline Layout checkpointed_layout(const ov_tower_cfg& c, const ov_bf16* ckpt, void* slot, int B, int L) {
+    return {const_cast<ov_bf16*>(ckpt), (size_t)B * L * c.width, (ov_bf16*)slot, 0};
+}
+inline Slot layer_slot(const ov_tower_cfg& c, const Layout& ly, int k, int64_t M) {     // k = i - first
+    return slot_at(c, ly.x + (size_t)k * ly.x_stride, ly.rest + (size_t)k * ly.rest_stride, M);
 }
 
 // One block of the saving forward: the same operator sequence as run_block, with qkv / attention output / x1 / ... written where the
@@ -599,8 +615,8 @@ int forward_saving_layer(const ov_tower_cfg& c, const ov_block_weights& w, const
     int rc;
     if ((rc = ov_layernorm(s.x, OV_BF16, D, w.ln1_w, w.ln1_b, s.n1, OV_BF16, D, M, D, c.ln_eps, stream))) return rc;
     if ((rc = ov_gemm(s.n1, D, w.qkv_w, D, w.qkv_b, s.qkv, 3 * D, M, 3 * D, D, OV_EPI_BIAS, nullptr, 0, 0, 0, 0, stream))) return rc;
-    rc = saved_lse_used(c, L) ? ov_attention_lse(s.qkv, 3 * D, s.o, D, s.lse, B, L, H, hd, scale, stream)
-                              : ov_attention(s.qkv, 3 * D, s.o, D, B, L, H, hd, scale, stream);
+    rc = ov_attn_bwd_resident(hd, L) ? ov_attention_lse(s.qkv, 3 * D, s.o, D, s.lse, B, L, H, hd, scale, stream)
+                                     : ov_attention(s.qkv, 3 * D, s.o, D, B, L, H, hd, scale, stream);
     if (rc) return rc;
     if ((rc = ov_gemm(s.o, D, w.out_w, D, w.out_b, s.x1, D, M, D, D, OV_EPI_BIAS_RESIDUAL, s.x, D, 0, 0, 0, stream))) return rc;
     if ((rc = ov_layernorm(s.x1, OV_BF16, D, w.ln2_w, w.ln2_b, s.n2, OV_BF16, D, M, D, c.ln_eps, stream))) return rc;
@@ -609,34 +625,82 @@ int forward_saving_layer(const ov_tower_cfg& c, const ov_block_weights& w, const
     return ov_gemm(s.act, c.mlp_pad, w.proj_w, c.mlp_pad, w.proj_b, y, D, M, D, c.mlp_pad, OV_EPI_BIAS_RESIDUAL, s.x1, D, 0, 0, 0, stream);
 }
 
-// layers [first, layers) keep their slots in `saved` (slot 0 = layer first); layer i reads its input from its own slot and writes its
-// output straight into the next slot (the last one into x): one copy for the kept part of the tower
-int forward_saving_kept(const ov_tower* t, int first, ov_bf16* x, ov_bf16* saved, int B, int L, ov_stream_t stream) {
+// The training forward: layers [0, first) run in place on x with their intermediates in `scratch` (the same operators on the same
+// values, nothing kept); then x is copied into layer first's input, and each kept layer reads its input from its slot and writes its
+// output straight into the next layer's input, the top layer into x.
+int forward_walk(const ov_tower* t, int first, ov_bf16* x, ov_bf16* scratch, const Layout& ly, int B, int L, ov_stream_t stream) {
     const ov_tower_cfg& c = t->cfg;
     const int64_t M = (int64_t)B * L;
-    const size_t spl = saved_per_layer(c, B, L);
-    hipError_t e = hipMemcpyAsync(saved, x, (size_t)M * c.width * 2, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+    for (int i = 0; i < first; ++i) {
+        const int rc = forward_saving_layer(c, t->blocks[i], slot_at(c, x, scratch, M), x, B, L, stream);
+        if (rc) return rc;
+    }
+    if (first == c.layers) return OV_OK;
+    const hipError_t e = hipMemcpyAsync(ly.x, x, (size_t)M * c.width * sizeof(ov_bf16), hipMemcpyDeviceToDevice, (hipStream_t)stream);
     if (e != hipSuccess) return OV_ERR_HIP - (int)e;
     for (int i = first; i < c.layers; ++i) {
-        ov_bf16* sx = saved + (size_t)(i - first) * spl;
-        ov_bf16* y = i + 1 < c.layers ? sx + spl : x;
-        const int rc = forward_saving_layer(c, t->blocks[i], slot_at(c, sx, sx + (size_t)M * c.width, M), y, B, L, stream);
+        const Slot s = layer_slot(c, ly, i - first, M);
+        const int rc = forward_saving_layer(c, t->blocks[i], s, i + 1 < c.layers ? s.x + ly.x_stride : x, B, L, stream);
         if (rc) return rc;
     }
     return OV_OK;
 }
+
+// The lowest layer a backward over the kept layers [first, layers) runs: `first` when d(input) is wanted, otherwise the lowest one with
+// a requested pair (layers: none).  -1 when a pair of grads has one NULL pointer or a misaligned one.
+int lowest_layer(const ov_tower* t, int first, const ov_block_grads* grads, bool want_dx) {
+    int lo = want_dx ? first : t->cfg.layers;
+    for (int i = t->cfg.layers - 1; i >= first; --i) {
+        const int p = block_grad_pairs(&grads[i - first]);
+        if (p < 0) return -1;
+        if (p && i < lo) lo = i;
+    }
+    return lo;
+}
+
+// The training backward: layers layers-1 .. lo in reverse; dx holds d(block output) on entry and d(block input) on exit, and layer lo
+// writes it only when want_dx.  rebuild: each layer's slot is first rebuilt from its input by the forward's own launches without c_proj
+// (the backward never reads the block output), except the top layer's when top_kept.  grads[i - first] -> block_backward_partial;
+// grads = NULL -> block_backward_input (input gradients only).
+int backward_walk(const ov_tower* t, int first, int lo, const Layout& ly, bool rebuild, bool top_kept, ov_bf16* dx,
+                  const ov_block_grads* grads, bool want_dx, int B, int L, void* workspace, size_t workspace_bytes, ov_stream_t stream) {
+    const ov_tower_cfg& c = t->cfg;
+    const int64_t M = (int64_t)B * L;
+    for (int i = c.layers - 1; i >= lo; --i) {
+        const Slot s = layer_slot(c, ly, i - first, M);
+        int rc;
+        if (rebuild && !(top_kept && i == c.layers - 1) && (rc = forward_saving_layer(c, t->blocks[i], s, nullptr, B, L, stream)))
+            return rc;
+        const ov_block_saved sv = block_saved_of(c, s, L);
+        rc = grads ? block_backward_partial(&c, &t->blocks[i], s.x, &sv, dx, (i > lo || want_dx) ? dx : nullptr, &grads[i - first], B, L,
+                                            workspace, workspace_bytes, stream)
+                   : block_backward_input(&c, &t->blocks[i], s.x, &sv, dx, dx, B, L, workspace, stream);
+        if (rc) return rc;
+    }
+    return OV_OK;
+}
+
+// The checks the training entry points share, made after their own pointer checks and reported in this order: an fp8 tower where the
+// entry point runs the bf16 forward (bf16) or a block shape the backward kernels do not take (!shape_ok; backward.hip's block_cfg_ok:
+// width % 64, head_dim % 8 and <= 96, mlp_pad % 64); a short workspace; a pointer in `ptrs` off 16 bytes; a block that is not set or
+// holds LN-folded weights (the walks run and differentiate the module's own).
+int check_walk(const ov_tower* t, bool bf16, bool shape_ok, bool ws_ok, uintptr_t ptrs) {
+    if ((bf16 && tower_fp8(t)) || !shape_ok) return OV_ERR_UNSUPPORTED;
+    if (!ws_ok) return OV_ERR_WORKSPACE;
+    if (ptrs & 15) return OV_ERR_INVALID;
+    for (int i = 0; i < t->cfg.layers; ++i)
+        if (!t->set[i] || t->blocks[i].qkv_colsum || t->blocks[i].fc_colsum) return OV_ERR_INVALID;
+    return OV_OK;
+}
 }  // namespace
 
+// (every intermediate lands in `saved`: the workspace is checked but stays unused)
 extern "C" int ov_tower_forward_saving(const ov_tower* t, ov_bf16* x, ov_bf16* saved, int B, int L, void* workspace,
                                        size_t workspace_bytes, ov_stream_t stream) {
     if (!t || !x || !saved || !workspace || B <= 0 || L <= 0) return OV_ERR_INVALID;
-    if (tower_fp8(t)) return OV_ERR_UNSUPPORTED;                   // the backward differentiates the bf16 path
-    if (workspace_bytes < ov_tower_workspace_bytes(t, B, L)) return OV_ERR_WORKSPACE;
-    if (((uintptr_t)x | (uintptr_t)saved | (uintptr_t)workspace) & 15) return OV_ERR_INVALID;
-    const ov_tower_cfg& c = t->cfg;                            // (every intermediate lands in `saved`: the workspace stays unused)
-    for (int i = 0; i < c.layers; ++i)
-        if (!t->set[i] || t->blocks[i].qkv_colsum || t->blocks[i].fc_colsum) return OV_ERR_INVALID;   // the module's own weights
-    return forward_saving_kept(t, 0, x, saved, B, L, stream);
+    const int rc = check_walk(t, true, true, workspace_bytes >= ov_tower_workspace_bytes(t, B, L),
+                              (uintptr_t)x | (uintptr_t)saved | (uintptr_t)workspace);
+    return rc ? rc : forward_walk(t, 0, x, nullptr, saving_layout(t->cfg, saved, B, L), B, L, stream);
 }
 
 // ---- frozen lower layers: keep only layers [first, layers) ----------------------------------------------------------------------------
@@ -659,21 +723,11 @@ extern "C" size_t ov_tower_forward_saving_from_workspace_bytes(const ov_tower* t
 extern "C" int ov_tower_forward_saving_from(const ov_tower* t, int first, ov_bf16* x, ov_bf16* saved, int B, int L, void* workspace,
                                             size_t workspace_bytes, ov_stream_t stream) {
     if (!t || !x || B <= 0 || L <= 0 || first < 0 || first > t->cfg.layers) return OV_ERR_INVALID;
-    const ov_tower_cfg& c = t->cfg;
-    if (first < c.layers && !saved) return OV_ERR_INVALID;
+    if (first < t->cfg.layers && !saved) return OV_ERR_INVALID;
     const size_t need = ov_tower_forward_saving_from_workspace_bytes(t, first, B, L);
     if (need > 0 && !workspace) return OV_ERR_INVALID;
-    if (tower_fp8(t)) return OV_ERR_UNSUPPORTED;
-    if (workspace_bytes < need) return OV_ERR_WORKSPACE;
-    if (((uintptr_t)x | (uintptr_t)saved | (uintptr_t)workspace) & 15) return OV_ERR_INVALID;
-    for (int i = 0; i < c.layers; ++i)
-        if (!t->set[i] || t->blocks[i].qkv_colsum || t->blocks[i].fc_colsum) return OV_ERR_INVALID;
-    const int64_t M = (int64_t)B * L;
-    for (int i = 0; i < first; ++i) {                                // x -> x in place, the same operators on the same values
-        const int rc = forward_saving_layer(c, t->blocks[i], slot_at(c, x, (ov_bf16*)workspace, M), x, B, L, stream);
-        if (rc) return rc;
-    }
-    return first < c.layers ? forward_saving_kept(t, first, x, saved, B, L, stream) : OV_OK;
+    const int rc = check_walk(t, true, true, workspace_bytes >= need, (uintptr_t)x | (uintptr_t)saved | (uintptr_t)workspace);
+    return rc ? rc : forward_walk(t, first, x, (ov_bf16*)workspace, saving_layout(t->cfg, saved, B, L), B, L, stream);
 }
 
 extern "C" size_t ov_tower_backward_workspace_bytes(const ov_tower* t, int B, int L) {
@@ -681,27 +735,32 @@ extern "C" size_t ov_tower_backward_workspace_bytes(const ov_tower* t, int B, in
     return ov_block_backward_workspace_bytes(&t->cfg, B, L);
 }
 
+// Every pair of every layer and dx: block_backward_partial then makes exactly ov_block_backward's launches.  The checks keep the codes
+// and the order in which a walk over ov_block_backward reported them (the top layer's, then the workspace and the alignment, then the
+// layers below; folded weights are OV_ERR_UNSUPPORTED here), but all of them come before the first launch.
 extern "C" int ov_tower_backward(const ov_tower* t, const ov_bf16* saved, ov_bf16* dx, const ov_block_grads* grads, int B, int L,
                                  void* workspace, size_t workspace_bytes, ov_stream_t stream) {
     if (!t || !saved || !dx || !grads || !workspace || B <= 0 || L <= 0) return OV_ERR_INVALID;
     const ov_tower_cfg& c = t->cfg;
     for (int i = 0; i < c.layers; ++i)
         if (!t->set[i]) return OV_ERR_INVALID;
-    for (int i = c.layers - 1; i >= 0; --i) {                     // dx holds d(block output) on entry and d(block input) on exit
-        const ov_bf16* sx = saved + (size_t)i * saved_per_layer(c, B, L);
-        const ov_block_saved sv = block_saved_at(c, sx, B, L);
-        const int rc = ov_block_backward(&c, &t->blocks[i], sx, &sv, dx, dx, &grads[i], B, L, workspace, workspace_bytes, stream);
-        if (rc) return rc;
-    }
-    return OV_OK;
+    const size_t need = ov_tower_backward_workspace_bytes(t, B, L);
+    if (need == 0) return OV_ERR_UNSUPPORTED;                       // block_cfg_ok
+    auto layer_rc = [&](int i) -> int {
+        if (t->blocks[i].qkv_colsum || t->blocks[i].fc_colsum) return OV_ERR_UNSUPPORTED;
+        return block_grad_pairs(&grads[i]) == 63 ? OV_OK : OV_ERR_INVALID;
+    };
+    int rc = layer_rc(c.layers - 1);
+    if (rc) return rc;
+    if (workspace_bytes < need) return OV_ERR_WORKSPACE;
+    if (((uintptr_t)saved | (uintptr_t)dx | (uintptr_t)workspace) & 15) return OV_ERR_INVALID;
+    for (int i = c.layers - 2; i >= 0; --i)
+        if ((rc = layer_rc(i))) return rc;
+    return backward_walk(t, 0, 0, saving_layout(c, saved, B, L), false, false, dx, grads, true, B, L, workspace, workspace_bytes, stream);
 }
 
 // Input gradients only (frozen weights): the same layers in reverse over the same saved activations, with the dX chain of each block
-// and no parameter-gradient work (backward.hip: block_backward_input).  dx comes out bitwise equal to ov_tower_backward's.
-size_t block_backward_input_workspace_bytes(const ov_tower_cfg* cfg, int B, int L);
-int block_backward_input(const ov_tower_cfg* cfg, const ov_block_weights* w, const ov_bf16* x, const ov_block_saved* s, const ov_bf16* dy,
-                         ov_bf16* dx, int B, int L, void* workspace, ov_stream_t stream);
-
+// and no parameter-gradient work.  dx comes out bitwise equal to ov_tower_backward's.
 extern "C" size_t ov_tower_backward_input_workspace_bytes(const ov_tower* t, int B, int L) {
     if (!t) return 0;
     return block_backward_input_workspace_bytes(&t->cfg, B, L);
@@ -710,29 +769,15 @@ extern "C" size_t ov_tower_backward_input_workspace_bytes(const ov_tower* t, int
 extern "C" int ov_tower_backward_input(const ov_tower* t, const ov_bf16* saved, ov_bf16* dx, int B, int L, void* workspace,
                                        size_t workspace_bytes, ov_stream_t stream) {
     if (!t || !saved || !dx || !workspace || B <= 0 || L <= 0) return OV_ERR_INVALID;
-    const ov_tower_cfg& c = t->cfg;
     const size_t need = ov_tower_backward_input_workspace_bytes(t, B, L);
-    if (need == 0) return OV_ERR_UNSUPPORTED;                       // block_cfg_ok: width % 64, head_dim % 8 and <= 96, mlp_pad % 64
-    if (workspace_bytes < need) return OV_ERR_WORKSPACE;
-    if (((uintptr_t)saved | (uintptr_t)dx | (uintptr_t)workspace) & 15) return OV_ERR_INVALID;
-    for (int i = 0; i < c.layers; ++i)
-        if (!t->set[i] || t->blocks[i].qkv_colsum || t->blocks[i].fc_colsum) return OV_ERR_INVALID;
-    for (int i = c.layers - 1; i >= 0; --i) {                     // dx holds d(block output) on entry and d(block input) on exit
-        const ov_bf16* sx = saved + (size_t)i * saved_per_layer(c, B, L);
-        const ov_block_saved sv = block_saved_at(c, sx, B, L);
-        const int rc = block_backward_input(&c, &t->blocks[i], sx, &sv, dx, dx, B, L, workspace, stream);
-        if (rc) return rc;
-    }
-    return OV_OK;
+    const int rc = check_walk(t, false, need > 0, workspace_bytes >= need, (uintptr_t)saved | (uintptr_t)dx | (uintptr_t)workspace);
+    return rc ? rc : backward_walk(t, 0, 0, saving_layout(t->cfg, saved, B, L), false, false, dx, nullptr, true, B, L, workspace,
+                                   workspace_bytes, stream);
 }
 
-// Partial backward (frozen parameters): the layers [first, layers) that ov_tower_forward_saving_from kept, in reverse, each through
-// block_backward_partial (backward.hip) with the pairs grads[i - first] requests.  Frozen blocks above the lowest trainable one run
-// input-only; with want_dx = 0 nothing runs below it.  Every gradient computed is bitwise ov_tower_backward's.
-int block_grad_pairs(const ov_block_grads* g);
-int block_backward_partial(const ov_tower_cfg* cfg, const ov_block_weights* w, const ov_bf16* x, const ov_block_saved* s, const ov_bf16* dy,
-                           ov_bf16* dx, const ov_block_grads* g, int B, int L, void* workspace, size_t workspace_bytes, ov_stream_t stream);
-
+// Partial backward (frozen parameters): the layers [first, layers) that ov_tower_forward_saving_from kept, in reverse, with the pairs
+// grads[i - first] requests.  Frozen blocks above the lowest trainable one run input-only; with want_dx = 0 nothing runs below it.
+// Every gradient computed is bitwise ov_tower_backward's.
 extern "C" size_t ov_tower_backward_partial_workspace_bytes(const ov_tower* t, int B, int L) {
     if (!t) return 0;
     return ov_block_backward_workspace_bytes(&t->cfg, B, L);
@@ -741,29 +786,14 @@ extern "C" size_t ov_tower_backward_partial_workspace_bytes(const ov_tower* t, i
 extern "C" int ov_tower_backward_partial(const ov_tower* t, int first, const ov_bf16* saved, ov_bf16* dx, const ov_block_grads* grads,
                                          int want_dx, int B, int L, void* workspace, size_t workspace_bytes, ov_stream_t stream) {
     if (!t || !dx || B <= 0 || L <= 0 || first < 0 || first > t->cfg.layers) return OV_ERR_INVALID;
-    const ov_tower_cfg& c = t->cfg;
-    if (first == c.layers) return OV_OK;                          // nothing kept: d(input of layer `first`) = d(output), already in dx
+    if (first == t->cfg.layers) return OV_OK;                     // nothing kept: d(input of layer `first`) = d(output), already in dx
     if (!saved || !grads || !workspace) return OV_ERR_INVALID;
-    int lo = want_dx ? first : c.layers;                          // the lowest layer that runs
-    for (int i = c.layers - 1; i >= first; --i) {
-        const int p = block_grad_pairs(&grads[i - first]);
-        if (p < 0) return OV_ERR_INVALID;                          // a pair with one NULL pointer, or a misaligned one
-        if (p && i < lo) lo = i;
-    }
+    const int lo = lowest_layer(t, first, grads, want_dx);
+    if (lo < 0) return OV_ERR_INVALID;
     const size_t need = ov_tower_backward_partial_workspace_bytes(t, B, L);
-    if (need == 0) return OV_ERR_UNSUPPORTED;                       // block_cfg_ok: width % 64, head_dim % 8 and <= 96, mlp_pad % 64
-    if (workspace_bytes < need) return OV_ERR_WORKSPACE;
-    if (((uintptr_t)saved | (uintptr_t)dx | (uintptr_t)workspace) & 15) return OV_ERR_INVALID;
-    for (int i = 0; i < c.layers; ++i)
-        if (!t->set[i] || t->blocks[i].qkv_colsum || t->blocks[i].fc_colsum) return OV_ERR_INVALID;
-    for (int i = c.layers - 1; i >= lo; --i) {                    // dx holds d(block output) on entry and d(block input) on exit
-        const ov_bf16* sx = saved + (size_t)(i - first) * saved_per_layer(c, B, L);
-        const ov_block_saved sv = block_saved_at(c, sx, B, L);
-        const int rc = block_backward_partial(&c, &t->blocks[i], sx, &sv, dx, (i > lo || want_dx) ? dx : nullptr, &grads[i - first], B, L,
-                                              workspace, workspace_bytes, stream);
-        if (rc) return rc;
-    }
-    return OV_OK;
+    const int rc = check_walk(t, false, need > 0, workspace_bytes >= need, (uintptr_t)saved | (uintptr_t)dx | (uintptr_t)workspace);
+    return rc ? rc : backward_walk(t, first, lo, saving_layout(t->cfg, saved, B, L), false, false, dx, grads, want_dx, B, L, workspace,
+                                   workspace_bytes, stream);
 }
 
 // ---- activation recomputation (the reference's remat='full' per block): keep each kept layer's input only ----------------------------
@@ -777,74 +807,32 @@ extern "C" size_t ov_tower_slot_bytes(const ov_tower* t, int B, int L) {
     return slot_rest_bytes(t->cfg, B, L);
 }
 
-// Layers below `first` as in ov_tower_forward_saving_from (x in place, intermediates in `slot`); layer i >= first reads its input from
-// ckpt[i - first], puts its intermediates in `slot` and writes its output into ckpt[i - first + 1] (the last one into x): the operators
-// of forward_saving_kept on the same values, so `slot` ends up holding exactly the top layer's saved slot (x part: ckpt[layers-1-first]).
+// The layers below `first` as in ov_tower_forward_saving_from with `slot` as their scratch; the kept layers read their inputs from ckpt
+// and share `slot`, which ends up holding exactly the top layer's saved slot (x part: ckpt[layers-1-first]).
 extern "C" int ov_tower_forward_checkpointed(const ov_tower* t, int first, ov_bf16* x, ov_bf16* ckpt, void* slot, size_t slot_bytes, int B,
                                              int L, ov_stream_t stream) {
     if (!t || !x || !slot || B <= 0 || L <= 0 || first < 0 || first > t->cfg.layers) return OV_ERR_INVALID;
-    const ov_tower_cfg& c = t->cfg;
-    if (first < c.layers && !ckpt) return OV_ERR_INVALID;
-    if (tower_fp8(t)) return OV_ERR_UNSUPPORTED;
-    if (slot_bytes < ov_tower_slot_bytes(t, B, L)) return OV_ERR_WORKSPACE;
-    if (((uintptr_t)x | (uintptr_t)ckpt | (uintptr_t)slot) & 15) return OV_ERR_INVALID;
-    for (int i = 0; i < c.layers; ++i)
-        if (!t->set[i] || t->blocks[i].qkv_colsum || t->blocks[i].fc_colsum) return OV_ERR_INVALID;
-    const int64_t M = (int64_t)B * L;
-    const size_t xe = (size_t)M * c.width;
-    for (int i = 0; i < first; ++i) {
-        const int rc = forward_saving_layer(c, t->blocks[i], slot_at(c, x, (ov_bf16*)slot, M), x, B, L, stream);
-        if (rc) return rc;
-    }
-    if (first == c.layers) return OV_OK;
-    hipError_t e = hipMemcpyAsync(ckpt, x, xe * sizeof(ov_bf16), hipMemcpyDeviceToDevice, (hipStream_t)stream);
-    if (e != hipSuccess) return OV_ERR_HIP - (int)e;
-    for (int i = first; i < c.layers; ++i) {
-        ov_bf16* sx = ckpt + (size_t)(i - first) * xe;
-        ov_bf16* y = i + 1 < c.layers ? sx + xe : x;
-        const int rc = forward_saving_layer(c, t->blocks[i], slot_at(c, sx, (ov_bf16*)slot, M), y, B, L, stream);
-        if (rc) return rc;
-    }
-    return OV_OK;
+    if (first < t->cfg.layers && !ckpt) return OV_ERR_INVALID;
+    const int rc = check_walk(t, true, true, slot_bytes >= ov_tower_slot_bytes(t, B, L), (uintptr_t)x | (uintptr_t)ckpt | (uintptr_t)slot);
+    return rc ? rc : forward_walk(t, first, x, (ov_bf16*)slot, checkpointed_layout(t->cfg, ckpt, slot, B, L), B, L, stream);
 }
 
-// ov_tower_backward_partial over checkpoints: before its block backward, each layer's slot is rebuilt in `slot` from ckpt[i - first]
-// by the forward's own launches (forward_saving_layer without c_proj: the backward never reads the block output), except the top
-// layer's when the caller says `slot` still holds it from ov_tower_forward_checkpointed.  The same grads / want_dx / lowest-layer
-// rules; every gradient is bitwise ov_tower_backward_partial's over ov_tower_forward_saving_from's slots.
+// ov_tower_backward_partial over checkpoints: each layer's slot is rebuilt in `slot` from ckpt[i - first] before its block backward,
+// except the top layer's when the caller says `slot` still holds it from ov_tower_forward_checkpointed.  Every gradient is bitwise
+// ov_tower_backward_partial's over ov_tower_forward_saving_from's slots.
 extern "C" int ov_tower_backward_checkpointed(const ov_tower* t, int first, const ov_bf16* ckpt, void* slot, size_t slot_bytes,
                                               int slot_holds_top, ov_bf16* dx, const ov_block_grads* grads, int want_dx, int B, int L,
                                               void* workspace, size_t workspace_bytes, ov_stream_t stream) {
     if (!t || !dx || B <= 0 || L <= 0 || first < 0 || first > t->cfg.layers) return OV_ERR_INVALID;
-    const ov_tower_cfg& c = t->cfg;
-    if (first == c.layers) return OV_OK;                          // nothing kept: d(input of layer `first`) = d(output), already in dx
+    if (first == t->cfg.layers) return OV_OK;                     // nothing kept: d(input of layer `first`) = d(output), already in dx
     if (!ckpt || !slot || !grads || !workspace) return OV_ERR_INVALID;
-    int lo = want_dx ? first : c.layers;                          // the lowest layer that runs
-    for (int i = c.layers - 1; i >= first; --i) {
-        const int p = block_grad_pairs(&grads[i - first]);
-        if (p < 0) return OV_ERR_INVALID;                          // a pair with one NULL pointer, or a misaligned one
-        if (p && i < lo) lo = i;
-    }
-    if (tower_fp8(t)) return OV_ERR_UNSUPPORTED;                   // the recompute runs the bf16 forward
+    const int lo = lowest_layer(t, first, grads, want_dx);
+    if (lo < 0) return OV_ERR_INVALID;
     const size_t need = ov_tower_backward_partial_workspace_bytes(t, B, L);
-    if (need == 0) return OV_ERR_UNSUPPORTED;                       // block_cfg_ok: width % 64, head_dim % 8 and <= 96, mlp_pad % 64
-    if (workspace_bytes < need || slot_bytes < ov_tower_slot_bytes(t, B, L)) return OV_ERR_WORKSPACE;
-    if (((uintptr_t)ckpt | (uintptr_t)slot | (uintptr_t)dx | (uintptr_t)workspace) & 15) return OV_ERR_INVALID;
-    for (int i = 0; i < c.layers; ++i)
-        if (!t->set[i] || t->blocks[i].qkv_colsum || t->blocks[i].fc_colsum) return OV_ERR_INVALID;
-    const int64_t M = (int64_t)B * L;
-    const size_t xe = (size_t)M * c.width;
-    for (int i = c.layers - 1; i >= lo; --i) {                    // dx holds d(block output) on entry and d(block input) on exit
-        ov_bf16* sx = const_cast<ov_bf16*>(ckpt) + (size_t)(i - first) * xe;
-        const Slot s = slot_at(c, sx, (ov_bf16*)slot, M);
-        int rc;
-        if (!(slot_holds_top && i == c.layers - 1) && (rc = forward_saving_layer(c, t->blocks[i], s, nullptr, B, L, stream))) return rc;
-        const ov_block_saved sv = block_saved_of(c, s, L);
-        rc = block_backward_partial(&c, &t->blocks[i], sx, &sv, dx, (i > lo || want_dx) ? dx : nullptr, &grads[i - first], B, L,
-                                    workspace, workspace_bytes, stream);
-        if (rc) return rc;
-    }
-    return OV_OK;
+    const int rc = check_walk(t, true, need > 0, workspace_bytes >= need && slot_bytes >= ov_tower_slot_bytes(t, B, L),
+                              (uintptr_t)ckpt | (uintptr_t)slot | (uintptr_t)dx | (uintptr_t)workspace);
+    return rc ? rc : backward_walk(t, first, lo, checkpointed_layout(t->cfg, ckpt, slot, B, L), true, slot_holds_top, dx, grads, want_dx,
+                                   B, L, workspace, workspace_bytes, stream);
 }
 
 extern "C" size_t ov_vision_workspace_bytes(const ov_tower* t, const ov_vision_head* h, int B) {

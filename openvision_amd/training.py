@@ -1,9 +1,10 @@
 """Training-side forward with gradients: the block stacks and the InfoNCE loss are autograd nodes whose
-forward AND backward are the HIP kernels (``ov_tower_forward_saving`` / ``ov_tower_backward``, ``ov_clip_loss`` /
-``ov_clip_loss_backward``).  The light ends around the towers run on the HIP operators too: the patch projection and the output
-projections are autograd nodes over ``ov_gemm`` / ``ov_linear_backward``, ``ln_post`` / ``ln_final`` over ``ov_layernorm`` /
-``ov_layernorm_backward`` (open_clip/transformer.py:609-651, model.py:265-315); what is left to torch autograd is data movement and
-element-wise plumbing (class / positional embedding adds, token gather, mean pooling, L2 normalisation) -- no aten GEMM.
+forward AND backward are the HIP kernels (``ov_tower_forward_saving_from`` / ``ov_tower_backward_partial`` or, under recomputation,
+``ov_tower_forward_checkpointed`` / ``ov_tower_backward_checkpointed``; ``ov_clip_loss`` / ``ov_clip_loss_backward``).  The light
+ends around the towers run on the HIP operators too: the patch projection and the output projections are autograd nodes over
+``ov_gemm`` / ``ov_linear_backward``, ``ln_post`` / ``ln_final`` over ``ov_layernorm`` / ``ov_layernorm_backward``
+(open_clip/transformer.py:609-651, model.py:265-315); what is left to torch autograd is data movement and element-wise plumbing
+(class / positional embedding adds, token gather, mean pooling, L2 normalisation) -- no aten GEMM.
 
 Opt-in: the inference entry points of ``openvision_amd.model`` never build a graph; a training loop calls
 
@@ -124,20 +125,38 @@ def _packed_blocks(transformer, params, mlp: int, mlp_pad: int, span=(0, -1)):
     return st["keep"]
 
 
+def _weights(ts) -> _lib.BlockWeights:
+    return _lib.BlockWeights(*[C.c_void_p(t.data_ptr()) for t in ts], None, None)
+
+
+def _tower_handle(lib, cfg, keep):
+    handle = lib.ov_tower_create(C.byref(cfg))
+    if not handle:
+        raise _lib.OvhipError("ov_tower_create failed")
+    try:
+        for i in range(cfg.layers):
+            check(lib.ov_tower_set_block(handle, i, C.byref(_weights(keep[i]))), "ov_tower_set_block")
+    except Exception:
+        lib.ov_tower_destroy(handle)
+        raise
+    return handle
+
+
 class _TowerFn(torch.autograd.Function):
     """Transformer.forward (transformer.py:355-366) as one autograd node over the blocks [lo, hi) (all of them by default; several
     consecutive nodes when ``tower_forward`` is asked for chunks, so that parameter gradients become available chunk by chunk).
 
     Frozen parameters (``requires_grad=False``: ``lock_image_tower``, a frozen text tower under gradient ascent) are honoured per
-    (weight, bias) pair of a block: a pair is frozen when both of its tensors are.  When x needs no gradient either, the blocks below
-    the lowest trainable one run without keeping anything (``ov_tower_forward_saving_from``) and the backward stops at that block
-    (``ov_tower_backward_partial``); frozen blocks above it run input-only.  Every gradient that is computed is bitwise the one of
-    the all-trainable path; with everything trainable the node makes exactly that path's calls.
+    (weight, bias) pair of a block: a pair is frozen when both of its tensors are.  ``first`` is 0 when x needs a gradient, else the
+    lowest block with a trainable pair: the blocks below it run without keeping anything (``ov_tower_forward_saving_from``) and the
+    backward stops at it (``ov_tower_backward_partial``, the requested pairs only); frozen blocks above it run input-only.  With
+    everything trainable that is the full backward's launches, and every gradient that is computed is bitwise the all-trainable one.
 
-    Recomputation (``transformer.grad_checkpointing``): the same `first` rule, but ``ov_tower_forward_checkpointed`` keeps only the
-    inputs of layers [first, hi - lo) ("saved") and one layer's intermediates ("slot"); ``ov_tower_backward_checkpointed`` rebuilds
-    each block's slot before its backward.  The node holding the tower's last block keeps its slot until its backward (no recompute
-    of that block); every other node hands its slot back after the forward.  Loss and gradients are bitwise those without it."""
+    Recomputation (``transformer.grad_checkpointing``): the same calls' checkpointed forms.  ``ov_tower_forward_checkpointed`` keeps
+    only the inputs of layers [first, hi - lo) ("saved") and one layer's intermediates ("slot"); ``ov_tower_backward_checkpointed``
+    rebuilds each block's slot before its backward.  The node holding the tower's last block keeps its slot until its backward (no
+    recompute of that block); every other node hands its slot back after the forward.  Loss and gradients are bitwise those without
+    it.  In both modes a failed native call hands every pool buffer it took back."""
 
     @staticmethod
     def forward(ctx, transformer, lo, hi, x, *params):
@@ -148,59 +167,46 @@ class _TowerFn(torch.autograd.Function):
         if d % 64 or d % heads or (d // heads) % 8 or d // heads > 96:
             raise _lib.OvhipError("training path: width % 64 == 0 and head_dim % 8 == 0, <= 96 are required")
         bsz, seq, _ = x.shape
+        layers = len(blocks)
         need_x, need_p = ctx.needs_input_grad[3], ctx.needs_input_grad[4:]
-        pairs = [[need_p[12 * i + 2 * k] or need_p[12 * i + 2 * k + 1] for k in range(6)] for i in range(len(blocks))]
-        every = need_x and all(need_p)
-        first = 0 if need_x else next((i for i, pr in enumerate(pairs) if any(pr)), len(blocks))
-        cfg = _lib.TowerCfg(d, len(blocks), heads, mlp, mlp_pad, int(b0.gelu_tanh), float(b0.ln_1.eps))
-        handle = lib.ov_tower_create(C.byref(cfg))
-        if not handle:
-            raise _lib.OvhipError("ov_tower_create failed")
+        pairs = [[need_p[12 * i + 2 * k] or need_p[12 * i + 2 * k + 1] for k in range(6)] for i in range(layers)]
+        first = 0 if need_x else next((i for i, pr in enumerate(pairs) if any(pr)), layers)
+        cfg = _lib.TowerCfg(d, layers, heads, mlp, mlp_pad, int(b0.gelu_tanh), float(b0.ln_1.eps))
+        keep = _packed_blocks(transformer, params, mlp, mlp_pad, (lo, hi))
         pool = _train_state(transformer)["pool"]
         remat = bool(getattr(transformer, "grad_checkpointing", False))
+        handle = _tower_handle(lib, cfg, keep)
         saved = slot = None
         try:
-            keep = _packed_blocks(transformer, params, mlp, mlp_pad, (lo, hi))
-            for i, ts in enumerate(keep):
-                bw = _lib.BlockWeights(*[C.c_void_p(t.data_ptr()) for t in ts], None, None)
-                check(lib.ov_tower_set_block(handle, i, C.byref(bw)), "ov_tower_set_block")
             xb = x.detach().to(torch.bfloat16).contiguous().clone()
+            if remat:        # the kept layers' inputs, and one layer's intermediates (the layers below `first` use them as scratch)
+                nsaved, nslot, kind = (lib.ov_tower_checkpoint_bytes(handle, first, bsz, seq), lib.ov_tower_slot_bytes(handle, bsz, seq),
+                                       "slot")
+            else:            # the kept layers' slots, and a workspace for the intermediates of the layers below `first` (none if first = 0)
+                nsaved, nslot, kind = (lib.ov_tower_saved_bytes_from(handle, first, bsz, seq),
+                                       lib.ov_tower_forward_saving_from_workspace_bytes(handle, first, bsz, seq), "ws")
+            if first < layers:
+                saved = pool.take(nsaved, x.device, "saved")
+            if nslot:
+                slot = pool.take(nslot, x.device, kind)
             if remat:
-                nslot = lib.ov_tower_slot_bytes(handle, bsz, seq)
-                if first < len(blocks):
-                    saved = pool.take(lib.ov_tower_checkpoint_bytes(handle, first, bsz, seq), x.device, "saved")
-                slot = pool.take(nslot, x.device, "slot")
-                try:
-                    check(lib.ov_tower_forward_checkpointed(handle, first, ptr(xb), ptr(saved), ptr(slot), nslot, bsz, seq, stream_ptr()),
-                          "ov_tower_forward_checkpointed")
-                except BaseException:
-                    for t in (saved, slot):
-                        if t is not None:
-                            pool.give(t)
-                    raise
-                if saved is None or hi < len(transformer.resblocks):   # only the top node keeps its slot for the backward
-                    pool.give(slot)
-                    slot = None
-                ws = None
-            elif every:
-                saved = pool.take(lib.ov_tower_saved_bytes(handle, bsz, seq), x.device, "saved")
-                nbytes = lib.ov_tower_workspace_bytes(handle, bsz, seq)
-                ws = pool.take(nbytes, x.device)
-                check(lib.ov_tower_forward_saving(handle, ptr(xb), ptr(saved), bsz, seq, ptr(ws), nbytes, stream_ptr()),
-                      "ov_tower_forward_saving")
+                check(lib.ov_tower_forward_checkpointed(handle, first, ptr(xb), ptr(saved), ptr(slot), nslot, bsz, seq, stream_ptr()),
+                      "ov_tower_forward_checkpointed")
             else:
-                if first < len(blocks):
-                    saved = pool.take(lib.ov_tower_saved_bytes_from(handle, first, bsz, seq), x.device, "saved")
-                nbytes = lib.ov_tower_forward_saving_from_workspace_bytes(handle, first, bsz, seq)
-                ws = pool.take(nbytes, x.device) if nbytes else None
-                check(lib.ov_tower_forward_saving_from(handle, first, ptr(xb), ptr(saved), bsz, seq, ptr(ws), nbytes, stream_ptr()),
+                check(lib.ov_tower_forward_saving_from(handle, first, ptr(xb), ptr(saved), bsz, seq, ptr(slot), nslot, stream_ptr()),
                       "ov_tower_forward_saving_from")
-            if ws is not None:
-                pool.give(ws)
+        except BaseException:
+            for t in (saved, slot):
+                if t is not None:
+                    pool.give(t)
+            raise
         finally:
             lib.ov_tower_destroy(handle)
+        if slot is not None and (not remat or saved is None or hi < len(transformer.resblocks)):
+            pool.give(slot)                   # only the top node under recomputation keeps its slot for the backward
+            slot = None
         ctx.cfg, ctx.keep, ctx.saved, ctx.shape, ctx.mlp, ctx.pool = cfg, keep, saved, (bsz, seq, d), mlp, pool
-        ctx.every, ctx.first, ctx.pairs, ctx.need = every, first, pairs, (need_x, need_p)
+        ctx.first, ctx.pairs, ctx.need = first, pairs, (need_x, need_p)
         ctx.saved_gen = saved._ovhip_gen if saved is not None else None
         ctx.remat, ctx.slot = remat, slot
         ctx.x_dtype, ctx.p_dtypes = x.dtype, [p.dtype for p in params]
@@ -215,53 +221,35 @@ class _TowerFn(torch.autograd.Function):
             raise _lib.OvhipError("training path: the saved activations of this graph were recycled by a later forward; a second "
                                   "backward over the same graph must come before the next forward of this tower")
         need_x, need_p = ctx.need
-        first = ctx.first
-        handle = lib.ov_tower_create(C.byref(ctx.cfg))
+        first, pool = ctx.first, ctx.pool
+        # frozen pairs: NULL in ov_block_grads, no buffers, no work; with everything trainable every pair is requested
+        grads = [[None] * 12 for _ in range(first)]
+        grads += [[torch.empty_like(t) if ctx.pairs[i][j // 2] else None for j, t in enumerate(ctx.keep[i])] for i in range(first, layers)]
+        garr = (_lib.BlockGrads * (layers - first))(*[_lib.BlockGrads(*[ptr(t) for t in g]) for g in grads[first:]])
+        dx = grad_out.detach().to(torch.bfloat16).contiguous().clone()
+        slot, holds = ctx.slot, ctx.slot is not None
+        ctx.slot = None                       # the backward overwrites it: a second backward over this graph recomputes the top block
+        handle = ws = None
         try:
-            for i, ts in enumerate(ctx.keep):
-                bw = _lib.BlockWeights(*[C.c_void_p(t.data_ptr()) for t in ts], None, None)
-                check(lib.ov_tower_set_block(handle, i, C.byref(bw)), "ov_tower_set_block")
-            dx = grad_out.detach().to(torch.bfloat16).contiguous().clone()
-            if ctx.remat:             # the partial backward's grads rules; with everything trainable every pair is requested
-                grads = [[None] * 12 for _ in range(first)]
-                grads += [[torch.empty_like(t) if ctx.pairs[i][j // 2] else None for j, t in enumerate(ctx.keep[i])]
-                          for i in range(first, layers)]
-                garr = (_lib.BlockGrads * (layers - first))(*[_lib.BlockGrads(*[ptr(t) for t in g]) for g in grads[first:]])
-                nbytes = lib.ov_tower_backward_partial_workspace_bytes(handle, bsz, seq)
+            handle = _tower_handle(lib, ctx.cfg, ctx.keep)
+            nbytes = lib.ov_tower_backward_partial_workspace_bytes(handle, bsz, seq)
+            ws = pool.take(nbytes, dx.device)
+            if ctx.remat:
                 nslot = lib.ov_tower_slot_bytes(handle, bsz, seq)
-                slot, holds = ctx.slot, ctx.slot is not None
-                ctx.slot = None               # the backward overwrites it: a second backward over this graph recomputes the top block
-                ws = ctx.pool.take(nbytes, dx.device)
                 if slot is None:
-                    slot = ctx.pool.take(nslot, dx.device, "slot")
-                try:
-                    check(lib.ov_tower_backward_checkpointed(handle, first, ptr(ctx.saved), ptr(slot), nslot, int(holds), ptr(dx), garr,
-                                                             int(need_x), bsz, seq, ptr(ws), nbytes, stream_ptr()),
-                          "ov_tower_backward_checkpointed")
-                finally:                      # an error leaves nothing outstanding either
-                    for t in (slot, ws, ctx.saved):
-                        ctx.pool.give(t)
-            elif ctx.every:
-                grads = [[torch.empty_like(t) for t in ts] for ts in ctx.keep]
-                garr = (_lib.BlockGrads * layers)(*[_lib.BlockGrads(*[C.c_void_p(t.data_ptr()) for t in g]) for g in grads])
-                nbytes = lib.ov_tower_backward_workspace_bytes(handle, bsz, seq)
-                ws = ctx.pool.take(nbytes, dx.device)
-                check(lib.ov_tower_backward(handle, ptr(ctx.saved), ptr(dx), garr, bsz, seq, ptr(ws), nbytes, stream_ptr()),
-                      "ov_tower_backward")
-            else:                     # frozen pairs: NULL in ov_block_grads, no buffers, no work
-                grads = [[None] * 12 for _ in range(first)]
-                grads += [[torch.empty_like(t) if ctx.pairs[i][j // 2] else None for j, t in enumerate(ctx.keep[i])]
-                          for i in range(first, layers)]
-                garr = (_lib.BlockGrads * (layers - first))(*[_lib.BlockGrads(*[ptr(t) for t in g]) for g in grads[first:]])
-                nbytes = lib.ov_tower_backward_partial_workspace_bytes(handle, bsz, seq)
-                ws = ctx.pool.take(nbytes, dx.device)
+                    slot = pool.take(nslot, dx.device, "slot")
+                check(lib.ov_tower_backward_checkpointed(handle, first, ptr(ctx.saved), ptr(slot), nslot, int(holds), ptr(dx), garr,
+                                                         int(need_x), bsz, seq, ptr(ws), nbytes, stream_ptr()),
+                      "ov_tower_backward_checkpointed")
+            else:
                 check(lib.ov_tower_backward_partial(handle, first, ptr(ctx.saved), ptr(dx), garr, int(need_x), bsz, seq, ptr(ws), nbytes,
                                                     stream_ptr()), "ov_tower_backward_partial")
-            if not ctx.remat:
-                ctx.pool.give(ws)
-                ctx.pool.give(ctx.saved)     # ordered on the stream: the next forward's writes come after this backward's reads
-        finally:
-            lib.ov_tower_destroy(handle)
+        finally:                              # on success and on error alike; ordered on the stream: the next forward's writes come
+            for t in (slot, ws, ctx.saved):   # after this backward's reads
+                if t is not None:
+                    pool.give(t)
+            if handle is not None:
+                lib.ov_tower_destroy(handle)
         mlp = ctx.mlp                                             # drop the (exactly zero) gradients of the MLP padding
         for gs in grads:
             if gs[8] is not None:

@@ -22,30 +22,13 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr, stream_ptr
-from .training import _block_tensors, _LinearFn, _packed_blocks, _train_state
+from .training import _block_tensors, _LinearFn, _packed_blocks, _tower_handle, _train_state, _weights
 
 __all__ = ["mlp_feature", "MLPFeatureLoss"]
 
 
 def _a256(n: int) -> int:
     return (n + 255) // 256 * 256
-
-
-def _weights(ts) -> _lib.BlockWeights:
-    return _lib.BlockWeights(*[C.c_void_p(t.data_ptr()) for t in ts], None, None)
-
-
-def _tower_handle(lib, cfg, keep):
-    handle = lib.ov_tower_create(C.byref(cfg))
-    if not handle:
-        raise _lib.OvhipError("ov_tower_create failed")
-    try:
-        for i in range(cfg.layers):
-            check(lib.ov_tower_set_block(handle, i, C.byref(_weights(keep[i]))), "ov_tower_set_block")
-    except Exception:
-        lib.ov_tower_destroy(handle)
-        raise
-    return handle
 
 
 class _FeatureFn(torch.autograd.Function):

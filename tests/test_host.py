@@ -194,6 +194,56 @@ def test_training_pool_keeps_what_a_step_needs_and_serves_by_purpose():
     assert len(pool.lists["ws"]) == 1
 
 
+class _FailingTowerLib:
+    """libovhip's tower calls as training._TowerFn makes them, with nothing launched: every byte count is small and every call
+    succeeds except the forward / backward walk whose name starts with `fail`."""
+
+    def __init__(self, fail):
+        self.fail = fail
+
+    def ov_tower_forward_saving_from_workspace_bytes(self, t, first, B, L):
+        return 4096 if first > 0 else 0
+
+    def ov_error_string(self, rc):
+        return b"injected failure"
+
+    def __getattr__(self, name):
+        if "_bytes" in name:
+            return lambda *a: 4096
+        if name.startswith(("ov_tower_forward", "ov_tower_backward")):
+            return lambda *a: -1 if name.startswith(self.fail) else 0
+        return {"ov_tower_create": lambda cfg: 1, "ov_tower_set_block": lambda *a: 0, "ov_tower_destroy": lambda t: None}[name]
+
+
+@pytest.mark.parametrize("remat", [False, True], ids=["saving", "remat"])
+@pytest.mark.parametrize("frozen", [0, 2], ids=["all_trainable", "frozen_lower"])
+def test_tower_node_hands_its_pool_buffers_back_when_a_native_call_fails(monkeypatch, remat, frozen):
+    """A failed forward or backward call of training._TowerFn leaves nothing outstanding in the tower's pool, in both modes, with
+    everything trainable (x needs a gradient) and with frozen lower blocks (first > 0)."""
+    from openvision_amd import _lib, training
+    m = create_model(preset("vit-tiny-patch16-160"))
+    m.visual.set_grad_checkpointing(remat)
+    tr = m.visual.transformer
+    blocks = list(tr.resblocks)
+    for blk in blocks[:frozen]:
+        blk.requires_grad_(False)
+    params = [p for blk in blocks for p in training._block_tensors(blk)]
+    x = torch.randn(2, 5, blocks[0].attn.embed_dim, requires_grad=frozen == 0)
+    fake = _FailingTowerLib("ov_tower_forward")
+    monkeypatch.setattr(_lib, "load", lambda: fake)
+    monkeypatch.setattr(training, "stream_ptr", lambda: None)
+    pool = training._train_state(tr)["pool"]
+    with pytest.raises(OvhipError):
+        training._TowerFn.apply(tr, 0, len(blocks), x, *params)
+    assert pool.out and not any(pool.out.values()), pool.out
+    fake.fail = "ov_tower_backward"
+    y = training._TowerFn.apply(tr, 0, len(blocks), x, *params)
+    assert pool.out["saved"] == 1
+    with pytest.raises(OvhipError):
+        y.sum().backward()
+    assert not any(pool.out.values()), pool.out
+
+
 def test_fused_adamw_state_dict_hooks_and_none_gradients():
     """training.FusedAdamW host logic on CPU tensors: state_dict/load_state_dict round-trips step count and moments and refuses another
     layout; a second overlap_gradient_exchange replaces the hooks instead of doubling them; a parameter whose .grad was set to None

@@ -154,6 +154,41 @@ def test_partial_backward_rejects_folded_weights_without_hip():
         lib.ov_tower_destroy(t)
 
 
+def test_tower_backward_checks_every_layer_before_its_first_launch_without_hip():
+    """ov_tower_backward needs every pair of every layer: a NULL or half-NULL pair, or a misaligned pointer, in a layer BELOW the top
+    one is rejected before anything runs (not after the layers above have run); folded weights in any layer are OV_ERR_UNSUPPORTED."""
+    lib = _lib.load()
+    layers, Bn, L = 3, 8, 257
+    t = _tower(lib, layers=layers)
+    try:
+        a = C.c_void_p(1 << 20)
+        nb = lib.ov_tower_backward_workspace_bytes(t, Bn, L)
+        bwd = lib.ov_tower_backward
+        for blk in range(layers):
+            for j in (0, 5, 11):
+                assert bwd(t, a, a, _grads(layers, half=(blk, j)), Bn, L, a, nb, None) == -1, (blk, j)
+            assert bwd(t, a, a, _grads(layers, frozen={(blk, 2)}), Bn, L, a, nb, None) == -1, blk
+        assert bwd(t, a, a, _grads(layers, misaligned=(0, 7)), Bn, L, a, nb, None) == -1
+        # the order of the codes: the top layer's checks, the workspace, the alignment, the layers below
+        assert bwd(t, a, a, _grads(layers, half=(layers - 1, 4)), Bn, L, a, nb - 1, None) == -1
+        assert bwd(t, a, a, _grads(layers, half=(0, 4)), Bn, L, a, nb - 1, None) == -3
+        assert bwd(t, a, a, _grads(layers), Bn, L, a, nb - 1, None) == -3
+        assert bwd(t, a, C.c_void_p((1 << 20) + 4), _grads(layers), Bn, L, a, nb, None) == -1
+    finally:
+        lib.ov_tower_destroy(t)
+    t = _tower(lib, layers=2, blocks=False)
+    try:
+        a = C.c_void_p(1 << 20)
+        nb = lib.ov_tower_backward_workspace_bytes(t, 2, 101)
+        for folded in (0, 1):
+            for i in range(2):
+                w = _lib.BlockWeights(*([a] * 12), *((a, a) if i == folded else (None, None)))
+                assert lib.ov_tower_set_block(t, i, C.byref(w)) == 0
+            assert lib.ov_tower_backward(t, a, a, _grads(2), 2, 101, a, nb, None) == -2, folded
+    finally:
+        lib.ov_tower_destroy(t)
+
+
 @pytest.mark.timeout(900)
 def test_layernorm_backward_rows_use_no_scratch():
     out = subprocess.run([B.hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-gpu-rdc", "--cuda-device-only", "-S", "-o", "-",

@@ -142,6 +142,12 @@ int ov_attention(const ov_bf16* qkv, int64_t ld_qkv, ov_bf16* out, int64_t ld_ou
  * log2 units, for ov_attention_backward_saved.  head_dim 64 and L <= 288 only (OV_ERR_UNSUPPORTED otherwise). */
 int ov_attention_lse(const ov_bf16* qkv, int64_t ld_qkv, ov_bf16* out, int64_t ld_out, float* lse, int B, int L, int H, int hd, float scale,
                      ov_stream_t stream);
+/* Prefix-causal attention (the text decoder's prefix-LM mask, text_transformer.py:418-442 with li = prefix; make_causal_mask for
+ * prefix = 0): key j is visible to query i iff j < prefix or j <= i.  An invisible key has weight exactly 0; 32 x 32 tile pairs that
+ * are wholly invisible are skipped.  0 <= prefix <= L, OV_ERR_INVALID otherwise; prefix == L is ov_attention itself (bitwise).  Same
+ * layouts, head dims and argument checks as ov_attention.  No e4m3-output form. */
+int ov_attention_prefix(const ov_bf16* qkv, int64_t ld_qkv, ov_bf16* out, int64_t ld_out, int B, int L, int H, int hd, float scale,
+                        int prefix, ov_stream_t stream);
 
 /* Patch gather for conv1: image [B,3,S,S] (img_dtype) -> P[B*g*g, Kpad] bf16,
  * column index c*P*P + i*P + j (the flattening of conv1.weight[D,3,P,P]); columns >= 3*P*P zeroed. */
@@ -308,6 +314,19 @@ int ov_siglip_loss_backward(const float* img, const float* all_txt, int b, int N
                             const float* logit_bias, int label_offset, const float* grad_loss, float* d_img, float* d_all_txt,
                             float* d_scale, float* d_bias, void* workspace, size_t workspace_bytes, ov_stream_t stream);
 
+/* ---- caption loss: masked softmax cross-entropy over the vocabulary (softmax_xent with reduction=True and a mask,
+ * src/losses/common.py:225-251; no label smoothing).  logits fp32 [R, V] (row pitch ld >= V), labels int64 [R], mask fp32 [R]:
+ *     nll_r = logsumexp(logits_r) - logits_r[label_r]   (0 for a label outside [0, V));   *loss = sum nll_r mask_r / (sum mask_r + 1e-8)
+ * row_lse [R] keeps every row's log-sum-exp for the backward.  fp32 throughout, one pass over a row, deterministic, device scalars in
+ * and out.  Backward: dlogits = (*grad) mask_r / (sum mask + 1e-8) (softmax(logits_r) - onehot_r); rows with mask_r == 0 are exactly
+ * zero; dlogits may alias logits.  Workspace for either call: ov_softmax_xent_workspace_bytes(R). */
+size_t ov_softmax_xent_workspace_bytes(int64_t R);
+int ov_softmax_xent(const float* logits, int64_t ld, const int64_t* labels, const float* mask, int64_t R, int V, float* loss,
+                    float* row_lse, void* workspace, size_t workspace_bytes, ov_stream_t stream);
+int ov_softmax_xent_backward(const float* logits, int64_t ld, const int64_t* labels, const float* mask, const float* row_lse,
+                             const float* grad, float* dlogits, int64_t ld_dlogits, int64_t R, int V, void* workspace,
+                             size_t workspace_bytes, ov_stream_t stream);
+
 /* ---- operator-level backward of the block (the reference gets these from torch autograd through nn.Linear,
  * nn.LayerNorm and nn.GELU: transformer.py:15-30, 232-236).  bf16 activations and gradients, fp32 arithmetic and parameter-gradient
  * sums, deterministic (two-stage reductions in a fixed order). ---------------------------------------------------------------- */
@@ -346,6 +365,14 @@ int ov_attention_backward(const ov_bf16* qkv, int64_t ld_qkv, const ov_bf16* out
 int ov_attention_backward_saved(const ov_bf16* qkv, int64_t ld_qkv, const ov_bf16* out, int64_t ld_out, const ov_bf16* dout, int64_t ld_dout,
                                 ov_bf16* dqkv, int64_t ld_dqkv, const float* lse, int B, int L, int H, int hd, float scale, void* workspace,
                                 size_t workspace_bytes, ov_stream_t stream);
+/* Backward of ov_attention_prefix under the same visibility rule: always the two streaming kernels (every L and head dim), which skip
+ * the invisible tile pairs in the dQ pass and in the dK / dV pass; deterministic.  The workspace (row lse and delta) is needed for
+ * every shape: ov_attention_prefix_backward_workspace_bytes >= ov_attention_backward_workspace_bytes.  prefix == L is
+ * ov_attention_backward itself (bitwise); prefix outside [0, L] is OV_ERR_INVALID. */
+size_t ov_attention_prefix_backward_workspace_bytes(int B, int L, int H, int hd);
+int ov_attention_prefix_backward(const ov_bf16* qkv, int64_t ld_qkv, const ov_bf16* out, int64_t ld_out, const ov_bf16* dout,
+                                 int64_t ld_dout, ov_bf16* dqkv, int64_t ld_dqkv, int B, int L, int H, int hd, float scale, int prefix,
+                                 void* workspace, size_t workspace_bytes, ov_stream_t stream);
 
 /* da = dh * gelu'(a) on the pre-activation a [rows, N] (tanh_form = 0: exact erf GELU, vision; 1: tanh form, text).  N % 8 == 0.
  * h_out (optional) receives gelu(a).  da may alias dh and h_out may alias a (element-wise, in place). */
@@ -442,6 +469,12 @@ int       ov_tower_set_fp8_hidden_scale(ov_tower* t, float* amax, int mode);
 #define OV_FP8_PROJ 8
 #define OV_FP8_ALL 15
 int       ov_tower_set_fp8_mask(ov_tower* t, const unsigned char* mask, int n);
+/* Attention mask of every block of the tower (host state only): prefix = -1 (the default at creation) is unmasked; prefix >= 0 makes
+ * every walk -- ov_tower_forward, ov_tower_forward_saving[_from], ov_tower_backward[_partial / _input] and the checkpointed pair --
+ * run ov_attention_prefix / ov_attention_prefix_backward with that prefix.  A later call whose L is smaller than the prefix returns
+ * OV_ERR_INVALID; a tower in fp8 / fp8-mixed precision with a prefix set returns OV_ERR_UNSUPPORTED from ov_tower_forward (no fp8
+ * under a mask).  prefix < -1 is OV_ERR_INVALID.  The sizes ov_tower_saved_bytes* / *_workspace_bytes report hold for either state. */
+int       ov_tower_set_prefix(ov_tower* t, int prefix);
 size_t    ov_tower_workspace_bytes(const ov_tower* t, int B, int L);
 /* x[B*L, D] bf16 is updated in place through all `layers` blocks. */
 int       ov_tower_forward(const ov_tower* t, ov_bf16* x, int B, int L, void* workspace,
@@ -477,6 +510,11 @@ size_t ov_block_backward_workspace_bytes(const ov_tower_cfg* cfg, int B, int L);
 int ov_block_backward(const ov_tower_cfg* cfg, const ov_block_weights* w, const ov_bf16* x, const ov_block_saved* saved /* or NULL */,
                       const ov_bf16* dy, ov_bf16* dx, const ov_block_grads* g, int B, int L, void* workspace, size_t workspace_bytes,
                       ov_stream_t stream);
+/* The same for a block whose attention ran under ov_attention_prefix (prefix in [0, L]; -1 = unmasked = ov_block_backward);
+ * saved->attn_lse is ignored when 0 <= prefix < L.  Same workspace. */
+int ov_block_backward_prefix(const ov_tower_cfg* cfg, const ov_block_weights* w, const ov_bf16* x, const ov_block_saved* saved /* or NULL */,
+                             const ov_bf16* dy, ov_bf16* dx, const ov_block_grads* g, int prefix, int B, int L, void* workspace,
+                             size_t workspace_bytes, ov_stream_t stream);
 
 /* Training-side tower entry points.  ov_tower_forward_saving = the tower forward on the caller's stream that keeps, per layer and
  * token, [x | qkv | attention out | x1 | ln_1 out | ln_2 out | c_fc pre-activation | c_fc activation] (8 D + 2 mlp_pad bf16, plus the

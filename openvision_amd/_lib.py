@@ -86,6 +86,17 @@ SIGNATURES = {
     "ov_gemm_rowparts": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_void_p, c_int64,
                                  c_void_p, c_void_p]),
     "ov_attention": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_float, c_void_p]),
+    "ov_attention_prefix": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p]),
+    "ov_attention_prefix_backward_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "ov_attention_prefix_backward": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int,
+                                             c_int, c_float, c_int, c_void_p, c_size_t, c_void_p]),
+    "ov_softmax_xent_workspace_bytes": (c_size_t, [c_int64]),
+    "ov_softmax_xent": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "ov_softmax_xent_backward": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int,
+                                         c_void_p, c_size_t, c_void_p]),
+    "ov_tower_set_prefix": (c_int, [c_void_p, c_int]),
+    "ov_block_backward_prefix": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
+                                         c_size_t, c_void_p]),
     "ov_im2col_patches": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "ov_im2col_patches_keep": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "ov_patch_keep_inverse": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),

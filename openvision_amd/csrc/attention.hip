@@ -1,4 +1,5 @@
-// attention.hip — fused non-causal multi-head self-attention, head_dim 64, gfx950 (MI355X).
+// attention.hip — fused multi-head self-attention, gfx950 (MI355X): non-causal (head_dim 64 tuned, generic up to 96) and, in the generic
+// kernel's MASK form, prefix-causal (ov_attention_prefix, at the end of this file).
 //
 // Replaces the softmax(q k^T / sqrt(hd)) v core of nn.MultiheadAttention (reference
 // open_clip/transformer.py:225,239-252; no mask: attn_mask=None, no dropout in eval) with a flash-style
@@ -29,6 +30,7 @@ struct AttnArgs {
     ov_bf16* out; int64_t ldo;
     int B, L, H, nqt, KC;
     float scale_log2;
+    int prefix;                   // MASK kernels: key j is visible to query i iff j < prefix or j <= i
 };
 
 typedef __attribute__((address_space(3))) s16x4_t* lds_s16x4_ptr;
@@ -776,8 +778,15 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_hd64_stream(const AttnSArgs a
 // Generic head_dim kernel (head_dim 72 = So400m, 80 = H/14; any multiple of 8 up to 96): same S^T / P^T / O^T scheme with
 // the head padded to 96 in LDS (zero columns), 256-key chunks staged through registers, one key tile per step.  A plain,
 // correctness-first variant: these model sizes are not on the benchmark configuration.
-template <int HDP>
+// MASK (ov_attention_prefix): prefix-causal visibility, key j is visible to query i iff j < a.prefix or j <= i.  A query tile q0 sees
+// keys [0, max(prefix, q0 + 32)): key tiles wholly beyond that are never staged-for or computed by its wave, chunks beyond the
+// workgroup's last tile are not staged at all; the tiles that straddle the boundary enter the online softmax with -inf scores.  Every
+// tile a wave does process has its first key visible to all of its queries (it starts below prefix or at / below q0), so no row's
+// running maximum stays -inf.  HDP = 64 serves head_dim 64 under a mask (K rows of 128 B, 16-byte chunks XOR-swizzled by
+// (key >> 1) & 7 as in the persistent kernel: the unswizzled 128-B pitch would put the 32 rows of a ds_read_b128 on four banks).
+template <int HDP, bool MASK = false>
 __global__ __launch_bounds__(640) void attn_fwd_generic(const AttnArgs a, int hd) {
+    constexpr bool SWZ = HDP == 64;
     constexpr int KS = HDP / 16;           // k-steps of S^T = K.Q^T
     constexpr int DT = HDP / 32;           // 32-row tiles of O^T
     constexpr int CH = HDP / 8;            // 16-byte chunks per (padded) row
@@ -817,7 +826,10 @@ __global__ __launch_bounds__(640) void attn_fwd_generic(const AttnArgs a, int hd
     const int vi = lane & 15, vg = (lane >> 4) & 1;
     const int v_lane_off = (4 * h2 + (vi >> 2)) * 64 + (16 * vg + 4 * (vi & 3)) * 2;
 
-    for (int kc0 = 0; kc0 < L; kc0 += KC) {
+    // MASK: keys this workgroup's last query tile sees (a multiple of 32 or prefix, clipped) / this wave's tile sees
+    const int kend_wg = MASK ? min(L, max(a.prefix, min(a.nqt, ((int)blockIdx.y + 1) * nw) * 32)) : L;
+    const int kvis = MASK ? min(L, max(a.prefix, q0 + 32)) : L;
+    for (int kc0 = 0; kc0 < kend_wg; kc0 += KC) {
         if (kc0) __syncthreads();
         for (int idx = tid; idx < KC * CH; idx += nthreads) {
             const int row = idx / CH, c = idx - row * CH;
@@ -827,12 +839,12 @@ __global__ __launch_bounds__(640) void attn_fwd_generic(const AttnArgs a, int hd
                 kv = *(const u32x4_t*)p;
                 vv = *(const u32x4_t*)(p + HD);
             }
-            *(u32x4_t*)(ks + row * (HDP * 2) + c * 16) = kv;
+            *(u32x4_t*)(ks + row * (HDP * 2) + ((SWZ ? c ^ ((row >> 1) & 7) : c) << 4)) = kv;
             *(u32x4_t*)(vs + (c >> 2) * (KC * 64) + row * 64 + (c & 3) * 16) = vv;
         }
         __syncthreads();
-        if (!active) continue;
-        const int nk = (L - kc0) < KC ? (L - kc0) : KC;
+        if (!active || kvis <= kc0) continue;
+        const int nk = (kvis - kc0) < KC ? (kvis - kc0) : KC;
         // a last key tile that holds ONE key (L = 32 k + 1: 257) is folded in on the VALU behind the tile loop, as in the head_dim 64
         // kernels: a tile step for it is a ninth of the loop at L = 257
         const bool lone_key = (nk & 31) == 1 && nk > 32;
@@ -841,10 +853,11 @@ __global__ __launch_bounds__(640) void attn_fwd_generic(const AttnArgs a, int hd
             f32x16_t s;
 #pragma unroll
             for (int i = 0; i < 16; ++i) s[i] = 0.f;
-            const char* kp = ks + (kt * 32 + r) * (HDP * 2) + h2 * 16;
+            const char* kp = ks + (kt * 32 + r) * (HDP * 2);
 #pragma unroll
             for (int st = 0; st < KS; ++st) {
-                const bf16x8_t kf = *(const bf16x8_t*)(kp + st * 32);
+                const int c = 2 * st + h2;
+                const bf16x8_t kf = *(const bf16x8_t*)(kp + ((SWZ ? c ^ ((r >> 1) & 7) : c) << 4));
                 s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[st], s, 0, 0, 0);
             }
             if (kt * 32 + 32 > nk) {
@@ -852,6 +865,13 @@ __global__ __launch_bounds__(640) void attn_fwd_generic(const AttnArgs a, int hd
                 for (int i = 0; i < 16; ++i) {
                     const int key = kt * 32 + (i & 3) + 8 * (i >> 2) + 4 * h2;
                     if (key >= nk) s[i] = -INFINITY;
+                }
+            }
+            if (MASK && kc0 + kt * 32 + 31 >= a.prefix && kc0 + kt * 32 + 31 > q0) {   // the tile straddles the boundary (wave-uniform)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const int key = kc0 + kt * 32 + (i & 3) + 8 * (i >> 2) + 4 * h2;
+                    if (key >= a.prefix && key > q0 + r) s[i] = -INFINITY;
                 }
             }
             // (the maximum reads the accumulator from inline asm: the MFMA -> VALU wait states are not inserted in front of inline asm,
@@ -863,8 +883,10 @@ __global__ __launch_bounds__(640) void attn_fwd_generic(const AttnArgs a, int hd
                 const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(mx), __float_as_uint(mx), false, false);
                 mx = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1])) * a.scale_log2;
             }
-            if (!__all(mx - m <= 8.0f)) {
-                const float mn = fmaxf(m, mx);
+            // MASK: each row decides by its own scores alone (alpha = 1 exactly otherwise), so that keys a row cannot see -- which move
+            // the maxima of the rows below it in the tile -- leave its result bitwise unchanged
+            if (MASK ? __any(mx - m > 8.0f) : !__all(mx - m <= 8.0f)) {
+                const float mn = (!MASK || mx - m > 8.0f) ? fmaxf(m, mx) : m;
                 const float alpha = __builtin_amdgcn_exp2f(m - mn);
                 m = mn;
                 lsum *= alpha;
@@ -896,11 +918,12 @@ __global__ __launch_bounds__(640) void attn_fwd_generic(const AttnArgs a, int hd
         }
         if (lone_key) {
             const int key = nk - 1;                                   // row of the chunk
-            const char* kp = ks + key * (HDP * 2) + h2 * 16;
+            const char* kp = ks + key * (HDP * 2);
             float s0 = 0.f, s1 = 0.f;
 #pragma unroll
             for (int st = 0; st < KS; ++st) {
-                const u32x4_t kq = *(const u32x4_t*)(kp + st * 32), qq = __builtin_bit_cast(u32x4_t, qf[st]);
+                const int c = 2 * st + h2;
+                const u32x4_t kq = *(const u32x4_t*)(kp + ((SWZ ? c ^ ((key >> 1) & 7) : c) << 4)), qq = __builtin_bit_cast(u32x4_t, qf[st]);
                 asm("v_dot2c_f32_bf16 %0, %1, %2" : "+v"(s0) : "v"(qq[0]), "v"(kq[0]));
                 asm("v_dot2c_f32_bf16 %0, %1, %2" : "+v"(s1) : "v"(qq[1]), "v"(kq[1]));
                 asm("v_dot2c_f32_bf16 %0, %1, %2" : "+v"(s0) : "v"(qq[2]), "v"(kq[2]));
@@ -912,9 +935,13 @@ __global__ __launch_bounds__(640) void attn_fwd_generic(const AttnArgs a, int hd
                 const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(sd), __float_as_uint(sd), false, false);
                 sd = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
             }
-            const float mx = sd * a.scale_log2;
-            if (!__all(mx - m <= 8.0f)) {
-                const float mn = fmaxf(m, mx);
+            // MASK: the lone key is visible to this lane's query like any other key (weight exactly 0 otherwise)
+            const bool seen = !MASK || kc0 + key < a.prefix || kc0 + key <= q0 + r;
+            const float mx = seen ? sd * a.scale_log2 : -INFINITY;
+            // MASK: each row decides by its own scores alone (alpha = 1 exactly otherwise), so that keys a row cannot see -- which move
+            // the maxima of the rows below it in the tile -- leave its result bitwise unchanged
+            if (MASK ? __any(mx - m > 8.0f) : !__all(mx - m <= 8.0f)) {
+                const float mn = (!MASK || mx - m > 8.0f) ? fmaxf(m, mx) : m;
                 const float alpha = __builtin_amdgcn_exp2f(m - mn);
                 m = mn;
                 lsum *= alpha;
@@ -1084,6 +1111,7 @@ int attention_impl(const ov_bf16* qkv, int64_t ld_qkv, ov_bf16* out, int64_t ld_
     g.qkv = qkv; g.ldq = ld_qkv; g.out = out; g.ldo = ld_out;
     g.B = B; g.L = L; g.H = H; g.nqt = nqt;
     g.scale_log2 = scale_log2;
+    g.prefix = L;
     // up to 320 (padded) keys: the whole head resident in LDS (123 KB at 320) and one wave per query tile (<= 10), so a head is
     // staged once by one workgroup (L = 257 used to take two 256-key chunks and a second workgroup for the 257th query row: So400m's
     // attention 8.0 ms per step); longer sequences: 256-key chunks, 8 waves
@@ -1105,3 +1133,41 @@ int attention_impl(const ov_bf16* qkv, int64_t ld_qkv, ov_bf16* out, int64_t ld_
     return OV_OK;
 }
 }  // namespace
+
+// Prefix-causal attention (the text decoder's prefix-LM mask; prefix = 0: causal, prefix = L: unmasked = ov_attention itself).
+// Every head_dim takes the generic kernel's MASK form: 64 at its own width (HDP = 64), 72 / 80 / ... padded to 96.
+extern "C" int ov_attention_prefix(const ov_bf16* qkv, int64_t ld_qkv, ov_bf16* out, int64_t ld_out, int B, int L, int H, int hd, float scale,
+                                   int prefix, ov_stream_t stream) {
+    if (!qkv || !out || B <= 0 || L <= 0 || H <= 0) return OV_ERR_INVALID;
+    if (prefix < 0 || prefix > L) return OV_ERR_INVALID;
+    if (prefix == L) return ov_attention(qkv, ld_qkv, out, ld_out, B, L, H, hd, scale, stream);
+    if (hd <= 0 || hd % 8 || hd > 96) return OV_ERR_UNSUPPORTED;
+    if (ld_qkv % 8 || ld_out % 8 || ld_qkv < 3 * H * hd || ld_out < H * hd) return OV_ERR_INVALID;
+    if (((uintptr_t)qkv | (uintptr_t)out) & 15) return OV_ERR_INVALID;
+    if ((int64_t)B * H > 0x7fffffffLL) return OV_ERR_UNSUPPORTED;
+    AttnArgs g;
+    g.qkv = qkv; g.ldq = ld_qkv; g.out = out; g.ldo = ld_out;
+    g.B = B; g.L = L; g.H = H; g.nqt = (L + 31) / 32;
+    g.scale_log2 = scale * 1.4426950408889634f;
+    g.prefix = prefix;
+    const int lp = g.nqt * 32;
+    const bool resident = lp <= 320;                  // as the unmasked generic launch: the head resident, one wave per query tile
+    g.KC = resident ? lp : 256;
+    const int nwg = resident ? g.nqt : 8;
+    const int hdp = hd == 64 ? 64 : 96;
+    const size_t smem = (size_t)g.KC * hdp * 4;       // K (KC x 2 hdp B) + V (hdp / 32 x KC x 64 B)
+    static OvPerDeviceOnce attr;
+    const int dev = ov_current_device();
+    if (attr.need(dev)) {
+        hipError_t e = hipFuncSetAttribute((const void*)attn_fwd_generic<64, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e == hipSuccess)
+            e = hipFuncSetAttribute((const void*)attn_fwd_generic<96, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e != hipSuccess) return OV_ERR_HIP - (int)e;
+        attr.mark(dev);
+    }
+    const dim3 grid((unsigned)(B * H), (unsigned)((g.nqt + nwg - 1) / nwg)), blk(nwg * 64);
+    if (hdp == 64) hipLaunchKernelGGL((attn_fwd_generic<64, true>), grid, blk, smem, (hipStream_t)stream, g, hd);
+    else hipLaunchKernelGGL((attn_fwd_generic<96, true>), grid, blk, smem, (hipStream_t)stream, g, hd);
+    OV_LAUNCH_CHECK();
+    return OV_OK;
+}

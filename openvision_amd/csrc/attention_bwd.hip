@@ -1,4 +1,5 @@
-// attention_bwd.hip — backward of the unmasked softmax attention inside nn.MultiheadAttention (gfx950, head_dim 64).
+// attention_bwd.hip — backward of the softmax attention inside nn.MultiheadAttention (gfx950): unmasked, and prefix-causal in the
+// streaming kernels' MASK form (ov_attention_prefix_backward).
 //
 // The reference obtains it from autograd through nn.MultiheadAttention (open_clip/transformer.py:225,239-252; torch
 // nn/functional.py scaled-dot-product path).  With S = scale Q K^T, P = softmax(S), O = P V and an upstream dO:
@@ -275,6 +276,9 @@ __global__ __launch_bounds__(640) void attn_bwd_hd64(const AttnBwdArgs a) {
 //   attn_bwd_stream_q   own = query tiles; chunks of K (pass 1: lse) then K and V (pass 2: dQ); writes lse, delta to global
 //   attn_bwd_stream_kv  own = key tiles; chunks of Q and dO with their lse / delta; writes dK, dV
 // NDH = 32-wide d slices of an image (2: head_dim 64; 3: head dims 72 / 80 zero-padded to 96, So400m and H/14).
+// MASK (ov_attention_prefix_backward): the prefix-causal rule of the forward.  P = 0 exactly for an invisible pair, and the 32 x 32 tile
+// pairs no query of which sees any key are skipped in all three passes (a query tile q0 sees keys below max(prefix, q0 + 32); a key
+// tile k0 >= prefix is seen by the query tiles from k0 on), whole 256-row chunks of them are not staged.
 constexpr int CH = 256;                       // chunk rows
 
 struct AttnBwdSArgs {
@@ -282,6 +286,7 @@ struct AttnBwdSArgs {
     float* lse;                               // [B*H, Lpad] log2-domain row lse
     float* dlt;                               // [B*H, Lpad]
     int Lpad, nblk, hd;
+    int prefix;                               // MASK kernels: key j is visible to query i iff j < prefix or j <= i
 };
 
 template <int NDH>
@@ -358,7 +363,7 @@ __device__ __forceinline__ void tr_half(unsigned a0, unsigned b0, bf16x8_t& f0, 
         }                                                                                                                             \
     };
 
-template <int NDH>
+template <int NDH, bool MASK = false>
 __global__ __launch_bounds__(512) void attn_bwd_stream_q(const AttnBwdSArgs g) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     typedef Stream<NDH> St;
@@ -379,7 +384,10 @@ __global__ __launch_bounds__(512) void attn_bwd_stream_q(const AttnBwdSArgs g) {
     bf16x8_t qB[2 * NDH], dB[2 * NDH];
     St::load_own(qB, qbase, a.ldq, qrow, h2, hd);
     St::load_own(dB, dbase, a.lddo, qrow, h2, hd);
-    const int nchunk = (L + CH - 1) / CH;
+    // MASK: keys below kvis are the ones this wave's query tile sees, below kend the workgroup's last tile
+    const int kvis = MASK ? min(L, max(g.prefix, blk * CH + wave * 32 + 32)) : L;
+    const int kend = MASK ? min(L, max(g.prefix, blk * CH + CH)) : L;
+    const int nchunk = (kend + CH - 1) / CH;
 
     // pass 1: lse over all keys
     float m = -INFINITY, l = 0.f;
@@ -387,7 +395,7 @@ __global__ __launch_bounds__(512) void attn_bwd_stream_q(const AttnBwdSArgs g) {
         __syncthreads();
         St::stage(img0, img1, qbase + HD, qbase + HD, a.ldq, a.ldq, ck * CH, L, hd, tid, blockDim.x, 1);
         __syncthreads();
-        const int ntile = (min(L - ck * CH, CH) + 31) >> 5;
+        const int ntile = (max(min(kvis - ck * CH, CH), 0) + 31) >> 5;
         for (int j = 0; j < ntile; ++j) {
             f32x16_t s;
 #pragma unroll
@@ -398,7 +406,8 @@ __global__ __launch_bounds__(512) void attn_bwd_stream_q(const AttnBwdSArgs g) {
 #pragma unroll
             for (int t = 0; t < 16; ++t) {
                 const int key = ck * CH + j * 32 + (t & 3) + 8 * (t >> 2) + 4 * h2;
-                s[t] = key < L ? s[t] * a.scale_log2 : -INFINITY;
+                const bool seen = key < L && (!MASK || key < g.prefix || key <= query);
+                s[t] = seen ? s[t] * a.scale_log2 : -INFINITY;
                 mx = fmaxf(mx, s[t]);
             }
             if (mx > -INFINITY) {
@@ -445,7 +454,7 @@ __global__ __launch_bounds__(512) void attn_bwd_stream_q(const AttnBwdSArgs g) {
         __syncthreads();
         St::stage(img0, img1, qbase + HD, qbase + 2 * HD, a.ldq, a.ldq, ck * CH, L, hd, tid, blockDim.x, 2);
         __syncthreads();
-        const int ntile = (min(L - ck * CH, CH) + 31) >> 5;
+        const int ntile = (max(min(kvis - ck * CH, CH), 0) + 31) >> 5;
         for (int j = 0; j < ntile; ++j) {
             f32x16_t s, dp;
 #pragma unroll
@@ -457,7 +466,8 @@ __global__ __launch_bounds__(512) void attn_bwd_stream_q(const AttnBwdSArgs g) {
 #pragma unroll
             for (int t = 0; t < 16; ++t) {
                 const int key = ck * CH + j * 32 + (t & 3) + 8 * (t >> 2) + 4 * h2;
-                const float p = key < L ? __builtin_amdgcn_exp2f(fmaf(s[t], a.scale_log2, -lse2)) : 0.f;
+                const bool seen = key < L && (!MASK || key < g.prefix || key <= query);
+                const float p = seen ? __builtin_amdgcn_exp2f(fmaf(s[t], a.scale_log2, -lse2)) : 0.f;
                 s[t] = p * (dp[t] - delta);
             }
             tr_mma(img0, j, pack8(s, 0), pack8(s, 1), dq);
@@ -466,7 +476,7 @@ __global__ __launch_bounds__(512) void attn_bwd_stream_q(const AttnBwdSArgs g) {
     if (query < L) St::store(a.dqkv + ((int64_t)b * L + query) * a.lddq + h * hd, dq, a.scale, h2, hd);
 }
 
-template <int NDH>
+template <int NDH, bool MASK = false>
 __global__ __launch_bounds__(512) void attn_bwd_stream_kv(const AttnBwdSArgs g) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     typedef Stream<NDH> St;
@@ -495,7 +505,9 @@ __global__ __launch_bounds__(512) void attn_bwd_stream_kv(const AttnBwdSArgs g) 
 #pragma unroll
         for (int t = 0; t < 16; ++t) { dk[dh][t] = 0.f; dv[dh][t] = 0.f; }
     const int nchunk = (L + CH - 1) / CH;
-    for (int ck = 0; ck < nchunk; ++ck) {
+    // MASK: a key block at or beyond the prefix is seen by the query chunks from its own on; this wave's key tile k0 likewise by tiles
+    const int k0 = blk * CH + wave * 32;
+    for (int ck = (MASK && blk * CH >= g.prefix) ? blk : 0; ck < nchunk; ++ck) {
         __syncthreads();
         St::stage(img0, img1, qbase, dbase, a.ldq, a.lddo, ck * CH, L, hd, tid, blockDim.x, 2);
         for (int q = tid; q < CH; q += blockDim.x) {
@@ -507,6 +519,7 @@ __global__ __launch_bounds__(512) void attn_bwd_stream_kv(const AttnBwdSArgs g) 
         __syncthreads();
         const int ntile = (min(L - ck * CH, CH) + 31) >> 5;
         for (int i = 0; i < ntile; ++i) {
+            if (MASK && k0 >= g.prefix && ck * CH + i * 32 + 31 < k0) continue;     // no query of the tile sees a key of this wave's
             f32x16_t s, dp;
 #pragma unroll
             for (int t = 0; t < 16; ++t) { s[t] = 0.f; dp[t] = 0.f; }
@@ -517,7 +530,8 @@ __global__ __launch_bounds__(512) void attn_bwd_stream_kv(const AttnBwdSArgs g) 
 #pragma unroll
             for (int t = 0; t < 16; ++t) {
                 const int ql = i * 32 + (t & 3) + 8 * (t >> 2) + 4 * h2;
-                const float p = ck * CH + ql < L ? __builtin_amdgcn_exp2f(fmaf(s[t], a.scale_log2, -lse_s[ql])) : 0.f;
+                const bool seen = ck * CH + ql < L && (!MASK || key < g.prefix || key <= ck * CH + ql);
+                const float p = seen ? __builtin_amdgcn_exp2f(fmaf(s[t], a.scale_log2, -lse_s[ql])) : 0.f;
                 s[t] = p;
                 dp[t] = p * (dp[t] - dlt_s[ql]);
             }
@@ -542,25 +556,33 @@ extern "C" size_t ov_attention_backward_workspace_bytes(int B, int L, int H, int
 }
 
 namespace {
-template <int NDH>
+template <int NDH, bool MASK = false>
 int launch_stream(const AttnBwdSArgs& g, int B, hipStream_t st) {
     static OvPerDeviceOnce attr;
     const int dev = ov_current_device();
     const size_t smem = (size_t)2 * Stream<NDH>::IMG + (size_t)2 * CH * sizeof(float);
     if (attr.need(dev)) {
-        hipError_t e = hipFuncSetAttribute((const void*)attn_bwd_stream_q<NDH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)attn_bwd_stream_kv<NDH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+        hipError_t e = hipFuncSetAttribute((const void*)attn_bwd_stream_q<NDH, MASK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)attn_bwd_stream_kv<NDH, MASK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
         if (e != hipSuccess) return ov_hip(e);
         attr.mark(dev);
     }
     const dim3 grid((unsigned)(B * g.a.H * g.nblk));
-    hipLaunchKernelGGL(attn_bwd_stream_q<NDH>, grid, dim3(512), smem, st, g);
+    hipLaunchKernelGGL((attn_bwd_stream_q<NDH, MASK>), grid, dim3(512), smem, st, g);
     OV_LAUNCH_CHECK();
-    hipLaunchKernelGGL(attn_bwd_stream_kv<NDH>, grid, dim3(512), smem, st, g);
+    hipLaunchKernelGGL((attn_bwd_stream_kv<NDH, MASK>), grid, dim3(512), smem, st, g);
     OV_LAUNCH_CHECK();
     return OV_OK;
 }
 }  // namespace
+
+// The masked backward always takes the streaming kernels (row lse and delta in the workspace), also where the unmasked one is resident.
+extern "C" size_t ov_attention_prefix_backward_workspace_bytes(int B, int L, int H, int hd) {
+    (void)hd;
+    if (B <= 0 || L <= 0 || H <= 0) return 0;
+    const int64_t lpad = (int64_t)(L + CH - 1) / CH * CH;
+    return (size_t)2 * B * H * lpad * sizeof(float);
+}
 
 // lse (or NULL): the forward's row statistics from ov_attention_lse, [B*H][L rounded up to 32]; used by the resident kernel
 // (head_dim 64, L <= 288), ignored by the streaming kernels
@@ -600,6 +622,7 @@ extern "C" int ov_attention_backward_saved(const ov_bf16* qkv, int64_t ld_qkv, c
     AttnBwdSArgs g;
     g.a = a;
     g.hd = hd;
+    g.prefix = L;
     g.nblk = (L + CH - 1) / CH;
     g.Lpad = g.nblk * CH;
     g.lse = (float*)workspace;
@@ -613,4 +636,33 @@ extern "C" int ov_attention_backward(const ov_bf16* qkv, int64_t ld_qkv, const o
                                      void* workspace, size_t workspace_bytes, ov_stream_t stream) {
     return ov_attention_backward_saved(qkv, ld_qkv, out, ld_out, dout, ld_dout, dqkv, ld_dqkv, nullptr, B, L, H, hd, scale, workspace,
                                        workspace_bytes, stream);
+}
+
+extern "C" int ov_attention_prefix_backward(const ov_bf16* qkv, int64_t ld_qkv, const ov_bf16* out, int64_t ld_out, const ov_bf16* dout,
+                                            int64_t ld_dout, ov_bf16* dqkv, int64_t ld_dqkv, int B, int L, int H, int hd, float scale,
+                                            int prefix, void* workspace, size_t workspace_bytes, ov_stream_t stream) {
+    if (!qkv || !out || !dout || !dqkv || B <= 0 || L <= 0 || H <= 0) return OV_ERR_INVALID;
+    if (prefix < 0 || prefix > L) return OV_ERR_INVALID;
+    if (prefix == L)
+        return ov_attention_backward(qkv, ld_qkv, out, ld_out, dout, ld_dout, dqkv, ld_dqkv, B, L, H, hd, scale, workspace, workspace_bytes, stream);
+    if (hd <= 0 || hd % 8 || hd > 96) return OV_ERR_UNSUPPORTED;
+    if (ld_qkv % 8 || ld_out % 8 || ld_dout % 8 || ld_dqkv % 8 || ld_qkv < 3 * H * hd || ld_dqkv < 3 * H * hd || ld_out < H * hd ||
+        ld_dout < H * hd)
+        return OV_ERR_UNSUPPORTED;
+    if (((uintptr_t)qkv | (uintptr_t)out | (uintptr_t)dout | (uintptr_t)dqkv) & 15) return OV_ERR_INVALID;
+    if (!workspace || ((uintptr_t)workspace & 15)) return OV_ERR_INVALID;
+    if (workspace_bytes < ov_attention_prefix_backward_workspace_bytes(B, L, H, hd)) return OV_ERR_WORKSPACE;
+    AttnBwdSArgs g;
+    g.a.qkv = qkv; g.a.ldq = ld_qkv; g.a.out = out; g.a.ldo = ld_out; g.a.dout = dout; g.a.lddo = ld_dout; g.a.dqkv = dqkv; g.a.lddq = ld_dqkv;
+    g.a.L = L; g.a.H = H; g.a.KC = (L + 31) / 32 * 32;
+    g.a.scale = scale; g.a.scale_log2 = scale * 1.4426950408889634f;
+    g.a.lse_in = nullptr;
+    g.hd = hd;
+    g.prefix = prefix;
+    g.nblk = (L + CH - 1) / CH;
+    g.Lpad = g.nblk * CH;
+    g.lse = (float*)workspace;
+    g.dlt = g.lse + (size_t)B * H * g.Lpad;
+    if ((int64_t)B * H * g.nblk > 0x7fffffffLL) return OV_ERR_UNSUPPORTED;
+    return hd <= 64 ? launch_stream<2, true>(g, B, (hipStream_t)stream) : launch_stream<3, true>(g, B, (hipStream_t)stream);
 }

@@ -24,6 +24,12 @@ extern "C" int ov_attention_backward_saved(const ov_bf16* qkv, int64_t ld_qkv, c
                                            int64_t ld_dout, ov_bf16* dqkv, int64_t ld_dqkv, const float* lse, int B, int L, int H, int hd,
                                            float scale, void* workspace, size_t workspace_bytes, ov_stream_t stream);
 extern "C" size_t ov_attention_backward_workspace_bytes(int B, int L, int H, int hd);
+extern "C" int ov_attention_prefix(const ov_bf16* qkv, int64_t ld_qkv, ov_bf16* out, int64_t ld_out, int B, int L, int H, int hd, float scale,
+                                   int prefix, ov_stream_t stream);
+extern "C" size_t ov_attention_prefix_backward_workspace_bytes(int B, int L, int H, int hd);
+extern "C" int ov_attention_prefix_backward(const ov_bf16* qkv, int64_t ld_qkv, const ov_bf16* out, int64_t ld_out, const ov_bf16* dout,
+                                            int64_t ld_dout, ov_bf16* dqkv, int64_t ld_dqkv, int B, int L, int H, int hd, float scale,
+                                            int prefix, void* workspace, size_t workspace_bytes, ov_stream_t stream);
 extern "C" int ov_gemm_batched(const ov_bf16* A, int64_t lda, int64_t stride_a, const ov_bf16* W, int64_t ldw, int64_t stride_w,
                                ov_bf16* C, int64_t ldc, int64_t stride_c, int64_t M, int N, int K, int batch, ov_stream_t stream);
 extern "C" int ov_gemm_tn_batched(const ov_bf16* P, int64_t ldp, const ov_bf16* Q, int64_t ldq, ov_bf16* C, int64_t ldc, int64_t stride_c,
@@ -549,7 +555,8 @@ inline BlockBufs plan_block(const ov_tower_cfg* c, int B, int L, char* base) {
     lb = lb > l2 ? lb : l2; lb = lb > l3 ? lb : l3; lb = lb > l4 ? lb : l4;
     b.lin_bytes = lb; b.lin = take(lb);
     b.ln_bytes = ov_layernorm_backward_workspace_bytes(M, D); b.ln = take(b.ln_bytes);
-    b.att_bytes = ov_attention_backward_workspace_bytes(B, L, c->heads, c->width / c->heads); b.att = take(b.att_bytes + 256);
+    b.att_bytes = ov_attention_prefix_backward_workspace_bytes(B, L, c->heads, c->width / c->heads);   // >= the unmasked backward's
+    b.att = take(b.att_bytes + 256);
     b.total = off;
     return b;
 }
@@ -565,9 +572,25 @@ extern "C" size_t ov_block_backward_workspace_bytes(const ov_tower_cfg* cfg, int
     return plan_block(cfg, B, L, nullptr).total;
 }
 
+namespace {
+// the attention backward of a block: masked (prefix >= 0; the kept lse is not used) or not
+int attn_bwd(int prefix, const ov_bf16* qkv, int64_t ldq, const ov_bf16* o, int64_t ldo, const ov_bf16* dout, int64_t lddo, ov_bf16* dqkv,
+             int64_t lddq, const float* lse, int B, int L, int H, int hd, float scale, void* ws, size_t ws_bytes, ov_stream_t stream) {
+    if (prefix >= 0) return ov_attention_prefix_backward(qkv, ldq, o, ldo, dout, lddo, dqkv, lddq, B, L, H, hd, scale, prefix, ws, ws_bytes, stream);
+    return ov_attention_backward_saved(qkv, ldq, o, ldo, dout, lddo, dqkv, lddq, lse, B, L, H, hd, scale, ws, ws_bytes, stream);
+}
+}  // namespace
+
 extern "C" int ov_block_backward(const ov_tower_cfg* cfg, const ov_block_weights* w, const ov_bf16* x, const ov_block_saved* saved,
                                  const ov_bf16* dy, ov_bf16* dx, const ov_block_grads* g, int B, int L, void* workspace,
                                  size_t workspace_bytes, ov_stream_t stream) {
+    return ov_block_backward_prefix(cfg, w, x, saved, dy, dx, g, -1, B, L, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ov_block_backward_prefix(const ov_tower_cfg* cfg, const ov_block_weights* w, const ov_bf16* x, const ov_block_saved* saved,
+                                        const ov_bf16* dy, ov_bf16* dx, const ov_block_grads* g, int prefix, int B, int L, void* workspace,
+                                        size_t workspace_bytes, ov_stream_t stream) {
+    if (prefix < -1 || prefix > L) return OV_ERR_INVALID;
     if (!cfg || !w || !x || !dy || !dx || !g || !workspace || B <= 0 || L <= 0) return OV_ERR_INVALID;
     if (saved && (!saved->qkv || !saved->attn_out || !saved->x1)) return OV_ERR_INVALID;
     if (!block_cfg_ok(cfg)) return OV_ERR_UNSUPPORTED;                        // head_dim % 8 == 0 and <= 96, width % 64 == 0
@@ -594,7 +617,8 @@ extern "C" int ov_block_backward(const ov_tower_cfg* cfg, const ov_block_weights
         b.qkv = const_cast<ov_bf16*>(saved->qkv); b.o = const_cast<ov_bf16*>(saved->attn_out); b.x1 = const_cast<ov_bf16*>(saved->x1);
     } else {
         OV_TRY(ov_gemm(b.n1, D, w->qkv_w, D, w->qkv_b, b.qkv, 3 * D, M, 3 * D, D, OV_EPI_BIAS, nullptr, 0, 0, 0, 0, stream));
-        OV_TRY(ov_attention(b.qkv, 3 * D, b.o, D, B, L, H, hd, scale, stream));
+        if (prefix >= 0) OV_TRY(ov_attention_prefix(b.qkv, 3 * D, b.o, D, B, L, H, hd, scale, prefix, stream));
+        else OV_TRY(ov_attention(b.qkv, 3 * D, b.o, D, B, L, H, hd, scale, stream));
         OV_TRY(ov_gemm(b.o, D, w->out_w, D, w->out_b, b.x1, D, M, D, D, OV_EPI_BIAS_RESIDUAL, x, D, 0, 0, 0, stream));
     }
     if (saved && saved->ln2_out) b.n2 = const_cast<ov_bf16*>(saved->ln2_out);
@@ -616,8 +640,8 @@ extern "C" int ov_block_backward(const ov_tower_cfg* cfg, const ov_block_weights
     OV_TRY(ov_layernorm_backward(b.x1, D, w->ln2_w, b.t1, D, dy, D, b.dx1, D, g->ln2_w, g->ln2_b, M, D, eps, b.ln, b.ln_bytes, stream)); // dx1 = dy + ...
     // ---- attention branch: x1 = x + out_proj(attn(qkv))
     OV_TRY(ov_linear_backward(b.dx1, D, b.o, D, w->out_w, D, M, D, D, b.t1, D, g->out_w, D, g->out_b, b.lin, b.lin_bytes, stream));     // t1 = d attention out
-    OV_TRY(ov_attention_backward_saved(b.qkv, 3 * D, b.o, D, b.t1, D, b.dqkv, 3 * D, saved ? saved->attn_lse : nullptr, B, L, H, hd, scale, b.att,
-                                       b.att_bytes, stream));
+    OV_TRY(attn_bwd(prefix, b.qkv, 3 * D, b.o, D, b.t1, D, b.dqkv, 3 * D, saved ? saved->attn_lse : nullptr, B, L, H, hd, scale, b.att,
+                    b.att_bytes, stream));
     OV_TRY(ov_linear_backward(b.dqkv, 3 * D, b.n1, D, w->qkv_w, D, M, 3 * D, D, b.t1, D, g->qkv_w, D, g->qkv_b, b.lin, b.lin_bytes, stream));  // t1 = d ln_1 out
     OV_TRY(ov_layernorm_backward(x, D, w->ln1_w, b.t1, D, b.dx1, D, dx, D, g->ln1_w, g->ln1_b, M, D, eps, b.ln, b.ln_bytes, stream));
 #undef OV_TRY
@@ -688,7 +712,7 @@ inline InputBufs plan_input(const ov_tower_cfg* c, int B, int L, bool mlp, char*
     b.dx1 = mlp ? (ov_bf16*)take((size_t)M * D * 2) : nullptr;
     b.t1 = (ov_bf16*)take((size_t)M * D * 2);
     b.dqkv = (ov_bf16*)take((size_t)M * 3 * D * 2);
-    b.att_bytes = ov_attention_backward_workspace_bytes(B, L, c->heads, c->width / c->heads);
+    b.att_bytes = ov_attention_prefix_backward_workspace_bytes(B, L, c->heads, c->width / c->heads);   // >= the unmasked backward's
     b.att = take(b.att_bytes + 256);
     b.total = off;
     return b;
@@ -700,14 +724,14 @@ inline const float* lse_if_used(const ov_tower_cfg* c, int L, const float* lse) 
 
 // the attention half: dx = dx1 + d(x + out_proj(attn(ln_1(x))))/dx . dx1
 int attn_backward_input(const ov_tower_cfg* cfg, const ov_block_weights* w, const ov_bf16* x, const ov_bf16* qkv, const ov_bf16* attn_out,
-                        const float* lse, const ov_bf16* dx1, ov_bf16* dx, int B, int L, const InputBufs& b, ov_stream_t stream) {
+                        const float* lse, const ov_bf16* dx1, ov_bf16* dx, int prefix, int B, int L, const InputBufs& b, ov_stream_t stream) {
     const int D = cfg->width, H = cfg->heads, hd = D / H;
     const int64_t M = (int64_t)B * L;
     const float scale = 1.0f / sqrtf((float)hd);
     int rc;
     if ((rc = linear_dx(dx1, D, w->out_w, D, M, D, D, b.t1, D, b.wt, stream))) return rc;                                   // t1 = d attention out
-    if ((rc = ov_attention_backward_saved(qkv, 3 * D, attn_out, D, b.t1, D, b.dqkv, 3 * D, lse_if_used(cfg, L, lse), B, L, H, hd, scale, b.att,
-                                          b.att_bytes, stream)))
+    if ((rc = attn_bwd(prefix, qkv, 3 * D, attn_out, D, b.t1, D, b.dqkv, 3 * D, lse_if_used(cfg, L, lse), B, L, H, hd, scale, b.att, b.att_bytes,
+                       stream)))
         return rc;
     if ((rc = linear_dx(b.dqkv, 3 * D, w->qkv_w, D, M, 3 * D, D, b.t1, D, b.wt, stream))) return rc;                        // t1 = d ln_1 out
     return layernorm_dx(x, D, w->ln1_w, b.t1, D, dx1, D, dx, D, M, D, cfg->ln_eps, stream);
@@ -730,7 +754,7 @@ extern "C" int ov_block_attn_backward_input(const ov_tower_cfg* cfg, const ov_bl
     if (((uintptr_t)workspace | (uintptr_t)x | (uintptr_t)qkv | (uintptr_t)attn_out | (uintptr_t)dx1 | (uintptr_t)dx | (uintptr_t)lse) & 15)
         return OV_ERR_INVALID;
     const InputBufs b = plan_input(cfg, B, L, false, (char*)workspace);
-    return attn_backward_input(cfg, w, x, qkv, attn_out, lse, dx1, dx, B, L, b, stream);
+    return attn_backward_input(cfg, w, x, qkv, attn_out, lse, dx1, dx, -1, B, L, b, stream);
 }
 
 // One block's input gradient from the activations ov_tower_forward_saving kept (qkv, attention out, x1, c_fc pre-activation, lse):
@@ -740,7 +764,7 @@ size_t block_backward_input_workspace_bytes(const ov_tower_cfg* cfg, int B, int 
     return plan_input(cfg, B, L, true, nullptr).total;
 }
 int block_backward_input(const ov_tower_cfg* cfg, const ov_block_weights* w, const ov_bf16* x, const ov_block_saved* s, const ov_bf16* dy,
-                         ov_bf16* dx, int B, int L, void* workspace, ov_stream_t stream) {
+                         ov_bf16* dx, int prefix, int B, int L, void* workspace, ov_stream_t stream) {
     const int D = cfg->width, F = cfg->mlp_pad;
     const int64_t M = (int64_t)B * L;
     const InputBufs b = plan_input(cfg, B, L, true, (char*)workspace);
@@ -751,7 +775,7 @@ int block_backward_input(const ov_tower_cfg* cfg, const ov_block_weights* w, con
         return rc;
     if ((rc = linear_dx(b.dh, F, w->fc_w, D, M, F, D, b.t1, D, b.wt, stream))) return rc;
     if ((rc = layernorm_dx(s->x1, D, w->ln2_w, b.t1, D, dy, D, b.dx1, D, M, D, cfg->ln_eps, stream))) return rc;
-    return attn_backward_input(cfg, w, x, s->qkv, s->attn_out, s->attn_lse, b.dx1, dx, B, L, b, stream);
+    return attn_backward_input(cfg, w, x, s->qkv, s->attn_out, s->attn_lse, b.dx1, dx, prefix, B, L, b, stream);
 }
 
 // ---- partial backward (frozen parameters: LiT, a frozen text tower) ----------------------------------------------------------------
@@ -776,8 +800,8 @@ int block_grad_pairs(const ov_block_grads* g) {
 // dW-only or combined linear_backward; the full, dx-only or parameter-only LayerNorm rows), so what comes out is bitwise its result.
 // Workspace: ov_block_backward_workspace_bytes.
 int block_backward_partial(const ov_tower_cfg* cfg, const ov_block_weights* w, const ov_bf16* x, const ov_block_saved* s,
-                           const ov_bf16* dy, ov_bf16* dx, const ov_block_grads* g, int B, int L, void* workspace, size_t workspace_bytes,
-                           ov_stream_t stream) {
+                           const ov_bf16* dy, ov_bf16* dx, const ov_block_grads* g, int prefix, int B, int L, void* workspace,
+                           size_t workspace_bytes, ov_stream_t stream) {
     const int pairs = block_grad_pairs(g);
     if (pairs < 0) return OV_ERR_INVALID;
     const bool p_ln1 = pairs & 1, p_qkv = pairs & 2, p_out = pairs & 4, p_ln2 = pairs & 8, p_fc = pairs & 16, p_proj = pairs & 32;
@@ -814,8 +838,7 @@ int block_backward_partial(const ov_tower_cfg* cfg, const ov_block_weights* w, c
         OV_TRY(ov_linear_backward(b.dx1, D, s->attn_out, D, w->out_w, D, M, D, D, need_dqkv ? b.t1 : nullptr, D, p_out ? g->out_w : nullptr,
                                   D, p_out ? g->out_b : nullptr, b.lin, b.lin_bytes, stream));
     if (need_dqkv)
-        OV_TRY(ov_attention_backward_saved(s->qkv, 3 * D, s->attn_out, D, b.t1, D, b.dqkv, 3 * D, s->attn_lse, B, L, H, hd, scale, b.att,
-                                           b.att_bytes, stream));
+        OV_TRY(attn_bwd(prefix, s->qkv, 3 * D, s->attn_out, D, b.t1, D, b.dqkv, 3 * D, s->attn_lse, B, L, H, hd, scale, b.att, b.att_bytes, stream));
     if (p_qkv || need_dln1)
         OV_TRY(ov_linear_backward(b.dqkv, 3 * D, s->ln1_out, D, w->qkv_w, D, M, 3 * D, D, need_dln1 ? b.t1 : nullptr, D,
                                   p_qkv ? g->qkv_w : nullptr, D, p_qkv ? g->qkv_b : nullptr, b.lin, b.lin_bytes, stream));

@@ -37,6 +37,7 @@ struct ov_tower {
     float* h_amax;                // fp8 path: [4 * layers]: scales' maxima (hidden | attention out) and the running ones (device, borrowed)
     int h_mode;
     unsigned char* mask8;         // fp8 path: per layer, which of the four GEMMs take e4m3 operands (OV_FP8_QKV | _OUT | _FC | _PROJ)
+    int prefix;                   // attention mask of every block: -1 = none, >= 0 = ov_attention_prefix's prefix (ov_tower_set_prefix)
 };
 
 // Row pitch (elements) of the workspace's `big` region (qkv / MLP hidden).  max(3 D, mlp_pad) is a power-of-two number of bytes for
@@ -225,6 +226,7 @@ extern "C" ov_tower* ov_tower_create(const ov_tower_cfg* cfg) {
     t->cfg = *cfg;
     t->h_amax = nullptr;
     t->h_mode = 0;
+    t->prefix = -1;
     t->blocks = new (std::nothrow) ov_block_weights[cfg->layers]();
     t->set = new (std::nothrow) unsigned char[cfg->layers]();
     t->fp8 = new (std::nothrow) ov_block_fp8[cfg->layers]();
@@ -301,6 +303,12 @@ extern "C" int ov_tower_set_fp8_mask(ov_tower* t, const unsigned char* mask, int
     return OV_OK;
 }
 
+extern "C" int ov_tower_set_prefix(ov_tower* t, int prefix) {
+    if (!t || prefix < -1) return OV_ERR_INVALID;
+    t->prefix = prefix;
+    return OV_OK;
+}
+
 extern "C" size_t ov_tower_workspace_bytes(const ov_tower* t, int B, int L) {
     if (!t || B <= 0 || L <= 0) return 0;
     const size_t M = (size_t)B * L;
@@ -316,7 +324,7 @@ namespace {
 // `parts` (or NULL): partial sums of x's row statistics (ov_rowparts layout).  parts_in: they describe x on entry (left by the previous
 // block's c_proj); they always describe x on exit.
 int run_block(const ov_tower_cfg& c, const ov_block_weights& w, ov_bf16* x, ov_bf16* h, ov_bf16* big, float* stats, float* parts,
-              bool parts_in, int B, int L, ov_stream_t stream, bool prof) {
+              bool parts_in, int B, int L, ov_stream_t stream, bool prof, int prefix) {
     const int D = c.width, H = c.heads, hd = D / H;
     const int64_t M = (int64_t)B * L;
     const int ldb = big_pitch(c);                               // row pitch of `big` (shared by qkv and the MLP hidden)
@@ -340,7 +348,8 @@ int run_block(const ov_tower_cfg& c, const ov_block_weights& w, ov_bf16* x, ov_b
         OV_STEP(OV_PROF_LN, ov_layernorm(x, OV_BF16, D, w.ln1_w, w.ln1_b, h, OV_BF16, D, M, D, c.ln_eps, stream));
         OV_STEP(OV_PROF_GEMM_QKV, ov_gemm(h, D, w.qkv_w, D, w.qkv_b, big, ldb, M, 3 * D, D, OV_EPI_BIAS, nullptr, 0, 0, 0, 0, stream));
     }
-    OV_STEP(OV_PROF_ATTN, ov_attention(big, ldb, h, D, B, L, H, hd, scale, stream));
+    if (prefix >= 0) OV_STEP(OV_PROF_ATTN, ov_attention_prefix(big, ldb, h, D, B, L, H, hd, scale, prefix, stream));
+    else OV_STEP(OV_PROF_ATTN, ov_attention(big, ldb, h, D, B, L, H, hd, scale, stream));
     if (rp) OV_STEP(OV_PROF_GEMM_OUT, ov_gemm_rowparts(h, D, w.out_w, D, w.out_b, x, D, M, D, D, x, D, parts, stream));
     else OV_STEP(OV_PROF_GEMM_OUT, ov_gemm(h, D, w.out_w, D, w.out_b, x, D, M, D, D, OV_EPI_BIAS_RESIDUAL, x, D, 0, 0, 0, stream));
     if (fold) {
@@ -505,6 +514,8 @@ extern "C" int ov_tower_forward(const ov_tower* t, ov_bf16* x, int B, int L, voi
     }
     const int64_t off = (int64_t)Bm * L;
     const bool fp8 = tower_fp8(t);
+    if (t->prefix >= 0 && fp8) return OV_ERR_UNSUPPORTED;          // no fp8 under a mask
+    if (t->prefix > L) return OV_ERR_INVALID;
     int rc = OV_OK;
     if (fp8 && t->h_amax && t->h_mode == 2)            // delayed scaling: last forward's maxima become this forward's scales
         rc = ov_amax_roll(t->h_amax, t->h_amax + 2 * c.layers, 2 * c.layers, stream);
@@ -520,12 +531,12 @@ extern "C" int ov_tower_forward(const ov_tower* t, ov_bf16* x, int B, int L, voi
         float* an = t->h_amax ? t->h_amax + 3 * c.layers + i : nullptr;
         const int hm = t->h_amax ? t->h_mode : 0;
         rc = fp8 ? run_block_fp8(c, t->blocks[i], t->fp8[i], t->mask8[i], x, h, big, stats, q8, qs, ha, aa, hn, an, hm, Bm, L, stream, true)
-                 : run_block(c, t->blocks[i], x, h, big, stats, parts, i > 0, Bm, L, stream, true);
+                 : run_block(c, t->blocks[i], x, h, big, stats, parts, i > 0, Bm, L, stream, true, t->prefix);
         if (rc == OV_OK && nt > 0) {
             rc = fp8 ? run_block_fp8(c, t->blocks[i], t->fp8[i], t->mask8[i], x + off * D, h + off * D, big + off * ldb, stats + 2 * off,
                                      q8 + off * qw, qs + off, ha, aa, hn, an, hm, nt, L, (ov_stream_t)tc->stream, false)
                      : run_block(c, t->blocks[i], x + off * D, h + off * D, big + off * ldb, stats + 2 * off,
-                                 parts ? parts + 2 * off * G : nullptr, i > 0, nt, L, (ov_stream_t)tc->stream, false);
+                                 parts ? parts + 2 * off * G : nullptr, i > 0, nt, L, (ov_stream_t)tc->stream, false, t->prefix);
         }
     }
     if (nt > 0) {
@@ -544,10 +555,11 @@ extern "C" int ov_tower_forward(const ov_tower* t, ov_bf16* x, int B, int L, voi
 // them; block_backward_input computes dx alone, in a smaller workspace.
 int block_grad_pairs(const ov_block_grads* g);
 int block_backward_partial(const ov_tower_cfg* cfg, const ov_block_weights* w, const ov_bf16* x, const ov_block_saved* s, const ov_bf16* dy,
-                           ov_bf16* dx, const ov_block_grads* g, int B, int L, void* workspace, size_t workspace_bytes, ov_stream_t stream);
+                           ov_bf16* dx, const ov_block_grads* g, int prefix, int B, int L, void* workspace, size_t workspace_bytes,
+                           ov_stream_t stream);
 size_t block_backward_input_workspace_bytes(const ov_tower_cfg* cfg, int B, int L);
 int block_backward_input(const ov_tower_cfg* cfg, const ov_block_weights* w, const ov_bf16* x, const ov_block_saved* s, const ov_bf16* dy,
-                         ov_bf16* dx, int B, int L, void* workspace, ov_stream_t stream);
+                         ov_bf16* dx, int prefix, int B, int L, void* workspace, ov_stream_t stream);
 
 // saved activations of one layer: [x | qkv | attention out | x1 | ln_1 out | ln_2 out | c_fc pre-activation | c_fc activation],
 // 8 D + 2 mlp_pad bf16 per token (the default keeps them all; ov_tower_forward_checkpointed keeps only x and recomputes the rest
@@ -581,10 +593,10 @@ inline Slot slot_at(const ov_tower_cfg& c, ov_bf16* sx, ov_bf16* rest, int64_t M
     s.lse = (float*)(s.act + (size_t)M * c.mlp_pad);
     return s;
 }
-inline ov_block_saved block_saved_of(const ov_tower_cfg& c, const Slot& s, int L) {
+inline ov_block_saved block_saved_of(const ov_tower_cfg& c, const Slot& s, int L, int prefix) {
     ov_block_saved sv;
     sv.qkv = s.qkv; sv.attn_out = s.o; sv.x1 = s.x1; sv.ln1_out = s.n1; sv.ln2_out = s.n2; sv.fc_pre = s.pre; sv.fc_act = s.act;
-    sv.attn_lse = ov_attn_bwd_resident(c.width / c.heads, L) ? s.lse : nullptr;
+    sv.attn_lse = prefix < 0 && ov_attn_bwd_resident(c.width / c.heads, L) ? s.lse : nullptr;   // (the masked forward keeps none)
     return sv;
 }
 
@@ -607,7 +619,8 @@ inline Slot layer_slot(const ov_tower_cfg& c, const Layout& ly, int k, int64_t M
 // One block of the saving forward: the same operator sequence as run_block, with qkv / attention output / x1 / ... written where the
 // backward will read them, the input read from s.x and the output written to y (y may be s.x: nothing reads the input after out_proj).
 // y = NULL: the slot only (the backward's recompute), c_proj is not run.
-int forward_saving_layer(const ov_tower_cfg& c, const ov_block_weights& w, const Slot& s, ov_bf16* y, int B, int L, ov_stream_t stream) {
+int forward_saving_layer(const ov_tower_cfg& c, const ov_block_weights& w, const Slot& s, ov_bf16* y, int B, int L, ov_stream_t stream,
+                         int prefix) {
     const int D = c.width, H = c.heads, hd = D / H;
     const int64_t M = (int64_t)B * L;
     const float scale = 1.0f / sqrtf((float)hd);
@@ -615,8 +628,10 @@ int forward_saving_layer(const ov_tower_cfg& c, const ov_block_weights& w, const
     int rc;
     if ((rc = ov_layernorm(s.x, OV_BF16, D, w.ln1_w, w.ln1_b, s.n1, OV_BF16, D, M, D, c.ln_eps, stream))) return rc;
     if ((rc = ov_gemm(s.n1, D, w.qkv_w, D, w.qkv_b, s.qkv, 3 * D, M, 3 * D, D, OV_EPI_BIAS, nullptr, 0, 0, 0, 0, stream))) return rc;
-    rc = ov_attn_bwd_resident(hd, L) ? ov_attention_lse(s.qkv, 3 * D, s.o, D, s.lse, B, L, H, hd, scale, stream)
-                                     : ov_attention(s.qkv, 3 * D, s.o, D, B, L, H, hd, scale, stream);
+    if (prefix >= 0) rc = ov_attention_prefix(s.qkv, 3 * D, s.o, D, B, L, H, hd, scale, prefix, stream);
+    else
+        rc = ov_attn_bwd_resident(hd, L) ? ov_attention_lse(s.qkv, 3 * D, s.o, D, s.lse, B, L, H, hd, scale, stream)
+                                         : ov_attention(s.qkv, 3 * D, s.o, D, B, L, H, hd, scale, stream);
     if (rc) return rc;
     if ((rc = ov_gemm(s.o, D, w.out_w, D, w.out_b, s.x1, D, M, D, D, OV_EPI_BIAS_RESIDUAL, s.x, D, 0, 0, 0, stream))) return rc;
     if ((rc = ov_layernorm(s.x1, OV_BF16, D, w.ln2_w, w.ln2_b, s.n2, OV_BF16, D, M, D, c.ln_eps, stream))) return rc;
@@ -631,8 +646,9 @@ int forward_saving_layer(const ov_tower_cfg& c, const ov_block_weights& w, const
 int forward_walk(const ov_tower* t, int first, ov_bf16* x, ov_bf16* scratch, const Layout& ly, int B, int L, ov_stream_t stream) {
     const ov_tower_cfg& c = t->cfg;
     const int64_t M = (int64_t)B * L;
+    if (t->prefix > L) return OV_ERR_INVALID;
     for (int i = 0; i < first; ++i) {
-        const int rc = forward_saving_layer(c, t->blocks[i], slot_at(c, x, scratch, M), x, B, L, stream);
+        const int rc = forward_saving_layer(c, t->blocks[i], slot_at(c, x, scratch, M), x, B, L, stream, t->prefix);
         if (rc) return rc;
     }
     if (first == c.layers) return OV_OK;
@@ -640,7 +656,7 @@ int forward_walk(const ov_tower* t, int first, ov_bf16* x, ov_bf16* scratch, con
     if (e != hipSuccess) return OV_ERR_HIP - (int)e;
     for (int i = first; i < c.layers; ++i) {
         const Slot s = layer_slot(c, ly, i - first, M);
-        const int rc = forward_saving_layer(c, t->blocks[i], s, i + 1 < c.layers ? s.x + ly.x_stride : x, B, L, stream);
+        const int rc = forward_saving_layer(c, t->blocks[i], s, i + 1 < c.layers ? s.x + ly.x_stride : x, B, L, stream, t->prefix);
         if (rc) return rc;
     }
     return OV_OK;
@@ -666,15 +682,16 @@ int backward_walk(const ov_tower* t, int first, int lo, const Layout& ly, bool r
                   const ov_block_grads* grads, bool want_dx, int B, int L, void* workspace, size_t workspace_bytes, ov_stream_t stream) {
     const ov_tower_cfg& c = t->cfg;
     const int64_t M = (int64_t)B * L;
+    if (t->prefix > L) return OV_ERR_INVALID;
     for (int i = c.layers - 1; i >= lo; --i) {
         const Slot s = layer_slot(c, ly, i - first, M);
         int rc;
-        if (rebuild && !(top_kept && i == c.layers - 1) && (rc = forward_saving_layer(c, t->blocks[i], s, nullptr, B, L, stream)))
+        if (rebuild && !(top_kept && i == c.layers - 1) && (rc = forward_saving_layer(c, t->blocks[i], s, nullptr, B, L, stream, t->prefix)))
             return rc;
-        const ov_block_saved sv = block_saved_of(c, s, L);
-        rc = grads ? block_backward_partial(&c, &t->blocks[i], s.x, &sv, dx, (i > lo || want_dx) ? dx : nullptr, &grads[i - first], B, L,
-                                            workspace, workspace_bytes, stream)
-                   : block_backward_input(&c, &t->blocks[i], s.x, &sv, dx, dx, B, L, workspace, stream);
+        const ov_block_saved sv = block_saved_of(c, s, L, t->prefix);
+        rc = grads ? block_backward_partial(&c, &t->blocks[i], s.x, &sv, dx, (i > lo || want_dx) ? dx : nullptr, &grads[i - first], t->prefix,
+                                            B, L, workspace, workspace_bytes, stream)
+                   : block_backward_input(&c, &t->blocks[i], s.x, &sv, dx, dx, t->prefix, B, L, workspace, stream);
         if (rc) return rc;
     }
     return OV_OK;

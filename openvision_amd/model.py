@@ -373,17 +373,19 @@ class ResidualAttentionBlock(nn.Module):
         keep = self._fp8_pk.get(key, build)
         return _lib.BlockFp8(*[C.c_void_p(t.data_ptr()) for t in keep]), keep
 
-    def forward(self, q_x: torch.Tensor, k_x=None, v_x=None, attn_mask=None) -> torch.Tensor:
+    def forward(self, q_x: torch.Tensor, k_x=None, v_x=None, attn_mask=None, causal_prefix: Optional[int] = None) -> torch.Tensor:
         if k_x is not None or v_x is not None or attn_mask is not None:
             raise NotImplementedError("OpenVision blocks are unmasked self-attention (no k_x/v_x/attn_mask)")
-        return _run_blocks([self], q_x)
+        return _run_blocks([self], q_x, prefix=causal_prefix)
 
 
 class _TowerHandle:
     """ov_tower handle + the packed tensors it borrows (kept alive here)."""
 
-    def __init__(self, blocks, fp8: bool = False, mask=None):
+    def __init__(self, blocks, fp8: bool = False, mask=None, prefix: Optional[int] = None, fold_ln: bool = True):
         lib = _lib.load()
+        if prefix is not None and fp8:
+            raise _lib.OvhipError("a causal prefix needs bf16 precision (no fp8 under an attention mask)")
         b0 = blocks[0]
         d = b0.attn.embed_dim
         if d % 64:
@@ -394,7 +396,7 @@ class _TowerHandle:
             raise _lib.OvhipError("ov_tower_create failed (invalid tower configuration)")
         self.keep = []
         for i, blk in enumerate(blocks):
-            bw, keep = blk.packed_block(fold_ln=os.environ.get("OVHIP_NO_LN_FOLD", "0") != "1")
+            bw, keep = blk.packed_block(fold_ln=fold_ln and os.environ.get("OVHIP_NO_LN_FOLD", "0") != "1")
             self.keep.append(keep)
             check(lib.ov_tower_set_block(self.handle, i, C.byref(bw)), "ov_tower_set_block")
             if fp8:
@@ -402,6 +404,9 @@ class _TowerHandle:
                 self.keep.append(keep8)
                 check(lib.ov_tower_set_block_fp8(self.handle, i, C.byref(b8)), "ov_tower_set_block_fp8")
         self.width, self.layers, self.fp8 = d, len(blocks), fp8
+        self.prefix = prefix
+        if prefix is not None:              # every block's attention: key j visible to query i iff j < prefix or j <= i
+            check(lib.ov_tower_set_prefix(self.handle, int(prefix)), "ov_tower_set_prefix")
         self.h_amax = None
         self.mask = [FP8_ALL] * len(blocks) if mask is None else list(mask)
         if fp8 and mask is not None:
@@ -466,25 +471,38 @@ class _TowerCache:
         self._pk = _Packed()
         self.precision = default_precision()
         self.mask = None             # explicit per-layer OV_FP8_* masks (set_fp8_mask); None = what the precision name implies
+        self.fold_ln = True          # False: the module's own LayerNorms and weights, the launches of the training forward (caption decoder)
 
-    def get(self, blocks) -> _TowerHandle:
+    def get(self, blocks, prefix: Optional[int] = None) -> _TowerHandle:
         fp8 = self.precision != "bf16"
         mask = None
         if fp8:
             mask = self.mask if self.mask is not None else (fp8_mixed_mask(len(blocks)) if self.precision == "fp8-mixed" else None)
             if mask is not None and len(mask) != len(blocks):
                 mask = (list(mask) + [mask[-1]] * len(blocks))[: len(blocks)]        # sub-stacks (exploded forward): layer-wise prefix
-        key = (fp8, None if mask is None else tuple(mask))
-        return self._pk.get(_block_params(blocks), lambda: _TowerHandle(blocks, fp8=fp8, mask=mask), extra=key)
+        key = (fp8, None if mask is None else tuple(mask), prefix, self.fold_ln)
+        return self._pk.get(_block_params(blocks), lambda: _TowerHandle(blocks, fp8=fp8, mask=mask, prefix=prefix, fold_ln=self.fold_ln),
+                            extra=key)
 
 
-def _run_blocks(blocks, x: torch.Tensor, cache: Optional[_TowerCache] = None, ws: Optional[_Workspace] = None):
-    """x [B, L, D] (fp32 or bf16, cuda) -> same shape/dtype after the given blocks (ov_tower_forward)."""
+def _check_prefix(prefix: Optional[int], seq: Optional[int] = None) -> Optional[int]:
+    if prefix is None:
+        return None
+    prefix = int(prefix)
+    if prefix < 0 or (seq is not None and prefix > seq):
+        raise ValueError(f"causal prefix {prefix} outside [0, {seq if seq is not None else 'L'}]")
+    return prefix
+
+
+def _run_blocks(blocks, x: torch.Tensor, cache: Optional[_TowerCache] = None, ws: Optional[_Workspace] = None,
+                prefix: Optional[int] = None):
+    """x [B, L, D] (fp32 or bf16, cuda) -> same shape/dtype after the given blocks (ov_tower_forward).  prefix: None = unmasked
+    attention, else the prefix-causal mask of ov_attention_prefix in every block."""
     _require_cuda(x, "Transformer")
     if x.dim() != 3:
         raise ValueError("expected [batch, tokens, width]")
     lib = _lib.load()
-    tower = (cache or _TowerCache()).get(blocks)
+    tower = (cache or _TowerCache()).get(blocks, _check_prefix(prefix, x.shape[1]))
     bsz, seq, d = x.shape
     if d != tower.width:
         raise ValueError(f"width {d} != {tower.width}")
@@ -507,12 +525,18 @@ class Transformer(nn.Module):
                                         for _ in range(layers)])
         self._cache = _TowerCache()
         self._ws = _Workspace()
+        self.causal_prefix: Optional[int] = None      # None = unmasked; see set_causal_prefix
+
+    def set_causal_prefix(self, prefix: Optional[int]) -> None:
+        """Attention mask of every block: None (default) = unmasked; an int P >= 0 = prefix-causal, key j is visible to query i iff
+        j < P or j <= i (P = 0: causal; the text decoder runs its stack with P = image tokens + text tokens).  bf16 precision only."""
+        self.causal_prefix = _check_prefix(prefix)
 
     def get_cast_dtype(self) -> torch.dtype:
         return self.resblocks[0].mlp.c_fc.weight.dtype          # transformer.py:350-353
 
     def tower(self) -> _TowerHandle:
-        return self._cache.get(list(self.resblocks))
+        return self._cache.get(list(self.resblocks), self.causal_prefix)
 
     def set_precision(self, precision: str, mask=None) -> None:
         """"bf16", "fp8" (all four GEMMs of every block in e4m3) or "fp8-mixed" (fp8_mixed_mask); `mask`: an OV_FP8_* bit set for
@@ -535,7 +559,7 @@ class Transformer(nn.Module):
     def forward(self, x: torch.Tensor, attn_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
         if attn_mask is not None:
             raise NotImplementedError("attn_mask is None on the OpenVision path (no_causal_mask=True)")
-        return _run_blocks(list(self.resblocks), x, self._cache, self._ws)
+        return _run_blocks(list(self.resblocks), x, self._cache, self._ws, self.causal_prefix)
 
 
 class PatchDropout(nn.Module):
@@ -865,7 +889,8 @@ class CLIP(nn.Module):
             self.visual._check_image(image)
             x = image.detach()
             x = x.contiguous() if x.dtype in (torch.float32, torch.bfloat16) else x.float().contiguous()
-            return self._graphs.run(("img", tuple(x.shape), x.dtype, bool(normalize), self.visual.transformer._cache.precision),
+            return self._graphs.run(("img", tuple(x.shape), x.dtype, bool(normalize), self.visual.transformer._cache.precision,
+                                     self.visual.transformer.causal_prefix),
                                     self._weights_sig, x, lambda t: self.visual._encode(t, normalize))
         return self.visual._encode(image, normalize)
 
@@ -876,7 +901,8 @@ class CLIP(nn.Module):
             raise ValueError(f"expected tokens [B,{self.context_length}], got {tuple(text.shape)}")
         if 0 < text.shape[0] <= self.graph_max_batch and not torch.cuda.is_current_stream_capturing() and not _graphed:
             t = text.detach().to(torch.int64).contiguous()
-            return self._graphs.run(("txt", tuple(t.shape), bool(normalize), self.transformer._cache.precision), self._weights_sig,
+            return self._graphs.run(("txt", tuple(t.shape), bool(normalize), self.transformer._cache.precision,
+                                     self.transformer.causal_prefix), self._weights_sig,
                                     t, lambda z: self.encode_text(z, normalize, _graphed=True))
         lib = _lib.load()
         head, _keep = self._text_head()

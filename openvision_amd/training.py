@@ -129,11 +129,13 @@ def _weights(ts) -> _lib.BlockWeights:
     return _lib.BlockWeights(*[C.c_void_p(t.data_ptr()) for t in ts], None, None)
 
 
-def _tower_handle(lib, cfg, keep):
+def _tower_handle(lib, cfg, keep, prefix=None):
     handle = lib.ov_tower_create(C.byref(cfg))
     if not handle:
         raise _lib.OvhipError("ov_tower_create failed")
     try:
+        if prefix is not None:
+            check(lib.ov_tower_set_prefix(handle, int(prefix)), "ov_tower_set_prefix")
         for i in range(cfg.layers):
             check(lib.ov_tower_set_block(handle, i, C.byref(_weights(keep[i]))), "ov_tower_set_block")
     except Exception:
@@ -156,10 +158,21 @@ class _TowerFn(torch.autograd.Function):
     only the inputs of layers [first, hi - lo) ("saved") and one layer's intermediates ("slot"); ``ov_tower_backward_checkpointed``
     rebuilds each block's slot before its backward.  The node holding the tower's last block keeps its slot until its backward (no
     recompute of that block); every other node hands its slot back after the forward.  Loss and gradients are bitwise those without
-    it.  In both modes a failed native call hands every pool buffer it took back."""
+    it.  In both modes a failed native call hands every pool buffer it took back.
 
-    @staticmethod
-    def forward(ctx, transformer, lo, hi, x, *params):
+    ``_PrefixTowerFn`` below is the same node with a prefix-causal attention mask (``ov_tower_set_prefix`` on the handle of the
+    forward and, from the ctx, on the handle of the backward)."""
+
+    NARGS = 3            # non-tensor arguments in front of x
+
+    @classmethod
+    def _split(cls, args):
+        return None, args[0], args[1:]
+
+    @classmethod
+    def forward(cls, ctx, transformer, lo, hi, *args):
+        prefix, x, params = cls._split(args)
+        ctx.nargs = cls.NARGS
         lib = _lib.load()
         blocks = list(transformer.resblocks)[lo:hi]
         b0 = blocks[0]
@@ -168,14 +181,16 @@ class _TowerFn(torch.autograd.Function):
             raise _lib.OvhipError("training path: width % 64 == 0 and head_dim % 8 == 0, <= 96 are required")
         bsz, seq, _ = x.shape
         layers = len(blocks)
-        need_x, need_p = ctx.needs_input_grad[3], ctx.needs_input_grad[4:]
+        need_x, need_p = ctx.needs_input_grad[ctx.nargs], ctx.needs_input_grad[ctx.nargs + 1:]
+        if prefix is not None and not 0 <= int(prefix) <= seq:
+            raise ValueError(f"causal prefix {prefix} outside [0, {seq}]")
         pairs = [[need_p[12 * i + 2 * k] or need_p[12 * i + 2 * k + 1] for k in range(6)] for i in range(layers)]
         first = 0 if need_x else next((i for i, pr in enumerate(pairs) if any(pr)), layers)
         cfg = _lib.TowerCfg(d, layers, heads, mlp, mlp_pad, int(b0.gelu_tanh), float(b0.ln_1.eps))
         keep = _packed_blocks(transformer, params, mlp, mlp_pad, (lo, hi))
         pool = _train_state(transformer)["pool"]
         remat = bool(getattr(transformer, "grad_checkpointing", False))
-        handle = _tower_handle(lib, cfg, keep)
+        handle = _tower_handle(lib, cfg, keep, prefix)
         saved = slot = None
         try:
             xb = x.detach().to(torch.bfloat16).contiguous().clone()
@@ -207,6 +222,7 @@ class _TowerFn(torch.autograd.Function):
             slot = None
         ctx.cfg, ctx.keep, ctx.saved, ctx.shape, ctx.mlp, ctx.pool = cfg, keep, saved, (bsz, seq, d), mlp, pool
         ctx.first, ctx.pairs, ctx.need = first, pairs, (need_x, need_p)
+        ctx.prefix = prefix                   # the backward masks as the forward did
         ctx.saved_gen = saved._ovhip_gen if saved is not None else None
         ctx.remat, ctx.slot = remat, slot
         ctx.x_dtype, ctx.p_dtypes = x.dtype, [p.dtype for p in params]
@@ -231,7 +247,7 @@ class _TowerFn(torch.autograd.Function):
         ctx.slot = None                       # the backward overwrites it: a second backward over this graph recomputes the top block
         handle = ws = None
         try:
-            handle = _tower_handle(lib, ctx.cfg, ctx.keep)
+            handle = _tower_handle(lib, ctx.cfg, ctx.keep, ctx.prefix)
             nbytes = lib.ov_tower_backward_partial_workspace_bytes(handle, bsz, seq)
             ws = pool.take(nbytes, dx.device)
             if ctx.remat:
@@ -259,7 +275,17 @@ class _TowerFn(torch.autograd.Function):
         # the frozen half of a mixed pair was computed with its partner and is dropped here
         flat = [g.to(ctx.p_dtypes[12 * i + j]) if g is not None and need_p[12 * i + j] else None
                 for i, gs in enumerate(grads) for j, g in enumerate(gs)]
-        return (None, None, None, dx.view(bsz, seq, d).to(ctx.x_dtype) if need_x else None, *flat)
+        return (*([None] * ctx.nargs), dx.view(bsz, seq, d).to(ctx.x_dtype) if need_x else None, *flat)
+
+
+class _PrefixTowerFn(_TowerFn):
+    """``_TowerFn`` under the prefix-causal mask: apply(transformer, lo, hi, prefix, x, *params)."""
+
+    NARGS = 4
+
+    @classmethod
+    def _split(cls, args):
+        return int(args[0]), args[1], args[2:]
 
 
 def _round_up(x: int, m: int) -> int:
@@ -444,8 +470,15 @@ def set_backward_chunk_layers(n: int) -> None:
     CHUNK_LAYERS[0] = max(0, int(n))
 
 
-def tower_forward(transformer, x: torch.Tensor) -> torch.Tensor:
-    """``transformer(x)`` with gradients: x [B, L, D] on the device -> same shape; d x and every block parameter receive grad."""
+_OWN = object()
+
+
+def tower_forward(transformer, x: torch.Tensor, prefix=_OWN) -> torch.Tensor:
+    """``transformer(x)`` with gradients: x [B, L, D] on the device -> same shape; d x and every block parameter receive grad.
+    ``prefix``: the attention mask of every block -- by default the transformer's own ``causal_prefix``; None = unmasked; an int P =
+    key j visible to query i iff j < P or j <= i.  It is kept on the autograd node, so the backward uses the forward's value."""
+    if prefix is _OWN:
+        prefix = getattr(transformer, "causal_prefix", None)
     if not x.is_cuda:
         raise _lib.OvhipError("training path: tensors must live on an MI355X device (no CPU fallback)")
     blocks = list(transformer.resblocks)
@@ -453,18 +486,21 @@ def tower_forward(transformer, x: torch.Tensor) -> torch.Tensor:
     for lo in range(0, len(blocks), step):
         hi = min(len(blocks), lo + step)
         params = [p for blk in blocks[lo:hi] for p in _block_tensors(blk)]
-        x = _TowerFn.apply(transformer, lo, hi, x, *params)
+        x = _TowerFn.apply(transformer, lo, hi, x, *params) if prefix is None else _PrefixTowerFn.apply(transformer, lo, hi, prefix, x, *params)
     return x
 
 
-def encode_image(model, image: torch.Tensor, normalize: bool = True, keep: torch.Tensor = None) -> torch.Tensor:
+def encode_image(model, image: torch.Tensor, normalize: bool = True, keep: torch.Tensor = None, output_tokens: bool = False):
     """CLIP.encode_image (model.py:265-267) with gradients.  VisionTransformer.forward, transformer.py:609-651, for the
     OpenVision configuration (no ln_pre, pool -> ln_post -> proj).
 
     Patch dropout (transformer.py:619): when the vision tower is in training mode with ``patch_dropout`` p > 0, the kept patches are
     drawn as the reference draws them (``PatchDropout.sample``: CPU default generator) and the tower runs on those 1 + K tokens.
     ``keep`` (integer [B, K], patch indices in [0, G), no repeats within an image) overrides the draw, whatever the mode and p; such
-    a table is checked on the device and the flag read back (one host synchronisation), a bad one raises IndexError."""
+    a table is checked on the device and the flag read back (one host synchronisation), a bad one raises IndexError.
+
+    ``output_tokens``: also return what the reference hands to the caption decoder (vit.py:753,786): the block stack's output without
+    the CLS token and BEFORE ln_post, [B, L - 1, width] (the kept patches under patch dropout), with gradients into the tower."""
     v = model.visual
     if not isinstance(v.ln_pre, torch.nn.Identity):
         raise _lib.OvhipError("training path: ln_pre is Identity for OpenVision towers")
@@ -493,6 +529,7 @@ def encode_image(model, image: torch.Tensor, normalize: bool = True, keep: torch
         cls = v.class_embedding.float().expand(x.shape[0], 1, -1)
         x = torch.cat([cls, x], dim=1) + v.positional_embedding.float()                            # :615-617
     x = tower_forward(v.transformer, x)
+    tokens = x[:, 1:]
     if v.final_ln_after_pool:
         pooled = x[:, 1:].mean(dim=1) if v.pool_type == "avg" else x[:, 0]
         pooled = _LayerNormFn.apply(pooled, v.ln_post.weight, v.ln_post.bias, v.ln_post.eps)
@@ -500,15 +537,17 @@ def encode_image(model, image: torch.Tensor, normalize: bool = True, keep: torch
         xx = _LayerNormFn.apply(x, v.ln_post.weight, v.ln_post.bias, v.ln_post.eps)
         pooled = xx[:, 1:].mean(dim=1) if v.pool_type == "avg" else xx[:, 0]
     out = _LinearFn.apply(pooled, v.proj.t(), None)
-    return F.normalize(out, dim=-1) if normalize else out
+    out = F.normalize(out, dim=-1) if normalize else out
+    return (out, tokens) if output_tokens else out
 
 
-def encode_text_embeddings(model, x: torch.Tensor, normalize: bool = True, pool_index=None) -> torch.Tensor:
+def encode_text_embeddings(model, x: torch.Tensor, normalize: bool = True, pool_index=None, output_tokens: bool = False):
     """The text tower from token EMBEDDINGS x [B, T, width] (before the positional embedding), with gradients to x: the entry of
     ov-gradient-ascent.py:102-127, which feeds `soft_one_hot @ token_embedding.weight` instead of token ids.  `pool_index` (int64 [B])
     selects the pooled position for text_pool_type 'argmax' (ids are not available here)."""
     x = x.float() + model.positional_embedding.float()[: x.shape[1]]
     x = tower_forward(model.transformer, x)
+    tokens = x[:, :-1]             # output_tokens: the stack's output without its last position, before ln_final (text_transformer.py:676-682)
     x = _LayerNormFn.apply(x, model.ln_final.weight, model.ln_final.bias, model.ln_final.eps)
     pool = getattr(model, "text_pool_type", "last")
     if pool == "last":
@@ -522,10 +561,11 @@ def encode_text_embeddings(model, x: torch.Tensor, normalize: bool = True, pool_
     else:
         raise _lib.OvhipError(f"training path: text pool type {pool!r} is not supported")
     out = _LinearFn.apply(pooled, model.text_projection.t(), None)
-    return F.normalize(out, dim=-1) if normalize else out
+    out = F.normalize(out, dim=-1) if normalize else out
+    return (out, tokens) if output_tokens else out
 
 
-def encode_text(model, text: torch.Tensor, normalize: bool = True) -> torch.Tensor:
+def encode_text(model, text: torch.Tensor, normalize: bool = True, output_tokens: bool = False):
     """CLIP.encode_text (model.py:269-284) with gradients: no mask, ln_final on all tokens, pool per text_pool_type.  `text`: int64
     token ids [B, T], or a float [B, T, vocab] matrix of (soft) one-hot rows (ov-gradient-ascent.py:105: `text @ token_embedding.weight`,
     gradients flow to the rows)."""
@@ -533,9 +573,9 @@ def encode_text(model, text: torch.Tensor, normalize: bool = True) -> torch.Tens
         if text.dim() != 3 or text.shape[-1] != model.token_embedding.weight.shape[0]:
             raise ValueError("soft tokens must be [B, T, vocab_size]")
         return encode_text_embeddings(model, text.float() @ model.token_embedding.weight.float(), normalize,
-                                      text.argmax(dim=-1).argmax(dim=-1))
+                                      text.argmax(dim=-1).argmax(dim=-1), output_tokens)
     x = F.embedding(text, model.token_embedding.weight.float())
-    return encode_text_embeddings(model, x, normalize, text.argmax(dim=-1))
+    return encode_text_embeddings(model, x, normalize, text.argmax(dim=-1), output_tokens)
 
 
 def clip_forward(model, image: torch.Tensor, text: torch.Tensor) -> Tuple[torch.Tensor, ...]:
@@ -548,13 +588,43 @@ def clip_forward(model, image: torch.Tensor, text: torch.Tensor) -> Tuple[torch.
     return out
 
 
+def decode(decoder, image_tokens: torch.Tensor, text_tokens: torch.Tensor) -> torch.Tensor:
+    """``caption.TextDecoder.forward`` with gradients (text_decoder.py:436-576, concat fusion): bias-free projections of both token
+    sets (``_LinearFn``), ``[image | text | learnable]`` through the decoder's blocks under the prefix-LM mask with prefix =
+    L_image + L_text (``tower_forward``), the last T_out positions through ``decoder_norm`` (``_LayerNormFn``) and the bias-free
+    vocabulary head (``_LinearFn``) -> fp32 logits [B, T_out, vocab].  Gradients reach the decoder's parameters and both inputs."""
+    bsz, li, _ = image_tokens.shape
+    lt = text_tokens.shape[1]
+    w = decoder.width
+    xi = _LinearFn.apply(image_tokens.reshape(bsz * li, -1), decoder.image_projection.weight, None).view(bsz, li, w)
+    xt = _LinearFn.apply(text_tokens.reshape(bsz * lt, -1), decoder.text_projection.weight, None).view(bsz, lt, w)
+    lr = decoder.learnable_tokens.float().unsqueeze(0).expand(bsz, -1, -1)
+    x = torch.cat([xi, xt, lr], dim=1)
+    x = tower_forward(decoder.transformer, x, prefix=li + lt)
+    n = decoder.num_learnable_tokens
+    y = _LayerNormFn.apply(x[:, -n:].contiguous(), decoder.decoder_norm.weight, decoder.decoder_norm.bias, decoder.decoder_norm.eps)
+    return _LinearFn.apply(y.reshape(bsz * n, w), decoder.head.weight, None).view(bsz, n, -1)
+
+
+def coca_forward(model, decoder, image: torch.Tensor, text: torch.Tensor):
+    """The reference trainer's 'coca' forward (src/main_clip.py:448-465): both towers once, their features for the contrastive loss
+    and their tokens through the caption decoder -> (image_features, text_features, logit_scale.exp(), caption_logits).
+
+        img_f, txt_f, scale, cap = training.coca_forward(model, decoder, images, tokens)
+        loss = ClipLoss()(img_f, txt_f, scale) + 2 * CaptionLoss()(cap, labels, mask)"""
+    img_f, img_tok = encode_image(model, image, True, output_tokens=True)
+    txt_f, txt_tok = encode_text(model, text, True, output_tokens=True)
+    return img_f, txt_f, model.logit_scale.exp(), decode(decoder, img_tok, txt_tok)
+
+
 # --------------------------------------------------------------------------------------------------------------------------
 # parameter update + data-parallel gradient exchange: what closes the training step (src/main_clip.py:480-483)
 # --------------------------------------------------------------------------------------------------------------------------
 def default_decay_filter(name: str, p: torch.Tensor) -> bool:
     """The reference decays '.*/kernel$' only (build_optax.py:259: Dense / Conv kernels): here the 2-D (and conv) weight matrices;
     biases, LayerNorm parameters, class / positional / token embeddings, the logit scale and the logit bias are not decayed."""
-    if name.endswith("token_embedding.weight") or "positional_embedding" in name or name.endswith("class_embedding"):
+    if (name.endswith("token_embedding.weight") or "positional_embedding" in name or name.endswith("class_embedding")
+            or name.endswith("learnable_tokens")):
         return False
     return p.dim() >= 2
 
@@ -567,14 +637,16 @@ class FusedAdamW:
     Parameters are re-homed into two flat fp32 buffers (decayed / not decayed) and their ``.grad`` into matching flat gradient
     buffers, so the all-reduce works on a few large contiguous buckets (xGMI rings are per-link bound: few, large messages) and the
     update is two launches.  fp32 parameters only.  After ``step()`` the packed bf16 copies of the model are invalidated (the
-    kernel writes parameters without touching ``_version``)."""
+    kernel writes parameters without touching ``_version``).  ``model`` may be a list of modules (CLIP + caption decoder)."""
 
     def __init__(self, model, lr: float, b1: float = 0.9, b2: float = 0.95, eps: float = 1e-8, wd: float = 0.2,
                  clip_norm: float = None, decay_filter=default_decay_filter, bucket_bytes: int = 256 << 20):
         self.model, self.lr, self.b1, self.b2, self.eps, self.wd, self.clip_norm = model, lr, b1, b2, eps, wd, clip_norm
         self.bucket_bytes = int(bucket_bytes)
         self.t = 0
-        named = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
+        # `model`: one module, or a list / tuple of modules (the CLIP model and its caption decoder): names get the module's index
+        mods = list(model) if isinstance(model, (list, tuple)) else [model]
+        named = [((f"{i}." if len(mods) > 1 else "") + n, p) for i, m in enumerate(mods) for n, p in m.named_parameters() if p.requires_grad]
         if not named:
             raise ValueError("no trainable parameters")
         dev = named[0][1].device          # CPU tensors: buffers and the gradient exchange work (gloo tests); step() refuses

@@ -532,8 +532,10 @@ int    ov_tower_backward(const ov_tower* t, const ov_bf16* saved, ov_bf16* dx, c
                          void* workspace, size_t workspace_bytes, ov_stream_t stream);
 
 /* Input gradients only (frozen weights: feature visualisation, gradient ascent on the inputs): ov_tower_backward over the same saved
- * activations without any parameter-gradient work (no dW products, bias or LayerNorm parameter sums).  dx is bitwise the dx of
- * ov_tower_backward. */
+ * activations without any parameter-gradient work (no dW products, bias or LayerNorm parameter sums).  The block backward is one chain
+ * of launches, called with every pair by ov_block_backward / ov_tower_backward, with the requested pairs by ov_tower_backward_partial
+ * and with none here (its attention half alone: ov_block_attn_backward_input), so dx is bitwise the dx of ov_tower_backward.  The
+ * workspace is smaller than ov_tower_backward's: no parameter-gradient staging. */
 size_t ov_tower_backward_input_workspace_bytes(const ov_tower* t, int B, int L);
 int    ov_tower_backward_input(const ov_tower* t, const ov_bf16* saved, ov_bf16* dx, int B, int L, void* workspace, size_t workspace_bytes,
                                ov_stream_t stream);

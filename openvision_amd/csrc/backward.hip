@@ -395,17 +395,20 @@ extern "C" size_t ov_linear_backward_workspace_bytes(int64_t M, int N, int K) {
 }
 
 // dx_epi / dx_r: the epilogue of the dX product and its second operand [M, K] (ov_block_backward: the GELU derivative at the c_fc
-// pre-activation multiplies dy Wproj right there, OV_EPI_GELU_GRAD_*); OV_EPI_BIAS / NULL = plain dX
+// pre-activation multiplies dy Wproj right there, OV_EPI_GELU_GRAD_*); OV_EPI_BIAS / NULL = plain dX.  wt_only (dX alone is asked
+// for): the workspace need only hold the W^T staging area, align256(K N bf16), the first section of the full layout
 static int linear_backward(const ov_bf16* dY, int64_t lddy, const ov_bf16* X, int64_t ldx, const ov_bf16* W, int64_t ldw,
                            int64_t M, int N, int K, ov_bf16* dX, int64_t lddx, ov_bf16* dW, int64_t lddw, float* db,
-                           void* workspace, size_t workspace_bytes, ov_stream_t stream, int dx_epi, const ov_bf16* dx_r, int64_t lddxr) {
+                           void* workspace, size_t workspace_bytes, ov_stream_t stream, int dx_epi, const ov_bf16* dx_r, int64_t lddxr,
+                           bool wt_only = false) {
     if (!dY || !W || !workspace || M <= 0 || N <= 0 || K <= 0) return OV_ERR_INVALID;
     if ((!dX && !dW && !db) || (dW && !X)) return OV_ERR_INVALID;
     if (N % 64 || K % 64 || lddy % 8 || ldw % 8 || lddy < N || ldw < K || (X && (ldx % 8 || ldx < K))) return OV_ERR_UNSUPPORTED;
     if ((dX && (lddx % 8 || lddx < K)) || (dW && (lddw % 8 || lddw < K))) return OV_ERR_UNSUPPORTED;
     if (((uintptr_t)dY | (uintptr_t)X | (uintptr_t)W | (uintptr_t)dX | (uintptr_t)dW | (uintptr_t)db | (uintptr_t)workspace) & 15)
         return OV_ERR_INVALID;
-    if (workspace_bytes < ov_linear_backward_workspace_bytes(M, N, K)) return OV_ERR_WORKSPACE;
+    if (wt_only && (dW || db)) return OV_ERR_INVALID;
+    if (workspace_bytes < (wt_only ? align256((size_t)K * N * 2) : ov_linear_backward_workspace_bytes(M, N, K))) return OV_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     const SplitK sp = plan_splitk(M, N, K);
     const int64_t mp = sp.mp;
@@ -486,7 +489,39 @@ extern "C" int ov_linear_backward(const ov_bf16* dY, int64_t lddy, const ov_bf16
 namespace {
 constexpr int LNB_BLOCKS = 1024;
 inline int64_t lnb_blocks(int64_t rows) { const int64_t b = (rows + 3) / 4; return b < LNB_BLOCKS ? b : LNB_BLOCKS; }
+
+// the rows of the LayerNorm backward: the one place that picks layernorm_bwd_rows' chunk count.  The same grid whatever is computed
+template <bool PARAMS, bool DX>
+int layernorm_bwd_launch(const ov_bf16* x, int64_t ldx, const float* gamma, const ov_bf16* dy, int64_t lddy, const ov_bf16* dres,
+                         int64_t lddres, ov_bf16* dx, int64_t lddx, int64_t rows, int D, float eps, float* part, hipStream_t st) {
+    const dim3 grid((unsigned)lnb_blocks(rows)), blk(256);
+    const int nch = (D / 8 + 63) / 64;
+    if (nch <= 1) hipLaunchKernelGGL((layernorm_bwd_rows<1, PARAMS, DX>), grid, blk, 0, st, x, ldx, gamma, dy, lddy, dres, lddres, dx, lddx, rows, D, eps, part);
+    else if (nch <= 2) hipLaunchKernelGGL((layernorm_bwd_rows<2, PARAMS, DX>), grid, blk, 0, st, x, ldx, gamma, dy, lddy, dres, lddres, dx, lddx, rows, D, eps, part);
+    else if (nch <= 3) hipLaunchKernelGGL((layernorm_bwd_rows<3, PARAMS, DX>), grid, blk, 0, st, x, ldx, gamma, dy, lddy, dres, lddres, dx, lddx, rows, D, eps, part);
+    else if (nch <= 4) hipLaunchKernelGGL((layernorm_bwd_rows<4, PARAMS, DX>), grid, blk, 0, st, x, ldx, gamma, dy, lddy, dres, lddres, dx, lddx, rows, D, eps, part);
+    else hipLaunchKernelGGL((layernorm_bwd_rows<8, PARAMS, DX>), grid, blk, 0, st, x, ldx, gamma, dy, lddy, dres, lddres, dx, lddx, rows, D, eps, part);
+    OV_LAUNCH_CHECK();
+    return OV_OK;
 }
+
+// ov_layernorm_backward after its argument checks.  dgamma == NULL: dx alone (no workspace); dx == NULL: dgamma / dbeta alone (a
+// trainable LayerNorm whose input gradient nobody reads).  What is computed is, bit for bit, what the full form computes for it.
+int layernorm_backward(const ov_bf16* x, int64_t ldx, const float* gamma, const ov_bf16* dy, int64_t lddy, const ov_bf16* dres,
+                       int64_t lddres, ov_bf16* dx, int64_t lddx, float* dgamma, float* dbeta, int64_t rows, int D, float eps,
+                       void* workspace, ov_stream_t stream) {
+    hipStream_t st = (hipStream_t)stream;
+    float* part = (float*)workspace;
+    if (!dgamma) return layernorm_bwd_launch<false, true>(x, ldx, gamma, dy, lddy, dres, lddres, dx, lddx, rows, D, eps, nullptr, st);
+    const int rc = dx ? layernorm_bwd_launch<true, true>(x, ldx, gamma, dy, lddy, dres, lddres, dx, lddx, rows, D, eps, part, st)
+                      : layernorm_bwd_launch<true, false>(x, ldx, gamma, dy, lddy, nullptr, 0, nullptr, 0, rows, D, eps, part, st);
+    if (rc) return rc;
+    // part[w] = [dgamma partial | dbeta partial] of wave w: both column sums from one pair of launches (the same additions in the same order)
+    const int64_t blocks = lnb_blocks(rows);
+    float* scratch = part + (size_t)blocks * 4 * 2 * D;
+    return launch_rows_sum(part, blocks * 4, 2 * D, (int64_t)2 * D, scratch, dgamma, st, dbeta, D);
+}
+}  // namespace
 
 extern "C" size_t ov_layernorm_backward_workspace_bytes(int64_t rows, int D) {
     if (rows <= 0 || D <= 0) return 0;
@@ -501,21 +536,7 @@ extern "C" int ov_layernorm_backward(const ov_bf16* x, int64_t ldx, const float*
     if (dres && (lddres % 8 || lddres < D)) return OV_ERR_UNSUPPORTED;
     if (((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)dy | (uintptr_t)dres | (uintptr_t)dx | (uintptr_t)workspace) & 15) return OV_ERR_INVALID;
     if (workspace_bytes < ov_layernorm_backward_workspace_bytes(rows, D)) return OV_ERR_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    const int64_t blocks = lnb_blocks(rows);
-    const dim3 grid((unsigned)blocks), blk(256);
-    float* part = (float*)workspace;
-    const int nch = (D / 8 + 63) / 64;
-    if (nch <= 1) hipLaunchKernelGGL(layernorm_bwd_rows<1>, grid, blk, 0, st, x, ldx, gamma, dy, lddy, dres, lddres, dx, lddx, rows, D, eps, part);
-    else if (nch <= 2) hipLaunchKernelGGL(layernorm_bwd_rows<2>, grid, blk, 0, st, x, ldx, gamma, dy, lddy, dres, lddres, dx, lddx, rows, D, eps, part);
-    else if (nch <= 3) hipLaunchKernelGGL(layernorm_bwd_rows<3>, grid, blk, 0, st, x, ldx, gamma, dy, lddy, dres, lddres, dx, lddx, rows, D, eps, part);
-    else if (nch <= 4) hipLaunchKernelGGL(layernorm_bwd_rows<4>, grid, blk, 0, st, x, ldx, gamma, dy, lddy, dres, lddres, dx, lddx, rows, D, eps, part);
-    else hipLaunchKernelGGL(layernorm_bwd_rows<8>, grid, blk, 0, st, x, ldx, gamma, dy, lddy, dres, lddres, dx, lddx, rows, D, eps, part);
-    OV_LAUNCH_CHECK();
-    // part[w][0][:] = dgamma partial, part[w][1][:] = dbeta partial of wave w: two strided column sums
-    float* scratch = part + (size_t)blocks * 4 * 2 * D;
-    // part[w] = [dgamma partial | dbeta partial]: both column sums from one pair of launches (the same additions in the same order)
-    return launch_rows_sum(part, blocks * 4, 2 * D, (int64_t)2 * D, scratch, dgamma, st, dbeta, D);
+    return layernorm_backward(x, ldx, gamma, dy, lddy, dres, lddres, dx, lddx, dgamma, dbeta, rows, D, eps, workspace, stream);
 }
 
 extern "C" int ov_gelu_backward(const ov_bf16* a, int64_t lda, const ov_bf16* dh, int64_t lddh, ov_bf16* da, int64_t ldda, ov_bf16* h_out,
@@ -535,28 +556,43 @@ extern "C" int ov_gelu_backward(const ov_bf16* a, int64_t lda, const ov_bf16* dh
 }
 
 // ---- one ResidualAttentionBlock (transformer.py:254-265: x1 = x + attn(ln_1(x)); y = x1 + mlp(ln_2(x1))) ----------------------
-// Activation recomputation: only the block input x is kept by the caller; ln_1, qkv, attention, x1, ln_2 and the c_fc
-// pre-activation are recomputed here with the forward's own kernels, then the chain rule runs back through the operators above.
+// One backward chain, block_backward_chain below, serves every entry point: ov_block_backward[_prefix] (which first recomputes the
+// intermediates the caller did not keep), the towers' block_backward_partial (any subset of the parameter pairs, dx optional),
+// block_backward_input (dx alone) and, with its attention half, ov_block_attn_backward_input.  A quantity that several of them compute
+// therefore comes from the same launches and is bitwise the same.
 namespace {
+// Workspace of the chain.  PLAN_RECOMPUTE: room for the six forward intermediates (ov_block_backward without `saved`; `a` also takes
+// gelu(a) when the activation was not kept); PLAN_PARAMS: the dW / db staging of ov_linear_backward and the LayerNorm partial sums --
+// without it `lin` holds the widest W^T alone, which is all a dX product stages; PLAN_MLP: the MLP half's dh and dx1.
+enum { PLAN_RECOMPUTE = 1, PLAN_PARAMS = 2, PLAN_MLP = 4, PLAN_FULL = 7 };
 struct BlockBufs { ov_bf16 *n1, *qkv, *o, *x1, *n2, *a, *dh, *t1, *dx1, *dqkv; char* lin; char* ln; char* att; size_t lin_bytes, ln_bytes, att_bytes, total; };
-inline BlockBufs plan_block(const ov_tower_cfg* c, int B, int L, char* base) {
+inline BlockBufs plan_block(const ov_tower_cfg* c, int B, int L, int what, char* base) {
     const int64_t M = (int64_t)B * L;
     const int D = c->width, F = c->mlp_pad;
+    const bool re = what & PLAN_RECOMPUTE, mlp = what & PLAN_MLP;
     BlockBufs b;
     size_t off = 0;
-    auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += align256(bytes); return p; };
-    b.n1 = (ov_bf16*)take((size_t)M * D * 2);   b.qkv = (ov_bf16*)take((size_t)M * 3 * D * 2);  b.o = (ov_bf16*)take((size_t)M * D * 2);
-    b.x1 = (ov_bf16*)take((size_t)M * D * 2);   b.n2 = (ov_bf16*)take((size_t)M * D * 2);       b.a = (ov_bf16*)take((size_t)M * F * 2);
-    b.dh = (ov_bf16*)take((size_t)M * F * 2);   b.t1 = (ov_bf16*)take((size_t)M * D * 2);       b.dx1 = (ov_bf16*)take((size_t)M * D * 2);
-    b.dqkv = (ov_bf16*)take((size_t)M * 3 * D * 2);
-    size_t lb = ov_linear_backward_workspace_bytes(M, 3 * D, D);
-    const size_t l2 = ov_linear_backward_workspace_bytes(M, D, D), l3 = ov_linear_backward_workspace_bytes(M, F, D),
-                 l4 = ov_linear_backward_workspace_bytes(M, D, F);
-    lb = lb > l2 ? lb : l2; lb = lb > l3 ? lb : l3; lb = lb > l4 ? lb : l4;
-    b.lin_bytes = lb; b.lin = take(lb);
-    b.ln_bytes = ov_layernorm_backward_workspace_bytes(M, D); b.ln = take(b.ln_bytes);
+    auto take = [&](bool on, size_t bytes) { char* p = base && on ? base + off : nullptr; if (on) off += align256(bytes); return p; };
+    b.n1 = (ov_bf16*)take(re, (size_t)M * D * 2);   b.qkv = (ov_bf16*)take(re, (size_t)M * 3 * D * 2);  b.o = (ov_bf16*)take(re, (size_t)M * D * 2);
+    b.x1 = (ov_bf16*)take(re, (size_t)M * D * 2);   b.n2 = (ov_bf16*)take(re, (size_t)M * D * 2);       b.a = (ov_bf16*)take(re, (size_t)M * F * 2);
+    b.dh = (ov_bf16*)take(mlp, (size_t)M * F * 2);  b.t1 = (ov_bf16*)take(true, (size_t)M * D * 2);     b.dx1 = (ov_bf16*)take(mlp, (size_t)M * D * 2);
+    b.dqkv = (ov_bf16*)take(true, (size_t)M * 3 * D * 2);
+    if (what & PLAN_PARAMS) {
+        size_t lb = ov_linear_backward_workspace_bytes(M, 3 * D, D);
+        const size_t l2 = ov_linear_backward_workspace_bytes(M, D, D), l3 = ov_linear_backward_workspace_bytes(M, F, D),
+                     l4 = ov_linear_backward_workspace_bytes(M, D, F);
+        lb = lb > l2 ? lb : l2; lb = lb > l3 ? lb : l3; lb = lb > l4 ? lb : l4;
+        b.lin_bytes = lb;
+        b.ln_bytes = ov_layernorm_backward_workspace_bytes(M, D);
+    } else {
+        const int64_t wn = mlp && F > 3 * D ? F : 3 * D;          // widest W^T: [D, 3D] (QKV) or [F, D] / [D, F] (c_proj / c_fc)
+        b.lin_bytes = align256((size_t)wn * D * 2);
+        b.ln_bytes = 0;
+    }
+    b.lin = take(true, b.lin_bytes);
+    b.ln = take(b.ln_bytes > 0, b.ln_bytes);
     b.att_bytes = ov_attention_prefix_backward_workspace_bytes(B, L, c->heads, c->width / c->heads);   // >= the unmasked backward's
-    b.att = take(b.att_bytes + 256);
+    b.att = take(true, b.att_bytes + 256);
     b.total = off;
     return b;
 }
@@ -565,21 +601,97 @@ inline bool block_cfg_ok(const ov_tower_cfg* c) {
     const int hd = c->width / c->heads;
     return hd % 8 == 0 && hd <= 96 && c->mlp > 0 && c->mlp <= c->mlp_pad && c->mlp_pad % 64 == 0;
 }
-}  // namespace
-
-extern "C" size_t ov_block_backward_workspace_bytes(const ov_tower_cfg* cfg, int B, int L) {
+inline size_t plan_bytes(const ov_tower_cfg* cfg, int B, int L, int what) {
     if (!block_cfg_ok(cfg) || B <= 0 || L <= 0) return 0;
-    return plan_block(cfg, B, L, nullptr).total;
+    return plan_block(cfg, B, L, what, nullptr).total;
 }
 
-namespace {
 // the attention backward of a block: masked (prefix >= 0; the kept lse is not used) or not
 int attn_bwd(int prefix, const ov_bf16* qkv, int64_t ldq, const ov_bf16* o, int64_t ldo, const ov_bf16* dout, int64_t lddo, ov_bf16* dqkv,
              int64_t lddq, const float* lse, int B, int L, int H, int hd, float scale, void* ws, size_t ws_bytes, ov_stream_t stream) {
     if (prefix >= 0) return ov_attention_prefix_backward(qkv, ldq, o, ldo, dout, lddo, dqkv, lddq, B, L, H, hd, scale, prefix, ws, ws_bytes, stream);
     return ov_attention_backward_saved(qkv, ldq, o, ldo, dout, lddo, dqkv, lddq, lse, B, L, H, hd, scale, ws, ws_bytes, stream);
 }
+
+// ov_linear_backward of a dense layer (every pitch = its matrix's width) in the chain's staging area; a dX-only call stages W^T alone
+int chain_linear(const BlockBufs& b, int64_t M, ov_stream_t stream, const ov_bf16* dY, const ov_bf16* X, const ov_bf16* W, int N, int K,
+                 ov_bf16* dX, ov_bf16* dW, float* db, int dx_epi = OV_EPI_BIAS, const ov_bf16* dx_r = nullptr) {
+    return linear_backward(dY, N, X, K, W, K, M, N, K, dX, K, dW, K, db, b.lin, b.lin_bytes, stream, dx_epi, dx_r, K, !dW && !db);
+}
+
+#define OV_TRY(call) do { if ((rc = (call)) != OV_OK) return rc; } while (0)
+// The six (weight, bias) pairs of ov_block_grads as bits of `pairs`, bit k = pair k in declaration order (ln_1, in_proj, out_proj,
+// ln_2, c_fc, c_proj).  Both halves launch nothing that no requested output needs.
+// MLP half, y = x1 + c_proj(gelu(a)): the pairs ln_2, c_fc, c_proj of `g` and, when need_dx1, b.dx1 = d x1 (dy included).
+// s.fc_act == NULL (the activation was not kept): dh = dy Wproj, then one element-wise pass turns it into da and leaves gelu(a) in b.a
+// for the c_proj dW; otherwise the GELU derivative at s.fc_pre rides on the epilogue of dy Wproj.
+int chain_mlp(const ov_tower_cfg* cfg, const ov_block_weights* w, const ov_block_saved& s, const ov_bf16* dy, const ov_block_grads* g,
+              int pairs, bool need_dx1, const BlockBufs& b, int64_t M, ov_stream_t stream) {
+    const bool p_ln2 = pairs & 8, p_fc = pairs & 16, p_proj = pairs & 32;
+    const bool need_dln2 = p_ln2 || need_dx1;             // d ln_2 out (c_fc dX)
+    const bool need_dh = p_fc || need_dln2;               // d c_fc pre-activation (c_proj dX with the GELU derivative)
+    const int D = cfg->width, F = cfg->mlp_pad;
+    const ov_bf16* act = s.fc_act;
+    int rc;
+    if (act && need_dh) {
+        OV_TRY(chain_linear(b, M, stream, dy, nullptr, w->proj_w, D, F, b.dh, nullptr, nullptr,
+                            cfg->gelu_tanh ? OV_EPI_GELU_GRAD_TANH : OV_EPI_GELU_GRAD_ERF, s.fc_pre));
+    } else if (!act && (need_dh || p_proj)) {
+        OV_TRY(chain_linear(b, M, stream, dy, nullptr, w->proj_w, D, F, b.dh, nullptr, nullptr));                       // dh = dy Wproj
+        OV_TRY(ov_gelu_backward(s.fc_pre, F, b.dh, F, b.dh, F, b.a, F, M, F, cfg->gelu_tanh, stream));                  // dh -> da (in place), b.a = gelu(a)
+        act = b.a;
+    }
+    if (p_proj) OV_TRY(chain_linear(b, M, stream, dy, act, w->proj_w, D, F, nullptr, g->proj_w, g->proj_b));
+    if (p_fc || need_dln2)                                                                                              // t1 = d ln_2 out
+        OV_TRY(chain_linear(b, M, stream, b.dh, s.ln2_out, w->fc_w, F, D, need_dln2 ? b.t1 : nullptr, p_fc ? g->fc_w : nullptr,
+                            p_fc ? g->fc_b : nullptr));
+    if (p_ln2 && need_dx1)                                                                                              // dx1 = dy + ...
+        OV_TRY(ov_layernorm_backward(s.x1, D, w->ln2_w, b.t1, D, dy, D, b.dx1, D, g->ln2_w, g->ln2_b, M, D, cfg->ln_eps, b.ln, b.ln_bytes, stream));
+    else if (p_ln2 || need_dx1)
+        OV_TRY(layernorm_backward(s.x1, D, w->ln2_w, b.t1, D, dy, D, need_dx1 ? b.dx1 : nullptr, D, p_ln2 ? g->ln2_w : nullptr,
+                                  p_ln2 ? g->ln2_b : nullptr, M, D, cfg->ln_eps, b.ln, stream));
+    return OV_OK;
+}
+
+// Attention half, x1 = x + out_proj(attn(qkv)): the pairs ln_1, in_proj, out_proj of `g` and, when dx != NULL, dx = dx1 + the branch's
+// input gradient (dx may alias dx1).  Reads s.ln1_out only for the in_proj dW.
+int chain_attn(const ov_tower_cfg* cfg, const ov_block_weights* w, const ov_bf16* x, const ov_block_saved& s, const ov_bf16* dx1, ov_bf16* dx,
+               const ov_block_grads* g, int pairs, int prefix, const BlockBufs& b, int B, int L, ov_stream_t stream) {
+    const bool p_ln1 = pairs & 1, p_qkv = pairs & 2, p_out = pairs & 4;
+    const bool need_dln1 = p_ln1 || dx;                   // d ln_1 out (QKV dX)
+    const bool need_dqkv = p_qkv || need_dln1;            // attention backward (reads d attention out: out_proj dX)
+    const int D = cfg->width, H = cfg->heads, hd = D / H;
+    const int64_t M = (int64_t)B * L;
+    int rc;
+    if (p_out || need_dqkv)                                                                                             // t1 = d attention out
+        OV_TRY(chain_linear(b, M, stream, dx1, s.attn_out, w->out_w, D, D, need_dqkv ? b.t1 : nullptr, p_out ? g->out_w : nullptr,
+                            p_out ? g->out_b : nullptr));
+    if (need_dqkv)
+        OV_TRY(attn_bwd(prefix, s.qkv, 3 * D, s.attn_out, D, b.t1, D, b.dqkv, 3 * D, s.attn_lse, B, L, H, hd, 1.0f / sqrtf((float)hd), b.att,
+                        b.att_bytes, stream));
+    if (p_qkv || need_dln1)                                                                                             // t1 = d ln_1 out
+        OV_TRY(chain_linear(b, M, stream, b.dqkv, s.ln1_out, w->qkv_w, 3 * D, D, need_dln1 ? b.t1 : nullptr, p_qkv ? g->qkv_w : nullptr,
+                            p_qkv ? g->qkv_b : nullptr));
+    if (p_ln1 && dx)
+        OV_TRY(ov_layernorm_backward(x, D, w->ln1_w, b.t1, D, dx1, D, dx, D, g->ln1_w, g->ln1_b, M, D, cfg->ln_eps, b.ln, b.ln_bytes, stream));
+    else if (p_ln1 || dx)
+        OV_TRY(layernorm_backward(x, D, w->ln1_w, b.t1, D, dx1, D, dx, D, p_ln1 ? g->ln1_w : nullptr, p_ln1 ? g->ln1_b : nullptr, M, D,
+                                  cfg->ln_eps, b.ln, stream));
+    return OV_OK;
+}
+#undef OV_TRY
+
+// c_proj dX(+GELU') -> c_proj dW -> c_fc dX/dW -> LN_2 backward -> out_proj dX/dW -> attention backward -> QKV dX/dW -> LN_1 backward
+// over the block's intermediates `s` (every field set but fc_act and attn_lse, which may be NULL), for the requested pairs of `g` and,
+// when dx != NULL, the block input's gradient (dx may alias dy).  d x1 is needed by everything in the attention half.
+int block_backward_chain(const ov_tower_cfg* cfg, const ov_block_weights* w, const ov_bf16* x, const ov_block_saved& s, const ov_bf16* dy,
+                         ov_bf16* dx, const ov_block_grads* g, int pairs, int prefix, const BlockBufs& b, int B, int L, ov_stream_t stream) {
+    const int rc = chain_mlp(cfg, w, s, dy, g, pairs, (pairs & 7) || dx, b, (int64_t)B * L, stream);
+    return rc ? rc : chain_attn(cfg, w, x, s, b.dx1, dx, g, pairs, prefix, b, B, L, stream);
+}
 }  // namespace
+
+extern "C" size_t ov_block_backward_workspace_bytes(const ov_tower_cfg* cfg, int B, int L) { return plan_bytes(cfg, B, L, PLAN_FULL); }
 
 extern "C" int ov_block_backward(const ov_tower_cfg* cfg, const ov_block_weights* w, const ov_bf16* x, const ov_block_saved* saved,
                                  const ov_bf16* dy, ov_bf16* dx, const ov_block_grads* g, int B, int L, void* workspace,
@@ -587,6 +699,9 @@ extern "C" int ov_block_backward(const ov_tower_cfg* cfg, const ov_block_weights
     return ov_block_backward_prefix(cfg, w, x, saved, dy, dx, g, -1, B, L, workspace, workspace_bytes, stream);
 }
 
+// Activation recomputation: what `saved` lacks (ln_1, qkv, attention, x1, ln_2, the c_fc pre-activation) is recomputed here with the
+// forward's own kernels, then the chain runs with all six pairs.  gelu(a) is never recomputed by a forward kernel: without a kept
+// fc_act (and fc_pre) the chain takes its element-wise route, an arithmetic path of its own beside the fused epilogue.
 extern "C" int ov_block_backward_prefix(const ov_tower_cfg* cfg, const ov_block_weights* w, const ov_bf16* x, const ov_block_saved* saved,
                                         const ov_bf16* dy, ov_bf16* dx, const ov_block_grads* g, int prefix, int B, int L, void* workspace,
                                         size_t workspace_bytes, ov_stream_t stream) {
@@ -605,143 +720,35 @@ extern "C" int ov_block_backward_prefix(const ov_tower_cfg* cfg, const ov_block_
     const int64_t M = (int64_t)B * L;
     if (workspace_bytes < ov_block_backward_workspace_bytes(cfg, B, L)) return OV_ERR_WORKSPACE;
     if (((uintptr_t)workspace | (uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx) & 15) return OV_ERR_INVALID;
-    BlockBufs b = plan_block(cfg, B, L, (char*)workspace);
+    const BlockBufs b = plan_block(cfg, B, L, PLAN_FULL, (char*)workspace);
     const int hd = D / H;
     const float eps = cfg->ln_eps, scale = 1.0f / sqrtf((float)hd);
+    ov_block_saved s = {b.qkv, b.o, b.x1, b.a, b.n1, b.n2, nullptr, saved ? saved->attn_lse : nullptr};
     int rc;
 #define OV_TRY(call) do { if ((rc = (call)) != OV_OK) return rc; } while (0)
-    // ---- the forward's intermediates: kept by ov_tower_forward_saving or recomputed here
-    if (saved && saved->ln1_out) b.n1 = const_cast<ov_bf16*>(saved->ln1_out);
+    if (saved && saved->ln1_out) s.ln1_out = saved->ln1_out;
     else OV_TRY(ov_layernorm(x, OV_BF16, D, w->ln1_w, w->ln1_b, b.n1, OV_BF16, D, M, D, eps, stream));
     if (saved) {
-        b.qkv = const_cast<ov_bf16*>(saved->qkv); b.o = const_cast<ov_bf16*>(saved->attn_out); b.x1 = const_cast<ov_bf16*>(saved->x1);
+        s.qkv = saved->qkv; s.attn_out = saved->attn_out; s.x1 = saved->x1;
     } else {
-        OV_TRY(ov_gemm(b.n1, D, w->qkv_w, D, w->qkv_b, b.qkv, 3 * D, M, 3 * D, D, OV_EPI_BIAS, nullptr, 0, 0, 0, 0, stream));
+        OV_TRY(ov_gemm(s.ln1_out, D, w->qkv_w, D, w->qkv_b, b.qkv, 3 * D, M, 3 * D, D, OV_EPI_BIAS, nullptr, 0, 0, 0, 0, stream));
         if (prefix >= 0) OV_TRY(ov_attention_prefix(b.qkv, 3 * D, b.o, D, B, L, H, hd, scale, prefix, stream));
         else OV_TRY(ov_attention(b.qkv, 3 * D, b.o, D, B, L, H, hd, scale, stream));
         OV_TRY(ov_gemm(b.o, D, w->out_w, D, w->out_b, b.x1, D, M, D, D, OV_EPI_BIAS_RESIDUAL, x, D, 0, 0, 0, stream));
     }
-    if (saved && saved->ln2_out) b.n2 = const_cast<ov_bf16*>(saved->ln2_out);
-    else OV_TRY(ov_layernorm(b.x1, OV_BF16, D, w->ln2_w, w->ln2_b, b.n2, OV_BF16, D, M, D, eps, stream));
-    const ov_bf16* pre = (saved && saved->fc_pre) ? saved->fc_pre : b.a;
-    if (pre == b.a) OV_TRY(ov_gemm(b.n2, D, w->fc_w, D, w->fc_b, b.a, F, M, F, D, OV_EPI_BIAS, nullptr, 0, 0, 0, 0, stream));
-    // ---- MLP branch: y = x1 + c_proj(gelu(a))
-    const ov_bf16* act = b.a;
-    if (saved && saved->fc_act && saved->fc_pre) {      // da = (dy Wproj) * gelu'(a) in the product's own epilogue; gelu(a) was kept
-        OV_TRY(linear_backward(dy, D, nullptr, 0, w->proj_w, F, M, D, F, b.dh, F, nullptr, 0, nullptr, b.lin, b.lin_bytes, stream,
-                               cfg->gelu_tanh ? OV_EPI_GELU_GRAD_TANH : OV_EPI_GELU_GRAD_ERF, pre, F));
-        act = saved->fc_act;
-    } else {
-        OV_TRY(ov_linear_backward(dy, D, nullptr, 0, w->proj_w, F, M, D, F, b.dh, F, nullptr, 0, nullptr, b.lin, b.lin_bytes, stream));  // dh = dy Wproj
-        OV_TRY(ov_gelu_backward(pre, F, b.dh, F, b.dh, F, b.a, F, M, F, cfg->gelu_tanh, stream));                                      // dh -> da (in place), b.a = gelu(a)
-    }
-    OV_TRY(ov_linear_backward(dy, D, act, F, w->proj_w, F, M, D, F, nullptr, 0, g->proj_w, F, g->proj_b, b.lin, b.lin_bytes, stream));
-    OV_TRY(ov_linear_backward(b.dh, F, b.n2, D, w->fc_w, D, M, F, D, b.t1, D, g->fc_w, D, g->fc_b, b.lin, b.lin_bytes, stream));        // t1 = d ln_2 out
-    OV_TRY(ov_layernorm_backward(b.x1, D, w->ln2_w, b.t1, D, dy, D, b.dx1, D, g->ln2_w, g->ln2_b, M, D, eps, b.ln, b.ln_bytes, stream)); // dx1 = dy + ...
-    // ---- attention branch: x1 = x + out_proj(attn(qkv))
-    OV_TRY(ov_linear_backward(b.dx1, D, b.o, D, w->out_w, D, M, D, D, b.t1, D, g->out_w, D, g->out_b, b.lin, b.lin_bytes, stream));     // t1 = d attention out
-    OV_TRY(attn_bwd(prefix, b.qkv, 3 * D, b.o, D, b.t1, D, b.dqkv, 3 * D, saved ? saved->attn_lse : nullptr, B, L, H, hd, scale, b.att,
-                    b.att_bytes, stream));
-    OV_TRY(ov_linear_backward(b.dqkv, 3 * D, b.n1, D, w->qkv_w, D, M, 3 * D, D, b.t1, D, g->qkv_w, D, g->qkv_b, b.lin, b.lin_bytes, stream));  // t1 = d ln_1 out
-    OV_TRY(ov_layernorm_backward(x, D, w->ln1_w, b.t1, D, b.dx1, D, dx, D, g->ln1_w, g->ln1_b, M, D, eps, b.ln, b.ln_bytes, stream));
+    if (saved && saved->ln2_out) s.ln2_out = saved->ln2_out;
+    else OV_TRY(ov_layernorm(s.x1, OV_BF16, D, w->ln2_w, w->ln2_b, b.n2, OV_BF16, D, M, D, eps, stream));
+    if (saved && saved->fc_pre) s.fc_pre = saved->fc_pre;
+    else OV_TRY(ov_gemm(s.ln2_out, D, w->fc_w, D, w->fc_b, b.a, F, M, F, D, OV_EPI_BIAS, nullptr, 0, 0, 0, 0, stream));
+    if (saved && saved->fc_pre) s.fc_act = saved->fc_act;                     // the fused GELU derivative needs both
 #undef OV_TRY
-    return OV_OK;
+    return block_backward_chain(cfg, w, x, s, dy, dx, g, 63, prefix, b, B, L, stream);
 }
 
 // ---- input-only backward (frozen weights: feature visualisation, gradient ascent on the inputs) -----------------------------------
-// The dX chain of ov_block_backward and nothing else: no weight-gradient products, bias sums or LayerNorm parameter sums.  Every step
-// is the launch ov_block_backward makes for the same quantity (the same transposes, GEMMs, epilogues and LayerNorm-backward rows), so
-// dx comes out bitwise the same.
-namespace {
-// dX[M, K] = epi(dY[M, N] . W[N, K]): linear_backward's dX route (W^T staged in Wt [K, N], then ov_gemm contracting over N)
-int linear_dx(const ov_bf16* dY, int64_t lddy, const ov_bf16* W, int64_t ldw, int64_t M, int N, int K, ov_bf16* dX, int64_t lddx,
-              ov_bf16* Wt, ov_stream_t stream, int epi = OV_EPI_BIAS, const ov_bf16* R = nullptr, int64_t ldr = 0) {
-    int rc;
-    if ((rc = launch_transpose(W, ldw, N, N, K, Wt, N, (hipStream_t)stream)) != OV_OK) return rc;
-    return ov_gemm(dY, lddy, Wt, N, nullptr, dX, lddx, M, K, N, epi, R, ldr, 0, 0, 0, stream);
-}
-
-// dx = LN-backward(x, gamma, dy) (+ dres): ov_layernorm_backward's rows without the parameter sums
-int layernorm_dx(const ov_bf16* x, int64_t ldx, const float* gamma, const ov_bf16* dy, int64_t lddy, const ov_bf16* dres, int64_t lddres,
-                 ov_bf16* dx, int64_t lddx, int64_t rows, int D, float eps, ov_stream_t stream) {
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((unsigned)lnb_blocks(rows)), blk(256);
-    const int nch = (D / 8 + 63) / 64;
-    float* np = nullptr;
-    if (nch <= 1) hipLaunchKernelGGL((layernorm_bwd_rows<1, false>), grid, blk, 0, st, x, ldx, gamma, dy, lddy, dres, lddres, dx, lddx, rows, D, eps, np);
-    else if (nch <= 2) hipLaunchKernelGGL((layernorm_bwd_rows<2, false>), grid, blk, 0, st, x, ldx, gamma, dy, lddy, dres, lddres, dx, lddx, rows, D, eps, np);
-    else if (nch <= 3) hipLaunchKernelGGL((layernorm_bwd_rows<3, false>), grid, blk, 0, st, x, ldx, gamma, dy, lddy, dres, lddres, dx, lddx, rows, D, eps, np);
-    else if (nch <= 4) hipLaunchKernelGGL((layernorm_bwd_rows<4, false>), grid, blk, 0, st, x, ldx, gamma, dy, lddy, dres, lddres, dx, lddx, rows, D, eps, np);
-    else hipLaunchKernelGGL((layernorm_bwd_rows<8, false>), grid, blk, 0, st, x, ldx, gamma, dy, lddy, dres, lddres, dx, lddx, rows, D, eps, np);
-    OV_LAUNCH_CHECK();
-    return OV_OK;
-}
-
-// dgamma / dbeta alone (a trainable LayerNorm whose input gradient is not wanted): ov_layernorm_backward's rows without dx, then the
-// same column sums -- bitwise its dgamma / dbeta.  `workspace`: ov_layernorm_backward_workspace_bytes(rows, D).
-int layernorm_params(const ov_bf16* x, int64_t ldx, const float* gamma, const ov_bf16* dy, int64_t lddy, float* dgamma, float* dbeta,
-                     int64_t rows, int D, float eps, void* workspace, ov_stream_t stream) {
-    hipStream_t st = (hipStream_t)stream;
-    const int64_t blocks = lnb_blocks(rows);
-    const dim3 grid((unsigned)blocks), blk(256);
-    float* part = (float*)workspace;
-    const int nch = (D / 8 + 63) / 64;
-    const ov_bf16* nr = nullptr;
-    ov_bf16* nx = nullptr;
-    if (nch <= 1) hipLaunchKernelGGL((layernorm_bwd_rows<1, true, false>), grid, blk, 0, st, x, ldx, gamma, dy, lddy, nr, 0, nx, 0, rows, D, eps, part);
-    else if (nch <= 2) hipLaunchKernelGGL((layernorm_bwd_rows<2, true, false>), grid, blk, 0, st, x, ldx, gamma, dy, lddy, nr, 0, nx, 0, rows, D, eps, part);
-    else if (nch <= 3) hipLaunchKernelGGL((layernorm_bwd_rows<3, true, false>), grid, blk, 0, st, x, ldx, gamma, dy, lddy, nr, 0, nx, 0, rows, D, eps, part);
-    else if (nch <= 4) hipLaunchKernelGGL((layernorm_bwd_rows<4, true, false>), grid, blk, 0, st, x, ldx, gamma, dy, lddy, nr, 0, nx, 0, rows, D, eps, part);
-    else hipLaunchKernelGGL((layernorm_bwd_rows<8, true, false>), grid, blk, 0, st, x, ldx, gamma, dy, lddy, nr, 0, nx, 0, rows, D, eps, part);
-    OV_LAUNCH_CHECK();
-    float* scratch = part + (size_t)blocks * 4 * 2 * D;
-    return launch_rows_sum(part, blocks * 4, 2 * D, (int64_t)2 * D, scratch, dgamma, st, dbeta, D);
-}
-
-struct InputBufs { ov_bf16 *wt, *dh, *t1, *dx1, *dqkv; char* att; size_t att_bytes, total; };
-// mlp = false: the attention half only (no dh, no dx1)
-inline InputBufs plan_input(const ov_tower_cfg* c, int B, int L, bool mlp, char* base) {
-    const int64_t M = (int64_t)B * L;
-    const int D = c->width, F = c->mlp_pad;
-    InputBufs b;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += align256(bytes); return p; };
-    const int64_t wn = mlp && F > 3 * D ? F : 3 * D;              // widest W^T: [D, 3D] (QKV) or [F, D] / [D, F] (c_proj / c_fc)
-    b.wt = (ov_bf16*)take((size_t)wn * D * 2);
-    b.dh = mlp ? (ov_bf16*)take((size_t)M * F * 2) : nullptr;
-    b.dx1 = mlp ? (ov_bf16*)take((size_t)M * D * 2) : nullptr;
-    b.t1 = (ov_bf16*)take((size_t)M * D * 2);
-    b.dqkv = (ov_bf16*)take((size_t)M * 3 * D * 2);
-    b.att_bytes = ov_attention_prefix_backward_workspace_bytes(B, L, c->heads, c->width / c->heads);   // >= the unmasked backward's
-    b.att = take(b.att_bytes + 256);
-    b.total = off;
-    return b;
-}
-
-inline const float* lse_if_used(const ov_tower_cfg* c, int L, const float* lse) {   // ov_tower_forward_saving's rule
-    return ov_attn_bwd_resident(c->width / c->heads, L) ? lse : nullptr;
-}
-
-// the attention half: dx = dx1 + d(x + out_proj(attn(ln_1(x))))/dx . dx1
-int attn_backward_input(const ov_tower_cfg* cfg, const ov_block_weights* w, const ov_bf16* x, const ov_bf16* qkv, const ov_bf16* attn_out,
-                        const float* lse, const ov_bf16* dx1, ov_bf16* dx, int prefix, int B, int L, const InputBufs& b, ov_stream_t stream) {
-    const int D = cfg->width, H = cfg->heads, hd = D / H;
-    const int64_t M = (int64_t)B * L;
-    const float scale = 1.0f / sqrtf((float)hd);
-    int rc;
-    if ((rc = linear_dx(dx1, D, w->out_w, D, M, D, D, b.t1, D, b.wt, stream))) return rc;                                   // t1 = d attention out
-    if ((rc = attn_bwd(prefix, qkv, 3 * D, attn_out, D, b.t1, D, b.dqkv, 3 * D, lse_if_used(cfg, L, lse), B, L, H, hd, scale, b.att, b.att_bytes,
-                       stream)))
-        return rc;
-    if ((rc = linear_dx(b.dqkv, 3 * D, w->qkv_w, D, M, 3 * D, D, b.t1, D, b.wt, stream))) return rc;                        // t1 = d ln_1 out
-    return layernorm_dx(x, D, w->ln1_w, b.t1, D, dx1, D, dx, D, M, D, cfg->ln_eps, stream);
-}
-}  // namespace
-
-extern "C" size_t ov_block_attn_backward_input_workspace_bytes(const ov_tower_cfg* cfg, int B, int L) {
-    if (!block_cfg_ok(cfg) || B <= 0 || L <= 0) return 0;
-    return plan_input(cfg, B, L, false, nullptr).total;
-}
+// The chain with no pair requested: no weight-gradient products, bias sums or LayerNorm parameter sums, and a workspace without their
+// staging (PLAN_PARAMS off).  ov_block_attn_backward_input is the attention half of that: dx = dx1 + d(x + out_proj(attn(ln_1(x))))/dx . dx1
+extern "C" size_t ov_block_attn_backward_input_workspace_bytes(const ov_tower_cfg* cfg, int B, int L) { return plan_bytes(cfg, B, L, 0); }
 
 extern "C" int ov_block_attn_backward_input(const ov_tower_cfg* cfg, const ov_block_weights* w, const ov_bf16* x, const ov_bf16* qkv,
                                             const ov_bf16* attn_out, const float* lse, const ov_bf16* dx1, ov_bf16* dx, int B, int L,
@@ -753,35 +760,22 @@ extern "C" int ov_block_attn_backward_input(const ov_tower_cfg* cfg, const ov_bl
     if (workspace_bytes < ov_block_attn_backward_input_workspace_bytes(cfg, B, L)) return OV_ERR_WORKSPACE;
     if (((uintptr_t)workspace | (uintptr_t)x | (uintptr_t)qkv | (uintptr_t)attn_out | (uintptr_t)dx1 | (uintptr_t)dx | (uintptr_t)lse) & 15)
         return OV_ERR_INVALID;
-    const InputBufs b = plan_input(cfg, B, L, false, (char*)workspace);
-    return attn_backward_input(cfg, w, x, qkv, attn_out, lse, dx1, dx, -1, B, L, b, stream);
+    ov_block_saved s = {};
+    s.qkv = qkv; s.attn_out = attn_out;
+    s.attn_lse = ov_attn_bwd_resident(cfg->width / cfg->heads, L) ? lse : nullptr;      // ov_tower_forward_saving's rule
+    return chain_attn(cfg, w, x, s, dx1, dx, nullptr, 0, -1, plan_block(cfg, B, L, 0, (char*)workspace), B, L, stream);
 }
 
-// One block's input gradient from the activations ov_tower_forward_saving kept (qkv, attention out, x1, c_fc pre-activation, lse):
-// ov_tower_backward_input (tower.hip) runs it over the layers in reverse.  Arguments are checked there.
-size_t block_backward_input_workspace_bytes(const ov_tower_cfg* cfg, int B, int L) {
-    if (!block_cfg_ok(cfg) || B <= 0 || L <= 0) return 0;
-    return plan_input(cfg, B, L, true, nullptr).total;
-}
+// ---- the towers' block backward (tower.hip walks it over the layers in reverse; arguments are checked there) ----------------------
+// Every field of `s` is set (ov_tower_forward_saving's slot).  block_backward_input: dx alone, in the smaller input-only workspace.
+size_t block_backward_input_workspace_bytes(const ov_tower_cfg* cfg, int B, int L) { return plan_bytes(cfg, B, L, PLAN_MLP); }
 int block_backward_input(const ov_tower_cfg* cfg, const ov_block_weights* w, const ov_bf16* x, const ov_block_saved* s, const ov_bf16* dy,
                          ov_bf16* dx, int prefix, int B, int L, void* workspace, ov_stream_t stream) {
-    const int D = cfg->width, F = cfg->mlp_pad;
-    const int64_t M = (int64_t)B * L;
-    const InputBufs b = plan_input(cfg, B, L, true, (char*)workspace);
-    int rc;
-    // MLP branch: dh = (dy Wproj) * gelu'(a) in the product's epilogue, d ln_2 out = dh Wfc, dx1 = dy + LN_2-backward
-    if ((rc = linear_dx(dy, D, w->proj_w, F, M, D, F, b.dh, F, b.wt, stream, cfg->gelu_tanh ? OV_EPI_GELU_GRAD_TANH : OV_EPI_GELU_GRAD_ERF,
-                        s->fc_pre, F)))
-        return rc;
-    if ((rc = linear_dx(b.dh, F, w->fc_w, D, M, F, D, b.t1, D, b.wt, stream))) return rc;
-    if ((rc = layernorm_dx(s->x1, D, w->ln2_w, b.t1, D, dy, D, b.dx1, D, M, D, cfg->ln_eps, stream))) return rc;
-    return attn_backward_input(cfg, w, x, s->qkv, s->attn_out, s->attn_lse, b.dx1, dx, prefix, B, L, b, stream);
+    return block_backward_chain(cfg, w, x, *s, dy, dx, nullptr, 0, prefix, plan_block(cfg, B, L, PLAN_MLP, (char*)workspace), B, L, stream);
 }
 
-// ---- partial backward (frozen parameters: LiT, a frozen text tower) ----------------------------------------------------------------
-// The six (weight, bias) pairs of ov_block_grads, bit k = pair k in declaration order (ln_1, in_proj, out_proj, ln_2, c_fc, c_proj):
-// the requested ones, 0 for g == NULL, -1 when a pair has exactly one NULL pointer or a pointer is not 16-byte aligned (the dW / db
-// products require it; checked here so that the tower rejects it before its first launch).
+// The requested pairs of `g`: 0 for g == NULL, -1 when a pair has exactly one NULL pointer or a pointer is not 16-byte aligned (the
+// dW / db products require it; checked here so that the tower rejects it before its first launch).
 int block_grad_pairs(const ov_block_grads* g) {
     if (!g) return 0;
     const void* p[12] = {g->ln1_w, g->ln1_b, g->qkv_w, g->qkv_b, g->out_w, g->out_b, g->ln2_w, g->ln2_b, g->fc_w, g->fc_b, g->proj_w, g->proj_b};
@@ -794,60 +788,14 @@ int block_grad_pairs(const ov_block_grads* g) {
     return m;
 }
 
-// One block's backward over the activations ov_tower_forward_saving kept (every field of `s` set; the tower checks the arguments),
-// computing only the requested pairs of `g` and, when dx != NULL, the block input's gradient (dx may alias dy).  Nothing is launched
-// that no requested output needs, and each launch that is made is the one ov_block_backward makes for that quantity (a dX-only,
-// dW-only or combined linear_backward; the full, dx-only or parameter-only LayerNorm rows), so what comes out is bitwise its result.
-// Workspace: ov_block_backward_workspace_bytes.
+// block_backward_partial (frozen parameters: LiT, a frozen text tower): the requested pairs of `g` and, when dx != NULL, the block
+// input's gradient (dx may alias dy).  Workspace: ov_block_backward_workspace_bytes.
 int block_backward_partial(const ov_tower_cfg* cfg, const ov_block_weights* w, const ov_bf16* x, const ov_block_saved* s,
                            const ov_bf16* dy, ov_bf16* dx, const ov_block_grads* g, int prefix, int B, int L, void* workspace,
                            size_t workspace_bytes, ov_stream_t stream) {
     const int pairs = block_grad_pairs(g);
     if (pairs < 0) return OV_ERR_INVALID;
-    const bool p_ln1 = pairs & 1, p_qkv = pairs & 2, p_out = pairs & 4, p_ln2 = pairs & 8, p_fc = pairs & 16, p_proj = pairs & 32;
-    // what each intermediate gradient is needed for, from the bottom of the block up
-    const bool need_dln1 = p_ln1 || dx;                   // d ln_1 out (QKV dX)
-    const bool need_dqkv = p_qkv || need_dln1;            // attention backward (reads d attention out: out_proj dX)
-    const bool need_dx1 = p_out || need_dqkv;             // LN_2 backward's dx (plus dy) = d x1
-    const bool need_dln2 = p_ln2 || need_dx1;             // d ln_2 out (c_fc dX)
-    const bool need_dh = p_fc || need_dln2;               // d c_fc pre-activation (c_proj dX with the GELU derivative)
-    const int D = cfg->width, F = cfg->mlp_pad, H = cfg->heads, hd = D / H;
-    const int64_t M = (int64_t)B * L;
-    const float eps = cfg->ln_eps, scale = 1.0f / sqrtf((float)hd);
-    BlockBufs b = plan_block(cfg, B, L, (char*)workspace);
+    const BlockBufs b = plan_block(cfg, B, L, PLAN_FULL, (char*)workspace);
     if (workspace_bytes < b.total) return OV_ERR_WORKSPACE;
-    int rc;
-#define OV_TRY(call) do { if ((rc = (call)) != OV_OK) return rc; } while (0)
-    // ---- MLP branch: y = x1 + c_proj(gelu(a))
-    if (need_dh)
-        OV_TRY(linear_backward(dy, D, nullptr, 0, w->proj_w, F, M, D, F, b.dh, F, nullptr, 0, nullptr, b.lin, b.lin_bytes, stream,
-                               cfg->gelu_tanh ? OV_EPI_GELU_GRAD_TANH : OV_EPI_GELU_GRAD_ERF, s->fc_pre, F));
-    if (p_proj)
-        OV_TRY(ov_linear_backward(dy, D, s->fc_act, F, w->proj_w, F, M, D, F, nullptr, 0, g->proj_w, F, g->proj_b, b.lin, b.lin_bytes, stream));
-    if (p_fc || need_dln2)
-        OV_TRY(ov_linear_backward(b.dh, F, s->ln2_out, D, w->fc_w, D, M, F, D, need_dln2 ? b.t1 : nullptr, D, p_fc ? g->fc_w : nullptr, D,
-                                  p_fc ? g->fc_b : nullptr, b.lin, b.lin_bytes, stream));
-    if (p_ln2 && need_dx1)
-        OV_TRY(ov_layernorm_backward(s->x1, D, w->ln2_w, b.t1, D, dy, D, b.dx1, D, g->ln2_w, g->ln2_b, M, D, eps, b.ln, b.ln_bytes, stream));
-    else if (need_dx1)
-        OV_TRY(layernorm_dx(s->x1, D, w->ln2_w, b.t1, D, dy, D, b.dx1, D, M, D, eps, stream));
-    else if (p_ln2)
-        OV_TRY(layernorm_params(s->x1, D, w->ln2_w, b.t1, D, g->ln2_w, g->ln2_b, M, D, eps, b.ln, stream));
-    // ---- attention branch: x1 = x + out_proj(attn(qkv))
-    if (p_out || need_dqkv)
-        OV_TRY(ov_linear_backward(b.dx1, D, s->attn_out, D, w->out_w, D, M, D, D, need_dqkv ? b.t1 : nullptr, D, p_out ? g->out_w : nullptr,
-                                  D, p_out ? g->out_b : nullptr, b.lin, b.lin_bytes, stream));
-    if (need_dqkv)
-        OV_TRY(attn_bwd(prefix, s->qkv, 3 * D, s->attn_out, D, b.t1, D, b.dqkv, 3 * D, s->attn_lse, B, L, H, hd, scale, b.att, b.att_bytes, stream));
-    if (p_qkv || need_dln1)
-        OV_TRY(ov_linear_backward(b.dqkv, 3 * D, s->ln1_out, D, w->qkv_w, D, M, 3 * D, D, need_dln1 ? b.t1 : nullptr, D,
-                                  p_qkv ? g->qkv_w : nullptr, D, p_qkv ? g->qkv_b : nullptr, b.lin, b.lin_bytes, stream));
-    if (p_ln1 && dx)
-        OV_TRY(ov_layernorm_backward(x, D, w->ln1_w, b.t1, D, b.dx1, D, dx, D, g->ln1_w, g->ln1_b, M, D, eps, b.ln, b.ln_bytes, stream));
-    else if (dx)
-        OV_TRY(layernorm_dx(x, D, w->ln1_w, b.t1, D, b.dx1, D, dx, D, M, D, eps, stream));
-    else if (p_ln1)
-        OV_TRY(layernorm_params(x, D, w->ln1_w, b.t1, D, g->ln1_w, g->ln1_b, M, D, eps, b.ln, stream));
-#undef OV_TRY
-    return OV_OK;
+    return block_backward_chain(cfg, w, x, *s, dy, dx, g, pairs, prefix, b, B, L, stream);
 }

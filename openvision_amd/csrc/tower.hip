@@ -320,27 +320,46 @@ extern "C" size_t ov_tower_workspace_bytes(const ov_tower* t, int B, int L) {
 }
 
 namespace {
-// One ResidualAttentionBlock on rows [0, B*L) of x (in place).  `prof` = record in-situ timings for these launches.
-// `parts` (or NULL): partial sums of x's row statistics (ov_rowparts layout).  parts_in: they describe x on entry (left by the previous
-// block's c_proj); they always describe x on exit.
-int run_block(const ov_tower_cfg& c, const ov_block_weights& w, ov_bf16* x, ov_bf16* h, ov_bf16* big, float* stats, float* parts,
-              bool parts_in, int B, int L, ov_stream_t stream, bool prof, int prefix) {
-    const int D = c.width, H = c.heads, hd = D / H;
+// One part of the batch (the main part on the caller's stream, or the tail images on the side stream): its rows of the token stream
+// and of every workspace region.  `parts` (or NULL): partial sums of x's row statistics (ov_rowparts layout; NULL under fp8); q8 / qs:
+// the fp8 activation buffer and its row scales (fp8 towers).  prof = record in-situ timings for these launches.
+struct BlockPart { ov_bf16 *x, *h, *big; float *stats, *parts; unsigned char* q8; float* qs; int B; ov_stream_t stream; bool prof; };
+// fp8 path: one layer's scale maxima (MLP hidden | attention out), the running ones, and the tower's h_mode (0 = none set)
+struct Fp8Scales { float *h_amax, *a_amax, *h_next, *a_next; int h_mode; };
+
+// One ResidualAttentionBlock on rows [0, B*L) of p.x (in place).  parts_in: p.parts describe x on entry (left by the previous block's
+// c_proj); they always describe x on exit.  Per GEMM: fp8 (e4m3) operands where `mask` names it (q != NULL; BASELINE.json config #5;
+// OV_FP8_ALL = all four), else the LayerNorm folded into the QKV / c_fc epilogue where the weights carry the fold, else the plain GEMM
+// -- so mask 0 is the bf16 block.  In front of an fp8 QKV / c_fc the LayerNorm is fused with the row quantisation; in front of an fp8
+// out_proj / c_proj the attention output / MLP hidden is written as e4m3 by its producer where that producer has a static scale
+// (h_mode >= 2: attention epilogue for head_dim 64, an fp8 c_fc's epilogue) and re-quantised row by row otherwise.
+int run_block(const ov_tower_cfg& c, const ov_block_weights& w, const ov_block_fp8* q, int mask, const Fp8Scales& sc, const BlockPart& p,
+              bool parts_in, int L, int prefix) {
+    const int D = c.width, H = c.heads, hd = D / H, F = c.mlp_pad, B = p.B;
     const int64_t M = (int64_t)B * L;
     const int ldb = big_pitch(c);                               // row pitch of `big` (shared by qkv and the MLP hidden)
     const float scale = 1.0f / sqrtf((float)hd);
     const int gelu = c.gelu_tanh ? OV_EPI_BIAS_GELU_TANH : OV_EPI_BIAS_GELU_ERF;
     const int fc_cls = c.gelu_tanh ? OV_PROF_GEMM_FC_TANH : OV_PROF_GEMM_FC;
     const bool fold = w.qkv_colsum != nullptr && w.fc_colsum != nullptr;   // LN folded into the QKV / c_fc epilogues
+    const bool rp = fold && p.parts != nullptr;                 // statistics ride on the residual GEMMs' epilogues
+    const bool f_qkv = mask & OV_FP8_QKV, f_out = mask & OV_FP8_OUT, f_fc = mask & OV_FP8_FC, f_proj = mask & OV_FP8_PROJ;
+    ov_bf16 *x = p.x, *h = p.h, *big = p.big;
+    float *stats = p.stats, *parts = p.parts, *qs = p.qs;
+    unsigned char* q8 = p.q8;
+    ov_stream_t stream = p.stream;
     int rc;
-#define OV_STEP(cls, call)                                           \
-    do {                                                             \
-        if (prof) { ProfScope ps__(cls, stream, M); rc = (call); }   \
-        else rc = (call);                                            \
-        if (rc) return rc;                                           \
+#define OV_STEP(cls, call)                                             \
+    do {                                                               \
+        if (p.prof) { ProfScope ps__(cls, stream, M); rc = (call); }   \
+        else rc = (call);                                              \
+        if (rc) return rc;                                             \
     } while (0)
-    const bool rp = fold && parts != nullptr;                   // statistics ride on the residual GEMMs' epilogues
-    if (fold) {
+    // ---- attention half ----
+    if (f_qkv) {
+        OV_STEP(OV_PROF_LN, ov_layernorm_quant_fp8(x, D, w.ln1_w, w.ln1_b, q8, D, qs, M, D, c.ln_eps, stream));
+        OV_STEP(OV_PROF_GEMM_QKV, ov_gemm_fp8(q8, D, q->qkv_w8, D, qs, q->qkv_s, q->qkv_b, big, ldb, M, 3 * D, D, OV_EPI_BIAS, nullptr, 0, stream));
+    } else if (fold) {
         if (rp && parts_in) OV_STEP(OV_PROF_LN, ov_rowstats_finalize(parts, stats, M, D, c.ln_eps, stream));
         else OV_STEP(OV_PROF_LN, ov_rowstats(x, D, stats, M, D, c.ln_eps, stream));
         OV_STEP(OV_PROF_GEMM_QKV, ov_gemm_ln(x, D, w.qkv_w, D, w.qkv_b, w.qkv_colsum, stats, big, ldb, M, 3 * D, D, OV_EPI_BIAS, stream));
@@ -348,21 +367,52 @@ int run_block(const ov_tower_cfg& c, const ov_block_weights& w, ov_bf16* x, ov_b
         OV_STEP(OV_PROF_LN, ov_layernorm(x, OV_BF16, D, w.ln1_w, w.ln1_b, h, OV_BF16, D, M, D, c.ln_eps, stream));
         OV_STEP(OV_PROF_GEMM_QKV, ov_gemm(h, D, w.qkv_w, D, w.qkv_b, big, ldb, M, 3 * D, D, OV_EPI_BIAS, nullptr, 0, 0, 0, 0, stream));
     }
-    if (prefix >= 0) OV_STEP(OV_PROF_ATTN, ov_attention_prefix(big, ldb, h, D, B, L, H, hd, scale, prefix, stream));
-    else OV_STEP(OV_PROF_ATTN, ov_attention(big, ldb, h, D, B, L, H, hd, scale, stream));
-    if (rp) OV_STEP(OV_PROF_GEMM_OUT, ov_gemm_rowparts(h, D, w.out_w, D, w.out_b, x, D, M, D, D, x, D, parts, stream));
-    else OV_STEP(OV_PROF_GEMM_OUT, ov_gemm(h, D, w.out_w, D, w.out_b, x, D, M, D, D, OV_EPI_BIAS_RESIDUAL, x, D, 0, 0, 0, stream));
-    if (fold) {
+    if (f_out && sc.h_mode >= 2 && hd == 64) {
+        // static scale: the attention epilogue writes e4m3 itself (into the fp8 activation buffer, free at this point)
+        OV_STEP(OV_PROF_ATTN, ov_attention_fp8out(big, ldb, q8, D, B, L, H, hd, scale, sc.a_amax, sc.a_next, stream));
+        OV_STEP(OV_PROF_GEMM_OUT, ov_gemm_fp8_static(q8, D, q->out_w8, D, nullptr, sc.a_amax, q->out_s, w.out_b, x, D, nullptr, nullptr, M, D, D,
+                                                     OV_EPI_BIAS_RESIDUAL, x, D, stream));
+    } else {
+        if (prefix >= 0) OV_STEP(OV_PROF_ATTN, ov_attention_prefix(big, ldb, h, D, B, L, H, hd, scale, prefix, stream));
+        else OV_STEP(OV_PROF_ATTN, ov_attention(big, ldb, h, D, B, L, H, hd, scale, stream));
+        if (f_out) {
+            OV_STEP(OV_PROF_LN, ov_quant_rows_fp8(h, D, q8, D, qs, M, D, sc.h_mode == 1 ? sc.a_amax : nullptr, stream));
+            OV_STEP(OV_PROF_GEMM_OUT, ov_gemm_fp8(q8, D, q->out_w8, D, qs, q->out_s, w.out_b, x, D, M, D, D, OV_EPI_BIAS_RESIDUAL, x, D, stream));
+        } else if (rp) {
+            OV_STEP(OV_PROF_GEMM_OUT, ov_gemm_rowparts(h, D, w.out_w, D, w.out_b, x, D, M, D, D, x, D, parts, stream));
+        } else {
+            OV_STEP(OV_PROF_GEMM_OUT, ov_gemm(h, D, w.out_w, D, w.out_b, x, D, M, D, D, OV_EPI_BIAS_RESIDUAL, x, D, 0, 0, 0, stream));
+        }
+    }
+    // ---- MLP half ----
+    if (f_fc) {
+        OV_STEP(OV_PROF_LN, ov_layernorm_quant_fp8(x, D, w.ln2_w, w.ln2_b, q8, D, qs, M, D, c.ln_eps, stream));
+    } else if (fold) {
         if (rp) OV_STEP(OV_PROF_LN, ov_rowstats_finalize(parts, stats, M, D, c.ln_eps, stream));
         else OV_STEP(OV_PROF_LN, ov_rowstats(x, D, stats, M, D, c.ln_eps, stream));
-        OV_STEP(fc_cls, ov_gemm_ln(x, D, w.fc_w, D, w.fc_b, w.fc_colsum, stats, big, ldb, M, c.mlp_pad, D, gelu, stream));
     } else {
         OV_STEP(OV_PROF_LN, ov_layernorm(x, OV_BF16, D, w.ln2_w, w.ln2_b, h, OV_BF16, D, M, D, c.ln_eps, stream));
-        OV_STEP(fc_cls, ov_gemm(h, D, w.fc_w, D, w.fc_b, big, ldb, M, c.mlp_pad, D, gelu, nullptr, 0, 0, 0, 0, stream));
     }
-    if (rp) OV_STEP(OV_PROF_GEMM_PROJ, ov_gemm_rowparts(big, ldb, w.proj_w, c.mlp_pad, w.proj_b, x, D, M, D, c.mlp_pad, x, D, parts, stream));
-    else OV_STEP(OV_PROF_GEMM_PROJ, ov_gemm(big, ldb, w.proj_w, c.mlp_pad, w.proj_b, x, D, M, D, c.mlp_pad, OV_EPI_BIAS_RESIDUAL, x,
-                                            D, 0, 0, 0, stream));
+    if (f_fc && f_proj && sc.h_mode >= 2) {
+        // static hidden scale: c_fc quantises its own output (e4m3 bytes, pitch F, in the `big` region), c_proj reads it as is
+        unsigned char* h8 = (unsigned char*)big;
+        OV_STEP(fc_cls, ov_gemm_fp8_static(q8, D, q->fc_w8, D, qs, nullptr, q->fc_s, q->fc_b, h8, F, sc.h_amax, sc.h_next, M, F, D, gelu, nullptr, 0,
+                                           stream));
+        OV_STEP(OV_PROF_GEMM_PROJ, ov_gemm_fp8_static(h8, F, q->proj_w8, F, nullptr, sc.h_amax, q->proj_s, w.proj_b, x, D, nullptr, nullptr, M, D, F,
+                                                      OV_EPI_BIAS_RESIDUAL, x, D, stream));
+    } else {
+        if (f_fc) OV_STEP(fc_cls, ov_gemm_fp8(q8, D, q->fc_w8, D, qs, q->fc_s, q->fc_b, big, ldb, M, F, D, gelu, nullptr, 0, stream));
+        else if (fold) OV_STEP(fc_cls, ov_gemm_ln(x, D, w.fc_w, D, w.fc_b, w.fc_colsum, stats, big, ldb, M, F, D, gelu, stream));
+        else OV_STEP(fc_cls, ov_gemm(h, D, w.fc_w, D, w.fc_b, big, ldb, M, F, D, gelu, nullptr, 0, 0, 0, 0, stream));
+        if (f_proj) {
+            OV_STEP(OV_PROF_LN, ov_quant_rows_fp8(big, ldb, q8, F, qs, M, F, (sc.h_mode == 1 && f_fc) ? sc.h_amax : nullptr, stream));
+            OV_STEP(OV_PROF_GEMM_PROJ, ov_gemm_fp8(q8, F, q->proj_w8, F, qs, q->proj_s, w.proj_b, x, D, M, D, F, OV_EPI_BIAS_RESIDUAL, x, D, stream));
+        } else if (rp) {
+            OV_STEP(OV_PROF_GEMM_PROJ, ov_gemm_rowparts(big, ldb, w.proj_w, F, w.proj_b, x, D, M, D, F, x, D, parts, stream));
+        } else {
+            OV_STEP(OV_PROF_GEMM_PROJ, ov_gemm(big, ldb, w.proj_w, F, w.proj_b, x, D, M, D, F, OV_EPI_BIAS_RESIDUAL, x, D, 0, 0, 0, stream));
+        }
+    }
 #undef OV_STEP
     return OV_OK;
 }
@@ -397,85 +447,6 @@ int tail_images(int B, int L) {
     const int tail = B - Bm;
     if (Bm <= 0 || tail <= 0 || tail > B / 8) return 0;
     return tail;
-}
-}  // namespace
-
-namespace {
-// The same block with fp8 (e4m3) operands on the GEMMs `mask` names (BASELINE.json config #5; OV_FP8_ALL = all four): in front of an
-// fp8 QKV / c_fc the LayerNorm is fused with the row quantisation; in front of an fp8 out_proj / c_proj the attention output / MLP
-// hidden is written as e4m3 by its producer where that producer has a static scale (h_mode >= 2: attention epilogue for head_dim 64,
-// an fp8 c_fc's epilogue) and re-quantised row by row otherwise.  A GEMM outside the mask runs exactly as in run_block (LN fold
-// included), so mask 0 is the bf16 block.
-int run_block_fp8(const ov_tower_cfg& c, const ov_block_weights& w, const ov_block_fp8& q, int mask, ov_bf16* x, ov_bf16* h, ov_bf16* big,
-                  float* stats, unsigned char* q8, float* qs, float* h_amax, float* a_amax, float* h_next, float* a_next, int h_mode, int B,
-                  int L, ov_stream_t stream, bool prof) {
-    const int D = c.width, H = c.heads, hd = D / H, F = c.mlp_pad;
-    const int64_t M = (int64_t)B * L;
-    const int ldb = big_pitch(c);
-    const float scale = 1.0f / sqrtf((float)hd);
-    const int gelu = c.gelu_tanh ? OV_EPI_BIAS_GELU_TANH : OV_EPI_BIAS_GELU_ERF;
-    const int fc_cls = c.gelu_tanh ? OV_PROF_GEMM_FC_TANH : OV_PROF_GEMM_FC;
-    const bool fold = w.qkv_colsum != nullptr && w.fc_colsum != nullptr;
-    const bool f_qkv = mask & OV_FP8_QKV, f_out = mask & OV_FP8_OUT, f_fc = mask & OV_FP8_FC, f_proj = mask & OV_FP8_PROJ;
-    int rc;
-#define OV_STEP(cls, call)                                           \
-    do {                                                             \
-        if (prof) { ProfScope ps__(cls, stream, M); rc = (call); }   \
-        else rc = (call);                                            \
-        if (rc) return rc;                                           \
-    } while (0)
-    // ---- attention half ----
-    if (f_qkv) {
-        OV_STEP(OV_PROF_LN, ov_layernorm_quant_fp8(x, D, w.ln1_w, w.ln1_b, q8, D, qs, M, D, c.ln_eps, stream));
-        OV_STEP(OV_PROF_GEMM_QKV, ov_gemm_fp8(q8, D, q.qkv_w8, D, qs, q.qkv_s, q.qkv_b, big, ldb, M, 3 * D, D, OV_EPI_BIAS, nullptr, 0, stream));
-    } else if (fold) {
-        OV_STEP(OV_PROF_LN, ov_rowstats(x, D, stats, M, D, c.ln_eps, stream));
-        OV_STEP(OV_PROF_GEMM_QKV, ov_gemm_ln(x, D, w.qkv_w, D, w.qkv_b, w.qkv_colsum, stats, big, ldb, M, 3 * D, D, OV_EPI_BIAS, stream));
-    } else {
-        OV_STEP(OV_PROF_LN, ov_layernorm(x, OV_BF16, D, w.ln1_w, w.ln1_b, h, OV_BF16, D, M, D, c.ln_eps, stream));
-        OV_STEP(OV_PROF_GEMM_QKV, ov_gemm(h, D, w.qkv_w, D, w.qkv_b, big, ldb, M, 3 * D, D, OV_EPI_BIAS, nullptr, 0, 0, 0, 0, stream));
-    }
-    if (f_out && h_mode >= 2 && hd == 64) {
-        // static scale: the attention epilogue writes e4m3 itself (into the fp8 activation buffer, free at this point)
-        OV_STEP(OV_PROF_ATTN, ov_attention_fp8out(big, ldb, q8, D, B, L, H, hd, scale, a_amax, a_next, stream));
-        OV_STEP(OV_PROF_GEMM_OUT, ov_gemm_fp8_static(q8, D, q.out_w8, D, nullptr, a_amax, q.out_s, w.out_b, x, D, nullptr, nullptr, M, D, D,
-                                                     OV_EPI_BIAS_RESIDUAL, x, D, stream));
-    } else {
-        OV_STEP(OV_PROF_ATTN, ov_attention(big, ldb, h, D, B, L, H, hd, scale, stream));
-        if (f_out) {
-            OV_STEP(OV_PROF_LN, ov_quant_rows_fp8(h, D, q8, D, qs, M, D, h_mode == 1 ? a_amax : nullptr, stream));
-            OV_STEP(OV_PROF_GEMM_OUT, ov_gemm_fp8(q8, D, q.out_w8, D, qs, q.out_s, w.out_b, x, D, M, D, D, OV_EPI_BIAS_RESIDUAL, x, D, stream));
-        } else {
-            OV_STEP(OV_PROF_GEMM_OUT, ov_gemm(h, D, w.out_w, D, w.out_b, x, D, M, D, D, OV_EPI_BIAS_RESIDUAL, x, D, 0, 0, 0, stream));
-        }
-    }
-    // ---- MLP half ----
-    if (f_fc) {
-        OV_STEP(OV_PROF_LN, ov_layernorm_quant_fp8(x, D, w.ln2_w, w.ln2_b, q8, D, qs, M, D, c.ln_eps, stream));
-    } else if (fold) {
-        OV_STEP(OV_PROF_LN, ov_rowstats(x, D, stats, M, D, c.ln_eps, stream));
-    } else {
-        OV_STEP(OV_PROF_LN, ov_layernorm(x, OV_BF16, D, w.ln2_w, w.ln2_b, h, OV_BF16, D, M, D, c.ln_eps, stream));
-    }
-    if (f_fc && f_proj && h_mode >= 2) {
-        // static hidden scale: c_fc quantises its own output (e4m3 bytes, pitch F, in the `big` region), c_proj reads it as is
-        unsigned char* h8 = (unsigned char*)big;
-        OV_STEP(fc_cls, ov_gemm_fp8_static(q8, D, q.fc_w8, D, qs, nullptr, q.fc_s, q.fc_b, h8, F, h_amax, h_next, M, F, D, gelu, nullptr, 0, stream));
-        OV_STEP(OV_PROF_GEMM_PROJ, ov_gemm_fp8_static(h8, F, q.proj_w8, F, nullptr, h_amax, q.proj_s, w.proj_b, x, D, nullptr, nullptr, M, D, F,
-                                                      OV_EPI_BIAS_RESIDUAL, x, D, stream));
-    } else {
-        if (f_fc) OV_STEP(fc_cls, ov_gemm_fp8(q8, D, q.fc_w8, D, qs, q.fc_s, q.fc_b, big, ldb, M, F, D, gelu, nullptr, 0, stream));
-        else if (fold) OV_STEP(fc_cls, ov_gemm_ln(x, D, w.fc_w, D, w.fc_b, w.fc_colsum, stats, big, ldb, M, F, D, gelu, stream));
-        else OV_STEP(fc_cls, ov_gemm(h, D, w.fc_w, D, w.fc_b, big, ldb, M, F, D, gelu, nullptr, 0, 0, 0, 0, stream));
-        if (f_proj) {
-            OV_STEP(OV_PROF_LN, ov_quant_rows_fp8(big, ldb, q8, F, qs, M, F, (h_mode == 1 && f_fc) ? h_amax : nullptr, stream));
-            OV_STEP(OV_PROF_GEMM_PROJ, ov_gemm_fp8(q8, F, q.proj_w8, F, qs, q.proj_s, w.proj_b, x, D, M, D, F, OV_EPI_BIAS_RESIDUAL, x, D, stream));
-        } else {
-            OV_STEP(OV_PROF_GEMM_PROJ, ov_gemm(big, ldb, w.proj_w, F, w.proj_b, x, D, M, D, F, OV_EPI_BIAS_RESIDUAL, x, D, 0, 0, 0, stream));
-        }
-    }
-#undef OV_STEP
-    return OV_OK;
 }
 }  // namespace
 
@@ -524,20 +495,16 @@ extern "C" int ov_tower_forward(const ov_tower* t, ov_bf16* x, int B, int L, voi
     const int qw = D > c.mlp_pad ? D : c.mlp_pad;                 // row pitch reserved per token in the fp8 activation buffer
     unsigned char* q8 = (unsigned char*)stats + align_up((size_t)M * 8, 256);
     float* qs = (float*)(q8 + align_up((size_t)M * qw, 256));
+    const BlockPart main_part = {x, h, big, stats, parts, q8, qs, Bm, stream, true};
+    const BlockPart tail_part = {x + off * D, h + off * D, big + off * ldb, stats + 2 * off, parts ? parts + 2 * off * G : nullptr,
+                                 q8 + off * qw, qs + off, nt, (ov_stream_t)(nt > 0 ? tc->stream : nullptr), false};
     for (int i = 0; i < c.layers && rc == OV_OK; ++i) {
-        float* ha = t->h_amax ? t->h_amax + i : nullptr;
-        float* aa = t->h_amax ? t->h_amax + c.layers + i : nullptr;
-        float* hn = t->h_amax ? t->h_amax + 2 * c.layers + i : nullptr;
-        float* an = t->h_amax ? t->h_amax + 3 * c.layers + i : nullptr;
-        const int hm = t->h_amax ? t->h_mode : 0;
-        rc = fp8 ? run_block_fp8(c, t->blocks[i], t->fp8[i], t->mask8[i], x, h, big, stats, q8, qs, ha, aa, hn, an, hm, Bm, L, stream, true)
-                 : run_block(c, t->blocks[i], x, h, big, stats, parts, i > 0, Bm, L, stream, true, t->prefix);
-        if (rc == OV_OK && nt > 0) {
-            rc = fp8 ? run_block_fp8(c, t->blocks[i], t->fp8[i], t->mask8[i], x + off * D, h + off * D, big + off * ldb, stats + 2 * off,
-                                     q8 + off * qw, qs + off, ha, aa, hn, an, hm, nt, L, (ov_stream_t)tc->stream, false)
-                     : run_block(c, t->blocks[i], x + off * D, h + off * D, big + off * ldb, stats + 2 * off,
-                                 parts ? parts + 2 * off * G : nullptr, i > 0, nt, L, (ov_stream_t)tc->stream, false, t->prefix);
-        }
+        Fp8Scales sc = {nullptr, nullptr, nullptr, nullptr, 0};
+        if (t->h_amax) sc = {t->h_amax + i, t->h_amax + c.layers + i, t->h_amax + 2 * c.layers + i, t->h_amax + 3 * c.layers + i, t->h_mode};
+        const ov_block_fp8* q = fp8 ? &t->fp8[i] : nullptr;
+        const int mask = fp8 ? t->mask8[i] : 0;
+        rc = run_block(c, t->blocks[i], q, mask, sc, main_part, i > 0, L, t->prefix);
+        if (rc == OV_OK && nt > 0) rc = run_block(c, t->blocks[i], q, mask, sc, tail_part, i > 0, L, t->prefix);
     }
     if (nt > 0) {
         // always join, also after an error between fork and here: whatever the side stream got stays ordered before the
@@ -550,9 +517,9 @@ extern "C" int ov_tower_forward(const ov_tower* t, ov_bf16* x, int B, int L, voi
 }
 
 // ---- training-side entry points: keep every block's input, run the blocks' backward in reverse -------------
-// backward.hip, one block over its kept activations (arguments checked here): block_backward_partial computes the requested pairs of g
-// (block_grad_pairs: bit k = pair k, -1 for a half-NULL or misaligned pair) and dx unless NULL, with ov_block_backward's launches for
-// them; block_backward_input computes dx alone, in a smaller workspace.
+// backward.hip, one block over its kept activations (arguments checked here), both the block's one backward chain:
+// block_backward_partial called with the requested pairs of g (block_grad_pairs: bit k = pair k, -1 for a half-NULL or misaligned
+// pair) and dx unless NULL; block_backward_input with no pair, dx alone, in a smaller workspace.
 int block_grad_pairs(const ov_block_grads* g);
 int block_backward_partial(const ov_tower_cfg* cfg, const ov_block_weights* w, const ov_bf16* x, const ov_block_saved* s, const ov_bf16* dy,
                            ov_bf16* dx, const ov_block_grads* g, int prefix, int B, int L, void* workspace, size_t workspace_bytes,
@@ -752,7 +719,7 @@ extern "C" size_t ov_tower_backward_workspace_bytes(const ov_tower* t, int B, in
     return ov_block_backward_workspace_bytes(&t->cfg, B, L);
 }
 
-// Every pair of every layer and dx: block_backward_partial then makes exactly ov_block_backward's launches.  The checks keep the codes
+// Every pair of every layer and dx: block_backward_partial then runs the chain as ov_block_backward does.  The checks keep the codes
 // and the order in which a walk over ov_block_backward reported them (the top layer's, then the workspace and the alignment, then the
 // layers below; folded weights are OV_ERR_UNSUPPORTED here), but all of them come before the first launch.
 extern "C" int ov_tower_backward(const ov_tower* t, const ov_bf16* saved, ov_bf16* dx, const ov_block_grads* grads, int B, int L,

@@ -35,13 +35,13 @@ def gemm(a, w, bias=None, epi=0, resid=None, out=None, out_group=0, resid_mod=0,
     return out
 
 
-def gemm_keep(a, w, bias, epi, ldc=None, ldc2=None):
-    """C = gelu(a w^T + bias), C2 = a w^T + bias (both bf16) from one launch: ov_gemm_keep."""
+def gemm_keep(a, w, bias, epi, ldc=None, ldc2=None, fill=0.0):
+    """C = gelu(a w^T + bias), C2 = a w^T + bias (both bf16) from one launch: ov_gemm_keep.  fill: what both outputs hold before."""
     lib = _lib.load()
     m, k = a.shape
     n = w.shape[0]
-    out = torch.zeros(m, ldc or n, dtype=torch.bfloat16, device=a.device)
-    pre = torch.zeros(m, ldc2 or n, dtype=torch.bfloat16, device=a.device)
+    out = torch.full((m, ldc or n), fill, dtype=torch.bfloat16, device=a.device)
+    pre = torch.full((m, ldc2 or n), fill, dtype=torch.bfloat16, device=a.device)
     check(lib.ov_gemm_keep(ptr(a), a.stride(0), ptr(w), w.stride(0), ptr(bias), ptr(out), out.stride(0), ptr(pre), pre.stride(0),
                            m, n, k, epi, stream_ptr()))
     return out, pre

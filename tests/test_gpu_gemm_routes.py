@@ -1,0 +1,403 @@
+"""The persistent GEMM's tile walks and store policies against an independent fp64 reference.
+
+The other GEMM tests compare sibling launches bit for bit (persistent against plain, ov_gemm_keep against two ov_gemm calls), which
+is blind to anything both get wrong alike: a tile the walk skips or visits twice, a store form that drops columns.  Here every
+form the launcher selects by size (gemm.hip: launch<EPI>, persist_policy, gemm_ngroup) is compared with
+A.double() @ W.double().T (+ bias) (+ R) computed by torch ON THE DEVICE (rocBLAS fp64: the fp64-on-device route of the two the
+plan allowed), in row chunks so that no fp64 temporary exceeds 1 GB.
+
+Bound per element, derived, not tuned (REL = 2^-8 = hipops.REL: one bf16 rounding, half an ulp of an 8-bit significand, is at most
+2^-8 of the value -- reached just above a power of two, so a correct kernel comes close to ratio 1):
+
+    bias:      |got - ref| <= REL |ref| + K 2^-24 S + 1e-6,           S = |A| |W|^T + |bias| (+ |R|)
+               (one rounding of the output; K 2^-24 S = worst-case fp32 accumulation error in any order; S from an fp32 matmul)
+    residual:  the same + REL (1 + REL) |pre|,  pre = A W^T + bias.
+               The residual epilogue is out = bf16(bf16(acc + bias) + R) (common.h, epi_combine: "combine(bf16(acc + bias), R)") --
+               the Linear's output is rounded to bf16 before the residual is added, as the bf16 model this path replaces does
+               (a bf16 nn.Linear, then x + y in bf16).  A bound with ONE rounding (the first line) therefore does not hold for a
+               correct kernel wherever pre and R cancel (err up to 2^-8 |pre| where |ref| ~ 0): a torch fp32 restatement of the
+               epilogue on a (300, 200, 192) problem of the same distribution gives max err / bound = 42 with it, and the residual
+               tests print the ratio under it next to the asserted one.  Corrected derivation: two roundings, of pre (REL |pre|) and
+               of the sum, which carries the first rounding's error (REL (|ref| + REL |pre|)).
+               A tile visited twice adds pre twice (the runs are in place, C aliasing R): err = |pre|, 256 x the extra term.
+    GELU:      1.13 x (the bias bound, for the pre-activation) + REL |ref| + E      (1.13 = max |gelu'|)
+               E, erf form: common.h states |GELU error| <= 1.4e-4 on [-4, 4] and <= 6.6e-5 |x| beyond (gelu_erf_f2; a Python
+               restatement of the polynomial on a 2^-12 grid over [-8, 8] gives 1.376e-4 and 6.61e-5 |x|): E = max(1.4e-4, 6.6e-5 |pre|).
+               E, tanh form: common.h states no figure.  gelu_tanh_f2 is the closed form x / (1 + exp2(-2 log2(e) u)), algebraically
+               the tanh GELU, so the restatement in fp64 differs from fp64 0.5 x (1 + tanh u) by 1.8e-15; evaluated in fp32 (numpy,
+               the same operation order) on the 2^-12 grid over [-8, 8] the maximum difference is 5.2e-7 (the |x| weighting
+               included: it is the error of the GELU value itself).  With the factor 2: E = 1.1e-6.
+    LN fold:   x Wg - mean colsum cancels, the bounds above do not apply: the rule of
+               test_gemm_ln_fold_matches_layernorm_then_linear, |got - ref| <= 2e-2 + 1.5e-2 |ref| against Linear(LayerNorm(x)) in
+               fp64, the same input construction (mean 0.4, spread 1.7).
+
+Every output starts as the bf16 sentinel 77, so a skipped tile fails the bound instead of passing as zeros, and padding behind the
+last valid column must still hold it.  Every case asserts, from a restatement of the launcher's rules and the device's CU count,
+that the form it names is the one selected."""
+import functools
+import math
+import os
+import subprocess
+import sys
+import tempfile
+from types import SimpleNamespace
+
+import pytest
+import torch
+
+import hipops as H
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+BM = BN = 256
+BK = 64
+SKINNY_TILES = 96
+SENT = 77.0
+REL = H.REL
+E_TANH = 1.1e-6
+LN_RTOL, LN_ATOL = 1.5e-2, 2e-2
+CHUNK = 4096                      # rows per fp64 chunk: 4096 x 4096 x 8 B = 128 MB for the widest N here
+
+
+def route(M, N, K, epi=0, keep=False, nt_min_mb=192):
+    """What gemm.hip's launcher selects for this shape on this device (launch<EPI>, gemm_ngroup, persist_policy)."""
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    tm, tn = -(-M // BM), -(-N // BN)
+    nwg = tm * tn
+    if not keep and nwg <= SKINNY_TILES:
+        kernel = "skinny"
+    elif nwg < cus or K < 3 * BK:
+        kernel = "plain"
+    else:
+        kernel = "persistent"
+    wbytes = tn * BN * K * 2
+    ngroup = tn if (wbytes <= (3 << 20) or tn <= 4 or tn % 4 or tm < 16) else 4
+    rem, nper = N % BN, cus >> 3
+    rot = tn - 1 if (0 < rem <= 128 and ngroup >= tn and tn > 1 and tn & (tn - 1) == 0 and cus % 8 == 0 and nper % tn == 0) else 0
+    return SimpleNamespace(cus=cus, tm=tm, tn=tn, nwg=nwg, kernel=kernel, grouped=ngroup < tn, groups=tn // ngroup, rot=rot, rem=rem,
+                           pr=tm & 7, rev=epi == 3 and K >= 2 * N, st_plain=M * N * 2 < (nt_min_mb << 20), wbytes=wbytes)
+
+
+# case -> (M, N, K), the walk it must select, and what else makes it the case it is (each asserted before the launch)
+CASES = {
+    1: ((22100, 768, 192), "plain", [("tile count not a multiple of 8: XCD runs of unequal length", lambda r: r.nwg % 8 != 0),
+                                     ("ragged last row tile", lambda r: 22100 % BM != 0)]),
+    2: ((17052, 840, 192), "rotated", [("tiles_n = 4", lambda r: r.tn == 4 and r.rot == 3), ("72-column last n-tile", lambda r: r.rem == 72),
+                                       ("67 row panels, pr = 3", lambda r: r.tm == 67 and r.pr == 3)]),
+    3: ((8904, 1800, 192), "rotated", [("tiles_n = 8", lambda r: r.tn == 8 and r.rot == 7), ("8-column last n-tile", lambda r: r.rem == 8),
+                                       ("W is 0.75 MiB", lambda r: r.wbytes == 3 << 18), ("35 panels", lambda r: r.tm == 35)]),
+    4: ((8904, 2048, 832), "grouped", [("2 groups", lambda r: r.groups == 2), ("35 panels: XCDs own 5, 5, 5, 4, ...", lambda r: r.tm == 35 and r.pr == 3)]),
+    5: ((8904, 1800, 832), "grouped", [("8-column last n-tile", lambda r: r.rem == 8), ("2 groups", lambda r: r.groups == 2)]),
+    6: ((5688, 3072, 576), "grouped", [("3 groups", lambda r: r.groups == 3), ("23 panels, pr = 7", lambda r: r.tm == 23 and r.pr == 7)]),
+    7: ((8192, 2048, 832), "grouped", [("one tile per workgroup", lambda r: r.nwg == r.cus)]),
+    8: ((8904, 2048, 4096), "grouped", [("2 groups", lambda r: r.groups == 2), ("35 panels", lambda r: r.tm == 35)]),
+    # rowparts only: case 2's form at the nearest N that ov_gemm_rowparts admits (N % 32 == 0; 840 is refused, see the rowparts test)
+    "2r": ((17052, 832, 192), "rotated", [("tiles_n = 4", lambda r: r.tn == 4 and r.rot == 3), ("64-column last n-tile", lambda r: r.rem == 64),
+                                          ("67 row panels, pr = 3", lambda r: r.tm == 67 and r.pr == 3)]),
+    # the store-policy threshold itself, in a process without OVHIP_GEMM_NT_MIN_MB
+    "203MB": ((24832, 4096, 192), "plain", [("output of at least 192 MB", lambda r: not r.st_plain)]),
+}
+
+
+def selected(case, epi=0, keep=False, nt_min_mb=192, rev=False):
+    """Asserts that `case` reaches the kernel form it is in the table for; returns its shape."""
+    (M, N, K), walk, extra = CASES[case]
+    r = route(M, N, K, epi, keep, nt_min_mb)
+    assert r.kernel == "persistent", f"case {case} {(M, N, K)}: {r.nwg} tiles on {r.cus} CUs, K = {K} selects the {r.kernel} kernel"
+    got = "grouped" if r.grouped else "rotated" if r.rot else "plain"
+    assert got == walk, f"case {case} {(M, N, K)}: the launcher selects the {got} walk, the case is there for the {walk} walk"
+    for what, holds in extra:
+        assert holds(r), f"case {case} {(M, N, K)} on {r.cus} CUs no longer has: {what}"
+    assert r.rev == rev, f"case {case} {(M, N, K)} epilogue {epi}: descending row walk {r.rev}, wanted {rev}"
+    return M, N, K
+
+
+@functools.lru_cache(maxsize=None)
+def operands(M, N, K):
+    """A, W bf16, bias fp32 on the device (CPU generator: the child processes build the same)."""
+    g = torch.Generator().manual_seed(1000003 * K + 1009 * N + M)
+    a = torch.randn(M, K, generator=g).to(torch.bfloat16).to(DEV)
+    w = (torch.randn(N, K, generator=g) / K ** 0.5).to(torch.bfloat16).to(DEV)
+    return a, w, torch.randn(N, generator=g).to(DEV)
+
+
+@functools.lru_cache(maxsize=None)
+def residual(M, N):
+    g = torch.Generator().manual_seed(7 * M + N)
+    return torch.randn(M, N, generator=g).to(torch.bfloat16).to(DEV)
+
+
+@functools.lru_cache(maxsize=None)
+def fold_operands(M, N, K):
+    """The LN-folded operands of test_gemm_ln_fold_matches_layernorm_then_linear: x, Wg, cvec, colsum and the unfolded w, bias, gamma,
+    beta (fp32) the reference uses."""
+    rnd = lambda *s, seed: torch.randn(*s, generator=torch.Generator().manual_seed(seed + M + N + K))
+    x = (rnd(M, K, seed=30) * 1.7 + 0.4).to(torch.bfloat16)
+    w, bias = rnd(N, K, seed=31) / K ** 0.5, rnd(N, seed=32) * 0.1
+    gamma, beta = rnd(K, seed=33) * 0.1 + 1, rnd(K, seed=34) * 0.1
+    wg = (w * gamma[None, :]).to(torch.bfloat16)
+    colsum = wg.float().sum(1)
+    cvec = w.to(torch.bfloat16).float() @ beta + bias
+    return tuple(t.to(DEV) for t in (x, wg, cvec, colsum, w, bias, gamma, beta))
+
+
+def gelu64(x, tanh):
+    return torch.nn.functional.gelu(x, approximate="tanh" if tanh else "none")
+
+
+def _worst(err, bound, row0):
+    q = err / bound
+    k = int(q.argmax())
+    return float(q.view(-1)[k]), row0 + k // q.shape[1], k % q.shape[1]
+
+
+def _merge(res, name, item):
+    old = res.get(name)
+    if old is None or math.isnan(item[0]) or item[0] > old[0]:        # (a NaN is kept: it fails the assertion)
+        res[name] = item
+
+
+def linear_ratios(a, w, bias, outs, r=None):
+    """outs: name -> (bf16 [M, >= N], kind), kind in pre | erf | tanh | res | res1 (res1: the residual under the ONE-rounding bound, for
+    the record).  Returns name -> (max err / bound, row, column) against fp64 on the device, in row chunks."""
+    M, K = a.shape
+    N = w.shape[0]
+    wd, wabs, bd = w.double(), w.float().abs(), bias.double()
+    res = {}
+    for i in range(0, M, CHUNK):
+        sl = slice(i, min(M, i + CHUNK))
+        pre = a[sl].double() @ wd.T + bd
+        s = (a[sl].float().abs() @ wabs.T + bias.abs()).double()
+        b_pre = REL * pre.abs() + K * 2.0 ** -24 * s + 1e-6
+        for name, (got, kind) in outs.items():
+            g = got[sl, :N].double()
+            if kind == "pre":
+                ref, bound = pre, b_pre
+            elif kind in ("res", "res1"):
+                rr = r[sl].double()
+                ref = pre + rr
+                bound = REL * ref.abs() + K * 2.0 ** -24 * (s + rr.abs()) + 1e-6
+                if kind == "res":
+                    bound = bound + REL * (1 + REL) * pre.abs()
+            else:
+                ref = gelu64(pre, kind == "tanh")
+                e = E_TANH if kind == "tanh" else torch.clamp(6.6e-5 * pre.abs(), min=1.4e-4)
+                bound = 1.13 * b_pre + REL * ref.abs() + e
+            _merge(res, name, _worst((g - ref).abs(), bound, i))
+    return res
+
+
+def fold_ratios(M, N, K, outs):
+    """outs: name -> (bf16 [M, >= N], epi 0 | 1 | 2) of ov_gemm_ln on fold_operands(M, N, K): max err / (atol + rtol |ref|) against
+    Linear(LayerNorm(x)) (then GELU) in fp64."""
+    x, _, _, _, w, bias, gamma, beta = fold_operands(M, N, K)
+    wd = w.double()
+    res = {}
+    for i in range(0, M, CHUNK):
+        sl = slice(i, min(M, i + CHUNK))
+        xd = x[sl].double()
+        mu, var = xd.mean(1, keepdim=True), xd.var(1, unbiased=False, keepdim=True)
+        lin = ((xd - mu) * (var + 1e-6).rsqrt() * gamma.double() + beta.double()) @ wd.T + bias.double()
+        for name, (got, epi) in outs.items():
+            ref = gelu64(lin, epi == 2) if epi else lin
+            _merge(res, name, _worst((got[sl, :N].double() - ref).abs(), LN_ATOL + LN_RTOL * ref.abs(), i))
+    return res
+
+
+def report(tag, res, skip=()):
+    for name, (q, row, col) in res.items():
+        print(f"{tag} {name}: max err / bound {q:.3f}")
+    bad = {n: (q, f"row {row} column {col} = tile ({row // BM}, {col // BN})") for n, (q, row, col) in res.items()
+           if n not in skip and not q <= 1.0}
+    assert not bad, (tag, bad)
+
+
+def sentinel(M, width):
+    return torch.full((M, width), SENT, dtype=torch.bfloat16, device=DEV)
+
+
+def padding_kept(out, N):
+    return bool((out[:, N:] == SENT).all())
+
+
+EPI_KIND = {0: "pre", 1: "erf", 2: "tanh", 3: "res"}
+
+
+@pytest.mark.parametrize("epi", [0, 1, 3])
+@pytest.mark.parametrize("case", [1, 2, 3, 4, 5, 6, 7])
+def test_walk_epilogues_within_the_fp64_bound(case, epi):
+    """Bias, erf-GELU and in-place residual epilogues over the plain, rotated and grouped walks of the case table."""
+    M, N, K = selected(case, epi)
+    a, w, bias = operands(M, N, K)
+    if epi == 3:
+        r = residual(M, N)
+        out = r.clone()
+        H.gemm(a, w, bias, epi=3, resid=out, out=out)
+        res = linear_ratios(a, w, bias, {"residual": (out, "res"), "residual (one-rounding bound)": (out, "res1")}, r)
+        report(f"case {case} {(M, N, K)}", res, skip=("residual (one-rounding bound)",))
+    else:
+        out = H.gemm(a, w, bias, epi=epi, out=sentinel(M, N))
+        report(f"case {case} {(M, N, K)}", linear_ratios(a, w, bias, {("bias", "gelu erf")[epi]: (out, EPI_KIND[epi])}))
+
+
+def test_grouped_walk_with_descending_rows_residual():
+    """Case 8: K >= 2 N, so the residual epilogue walks the row tiles of the grouped walk from the last to the first."""
+    M, N, K = selected(8, 3, rev=True)
+    a, w, bias = operands(M, N, K)
+    r = residual(M, N)
+    out = r.clone()
+    H.gemm(a, w, bias, epi=3, resid=out, out=out)
+    res = linear_ratios(a, w, bias, {"residual": (out, "res"), "residual (one-rounding bound)": (out, "res1")}, r)
+    report(f"case 8 {(M, N, K)}", res, skip=("residual (one-rounding bound)",))
+
+
+@pytest.mark.parametrize("case", [4, 6])
+def test_grouped_walk_keep_both_outputs(case):
+    """ov_gemm_keep over the grouped walk: the GELU output and the kept pre-activation, padded ldc / ldc2."""
+    M, N, K = selected(case, 1, keep=True)
+    a, w, bias = operands(M, N, K)
+    out, pre = H.gemm_keep(a, w, bias, 1, ldc=N + 64, ldc2=N + 8, fill=SENT)
+    report(f"case {case} {(M, N, K)} keep", linear_ratios(a, w, bias, {"gelu erf": (out, "erf"), "pre-activation": (pre, "pre")}))
+    assert padding_kept(out, N) and padding_kept(pre, N)
+
+
+@pytest.mark.parametrize("epi", [0, 1])
+@pytest.mark.parametrize("case", [4, 6])
+def test_grouped_walk_ln_fold(case, epi):
+    M, N, K = selected(case, epi)
+    x, wg, cvec, colsum = fold_operands(M, N, K)[:4]
+    out = H.gemm_ln(x, wg, cvec, colsum, H.rowstats(x), epi=epi, out=sentinel(M, N + 8))
+    report(f"case {case} {(M, N, K)} LN fold", fold_ratios(M, N, K, {("bias", "gelu erf")[epi]: (out, epi)}))
+    assert padding_kept(out, N)
+
+
+@pytest.mark.parametrize("case", ["2r", 4, 8])
+def test_walk_rowparts(case):
+    """ov_gemm_rowparts (the residual epilogue with fused row statistics), in place as the tower calls it: the output against fp64,
+    the parts against the 32-column sums and sums of squares of the stored output in fp64 (rtol 1e-5, atol 1e-4: the rule of
+    test_gemm_rowparts_are_the_row_partial_sums_of_the_output).  The rotated walk runs at N = 832 instead of case 2's 840: the entry
+    point needs N % 32 == 0 and refuses 840, which is asserted; 832 keeps tiles_n = 4, the 67 panels and a half last n-tile."""
+    if case == "2r":
+        M2, N2, K2 = CASES[2][0]
+        a2, w2, b2 = operands(M2, N2, K2)
+        with pytest.raises(H._lib.OvhipError):
+            H.gemm_rowparts(a2, w2, b2, residual(M2, N2), parts=torch.empty(M2, N2 // 32, 2, device=DEV))
+    M, N, K = selected(case, 3, rev=case == 8)
+    a, w, bias = operands(M, N, K)
+    r = residual(M, N)
+    out = r.clone()
+    _, parts = H.gemm_rowparts(a, w, bias, out, out=out)
+    res = linear_ratios(a, w, bias, {"residual": (out, "res"), "residual (one-rounding bound)": (out, "res1")}, r)
+    report(f"case {case} {(M, N, K)} rowparts", res, skip=("residual (one-rounding bound)",))
+    assert not torch.isnan(parts).any()
+    x = out.double().view(M, N // 32, 32)
+    for j, want in enumerate((x.sum(-1), (x * x).sum(-1))):
+        err = (parts[..., j].double() - want).abs()
+        assert bool((err <= 1e-4 + 1e-5 * want.abs()).all()), (case, j, float(err.max()))
+
+
+def test_output_of_203_mb_is_streamed_by_the_default_threshold():
+    """No environment set: a 203 MB output crosses the 192 MB rule, so the bias epilogue stores with streaming stores and the LN-folded
+    GELU takes the LDS-transposed streamed form -- the production combination, selected by the threshold itself."""
+    for v in ("OVHIP_GEMM_NT_MIN_MB", "OVHIP_GEMM_GELU_LDS"):
+        assert v not in os.environ, f"{v} is set: this test is about the defaults"
+    M, N, K = selected("203MB")
+    a, w, bias = operands(M, N, K)
+    out = H.gemm(a, w, bias, epi=0, out=sentinel(M, N))
+    report(f"203 MB {(M, N, K)}", linear_ratios(a, w, bias, {"bias, streamed": (out, "pre")}))
+    del out
+    x, wg, cvec, colsum = fold_operands(M, N, K)[:4]
+    out = H.gemm_ln(x, wg, cvec, colsum, H.rowstats(x), epi=1, out=sentinel(M, N))
+    report(f"203 MB {(M, N, K)}", fold_ratios(M, N, K, {"LN fold + gelu erf, LDS form streamed": (out, 1)}))
+
+
+# ---- store policy and the GELU-form switch: read once per process, so each setting runs in a child process of its own ----
+
+CHILD_CASES = (1, 3, 4, 6)
+LINEAR_FORMS = {"bias": "pre", "gelu erf": "erf", "gelu tanh": "tanh", "keep gelu erf": "erf", "keep pre-activation": "pre"}
+FOLD_FORMS = {"fold bias": 0, "fold gelu erf": 1, "fold gelu tanh": 2}
+SETTINGS = {
+    "default": ({}, "all"),
+    "streamed": ({"OVHIP_GEMM_NT_MIN_MB": "0"}, "all"),
+    "lds form, plain stores": ({"OVHIP_GEMM_GELU_LDS": "1"}, "foldgelu"),
+    "direct form, streamed": ({"OVHIP_GEMM_GELU_LDS": "0", "OVHIP_GEMM_NT_MIN_MB": "0"}, "foldgelu"),
+}
+
+
+def child_main(path, which):
+    """(In the child process.)  Every entry point over CHILD_CASES, outputs to `path`; which = foldgelu: the LN-folded GELUs only."""
+    outs = {}
+    for case in CHILD_CASES:
+        M, N, K = CASES[case][0]
+        if which == "all":
+            a, w, bias = operands(M, N, K)
+            for name, epi in (("bias", 0), ("gelu erf", 1), ("gelu tanh", 2)):
+                outs[case, name] = H.gemm(a, w, bias, epi=epi, out=sentinel(M, N)).cpu()
+            out, pre = H.gemm_keep(a, w, bias, 1, ldc=N + 64, ldc2=N + 8, fill=SENT)
+            outs[case, "keep gelu erf"], outs[case, "keep pre-activation"] = out.cpu(), pre.cpu()
+        x, wg, cvec, colsum = fold_operands(M, N, K)[:4]
+        st = H.rowstats(x)
+        for name, epi in FOLD_FORMS.items():
+            if which == "all" or epi:
+                outs[case, name] = H.gemm_ln(x, wg, cvec, colsum, st, epi=epi, out=sentinel(M, N)).cpu()
+    torch.save(outs, path)
+
+
+@functools.lru_cache(maxsize=None)
+def child_outputs(setting):
+    """Runs the child of `setting` (once per session, one child at a time) and returns what it saved."""
+    env_add, which = SETTINGS[setting]
+    tests = os.path.dirname(os.path.abspath(__file__))
+    env = {k: v for k, v in os.environ.items() if k not in ("OVHIP_GEMM_NT_MIN_MB", "OVHIP_GEMM_GELU_LDS")}
+    env.update(env_add, OV_ROOT=os.path.dirname(tests))
+    code = ("import os, sys; sys.path[:0] = [os.environ['OV_ROOT'], os.path.join(os.environ['OV_ROOT'], 'tests')]; "
+            "import test_gpu_gemm_routes as T; T.child_main(sys.argv[1], sys.argv[2])")
+    with tempfile.TemporaryDirectory() as d:
+        path = os.path.join(d, "outs.pt")
+        subprocess.run([sys.executable, "-c", code, path, which], check=True, env=env, timeout=300)
+        return torch.load(path)
+
+
+@pytest.mark.parametrize("setting", list(SETTINGS))
+def test_store_policy_outputs_within_the_fp64_bound(setting):
+    """Every output of the child under `setting` -- plain stores (default), every bias / GELU output streamed
+    (OVHIP_GEMM_NT_MIN_MB=0; the folded GELU then in its LDS-transposed form: the production combination), the LDS form with plain
+    stores (OVHIP_GEMM_GELU_LDS=1), the direct form streamed (GELU_LDS=0, NT_MIN_MB=0) -- within its bound."""
+    env_add, which = SETTINGS[setting]
+    nt = int(env_add.get("OVHIP_GEMM_NT_MIN_MB", 192))
+    outs = child_outputs(setting)
+    for case in CHILD_CASES:
+        for epi in (0, 1, 2):
+            M, N, K = selected(case, epi, nt_min_mb=nt)
+        assert route(M, N, K, nt_min_mb=nt).st_plain == (nt != 0), (case, nt)
+        selected(case, 1, keep=True, nt_min_mb=nt)
+        dev = {name: t.to(DEV) for (c, name), t in outs.items() if c == case}
+        assert set(dev) == (set(LINEAR_FORMS) | set(FOLD_FORMS) if which == "all" else {"fold gelu erf", "fold gelu tanh"})
+        tag = f"[{setting}] case {case} {(M, N, K)}"
+        if which == "all":
+            a, w, bias = operands(M, N, K)
+            report(tag, linear_ratios(a, w, bias, {n: (dev[n], kind) for n, kind in LINEAR_FORMS.items()}))
+            assert padding_kept(dev["keep gelu erf"], N) and padding_kept(dev["keep pre-activation"], N)
+        report(tag, fold_ratios(M, N, K, {n: (dev[n], epi) for n, epi in FOLD_FORMS.items() if n in dev}))
+
+
+def _bitwise(x, y, names):
+    for case in CHILD_CASES:
+        for name in names:
+            assert torch.equal(x[case, name], y[case, name]), (case, name)
+
+
+def test_streamed_stores_are_bitwise_the_plain_stores():
+    """OVHIP_GEMM_NT_MIN_MB=0 changes only the store instruction of the forms whose instantiation it leaves alone: bias, unfolded GELU,
+    KEEP (both outputs, padding included) and fold + bias equal the default process's outputs bit for bit."""
+    _bitwise(child_outputs("default"), child_outputs("streamed"), list(LINEAR_FORMS) + ["fold bias"])
+
+
+def test_lds_gelu_form_plain_stores_bitwise_the_streamed():
+    """OVHIP_GEMM_GELU_LDS=1 under the default threshold (LDS form, plain stores) against NT_MIN_MB=0 (LDS form by default, streamed)."""
+    _bitwise(child_outputs("lds form, plain stores"), child_outputs("streamed"), ["fold gelu erf", "fold gelu tanh"])
+
+
+def test_direct_gelu_form_streamed_bitwise_the_default():
+    """OVHIP_GEMM_GELU_LDS=0 with NT_MIN_MB=0 (direct form, streamed) against the default process (direct form, plain stores)."""
+    _bitwise(child_outputs("direct form, streamed"), child_outputs("default"), ["fold gelu erf", "fold gelu tanh"])

@@ -17,6 +17,7 @@
  *   ov_l2norm           F.normalize(x, dim=-1)                                model.py:267,284
  *   ov_logits           CLIP.get_logits (scale * img @ txt^T)                 model.py:286-293
  *   ov_clip_loss        ClipLoss.get_logits + cross_entropy both ways         loss.py:102-131
+ *   ov_clip_loss_multi  bidirectional_contrastive_loss, C caption sets        src/losses/common.py:120-189
  *   ov_siglip_loss      SigLipLoss._loss summed over every text block          loss.py:307-414
  *   ov_gemm_fp8         the same nn.Linear on fp8 e4m3 operands (config #5)           transformer.py:225,232-236
  *   ov_preprocess_image transforms.Resize -> ToTensor -> Normalize (Pillow-exact)  ov-zero-shot-test.py:72-77, transform.py:355-392
@@ -288,6 +289,45 @@ int ov_clip_loss_backward(const float* img, const float* txt, const float* all_i
                           const float* logit_scale, int label_offset, const float* lse_terms, const float* grad_loss, float* d_img,
                           float* d_txt, float* d_all_img, float* d_all_txt, float* d_scale, void* workspace,
                           size_t workspace_bytes, ov_stream_t stream);
+
+/* InfoNCE over C caption sets per image (bidirectional_contrastive_loss with local_loss, src/losses/common.py:120-189, which has
+ * C = 2): the mean over c of ov_clip_loss(img, txt_c), in one forward and one backward.
+ *   img           : this rank's image embeddings [b, E] fp32, contiguous
+ *   txt           : this rank's text embeddings, the C sets stacked [C b, E] fp32, contiguous: set c in rows c b ... c b + b - 1
+ *   all_img       : gathered image embeddings, N rows of E floats, row g at all_img + g * ld
+ *   all_txt       : gathered text embeddings, row g of set c at all_txt + c * set_stride + g * ld
+ *                   (the all-gather's packed [N, (1 + C) E] buffer in place: all_img = buf, all_txt = buf + E, ld = (1 + C) E,
+ *                    set_stride = E;  separate arrays [N, E] and [C, N, E]: ld = E, set_stride = N E;  N == b without a gather:
+ *                    all_img = img, all_txt = txt, ld = E, set_stride = b E)
+ *   logit_scale   : DEVICE scalar, the multiplier;  labels are i + label_offset
+ *   loss_out[0] = 1 / (2 C b) sum_c sum_i [ lse(A_c[i, :]) - A_c[i, i + off] + lse(B_c[i, :]) - B_c[i, i + off] ],
+ *                 A_c = scale img all_txt_c^T, B_c = scale txt_c all_img^T                     (fp32, device)
+ *   terms_out (optional, may be NULL): [4 C, b] fp32; for set c rows 4c ... 4c + 3 = lse_img, diag_img, lse_txt, diag_txt
+ * 1 <= C <= 4 and E % 8 == 0 (OV_ERR_UNSUPPORTED otherwise); ld >= E, ld and set_stride multiples of 4 floats, every base pointer
+ * 16-byte aligned (OV_ERR_INVALID otherwise).  workspace: ov_clip_loss_multi_workspace_bytes(b, N, C) bytes (0 for sizes that are
+ * not positive or C out of range).  Logits are never materialised; deterministic (no atomics). */
+size_t ov_clip_loss_multi_workspace_bytes(int b, int N, int C);
+int ov_clip_loss_multi(const float* img, const float* txt, const float* all_img, const float* all_txt, int64_t ld, int64_t set_stride,
+                       int b, int N, int E, int C, const float* logit_scale, int label_offset, float* loss_out, float* terms_out,
+                       void* workspace, size_t workspace_bytes, ov_stream_t stream);
+
+/* Backward of ov_clip_loss_multi, operands laid out as there; terms = the [4 C, b] block it wrote; coef = grad_loss * logit_scale /
+ * (2 C b) (both DEVICE scalars; grad_loss NULL = 1); P = softmax - onehot of each strip, recomputed and never materialised:
+ *     d_img [b, E]      = coef sum_c P_img,c all_txt_c     (ONE pass: the in-side loop runs over the C sets)     always written
+ *     d_txt [C b, E]    : rows of set c = coef P_txt,c all_img                                                    always written
+ *     d_all_img         = coef sum_c P_txt,c^T txt_c  (one pass), row g at d_all_img + g * ldg                    NULL = skip
+ *     d_all_txt         : set c = coef P_img,c^T img, row g at d_all_txt + c * gset_stride + g * ldg               NULL = skip
+ *     d_scale           = grad_loss / (2 C b) * sum over all 2 C strips of P .* (x . y)   (device scalar)          NULL = skip
+ * ldg / gset_stride follow the rules of ld / set_stride, so the gathered side can be written as one packed [N, (1 + C) E] gradient
+ * for one reduce-scatter (d_all_img = buf, d_all_txt = buf + E, ldg = (1 + C) E, gset_stride = E).  The caller routes the
+ * gathered-side terms as for ov_clip_loss_backward.  E % 32 == 0, E <= 1152 (OV_ERR_UNSUPPORTED otherwise).  Deterministic: no
+ * atomics, the d_scale partials (one per 32-row tile and job) are summed in a fixed order. */
+size_t ov_clip_loss_multi_backward_workspace_bytes(int b, int N, int C);
+int ov_clip_loss_multi_backward(const float* img, const float* txt, const float* all_img, const float* all_txt, int64_t ld,
+                                int64_t set_stride, int b, int N, int E, int C, const float* logit_scale, int label_offset,
+                                const float* terms, const float* grad_loss, float* d_img, float* d_txt, float* d_all_img,
+                                float* d_all_txt, int64_t ldg, int64_t gset_stride, float* d_scale, void* workspace,
+                                size_t workspace_bytes, ov_stream_t stream);
 
 /* SigLIP pairwise sigmoid loss on a local strip (SigLipLoss, loss.py:307-414; the neighbour-exchange ring is replaced by one
  * all-gather of the text features: only the order of the sums differs).

@@ -120,6 +120,13 @@ SIGNATURES = {
     "ov_clip_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p,
                              c_void_p, c_void_p, c_size_t, c_void_p]),
     "ov_clip_loss_backward_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "ov_clip_loss_multi_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "ov_clip_loss_multi": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_int,
+                                   c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "ov_clip_loss_multi_backward_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "ov_clip_loss_multi_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_int, c_void_p,
+                                            c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p,
+                                            c_void_p, c_size_t, c_void_p]),
     "ov_siglip_loss_workspace_bytes": (c_size_t, [c_int, c_int]),
     "ov_siglip_loss": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_size_t,
                                c_void_p]),

@@ -11,6 +11,9 @@ carries the gradient on through the towers.  The gathered-side terms are routed 
 ``gather_features`` does (loss.py:19-63): own chunk only, or summed over ranks (reduce-scatter) with ``gather_with_grad``.
 ``use_horovod`` is rejected (RCCL via torch.distributed is the only transport here).
 
+``MultiCaptionClipLoss`` is the InfoNCE OpenVision trains with: C caption sets per image (src/losses/common.py:120-189, C = 2), the
+mean over the sets of ``ClipLoss(image, text_c)`` in one fused forward and backward (``ov_clip_loss_multi*``) on one packed gather.
+
 ``SigLipLoss`` (loss.py:307-414) is the pairwise sigmoid objective on the same transport: one all-gather of the text features,
 one fused strip kernel (``ov_siglip_loss``), and in the backward the gathered side summed over ranks.
 """
@@ -211,6 +214,172 @@ class _ClipLossFn(torch.autograd.Function):
             tot = torch.cat([d_img + d_all[0], d_txt + d_all[1]], dim=1)          # [N, 2E]: both sides are the global set
             own = _sum_over_ranks_own_chunk(tot, b, rank, mod.group) if mod.gather_with_grad else tot[rank * b:(rank + 1) * b]
             g_img, g_txt = own[:, :e], own[:, e:]
+        dt_i, dt_t, dt_s = ctx.in_dtypes
+        return None, g_img.to(dt_i), g_txt.to(dt_t), d_scale[0].to(dt_s)
+
+
+def pack_caption_features(image_features: torch.Tensor, text_features: torch.Tensor, num_captions: int) -> torch.Tensor:
+    """[b, E] image rows and the stacked [C b, E] text rows (set c in rows c b ...) -> one [b, (1 + C) E] buffer: the image in
+    columns 0 ... E, set c in columns (1 + c) E ...  The layout ``ov_clip_loss_multi`` reads in place after the all-gather."""
+    b = image_features.shape[0]
+    return torch.cat([image_features] + [text_features[c * b:(c + 1) * b] for c in range(num_captions)], dim=1)
+
+
+def unpack_caption_features(packed: torch.Tensor, num_captions: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Inverse of ``pack_caption_features`` on [n, (1 + C) E] rows: ([n, E] image rows, [C n, E] stacked text rows)."""
+    e = packed.shape[1] // (1 + num_captions)
+    return packed[:, :e], torch.cat([packed[:, (1 + c) * e:(2 + c) * e] for c in range(num_captions)], dim=0)
+
+
+def gather_caption_features(image_features: torch.Tensor, text_features: torch.Tensor, num_captions: int, world_size: int,
+                            group=None) -> torch.Tensor:
+    """ONE all_gather_into_tensor of the packed rows -> [world_size * b, (1 + C) E] in rank order (seen by ``record_comm``)."""
+    if not (dist.is_available() and dist.is_initialized()):
+        raise RuntimeError("world_size > 1 needs an initialised torch.distributed process group (caller owns init)")
+    packed = pack_caption_features(image_features.detach().float(), text_features.detach().float(), num_captions).contiguous()
+    return _all_gather_rows(packed, world_size, group)
+
+
+def route_packed_gradient(full: torch.Tensor, b: int, rank: int, gather_with_grad: bool, group=None) -> torch.Tensor:
+    """What reaches this rank's own features from a packed [N, (1 + C) E] gradient of the gathered rows: with ``gather_with_grad``
+    the sum over ranks of rows [rank b, (rank + 1) b) (the backward of the differentiable all-gather: one reduce-scatter), else
+    this rank's own rows of its own gradient (the chunk put back into the detached gather).  Works on CPU tensors over gloo."""
+    if gather_with_grad:
+        return _sum_over_ranks_own_chunk(full, b, rank, group)
+    return full[rank * b:(rank + 1) * b]
+
+
+class MultiCaptionClipLoss(nn.Module):
+    """InfoNCE with ``num_captions`` caption sets per image: what OpenVision trains with (``bidirectional_contrastive_loss``,
+    src/losses/common.py:120-189, two sets, ``local_loss=True``).  ``text_features`` holds the sets stacked ``[C b, E]`` (set c in
+    rows ``c b ...``, the reference's ``ztxt[:half] / ztxt[half:]``); the loss is the mean over the sets of ``ClipLoss(image, text_c)``,
+    computed by one fused forward and one backward (``ov_clip_loss_multi*``): one all-gather of the packed ``[b, (1 + C) E]`` rows
+    read in place, the image-side gradients accumulated over the sets inside the kernel, and under ``gather_with_grad`` one
+    reduce-scatter of the packed gathered-side gradient.  Constructor as ``ClipLoss``, plus ``num_captions`` in front; the
+    reference's ``pmean`` over ranks is left to the gradient averaging, as in ``ClipLoss``."""
+
+    def __init__(self, num_captions: int = 2, local_loss: bool = False, gather_with_grad: bool = False, cache_labels: bool = False,
+                 rank: int = 0, world_size: int = 1, use_horovod: bool = False, group=None):
+        super().__init__()
+        if use_horovod:
+            raise NotImplementedError("horovod transport is not supported; use torch.distributed (RCCL)")
+        if not 1 <= int(num_captions) <= 4:
+            raise ValueError("num_captions must be 1 ... 4")
+        self.num_captions = int(num_captions)
+        self.group = group
+        self.local_loss, self.gather_with_grad, self.cache_labels = local_loss, gather_with_grad, cache_labels
+        self.rank, self.world_size, self.use_horovod = rank, world_size, use_horovod
+        self.always_collective = False   # tests only: take the world_size > 1 path (gather / reduce-scatter) in a world of one rank
+        self._ws: Optional[torch.Tensor] = None
+        self.last_terms: Optional[torch.Tensor] = None     # [4 C, b]: per set lse_img, diag_img, lse_txt, diag_txt
+
+    def _operands(self, img: torch.Tensor, txt: torch.Tensor):
+        """(x_img, x_txt, gathered operand, its image / text views, ld, set_stride, label offset) for this rank."""
+        c, b, e = self.num_captions, img.shape[0], img.shape[1]
+        if not (self.world_size > 1 or self.always_collective):
+            return img, txt, img, txt, e, b * e, 0
+        packed = gather_caption_features(img, txt, c, self.world_size, self.group)
+        if self.local_loss:
+            x_img, x_txt, off = img, txt, b * self.rank
+        else:                       # the global loss on every rank (loss.py:111-113): the local rows are the gathered rows
+            x_img, x_txt = (t.contiguous() for t in unpack_caption_features(packed, c))
+            off = 0
+        return x_img, x_txt, packed, packed[:, e:], (1 + c) * e, e, off
+
+    def _loss_strips(self, x_img, x_txt, all_img, all_txt, ld: int, set_stride: int, scale: torch.Tensor, off: int) -> torch.Tensor:
+        lib = _lib.load()
+        b, e = x_img.shape
+        n = all_img.shape[0]
+        nbytes = lib.ov_clip_loss_multi_workspace_bytes(b, n, self.num_captions)
+        if self._ws is None or self._ws.device != x_img.device or self._ws.numel() < nbytes:
+            self._ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=x_img.device)
+        out = torch.empty(1, dtype=torch.float32, device=x_img.device)
+        terms = torch.empty(4 * self.num_captions, b, dtype=torch.float32, device=x_img.device)
+        check(lib.ov_clip_loss_multi(ptr(x_img), ptr(x_txt), ptr(all_img), ptr(all_txt), ld, set_stride, b, n, e, self.num_captions,
+                                     ptr(scale), int(off), ptr(out), ptr(terms), ptr(self._ws), nbytes, stream_ptr()),
+              "ov_clip_loss_multi")
+        self.last_terms = terms
+        return out[0]
+
+    def _check(self, image_features, text_features):
+        if image_features.dim() != 2 or text_features.dim() != 2 or image_features.shape[1] != text_features.shape[1] \
+                or text_features.shape[0] != self.num_captions * image_features.shape[0]:
+            raise ValueError(f"MultiCaptionClipLoss: text_features must be [{self.num_captions} * b, E] for image_features [b, E], "
+                             f"got {tuple(text_features.shape)} for {tuple(image_features.shape)}")
+        if not (image_features.is_cuda and text_features.is_cuda):
+            raise _lib.OvhipError("MultiCaptionClipLoss: features must live on an MI355X device (no CPU fallback)")
+
+    def forward(self, image_features, text_features, logit_scale, output_dict: bool = False):
+        self._check(image_features, text_features)
+        needs_grad = torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad
+                                                     for t in (image_features, text_features, logit_scale))
+        if needs_grad:
+            if not isinstance(logit_scale, torch.Tensor):
+                logit_scale = torch.tensor(float(logit_scale), device=image_features.device)
+            loss = _MultiCaptionClipLossFn.apply(self, image_features, text_features, logit_scale)
+        else:
+            img, txt = image_features.detach().float().contiguous(), text_features.detach().float().contiguous()
+            scale = ClipLoss._device_scale(logit_scale, img.device)
+            x_img, x_txt, all_img, all_txt, ld, ss, off = self._operands(img, txt)
+            loss = self._loss_strips(x_img, x_txt, all_img, all_txt, ld, ss, scale, off)
+        return {"contrastive_loss": loss} if output_dict else loss
+
+
+class _MultiCaptionClipLossFn(torch.autograd.Function):
+    """MultiCaptionClipLoss as an autograd node.  forward = ov_clip_loss_multi on the packed gather; backward =
+    ov_clip_loss_multi_backward, the gathered side written as one packed [N, (1 + C) E] gradient and routed as ``_ClipLossFn``
+    routes its two halves (own chunk, or one reduce-scatter with gather_with_grad)."""
+
+    @staticmethod
+    def forward(ctx, mod: "MultiCaptionClipLoss", image_features, text_features, logit_scale):
+        img, txt = image_features.detach().float().contiguous(), text_features.detach().float().contiguous()
+        scale = ClipLoss._device_scale(logit_scale, img.device)
+        x_img, x_txt, all_img, all_txt, ld, ss, off = mod._operands(img, txt)
+        loss = mod._loss_strips(x_img, x_txt, all_img, all_txt, ld, ss, scale, off)
+        ctx.mod, ctx.off, ctx.b, ctx.lay = mod, off, img.shape[0], (ld, ss)
+        ctx.multi = mod.world_size > 1 or mod.always_collective
+        ctx.in_dtypes = (image_features.dtype, text_features.dtype, logit_scale.dtype)
+        ctx.save_for_backward(x_img, x_txt, all_img, all_txt, mod.last_terms, scale)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        mod: "MultiCaptionClipLoss" = ctx.mod
+        x_img, x_txt, all_img, all_txt, terms, scale = ctx.saved_tensors
+        lib = _lib.load()
+        c, rank, b = mod.num_captions, mod.rank, ctx.b
+        bx, e = x_img.shape
+        n = all_img.shape[0]
+        ld, ss = ctx.lay
+        single = not ctx.multi                      # world of one without the collectives: both sides are the same tensors
+        gathered_grad = single or not mod.local_loss or mod.gather_with_grad
+        dev = x_img.device
+        d_img, d_txt = torch.empty_like(x_img), torch.empty_like(x_txt)
+        d_scale = torch.empty(1, dtype=torch.float32, device=dev)
+        if not gathered_grad:
+            d_all, p_ai, p_at, ldg, gss = None, None, None, 0, 0
+        elif single:                                # laid out as the features themselves: [b, E] and [C b, E]
+            d_all = torch.empty((1 + c) * n, e, dtype=torch.float32, device=dev)
+            p_ai, p_at, ldg, gss = ptr(d_all), ptr(d_all[n:]), e, n * e
+        else:                                       # packed as the gather: [N, (1 + C) E]
+            d_all = torch.empty(n, (1 + c) * e, dtype=torch.float32, device=dev)
+            p_ai, p_at, ldg, gss = ptr(d_all), ptr(d_all[:, e:]), (1 + c) * e, e
+        grad = grad_out.detach().float().reshape(1).contiguous()        # device scalar: no host round trip
+        nbytes = lib.ov_clip_loss_multi_backward_workspace_bytes(bx, n, c)
+        wsb = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
+        check(lib.ov_clip_loss_multi_backward(ptr(x_img), ptr(x_txt), ptr(all_img), ptr(all_txt), ld, ss, bx, n, e, c, ptr(scale),
+                                              ctx.off, ptr(terms), ptr(grad), ptr(d_img), ptr(d_txt), p_ai, p_at, ldg, gss,
+                                              ptr(d_scale), ptr(wsb), nbytes, stream_ptr()), "ov_clip_loss_multi_backward")
+        if single:
+            g_img, g_txt = d_img + d_all[:n], d_txt + d_all[n:]
+        elif mod.local_loss:
+            g_img, g_txt = d_img, d_txt
+            if mod.gather_with_grad:
+                o_img, o_txt = unpack_caption_features(route_packed_gradient(d_all, b, rank, True, mod.group), c)
+                g_img, g_txt = g_img + o_img, g_txt + o_txt
+        else:                                       # both sides are the global set: [N, (1 + C) E] in all
+            tot = d_all + pack_caption_features(d_img, d_txt, c)
+            g_img, g_txt = unpack_caption_features(route_packed_gradient(tot, b, rank, mod.gather_with_grad, mod.group), c)
         dt_i, dt_t, dt_s = ctx.in_dtypes
         return None, g_img.to(dt_i), g_txt.to(dt_t), d_scale[0].to(dt_s)
 

@@ -578,10 +578,23 @@ def encode_text(model, text: torch.Tensor, normalize: bool = True, output_tokens
     return encode_text_embeddings(model, x, normalize, text.argmax(dim=-1), output_tokens)
 
 
+def caption_sets(image: torch.Tensor, text: torch.Tensor) -> int:
+    """C for an image batch [B, ...] and a token batch [C B, T]: the caption sets per image, stacked set by set (the reference's
+    ``concatenate([labels1, labels2])``, src/main_clip.py:408-411).  Raises unless the text rows are a positive multiple of B."""
+    nb, nt = image.shape[0], text.shape[0]
+    if nb <= 0 or nt < nb or nt % nb:
+        raise ValueError(f"text batch of {nt} rows is not a multiple of the image batch of {nb}: stack C caption sets as [C * B, T]")
+    return nt // nb
+
+
 def clip_forward(model, image: torch.Tensor, text: torch.Tensor) -> Tuple[torch.Tensor, ...]:
     """CLIP.forward (model.py:295-315) with gradients: (image_features, text_features, logit_scale.exp()), and ``logit_bias`` (the
     parameter itself, so its gradient flows) as a fourth element when the model has one (SigLIP).  Patch dropout as in
-    ``encode_image`` (drawn when the vision tower is in training mode with p > 0)."""
+    ``encode_image`` (drawn when the vision tower is in training mode with p > 0).
+
+    ``text`` may stack C caption sets per image as [C B, T]: the text tower runs once on all rows and ``text_features`` is [C B, E],
+    the input of ``MultiCaptionClipLoss(num_captions=C)``."""
+    caption_sets(image, text)
     out = (encode_image(model, image, True), encode_text(model, text, True), model.logit_scale.exp())
     if getattr(model, "logit_bias", None) is not None:
         return out + (model.logit_bias,)
@@ -610,10 +623,22 @@ def coca_forward(model, decoder, image: torch.Tensor, text: torch.Tensor):
     """The reference trainer's 'coca' forward (src/main_clip.py:448-465): both towers once, their features for the contrastive loss
     and their tokens through the caption decoder -> (image_features, text_features, logit_scale.exp(), caption_logits).
 
+    OpenVision's recipe carries two captions per image: ``text`` stacks them as [2 B, T] (src/main_clip.py:408-411), the text tower
+    runs once on all rows, and the decoder sees the first set's tokens only (src/models/two_towers.py:95-98), so ``labels`` and
+    ``mask`` are the first set's:
+
+        img_f, txt_f, scale, cap = training.coca_forward(model, decoder, images, torch.cat([tokens1, tokens2]))
+        loss = MultiCaptionClipLoss(2)(img_f, txt_f, scale) + 2 * CaptionLoss()(cap, labels, mask)
+
+    With one caption per image ([B, T] tokens) it is
+
         img_f, txt_f, scale, cap = training.coca_forward(model, decoder, images, tokens)
         loss = ClipLoss()(img_f, txt_f, scale) + 2 * CaptionLoss()(cap, labels, mask)"""
+    sets = caption_sets(image, text)
     img_f, img_tok = encode_image(model, image, True, output_tokens=True)
     txt_f, txt_tok = encode_text(model, text, True, output_tokens=True)
+    if sets > 1:
+        txt_tok = txt_tok[:image.shape[0]]
     return img_f, txt_f, model.logit_scale.exp(), decode(decoder, img_tok, txt_tok)
 
 

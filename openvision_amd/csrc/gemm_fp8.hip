@@ -119,6 +119,10 @@ __device__ __forceinline__ void epilogue_fp8(const Fp8Args& g, f32x4_t (&acc)[8]
     const char* const rd = img + er * 128 + ((ec ^ er) << 4);
     u32x4_t vo[8][2];
     float lmax = 0.f;
+    // MODE 1: columns of accumulator j still inside N, counted from this lane's first one (N % 4 == 0: the lane's 4 columns of a j are
+    // inside or outside together).  A partial n-tile's columns past N are NOT elements of C -- W row N-1 (clamped DMA) under
+    // colscale / bias [N-4+e] (clamped parameter block) -- and must stay out of the running maximum
+    const int nleft = g.N - (n0 + wn * 64 + fq * 4);
     auto put = [&](int i) {
 #pragma unroll
         for (int it = 0; it < 2; ++it) {
@@ -152,8 +156,9 @@ __device__ __forceinline__ void epilogue_fp8(const Fp8Args& g, f32x4_t (&acc)[8]
                 if (EPI == OV_EPI_BIAS_GELU_TANH) { v01 = gelu_tanh_f2(v01); v23 = gelu_tanh_f2(v23); }
                 if (MODE == 1) {
                     // 4 consecutive n -> 4 e4m3 bytes; image rows are 64 B (16 dwords), chunk ^= (row >> 1) & 3
-                    lmax = fmaxf(fmaxf(lmax, fabsf(v01[0])), fabsf(v01[1]));     // two v_max3_f32 with |x| source modifiers
-                    lmax = fmaxf(fmaxf(lmax, fabsf(v23[0])), fabsf(v23[1]));
+                    float tmax = fmaxf(fmaxf(lmax, fabsf(v01[0])), fabsf(v01[1]));     // two v_max3_f32 with |x| source modifiers
+                    tmax = fmaxf(fmaxf(tmax, fabsf(v23[0])), fabsf(v23[1]));
+                    lmax = j * 16 < nleft ? tmax : lmax;
                     const f32x2_t io = {inv_out, inv_out};
                     v01 *= io; v23 *= io;
                     int pk8 = 0;

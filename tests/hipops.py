@@ -128,22 +128,36 @@ def quantize_rows_e4m3(x):
     return q.view(torch.uint8).contiguous(), scale.contiguous()
 
 
-def gemm_fp8(aq, wq, rowscale, colscale, bias=None, epi=0, resid=None):
+def _out_buf(out, m, n, dtype, fill, device):
+    """The output of an fp8-path wrapper: the caller's buffer (out=, e.g. a column slice of a wider tensor: the pitch is its
+    stride(0)), else a fresh [m, n] tensor holding `fill` (None: uninitialised)."""
+    if out is not None:
+        assert out.shape == (m, n) and out.dtype == dtype and out.stride(1) == 1, (out.shape, out.dtype, out.stride())
+        return out
+    if fill is None:
+        return torch.empty(m, n, dtype=dtype, device=device)
+    return torch.full((m, n), fill, dtype=dtype, device=device)
+
+
+def gemm_fp8(aq, wq, rowscale, colscale, bias=None, epi=0, resid=None, out=None, fill=None):
+    """Operands may be column slices of wider buffers (pitch = stride(0)).  out: a caller's bf16 [m, n] buffer; fill: what a fresh
+    output holds before the launch."""
     lib = _lib.load()
     m, k = aq.shape
     n = wq.shape[0]
-    out = torch.empty(m, n, dtype=torch.bfloat16, device=aq.device)
+    out = _out_buf(out, m, n, torch.bfloat16, fill, aq.device)
     check(lib.ov_gemm_fp8(ptr(aq), aq.stride(0), ptr(wq), wq.stride(0), ptr(rowscale), ptr(colscale),
                           ptr(bias) if bias is not None else None, ptr(out), out.stride(0), m, n, k, epi,
                           ptr(resid) if resid is not None else None, resid.stride(0) if resid is not None else 0, stream_ptr()))
     return out
 
 
-def quant_rows_fp8(x, gamma=None, beta=None, eps=1e-6, amax=None):
-    """bf16 [rows, D] -> (uint8 e4m3 [rows, D], fp32 scales); with gamma/beta: LayerNorm first."""
+def quant_rows_fp8(x, gamma=None, beta=None, eps=1e-6, amax=None, out=None, fill=None):
+    """bf16 [rows, D] -> (uint8 e4m3 [rows, D], fp32 scales); with gamma/beta: LayerNorm first.  x may be a column slice of a wider
+    buffer; out: a caller's uint8 [rows, D] buffer; fill: the byte a fresh output holds before the launch."""
     lib = _lib.load()
     rows, d = x.shape
-    q = torch.empty(rows, d, dtype=torch.uint8, device=x.device)
+    q = _out_buf(out, rows, d, torch.uint8, fill, x.device)
     sc = torch.empty(rows, dtype=torch.float32, device=x.device)
     if gamma is None:
         check(lib.ov_quant_rows_fp8(ptr(x), x.stride(0), ptr(q), q.stride(0), ptr(sc), rows, d,
@@ -154,12 +168,13 @@ def quant_rows_fp8(x, gamma=None, beta=None, eps=1e-6, amax=None):
     return q, sc
 
 
-def gemm_fp8_static(aq, wq, colscale, bias, epi, rowscale=None, in_amax=None, out_amax=None, resid=None, amax_next=None):
-    """out_amax: returns e4m3 bytes [m, n]; in_amax: returns bf16."""
+def gemm_fp8_static(aq, wq, colscale, bias, epi, rowscale=None, in_amax=None, out_amax=None, resid=None, amax_next=None, out=None,
+                    fill=None):
+    """out_amax: returns e4m3 bytes [m, n]; in_amax: returns bf16.  out / fill: as gemm_fp8 (uint8 with out_amax)."""
     lib = _lib.load()
     m, k = aq.shape
     n = wq.shape[0]
-    out = torch.empty(m, n, dtype=torch.uint8 if out_amax is not None else torch.bfloat16, device=aq.device)
+    out = _out_buf(out, m, n, torch.uint8 if out_amax is not None else torch.bfloat16, fill, aq.device)
     check(lib.ov_gemm_fp8_static(ptr(aq), aq.stride(0), ptr(wq), wq.stride(0), ptr(rowscale) if rowscale is not None else None,
                                  ptr(in_amax) if in_amax is not None else None, ptr(colscale), ptr(bias) if bias is not None else None,
                                  ptr(out), out.stride(0), ptr(out_amax) if out_amax is not None else None,
@@ -168,14 +183,21 @@ def gemm_fp8_static(aq, wq, colscale, bias, epi, rowscale=None, in_amax=None, ou
     return out
 
 
-def attention_fp8out(qkv, B, L, Hh, amax, amax_next=None):
-    """head_dim 64; returns e4m3 bytes [B*L, Hh*64] under the static scale 2 * amax / 448."""
+def attention_fp8out(qkv, B, L, Hh, amax, amax_next=None, out=None, fill=None):
+    """head_dim 64; returns e4m3 bytes [B*L, Hh*64] under the static scale 2 * amax / 448.  out / fill: as gemm_fp8 (uint8)."""
     lib = _lib.load()
     d = Hh * 64
-    out = torch.empty(B * L, d, dtype=torch.uint8, device=qkv.device)
+    out = _out_buf(out, B * L, d, torch.uint8, fill, qkv.device)
     check(lib.ov_attention_fp8out(ptr(qkv), qkv.stride(0), ptr(out), out.stride(0), B, L, Hh, 64, 0.125, ptr(amax),
                                   ptr(amax_next) if amax_next is not None else None, stream_ptr()))
     return out
+
+
+def amax_roll(cur, next):
+    """ov_amax_roll: cur[i] = max(cur[i], next[i]) for i < len(next), in place; returns cur."""
+    lib = _lib.load()
+    check(lib.ov_amax_roll(ptr(cur), ptr(next), next.numel(), stream_ptr()), "ov_amax_roll")
+    return cur
 
 
 def clip_loss_backward(img, txt, all_img, all_txt, scale, label_offset, terms, grad=1.0, gathered=True):

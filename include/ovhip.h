@@ -12,6 +12,7 @@
  *   ov_im2col_patches   conv1 (stride = kernel = P) operand gather            transformer.py:469,610-612
  *   ov_cls_rows         class_embedding concat + pos-emb row 0                transformer.py:615-617
  *   ov_mean_pool        _global_pool 'avg' / 'tok'                            transformer.py:599-603
+ *   ov_mlp_out_pooled   _global_pool 'avg' of the last block's output, through its c_proj   transformer.py:264,599-603
  *   ov_text_embed       token_embedding(text) + positional_embedding         model.py:272-274
  *   ov_gather_rows      text_global_pool 'last' / 'first'                     transformer.py:655-658
  *   ov_l2norm           F.normalize(x, dim=-1)                                model.py:267,284
@@ -184,6 +185,15 @@ int ov_cls_rows(ov_bf16* x, int64_t ldx, const float* cls, const float* pos0, in
 /* out[b,:] = mean over tokens first..L-1 of x[b*L + t, :]  (first = 1: skip cls; 'avg' pooling). fp32 out. */
 int ov_mean_pool(const ov_bf16* x, int64_t ldx, float* out, int B, int L, int D, int first,
                  ov_stream_t stream);
+
+/* The mean over tokens first..L-1 of a block's output x1 + hid . W^T + bias, without forming that output (the mean commutes with the
+ * linear layer):  out[b, :] = mean_t x1[b*L + t, :] + (mean_t hid[b*L + t, :]) . W^T + bias,  fp32 [B, D], accumulated in fp32 from the
+ * bf16 inputs (exact-fp32 MFMA) and never rounded to bf16.  x1 [B*L, D] (pitch ldx), hid [B*L, F] (pitch ldh), W [D, F] (pitch ldw) bf16,
+ * bias fp32 [D].  F % 32 == 0.  Workspace: the pooled hidden, fp32 [B, F].  out is written by the pooling pass first and then
+ * read-modify-written by the product, so it must not overlap the workspace (or any input). */
+size_t ov_mlp_out_pooled_workspace_bytes(int B, int F);
+int ov_mlp_out_pooled(const ov_bf16* x1, int64_t ldx, const ov_bf16* hid, int64_t ldh, const ov_bf16* W, int64_t ldw, const float* bias,
+                      float* out, int B, int L, int D, int F, int first, void* workspace, size_t workspace_bytes, ov_stream_t stream);
 
 /* x[b*T + t, :] = bf16(bf16(table[tokens[b,t], :]) + bf16(pos[t, :])).  tokens int64; table/pos bf16.
  * Token ids outside [0, V) set *err_flag (device int, may be NULL) and are clamped. */

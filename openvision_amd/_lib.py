@@ -106,6 +106,9 @@ SIGNATURES = {
     "ov_col2im_patches_keep": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "ov_cls_rows": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "ov_mean_pool": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "ov_mlp_out_pooled_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "ov_mlp_out_pooled": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                  c_int, c_void_p, c_size_t, c_void_p]),
     "ov_text_embed": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p,
                               c_void_p]),
     "ov_gather_rows": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p]),

@@ -258,6 +258,50 @@ __global__ __launch_bounds__(256) void mean_pool_kernel(const ov_bf16* __restric
     }
 }
 
+// out[b, n] += <A[b, :], W[n, :]> + bias[n]: fp32 rows against a bf16 weight widened exactly, in the exact-fp32 MFMA (k-ordered fmaf
+// chain, as logits_kernel).  One workgroup per 32x32 tile; its four waves take a quarter of K each and are summed through LDS in wave
+// order, so a row's result depends on that row alone and on nothing that varies between launches.
+__global__ __launch_bounds__(256) void pooled_linear_kernel(const float* __restrict__ A, const ov_bf16* __restrict__ W, int64_t ldw,
+                                                            const float* __restrict__ bias, float* __restrict__ out, int B, int N,
+                                                            int K) {
+    __shared__ float red[4][16][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int j = lane & 31, half = lane >> 5;
+    const int i0 = blockIdx.y * 32, j0 = blockIdx.x * 32;
+    const int ai = (i0 + j) < B ? (i0 + j) : B - 1;
+    const int wj = (j0 + j) < N ? (j0 + j) : N - 1;
+    const int kq = K >> 2;
+    const float* ap = A + (int64_t)ai * K + wave * kq + 4 * half;
+    const ov_bf16* wp = W + (int64_t)wj * ldw + wave * kq + 4 * half;
+    f32x16_t acc;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+#pragma unroll 4
+    for (int k0 = 0; k0 < kq; k0 += 8) {
+        const u32x2_t wv = *(const u32x2_t*)(wp + k0);
+        const float4 av = *(const float4*)(ap + k0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(bf16lo_to_f32(wv[0]), av.x, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(bf16hi_to_f32(wv[0]), av.y, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(bf16lo_to_f32(wv[1]), av.z, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(bf16hi_to_f32(wv[1]), av.w, acc, 0, 0, 0);
+    }
+    // acc[i] = <W[j0 + (i&3) + 8*(i>>2) + 4*half], A[i0 + j]> over this wave's quarter of K
+#pragma unroll
+    for (int i = 0; i < 16; ++i) red[wave][i][lane] = acc[i];
+    __syncthreads();
+    if (wave == 0 && i0 + j < B) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int col = j0 + (i & 3) + 8 * (i >> 2) + 4 * half;
+            if (col < N) {
+                const float s = ((red[0][i][lane] + red[1][i][lane]) + red[2][i][lane]) + red[3][i][lane];
+                float* o = out + (int64_t)(i0 + j) * N + col;
+                *o = *o + (s + bias[col]);
+            }
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void text_embed_kernel(const int64_t* __restrict__ tokens, const ov_bf16* __restrict__ table,
                                                          const ov_bf16* __restrict__ pos, ov_bf16* __restrict__ x, int64_t ldx,
                                                          int T, int D, int V, int* __restrict__ err, int64_t total) {
@@ -393,6 +437,27 @@ extern "C" int ov_mean_pool(const ov_bf16* x, int64_t ldx, float* out, int B, in
     if (D % 8 || ldx % 8 || ldx < D || (((uintptr_t)x | (uintptr_t)out) & 15)) return OV_ERR_INVALID;
     hipLaunchKernelGGL(mean_pool_kernel, dim3((unsigned)B, (unsigned)((D / 8 + 63) / 64)), dim3(256), 0, (hipStream_t)stream, x,
                        ldx, out, L, D, first);
+    OV_LAUNCH_CHECK();
+    return OV_OK;
+}
+
+extern "C" size_t ov_mlp_out_pooled_workspace_bytes(int B, int F) {
+    return B > 0 && F > 0 ? (size_t)B * F * 4 : 0;
+}
+
+// The mean commutes with c_proj: two pooling passes and a [B, F] x [D, F]^T product, all fp32 past the bf16 inputs.
+extern "C" int ov_mlp_out_pooled(const ov_bf16* x1, int64_t ldx, const ov_bf16* hid, int64_t ldh, const ov_bf16* W, int64_t ldw,
+                                 const float* bias, float* out, int B, int L, int D, int F, int first, void* workspace,
+                                 size_t workspace_bytes, ov_stream_t stream) {
+    if (!x1 || !hid || !W || !bias || !out || !workspace || B <= 0 || L <= 0 || D <= 0 || F <= 0) return OV_ERR_INVALID;
+    if (F % 32 || ldw % 8 || ldw < F || (((uintptr_t)W | (uintptr_t)workspace | (uintptr_t)bias) & 15)) return OV_ERR_INVALID;
+    if (workspace_bytes < ov_mlp_out_pooled_workspace_bytes(B, F)) return OV_ERR_WORKSPACE;
+    float* mean_h = (float*)workspace;
+    int rc;
+    if ((rc = ov_mean_pool(x1, ldx, out, B, L, D, first, stream))) return rc;
+    if ((rc = ov_mean_pool(hid, ldh, mean_h, B, L, F, first, stream))) return rc;
+    hipLaunchKernelGGL(pooled_linear_kernel, dim3((unsigned)((D + 31) / 32), (unsigned)((B + 31) / 32)), dim3(256), 0,
+                       (hipStream_t)stream, mean_h, W, ldw, bias, out, B, D, F);
     OV_LAUNCH_CHECK();
     return OV_OK;
 }

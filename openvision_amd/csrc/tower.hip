@@ -333,8 +333,11 @@ struct Fp8Scales { float *h_amax, *a_amax, *h_next, *a_next; int h_mode; };
 // -- so mask 0 is the bf16 block.  In front of an fp8 QKV / c_fc the LayerNorm is fused with the row quantisation; in front of an fp8
 // out_proj / c_proj the attention output / MLP hidden is written as e4m3 by its producer where that producer has a static scale
 // (h_mode >= 2: attention epilogue for head_dim 64, an fp8 c_fc's epilogue) and re-quantised row by row otherwise.
+// stop (bf16 blocks only, mask 0): where a block whose token output nobody reads ends -- BLOCK_TO_ATTN after the attention (its output in
+// p.h, x untouched), BLOCK_TO_FC after c_fc (x = the stream after out-proj, the MLP hidden in p.big).
+enum BlockStop { BLOCK_FULL = 0, BLOCK_TO_ATTN = 1, BLOCK_TO_FC = 2 };
 int run_block(const ov_tower_cfg& c, const ov_block_weights& w, const ov_block_fp8* q, int mask, const Fp8Scales& sc, const BlockPart& p,
-              bool parts_in, int L, int prefix) {
+              bool parts_in, int L, int prefix, int stop = BLOCK_FULL) {
     const int D = c.width, H = c.heads, hd = D / H, F = c.mlp_pad, B = p.B;
     const int64_t M = (int64_t)B * L;
     const int ldb = big_pitch(c);                               // row pitch of `big` (shared by qkv and the MLP hidden)
@@ -375,6 +378,7 @@ int run_block(const ov_tower_cfg& c, const ov_block_weights& w, const ov_block_f
     } else {
         if (prefix >= 0) OV_STEP(OV_PROF_ATTN, ov_attention_prefix(big, ldb, h, D, B, L, H, hd, scale, prefix, stream));
         else OV_STEP(OV_PROF_ATTN, ov_attention(big, ldb, h, D, B, L, H, hd, scale, stream));
+        if (stop == BLOCK_TO_ATTN) return OV_OK;
         if (f_out) {
             OV_STEP(OV_PROF_LN, ov_quant_rows_fp8(h, D, q8, D, qs, M, D, sc.h_mode == 1 ? sc.a_amax : nullptr, stream));
             OV_STEP(OV_PROF_GEMM_OUT, ov_gemm_fp8(q8, D, q->out_w8, D, qs, q->out_s, w.out_b, x, D, M, D, D, OV_EPI_BIAS_RESIDUAL, x, D, stream));
@@ -404,6 +408,7 @@ int run_block(const ov_tower_cfg& c, const ov_block_weights& w, const ov_block_f
         if (f_fc) OV_STEP(fc_cls, ov_gemm_fp8(q8, D, q->fc_w8, D, qs, q->fc_s, q->fc_b, big, ldb, M, F, D, gelu, nullptr, 0, stream));
         else if (fold) OV_STEP(fc_cls, ov_gemm_ln(x, D, w.fc_w, D, w.fc_b, w.fc_colsum, stats, big, ldb, M, F, D, gelu, stream));
         else OV_STEP(fc_cls, ov_gemm(h, D, w.fc_w, D, w.fc_b, big, ldb, M, F, D, gelu, nullptr, 0, 0, 0, 0, stream));
+        if (stop == BLOCK_TO_FC) return OV_OK;
         if (f_proj) {
             OV_STEP(OV_PROF_LN, ov_quant_rows_fp8(big, ldb, q8, F, qs, M, F, (sc.h_mode == 1 && f_fc) ? sc.h_amax : nullptr, stream));
             OV_STEP(OV_PROF_GEMM_PROJ, ov_gemm_fp8(q8, F, q->proj_w8, F, qs, q->proj_s, w.proj_b, x, D, M, D, F, OV_EPI_BIAS_RESIDUAL, x, D, stream));
@@ -455,8 +460,9 @@ int tail_images(int B, int L) {
 // image(s) are peeled off and run, layer by layer, on an internal side stream: rows are independent through LN/GEMM and
 // attention never crosses images, so the split is exact; the main part then fills whole rounds and the tail's small
 // kernels slot into idle CUs.  Fork/join by events; everything remains ordered with respect to the caller's stream.
-extern "C" int ov_tower_forward(const ov_tower* t, ov_bf16* x, int B, int L, void* workspace, size_t workspace_bytes,
-                                ov_stream_t stream) {
+// last_stop: where the LAST block ends (BlockStop; anything but BLOCK_FULL needs a bf16 tower, and leaves that block to the caller).
+static int tower_walk(const ov_tower* t, ov_bf16* x, int B, int L, void* workspace, size_t workspace_bytes, ov_stream_t stream,
+                      int last_stop) {
     if (!t || !x || !workspace || B <= 0 || L <= 0) return OV_ERR_INVALID;
     if (workspace_bytes < ov_tower_workspace_bytes(t, B, L)) return OV_ERR_WORKSPACE;
     if (((uintptr_t)x | (uintptr_t)workspace) & 15) return OV_ERR_INVALID;
@@ -486,6 +492,7 @@ extern "C" int ov_tower_forward(const ov_tower* t, ov_bf16* x, int B, int L, voi
     const int64_t off = (int64_t)Bm * L;
     const bool fp8 = tower_fp8(t);
     if (t->prefix >= 0 && fp8) return OV_ERR_UNSUPPORTED;          // no fp8 under a mask
+    if (last_stop != BLOCK_FULL && fp8) return OV_ERR_UNSUPPORTED;
     if (t->prefix > L) return OV_ERR_INVALID;
     int rc = OV_OK;
     if (fp8 && t->h_amax && t->h_mode == 2)            // delayed scaling: last forward's maxima become this forward's scales
@@ -503,8 +510,9 @@ extern "C" int ov_tower_forward(const ov_tower* t, ov_bf16* x, int B, int L, voi
         if (t->h_amax) sc = {t->h_amax + i, t->h_amax + c.layers + i, t->h_amax + 2 * c.layers + i, t->h_amax + 3 * c.layers + i, t->h_mode};
         const ov_block_fp8* q = fp8 ? &t->fp8[i] : nullptr;
         const int mask = fp8 ? t->mask8[i] : 0;
-        rc = run_block(c, t->blocks[i], q, mask, sc, main_part, i > 0, L, t->prefix);
-        if (rc == OV_OK && nt > 0) rc = run_block(c, t->blocks[i], q, mask, sc, tail_part, i > 0, L, t->prefix);
+        const int stop = i == c.layers - 1 ? last_stop : BLOCK_FULL;
+        rc = run_block(c, t->blocks[i], q, mask, sc, main_part, i > 0, L, t->prefix, stop);
+        if (rc == OV_OK && nt > 0) rc = run_block(c, t->blocks[i], q, mask, sc, tail_part, i > 0, L, t->prefix, stop);
     }
     if (nt > 0) {
         // always join, also after an error between fork and here: whatever the side stream got stays ordered before the
@@ -514,6 +522,18 @@ extern "C" int ov_tower_forward(const ov_tower* t, ov_bf16* x, int B, int L, voi
         if (e != hipSuccess && rc == OV_OK) rc = OV_ERR_HIP - (int)e;
     }
     return rc;
+}
+
+extern "C" int ov_tower_forward(const ov_tower* t, ov_bf16* x, int B, int L, void* workspace, size_t workspace_bytes,
+                                ov_stream_t stream) {
+    return tower_walk(t, x, B, L, workspace, workspace_bytes, stream, BLOCK_FULL);
+}
+
+// OVHIP_LAST_BLOCK_FULL=1: ov_encode_image / ov_encode_text run the last block in full, as ov_tower_forward does (A/B and tests).
+static inline bool last_block_full() {
+    static int v = -1;
+    if (v < 0) { const char* e = getenv("OVHIP_LAST_BLOCK_FULL"); v = (e && e[0] == '1') ? 1 : 0; }
+    return v != 0;
 }
 
 // ---- training-side entry points: keep every block's input, run the blocks' backward in reverse -------------
@@ -848,28 +868,77 @@ extern "C" int ov_vision_head_forward(const ov_tower* t, const ov_vision_head* h
     return ov_vision_head_forward_tokens(t, h, x, B, g * g + 1, features, normalize, workspace, workspace_bytes, stream);
 }
 
-extern "C" int ov_vision_head_forward_tokens(const ov_tower* t, const ov_vision_head* h, const ov_bf16* x, int B, int L, float* features,
-                                             int normalize, void* workspace, size_t workspace_bytes, ov_stream_t stream) {
-    if (!t || !h || !x || !features || !workspace || B <= 0 || L < 2) return OV_ERR_INVALID;
+namespace {
+// The head's workspace (pooled fp32 [B, D] | ln_post rows | projected rows) and its part past the pooling.
+struct HeadBufs { float* pooled; ov_bf16 *ln, *feat; };
+int head_bufs(const ov_tower* t, const ov_vision_head* h, int B, void* workspace, size_t workspace_bytes, HeadBufs* hb) {
     const int D = t->cfg.width, E = h->embed_dim, EP = h->embed_pad;
     if (EP % 8 || EP < E) return OV_ERR_INVALID;
     if (!h->final_ln_after_pool) return OV_ERR_UNSUPPORTED;       // OpenVision: pool -> LN (transformer.py:638-640)
     const size_t o_pooled = 0, o_ln = align_up((size_t)B * D * 4, 256), o_feat = o_ln + align_up((size_t)B * D * 2, 256);
     if (workspace_bytes < o_feat + (size_t)B * EP * 2) return OV_ERR_WORKSPACE;
-    float* pooled = (float*)((char*)workspace + o_pooled);
-    ov_bf16* ln = (ov_bf16*)((char*)workspace + o_ln);
-    ov_bf16* feat = (ov_bf16*)((char*)workspace + o_feat);
+    hb->pooled = (float*)((char*)workspace + o_pooled);
+    hb->ln = (ov_bf16*)((char*)workspace + o_ln);
+    hb->feat = (ov_bf16*)((char*)workspace + o_feat);
+    return OV_OK;
+}
+// ln_post of the pooled rows (pooled = true; else hb.ln is filled already) -> @ proj (-> F.normalize)
+int head_finish(const ov_tower* t, const ov_vision_head* h, const HeadBufs& hb, bool pooled, int B, float* features, int normalize,
+                ov_stream_t stream) {
+    const int D = t->cfg.width, E = h->embed_dim, EP = h->embed_pad;
     int rc;
+    if (pooled && (rc = ov_layernorm(hb.pooled, OV_F32, D, h->ln_post_w, h->ln_post_b, hb.ln, OV_BF16, D, B, D, t->cfg.ln_eps, stream)))
+        return rc;
+    if ((rc = ov_gemm(hb.ln, D, h->proj_t, D, nullptr, hb.feat, EP, B, EP, D, OV_EPI_BIAS, nullptr, 0, 0, 0, 0, stream))) return rc;
+    if (normalize) return ov_l2norm(hb.feat, OV_BF16, EP, features, E, B, E, stream);
+    return ov_convert(hb.feat, OV_BF16, EP, features, OV_F32, E, B, E, stream);
+}
+}  // namespace
+
+extern "C" int ov_vision_head_forward_tokens(const ov_tower* t, const ov_vision_head* h, const ov_bf16* x, int B, int L, float* features,
+                                             int normalize, void* workspace, size_t workspace_bytes, ov_stream_t stream) {
+    if (!t || !h || !x || !features || !workspace || B <= 0 || L < 2) return OV_ERR_INVALID;
+    const int D = t->cfg.width;
+    HeadBufs hb;
+    int rc;
+    if ((rc = head_bufs(t, h, B, workspace, workspace_bytes, &hb))) return rc;
     if (h->pool_avg) {
-        if ((rc = ov_mean_pool(x, D, pooled, B, L, D, 1, stream))) return rc;
-        if ((rc = ov_layernorm(pooled, OV_F32, D, h->ln_post_w, h->ln_post_b, ln, OV_BF16, D, B, D, t->cfg.ln_eps, stream))) return rc;
+        if ((rc = ov_mean_pool(x, D, hb.pooled, B, L, D, 1, stream))) return rc;
     } else {
-        if ((rc = ov_layernorm(x, OV_BF16, (int64_t)L * D, h->ln_post_w, h->ln_post_b, ln, OV_BF16, D, B, D, t->cfg.ln_eps, stream)))
+        if ((rc = ov_layernorm(x, OV_BF16, (int64_t)L * D, h->ln_post_w, h->ln_post_b, hb.ln, OV_BF16, D, B, D, t->cfg.ln_eps, stream)))
             return rc;
     }
-    if ((rc = ov_gemm(ln, D, h->proj_t, D, nullptr, feat, EP, B, EP, D, OV_EPI_BIAS, nullptr, 0, 0, 0, 0, stream))) return rc;
-    if (normalize) return ov_l2norm(feat, OV_BF16, EP, features, E, B, E, stream);
-    return ov_convert(feat, OV_BF16, EP, features, OV_F32, E, B, E, stream);
+    return head_finish(t, h, hb, h->pool_avg != 0, B, features, normalize, stream);
+}
+
+// The blocks and the head of ov_encode_image / ov_encode_image_keep on the embedded tokens x [B, L, D].
+// avg pooling reads the last block's output through its mean over the patch tokens alone, and the mean commutes with c_proj: the last
+// block stops after c_fc, and ov_mlp_out_pooled forms mean(x1) + mean(hidden) . W2^T + b in fp32 on B rows (the pooled hidden in the
+// tower workspace's h region, free once c_fc has run) -- closer to the unrounded mean than the mean of L bf16-rounded token rows.
+// bf16 towers under pool -> LN; everything else runs the full block.
+static int blocks_and_head(const ov_tower* t, const ov_vision_head* h, ov_bf16* x, int B, int L, char* tower_ws, size_t tower_bytes,
+                           char* head_ws, size_t head_bytes, float* features, int normalize, ov_stream_t stream) {
+    const ov_tower_cfg& c = t->cfg;
+    const int D = c.width, F = c.mlp_pad;
+    const size_t h_bytes = align_up((size_t)B * L * D * 2, 256);            // the workspace's h region, in front of big
+    const bool pooled_tail = !last_block_full() && h->pool_avg && h->final_ln_after_pool && L >= 2 && !tower_fp8(t) && F % 32 == 0 &&
+                             ov_mlp_out_pooled_workspace_bytes(B, F) <= h_bytes;
+    int rc;
+    if (!pooled_tail) {
+        if ((rc = ov_tower_forward(t, x, B, L, tower_ws, tower_bytes, stream))) return rc;
+        return ov_vision_head_forward_tokens(t, h, x, B, L, features, normalize, head_ws, head_bytes, stream);
+    }
+    HeadBufs hb;
+    if ((rc = head_bufs(t, h, B, head_ws, head_bytes, &hb))) return rc;
+    if ((rc = tower_walk(t, x, B, L, tower_ws, tower_bytes, stream, BLOCK_TO_FC))) return rc;
+    const ov_block_weights& lw = t->blocks[c.layers - 1];
+    const ov_bf16* hidden = (const ov_bf16*)(tower_ws + h_bytes);
+    {   // in-situ profile: the pooled c_proj counts as the c_proj class, with the B rows it produces
+        ProfScope ps(OV_PROF_GEMM_PROJ, stream, B);
+        rc = ov_mlp_out_pooled(x, D, hidden, big_pitch(c), lw.proj_w, F, lw.proj_b, hb.pooled, B, L, D, F, 1, tower_ws, h_bytes, stream);
+    }
+    if (rc) return rc;
+    return head_finish(t, h, hb, true, B, features, normalize, stream);
 }
 
 extern "C" int ov_encode_image(const ov_tower* t, const ov_vision_head* h, const void* image, int img_dtype, int B,
@@ -885,8 +954,7 @@ extern "C" int ov_encode_image(const ov_tower* t, const ov_vision_head* h, const
     // the im2col buffer aliases the (not yet used) tower workspace
     if ((size_t)B * g * g * h->kpad * 2 > tower_bytes) return OV_ERR_WORKSPACE;
     if ((rc = ov_vision_embed(t, h, image, img_dtype, B, x, ws + w.tower, tower_bytes, stream))) return rc;
-    if ((rc = ov_tower_forward(t, x, B, L, ws + w.tower, tower_bytes, stream))) return rc;
-    return ov_vision_head_forward(t, h, x, B, features, normalize, ws + w.pooled, w.total - w.pooled, stream);
+    return blocks_and_head(t, h, x, B, L, ws + w.tower, tower_bytes, ws + w.pooled, w.total - w.pooled, features, normalize, stream);
 }
 
 int ov_im2col_patches_keep_pos(const void* image, int img_dtype, const int* keep, ov_bf16* out, int B, int S, int P, int K, int Kpad,
@@ -932,6 +1000,10 @@ extern "C" int ov_encode_image_keep(const ov_tower* t, const ov_vision_head* h, 
     ov_bf16* x = (ov_bf16*)(ws + w.x);
     int rc;
     if ((rc = ov_vision_embed_keep(t, h, image, img_dtype, keep, B, K, x, err_flag, ws + w.tower, w.pooled - w.tower, stream))) return rc;
+    // Patches dropped (the training-mode forward): the full block, so that the pooled output stays bitwise what the head makes of the
+    // token stream (output_tokens).  K = G drops nothing and is ov_encode_image on reordered patches: it takes that entry point's tail.
+    if (K == g * g)
+        return blocks_and_head(t, h, x, B, L, ws + w.tower, w.pooled - w.tower, ws + w.pooled, w.total - w.pooled, features, normalize, stream);
     if ((rc = ov_tower_forward(t, x, B, L, ws + w.tower, w.pooled - w.tower, stream))) return rc;
     return ov_vision_head_forward_tokens(t, h, x, B, L, features, normalize, ws + w.pooled, w.total - w.pooled, stream);
 }
@@ -954,9 +1026,48 @@ extern "C" int ov_encode_text(const ov_tower* t, const ov_text_head* h, const in
     ov_bf16* feat = (ov_bf16*)(ws + w.feat);
     int rc;
     if ((rc = ov_text_embed(tokens, h->token_embedding, h->pos, x, D, B, T, D, h->vocab_size, err_flag, stream))) return rc;
-    if ((rc = ov_tower_forward(t, x, B, T, ws + w.tower, ov_tower_workspace_bytes(t, B, T), stream))) return rc;
-    // ln_final is per-token, so only the pooled row needs it (model.py:276-277)
-    if ((rc = ov_gather_rows(x, D, last, D, B, T, h->pool_last ? T - 1 : 0, D, stream))) return rc;
+    const size_t tower_bytes = ov_tower_workspace_bytes(t, B, T);
+    const int row = h->pool_last ? T - 1 : 0;
+    const ov_tower_cfg& c = t->cfg;
+    const int F = c.mlp_pad;
+    // Past the last block's attention only the pooled row of each caption is read: out-proj, LN2, c_fc and c_proj of that block run on
+    // the B gathered rows (same GEMM entry points, and a GEMM row does not depend on the kernel form that computes it).  Their buffers
+    // (attention rows | LN2 rows | hidden | row statistics) lie in the workspace's big region, free once the attention has read qkv.
+    const size_t o_n = align_up((size_t)B * D * 2, 256), o_hid = 2 * o_n, o_stats = o_hid + align_up((size_t)B * F * 2, 256);
+    const size_t h_bytes = align_up((size_t)B * T * D * 2, 256), big_bytes = align_up((size_t)B * T * big_pitch(c) * 2, 256);
+    if (last_block_full() || tower_fp8(t) || o_stats + (size_t)B * 8 > big_bytes) {
+        if ((rc = ov_tower_forward(t, x, B, T, ws + w.tower, tower_bytes, stream))) return rc;
+        // ln_final is per-token, so only the pooled row needs it (model.py:276-277)
+        if ((rc = ov_gather_rows(x, D, last, D, B, T, row, D, stream))) return rc;
+    } else {
+        if ((rc = tower_walk(t, x, B, T, ws + w.tower, tower_bytes, stream, BLOCK_TO_ATTN))) return rc;
+        const ov_block_weights& lw = t->blocks[c.layers - 1];
+        const ov_bf16* attn = (const ov_bf16*)(ws + w.tower);
+        char* big = ws + w.tower + h_bytes;
+        ov_bf16 *a = (ov_bf16*)big, *n = (ov_bf16*)(big + o_n), *hid = (ov_bf16*)(big + o_hid);
+        float* stats = (float*)(big + o_stats);
+        const int gelu = c.gelu_tanh ? OV_EPI_BIAS_GELU_TANH : OV_EPI_BIAS_GELU_ERF;
+        // in-situ profile: each launch under the class of the full block's launch it replaces, with its B rows (the gathers with the
+        // out-proj they feed)
+#define OV_TAIL_STEP(cls, call)                                    \
+        do {                                                       \
+            { ProfScope ps__(cls, stream, B); rc = (call); }       \
+            if (rc) return rc;                                     \
+        } while (0)
+        const int fc_cls = c.gelu_tanh ? OV_PROF_GEMM_FC_TANH : OV_PROF_GEMM_FC;
+        if ((rc = ov_gather_rows(attn, D, a, D, B, T, row, D, stream))) return rc;
+        if ((rc = ov_gather_rows(x, D, last, D, B, T, row, D, stream))) return rc;
+        OV_TAIL_STEP(OV_PROF_GEMM_OUT, ov_gemm(a, D, lw.out_w, D, lw.out_b, last, D, B, D, D, OV_EPI_BIAS_RESIDUAL, last, D, 0, 0, 0, stream));
+        if (lw.fc_colsum) {
+            OV_TAIL_STEP(OV_PROF_LN, ov_rowstats(last, D, stats, B, D, c.ln_eps, stream));
+            OV_TAIL_STEP(fc_cls, ov_gemm_ln(last, D, lw.fc_w, D, lw.fc_b, lw.fc_colsum, stats, hid, F, B, F, D, gelu, stream));
+        } else {
+            OV_TAIL_STEP(OV_PROF_LN, ov_layernorm(last, OV_BF16, D, lw.ln2_w, lw.ln2_b, n, OV_BF16, D, B, D, c.ln_eps, stream));
+            OV_TAIL_STEP(fc_cls, ov_gemm(n, D, lw.fc_w, D, lw.fc_b, hid, F, B, F, D, gelu, nullptr, 0, 0, 0, 0, stream));
+        }
+        OV_TAIL_STEP(OV_PROF_GEMM_PROJ, ov_gemm(hid, F, lw.proj_w, F, lw.proj_b, last, D, B, D, F, OV_EPI_BIAS_RESIDUAL, last, D, 0, 0, 0, stream));
+#undef OV_TAIL_STEP
+    }
     if ((rc = ov_layernorm(last, OV_BF16, D, h->ln_final_w, h->ln_final_b, ln, OV_BF16, D, B, D, t->cfg.ln_eps, stream))) return rc;
     if ((rc = ov_gemm(ln, D, h->proj_t, D, nullptr, feat, EP, B, EP, D, OV_EPI_BIAS, nullptr, 0, 0, 0, 0, stream))) return rc;
     if (normalize) return ov_l2norm(feat, OV_BF16, EP, features, E, B, E, stream);

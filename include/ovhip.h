@@ -19,6 +19,7 @@
  *   ov_logits           CLIP.get_logits (scale * img @ txt^T)                 model.py:286-293
  *   ov_clip_loss        ClipLoss.get_logits + cross_entropy both ways         loss.py:102-131
  *   ov_clip_loss_multi  bidirectional_contrastive_loss, C caption sets        src/losses/common.py:120-189
+ *   ov_distill_loss     DistillClipLoss: InfoNCE + teacher-softmax cross entropy   loss.py:180-216
  *   ov_siglip_loss      SigLipLoss._loss summed over every text block          loss.py:307-414
  *   ov_gemm_fp8         the same nn.Linear on fp8 e4m3 operands (config #5)           transformer.py:225,232-236
  *   ov_preprocess_image transforms.Resize -> ToTensor -> Normalize (Pillow-exact)  ov-zero-shot-test.py:72-77, transform.py:355-392
@@ -338,6 +339,52 @@ int ov_clip_loss_multi_backward(const float* img, const float* txt, const float*
                                 const float* terms, const float* grad_loss, float* d_img, float* d_txt, float* d_all_img,
                                 float* d_all_txt, int64_t ldg, int64_t gset_stride, float* d_scale, void* workspace,
                                 size_t workspace_bytes, ov_stream_t stream);
+
+/* Distillation from a frozen teacher (DistillClipLoss, loss.py:180-216): the student's InfoNCE and, per direction, the cross
+ * entropy of the student's log-softmax under the teacher's softmax, in one forward and one backward.
+ *   img, txt        : the student's local embeddings [b, E] fp32, contiguous
+ *   all_img/all_txt : the student's gathered embeddings, N rows of E floats, row g at base + g * ld
+ *   t_img, t_txt    : the teacher's local embeddings [b, Et] fp32, contiguous (Et may differ from E)
+ *   t_all_img/t_all_txt: the teacher's gathered embeddings, N rows of Et floats, row g at base + g * ldt
+ *                     (the all-gather's packed [N, 2E + 2Et] buffer in place: all_img = buf, all_txt = buf + E, t_all_img = buf + 2E,
+ *                      t_all_txt = buf + 2E + Et, ld = ldt = 2E + 2Et;  separate arrays: ld = E, ldt = Et;  N == b without a gather:
+ *                      the gathered operands are the local ones)
+ *   logit_scale, t_logit_scale: DEVICE scalars s and st, the two multipliers;  labels are i + label_offset
+ *   with A = s img all_txt^T, T = st t_img t_all_txt^T, Q = softmax(T, dim=1) (and B, U, R likewise from txt, all_img, t_txt, t_all_img):
+ *   contrastive_out[0] = 1 / (2 b) sum_i [ lse(A_i) - A[i, i + off] + lse(B_i) - B[i, i + off] ]        (= ov_clip_loss's value)
+ *   distill_out[0]     = 1 / (2 b) sum_i [ lse(A_i) - sum_j Q_ij A_ij + lse(B_i) - sum_j R_ij B_ij ]    (fp32, device)
+ *   terms_out (required): [12, b] fp32.  Rows 0 ... 3 = the student's lse_img, diag_img, lse_txt, diag_txt, as ov_clip_loss defines
+ *                     them; row 4 = the teacher's lse of T, row 5 = sum_j Q_ij A_ij, row 6 = the teacher's lse of U, row 7 = sum_j R_ij B_ij;
+ *                     rows 8 ... 11 = the low parts of the four lse (lse_img, lse_txt, teacher T, teacher U): each lse is kept as an
+ *                     fp32 pair hi + lo, rows 0 / 2 / 4 / 6 holding hi = fl(lse), so that the backward's exp(logit - lse) is not
+ *                     rounded at the size of the lse
+ * The teacher's lse is taken first (one pass over the teacher operands), so the cross sums need no running-max rescale.
+ * E % 32 == 0, E <= 1152 (the backward's limit), Et % 8 == 0: OV_ERR_UNSUPPORTED otherwise.  ld >= E, ldt >= Et, both multiples of
+ * 4 floats, every base pointer 16-byte aligned, 0 <= label_offset, label_offset + b <= N: OV_ERR_INVALID otherwise, before any launch.
+ * workspace: ov_distill_loss_workspace_bytes(b, N) bytes (0 for sizes that are not positive).  Logits are never materialised;
+ * deterministic (no atomics). */
+size_t ov_distill_loss_workspace_bytes(int b, int N);
+int ov_distill_loss(const float* img, const float* txt, const float* all_img, const float* all_txt, int64_t ld, const float* t_img,
+                    const float* t_txt, const float* t_all_img, const float* t_all_txt, int64_t ldt, int b, int N, int E, int Et,
+                    const float* logit_scale, const float* t_logit_scale, int label_offset, float* contrastive_out,
+                    float* distill_out, float* terms_out, void* workspace, size_t workspace_bytes, ov_stream_t stream);
+
+/* Backward of ov_distill_loss, operands laid out as there; terms = the [12, b] block it wrote; grad_contrastive (g_c) and grad_distill
+ * (g_d) = the upstream gradients of the two outputs, DEVICE scalars, both required.  With P = softmax(A), Q = softmax(T) recomputed per
+ * tile from the saved lse and G = ((g_c + g_d) P - g_c onehot - g_d Q) / (2 b) per direction:
+ *     d_img = s G_i all_txt,  d_txt = s G_t all_img                               (local rows, [b, E], always written)
+ *     d_all_txt = s G_i^T img, d_all_img = s G_t^T txt                            (gathered rows, row g at base + g * ldg; NULL = skip)
+ *     d_scale = sum over both directions of G .* (x . y)                          (device scalar; NULL = skip)
+ * Nothing is computed for the teacher operands or t_logit_scale.  ldg follows ld's rules, so the gathered side can be written as one
+ * packed [N, 2E] gradient for one reduce-scatter (d_all_img = buf, d_all_txt = buf + E, ldg = 2E).  Shape limits as the forward's.
+ * Deterministic: no atomics, the d_scale partials (one per 32-row tile and direction) are summed in a fixed order. */
+size_t ov_distill_loss_backward_workspace_bytes(int b, int N);
+int ov_distill_loss_backward(const float* img, const float* txt, const float* all_img, const float* all_txt, int64_t ld,
+                             const float* t_img, const float* t_txt, const float* t_all_img, const float* t_all_txt, int64_t ldt, int b,
+                             int N, int E, int Et, const float* logit_scale, const float* t_logit_scale, int label_offset,
+                             const float* terms, const float* grad_contrastive, const float* grad_distill, float* d_img, float* d_txt,
+                             float* d_all_img, float* d_all_txt, int64_t ldg, float* d_scale, void* workspace, size_t workspace_bytes,
+                             ov_stream_t stream);
 
 /* SigLIP pairwise sigmoid loss on a local strip (SigLipLoss, loss.py:307-414; the neighbour-exchange ring is replaced by one
  * all-gather of the text features: only the order of the sums differs).

@@ -4,7 +4,7 @@ Python surface mirrors the reference's ``open_clip.model.CLIP`` and ``open_clip.
 in hand-written HIP kernels behind the C ABI of ``libovhip.so`` (see include/ovhip.h).  No CPU fallback."""
 from .config import preset, openvision_model_cfg, load_config_dir, PRESETS  # noqa: F401
 
-__all__ = ["CLIP", "ClipLoss", "MultiCaptionClipLoss", "gather_features", "create_model", "preset", "openvision_model_cfg", "load_config_dir",
+__all__ = ["CLIP", "ClipLoss", "MultiCaptionClipLoss", "DistillClipLoss", "gather_features", "create_model", "preset", "openvision_model_cfg", "load_config_dir",
            "WordPieceTokenizer"]
 
 
@@ -13,7 +13,7 @@ def __getattr__(name):   # lazy: importing the package must not require torch.cu
                 "logits", "l2_normalize"):
         from . import model
         return getattr(model, name)
-    if name in ("ClipLoss", "MultiCaptionClipLoss", "gather_features"):
+    if name in ("ClipLoss", "MultiCaptionClipLoss", "DistillClipLoss", "gather_features"):
         from . import loss
         return getattr(loss, name)
     if name == "WordPieceTokenizer":

@@ -14,6 +14,9 @@ carries the gradient on through the towers.  The gathered-side terms are routed 
 ``MultiCaptionClipLoss`` is the InfoNCE OpenVision trains with: C caption sets per image (src/losses/common.py:120-189, C = 2), the
 mean over the sets of ``ClipLoss(image, text_c)`` in one fused forward and backward (``ov_clip_loss_multi*``) on one packed gather.
 
+``DistillClipLoss`` (loss.py:180-216) adds the cross entropy under a frozen teacher's softmax to ``ClipLoss``: two outputs from one fused
+forward and backward (``ov_distill_loss*``) on one packed gather of the student's and the teacher's rows.
+
 ``SigLipLoss`` (loss.py:307-414) is the pairwise sigmoid objective on the same transport: one all-gather of the text features,
 one fused strip kernel (``ov_siglip_loss``), and in the backward the gathered side summed over ranks.
 """
@@ -487,3 +490,169 @@ class _SigLipLossFn(torch.autograd.Function):
         d_txt = _sum_over_ranks_own_chunk(d_all, b, mod.rank, mod.group) if ctx.multi else d_all
         dt_i, dt_t, dt_s, dt_b = ctx.in_dtypes
         return (None, d_img.to(dt_i), d_txt.to(dt_t), d_sc[0].to(dt_s), d_sc[1].to(dt_b) if ctx.has_bias else None)
+
+
+def pack_distill_features(image_features: torch.Tensor, text_features: torch.Tensor, dist_image_features: torch.Tensor,
+                          dist_text_features: torch.Tensor) -> torch.Tensor:
+    """Student rows [b, E] (image, text) and teacher rows [b, Et] (image, text) -> one [b, 2E + 2Et] buffer: student image in columns
+    0 ... E, student text in E ... 2E, teacher image in 2E ... 2E + Et, teacher text behind it.  The layout ``ov_distill_loss`` reads
+    in place after the all-gather (ld = ldt = 2E + 2Et)."""
+    return torch.cat([image_features, text_features, dist_image_features, dist_text_features], dim=1)
+
+
+def unpack_distill_features(packed: torch.Tensor, embed_dim: int):
+    """Inverse of ``pack_distill_features`` on [n, 2E + 2Et] rows, E = ``embed_dim``: four column views (student image, student text,
+    teacher image, teacher text)."""
+    e = embed_dim
+    et = (packed.shape[1] - 2 * e) // 2
+    return packed[:, :e], packed[:, e:2 * e], packed[:, 2 * e:2 * e + et], packed[:, 2 * e + et:]
+
+
+def gather_distill_features(image_features, text_features, dist_image_features, dist_text_features, world_size: int,
+                            group=None) -> torch.Tensor:
+    """ONE all_gather_into_tensor of the packed rows -> [world_size * b, 2E + 2Et] in rank order (seen by ``record_comm``)."""
+    if not (dist.is_available() and dist.is_initialized()):
+        raise RuntimeError("world_size > 1 needs an initialised torch.distributed process group (caller owns init)")
+    packed = pack_distill_features(*(t.detach().float() for t in (image_features, text_features, dist_image_features,
+                                                                  dist_text_features))).contiguous()
+    return _all_gather_rows(packed, world_size, group)
+
+
+class DistillClipLoss(ClipLoss):
+    """Distillation from a frozen teacher: the reference's ``DistillClipLoss`` (loss.py:180-216).  Constructor as ``ClipLoss``; the
+    call takes the student's features and multiplier, then the teacher's, and returns ``(contrastive_loss, distill_loss)``: the
+    student's InfoNCE and the cross entropy of the student's log-softmax under the teacher's softmax, both ways.  One fused forward
+    and one backward (``ov_distill_loss*``) on ONE all-gather of the packed ``[b, 2E + 2Et]`` rows read in place; the teacher's
+    embedding width may differ from the student's.  The student's gathered-side gradient is routed as ``ClipLoss`` routes it (own
+    chunk, or one reduce-scatter of the packed ``[N, 2E]`` gradient under ``gather_with_grad``); the teacher's share of the gather is
+    never exchanged back.
+
+    The teacher is frozen HERE: the reference would differentiate through teacher tensors that require grad, this build computes no
+    such gradient and therefore refuses them (``ValueError``) instead of returning none silently.
+
+    ``last_terms`` is the forward's [12, b] block: the student's lse_img, diag_img, lse_txt, diag_txt, then the teacher's lse and the
+    cross sum of the image strip and of the text strip, then the low parts of the four lse (ovhip.h)."""
+
+    _ws_bwd: Optional[torch.Tensor] = None      # the backward's workspace, kept like the forward's ``_ws``
+
+    def _check(self, image_features, text_features, dist_image_features, dist_text_features, dist_logit_scale):
+        s, t = (image_features, text_features), (dist_image_features, dist_text_features)
+        if any(x.dim() != 2 for x in s + t) or s[0].shape != s[1].shape or t[0].shape != t[1].shape or s[0].shape[0] != t[0].shape[0]:
+            raise ValueError("DistillClipLoss: student features must be two [b, E] tensors and teacher features two [b, Et] tensors "
+                             f"with the same b, got {[tuple(x.shape) for x in s + t]}")
+        if any(isinstance(x, torch.Tensor) and x.requires_grad for x in t + (dist_logit_scale,)):
+            raise ValueError("DistillClipLoss: the teacher is frozen here (no gradient is computed for dist_image_features, "
+                             "dist_text_features or dist_logit_scale): run the teacher under torch.no_grad() or detach its outputs")
+        if not all(x.is_cuda for x in s + t):
+            raise _lib.OvhipError("DistillClipLoss: features must live on an MI355X device (no CPU fallback)")
+
+    def _operands(self, img, txt, t_img, t_txt):
+        """(local student rows, local teacher rows, the four gathered operands, ld, ldt, label offset) for this rank."""
+        b, e = img.shape
+        et = t_img.shape[1]
+        if not (self.world_size > 1 or self.always_collective):
+            return (img, txt), (t_img, t_txt), (img, txt, t_img, t_txt), e, et, 0
+        packed = gather_distill_features(img, txt, t_img, t_txt, self.world_size, self.group)
+        views = unpack_distill_features(packed, e)
+        if self.local_loss:
+            x, u, off = (img, txt), (t_img, t_txt), b * self.rank
+        else:                       # the global loss on every rank (loss.py:111-113): the local rows are the gathered rows
+            x, u, off = (views[0].contiguous(), views[1].contiguous()), (views[2].contiguous(), views[3].contiguous()), 0
+        return x, u, views, packed.shape[1], packed.shape[1], off
+
+    def _distill_strips(self, x, u, g, ld: int, ldt: int, scale: torch.Tensor, t_scale: torch.Tensor, off: int):
+        lib = _lib.load()
+        b, e = x[0].shape
+        et, n, dev = u[0].shape[1], g[0].shape[0], x[0].device
+        nbytes = lib.ov_distill_loss_workspace_bytes(b, n)
+        if self._ws is None or self._ws.device != dev or self._ws.numel() < nbytes:
+            self._ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
+        out = torch.empty(2, dtype=torch.float32, device=dev)
+        terms = torch.empty(12, b, dtype=torch.float32, device=dev)
+        check(lib.ov_distill_loss(ptr(x[0]), ptr(x[1]), ptr(g[0]), ptr(g[1]), ld, ptr(u[0]), ptr(u[1]), ptr(g[2]), ptr(g[3]), ldt, b, n, e,
+                                  et, ptr(scale), ptr(t_scale), int(off), ptr(out[0:]), ptr(out[1:]), ptr(terms), ptr(self._ws), nbytes,
+                                  stream_ptr()), "ov_distill_loss")
+        self.last_terms = terms
+        return out[0], out[1]
+
+    def forward(self, image_features, text_features, logit_scale, dist_image_features, dist_text_features, dist_logit_scale,
+                output_dict: bool = False):
+        self._check(image_features, text_features, dist_image_features, dist_text_features, dist_logit_scale)
+        needs_grad = torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad
+                                                     for t in (image_features, text_features, logit_scale))
+        if needs_grad:
+            if not isinstance(logit_scale, torch.Tensor):
+                logit_scale = torch.tensor(float(logit_scale), device=image_features.device)
+            c, d = _DistillClipLossFn.apply(self, image_features, text_features, logit_scale, dist_image_features, dist_text_features,
+                                            dist_logit_scale)
+        else:
+            img, txt, t_img, t_txt = (t.detach().float().contiguous() for t in (image_features, text_features, dist_image_features,
+                                                                                 dist_text_features))
+            scale, t_scale = self._device_scale(logit_scale, img.device), self._device_scale(dist_logit_scale, img.device)
+            x, u, g, ld, ldt, off = self._operands(img, txt, t_img, t_txt)
+            c, d = self._distill_strips(x, u, g, ld, ldt, scale, t_scale, off)
+        return {"contrastive_loss": c, "distill_loss": d} if output_dict else (c, d)
+
+
+class _DistillClipLossFn(torch.autograd.Function):
+    """DistillClipLoss as an autograd node with two outputs.  forward = ov_distill_loss on the packed gather; backward =
+    ov_distill_loss_backward with both upstream gradients as device scalars, the student's gathered side written as one packed
+    [N, 2E] gradient and routed as ``_ClipLossFn`` routes its two halves.  The teacher inputs get None."""
+
+    @staticmethod
+    def forward(ctx, mod: "DistillClipLoss", image_features, text_features, logit_scale, dist_image_features, dist_text_features,
+                dist_logit_scale):
+        img, txt, t_img, t_txt = (t.detach().float().contiguous() for t in (image_features, text_features, dist_image_features,
+                                                                             dist_text_features))
+        scale, t_scale = mod._device_scale(logit_scale, img.device), mod._device_scale(dist_logit_scale, img.device)
+        x, u, g, ld, ldt, off = mod._operands(img, txt, t_img, t_txt)
+        c, d = mod._distill_strips(x, u, g, ld, ldt, scale, t_scale, off)
+        ctx.mod, ctx.off, ctx.b, ctx.lay = mod, off, img.shape[0], (ld, ldt)
+        ctx.multi = mod.world_size > 1 or mod.always_collective
+        ctx.in_dtypes = (image_features.dtype, text_features.dtype, logit_scale.dtype)
+        ctx.save_for_backward(*x, *u, *g, mod.last_terms, scale, t_scale)
+        return c, d
+
+    @staticmethod
+    def backward(ctx, grad_c, grad_d):
+        mod: "DistillClipLoss" = ctx.mod
+        x_img, x_txt, u_img, u_txt, y_img, y_txt, v_img, v_txt, terms, scale, t_scale = ctx.saved_tensors
+        lib = _lib.load()
+        rank, b = mod.rank, ctx.b
+        bx, e = x_img.shape
+        et, n, dev = u_img.shape[1], y_img.shape[0], x_img.device
+        ld, ldt = ctx.lay
+        single = not ctx.multi                      # world of one without the collectives: both sides are the same tensors
+        gathered_grad = single or not mod.local_loss or mod.gather_with_grad
+        d_img, d_txt = torch.empty_like(x_img), torch.empty_like(x_txt)
+        d_scale = torch.empty(1, dtype=torch.float32, device=dev)
+        if not gathered_grad:
+            d_all, p_ai, p_at, ldg = None, None, None, 0
+        elif single:                                # laid out as the features themselves: two [b, E] arrays
+            d_all = torch.empty(2, n, e, dtype=torch.float32, device=dev)
+            p_ai, p_at, ldg = ptr(d_all[0]), ptr(d_all[1]), e
+        else:                                       # packed [N, 2E]: the student's half of the gather's layout, for one reduce-scatter
+            d_all = torch.empty(n, 2 * e, dtype=torch.float32, device=dev)
+            p_ai, p_at, ldg = ptr(d_all), ptr(d_all[:, e:]), 2 * e
+        g_c = grad_c.detach().float().reshape(1).contiguous()           # device scalars: no host round trip
+        g_d = grad_d.detach().float().reshape(1).contiguous()
+        nbytes = lib.ov_distill_loss_backward_workspace_bytes(bx, n)
+        wsb = mod._ws_bwd
+        if wsb is None or wsb.device != dev or wsb.numel() < nbytes:
+            wsb = mod._ws_bwd = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
+        check(lib.ov_distill_loss_backward(ptr(x_img), ptr(x_txt), ptr(y_img), ptr(y_txt), ld, ptr(u_img), ptr(u_txt), ptr(v_img),
+                                           ptr(v_txt), ldt, bx, n, e, et, ptr(scale), ptr(t_scale), ctx.off, ptr(terms), ptr(g_c), ptr(g_d),
+                                           ptr(d_img), ptr(d_txt), p_ai, p_at, ldg, ptr(d_scale), ptr(wsb), nbytes, stream_ptr()),
+              "ov_distill_loss_backward")
+        if single:
+            g_img, g_txt = d_img + d_all[0], d_txt + d_all[1]
+        elif mod.local_loss:
+            g_img, g_txt = d_img, d_txt
+            if mod.gather_with_grad:
+                own = route_packed_gradient(d_all, b, rank, True, mod.group)
+                g_img, g_txt = g_img + own[:, :e], g_txt + own[:, e:]
+        else:                                       # both sides are the global set: [N, 2E] in all
+            own = route_packed_gradient(d_all + torch.cat([d_img, d_txt], dim=1), b, rank, mod.gather_with_grad, mod.group)
+            g_img, g_txt = own[:, :e], own[:, e:]
+        dt_i, dt_t, dt_s = ctx.in_dtypes
+        return None, g_img.to(dt_i), g_txt.to(dt_t), d_scale[0].to(dt_s), None, None, None

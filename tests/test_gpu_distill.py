@@ -1,0 +1,397 @@
+"""GPU: the fused distillation loss (csrc/distill.hip behind openvision_amd.loss.DistillClipLoss) against the reference's
+DistillClipLoss (tests/golden/distill_grad.npz, made over gloo in float64), the float64 restatement (tests/distill_restate.py),
+ov_clip_loss / ov_clip_loss_backward on the student operands, and a tiny distillation step.
+
+Bounds.  The project's figure for its fp32 strip losses (test_gpu_siglip.py, test_gpu_multicap.py): a loss to 1e-5 relative, a
+gradient to 1e-5 of its largest entry, d logit_scale to 1e-5 relative.  Two departures:
+  * the fixture's E = 768 cases, gradients only: the larger of 1e-5 and 4 x the error an fp32 torch restatement of the same formulas
+    makes against float64 on the same inputs (the factor 4: another summation order and the hardware v_exp);
+  * N = 1 makes both losses and every gradient exactly zero (P = Q = onehot = 1): there is no largest entry, so the error is
+    measured against the size of one term of the cancelling sum."""
+import os
+
+import pytest
+import torch
+
+from openvision_amd import _lib, preset, synth, training
+from openvision_amd._lib import check, ptr, stream_ptr
+from openvision_amd.loss import ClipLoss, DistillClipLoss
+from openvision_amd.model import create_model
+
+import distill_restate as DR
+import hipops as H
+from conftest import golden
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+SENTINEL = -12345.0
+
+
+def run_forward(args, s, st, off, packed=False):
+    """ov_distill_loss on the eight fp32 device operands (x_img, x_txt, y_img, y_txt, u_img, u_txt, v_img, v_txt).  ``packed``: the
+    four gathered operands are handed over as ONE [N, 2E + 2Et] buffer read in place (ld = ldt = 2E + 2Et); else as separate
+    contiguous arrays (ld = E, ldt = Et).  Returns (contrastive, distill, terms [12, b], state for run_backward)."""
+    lib = _lib.load()
+    x_img, x_txt, y_img, y_txt, u_img, u_txt, v_img, v_txt = (t.contiguous() for t in args)
+    (b, e), et, n = x_img.shape, u_img.shape[1], y_img.shape[0]
+    if packed:
+        buf = torch.cat([y_img, y_txt, v_img, v_txt], dim=1).contiguous()
+        g = (buf, buf[:, e:], buf[:, 2 * e:], buf[:, 2 * e + et:])
+        ld = ldt = 2 * e + 2 * et
+    else:
+        g, ld, ldt = (y_img, y_txt, v_img, v_txt), e, et
+    sc = torch.full((1,), float(s), dtype=torch.float32, device=DEV)
+    tsc = torch.full((1,), float(st), dtype=torch.float32, device=DEV)
+    nb = lib.ov_distill_loss_workspace_bytes(b, n)
+    ws = torch.empty(nb + 16, dtype=torch.uint8, device=DEV)
+    out = torch.empty(2, dtype=torch.float32, device=DEV)
+    terms = torch.empty(12, b, dtype=torch.float32, device=DEV)
+    check(lib.ov_distill_loss(ptr(x_img), ptr(x_txt), ptr(g[0]), ptr(g[1]), ld, ptr(u_img), ptr(u_txt), ptr(g[2]), ptr(g[3]), ldt, b, n, e,
+                              et, ptr(sc), ptr(tsc), off, ptr(out[0:]), ptr(out[1:]), ptr(terms), ptr(ws), nb, stream_ptr()),
+          "ov_distill_loss")
+    return out[0], out[1], terms, ((x_img, x_txt, u_img, u_txt), g, ld, ldt, sc, tsc, off, packed)
+
+
+def run_backward(state, terms, g_c, g_d, gathered=True):
+    """ov_distill_loss_backward.  The gathered-side gradient comes back packed [N, 2E] (ldg = 2E) when the operands were packed, else
+    as two [N, E] arrays; its buffer is filled with a sentinel first.  Returns d_img, d_txt, d_all_img | None, d_all_txt | None,
+    d_scale, the raw gathered buffer | None."""
+    lib = _lib.load()
+    (x_img, x_txt, u_img, u_txt), g, ld, ldt, sc, tsc, off, packed = state
+    (b, e), et, n = x_img.shape, u_img.shape[1], g[0].shape[0]
+    gc = torch.full((1,), float(g_c), dtype=torch.float32, device=DEV)
+    gd = torch.full((1,), float(g_d), dtype=torch.float32, device=DEV)
+    d_img, d_txt = torch.empty_like(x_img), torch.empty_like(x_txt)
+    d_s = torch.empty(1, dtype=torch.float32, device=DEV)
+    if packed:
+        gbuf = torch.full((n, 2 * e), SENTINEL, dtype=torch.float32, device=DEV)
+        views, ldg = (gbuf[:, :e], gbuf[:, e:]), 2 * e
+    else:
+        gbuf = torch.full((2, n, e), SENTINEL, dtype=torch.float32, device=DEV)
+        views, ldg = (gbuf[0], gbuf[1]), e
+    nbb = lib.ov_distill_loss_backward_workspace_bytes(b, n)
+    wsb = torch.empty(nbb + 16, dtype=torch.uint8, device=DEV)
+    check(lib.ov_distill_loss_backward(ptr(x_img), ptr(x_txt), ptr(g[0]), ptr(g[1]), ld, ptr(u_img), ptr(u_txt), ptr(g[2]), ptr(g[3]), ldt,
+                                       b, n, e, et, ptr(sc), ptr(tsc), off, ptr(terms), ptr(gc), ptr(gd), ptr(d_img), ptr(d_txt),
+                                       ptr(views[0]) if gathered else None, ptr(views[1]) if gathered else None, ldg if gathered else 0,
+                                       ptr(d_s), ptr(wsb), nbb, stream_ptr()), "ov_distill_loss_backward")
+    if not gathered:
+        return d_img, d_txt, None, None, d_s[0], gbuf
+    return d_img, d_txt, views[0].contiguous(), views[1].contiguous(), d_s[0], gbuf
+
+
+def err_of(got, ref):
+    got, ref = got.double().cpu(), torch.as_tensor(ref).double().cpu()
+    assert got.shape == ref.shape, (got.shape, ref.shape)
+    return float((got - ref).abs().max()), float(ref.abs().max())
+
+
+def close(got, ref, rel, what):
+    err, mag = err_of(got, ref)
+    print(f"{what}: max |err| {err:.3e} at max |ref| {mag:.3e} (bound {rel * mag:.3e})")
+    assert err <= rel * mag, (what, err, mag, rel)
+
+
+_FIXTURE_REF = {}
+
+
+def fixture_reference(case):
+    """Per case, computed once: the inputs (float64), and for the E = 768 cases the error of an fp32 torch restatement on the CPU."""
+    name, ws, b, e, et, local_loss, gwg, s, st, seed = case
+    if name not in _FIXTURE_REF:
+        inputs = DR.case_inputs(ws, b, e, et, seed)
+        fp32_err = None
+        if e == 768:
+            want = DR.per_rank(inputs, s, st, ws, local_loss, gwg, *DR.GRADS)
+            got = DR.per_rank(tuple(x.float() for x in inputs), s, st, ws, local_loss, gwg, *DR.GRADS)
+            fp32_err = max(float((g[k].double() - w[k]).abs().max()) / float(w[k].abs().max()) for g, w in zip(got, want) for k in (2, 3))
+        _FIXTURE_REF[name] = (inputs, fp32_err)
+    return _FIXTURE_REF[name]
+
+
+@pytest.mark.parametrize("case", DR.CASES, ids=[c[0] for c in DR.CASES])
+def test_kernel_against_the_reference_fixture(case):
+    """One process plays every rank: its local rows against the packed gathered set, label offset b r (or, without local_loss, the
+    global rows against themselves), upstream pair (1, 0.7), then the gathered side routed as the case's mode prescribes.  Losses
+    to 1e-5 relative; gradients to 1e-5 of their largest entry, in the E = 768 cases to the larger of that and 4 x the error of
+    an fp32 torch restatement against float64 (printed)."""
+    z = golden("distill_grad.npz")
+    name, ws, b, e, et, local_loss, gwg, s, st, seed = case
+    inputs64, fp32_err = fixture_reference(case)
+    for key, x in zip(("img", "txt", "timg", "ttxt"), inputs64):
+        assert abs(float(x.sum()) - float(z[f"{name}_{key}_sum"])) <= 1e-9 * float(z[f"{name}_{key}_abs_sum"])
+    inputs = tuple(x.float().to(DEV) for x in inputs64)
+    per = []
+    for r in range(ws):
+        args, off = DR.rank_args(inputs, r, ws, local_loss)
+        c, d, terms, state = run_forward(args, s, st, off, packed=True)
+        per.append((c, d) + run_backward(state, terms, *DR.GRADS))
+    rel = 1e-5
+    if fp32_err is not None:
+        rel = max(1e-5, 4 * fp32_err)
+        print(f"{name}: fp32 torch restatement vs float64: {fp32_err:.3e} of the largest entry -> gradient bound {rel:.3e}")
+    for r in range(ws):
+        c, d, _, _, _, _, d_s, _ = per[r]
+        gi, gt = DR.route([p[2:6] for p in per], r, b, ws, local_loss, gwg)
+        for got, key in ((c, "contrastive"), (d, "distill")):
+            ref = float(z[f"{name}_{key}"][r])
+            print(f"{name} rank {r}: {key} {float(got):.8f} reference {ref:.8f} rel err {abs(float(got) - ref) / abs(ref):.3e}")
+            assert abs(float(got) - ref) <= 1e-5 * abs(ref), (name, r, key, float(got), ref)
+        close(gi, z[f"{name}_dimg"][r], rel, (name, r, "dimg"))
+        close(gt, z[f"{name}_dtxt"][r], rel, (name, r, "dtxt"))
+        ref = float(z[f"{name}_dscale"][r])
+        print(f"{name} rank {r}: dscale {float(d_s):.6e} reference {ref:.6e} rel err {abs(float(d_s) - ref) / abs(ref):.3e}")
+        assert abs(float(d_s) - ref) <= 1e-5 * abs(ref), (name, r, float(d_s), ref)
+
+
+def split_rule(b, N):
+    """csrc/distill.hip ds_plan (ov_clip_loss's rule) restated: (column splits, 32-column tiles per split)."""
+    nrt, ntiles = (b + 31) // 32, (N + 31) // 32
+    nsplit = min(max(1024 // (2 * nrt), 1), max((ntiles + 3) // 4, 1))
+    tps = (ntiles + nsplit - 1) // nsplit
+    return (ntiles + tps - 1) // tps, tps
+
+
+# b, N, off, E, Et: every b in {1, 13, 32, 33} with N = b (off 0) and N = 3 b (off b); E in {64, 1152} x Et in {8, 96}; one N with two
+# column splits and a ragged last tile
+SHAPES = [(1, 1, 0, 64, 8), (1, 3, 1, 1152, 96), (13, 13, 0, 64, 96), (13, 39, 13, 1152, 8), (32, 32, 0, 1152, 96), (32, 96, 32, 64, 8),
+          (33, 33, 0, 1152, 8), (33, 99, 33, 64, 96), (13, 150, 26, 64, 96)]
+PAIRS = [(1.0, 1.0), (1.0, 0.0), (0.0, 1.0), (0.3, 2.0)]
+
+
+@pytest.mark.parametrize("b,N,off,E,Et", SHAPES, ids=[f"b{s[0]}_n{s[1]}_e{s[3]}_t{s[4]}" for s in SHAPES])
+def test_kernel_against_float64_restatement(b, N, off, E, Et):
+    """Both losses, the terms block and, for four upstream pairs, every gradient against the float64 restatement; contiguous and
+    packed operands bitwise equal; the pair (1, 0) against ov_clip_loss / ov_clip_loss_backward on the student operands."""
+    s, st = 5.0, 15.0
+    if (b, N) == (13, 150):
+        assert split_rule(b, N)[0] >= 2 and N % 32 != 0 and (N + 31) // 32 > split_rule(b, N)[1]
+    in64 = DR.make_inputs(N, E, Et, seed=2000 + 7 * b + N)
+    sl = slice(off, off + b)
+    args64 = (in64[0][sl], in64[1][sl], in64[0], in64[1], in64[2][sl], in64[3][sl], in64[2], in64[3])
+    args = tuple(x.float().contiguous().to(DEV) for x in args64)
+    c, d, terms, state = run_forward(args, s, st, off, packed=True)
+    c2, d2, terms2, state2 = run_forward(args, s, st, off, packed=False)
+    assert torch.equal(c, c2) and torch.equal(d, d2) and torch.equal(terms, terms2)
+    want_c, want_d = DR.strip_losses(*args64, s, st, off)
+    want_terms = DR.strip_terms(*args64, s, st, off)
+    print(f"contrastive {float(c):.7f} float64 {float(want_c):.7f}; distill {float(d):.7f} float64 {float(want_d):.7f}")
+    for got, want in ((c, want_c), (d, want_d)):
+        # N = 1: both losses are exactly 0 = lse - logit; the error is measured against the logit's size
+        assert abs(float(got) - float(want)) <= 1e-5 * (abs(float(want)) if N > 1 else s), (float(got), float(want))
+    close(terms[:8], want_terms, 1e-5, "terms")
+    close(terms[[0, 2, 4, 6]].double() + terms[8:12].double(), want_terms[[0, 2, 4, 6]], 1e-5, "lse hi + lo")
+    ref_c, ref_terms = H.clip_loss(args[0], args[1], args[2], args[3], s, off)
+    # contrastive_out is ov_clip_loss's value to 1e-6 relative (N = 1: both are 0 = lse - logit, measured against the logit's size)
+    assert abs(float(c) - float(ref_c)) <= 1e-6 * (abs(float(ref_c)) if N > 1 else s), (float(c), float(ref_c))
+    close(terms[:4], ref_terms, 1e-5, "student terms vs ov_clip_loss")
+    for g_c, g_d in PAIRS:
+        want = DR.strip_grads(*args64, s, st, off, g_c, g_d)
+        got = run_backward(state, terms, g_c, g_d)
+        unpacked = run_backward(state2, terms2, g_c, g_d)
+        for x, y in zip(got[:5], unpacked[:5]):
+            assert torch.equal(x, y)
+        for name, g_, w in zip(("d_img", "d_txt", "d_all_img", "d_all_txt"), got, want):
+            if N == 1:      # exactly zero: measured against one term of the cancelling sum, s (g_c + g_d) / (2 b) |y|, |y| = 1
+                assert float(w.abs().max()) < 1e-15 and float(g_.abs().max()) <= 1e-5 * s * (g_c + g_d) / (2 * b), (name, g_c, g_d)
+                continue
+            close(g_, w, 1e-5, (name, g_c, g_d))
+        print(f"d_scale ({g_c}, {g_d}): {float(got[4]):.6e} float64 {float(want[4]):.6e}")
+        mag = abs(float(want[4])) if N > 1 else s * (g_c + g_d)
+        assert abs(float(got[4]) - float(want[4])) <= 1e-5 * mag, ("d_scale", g_c, g_d, float(got[4]), float(want[4]))
+        if (g_c, g_d) == (1.0, 0.0):
+            ref = H.clip_loss_backward(args[0], args[1], args[2], args[3], s, off, ref_terms)
+            for name, g_, r_, w in zip(("d_img", "d_txt", "d_all_img", "d_all_txt"), got, ref, want):
+                if N > 1:
+                    close(g_, r_, 1e-5, (name, "vs ov_clip_loss_backward"))
+            # d logit_scale of ov_clip_loss_backward is itself off float64 (2.4e-5 relative at b = 1, N = 3, where this kernel is 4e-7
+            # off): the comparand's own error is part of the bound
+            ref_err = abs(float(ref[4]) - float(want[4]))
+            print(f"d_scale vs ov_clip_loss_backward: |diff| {abs(float(got[4]) - float(ref[4])):.3e}, its own |err| {ref_err:.3e}")
+            assert abs(float(got[4]) - float(ref[4])) <= 1e-5 * mag + ref_err
+
+
+@pytest.fixture(scope="module")
+def mid():
+    """b = 256, N = 1024, E = 768, Et = 1024, st = 20: inputs on the device and the float64 restatement computed there, once."""
+    b, N, E, Et, off, s, st = 256, 1024, 768, 1024, 512, 5.0, 20.0
+    in64 = tuple(x.to(DEV) for x in DR.make_inputs(N, E, Et, seed=77))
+    sl = slice(off, off + b)
+    args64 = (in64[0][sl], in64[1][sl], in64[0], in64[1], in64[2][sl], in64[3][sl], in64[2], in64[3])
+    args = tuple(x.float().contiguous() for x in args64)
+    want = {"losses": DR.strip_losses(*args64, s, st, off), "terms": DR.strip_terms(*args64, s, st, off),
+            "grads": DR.strip_grads(*args64, s, st, off, 0.3, 2.0)}
+    return args, s, st, off, want
+
+
+def test_mid_size_against_float64_on_the_device(mid):
+    args, s, st, off, want = mid
+    assert split_rule(256, 1024)[0] >= 2
+    c, d, terms, state = run_forward(args, s, st, off, packed=True)
+    for got, w, key in ((c, want["losses"][0], "contrastive"), (d, want["losses"][1], "distill")):
+        print(f"{key} {float(got):.7f} float64 {float(w):.7f} rel err {abs(float(got) - float(w)) / float(w):.3e}")
+        assert abs(float(got) - float(w)) <= 1e-5 * abs(float(w))
+    close(terms[:8], want["terms"], 1e-5, "terms")
+    got = run_backward(state, terms, 0.3, 2.0)
+    for name, g_, w in zip(("d_img", "d_txt", "d_all_img", "d_all_txt"), got, want["grads"]):
+        close(g_, w, 1e-5, name)
+    w_s = float(want["grads"][4])
+    print(f"d_scale {float(got[4]):.6e} float64 {w_s:.6e} rel err {abs(float(got[4]) - w_s) / abs(w_s):.3e}")
+    assert abs(float(got[4]) - w_s) <= 1e-5 * abs(w_s)
+
+
+def test_deterministic_and_null_outputs(mid):
+    """Two calls are bitwise equal; a requested gathered gradient overwrites every sentinel; NULL gathered outputs skip the work,
+    leave the buffer untouched and give bitwise the same local gradients."""
+    args, s, st, off, _ = mid
+    c, d, terms, state = run_forward(args, s, st, off, packed=True)
+    c2, d2, terms2, _ = run_forward(args, s, st, off, packed=True)
+    assert torch.equal(c, c2) and torch.equal(d, d2) and torch.equal(terms, terms2)
+    first = run_backward(state, terms, 0.3, 2.0)
+    again = run_backward(state, terms, 0.3, 2.0)
+    for x, y in zip(first, again):
+        assert torch.equal(x, y)
+    assert not bool((first[5] == SENTINEL).any()) and bool(torch.isfinite(first[5]).all())
+    local = run_backward(state, terms, 0.3, 2.0, gathered=False)
+    assert local[2] is None and local[3] is None and bool((local[5] == SENTINEL).all())
+    assert torch.equal(local[0], first[0]) and torch.equal(local[1], first[1]) and torch.equal(local[4], first[4])
+
+
+MODES = [(True, False), (True, True), (False, False)]
+MOD_S, MOD_ST = 5.0, 15.0
+
+
+def _module_inputs():
+    return DR.make_inputs(24, 192, 96, seed=5)
+
+
+def _module_run(fn, inputs):
+    img, txt, t_img, t_txt = (x.float().to(DEV) for x in inputs)
+    img.requires_grad_(True)
+    txt.requires_grad_(True)
+    sc = torch.tensor(MOD_S, device=DEV, requires_grad=True)
+    tsc = torch.tensor(MOD_ST, device=DEV)
+    c, d = fn(img, txt, sc, t_img, t_txt, tsc)
+    assert c.requires_grad and d.requires_grad
+    (c + d).backward()
+    with torch.no_grad():
+        plain = fn(img, txt, sc, t_img, t_txt, tsc, output_dict=True)
+    assert set(plain) == {"contrastive_loss", "distill_loss"} and fn.last_terms.shape == (12, img.shape[0])
+    assert torch.equal(plain["contrastive_loss"], c.detach()) and torch.equal(plain["distill_loss"], d.detach())
+    assert t_img.grad is None and t_txt.grad is None and tsc.grad is None
+    return float(c.detach()), float(d.detach()), img.grad.cpu(), txt.grad.cpu(), float(sc.grad)
+
+
+def _module_check(got, inputs, gathered_side, what):
+    """World size 1: with ``gathered_side`` a feature's gradient is its local-side plus its gathered-side term, else the local one."""
+    args, off = DR.rank_args(inputs, 0, 1, True)
+    want_c, want_d = DR.strip_losses(*args, MOD_S, MOD_ST, off)
+    w = DR.strip_grads(*args, MOD_S, MOD_ST, off, 1.0, 1.0)
+    pick = (lambda g: (g[0] + g[2], g[1] + g[3])) if gathered_side else (lambda g: (g[0], g[1]))
+    c, d, g_img, g_txt, g_s = got
+    assert abs(c - float(want_c)) <= 1e-5 * float(want_c) and abs(d - float(want_d)) <= 1e-5 * float(want_d), what
+    for name, g_, w_ in zip(("d_img", "d_txt"), (g_img, g_txt), pick(w)):
+        close(g_, w_, 1e-5, (what, name))
+    assert abs(g_s - float(w[4])) <= 1e-5 * abs(float(w[4])), (what, g_s, float(w[4]))
+
+
+@pytest.mark.parametrize("local_loss,gwg", MODES)
+def test_module_world_size_1(local_loss, gwg):
+    """DistillClipLoss()(...) with loss = c + d; loss.backward() against the restatement; output_dict; the contrastive output is
+    ClipLoss's."""
+    inputs = _module_inputs()
+    fn = DistillClipLoss(local_loss=local_loss, gather_with_grad=gwg)
+    got = _module_run(fn, inputs)
+    _module_check(got, inputs, True, (local_loss, gwg))
+    ref = ClipLoss()(inputs[0].float().to(DEV), inputs[1].float().to(DEV), MOD_S)
+    assert abs(got[0] - float(ref)) <= 1e-6 * float(ref)
+
+
+def _nccl_ws1_rank(store, q):
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import torch.distributed as dist
+    from openvision_amd import loss as L
+    torch.cuda.set_device(0)
+    dist.init_process_group("nccl", init_method=f"file://{store}", rank=0, world_size=1, device_id=torch.device(DEV))
+    inputs = _module_inputs()
+    out = {}
+    for local_loss, gwg in MODES:
+        fn = DistillClipLoss(local_loss=local_loss, gather_with_grad=gwg, rank=0, world_size=1)
+        fn.always_collective = True                          # all_gather_into_tensor (+ reduce_scatter_tensor) at world 1
+        log = []
+        L.record_comm(log)
+        c, d, gi, gt, gs = _module_run(fn, inputs)
+        L.record_comm(None)
+        out[(local_loss, gwg)] = (c, d, gi.numpy(), gt.numpy(), gs, len(log))
+    q.put(out)
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def test_rccl_branch_of_the_module_at_world_size_1():
+    """The RCCL code path (ONE packed all-gather per call read in place, packed [N, 2E] gathered-side gradient, reduce-scatter) in a
+    world of one rank.  A detached gather with local_loss returns the local-side gradient alone; the other two modes the whole one."""
+    import tempfile
+    import torch.multiprocessing as mp
+    ctx = mp.get_context("spawn")
+    with tempfile.TemporaryDirectory() as d:
+        q = ctx.Queue()
+        p = ctx.Process(target=_nccl_ws1_rank, args=(os.path.join(d, "store"), q))
+        p.start()
+        out = q.get(timeout=600)
+        p.join(120)
+    inputs = _module_inputs()
+    for (local_loss, gwg), (c, d_, gi, gt, gs, ncoll) in out.items():
+        assert ncoll == 2                                        # one gather in the differentiated call, one in the no_grad call
+        got = (c, d_, torch.from_numpy(gi), torch.from_numpy(gt), gs)
+        _module_check(got, inputs, not (local_loss and not gwg), ("rccl", local_loss, gwg))
+
+
+def test_distillation_step_tiny():
+    """Student vit-tiny-patch16-160 through training.clip_forward; teacher: a shallower tiny model with embed_dim 128 under no_grad on
+    the inference path; c + d, backward, one FusedAdamW step.  The gradients arriving at the student's features are the
+    restatement's, every trainable parameter gets a finite non-zero gradient, the teacher none."""
+    cfg = preset("vit-tiny-patch16-160")
+    tcfg = preset("vit-tiny-patch16-160")
+    tcfg["embed_dim"] = 128
+    tcfg["vision_cfg"]["layers"] = tcfg["text_cfg"]["layers"] = 2
+    student = create_model(cfg, device=DEV, state_dict=synth.make_state_dict(cfg))
+    teacher = create_model(tcfg, device=DEV, state_dict=synth.make_state_dict(tcfg, 1))
+    img = synth.make_images(6, 160, seed=61).to(DEV)
+    tok = synth.make_captions(6, seed=61).to(DEV)
+    opt = training.FusedAdamW(student, lr=1e-3)
+    opt.zero_grad()
+    with torch.no_grad():
+        t_img, t_txt, t_scale = teacher(img, tok)
+    assert t_img.shape == (6, 128) and not t_img.requires_grad
+    img_f, txt_f, scale = training.clip_forward(student, img, tok)
+    assert img_f.shape == (6, 192) and img_f.requires_grad
+    img_f.retain_grad()
+    txt_f.retain_grad()
+    c, d = DistillClipLoss()(img_f, txt_f, scale, t_img, t_txt, t_scale)
+    loss = c + d
+    loss.backward()
+    torch.cuda.synchronize()
+    c, d = c.detach(), d.detach()
+    assert bool(torch.isfinite(loss)) and float(c) > 0 and float(d) > 0 and abs(float(c) - float(d)) > 1e-4
+    f64 = [x.detach().double().cpu() for x in (img_f, txt_f, t_img, t_txt)]
+    args = (f64[0], f64[1], f64[0], f64[1], f64[2], f64[3], f64[2], f64[3])
+    s, st = float(scale.detach()), float(t_scale)
+    want_c, want_d = DR.strip_losses(*args, s, st, 0)
+    print(f"contrastive {float(c):.7f} float64 {float(want_c):.7f}; distill {float(d):.7f} float64 {float(want_d):.7f}; s {s:.4f} st {st:.4f}")
+    assert abs(float(c) - float(want_c)) <= 1e-5 * float(want_c) and abs(float(d) - float(want_d)) <= 1e-5 * float(want_d)
+    w = DR.strip_grads(*args, s, st, 0, 1.0, 1.0)
+    for name, g_, w_ in (("img_f", img_f.grad, w[0] + w[2]), ("txt_f", txt_f.grad, w[1] + w[3])):
+        close(g_.float(), w_, 1e-5, name)
+    before = {}
+    for n, p in student.named_parameters():
+        assert p.grad is not None and bool(torch.isfinite(p.grad).all()) and float(p.grad.abs().max()) > 0, n
+        before[n] = p.detach().clone()
+    for n, p in teacher.named_parameters():
+        assert p.grad is None, n
+    opt.step()
+    torch.cuda.synchronize()
+    for n, p in student.named_parameters():
+        assert bool(torch.isfinite(p).all()) and not torch.equal(p.detach(), before[n]), n

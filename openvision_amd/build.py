@@ -37,7 +37,7 @@ def _digest(paths) -> str:
 def build(force: bool = False, verbose: bool = True) -> str:
     bdir = os.path.join(CSRC, "build")
     os.makedirs(bdir, exist_ok=True)
-    deps = [os.path.join(CSRC, "common.h"), os.path.join(PKG, "..", "include", "ovhip.h")]
+    deps = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "strip.h"), os.path.join(PKG, "..", "include", "ovhip.h")]
     cc = hipcc()
 
     def compile_one(src):

@@ -5,7 +5,7 @@
 //     A = s x y^T [b, N] (student),   T = st u v^T [b, N] (teacher),   Q = softmax(T, dim=1)
 //     contrastive_i = lse(A_i) - A[i, i + off]
 //     distill_i     = lse(A_i) - sum_j Q_ij A_ij                  ( = -(Q * log_softmax(A)).sum(1), sum_j Q_ij = 1 )
-// and both outputs are the mean over the rows and the two directions.  The building blocks are loss.hip's / multicap.hip's:
+// and both outputs are the mean over the rows and the two directions.  The building blocks are strip.h's, as in multicap.hip:
 // exact-fp32 v_mfma_f32_32x32x2_f32 logit tiles that are never written, the gathered side as the MFMA A operand (row reductions
 // are lane-local), partial + finalize, no atomics, fixed summation order.  What is new here:
 //   * the teacher's lse comes FIRST (one pass of the same strip kernel over the teacher operands), so q = exp(T - lse_T) is final
@@ -21,27 +21,17 @@
 //     recomputes, and exp(dot * scale - lse) meets the very values its lse was summed from;
 //   * the exponent is fma(dot, scale, -lse_hi) - lse_lo: the product is not rounded at the size of the logit, and the lse is kept as
 //     an fp32 pair (hi = fl(M + log S), lo = (M - hi) + log S), not rounded at its own size (st = 20: 1e-6).
-#include "common.h"
+#include "strip.h"
 
 namespace {
 
-constexpr int DS_MAXT = 9;           // backward: e-tiles per wave, E <= 4 * 9 * 32 = 1152
-
-__device__ __forceinline__ f32x16_t mfma4(const float4 av, const float4 bv, f32x16_t acc) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bv.x, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, bv.y, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, bv.z, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, bv.w, acc, 0, 0, 0);
-    return acc;
-}
+using namespace strip;
 
 // One 32 x 32 tile of dots <Y[.], X[row]> over K floats in the summation order stated above.  yp / xp: this lane's row, already
 // offset by 4 * half.  STEP = 32: chain c takes the 32-float e-tiles c, c + 4, ... (K % 32 == 0); STEP = 8: the 8-float chunks.
 template <int STEP>
 __device__ __forceinline__ f32x16_t dot_tile(const float* yp, const float* xp, int K) {
-    f32x16_t c0, c1, c2, c3;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) { c0[i] = 0.f; c1[i] = 0.f; c2[i] = 0.f; c3[i] = 0.f; }
+    f32x16_t c0 = zero16(), c1 = zero16(), c2 = zero16(), c3 = zero16();
     for (int k0 = 0; k0 < K; k0 += 4 * STEP) {
 #pragma unroll
         for (int k = 0; k < STEP; k += 8) {
@@ -78,7 +68,7 @@ __device__ __forceinline__ void online_lse(const f32x16_t dots, float scale, int
     float mx = -INFINITY;
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
-        const int g = g0 + (i & 3) + 8 * (i >> 2) + 4 * half;
+        const int g = g0 + tile_row(i, half);
         if (g < N) mx = fmaxf(mx, dots[i] * scale);
     }
     if (mx > -INFINITY) {
@@ -86,7 +76,7 @@ __device__ __forceinline__ void online_lse(const f32x16_t dots, float scale, int
         float ps = 0.f;
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            const int g = g0 + (i & 3) + 8 * (i >> 2) + 4 * half;
+            const int g = g0 + tile_row(i, half);
             ps += g < N ? __expf(fmaf(dots[i], scale, -mn)) : 0.f;
         }
         s = s * __expf(m - mn) + ps;
@@ -123,7 +113,7 @@ __global__ __launch_bounds__(256) void distill_logits_partial(const DsArgs a) {
     for (int t = t0 + wave; t < t1; t += 4) {
         int gi = t * 32 + j;
         gi = gi < a.N ? gi : a.N - 1;
-        // dots[i] = <V[t*32 + (i&3) + 8*(i>>2) + 4*half], U[row]>, and the same of Y and X
+        // dots[i] = <V[t * 32 + tile_row(i, half)], U[row]>, and the same of Y and X
         const f32x16_t tdots = dot_tile<8>(V + (int64_t)gi * a.ldt + 4 * half, up, a.Et);
         if (TEACHER) {
             online_lse(tdots, tscale, t * 32, half, a.N, m, s);
@@ -131,7 +121,7 @@ __global__ __launch_bounds__(256) void distill_logits_partial(const DsArgs a) {
             const f32x16_t dots = dot_tile<32>(Y + (int64_t)gi * a.ld + 4 * half, xp, a.E);
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
-                const int g = t * 32 + (i & 3) + 8 * (i >> 2) + 4 * half;
+                const int g = t * 32 + tile_row(i, half);
                 const float v = dots[i] * scale;
                 if (g == label && row < a.b) a.diag[dir * a.bpad + row] = v;
                 const float q = g < a.N ? __expf(fmaf(tdots[i], tscale, -tl_hi) - tl_lo) : 0.f;
@@ -141,23 +131,15 @@ __global__ __launch_bounds__(256) void distill_logits_partial(const DsArgs a) {
         }
     }
     // combine the two lane halves of each row, then the four waves
-    {
-        const float mo = __shfl_xor(m, 32, 64), so = __shfl_xor(s, 32, 64), co = __shfl_xor(cross, 32, 64);
-        const float mn = fmaxf(m, mo);
-        if (mn > -INFINITY) s = s * __expf(m - mn) + so * __expf(mo - mn);
-        m = mn;
-        cross += co;
-    }
+    lse_merge_halves(m, s);
+    cross += __shfl_xor(cross, 32, 64);
     if (half == 0) { red[wave][j][0] = m; red[wave][j][1] = s; red[wave][j][2] = cross; }
     __syncthreads();
     if (wave == 0 && half == 0 && row < a.b) {
         float M = red[0][j][0], S = red[0][j][1], C = red[0][j][2];
 #pragma unroll
         for (int w = 1; w < 4; ++w) {
-            const float mw = red[w][j][0], sw = red[w][j][1];
-            const float mn = fmaxf(M, mw);
-            if (mn > -INFINITY) S = S * __expf(M - mn) + sw * __expf(mw - mn);
-            M = mn;
+            lse_merge(M, S, red[w][j][0], red[w][j][1]);
             C += red[w][j][2];
         }
         if (TEACHER) {
@@ -173,13 +155,8 @@ __global__ __launch_bounds__(256) void distill_logits_partial(const DsArgs a) {
 // the splits' (max, sumexp) of one row (p[0], p[1], then every split_stride floats) -> its lse as an fp32 pair: hi = fl(M + log S),
 // lo = what that rounding lost
 __device__ __forceinline__ void combine_lse(const float* p, int64_t split_stride, int nsplit, float& hi, float& lo) {
-    float M = -INFINITY, S = 0.f;
-    for (int sp = 0; sp < nsplit; ++sp) {
-        const float mw = p[sp * split_stride], sw = p[sp * split_stride + 1];
-        const float mn = fmaxf(M, mw);
-        if (mn > -INFINITY) S = S * __expf(M - mn) + sw * __expf(mw - mn);
-        M = mn;
-    }
+    float M, S;
+    lse_merge_splits(p, split_stride, nsplit, M, S);
     const float L = logf(S);
     hi = __fadd_rn(M, L);                                         // two-sum: hi + lo == M + L exactly
     const float bb = __fsub_rn(hi, M);
@@ -233,7 +210,7 @@ __global__ __launch_bounds__(256) void distill_loss_finalize(const float* __rest
 }
 
 // ---- backward ------------------------------------------------------------------------------------------------------------------
-// As clip_loss_bwd (loss.hip): the 32 x 32 logit tiles are recomputed, the coefficient tile is formed in registers and
+// As multicap_loss_bwd (multicap.hip): the 32 x 32 logit tiles are recomputed, the coefficient tile is formed in registers and
 // out += G . X_in accumulates in [32 x E] MFMA accumulators split over the four waves by e-tile; one workgroup per 32-row out tile
 // and direction, the in-side loop not split.  Here G = (g_c + g_d) exp(A - lse_A) - g_c [label] - g_d exp(T - lse_T).
 //   GATHERED = false: out rows are LOCAL rows (both lse by out row):      d x[r]  = s / (2 b) sum_g G[r, g] y[g]
@@ -260,7 +237,7 @@ struct DsBwdArgs {
 
 template <bool GATHERED>
 __global__ __launch_bounds__(256) void distill_loss_bwd(const DsBwdArgs a) {
-    __shared__ float part[2][4][16][64];
+    __shared__ Exchange part, tpart;                              // the student's partial tiles, the teacher's
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int j = lane & 31, half = lane >> 5;
     const int rt = blockIdx.x, dir = blockIdx.y;
@@ -287,11 +264,9 @@ __global__ __launch_bounds__(256) void distill_loss_bwd(const DsBwdArgs a) {
     const float gsum = gc + gd;
     const float coef = a.inv2b * scale;
 
-    f32x16_t acc_o[DS_MAXT];
+    f32x16_t acc_o[MAXT];
 #pragma unroll
-    for (int n = 0; n < DS_MAXT; ++n)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc_o[n][i] = 0.f;
+    for (int n = 0; n < MAXT; ++n) acc_o[n] = zero16();
     float dsc = 0.f;
 
     const int ntiles = (a.ni + 31) >> 5;
@@ -300,40 +275,20 @@ __global__ __launch_bounds__(256) void distill_loss_bwd(const DsBwdArgs a) {
         gi = gi < a.ni ? gi : a.ni - 1;
         const float* yip = XI + (int64_t)gi * a.ldxi + 4 * half;
         const float* uip = UI + (int64_t)gi * a.ldui + 4 * half;
-        f32x16_t acc, tacc;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) { acc[i] = 0.f; tacc[i] = 0.f; }
-        for (int n = 0; n < nown; ++n) {
-            const int e0 = (wave + 4 * n) * 32;
-#pragma unroll
-            for (int k0 = 0; k0 < 32; k0 += 8) {
-                const float4 av = *(const float4*)(yip + e0 + k0);
-                const float4 bv = *(const float4*)(xop + e0 + k0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bv.x, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, bv.y, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, bv.z, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, bv.w, acc, 0, 0, 0);
-            }
-        }
-        for (int k0 = 8 * wave; k0 < a.Et; k0 += 32) {            // the teacher's K in 8-float chunks: wave, wave + 4, ...
-            const float4 av = *(const float4*)(uip + k0);
-            const float4 bv = *(const float4*)(uop + k0);
-            tacc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bv.x, tacc, 0, 0, 0);
-            tacc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, bv.y, tacc, 0, 0, 0);
-            tacc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, bv.z, tacc, 0, 0, 0);
-            tacc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, bv.w, tacc, 0, 0, 0);
-        }
+        const f32x16_t acc = dot_wave<false>(yip, xop, E, wave, nown);
+        f32x16_t tacc = zero16();
+        for (int k0 = 8 * wave; k0 < a.Et; k0 += 32)              // the teacher's K in 8-float chunks: wave, wave + 4, ...
+            tacc = mfma4(*(const float4*)(uip + k0), *(const float4*)(uop + k0), tacc);
         __syncthreads();                                          // the previous tile's partials have been consumed
-#pragma unroll
-        for (int i = 0; i < 16; ++i) { part[0][wave][i][lane] = acc[i]; part[1][wave][i][lane] = tacc[i]; }
+        put(part, wave, lane, acc);
+        put(tpart, wave, lane, tacc);
         __syncthreads();
-        // acc[i] = <XI[t*32 + (i&3) + 8*(i>>2) + 4*half], XO[o]>, summed over the waves in a fixed order; the teacher's alike
         f32x16_t p;
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            const float sdot = ((part[0][0][i][lane] + part[0][1][i][lane]) + part[0][2][i][lane]) + part[0][3][i][lane];
-            const float tdot = ((part[1][0][i][lane] + part[1][1][i][lane]) + part[1][2][i][lane]) + part[1][3][i][lane];
-            const int g = t * 32 + (i & 3) + 8 * (i >> 2) + 4 * half;
+            const float sdot = get(part, i, lane);         // <XI[g], XO[o]>; the teacher's alike
+            const float tdot = get(tpart, i, lane);
+            const int g = t * 32 + tile_row(i, half);
             const bool valid = o < a.no && g < a.ni;
             const int gc_ = g < a.ni ? g : a.ni - 1;
             const float lse_v = GATHERED ? LSE[gc_] : lse_o;
@@ -347,62 +302,13 @@ __global__ __launch_bounds__(256) void distill_loss_bwd(const DsBwdArgs a) {
             p[i] = pv;
             dsc = fmaf(pv, sdot, dsc);
         }
-        // out[o, e] += sum_g G[o, g] * XI[g, e]: contraction step s2 pairs g0(s2) = (s2&3) + 8*(s2>>2) (k = 0, held by the lower
-        // lane half as register s2) with g0(s2) + 4 (k = 1, upper half): the A operand is this lane's own p[s2]
-#pragma unroll
-        for (int n = 0; n < DS_MAXT; ++n) {
-            if (n < nown) {
-                const int e = (wave + 4 * n) * 32 + j;
-#pragma unroll
-                for (int s2 = 0; s2 < 16; ++s2) {
-                    int g = t * 32 + (s2 & 3) + 8 * (s2 >> 2) + 4 * half;
-                    g = g < a.ni ? g : a.ni - 1;
-                    const float yv = XI[(int64_t)g * a.ldxi + e];
-                    acc_o[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(p[s2], yv, acc_o[n], 0, 0, 0);
-                }
-            }
-        }
+        accumulate<MAXT, false, false>(acc_o, p, XI, a.ldxi, t, a.ni, E, wave, nown, j, half);
     }
-#pragma unroll
-    for (int n = 0; n < DS_MAXT; ++n) {
-        if (n < nown) {
-            const int e = (wave + 4 * n) * 32 + j;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const int row = rt * 32 + (i & 3) + 8 * (i >> 2) + 4 * half;
-                if (row < a.no) OUT[(int64_t)row * a.ldout + e] = acc_o[n][i] * coef;
-            }
-        }
-    }
+    store<MAXT, false>(acc_o, OUT, a.ldout, rt, a.no, E, wave, nown, j, half, coef);
     if (!GATHERED) {                                              // d / d scale: every wave holds the same G; wave 0 reports
         dsc = wave_sum(dsc);
         if (wave == 0 && lane == 0) a.dsc_part[dir * a.nrt + rt] = dsc;
     }
-}
-
-__global__ __launch_bounds__(64) void distill_loss_bwd_scale(const float* __restrict__ part, int n, float inv2b,
-                                                             float* __restrict__ d_scale) {
-    float v = 0.f;
-    for (int i = threadIdx.x; i < n; i += 64) v += part[i];
-    v = wave_sum(v);
-    if (threadIdx.x == 0) d_scale[0] = v * inv2b;
-}
-
-struct DsPlan { int bpad, nrt, ntiles, nsplit, tps; };
-
-inline DsPlan ds_plan(int b, int N) {                             // ov_clip_loss's split rule
-    DsPlan p;
-    p.nrt = (b + 31) / 32;
-    p.bpad = p.nrt * 32;
-    p.ntiles = (N + 31) / 32;
-    int want = 1024 / (2 * p.nrt);
-    if (want < 1) want = 1;
-    int maxsplit = (p.ntiles + 3) / 4;
-    if (maxsplit < 1) maxsplit = 1;
-    p.nsplit = want < maxsplit ? want : maxsplit;
-    p.tps = (p.ntiles + p.nsplit - 1) / p.nsplit;
-    p.nsplit = (p.ntiles + p.tps - 1) / p.tps;
-    return p;
 }
 
 // shared by both entry points: sizes, the pitches of the gathered operands, 16-byte alignment of every base pointer
@@ -415,7 +321,7 @@ inline int ds_check(const float* img, const float* txt, const float* all_img, co
     if (((uintptr_t)img | (uintptr_t)txt | (uintptr_t)all_img | (uintptr_t)all_txt | (uintptr_t)t_img | (uintptr_t)t_txt |
          (uintptr_t)t_all_img | (uintptr_t)t_all_txt) & 15)
         return OV_ERR_INVALID;
-    if (E % 32 || E > 4 * DS_MAXT * 32 || Et % 8) return OV_ERR_UNSUPPORTED;
+    if (E % 32 || E > 4 * MAXT * 32 || Et % 8) return OV_ERR_UNSUPPORTED;
     return OV_OK;
 }
 
@@ -424,7 +330,7 @@ inline int ds_check(const float* img, const float* txt, const float* all_img, co
 // workspace: [teacher partials 2 nsplit bpad 2][teacher lse 2 bpad 2][student partials 2 nsplit bpad 3][diag 2 bpad]
 extern "C" size_t ov_distill_loss_workspace_bytes(int b, int N) {
     if (b <= 0 || N <= 0) return 0;
-    const DsPlan p = ds_plan(b, N);
+    const StripPlan p = strip_plan(b, N, 2);
     return ((size_t)2 * p.nsplit * p.bpad * 5 + (size_t)2 * p.bpad * 3) * sizeof(float);
 }
 
@@ -438,7 +344,7 @@ extern "C" int ov_distill_loss(const float* img, const float* txt, const float* 
     if (rc != OV_OK) return rc;
     if ((uintptr_t)workspace & 15) return OV_ERR_INVALID;
     if (workspace_bytes < ov_distill_loss_workspace_bytes(b, N)) return OV_ERR_WORKSPACE;
-    const DsPlan p = ds_plan(b, N);
+    const StripPlan p = strip_plan(b, N, 2);
     DsArgs a;
     a.x[0] = img; a.y[0] = all_txt; a.u[0] = t_img; a.v[0] = t_all_txt;
     a.x[1] = txt; a.y[1] = all_img; a.u[1] = t_txt; a.v[1] = t_all_img;
@@ -503,7 +409,7 @@ extern "C" int ov_distill_loss_backward(const float* img, const float* txt, cons
     hipLaunchKernelGGL(distill_loss_bwd<false>, dim3((unsigned)a.nrt, 2), dim3(256), 0, st, a);
     OV_LAUNCH_CHECK();
     if (d_scale) {
-        hipLaunchKernelGGL(distill_loss_bwd_scale, dim3(1), dim3(64), 0, st, a.dsc_part, 2 * a.nrt, inv2b, d_scale);
+        hipLaunchKernelGGL(scaled_sum<64>, dim3(1), dim3(64), 0, st, a.dsc_part, 2 * a.nrt, inv2b, nullptr, d_scale);
         OV_LAUNCH_CHECK();
     }
     if (d_all_img || d_all_txt) {

@@ -4,20 +4,22 @@
 // (src/losses/common.py:120-189) takes four log-softmax strips per rank and averages them.  With C sets stacked [C b, E]:
 //     A_c = s img all_txt_c^T [b, N],   B_c = s txt_c all_img^T [b, N]
 //     loss = 1 / (2 C b) sum_c sum_i [ lse(A_c[i, :]) - A_c[i, i + off] + lse(B_c[i, :]) - B_c[i, i + off] ]
-// i.e. the mean over c of ov_clip_loss(img, txt_c).  The building blocks are loss.hip's: exact-fp32 v_mfma_f32_32x32x2_f32 logit
-// tiles that are never written, the gathered side as the MFMA A operand (row reductions are lane-local), partial + finalize,
-// no atomics, fixed summation order.  What is new here:
+// i.e. the mean over c of the InfoNCE of (img, txt_c); ov_clip_loss (loss.hip) is this file at C = 1.  The building blocks are
+// strip.h's: exact-fp32 v_mfma_f32_32x32x2_f32 logit tiles that are never written, the gathered side as the MFMA A operand (row
+// reductions are lane-local).  Only a running (max, sum-exp) pair per local row plus the diagonal logit leave the forward kernel.
+// Two launches, no atomics, deterministic: partials per (strip, column split, row) -> finalize.  Beyond one pair of strips:
 //   * the 2 C strips are the forward grid's third dimension (strip 2c: img rows x all_txt_c, strip 2c + 1: txt_c rows x all_img);
 //   * the backward of the image side runs its in-side loop over the C sets INSIDE the kernel, into the same [32 x E] accumulators,
 //     and stores once: no C partial gradients to add afterwards;
 //   * the gathered operands and their gradients carry a row pitch and a per-set stride, so the all-gather's packed
 //     [N, (1 + C) E] buffer is read in place and the gathered-side gradient is written packed for one reduce-scatter.
-#include "common.h"
+#include "strip.h"
 
 namespace {
 
+using namespace strip;
+
 constexpr int MC_MAXC = 4;           // caption sets per image
-constexpr int MC_MAXT = 9;           // backward: e-tiles per wave, E <= 4 * 9 * 32 = 1152
 
 struct McArgs {
     const float* img;       // [b, E]
@@ -53,23 +55,11 @@ __global__ __launch_bounds__(256) void multicap_logits_partial(const McArgs a) {
         int gi = t * 32 + j;
         gi = gi < a.N ? gi : a.N - 1;
         const float* yp = Y + (int64_t)gi * a.ld + 4 * half;
-        f32x16_t acc;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-#pragma unroll 4
-        for (int k0 = 0; k0 < a.E; k0 += 8) {
-            const float4 av = *(const float4*)(yp + k0);
-            const float4 bv = *(const float4*)(xp + k0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bv.x, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, bv.y, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, bv.z, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, bv.w, acc, 0, 0, 0);
-        }
-        // acc[i] = <Y[t*32 + (i&3) + 8*(i>>2) + 4*half], X[row]>
+        f32x16_t acc = dot_full(yp, xp, a.E);                     // acc[i] = <Y[t * 32 + tile_row(i, half)], X[row]>
         float mx = -INFINITY;
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            const int g = t * 32 + (i & 3) + 8 * (i >> 2) + 4 * half;
+            const int g = t * 32 + tile_row(i, half);
             float v = acc[i] * scale;
             if (g == label && row < a.b) a.diag[strip * a.bpad + row] = v;
             if (g >= a.N) v = -INFINITY;
@@ -86,23 +76,13 @@ __global__ __launch_bounds__(256) void multicap_logits_partial(const McArgs a) {
         }
     }
     // combine the two lane halves of each row, then the four waves
-    {
-        const float mo = __shfl_xor(m, 32, 64), so = __shfl_xor(s, 32, 64);
-        const float mn = fmaxf(m, mo);
-        if (mn > -INFINITY) s = s * __expf(m - mn) + so * __expf(mo - mn);
-        m = mn;
-    }
+    lse_merge_halves(m, s);
     if (half == 0) { red[wave][j][0] = m; red[wave][j][1] = s; }
     __syncthreads();
     if (wave == 0 && half == 0 && row < a.b) {
         float M = red[0][j][0], S = red[0][j][1];
 #pragma unroll
-        for (int w = 1; w < 4; ++w) {
-            const float mw = red[w][j][0], sw = red[w][j][1];
-            const float mn = fmaxf(M, mw);
-            if (mn > -INFINITY) S = S * __expf(M - mn) + sw * __expf(mw - mn);
-            M = mn;
-        }
+        for (int w = 1; w < 4; ++w) lse_merge(M, S, red[w][j][0], red[w][j][1]);
         float* p = a.part + (((int64_t)strip * a.nsplit + split) * a.bpad + row) * 2;
         p[0] = M; p[1] = S;
     }
@@ -116,14 +96,8 @@ __global__ __launch_bounds__(256) void multicap_loss_finalize(const float* __res
     float local = 0.f;
     for (int i = threadIdx.x; i < nstrips * b; i += blockDim.x) {
         const int strip = i / b, row = i - strip * b;
-        float M = -INFINITY, S = 0.f;
-        for (int sp = 0; sp < nsplit; ++sp) {
-            const float* p = part + (((int64_t)strip * nsplit + sp) * bpad + row) * 2;
-            const float mw = p[0], sw = p[1];
-            const float mn = fmaxf(M, mw);
-            if (mn > -INFINITY) S = S * __expf(M - mn) + sw * __expf(mw - mn);
-            M = mn;
-        }
+        float M, S;
+        lse_merge_splits(part + ((int64_t)strip * nsplit * bpad + row) * 2, (int64_t)bpad * 2, nsplit, M, S);
         const float lse = M + logf(S);
         const float d = diag[strip * bpad + row];
         if (terms) {
@@ -139,8 +113,9 @@ __global__ __launch_bounds__(256) void multicap_loss_finalize(const float* __res
 }
 
 // ---- backward ------------------------------------------------------------------------------------------------------------------
-// As clip_loss_bwd (loss.hip): P = exp(s S - lse) - [label] per recomputed 32 x 32 logit tile, out += P . X_in in [32 x E] MFMA
-// accumulators split over the four waves by e-tile, one workgroup per 32-row out tile, the in-side loop not split.
+// d loss / d logits = (softmax - onehot) / (2 C b) per strip.  P = exp(s S - lse) - [label] is formed in registers per recomputed
+// 32 x 32 logit tile from the forward's per-row lse, and out += P . X_in accumulates in [32 x E] MFMA accumulators split over the
+// four waves by e-tile (strip.h).  One workgroup per 32-row out tile; the in-side loop is not split, so the result is deterministic.
 // blockIdx.y is the job: 0 = the image side, whose in-side loop runs over all C sets; 1 + c = the text side of set c.
 //   GATHERED = false: out rows are LOCAL rows, lse by out row
 //       job 0    : d img      = coef sum_c P_img,c . all_txt_c          job 1 + c: d txt_c     = coef P_txt,c . all_img
@@ -165,7 +140,7 @@ struct McBwdArgs {
 
 template <bool GATHERED>
 __global__ __launch_bounds__(256) void multicap_loss_bwd(const McBwdArgs a) {
-    __shared__ float part[4][16][64];
+    __shared__ Exchange part;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int j = lane & 31, half = lane >> 5;
     const int rt = blockIdx.x, job = blockIdx.y;
@@ -205,11 +180,9 @@ __global__ __launch_bounds__(256) void multicap_loss_bwd(const McBwdArgs a) {
     const float scale = *a.scale;
     const float coef = (a.grad ? *a.grad : 1.f) * a.inv2cb * scale;
 
-    f32x16_t acc_o[MC_MAXT];
+    f32x16_t acc_o[MAXT];
 #pragma unroll
-    for (int n = 0; n < MC_MAXT; ++n)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc_o[n][i] = 0.f;
+    for (int n = 0; n < MAXT; ++n) acc_o[n] = zero16();
     float dsc = 0.f;
 
     const int ntiles = (ni + 31) >> 5;
@@ -221,31 +194,15 @@ __global__ __launch_bounds__(256) void multicap_loss_bwd(const McBwdArgs a) {
             int gi = t * 32 + j;
             gi = gi < ni ? gi : ni - 1;
             const float* yip = XI + (int64_t)gi * ldxi + 4 * half;
-            f32x16_t acc;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-            for (int n = 0; n < nown; ++n) {
-                const int e0 = (wave + 4 * n) * 32;
-#pragma unroll
-                for (int k0 = 0; k0 < 32; k0 += 8) {
-                    const float4 av = *(const float4*)(yip + e0 + k0);
-                    const float4 bv = *(const float4*)(xop + e0 + k0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bv.x, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, bv.y, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, bv.z, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, bv.w, acc, 0, 0, 0);
-                }
-            }
+            const f32x16_t acc = dot_wave<false>(yip, xop, E, wave, nown);
             __syncthreads();                                      // the previous tile's partials have been consumed
-#pragma unroll
-            for (int i = 0; i < 16; ++i) part[wave][i][lane] = acc[i];
+            put(part, wave, lane, acc);
             __syncthreads();
-            // acc[i] = <XI[t*32 + (i&3) + 8*(i>>2) + 4*half], XO[o]>, summed over the waves in a fixed order
             f32x16_t p;
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
-                const float sdot = ((part[0][i][lane] + part[1][i][lane]) + part[2][i][lane]) + part[3][i][lane];
-                const int g = t * 32 + (i & 3) + 8 * (i >> 2) + 4 * half;
+                const float sdot = get(part, i, lane);            // <XI[g], XO[o]>
+                const int g = t * 32 + tile_row(i, half);
                 const bool valid = o < no && g < ni;
                 const float lse_v = GATHERED ? LSE[g < ni ? g : ni - 1] : lse_o;
                 const bool hit = GATHERED ? (o == g + a.label_offset) : (g == o + a.label_offset);
@@ -253,64 +210,14 @@ __global__ __launch_bounds__(256) void multicap_loss_bwd(const McBwdArgs a) {
                 p[i] = pv;
                 dsc = fmaf(pv, sdot, dsc);
             }
-            // out[o, e] += sum_g P[o, g] * XI[g, e]: contraction step s2 pairs g0(s2) = (s2&3) + 8*(s2>>2) (k = 0, held by the
-            // lower lane half as register s2) with g0(s2) + 4 (k = 1, upper half): the A operand is this lane's own p[s2]
-#pragma unroll
-            for (int n = 0; n < MC_MAXT; ++n) {
-                if (n < nown) {
-                    const int e = (wave + 4 * n) * 32 + j;
-#pragma unroll
-                    for (int s2 = 0; s2 < 16; ++s2) {
-                        int g = t * 32 + (s2 & 3) + 8 * (s2 >> 2) + 4 * half;
-                        g = g < ni ? g : ni - 1;
-                        const float yv = XI[(int64_t)g * ldxi + e];
-                        acc_o[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(p[s2], yv, acc_o[n], 0, 0, 0);
-                    }
-                }
-            }
+            accumulate<MAXT, false, true>(acc_o, p, XI, ldxi, t, ni, E, wave, nown, j, half);
         }
     }
-    const int64_t ldout = GATHERED ? a.ldo : (int64_t)E;
-#pragma unroll
-    for (int n = 0; n < MC_MAXT; ++n) {
-        if (n < nown) {
-            const int e = (wave + 4 * n) * 32 + j;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const int row = rt * 32 + (i & 3) + 8 * (i >> 2) + 4 * half;
-                if (row < no) OUT[(int64_t)row * ldout + e] = acc_o[n][i] * coef;
-            }
-        }
-    }
+    store<MAXT, false>(acc_o, OUT, GATHERED ? a.ldo : (int64_t)E, rt, no, E, wave, nown, j, half, coef);
     if (!GATHERED) {                                              // d loss / d scale: every wave holds the same P; wave 0 reports
         dsc = wave_sum(dsc);
         if (wave == 0 && lane == 0) a.dsc_part[job * a.nrt + rt] = dsc;
     }
-}
-
-__global__ __launch_bounds__(64) void multicap_loss_bwd_scale(const float* __restrict__ part, int n, float inv2cb,
-                                                              const float* __restrict__ grad, float* __restrict__ d_scale) {
-    float v = 0.f;
-    for (int i = threadIdx.x; i < n; i += 64) v += part[i];
-    v = wave_sum(v);
-    if (threadIdx.x == 0) d_scale[0] = v * inv2cb * (grad ? *grad : 1.f);
-}
-
-struct McPlan { int bpad, nrt, ntiles, nsplit, tps; };
-
-inline McPlan mc_plan(int b, int N, int C) {
-    McPlan p;
-    p.nrt = (b + 31) / 32;
-    p.bpad = p.nrt * 32;
-    p.ntiles = (N + 31) / 32;
-    int want = 1024 / (2 * C * p.nrt);
-    if (want < 1) want = 1;
-    int maxsplit = (p.ntiles + 3) / 4;
-    if (maxsplit < 1) maxsplit = 1;
-    p.nsplit = want < maxsplit ? want : maxsplit;
-    p.tps = (p.ntiles + p.nsplit - 1) / p.nsplit;
-    p.nsplit = (p.ntiles + p.tps - 1) / p.tps;
-    return p;
 }
 
 // shared by both entry points: sizes, the pitch of the gathered operands, 16-byte alignment of every row
@@ -329,7 +236,7 @@ inline int mc_check(const float* img, const float* txt, const float* all_img, co
 
 extern "C" size_t ov_clip_loss_multi_workspace_bytes(int b, int N, int C) {
     if (b <= 0 || N <= 0 || C < 1 || C > MC_MAXC) return 0;
-    const McPlan p = mc_plan(b, N, C);
+    const StripPlan p = strip_plan(b, N, 2 * C);
     return ((size_t)2 * C * p.nsplit * p.bpad * 2 + (size_t)2 * C * p.bpad) * sizeof(float);
 }
 
@@ -342,7 +249,7 @@ extern "C" int ov_clip_loss_multi(const float* img, const float* txt, const floa
     if (E % 8) return OV_ERR_UNSUPPORTED;
     if ((uintptr_t)workspace & 15) return OV_ERR_INVALID;
     if (workspace_bytes < ov_clip_loss_multi_workspace_bytes(b, N, C)) return OV_ERR_WORKSPACE;
-    const McPlan p = mc_plan(b, N, C);
+    const StripPlan p = strip_plan(b, N, 2 * C);
     McArgs a;
     a.img = img; a.txt = txt; a.all_img = all_img; a.all_txt = all_txt; a.ld = ld; a.set_stride = set_stride;
     a.part = (float*)workspace;
@@ -371,7 +278,7 @@ extern "C" int ov_clip_loss_multi_backward(const float* img, const float* txt, c
     if (!terms || !d_img || !d_txt || !workspace || !logit_scale) return OV_ERR_INVALID;
     const int rc = mc_check(img, txt, all_img, all_txt, ld, set_stride, b, N, E, C, label_offset);
     if (rc != OV_OK) return rc;
-    if (E % 32 || E > 4 * MC_MAXT * 32) return OV_ERR_UNSUPPORTED;
+    if (E % 32 || E > 4 * MAXT * 32) return OV_ERR_UNSUPPORTED;
     if (((uintptr_t)d_img | (uintptr_t)d_txt | (uintptr_t)workspace) & 15) return OV_ERR_INVALID;
     if (d_all_img || d_all_txt) {
         if (ldg < E || (ldg & 3) || gset_stride < 0 || (gset_stride & 3)) return OV_ERR_INVALID;
@@ -391,7 +298,7 @@ extern "C" int ov_clip_loss_multi_backward(const float* img, const float* txt, c
     hipLaunchKernelGGL(multicap_loss_bwd<false>, dim3((unsigned)a.nrt, (unsigned)(1 + C)), dim3(256), 0, st, a);
     OV_LAUNCH_CHECK();
     if (d_scale) {
-        hipLaunchKernelGGL(multicap_loss_bwd_scale, dim3(1), dim3(64), 0, st, a.dsc_part, (1 + C) * a.nrt, inv2cb, grad_loss, d_scale);
+        hipLaunchKernelGGL(scaled_sum<64>, dim3(1), dim3(64), 0, st, a.dsc_part, (1 + C) * a.nrt, inv2cb, grad_loss, d_scale);
         OV_LAUNCH_CHECK();
     }
     if (d_all_img || d_all_txt) {

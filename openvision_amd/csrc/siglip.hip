@@ -6,12 +6,12 @@
 //     loss    = (1 / b) * sum_{i < b, j < N} softplus(-l z)            (= -logsigmoid(l z), loss.py:349-358)
 // x = the local image rows [b, E], y = the gathered text rows [N, E] in rank order.  Each (i, j) term is independent (no softmax,
 // no row statistic), so the forward keeps nothing for the backward.  Logit tiles live in one f32x16 MFMA accumulator
-// (exact-fp32 v_mfma_f32_32x32x2_f32, as loss.hip); they are never written.  No atomics: every sum has a fixed order.
-#include "common.h"
+// (exact-fp32 v_mfma_f32_32x32x2_f32, strip.h); they are never written.  No atomics: every sum has a fixed order.
+#include "strip.h"
 
 namespace {
 
-constexpr int SIG_MAXT = 9;          // e-tiles per wave in the backward: E <= 4 * 9 * 32 = 1152
+using namespace strip;
 
 struct SigArgs {
     const float* x;         // local rows   [b, E]
@@ -45,22 +45,10 @@ __global__ __launch_bounds__(256) void siglip_loss_partial(const SigArgs a) {
         int gi = t * 32 + j;
         gi = gi < a.N ? gi : a.N - 1;
         const float* yp = a.y + (int64_t)gi * a.E + 4 * half;
-        f32x16_t acc;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-#pragma unroll 4
-        for (int k0 = 0; k0 < a.E; k0 += 8) {
-            const float4 av = *(const float4*)(yp + k0);
-            const float4 bv = *(const float4*)(xp + k0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bv.x, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, bv.y, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, bv.z, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, bv.w, acc, 0, 0, 0);
-        }
-        // acc[i] = <y[t*32 + (i&3) + 8*(i>>2) + 4*half], x[row]>
+        const f32x16_t acc = dot_full(yp, xp, a.E);               // acc[i] = <y[t * 32 + tile_row(i, half)], x[row]>
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            const int g = t * 32 + (i & 3) + 8 * (i >> 2) + 4 * half;
+            const int g = t * 32 + tile_row(i, half);
             const float z = fmaf(acc[i], scale, beta);
             const float u = g == label ? -z : z;                   // softplus(-l z)
             if (g < a.N && row < a.b) sum += softplus_stable(u);
@@ -88,7 +76,7 @@ __global__ __launch_bounds__(256) void siglip_loss_finalize(const float* __restr
 // g[i, j] = d loss / d z[i, j] = -l sigmoid(-l z) / b * grad_loss.  The logit tiles are recomputed with the same exact-fp32 MFMA,
 // g is formed in registers, and the product g . X_in accumulates into [32 rows x E] fp32 MFMA accumulators split over the four
 // waves of a workgroup by 32-column e-tile (the last e-tile may be partial: E % 8 == 0).  The logit tile's K reduction is split
-// the same way and summed through LDS in a fixed order, as clip_loss_bwd does.
+// the same way and summed through LDS in a fixed order (strip.h, RAGGED = true).
 //   MODE_B = false: out rows = LOCAL rows x:      d x[i] = s * sum_j g[i, j] * y[j]     (+ per-tile partials of d s, d beta)
 //   MODE_B = true : out rows = GATHERED rows y:   d y[j] = s * sum_i g[i, j] * x[i]
 // One launch holds both: workgroups [0, nrt_x) take local row tiles (each a sweep over all N gathered rows), the rest take
@@ -108,7 +96,7 @@ struct SigBwdArgs {
 };
 
 template <bool MODE_B>
-__device__ __forceinline__ void siglip_bwd_tile(const SigBwdArgs& a, int rt, float (*part)[16][64]) {
+__device__ __forceinline__ void siglip_bwd_tile(const SigBwdArgs& a, int rt, Exchange part) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int j = lane & 31, half = lane >> 5;
     const float* __restrict__ XO = MODE_B ? a.y : a.x;
@@ -124,11 +112,9 @@ __device__ __forceinline__ void siglip_bwd_tile(const SigBwdArgs& a, int rt, flo
     const float beta = a.bias ? *a.bias : 0.f;
     const float gl = (a.grad ? *a.grad : 1.f) * a.inv_b;
 
-    f32x16_t acc_o[SIG_MAXT];
+    f32x16_t acc_o[MAXT];
 #pragma unroll
-    for (int n = 0; n < SIG_MAXT; ++n)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc_o[n][i] = 0.f;
+    for (int n = 0; n < MAXT; ++n) acc_o[n] = zero16();
     float dsc = 0.f, dbs = 0.f;
 
     const int ntiles = (ni + 31) >> 5;
@@ -136,34 +122,15 @@ __device__ __forceinline__ void siglip_bwd_tile(const SigBwdArgs& a, int rt, flo
         int gi = t * 32 + j;
         gi = gi < ni ? gi : ni - 1;
         const float* yip = XI + (int64_t)gi * E + 4 * half;
-        f32x16_t acc;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-        for (int n = 0; n < nown; ++n) {
-            const int e0 = (wave + 4 * n) * 32;
-            const int kend = E - e0 < 32 ? E - e0 : 32;
-#pragma unroll
-            for (int k0 = 0; k0 < 32; k0 += 8) {
-                if (k0 < kend) {
-                    const float4 av = *(const float4*)(yip + e0 + k0);
-                    const float4 bv = *(const float4*)(xop + e0 + k0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bv.x, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, bv.y, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, bv.z, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, bv.w, acc, 0, 0, 0);
-                }
-            }
-        }
+        const f32x16_t acc = dot_wave<true>(yip, xop, E, wave, nown);
         __syncthreads();                                          // the previous tile's partials have been consumed
-#pragma unroll
-        for (int i = 0; i < 16; ++i) part[wave][i][lane] = acc[i];
+        put(part, wave, lane, acc);
         __syncthreads();
-        // acc[i] = <XI[t*32 + (i&3) + 8*(i>>2) + 4*half], XO[o]>, summed over the waves in a fixed order
         f32x16_t p;
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            const float sdot = ((part[0][i][lane] + part[1][i][lane]) + part[2][i][lane]) + part[3][i][lane];
-            const int g = t * 32 + (i & 3) + 8 * (i >> 2) + 4 * half;
+            const float sdot = get(part, i, lane);                // <XI[g], XO[o]>
+            const int g = t * 32 + tile_row(i, half);
             const bool valid = o < no && g < ni;
             const bool hit = MODE_B ? (o == g + a.label_offset) : (g == o + a.label_offset);
             const float z = fmaf(sdot, scale, beta);
@@ -173,37 +140,9 @@ __device__ __forceinline__ void siglip_bwd_tile(const SigBwdArgs& a, int rt, flo
             dsc = fmaf(gv, sdot, dsc);
             dbs += gv;
         }
-        // out[o, e] += sum_g p[o, g] * XI[g, e]: contraction step s pairs g0(s) = (s&3) + 8*(s>>2) (k = 0, held by the lower lane
-        // half as register s) with g0(s) + 4 (k = 1, upper half): the A operand is this lane's own p[s]
-#pragma unroll
-        for (int n = 0; n < SIG_MAXT; ++n) {
-            if (n < nown) {
-                int e = (wave + 4 * n) * 32 + j;
-                e = e < E ? e : E - 1;                            // columns past E of a partial e-tile: read in range, never stored
-#pragma unroll
-                for (int s2 = 0; s2 < 16; ++s2) {
-                    int g = t * 32 + (s2 & 3) + 8 * (s2 >> 2) + 4 * half;
-                    g = g < ni ? g : ni - 1;
-                    const float yv = XI[(int64_t)g * E + e];
-                    acc_o[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(p[s2], yv, acc_o[n], 0, 0, 0);
-                }
-            }
-        }
+        accumulate<MAXT, true, true>(acc_o, p, XI, E, t, ni, E, wave, nown, j, half);
     }
-    const float coef = gl * scale;
-#pragma unroll
-    for (int n = 0; n < SIG_MAXT; ++n) {
-        if (n < nown) {
-            const int e = (wave + 4 * n) * 32 + j;
-            if (e < E) {
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const int row = rt * 32 + (i & 3) + 8 * (i >> 2) + 4 * half;
-                    if (row < no) OUT[(int64_t)row * E + e] = acc_o[n][i] * coef;
-                }
-            }
-        }
-    }
+    store<MAXT, true>(acc_o, OUT, E, rt, no, E, wave, nown, j, half, gl * scale);
     if (!MODE_B) {                                                // every wave holds the same p: wave 0 reports
         dsc = wave_sum(dsc);
         dbs = wave_sum(dbs);
@@ -215,7 +154,7 @@ __device__ __forceinline__ void siglip_bwd_tile(const SigBwdArgs& a, int rt, flo
 }
 
 __global__ __launch_bounds__(256) void siglip_loss_bwd(const SigBwdArgs a) {
-    __shared__ float part[4][16][64];
+    __shared__ Exchange part;
     const int bid = blockIdx.x;
     if (bid < a.nrt_x) siglip_bwd_tile<false>(a, bid, part);
     else siglip_bwd_tile<true>(a, bid - a.nrt_x, part);
@@ -239,26 +178,10 @@ __global__ __launch_bounds__(64) void siglip_loss_bwd_scalars(const float* __res
     }
 }
 
-struct SigPlan { int nrt, ntiles, nsplit, tps; };
-
-inline SigPlan sig_plan(int b, int N) {
-    SigPlan p;
-    p.nrt = (b + 31) / 32;
-    p.ntiles = (N + 31) / 32;
-    int want = 1024 / p.nrt;                                      // ~1024 workgroups: four per CU
-    if (want < 1) want = 1;
-    int maxsplit = (p.ntiles + 3) / 4;                            // at least four column tiles (one per wave) per split
-    if (maxsplit < 1) maxsplit = 1;
-    p.nsplit = want < maxsplit ? want : maxsplit;
-    p.tps = (p.ntiles + p.nsplit - 1) / p.nsplit;
-    p.nsplit = (p.ntiles + p.tps - 1) / p.tps;
-    return p;
-}
-
 inline int sig_check(const float* x, const float* y, const float* scale, int b, int N, int E, int label_offset) {
     if (!x || !y || !scale) return OV_ERR_INVALID;
     if (b <= 0 || N <= 0 || E <= 0 || label_offset < 0 || (int64_t)label_offset + b > N) return OV_ERR_INVALID;
-    if (E % 8 || E > 4 * SIG_MAXT * 32) return OV_ERR_UNSUPPORTED;
+    if (E % 8 || E > 4 * MAXT * 32) return OV_ERR_UNSUPPORTED;
     if (((uintptr_t)x | (uintptr_t)y) & 15) return OV_ERR_INVALID;
     return OV_OK;
 }
@@ -267,7 +190,7 @@ inline int sig_check(const float* x, const float* y, const float* scale, int b, 
 
 extern "C" size_t ov_siglip_loss_workspace_bytes(int b, int N) {
     if (b <= 0 || N <= 0) return 0;
-    const SigPlan p = sig_plan(b, N);
+    const StripPlan p = strip_plan(b, N, 1);                      // one strip: x rows against y
     return (size_t)p.nrt * p.nsplit * sizeof(float);
 }
 
@@ -278,7 +201,7 @@ extern "C" int ov_siglip_loss(const float* img, const float* all_txt, int b, int
     if (rc != OV_OK) return rc;
     if (!loss_out || !workspace) return OV_ERR_INVALID;
     if (workspace_bytes < ov_siglip_loss_workspace_bytes(b, N)) return OV_ERR_WORKSPACE;
-    const SigPlan p = sig_plan(b, N);
+    const StripPlan p = strip_plan(b, N, 1);                      // one strip: x rows against y
     SigArgs a;
     a.x = img; a.y = all_txt; a.part = (float*)workspace;
     a.b = b; a.N = N; a.E = E; a.nsplit = p.nsplit; a.tiles_per_split = p.tps; a.ntiles = p.ntiles; a.label_offset = label_offset;

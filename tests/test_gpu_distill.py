@@ -145,7 +145,7 @@ def test_kernel_against_the_reference_fixture(case):
 
 
 def split_rule(b, N):
-    """csrc/distill.hip ds_plan (ov_clip_loss's rule) restated: (column splits, 32-column tiles per split)."""
+    """csrc/strip.h strip_plan with two strips (ov_clip_loss's rule) restated: (column splits, 32-column tiles per split)."""
     nrt, ntiles = (b + 31) // 32, (N + 31) // 32
     nsplit = min(max(1024 // (2 * nrt), 1), max((ntiles + 3) // 4, 1))
     tps = (ntiles + nsplit - 1) // nsplit

@@ -1,5 +1,5 @@
 """Per-kernel table of ONE training step out of a rocprofv3 --kernel-trace of tools/train_step_probe.py: the window between the last
-two clip_loss_bwd launches (= the backward of step n-1 and the forward of step n: one step's worth of launches, back to back).
+two multicap_loss_bwd<false> launches, the kernel ov_clip_loss_backward runs (= the backward of step n-1 and the forward of step n: one step's worth of launches, back to back).
 Usage: python tools/train_step_table.py gpurun_out/prof_train/run_kernel_trace.csv [out.md]"""
 import collections, csv, re, sys
 
@@ -14,7 +14,7 @@ def short(n):
     return (m.group(1) if m else n)[:80]
 
 
-marks = [i for i, r in enumerate(rows) if "clip_loss_bwd<false>" in r["Kernel_Name"]]
+marks = [i for i, r in enumerate(rows) if "multicap_loss_bwd<false>" in r["Kernel_Name"]]
 i0, i1 = marks[-2], marks[-1]
 t0, t1 = int(rows[i0]["Start_Timestamp"]), int(rows[i1]["Start_Timestamp"])
 agg = collections.defaultdict(lambda: [0, 0])

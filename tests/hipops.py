@@ -314,11 +314,21 @@ def tower1_forward_backward(cfg, weights, x, dy, B, L):
     return y, dx, grads
 
 
-def attention_backward(qkv, out, dout, B, L, H, hd=64):
+def _bwd_buffers(qkv, dqkv, ws, nb):
+    """dqkv=: a caller-owned [B*L, 3 H hd] bf16 tensor, e.g. a column slice of a wider one (its pitch is stride(0)); ws=: a caller-owned
+    uint8 workspace, handed over with its own size (e.g. a view of exactly `nb` bytes, to watch what lies behind it)."""
+    if dqkv is None:
+        dqkv = torch.empty_like(qkv)
+    assert dqkv.shape == qkv.shape and dqkv.dtype == torch.bfloat16 and dqkv.stride(1) == 1, (dqkv.shape, dqkv.dtype, dqkv.stride())
+    if ws is None:
+        return dqkv, torch.empty(nb + 256, dtype=torch.uint8, device=qkv.device), nb
+    assert ws.dtype == torch.uint8 and ws.is_contiguous()
+    return dqkv, ws, ws.numel()
+
+
+def attention_backward(qkv, out, dout, B, L, H, hd=64, dqkv=None, ws=None):
     lib = _lib.load()
-    dqkv = torch.empty_like(qkv)
-    nb = lib.ov_attention_backward_workspace_bytes(B, L, H, hd)
-    ws = torch.empty(nb + 256, dtype=torch.uint8, device=qkv.device)
+    dqkv, ws, nb = _bwd_buffers(qkv, dqkv, ws, lib.ov_attention_backward_workspace_bytes(B, L, H, hd))
     check(lib.ov_attention_backward(ptr(qkv), qkv.stride(0), ptr(out), out.stride(0), ptr(dout), dout.stride(0), ptr(dqkv), dqkv.stride(0),
                                     B, L, H, hd, hd ** -0.5, ptr(ws), nb, stream_ptr()), "ov_attention_backward")
     return dqkv
@@ -334,11 +344,9 @@ def attention_lse(qkv, B, L, H, hd=64):
     return out, lse
 
 
-def attention_backward_saved(qkv, out, dout, lse, B, L, H, hd=64):
+def attention_backward_saved(qkv, out, dout, lse, B, L, H, hd=64, dqkv=None, ws=None):
     lib = _lib.load()
-    dqkv = torch.empty_like(qkv)
-    nb = lib.ov_attention_backward_workspace_bytes(B, L, H, hd)
-    ws = torch.empty(nb + 256, dtype=torch.uint8, device=qkv.device)
+    dqkv, ws, nb = _bwd_buffers(qkv, dqkv, ws, lib.ov_attention_backward_workspace_bytes(B, L, H, hd))
     check(lib.ov_attention_backward_saved(ptr(qkv), qkv.stride(0), ptr(out), out.stride(0), ptr(dout), dout.stride(0), ptr(dqkv),
                                           dqkv.stride(0), ptr(lse), B, L, H, hd, hd ** -0.5, ptr(ws), nb, stream_ptr()),
           "ov_attention_backward_saved")
@@ -383,7 +391,8 @@ def attn_ref64(qkv, B, L, Hh, hd):
 
 
 def bound(ref, pv):
-    """Per-element bound: bf16 output rounding + P rounded to bf16 before P.V (each <= 2^-9 of its term; 2x headroom)."""
+    """Per-element bound: bf16 output rounding + P rounded to bf16 before P.V (each <= 2^-8 of its term, bf16's unit roundoff: REL is
+    that figure with no factor on top)."""
     return REL * ref.abs() + REL * pv + 1e-6
 
 
@@ -419,3 +428,100 @@ def spiked_qkv(B, L, Hh, hd, seed, deltas=(4.0, 20.0)):
 
 # the spiked shapes: hd 64 persistent (257), hd 64 streaming (321, 2305), generic chunked (321 at hd 72, 577 at hd 80)
 LONE_SPIKED = [(1, 257, 2, 64), (1, 321, 2, 64), (1, 2305, 2, 64), (1, 321, 2, 72), (1, 577, 2, 80)]
+
+
+# ---- attention backward: an fp64 closed form with per-element bounds on dQ, dK, dV (test_gpu_attention_bwd_edges.py)
+
+U_BWD = 2.0 ** -7                # twice bf16's unit roundoff 2^-8 (8 significant bits): derived in bwd_bound, not measured
+
+
+def _heads(t, B, L, Hh, hd):
+    """[B*L, >= Hh hd] -> [B, Hh, L, hd] fp64."""
+    return t[:, :Hh * hd].double().view(B, L, Hh, hd).transpose(1, 2)
+
+
+def _rows(t):
+    """[B, Hh, L, hd] -> [B*L, Hh hd]."""
+    B, Hh, L, hd = t.shape
+    return t.transpose(1, 2).reshape(B * L, Hh * hd)
+
+
+class BwdRef:
+    """What attn_grads_ref64 returns: dq, dk, dv, o, pv as [B*L, Hh*hd] and p, ds as [B, Hh, L, L], all fp64; q, k, v, do (the inputs
+    per head, [B, Hh, L, hd] fp64) and scale ride along for bwd_bound."""
+
+
+def attn_grads_ref64(qkv, dout, B, L, Hh, hd, mask=None):
+    """The attention backward in closed form, fp64 on the (bf16) inputs -- not autograd, because the bound needs P and dS:
+        S = scale Q K^T, P = softmax(S) (0 for a pair the [L, L] bool `mask` hides), O = P V, delta = rowsum(dO * O),
+        dV = P^T dO, dS = P * (dO V^T - delta), dQ = scale dS K, dK = scale dS^T Q.
+    Also pv = P.|V| (the forward bound's second term)."""
+    ref = BwdRef()
+    ref.q, ref.k, ref.v = q, k, v = _split(qkv, B, L, Hh, hd)
+    ref.do = do = _heads(dout, B, L, Hh, hd)
+    ref.scale = scale = hd ** -0.5
+    s = q @ k.transpose(-1, -2) * scale
+    if mask is not None:
+        s = s.masked_fill(~mask, float("-inf"))
+    ref.p = p = torch.softmax(s, dim=-1)
+    o = p @ v
+    ref.ds = ds = p * (do @ v.transpose(-1, -2) - (do * o).sum(-1, keepdim=True))
+    ref.o, ref.pv = _rows(o), _rows(p @ v.abs())
+    ref.dq, ref.dk, ref.dv = _rows(ds @ k * scale), _rows(ds.transpose(-1, -2) @ q * scale), _rows(p.transpose(-1, -2) @ do)
+    return ref
+
+
+def bwd_bound(ref, q, k, v, do, scale, eo):
+    """Per-element bounds (bound_dq, bound_dk, bound_dv), each [B*L, Hh*hd] fp64.  eo [B*L, Hh*hd]: a bound on |out - O| of the `out`
+    tensor the kernel is handed (it forms delta from it).  With U = 2^-7:
+        Ed[q]    = sum_d |dO[q, d]| eo[q, d]                   the error of delta
+        W        = U |dS| + P Ed                               the error of the bf16 dS that enters the second products
+        bound_dV = U |dV| + U (P^T |dO|)        + 1e-6         output rounding + P rounded to bf16
+        bound_dQ = U |dQ| + scale (W |K|)       + 1e-6
+        bound_dK = U |dK| + scale (W^T |Q|)     + 1e-6
+    The kernels round P and dS to bf16 before the second products and their outputs to bf16; each such rounding is at most 2^-8 of
+    its magnitude (bf16 has 8 significant bits).  With every rounding aligned the error is the expression above at 2^-8; U is twice
+    that, which covers the fp32 exp2 / log2 and the accumulation order.  A derivation: U is not tuned to what the kernels give.
+    (v is not needed: dP = dO V^T enters through dS.)"""
+    B, Hh, L, hd = q.shape
+    ed = (do.abs() * _heads(eo, B, L, Hh, hd)).sum(-1, keepdim=True)                   # [B, Hh, L, 1]
+    w = U_BWD * ref.ds.abs() + ref.p * ed
+    bdv = U_BWD * ref.dv.abs() + U_BWD * _rows(ref.p.transpose(-1, -2) @ do.abs()) + 1e-6
+    bdq = U_BWD * ref.dq.abs() + scale * _rows(w @ k.abs()) + 1e-6
+    bdk = U_BWD * ref.dk.abs() + scale * _rows(w.transpose(-1, -2) @ q.abs()) + 1e-6
+    return bdq, bdk, bdv
+
+
+def bwd_err_ratio(got_dqkv, ref, bounds):
+    """max |got - ref| / bound for dq, dk, dv (<= 1: inside).  got_dqkv: [B*L, >= 3 Hh hd] as (dq | dk | dv)."""
+    D = ref.dq.shape[1]
+    got = got_dqkv.double()
+    return tuple(float(((got[:, j * D:(j + 1) * D] - want).abs() / bd).max())
+                 for j, (want, bd) in enumerate(zip((ref.dq, ref.dk, ref.dv), bounds)))
+
+
+def spiked_bwd_case(B, L, Hh, hd, seed, boost=32.0):
+    """Random bf16 (qkv, dout) for the backward's tails.  For head j = b * Hh + h and row i = (97 j + 5) % (L - 1), the last key is
+    K[L-1] = alpha Q[i] with alpha chosen in fp64 so that its log2 logit in row i equals the log2-sum-exp of the other keys: key L - 1
+    then holds half of row i's softmax, which maximises its dS (a spike that takes the whole row gives P ~ 1 and dS ~ 0: nothing for a
+    backward to get wrong).  dout[L-1] is multiplied by `boost`, so that the last query -- alone in its tile or chunk at L = 32 k + 1 /
+    256 k + 1 -- dominates its column of dK and dV.  Returns (qkv, dout, [(b, h, i, weight of key L - 1 in row i after the bf16
+    rounding of K)]); the weight is asserted to lie in [0.3, 0.7]."""
+    D = Hh * hd
+    qkv = rnd(B * L, 3 * D, seed=seed).to(torch.bfloat16)
+    dout = rnd(B * L, D, seed=seed + 1).to(torch.bfloat16)
+    x = qkv.view(B, L, 3, Hh, hd)
+    c = hd ** -0.5 * LOG2E
+    probes = []
+    for b in range(B):
+        for h in range(Hh):
+            i = (97 * (b * Hh + h) + 5) % (L - 1)
+            qi = x[b, i, 0, h].double()
+            lse_other = float(torch.logsumexp(x[b, :L - 1, 1, h].double() @ qi * (c / LOG2E), 0)) * LOG2E
+            x[b, L - 1, 1, h] = (lse_other / (float(qi @ qi) * c) * qi).to(torch.bfloat16)
+            logit = float(x[b, L - 1, 1, h].double() @ qi) * c
+            weight = 1.0 / (1.0 + 2.0 ** (lse_other - logit))
+            assert 0.3 <= weight <= 0.7, (b, h, i, weight)
+            probes.append((b, h, i, weight))
+    dout.view(B, L, D)[:, L - 1] *= boost
+    return qkv, dout, probes

@@ -119,11 +119,19 @@ def attention_prefix(qkv, B, L, H, hd, prefix, out=None):
     return out
 
 
-def attention_prefix_backward(qkv, out, dout, B, L, H, hd, prefix):
+def attention_prefix_backward(qkv, out, dout, B, L, H, hd, prefix, dqkv=None, ws=None):
+    """dqkv= / ws=: caller-owned buffers, as hipops.attention_backward takes them (a slice of a wider tensor; a workspace handed over
+    with its own size)."""
     lib = _lib.load()
-    dqkv = torch.zeros_like(qkv)
     nb = lib.ov_attention_prefix_backward_workspace_bytes(B, L, H, hd)
-    ws = torch.empty(nb + 256, dtype=torch.uint8, device=qkv.device)
+    if dqkv is None:
+        dqkv = torch.zeros_like(qkv)
+    assert dqkv.shape == qkv.shape and dqkv.dtype == torch.bfloat16 and dqkv.stride(1) == 1, (dqkv.shape, dqkv.dtype, dqkv.stride())
+    if ws is None:
+        ws = torch.empty(nb + 256, dtype=torch.uint8, device=qkv.device)
+    else:
+        assert ws.dtype == torch.uint8 and ws.is_contiguous()
+        nb = ws.numel()
     check(lib.ov_attention_prefix_backward(ptr(qkv), qkv.stride(0), ptr(out), out.stride(0), ptr(dout), dout.stride(0), ptr(dqkv),
                                            dqkv.stride(0), B, L, H, hd, hd ** -0.5, prefix, ptr(ws), nb, stream_ptr()),
           "ov_attention_prefix_backward")

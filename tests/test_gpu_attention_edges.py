@@ -7,8 +7,8 @@ mistake in either: the output scale shrinks as L grows, and the lone key is one 
 
     |got - ref| <= 2^-8 |ref| + 2^-8 (P.|V|) + 1e-6          (ref = softmax(Q K^T * scale) V in fp64 on the bf16 inputs)
 
-The first term covers the bf16 output rounding (half an ulp is <= 2^-9 relative), the second the rounding of P to bf16 before P.V
-(<= 2^-9 of each term).  The reference, the bound and the spiked inputs live in hipops.py; test_attention_bound.py (CPU) pins what
+The first term covers the bf16 output rounding (half an ulp is <= 2^-8 relative: 8 significant bits), the second the rounding of P to
+bf16 before P.V (<= 2^-8 of each term).  The reference, the bound and the spiked inputs live in hipops.py; test_attention_bound.py (CPU) pins what
 the bound can see: an emulation of the kernel arithmetic stays well inside it, and the same emulation with a dropped,
 double-counted or unrescaled lone key lands outside it."""
 import json

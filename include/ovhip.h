@@ -436,6 +436,10 @@ int ov_transpose_bf16(const ov_bf16* in, int64_t ld_in, int64_t rows, int cols, 
  * Any of dX / dW / db may be NULL (skipped; x is only read for dW).  N % 64 == 0, K % 64 == 0.  Both products run on ov_gemm, fed by LDS-staged transposes
  * held in the workspace (ov_linear_backward_workspace_bytes). */
 size_t ov_linear_backward_workspace_bytes(int64_t M, int N, int K);
+/* What ov_linear_backward does for dW at this shape on the current device (for tests that assert which path they reach): *nz split-K
+ * ranges of *chunk rows each (the last one shorter when nz * chunk > M), *tn_route = 1 when dW comes straight from the row-major
+ * operands (M % 64 == 0 and OVHIP_DW_TRANSPOSE unset), 0 for the explicit-transpose route.  Any of the three may be NULL. */
+int ov_linear_backward_plan(int64_t M, int N, int K, int* nz, int64_t* chunk, int* tn_route);
 int ov_linear_backward(const ov_bf16* dY, int64_t lddy, const ov_bf16* X, int64_t ldx, const ov_bf16* W, int64_t ldw, int64_t M, int N,
                        int K, ov_bf16* dX, int64_t lddx, ov_bf16* dW, int64_t lddw, float* db, void* workspace,
                        size_t workspace_bytes, ov_stream_t stream);

@@ -156,6 +156,7 @@ SIGNATURES = {
                                       c_float, c_void_p, c_size_t, c_void_p]),
     "ov_transpose_bf16": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_int64, c_void_p]),
     "ov_linear_backward_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
+    "ov_linear_backward_plan": (c_int, [c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "ov_linear_backward": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_int, c_void_p, c_int64,
                                    c_void_p, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
     "ov_layernorm_backward_workspace_bytes": (c_size_t, [c_int64, c_int]),

@@ -375,6 +375,13 @@ int launch_transpose(const ov_bf16* in, int64_t ld_in, int64_t R, int64_t Rpad, 
     return OV_OK;
 }
 
+// OVHIP_DW_TRANSPOSE=1 (read once per process): dW through the explicit transposes at every M
+inline bool dw_force_transpose() {
+    static int force_tr = -1;
+    if (force_tr < 0) { const char* e = getenv("OVHIP_DW_TRANSPOSE"); force_tr = (e && e[0] == '1') ? 1 : 0; }
+    return force_tr != 0;
+}
+
 }  // namespace
 
 extern "C" int ov_transpose_bf16(const ov_bf16* in, int64_t ld_in, int64_t rows, int cols, ov_bf16* out, int64_t ld_out,
@@ -392,6 +399,15 @@ extern "C" size_t ov_linear_backward_workspace_bytes(int64_t M, int N, int K) {
     return align256((size_t)K * N * 2) + align256((size_t)N * sp.mp * 2) + align256((size_t)K * sp.mp * 2) +
            align256((size_t)sp.nz * N * K * 2) + align256((size_t)(sp.mp / 64) * N * 4) +     // >= the M / 256 chunk partials
            align256((size_t)RS_SPLIT * N * 4);
+}
+
+extern "C" int ov_linear_backward_plan(int64_t M, int N, int K, int* nz, int64_t* chunk, int* tn_route) {
+    if (M <= 0 || N <= 0 || K <= 0) return OV_ERR_INVALID;
+    const SplitK sp = plan_splitk(M, N, K);
+    if (nz) *nz = sp.nz;
+    if (chunk) *chunk = sp.chunk;
+    if (tn_route) *tn_route = (M % 64 == 0 && !dw_force_transpose()) ? 1 : 0;
+    return OV_OK;
 }
 
 // dx_epi / dx_r: the epilogue of the dX product and its second operand [M, K] (ov_block_backward: the GELU derivative at the c_fc
@@ -426,9 +442,7 @@ static int linear_backward(const ov_bf16* dY, int64_t lddy, const ov_bf16* X, in
     // dW = dY^T X straight from the row-major operands (transposing LDS reads) when the row count is a multiple of the 64-row
     // K-tile (B * L of every tower is: 257 * 256, 80 * 256, ...); OVHIP_DW_TRANSPOSE=1 forces the explicit-transpose route.  Both
     // routes accumulate the same products in the same order: bitwise the same dW.
-    static int force_tr = -1;
-    if (force_tr < 0) { const char* e = getenv("OVHIP_DW_TRANSPOSE"); force_tr = (e && e[0] == '1') ? 1 : 0; }
-    const bool tn = dW && (M % 64 == 0) && !force_tr;
+    const bool tn = dW && (M % 64 == 0) && !dw_force_transpose();
     if (dW && tn) {
         if (sp.nz == 1) {
             if ((rc = ov_gemm_tn_batched(dY, lddy, X, ldx, dW, lddw, 0, M, N, K, sp.chunk, 1, db, stream)) != OV_OK) return rc;

@@ -219,20 +219,38 @@ def clip_loss_backward(img, txt, all_img, all_txt, scale, label_offset, terms, g
     return d_img, d_txt, d_ai, d_at, d_s
 
 
-def linear_backward(dy, x, w, want=("dx", "dw", "db")):
-    """ov_linear_backward for y = x w^T + b: returns (dX bf16 [M,K] | None, dW bf16 [N,K] | None, db fp32 [N] | None)."""
+def _own_ws(ws, nb, device):
+    """ws=None: a fresh workspace with 256 spare bytes, handed over as `nb` bytes; else the caller's uint8 tensor, handed over with
+    its own size (e.g. a view of exactly `nb` bytes, to watch what lies behind it)."""
+    if ws is None:
+        return torch.empty(nb + 256, dtype=torch.uint8, device=device), nb
+    assert ws.dtype == torch.uint8 and ws.is_contiguous()
+    return ws, ws.numel()
+
+
+def linear_backward(dy, x, w, want=("dx", "dw", "db"), dx=None, dw=None, db=None, ws=None):
+    """ov_linear_backward for y = x w^T + b: returns (dX bf16 [M,K] | None, dW bf16 [N,K] | None, db fp32 [N] | None).  dx= / dw= /
+    db=: caller-owned outputs for the gradients named in `want` (dx, dw with their own row pitch); ws=: a caller-owned workspace."""
     lib = _lib.load()
     M, N = dy.shape
     K = x.shape[1]
-    dx = torch.empty(M, K, dtype=torch.bfloat16, device=dy.device) if "dx" in want else None
-    dw = torch.empty(N, K, dtype=torch.bfloat16, device=dy.device) if "dw" in want else None
-    db = torch.empty(N, dtype=torch.float32, device=dy.device) if "db" in want else None
-    nb = lib.ov_linear_backward_workspace_bytes(M, N, K)
-    ws = torch.empty(nb + 256, dtype=torch.uint8, device=dy.device)
+    dx = _out_buf(dx, M, K, torch.bfloat16, None, dy.device) if "dx" in want else None
+    dw = _out_buf(dw, N, K, torch.bfloat16, None, dy.device) if "dw" in want else None
+    db = (db if db is not None else torch.empty(N, dtype=torch.float32, device=dy.device)) if "db" in want else None
+    ws, nb = _own_ws(ws, lib.ov_linear_backward_workspace_bytes(M, N, K), dy.device)
     check(lib.ov_linear_backward(ptr(dy), dy.stride(0), ptr(x), x.stride(0), ptr(w), w.stride(0), M, N, K,
-                                 ptr(dx) if dx is not None else None, K, ptr(dw) if dw is not None else None, K,
+                                 ptr(dx) if dx is not None else None, dx.stride(0) if dx is not None else K,
+                                 ptr(dw) if dw is not None else None, dw.stride(0) if dw is not None else K,
                                  ptr(db) if db is not None else None, ptr(ws), nb, stream_ptr()), "ov_linear_backward")
     return dx, dw, db
+
+
+def linear_backward_plan(M, N, K):
+    """ov_linear_backward_plan: (nz, chunk, tn_route) -- for coverage assertions only, never for a bound."""
+    lib = _lib.load()
+    nz, chunk, tn = C.c_int(-1), C.c_int64(-1), C.c_int(-1)
+    check(lib.ov_linear_backward_plan(M, N, K, C.addressof(nz), C.addressof(chunk), C.addressof(tn)), "ov_linear_backward_plan")
+    return nz.value, chunk.value, bool(tn.value)
 
 
 def transpose(x):
@@ -244,25 +262,30 @@ def transpose(x):
     return out
 
 
-def layernorm_backward(x, gamma, dy, eps=1e-6, dres=None):
+def layernorm_backward(x, gamma, dy, eps=1e-6, dres=None, dx=None, ws=None):
+    """dx=: a caller-owned [rows, D] bf16 output with its own row pitch; ws=: a caller-owned workspace."""
     lib = _lib.load()
     rows, D = x.shape
-    dx = torch.empty_like(x)
+    dx = _out_buf(dx, rows, D, torch.bfloat16, None, x.device)
     dg = torch.empty(D, dtype=torch.float32, device=x.device)
     db = torch.empty(D, dtype=torch.float32, device=x.device)
-    nb = lib.ov_layernorm_backward_workspace_bytes(rows, D)
-    ws = torch.empty(nb + 256, dtype=torch.uint8, device=x.device)
+    ws, nb = _own_ws(ws, lib.ov_layernorm_backward_workspace_bytes(rows, D), x.device)
     check(lib.ov_layernorm_backward(ptr(x), x.stride(0), ptr(gamma), ptr(dy), dy.stride(0), ptr(dres) if dres is not None else None,
                                     dres.stride(0) if dres is not None else 0, ptr(dx), dx.stride(0), ptr(dg), ptr(db),
                                     rows, D, eps, ptr(ws), nb, stream_ptr()), "ov_layernorm_backward")
     return dx, dg, db
 
 
-def gelu_backward(a, dh, tanh, with_h=False):
+def gelu_backward(a, dh, tanh, with_h=False, da=None, h=None, inplace=False):
+    """da= / h=: caller-owned [rows, N] bf16 outputs with their own row pitch (h= implies with_h); inplace=True: da is dh itself, as
+    the block's backward chain calls it."""
     lib = _lib.load()
     rows, N = a.shape
-    da = torch.empty_like(a)
-    h = torch.empty_like(a) if with_h else None
+    assert not (inplace and da is not None)
+    da = dh if inplace else _out_buf(da, rows, N, torch.bfloat16, None, a.device)
+    with_h = with_h or h is not None
+    if with_h:
+        h = _out_buf(h, rows, N, torch.bfloat16, None, a.device)
     check(lib.ov_gelu_backward(ptr(a), a.stride(0), ptr(dh), dh.stride(0), ptr(da), da.stride(0), ptr(h) if with_h else None,
                                h.stride(0) if with_h else 0, rows, N, int(tanh), stream_ptr()), "ov_gelu_backward")
     return (da, h) if with_h else da
@@ -320,10 +343,7 @@ def _bwd_buffers(qkv, dqkv, ws, nb):
     if dqkv is None:
         dqkv = torch.empty_like(qkv)
     assert dqkv.shape == qkv.shape and dqkv.dtype == torch.bfloat16 and dqkv.stride(1) == 1, (dqkv.shape, dqkv.dtype, dqkv.stride())
-    if ws is None:
-        return dqkv, torch.empty(nb + 256, dtype=torch.uint8, device=qkv.device), nb
-    assert ws.dtype == torch.uint8 and ws.is_contiguous()
-    return dqkv, ws, ws.numel()
+    return (dqkv,) + _own_ws(ws, nb, qkv.device)
 
 
 def attention_backward(qkv, out, dout, B, L, H, hd=64, dqkv=None, ws=None):
@@ -525,3 +545,215 @@ def spiked_bwd_case(B, L, Hh, hd, seed, boost=32.0):
             probes.append((b, h, i, weight))
     dout.view(B, L, D)[:, L - 1] *= boost
     return qkv, dout, probes
+
+
+# ---- linear / LayerNorm / GELU backward: fp64 closed forms with per-element bounds (test_gpu_param_grad_edges.py; what the bounds can
+# see is pinned on the CPU by test_param_grad_bound.py)
+
+U16 = 2.0 ** -8                  # bf16's unit roundoff: 8 significant bits, round to nearest
+E32 = 2.0 ** -24                 # fp32's
+
+
+def linear_grads_ref64(dy, x, w):
+    """y = x w^T + b in fp64 on the (bf16) inputs: (dX [M, K], dW [N, K], db [N])."""
+    dy, x, w = dy.double(), x.double(), w.double()
+    return dy @ w, dy.T @ x, dy.sum(0)
+
+
+def linear_bounds(dy, x, w):
+    """Per-element bounds (bound_dX [M, K], bound_dW [N, K], bound_db [N]) on ov_linear_backward, fp64, from the inputs alone: nothing
+    here knows the split-K plan, the route or the device.  u = 2^-8, e = 2^-24.
+
+        bound_dX = u |dX| + N e (|dY| |W|) + 1e-6
+    dX is one fp32-accumulated product over N (a sum of n terms in any order is off by at most n e sum|terms| to first order) and
+    one bf16 rounding of the result.
+
+        T[n, k]  = sum over 64-row tiles t of | sum_{m in t} dY[m, n] X[m, k] |          (rows past M: zeros)
+        bound_dW = u (|dW| + T) + M e (|dY|^T |X|) + 1e-6
+    dW is cut into row ranges; each range's fp32 product P_z is rounded to bf16 (at most u |P_z|), the partials are summed in fp32 and
+    the sum is rounded to bf16 once more (u |dW|).  Whatever the plan, a range is a whole number of 64-row tiles (the K granule of
+    the GEMM), so |P_z| <= sum of its tiles' |tile sum| and sum_z |P_z| <= T: the worst plan is one range per tile.  The fp32 work
+    is `chunk` terms inside a range and `nz` terms across ranges, chunk + nz <= M + 2 terms in all; M e (|dY|^T |X|) covers it with
+    the second-order terms in the + 1e-6.  With one range there is no partial rounding and the bound is merely not tight.
+
+        bound_db = (M + 2) e sum_m |dY| + 1e-7
+    an fp32 sum of M terms in any order (per tile, per range or per 256-row chunk first)."""
+    M, N = dy.shape
+    dy, x, w = dy.double(), x.double(), w.double()
+    dx_ref, dw_ref, _ = linear_grads_ref64(dy, x, w)
+    bdx = U16 * dx_ref.abs() + N * E32 * (dy.abs() @ w.abs()) + 1e-6
+    mp = (M + 63) // 64 * 64
+    dyp, xp = torch.zeros(mp, N, dtype=torch.float64), torch.zeros(mp, x.shape[1], dtype=torch.float64)
+    dyp[:M], xp[:M] = dy, x
+    t = torch.zeros_like(dw_ref)
+    for i in range(0, mp, 64):
+        t += (dyp[i:i + 64].T @ xp[i:i + 64]).abs()
+    bdw = U16 * (dw_ref.abs() + t) + M * E32 * (dy.abs().T @ x.abs()) + 1e-6
+    bdb = (M + 2) * E32 * dy.abs().sum(0) + 1e-7
+    return bdx, bdw, bdb
+
+
+def spiked_linear_case(M, N, K, seed, boost=8.0):
+    """Gaussian bf16 (dy [M, N], x [M, K], w [N, K] / sqrt K) in which rows 0, 63, 64 and M - 1 (those that exist) of dy AND of x
+    are `boost` times larger: each of these rows -- the first and last of the first 64-row tile, the first of the second, the last
+    of all -- then carries boost^2 times an ordinary row's share of dW, so that dropping or doubling it stands far outside the
+    bound."""
+    dy, x = rnd(M, N, seed=seed), rnd(M, K, seed=seed + 1)
+    w = (rnd(N, K, seed=seed + 2) * K ** -0.5).to(torch.bfloat16)
+    for r in sorted({0, 63, 64, M - 1}):
+        if r < M:
+            dy[r] *= boost
+            x[r] *= boost
+    return dy.to(torch.bfloat16), x.to(torch.bfloat16), w
+
+
+class LnRef:
+    """What ln_grads_ref64 returns: dx [R, D], dgamma, dbeta [D] and the bounds bdx, bdg, bdb of the same shapes, all fp64."""
+
+
+def ln_grads_ref64(x, gamma, dy, dres, eps):
+    """The LayerNorm backward in closed form, fp64 on the inputs the kernel reads (bf16 x, dy, dres; fp32 gamma; dres may be None):
+        xhat = (x - mean) rstd,  q = dy gamma,  dx = rstd (q - mean q - xhat mean(q xhat)) + dres,
+        dgamma = sum_r dy xhat,  dbeta = sum_r dy
+    with per-element bounds on what ov_layernorm_backward may return.  u = 2^-8, e = 2^-24, means over the D columns of a row.
+
+    xhat first.  The fp32 mean is a D-term sum: off by at most D e mean|x|; x - mean adds one rounding, e (|x| + mean|x|); the
+    variance is a D-term sum of squares whose first-order sensitivity to the mean's error vanishes (sum (x - mean) = 0), so rstd
+    is off relatively by about (D / 2 + 3) e, rsqrt's ulp included; the product rounds once more:
+        dxh = e ((D + 4) (|x| + mean|x|) rstd + (D + 6) |xhat|)
+    (the first term is what grows when mean >> spread: cancellation in x - mean).
+
+    dx: q is one rounding; mean q a D-term sum; mean(q xhat) a D-term fma chain over products that carry xhat's error; the bracket
+    t = q - mean q - xhat mean(q xhat) is assembled with a few more roundings, multiplied by rstd (relative error as above), dres
+    is added and the result is rounded to bf16 once:
+        bdx = u |dx| + e (D + 8) rstd (|q| + mean|q| + |xhat| mean|q xhat|)                 the fp32 sums and roundings
+                     + rstd (dxh |mean(q xhat)| + |xhat| mean(|q| dxh))                      xhat's error, both places it enters
+                     + rstd (D + 6) e |t| + 1e-7                                             rstd's own error
+    dgamma: an fp32 sum over R rows (per wave, then over the waves: any order) of products that carry xhat's error:
+        bdg = (R + 2) e sum_r |dy xhat| + sum_r |dy| dxh + 1e-7
+    dbeta: bdb = (R + 2) e sum_r |dy| + 1e-7."""
+    x, g, dy = x.double(), gamma.double(), dy.double()
+    R, D = x.shape
+    mean = x.mean(1, keepdim=True)
+    xc = x - mean
+    rstd = ((xc ** 2).mean(1, keepdim=True) + eps).rsqrt()
+    xh = xc * rstd
+    q = dy * g
+    mq, mqx = q.mean(1, keepdim=True), (q * xh).mean(1, keepdim=True)
+    t = q - mq - xh * mqx
+    ref = LnRef()
+    ref.dx = rstd * t + (dres.double() if dres is not None else 0.0)
+    ref.dgamma, ref.dbeta = (dy * xh).sum(0), dy.sum(0)
+    dxh = E32 * ((D + 4) * (x.abs() + x.abs().mean(1, keepdim=True)) * rstd + (D + 6) * xh.abs())
+    ref.bdx = (U16 * ref.dx.abs()
+               + E32 * (D + 8) * rstd * (q.abs() + q.abs().mean(1, keepdim=True) + xh.abs() * (q * xh).abs().mean(1, keepdim=True))
+               + rstd * (dxh * mqx.abs() + xh.abs() * (q.abs() * dxh).mean(1, keepdim=True))
+               + rstd * (D + 6) * E32 * t.abs() + 1e-7)
+    ref.bdg = (R + 2) * E32 * (dy * xh).abs().sum(0) + (dy.abs() * dxh).sum(0) + 1e-7
+    ref.bdb = (R + 2) * E32 * dy.abs().sum(0) + 1e-7
+    return ref
+
+
+def ln_err_ratio(dx, dg, db, ref):
+    """max |got - ref| / bound for (dx, dgamma, dbeta) (<= 1: inside)."""
+    return (float(((dx.double() - ref.dx).abs() / ref.bdx).max()), float(((dg.double() - ref.dgamma).abs() / ref.bdg).max()),
+            float(((db.double() - ref.dbeta).abs() / ref.bdb).max()))
+
+
+def spiked_ln_case(rows, D, seed, mean=0.2, spread=1.5, boost=32.0, tail=4.0):
+    """(x bf16 [rows, D] ~ mean + spread N(0, 1), gamma fp32 [D] ~ 1 + 0.1 N(0, 1), dy bf16, dres bf16), rows 0 and rows - 1 of dy
+    `boost` times larger: a first or last row that is dropped, or overwritten by a wave's next row, stands far outside the
+    parameter bounds.  The last 8 columns of x (the last chunk, which a lone lane holds at D = 520, 1032, 1544, 2056) sit `tail`
+    spreads higher, an outlier channel group: a row statistic that leaves that chunk out is visibly wrong in dx.  mean = 8 (with
+    spread 1.5) is the cancellation case of the variance."""
+    x = rnd(rows, D, seed=seed) * spread + mean
+    x[:, D - 8:] += tail * spread
+    x = x.to(torch.bfloat16)
+    dy = rnd(rows, D, seed=seed + 1)
+    dy[0] *= boost
+    dy[rows - 1] *= boost if rows > 1 else 1.0
+    gamma = rnd(D, seed=seed + 2) * 0.1 + 1
+    dres = rnd(rows, D, seed=seed + 3).to(torch.bfloat16)
+    return x, gamma, dy.to(torch.bfloat16), dres
+
+
+# delta: the absolute error of the fp32 gelu' (and of Phi resp. sigmoid, which gives h = a Phi) as backward.hip evaluates them.
+#   erf form:  Phi = 1 - half_erfc or half_erfc, half_erfc = 0.5 p(t) exp(-a^2 / 2).  A&S 7.1.26 is within 1.5e-7 of erfc, so 0.75e-7
+#     of Phi.  t comes from a one-ulp rcp; the five-term Horner chain has intermediates <= 1.46 and t <= 1: <= 8 e on p t; exp2's
+#     argument is rounded twice (its effect on exp2 is <= 2 e |arg| ln 2 exp2(arg) <= 0.74 e) and exp2 is within one ulp: <= 2 e;
+#     half the sum, plus one rounding of 1 - half_erfc: <= 6 e on Phi.  gelu' adds a phi(a) (<= 0.242, relative error <= 5 e plus
+#     the same argument term, <= 2 e absolute) and one fma rounding (<= 1.13 e): delta_erf = 0.75e-7 + 10 e = 6.7e-7.
+#   tanh form: sg = rcp(1 + exp2(-2 log2(e) u)).  The argument's relative error is <= 4 e, which moves sg by <= 4 e |2u| sg (1 - sg)
+#     <= 0.9 e; exp2, the addition and rcp add <= 2.3 e: <= 3.2 e on sg (h = a sg).  gelu' = sg + 2 a sg (1 - sg) u'.  Where sg is not
+#     close to 1 the second term (<= 0.65 in magnitude) keeps a relative error <= 8 e and inherits sg's error times |2 a u' (1 - 2 sg)|:
+#     <= 8 e in all, 4.8e-7.  For a > 2.6 this stops: 1 - sg cancels (sg carries an absolute error up to 2 e, 1 - sg is of that
+#     order) while its factor 2 a u' grows like a^3, and the derivative's error reaches min(2 e, 1 - sg) 2 a u' = 3.7e-6 near a = 4.8
+#     (1.9e-6 in the fp32 emulation of test_param_grad_bound.py; 0 again from a = 5.3, where sg is 1 exactly).  That is above the
+#     1e-6 that the kernel's tests quote.  It is harmless -- gelu' is within 3 % of 1 there, so the bf16 rounding of da, 3.9e-3 |dh|,
+#     is three orders larger -- and the kernel stays as it is (the GEMM's GELU_GRAD epilogue shares the form and is pinned bitwise).
+#     DELTA_TANH is held at the quoted 1e-6 all the same: the tests do not widen it for that band.
+DELTA_ERF = 0.75e-7 + 10 * E32
+DELTA_TANH = 1e-6
+assert DELTA_ERF <= 1e-6 and DELTA_TANH <= 1e-6
+BF16_TINY = 2.0 ** -134          # half the spacing of the subnormal bf16 numbers
+
+
+def gelu_grads_ref64(a, dh, tanh):
+    """(da, h) = (dh gelu'(a), gelu(a)) in fp64 on the (bf16) inputs; erf form: Phi(a) + a phi(a) and a Phi(a) with Phi through
+    erfc (no cancellation in the negative tail); tanh form through sigmoid(2u), u = sqrt(2 / pi) (a + 0.044715 a^3)."""
+    a, dh = a.double(), dh.double()
+    if tanh:
+        c = 0.7978845608028654
+        s = torch.sigmoid(2.0 * c * (a + 0.044715 * a ** 3))
+        grad = s + 2.0 * a * s * (1.0 - s) * c * (1.0 + 3.0 * 0.044715 * a * a)
+    else:
+        s = 0.5 * torch.special.erfc(-a * 0.7071067811865476)
+        grad = s + a * torch.exp(-0.5 * a * a) * 0.3989422804014327
+    return dh * grad, a * s           # finite on |a| <= 2^16: every factor that saturates does so to exactly 0 or 1 beside finite ones
+
+
+def gelu_bounds(a, dh, tanh, ref=None):
+    """(bound_da, bound_h): |da err| <= u |da| + |dh| delta and |h err| <= u |h| + |a| delta -- one bf16 rounding of each output plus
+    the fp32 formula's absolute error delta (DELTA_ERF / DELTA_TANH above), which reaches da through dh and h through a.  u |.| is
+    the rounding of a normal bf16 result; a subnormal one (h = a Phi at the subnormal a of the all-values case) is rounded to the
+    subnormal spacing 2^-133 instead, so half of that, BF16_TINY = 2^-134, is added to both.  ref: gelu_grads_ref64's result, if
+    the caller has it."""
+    da, h = ref if ref is not None else gelu_grads_ref64(a, dh, tanh)
+    delta = DELTA_TANH if tanh else DELTA_ERF
+    return U16 * da.abs() + dh.double().abs() * delta + BF16_TINY, U16 * h.abs() + a.double().abs() * delta + BF16_TINY
+
+
+def gelu_err_ratio(da, h, a, dh, tanh):
+    """max |got - ref| / bound for (da, h) (<= 1: inside); a NaN anywhere gives nan, which no `<= 1.0` passes."""
+    ref = gelu_grads_ref64(a, dh, tanh)
+    r = []
+    for got, want, bd in zip((da, h), ref, gelu_bounds(a, dh, tanh, ref)):
+        q = (got.double() - want).abs() / bd
+        r.append(float("nan") if bool(torch.isnan(q).any()) else float(q.max()))
+    return tuple(r)
+
+
+def all_bf16_values(limit=2.0 ** 16):
+    """Every finite bf16 value with |a| <= limit, -0.0 and the subnormals included, in bit-pattern order."""
+    bits = torch.arange(0, 65536, dtype=torch.int32).to(torch.int16).view(torch.bfloat16)
+    f = bits.float()
+    return bits[torch.isfinite(f) & (f.abs() <= limit)]
+
+
+# the shapes of test_gpu_param_grad_edges.py (test_param_grad_bound.py runs its emulations at the same ones)
+LINEAR_NK = [(64, 64), (192, 320), (320, 64)]          # the 256-wide output tile ragged in N, in K and in neither
+LINEAR_TN_M = [64, 512, 1088, 2048, 16384]             # M % 64 == 0: dW straight from the row-major operands
+LINEAR_TR_M = [70, 1100, 8200]                         # explicit transposes, zeros past M
+DB_BOOST_LARGE_M = 512.0                               # the spike of the db-alone case at M = 33027, where bound_db is 52 per column
+LN_SHAPES = [(1, 8), (5, 200), (129, 200), (37, 520), (9, 1032), (9, 1152), (5, 1544), (5, 2056), (5, 4096), (4099, 64), (8195, 1152)]
+GELU_DH = (1.0, -3.0, 2.0 ** -20)
+
+
+def gelu_all_values_case():
+    """(a, dh) bf16 [3 * rows, 8]: every finite bf16 |a| <= 2^16 (padded with zeros to a multiple of 8) against each dh of GELU_DH."""
+    v = all_bf16_values()
+    pad = (-v.numel()) % 8
+    v = torch.cat([v, torch.zeros(pad, dtype=torch.bfloat16)]).view(-1, 8)
+    a = torch.cat([v] * len(GELU_DH))
+    dh = torch.cat([torch.full(v.shape, d, dtype=torch.bfloat16) for d in GELU_DH])
+    return a, dh

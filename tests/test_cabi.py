@@ -77,6 +77,7 @@ def test_argument_validation_of_the_widening_entry_points():
     assert lib.ov_attention_backward_workspace_bytes(2, 257, 16, 80) > 0
     assert lib.ov_gemm_batched(None, 64, 64, None, 64, 64, None, 64, 64, 64, 64, 64, 2, None) == -1
     assert lib.ov_linear_backward_workspace_bytes(65792, 4096, 1024) >= 2 * 65792 * (4096 + 1024)
+    assert lib.ov_linear_backward_plan(0, 64, 64, None, None, None) == -1 and lib.ov_linear_backward_plan(64, 64, 64, None, None, None) == 0
     assert lib.ov_layernorm_backward_workspace_bytes(65792, 1024) > 0
     assert lib.ov_quant_rows_fp8(None, 1024, None, 1024, None, 4, 1024, None, None) == -1
     assert lib.ov_layernorm_quant_fp8(None, 1024, None, None, None, 1024, None, 4, 1024, 1e-6, None) == -1

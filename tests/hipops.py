@@ -1,5 +1,7 @@
 """Thin test-side wrappers: torch tensors -> C ABI calls of libovhip.so (granular operators)."""
 import ctypes as C
+import math
+from types import SimpleNamespace
 
 import torch
 
@@ -35,13 +37,16 @@ def gemm(a, w, bias=None, epi=0, resid=None, out=None, out_group=0, resid_mod=0,
     return out
 
 
-def gemm_keep(a, w, bias, epi, ldc=None, ldc2=None, fill=0.0):
-    """C = gelu(a w^T + bias), C2 = a w^T + bias (both bf16) from one launch: ov_gemm_keep.  fill: what both outputs hold before."""
+def gemm_keep(a, w, bias, epi, ldc=None, ldc2=None, fill=0.0, out=None, pre=None):
+    """C = gelu(a w^T + bias), C2 = a w^T + bias (both bf16) from one launch: ov_gemm_keep.  fill: what both outputs hold before.
+    out= / pre=: caller-owned [M, >= N] bf16 outputs, each with its own row pitch."""
     lib = _lib.load()
     m, k = a.shape
     n = w.shape[0]
-    out = torch.full((m, ldc or n), fill, dtype=torch.bfloat16, device=a.device)
-    pre = torch.full((m, ldc2 or n), fill, dtype=torch.bfloat16, device=a.device)
+    if out is None:
+        out = torch.full((m, ldc or n), fill, dtype=torch.bfloat16, device=a.device)
+    if pre is None:
+        pre = torch.full((m, ldc2 or n), fill, dtype=torch.bfloat16, device=a.device)
     check(lib.ov_gemm_keep(ptr(a), a.stride(0), ptr(w), w.stride(0), ptr(bias), ptr(out), out.stride(0), ptr(pre), pre.stride(0),
                            m, n, k, epi, stream_ptr()))
     return out, pre
@@ -757,3 +762,270 @@ def gelu_all_values_case():
     a = torch.cat([v] * len(GELU_DH))
     dh = torch.cat([torch.full(v.shape, d, dtype=torch.bfloat16) for d in GELU_DH])
     return a, dh
+
+
+# ---- the bf16 GEMM kernels against fp64 (test_gpu_gemm_routes.py: the persistent kernel; test_gpu_gemm_small_routes.py: the skinny and
+# plain kernels, ov_gemm_batched, the LN fold; what the bounds can see is pinned on the CPU by test_gemm_small_bound.py).  The bounds
+# are derived in the module docstring of test_gpu_gemm_routes.py (bias, residual, GELU), at linear_ratios (GELU gradient) and at fold_bound below.
+
+DEV = "cuda:0"
+BM = BN = 256
+BK = 64
+SKINNY_TILES = 96
+SENT = 77.0
+E_TANH = 1.1e-6
+CHUNK = 4096                      # rows per fp64 chunk: 4096 x 4096 x 8 B = 128 MB for the widest N of the routes test
+
+
+def route(M, N, K, epi=0, keep=False, nt_min_mb=192):
+    """What gemm.hip's launcher selects for this shape on this device (launch<EPI>, gemm_ngroup, persist_policy)."""
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    tm, tn = -(-M // BM), -(-N // BN)
+    nwg = tm * tn
+    if not keep and nwg <= SKINNY_TILES:
+        kernel = "skinny"
+    elif nwg < cus or K < 3 * BK:
+        kernel = "plain"
+    else:
+        kernel = "persistent"
+    wbytes = tn * BN * K * 2
+    ngroup = tn if (wbytes <= (3 << 20) or tn <= 4 or tn % 4 or tm < 16) else 4
+    rem, nper = N % BN, cus >> 3
+    rot = tn - 1 if (0 < rem <= 128 and ngroup >= tn and tn > 1 and tn & (tn - 1) == 0 and cus % 8 == 0 and nper % tn == 0) else 0
+    return SimpleNamespace(cus=cus, tm=tm, tn=tn, nwg=nwg, kernel=kernel, grouped=ngroup < tn, groups=tn // ngroup, rot=rot, rem=rem,
+                           pr=tm & 7, rev=epi == 3 and K >= 2 * N, st_plain=M * N * 2 < (nt_min_mb << 20), wbytes=wbytes)
+
+
+def gelu64(x, tanh):
+    return torch.nn.functional.gelu(x, approximate="tanh" if tanh else "none")
+
+
+def _worst(err, bound, row0):
+    q = err / bound
+    k = int(q.argmax())
+    return float(q.view(-1)[k]), row0 + k // q.shape[1], k % q.shape[1]
+
+
+def _merge(res, name, item):
+    old = res.get(name)
+    if old is None or math.isnan(item[0]) or item[0] > old[0]:        # (a NaN is kept: it fails the assertion)
+        res[name] = item
+
+
+def linear_ratios(a, w, bias, outs, r=None):
+    """outs: name -> (bf16 [M, >= N], kind), kind in pre | erf | tanh | res | res1 | gerf | gtanh (res1: the residual under the
+    ONE-rounding bound, for the record; gerf / gtanh: the GELU-gradient epilogues, r = the pre-activation they differentiate at).  Returns name -> (max err / bound, row, column) against fp64 on the device, in row chunks."""
+    M, K = a.shape
+    N = w.shape[0]
+    wd, wabs, bd = w.double(), w.float().abs(), bias.double()
+    res = {}
+    for i in range(0, M, CHUNK):
+        sl = slice(i, min(M, i + CHUNK))
+        pre = a[sl].double() @ wd.T + bd
+        s = (a[sl].float().abs() @ wabs.T + bias.abs()).double()
+        b_pre = REL * pre.abs() + K * 2.0 ** -24 * s + 1e-6
+        for name, (got, kind) in outs.items():
+            g = got[sl, :N].double()
+            if kind == "pre":
+                ref, bound = pre, b_pre
+            elif kind in ("res", "res1"):
+                rr = r[sl].double()
+                ref = pre + rr
+                bound = REL * ref.abs() + K * 2.0 ** -24 * (s + rr.abs()) + 1e-6
+                if kind == "res":
+                    bound = bound + REL * (1 + REL) * pre.abs()
+            elif kind in GRAD_DELTA:
+                # GELU-gradient epilogue, out = bf16(bf16(pre) g32(R)), against ref = pre g'(R) with the exact fp64 g'.  The rounded
+                # pre is off by at most b_pre, and that error is carried with the factor |g32| <= |g'| + delta; g32 is within delta of
+                # g', on the magnitude |pre|; the product is rounded once:
+                #     |g'(R)| b_pre + delta (|pre| + b_pre) + REL |ref|
+                gd = gelu_grads_ref64(r[sl], torch.ones_like(r[sl]), kind == "gtanh")[0]
+                ref = pre * gd
+                bound = gd.abs() * b_pre + GRAD_DELTA[kind] * (pre.abs() + b_pre) + REL * ref.abs()
+            else:
+                ref = gelu64(pre, kind == "tanh")
+                e = E_TANH if kind == "tanh" else torch.clamp(6.6e-5 * pre.abs(), min=1.4e-4)
+                bound = 1.13 * b_pre + REL * ref.abs() + e
+            _merge(res, name, _worst((g - ref).abs(), bound, i))
+    return res
+
+
+def report(tag, res, skip=()):
+    for name, (q, row, col) in res.items():
+        print(f"{tag} {name}: max err / bound {q:.3f}")
+    bad = {n: (q, f"row {row} column {col} = tile ({row // BM}, {col // BN})") for n, (q, row, col) in res.items()
+           if n not in skip and not q <= 1.0}
+    assert not bad, (tag, bad)
+
+
+def sentinel(M, width):
+    return torch.full((M, width), SENT, dtype=torch.bfloat16, device=DEV)
+
+
+def padding_kept(out, N):
+    return bool((out[:, N:] == SENT).all())
+
+
+
+
+# delta of the GEMM's GELU-gradient epilogues (common.h): the absolute error of the fp32 gelu' against the exact fp64 derivative.
+#   erf form (gelu_erf_grad_f2x2, a degree-7 polynomial fit): common.h states |error| <= 4.3e-4 everywhere; the figure is taken from
+#     there (a restatement in fp32 on a 2^-12 grid over [-8, 8] gives 4.264e-4, at the clamp x = 4: test_gemm_small_bound.py prints it).
+#   tanh form (gelu_tanh_grad_f2, the closed form through sigmoid(2u)): common.h states no figure.  The restatement in fp32, the same
+#     operation order, on the 2^-12 grid over [-8, 8] differs from the fp64 derivative by at most 1.969e-6 (at x = 4.962, where 1 - sg
+#     cancels: the band that DELTA_TANH's comment above describes); with the factor 2, as for E_TANH: 3.94e-6.
+DELTA_GRAD_ERF = 4.3e-4
+DELTA_GRAD_TANH = 3.94e-6
+GRAD_DELTA = {"gerf": DELTA_GRAD_ERF, "gtanh": DELTA_GRAD_TANH}
+
+
+def gemm_batched(a, lda, stride_a, w, ldw, stride_w, out, ldc, stride_c, M, N, K, batch):
+    """ov_gemm_batched: C_z = A_z W_z^T for z < batch, every pointer, pitch and stride (in elements) as the caller gives it."""
+    lib = _lib.load()
+    check(lib.ov_gemm_batched(ptr(a), lda, stride_a, ptr(w), ldw, stride_w, ptr(out), ldc, stride_c, M, N, K, batch, stream_ptr()),
+          "ov_gemm_batched")
+    return out
+
+
+def pitched(t, pad=8, fill=float("nan")):
+    """t [rows, cols] as a view of a buffer `pad` columns wider whose padding holds `fill` (NaN: an operand read past its K or N
+    columns poisons the output)."""
+    buf = torch.full((t.shape[0], t.shape[1] + pad), fill, dtype=t.dtype, device=t.device)
+    buf[:, :t.shape[1]] = t
+    return buf[:, :t.shape[1]]
+
+
+# the shapes of test_gpu_gemm_small_routes.py (test_gemm_small_bound.py runs its emulation at the same ones): (M, N, K)
+SKINNY_SHAPES = [(1, 8, 64),              # one row, one quad, one K-tile
+                 (65, 72, 128),           # ragged both ways, 2 K-tiles
+                 (130, 200, 192),         # 3 K-tiles = the prefetch depth
+                 (257, 264, 256),         # 4 K-tiles = the ring
+                 (63, 1096, 320),         # 5 K-tiles: the first slot reuse; the last n-tile holds 8 columns
+                 (300, 96, 576)]          # two laps of the ring
+PLAIN_SHAPES = [(24827, 8, 64),           # 97 tiles (97 mod 8 = 1 in the XCD map), one K-tile
+                (1, 24584, 128),          # 97 column tiles, the last holds 8 columns; every A row clamped to row 0
+                (2500, 2568, 192),        # 110 tiles (110 mod 8 = 6)
+                (2305, 2816, 320)]        # 110 tiles
+SKINNY_ALL_EPI = [(130, 200, 192), (63, 1096, 320)]
+PLAIN_ALL_EPI = [(2500, 2568, 192)]
+ROWMAP_CASE = (3, 50, 200, 192)           # (B, g^2, D, K): the patch embedding with row maps at a small batch (skinny kernel)
+MAPPED_GELU_CASE = (25000, 200, 64, 50)   # (M, N, K, out_group): GELU-erf with out_group, which the ABI admits and the plain kernel runs
+BATCHED_CASE = (300, 264, 128, 3)         # (M, N, K, batch)
+ROWPARTS_SHAPES = [(257, 288, 256), (300, 96, 576), (2500, 2592, 192)]          # N / 32 odd in all three; the last is the plain kernel's
+FOLD_SHAPES = [s for s in SKINNY_SHAPES if 128 <= s[2] <= 320] + PLAIN_SHAPES[2:]
+FOLD_CLEAN_ONLY = (130, 200, 1024)        # K = 1024: the K S1 term is too pessimistic there for the double-rounding mistakes
+
+
+def gemm_case(M, N, K, r_rows=None):
+    """CPU operands (a bf16 [M, K], w bf16 [N, K] / sqrt K, bias fp32 [N], r bf16 [r_rows or M, N]), Gaussian; r (the residual, or the
+    pre-activation the GELU-gradient epilogues differentiate at) with spread 2, so that 4.6 % of it lies beyond the erf form's clamp
+    at |x| = 4 and in the tanh form's cancelling band."""
+    g = torch.Generator().manual_seed(1000003 * K + 1009 * N + M + 5)
+    a = torch.randn(M, K, generator=g).to(torch.bfloat16)
+    w = (torch.randn(N, K, generator=g) / K ** 0.5).to(torch.bfloat16)
+    bias = torch.randn(N, generator=g)
+    return a, w, bias, (torch.randn(r_rows or M, N, generator=g) * 2.0).to(torch.bfloat16)
+
+
+# ---- the LN fold, rstd (x W'^T - mean colsum) + cvec
+
+
+def stats64(x, eps=1e-6):
+    """{mean, rstd} per row, [M, 2] fp32: the fp64 statistics of the (bf16) rows rounded to fp32 -- not ov_rowstats' output, so a test
+    that hands these to ov_gemm_ln does not depend on that kernel."""
+    xd = x.double()
+    mean, var = xd.mean(1), xd.var(1, unbiased=False)
+    return torch.stack([mean, (var + eps).rsqrt()], 1).float()
+
+
+def spiked_fold_case(M, N, K):
+    """CPU operands of the fold, (x bf16 [M, K], wg bf16 [N, K], cvec fp32, colsum fp32, w, bias, gamma, beta fp32: the unfolded
+    Linear and LayerNorm), the construction of test_gemm_ln_fold_matches_layernorm_then_linear (x = 0.4 + 1.7 N(0, 1)) with three
+    spikes: the last row at mean / std = 8 (the row whose statistics a clamped or neighbouring read gets wrong: mean colsum is eight
+    times the spread there, so the cancellation is at its worst), row 0 with spread 8 (rstd far from its neighbours'), and +40 on
+    the last channel (an outlier channel, as trained towers have: whatever drops the end of K or mis-sums colsum shows)."""
+    rnd_ = lambda *s, seed: torch.randn(*s, generator=torch.Generator().manual_seed(seed + M + N + K))
+    x = rnd_(M, K, seed=130) * 1.7 + 0.4
+    x[M - 1] = rnd_(K, seed=135) * 1.7 + 8 * 1.7
+    x[0] = rnd_(K, seed=136) * 8.0 + 0.4
+    x[:, K - 1] += 40.0
+    x = x.to(torch.bfloat16)
+    w, bias = rnd_(N, K, seed=131) / K ** 0.5, rnd_(N, seed=132) * 0.1
+    gamma, beta = rnd_(K, seed=133) * 0.1 + 1, rnd_(K, seed=134) * 0.1
+    wg = (w * gamma[None, :]).to(torch.bfloat16)
+    colsum = wg.float().sum(1)
+    cvec = w.to(torch.bfloat16).float() @ beta + bias
+    return x, wg, cvec, colsum, w, bias, gamma, beta
+
+
+def fold_bound(x, wg, colsum, cvec, stats, epi=0):
+    """(ref, bound), fp64 [M, N], of ov_gemm_ln's output under epilogue epi (0 bias, 1 GELU erf, 2 GELU tanh).
+
+    The reference is the kernel's stated formula in fp64 on exactly the operands it receives (x, W' bf16; colsum, cvec, {mean, rstd}
+    fp32):  ref = rstd t + cvec,  t = x W'^T - mean colsum.   e = 2^-24, REL = 2^-8, S1 = |x| |W'|^T:
+        A     = rstd e (K S1 + 2 |t| + |mean colsum|) + 2 e |ref|
+        bound = REL (|ref| + A) + A
+    The kernel forms acc = x W'^T in fp32 (any order: off by at most K e S1), t32 = fma(colsum, -mean, acc) (one rounding, e |t|, of
+    a value whose product term is exact inside the fma) and v = fma(t32, rstd, cvec) (one rounding, e |ref|); acc's error and t32's
+    rounding are multiplied by rstd.  A carries each of these twice over where it costs nothing (2 |t|, 2 e |ref|) and |mean colsum|
+    once more for the cancellation's second-order terms, so that no absolute floor is needed.  The output is v rounded to bf16 once:
+    REL (|ref| + A).  With a GELU: 1.13 (= max |gelu'|) times the pre-activation's error, + the output rounding + the form's own error
+    E (as in linear_ratios):  1.13 A (1 + REL) + REL |gelu(ref)| + E.
+    No tuned term.  What it tells apart: test_gemm_small_bound.py."""
+    K = x.shape[1]
+    xd, wd = x.double(), wg.double()
+    mean, rstd = stats[:, 0:1].double(), stats[:, 1:2].double()
+    mc = mean * colsum.double()
+    t = xd @ wd.T - mc
+    ref = rstd * t + cvec.double()
+    s1 = (x.float().abs() @ wg.float().abs().T).double()
+    a = rstd * E32 * (K * s1 + 2 * t.abs() + mc.abs()) + 2 * E32 * ref.abs()
+    if epi == 0:
+        return ref, REL * (ref.abs() + a) + a
+    act = gelu64(ref, epi == 2)
+    e = E_TANH if epi == 2 else torch.clamp(6.6e-5 * ref.abs(), min=1.4e-4)
+    return act, 1.13 * (a * (1 + REL)) + REL * act.abs() + e
+
+
+def fold_ratios_bound(x, wg, colsum, cvec, stats, outs):
+    """outs: name -> (bf16 [M, >= N], epi 0 | 1 | 2).  name -> (max err / fold_bound, row, column), in row chunks."""
+    M, N = x.shape[0], wg.shape[0]
+    res = {}
+    for i in range(0, M, CHUNK):
+        sl = slice(i, min(M, i + CHUNK))
+        for name, (got, epi) in outs.items():
+            ref, bound = fold_bound(x[sl], wg, colsum, cvec, stats[sl], epi)
+            _merge(res, name, _worst((got[sl, :N].double() - ref).abs(), bound, i))
+    return res
+
+
+def patch_rows(out, B, g2):
+    """The rows a launch with out_group = g2 writes, [B g2, cols], of out [B (g2 + 1), cols] (row b (g2 + 1), image b's class row,
+    is not written) -- through a view, restating none of the kernel's index arithmetic."""
+    return out.unflatten(0, (B, g2 + 1))[:, 1:].reshape(B * g2, out.shape[1])
+
+
+def class_rows(out, B, g2):
+    return out.unflatten(0, (B, g2 + 1))[:, 0]
+
+
+LN_RTOL, LN_ATOL = 1.5e-2, 2e-2
+
+
+def ln_linear_ratios(operands, outs):
+    """The tuned rule of test_gemm_ln_fold_matches_layernorm_then_linear, kept beside fold_bound: operands = (x, wg, cvec, colsum, w,
+    bias, gamma, beta) as fold_operands / spiked_fold_case build them; outs: name -> (bf16 [M, >= N], epi 0 | 1 | 2) of ov_gemm_ln.
+    name -> (max err / (LN_ATOL + LN_RTOL |ref|), row, column) against Linear(LayerNorm(x)) (then GELU) in fp64, in row chunks."""
+    x, _, _, _, w, bias, gamma, beta = operands
+    M, N = x.shape[0], w.shape[0]
+    wd = w.double()
+    res = {}
+    for i in range(0, M, CHUNK):
+        sl = slice(i, min(M, i + CHUNK))
+        xd = x[sl].double()
+        mu, var = xd.mean(1, keepdim=True), xd.var(1, unbiased=False, keepdim=True)
+        lin = ((xd - mu) * (var + 1e-6).rsqrt() * gamma.double() + beta.double()) @ wd.T + bias.double()
+        for name, (got, epi) in outs.items():
+            ref = gelu64(lin, epi == 2) if epi else lin
+            _merge(res, name, _worst((got[sl, :N].double() - ref).abs(), LN_ATOL + LN_RTOL * ref.abs(), i))
+    return res

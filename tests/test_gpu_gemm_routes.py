@@ -27,55 +27,31 @@ Bound per element, derived, not tuned (REL = 2^-8 = hipops.REL: one bf16 roundin
                the tanh GELU, so the restatement in fp64 differs from fp64 0.5 x (1 + tanh u) by 1.8e-15; evaluated in fp32 (numpy,
                the same operation order) on the 2^-12 grid over [-8, 8] the maximum difference is 5.2e-7 (the |x| weighting
                included: it is the error of the GELU value itself).  With the factor 2: E = 1.1e-6.
-    LN fold:   x Wg - mean colsum cancels, the bounds above do not apply: the rule of
+    GELU':     the GELU-gradient epilogues, out = bf16(bf16(pre) g32(R)):  |g'(R)| (the bias bound) + delta (|pre| + the bias bound)
+               + REL |ref| against pre g'(R) with the exact fp64 derivative; delta = hipops.DELTA_GRAD_ERF / _TANH.
+    LN fold:   x Wg - mean colsum cancels, the bounds above do not apply.  Two rules, both asserted: hipops.fold_bound, derived from
+               the kernel's formula on the operands it receives (no tuned term; see there), and the older tuned rule of
                test_gemm_ln_fold_matches_layernorm_then_linear, |got - ref| <= 2e-2 + 1.5e-2 |ref| against Linear(LayerNorm(x)) in
                fp64, the same input construction (mean 0.4, spread 1.7).
+
+The helpers (route, linear_ratios, report, ...) live in hipops.py, shared with test_gpu_gemm_small_routes.py.
 
 Every output starts as the bf16 sentinel 77, so a skipped tile fails the bound instead of passing as zeros, and padding behind the
 last valid column must still hold it.  Every case asserts, from a restatement of the launcher's rules and the device's CU count,
 that the form it names is the one selected."""
 import functools
-import math
 import os
 import subprocess
 import sys
 import tempfile
-from types import SimpleNamespace
 
 import pytest
 import torch
 
 import hipops as H
+from hipops import BM, BN, DEV, SENT, fold_ratios_bound, linear_ratios, ln_linear_ratios, padding_kept, report, route, sentinel
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-BM = BN = 256
-BK = 64
-SKINNY_TILES = 96
-SENT = 77.0
-REL = H.REL
-E_TANH = 1.1e-6
-LN_RTOL, LN_ATOL = 1.5e-2, 2e-2
-CHUNK = 4096                      # rows per fp64 chunk: 4096 x 4096 x 8 B = 128 MB for the widest N here
-
-
-def route(M, N, K, epi=0, keep=False, nt_min_mb=192):
-    """What gemm.hip's launcher selects for this shape on this device (launch<EPI>, gemm_ngroup, persist_policy)."""
-    cus = torch.cuda.get_device_properties(0).multi_processor_count
-    tm, tn = -(-M // BM), -(-N // BN)
-    nwg = tm * tn
-    if not keep and nwg <= SKINNY_TILES:
-        kernel = "skinny"
-    elif nwg < cus or K < 3 * BK:
-        kernel = "plain"
-    else:
-        kernel = "persistent"
-    wbytes = tn * BN * K * 2
-    ngroup = tn if (wbytes <= (3 << 20) or tn <= 4 or tn % 4 or tm < 16) else 4
-    rem, nper = N % BN, cus >> 3
-    rot = tn - 1 if (0 < rem <= 128 and ngroup >= tn and tn > 1 and tn & (tn - 1) == 0 and cus % 8 == 0 and nper % tn == 0) else 0
-    return SimpleNamespace(cus=cus, tm=tm, tn=tn, nwg=nwg, kernel=kernel, grouped=ngroup < tn, groups=tn // ngroup, rot=rot, rem=rem,
-                           pr=tm & 7, rev=epi == 3 and K >= 2 * N, st_plain=M * N * 2 < (nt_min_mb << 20), wbytes=wbytes)
 
 
 # case -> (M, N, K), the walk it must select, and what else makes it the case it is (each asserted before the launch)
@@ -141,92 +117,20 @@ def fold_operands(M, N, K):
     return tuple(t.to(DEV) for t in (x, wg, cvec, colsum, w, bias, gamma, beta))
 
 
-def gelu64(x, tanh):
-    return torch.nn.functional.gelu(x, approximate="tanh" if tanh else "none")
-
-
-def _worst(err, bound, row0):
-    q = err / bound
-    k = int(q.argmax())
-    return float(q.view(-1)[k]), row0 + k // q.shape[1], k % q.shape[1]
-
-
-def _merge(res, name, item):
-    old = res.get(name)
-    if old is None or math.isnan(item[0]) or item[0] > old[0]:        # (a NaN is kept: it fails the assertion)
-        res[name] = item
-
-
-def linear_ratios(a, w, bias, outs, r=None):
-    """outs: name -> (bf16 [M, >= N], kind), kind in pre | erf | tanh | res | res1 (res1: the residual under the ONE-rounding bound, for
-    the record).  Returns name -> (max err / bound, row, column) against fp64 on the device, in row chunks."""
-    M, K = a.shape
-    N = w.shape[0]
-    wd, wabs, bd = w.double(), w.float().abs(), bias.double()
-    res = {}
-    for i in range(0, M, CHUNK):
-        sl = slice(i, min(M, i + CHUNK))
-        pre = a[sl].double() @ wd.T + bd
-        s = (a[sl].float().abs() @ wabs.T + bias.abs()).double()
-        b_pre = REL * pre.abs() + K * 2.0 ** -24 * s + 1e-6
-        for name, (got, kind) in outs.items():
-            g = got[sl, :N].double()
-            if kind == "pre":
-                ref, bound = pre, b_pre
-            elif kind in ("res", "res1"):
-                rr = r[sl].double()
-                ref = pre + rr
-                bound = REL * ref.abs() + K * 2.0 ** -24 * (s + rr.abs()) + 1e-6
-                if kind == "res":
-                    bound = bound + REL * (1 + REL) * pre.abs()
-            else:
-                ref = gelu64(pre, kind == "tanh")
-                e = E_TANH if kind == "tanh" else torch.clamp(6.6e-5 * pre.abs(), min=1.4e-4)
-                bound = 1.13 * b_pre + REL * ref.abs() + e
-            _merge(res, name, _worst((g - ref).abs(), bound, i))
-    return res
-
-
 def fold_ratios(M, N, K, outs):
     """outs: name -> (bf16 [M, >= N], epi 0 | 1 | 2) of ov_gemm_ln on fold_operands(M, N, K): max err / (atol + rtol |ref|) against
     Linear(LayerNorm(x)) (then GELU) in fp64."""
-    x, _, _, _, w, bias, gamma, beta = fold_operands(M, N, K)
-    wd = w.double()
-    res = {}
-    for i in range(0, M, CHUNK):
-        sl = slice(i, min(M, i + CHUNK))
-        xd = x[sl].double()
-        mu, var = xd.mean(1, keepdim=True), xd.var(1, unbiased=False, keepdim=True)
-        lin = ((xd - mu) * (var + 1e-6).rsqrt() * gamma.double() + beta.double()) @ wd.T + bias.double()
-        for name, (got, epi) in outs.items():
-            ref = gelu64(lin, epi == 2) if epi else lin
-            _merge(res, name, _worst((got[sl, :N].double() - ref).abs(), LN_ATOL + LN_RTOL * ref.abs(), i))
-    return res
+    return ln_linear_ratios(fold_operands(M, N, K), outs)
 
 
-def report(tag, res, skip=()):
-    for name, (q, row, col) in res.items():
-        print(f"{tag} {name}: max err / bound {q:.3f}")
-    bad = {n: (q, f"row {row} column {col} = tile ({row // BM}, {col // BN})") for n, (q, row, col) in res.items()
-           if n not in skip and not q <= 1.0}
-    assert not bad, (tag, bad)
+EPI_KIND = {0: "pre", 1: "erf", 2: "tanh", 3: "res", 4: "gerf", 5: "gtanh"}
+EPI_NAME = {0: "bias", 1: "gelu erf", 2: "gelu tanh", 4: "gelu' erf", 5: "gelu' tanh"}
 
 
-def sentinel(M, width):
-    return torch.full((M, width), SENT, dtype=torch.bfloat16, device=DEV)
-
-
-def padding_kept(out, N):
-    return bool((out[:, N:] == SENT).all())
-
-
-EPI_KIND = {0: "pre", 1: "erf", 2: "tanh", 3: "res"}
-
-
-@pytest.mark.parametrize("epi", [0, 1, 3])
-@pytest.mark.parametrize("case", [1, 2, 3, 4, 5, 6, 7])
+@pytest.mark.parametrize("case,epi", [(case, epi) for case in (1, 2, 3, 4, 5, 6, 7) for epi in (0, 1, 3)] + [(1, 2), (1, 4), (1, 5)])
 def test_walk_epilogues_within_the_fp64_bound(case, epi):
-    """Bias, erf-GELU and in-place residual epilogues over the plain, rotated and grouped walks of the case table."""
+    """Bias, erf-GELU and in-place residual epilogues over the plain, rotated and grouped walks of the case table; on case 1 the
+    persistent kernel's tanh-GELU and GELU-gradient instantiations too (R = the pre-activation, out of place)."""
     M, N, K = selected(case, epi)
     a, w, bias = operands(M, N, K)
     if epi == 3:
@@ -236,8 +140,9 @@ def test_walk_epilogues_within_the_fp64_bound(case, epi):
         res = linear_ratios(a, w, bias, {"residual": (out, "res"), "residual (one-rounding bound)": (out, "res1")}, r)
         report(f"case {case} {(M, N, K)}", res, skip=("residual (one-rounding bound)",))
     else:
-        out = H.gemm(a, w, bias, epi=epi, out=sentinel(M, N))
-        report(f"case {case} {(M, N, K)}", linear_ratios(a, w, bias, {("bias", "gelu erf")[epi]: (out, EPI_KIND[epi])}))
+        r = residual(M, N) if epi > 3 else None
+        out = H.gemm(a, w, bias, epi=epi, resid=r, out=sentinel(M, N))
+        report(f"case {case} {(M, N, K)}", linear_ratios(a, w, bias, {EPI_NAME[epi]: (out, EPI_KIND[epi])}, r))
 
 
 def test_grouped_walk_with_descending_rows_residual():
@@ -266,8 +171,10 @@ def test_grouped_walk_keep_both_outputs(case):
 def test_grouped_walk_ln_fold(case, epi):
     M, N, K = selected(case, epi)
     x, wg, cvec, colsum = fold_operands(M, N, K)[:4]
-    out = H.gemm_ln(x, wg, cvec, colsum, H.rowstats(x), epi=epi, out=sentinel(M, N + 8))
+    st = H.rowstats(x)
+    out = H.gemm_ln(x, wg, cvec, colsum, st, epi=epi, out=sentinel(M, N + 8))
     report(f"case {case} {(M, N, K)} LN fold", fold_ratios(M, N, K, {("bias", "gelu erf")[epi]: (out, epi)}))
+    report(f"case {case} {(M, N, K)} LN fold, fold_bound", fold_ratios_bound(x, wg, colsum, cvec, st, {("bias", "gelu erf")[epi]: (out, epi)}))
     assert padding_kept(out, N)
 
 

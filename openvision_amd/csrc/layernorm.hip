@@ -187,7 +187,8 @@ __global__ __launch_bounds__(256) void rowparts_kernel(const ov_bf16* __restrict
 }
 // {mean, rstd} of a row from its G partial sums: mean = S / D, var = Q / D - mean^2 (clamped at 0).  One pass instead of
 // rowstats_rows' two: fp32 sums of D <= 8192 bf16 values carry ~1e-7 relative error, so var is good to ~1e-7 (1 + mean^2 / var)
-// relative -- the LayerNorm inputs here have |mean| of the order of their standard deviation or below.  Eight lanes per row (a row's
+// relative -- the LayerNorm inputs here have |mean| of the order of their standard deviation or below (the domain, as a table of
+// |mean| / std against D: DESIGN.md §4, "The row passes against fp64"; tests/test_ln_rows_bound.py pins it).  Eight lanes per row (a row's
 // G float2 are contiguous: coalesced 8-byte reads), each adds its groups g = k, k + 8, ... in that order, then a fixed xor tree over
 // the eight lanes (the same for every row, whatever wrote the sums).
 __global__ __launch_bounds__(256) void rowstats_finalize_kernel(const float* __restrict__ parts, float* __restrict__ st, int64_t rows, int G, float invD, float eps) {

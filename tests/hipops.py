@@ -17,13 +17,16 @@ def _flag(t):
     return OV_F32 if t.dtype == torch.float32 else OV_BF16
 
 
-def layernorm(x, g, b, eps=1e-6, out_dtype=None):
+def layernorm(x, g, b, eps=1e-6, out_dtype=None, out=None):
+    """x, out: bf16 or fp32, each side on its own.  A 2-D x with unit column stride goes in as it is, its row pitch as ldx (a view of
+    a wider buffer, or rows L D apart); out (optional): a caller-owned [rows, >= D] view, its row pitch as ldy."""
     lib = _lib.load()
-    x2 = x.contiguous().view(-1, x.shape[-1])
-    y = torch.empty(x2.shape, dtype=out_dtype or x.dtype, device=x.device)
-    check(lib.ov_layernorm(ptr(x2), _flag(x2), x2.shape[1], ptr(g), ptr(b), ptr(y), _flag(y), x2.shape[1], x2.shape[0],
-                           x2.shape[1], eps, stream_ptr()))
-    return y.view(x.shape)
+    D = x.shape[-1]
+    x2 = x if x.dim() == 2 and x.stride(1) == 1 else x.contiguous().view(-1, D)
+    y = out if out is not None else torch.empty(x2.shape, dtype=out_dtype or x.dtype, device=x.device)
+    check(lib.ov_layernorm(ptr(x2), _flag(x2), x2.stride(0), ptr(g), ptr(b), ptr(y), _flag(y), y.stride(0), x2.shape[0],
+                           D, eps, stream_ptr()), "ov_layernorm")
+    return y if out is not None else y.view(x.shape)
 
 
 def gemm(a, w, bias=None, epi=0, resid=None, out=None, out_group=0, resid_mod=0, resid_off=0, out_rows=None):
@@ -958,7 +961,7 @@ def spiked_fold_case(M, N, K):
     return x, wg, cvec, colsum, w, bias, gamma, beta
 
 
-def fold_bound(x, wg, colsum, cvec, stats, epi=0):
+def fold_bound(x, wg, colsum, cvec, stats, epi=0, stat_err=None):
     """(ref, bound), fp64 [M, N], of ov_gemm_ln's output under epilogue epi (0 bias, 1 GELU erf, 2 GELU tanh).
 
     The reference is the kernel's stated formula in fp64 on exactly the operands it receives (x, W' bf16; colsum, cvec, {mean, rstd}
@@ -971,7 +974,13 @@ def fold_bound(x, wg, colsum, cvec, stats, epi=0):
     once more for the cancellation's second-order terms, so that no absolute floor is needed.  The output is v rounded to bf16 once:
     REL (|ref| + A).  With a GELU: 1.13 (= max |gelu'|) times the pre-activation's error, + the output rounding + the form's own error
     E (as in linear_ratios):  1.13 A (1 + REL) + REL |gelu(ref)| + E.
-    No tuned term.  What it tells apart: test_gemm_small_bound.py."""
+    No tuned term.  What it tells apart: test_gemm_small_bound.py.
+
+    stat_err = (b_mean, dr), fp64 [M]: the statistics came from a kernel and are within b_mean of `stats`' mean and dr of its rstd
+    (row_stats_ref64; `stats` then holds the fp64 statistics unrounded).  The mean's error reaches the output through
+    (rstd + dr) b_mean |colsum|, rstd's through dr |t|, and A's own terms grow by 1 + dr / rstd.  The reference becomes
+    Linear(LayerNorm(x)) on the folded operands, xhat W'^T + cvec = ref + d with d = rstd mean (colsum - sum_k W'): what the fp32
+    colsum the kernel is handed differs from the exact row sums by, an operand's error and so added to A in full."""
     K = x.shape[1]
     xd, wd = x.double(), wg.double()
     mean, rstd = stats[:, 0:1].double(), stats[:, 1:2].double()
@@ -980,6 +989,11 @@ def fold_bound(x, wg, colsum, cvec, stats, epi=0):
     ref = rstd * t + cvec.double()
     s1 = (x.float().abs() @ wg.float().abs().T).double()
     a = rstd * E32 * (K * s1 + 2 * t.abs() + mc.abs()) + 2 * E32 * ref.abs()
+    if stat_err is not None:
+        bm, dr = (v.double().view(-1, 1) for v in stat_err)
+        cs, d = colsum.double().abs(), rstd * mean * (colsum.double() - wd.sum(1))
+        a = a * (1 + dr / rstd) + (rstd + dr) * bm * cs + dr * t.abs() + d.abs()
+        ref = ref + d
     if epi == 0:
         return ref, REL * (ref.abs() + a) + a
     act = gelu64(ref, epi == 2)
@@ -1029,3 +1043,257 @@ def ln_linear_ratios(operands, outs):
             ref = gelu64(lin, epi == 2) if epi else lin
             _merge(res, name, _worst((got[sl, :N].double() - ref).abs(), LN_ATOL + LN_RTOL * ref.abs(), i))
     return res
+
+
+# ---- the row passes: LayerNorm, the row statistics (two-pass and one-pass) and the rows around the towers' heads
+#
+# Closed forms in fp64 on the operands the kernels receive, with per-element bounds from u = 2^-8, e = 2^-24 and
+# gamma_n = n e / (1 - n e) alone: no tuned term, no absolute floor, nothing of a kernel's summation order (derivations: DESIGN.md §4,
+# "The row passes against fp64"; what the bounds tell apart: test_ln_rows_bound.py).
+
+
+def gam(n):
+    return n * E32 / (1 - n * E32)
+
+
+def eps32(eps):
+    """eps as the kernels receive it: a C float."""
+    return float(torch.tensor(eps, dtype=torch.float32))
+
+
+def rstd_interval(var, b_var, eps):
+    """[lo, hi] of an fp32 rsqrtf(var^ + eps) whose var^ is within b_var of var (and >= 0): the eps add rounds once, rsqrtf is
+    within one ulp (2 e): (1 +- 3 e) covers both."""
+    return (var + eps + b_var).rsqrt() * (1 - 3 * E32), ((var - b_var).clamp_min(0) + eps).rsqrt() * (1 + 3 * E32)
+
+
+class RowRef:
+    """What row_stats_ref64 returns, all fp64 [R]: mean, var (biased), rstd; b_mean; b_var2 / b_var1 and the rstd intervals rstd2 /
+    rstd1 = (lo, hi) of the two-pass (ov_layernorm, ov_rowstats) and one-pass (ov_rowstats_finalize) forms."""
+
+
+def row_stats_ref64(x, eps=1e-6):
+    """mean: a D-term fp32 sum in any order (gamma_{D-1} mean|x|), 1 / D rounded, one product: gamma_D mean|x| + e |mean|.
+    Two-pass variance: d = x - mean^ rounds once (twice in d^2), the square once, D - 1 additions, 1 / D and the product: D + 4
+    roundings of mean((x - mean^)^2) = var + (mean^ - mean)^2 <= var + b_mean^2.
+    One-pass variance Q / D - mean^2: Q / D as the mean (the squares of bf16 values are exact in fp32); mean^2 carries the mean's
+    error twice, 2 |mean| b_mean + b_mean^2, its rounding and the subtraction's: 2 e mean^2 + e var.  The clamp at 0 only helps."""
+    xd = x.double()
+    g = gam(xd.shape[1])
+    r = RowRef()
+    r.mean, r.eps = xd.mean(1), eps32(eps)
+    r.var = ((xd - r.mean[:, None]) ** 2).mean(1)
+    r.rstd = (r.var + r.eps).rsqrt()
+    r.b_mean = g * xd.abs().mean(1) + E32 * r.mean.abs()
+    r.b_var2 = (g + 4 * E32) * (r.var + r.b_mean ** 2) + r.b_mean ** 2
+    r.b_var1 = ((g + 2 * E32) * (xd * xd).mean(1) + 2 * r.mean.abs() * r.b_mean + r.b_mean ** 2 + 2 * E32 * r.mean ** 2
+                + E32 * r.var)
+    r.rstd2, r.rstd1 = rstd_interval(r.var, r.b_var2, r.eps), rstd_interval(r.var, r.b_var1, r.eps)
+    return r
+
+
+def _over(num, den):
+    """num / den with 0 / 0 = 0 (an all-zero row: bound 0, error 0) and a NaN numerator kept (it fails every assertion)."""
+    return torch.where((num == 0) & (den == 0), torch.zeros_like(num), num / den)
+
+
+def stats_ratios(st, ref, onepass=False):
+    """(mean, rstd, rstd against the two-pass interval) of {mean, rstd} [R, 2]: |mean^ - mean| / b_mean, and how far rstd^ stands
+    from rstd as a fraction of the interval's side it lies on (<= 1: inside), each the maximum over the rows, with the row."""
+    got = st.double()
+    qm = _over((got[:, 0] - ref.mean).abs(), ref.b_mean)
+    res = [qm]
+    for lo, hi in (ref.rstd1 if onepass else ref.rstd2, ref.rstd2):
+        d = got[:, 1] - ref.rstd
+        res.append(torch.where(d >= 0, d / (hi - ref.rstd), -d / (ref.rstd - lo)))
+    out = []
+    for q in res:
+        q = torch.where(torch.isnan(q), torch.full_like(q, float("inf")), q)
+        k = int(q.argmax())
+        out.append((float(q[k]), k))
+    return out
+
+
+def ln_ref64(x, gamma, beta, eps=1e-6, out_bf16=True):
+    """(y, bound) fp64 [R, D] of ov_layernorm, y = (x - mean) rstd gamma + beta.  With dr the rstd interval's wider side and hi its
+    upper end:  d^ = x - mean^ is off by b_mean + e (|x - mean| + b_mean);  d^ rstd^ by
+        E1 = |x - mean| dr + hi (b_mean + e (|x - mean| + b_mean));
+    that product and the one with gamma round once each, gamma_2 (|x - mean| rstd + E1), and the sum with beta once:
+        E2 = |gamma| (E1 + gamma_2 (|x - mean| rstd + E1)),   bound = E2 + e (|y| + E2)   [+ u (|y| + bound) for a bf16 output]."""
+    st = row_stats_ref64(x, eps)
+    g, b = gamma.double(), beta.double()
+    xc = (x.double() - st.mean[:, None]).abs()
+    rstd, bm = st.rstd[:, None], st.b_mean[:, None]
+    y = (x.double() - st.mean[:, None]) * rstd * g + b
+    lo, hi = st.rstd2
+    dr = torch.maximum(hi - st.rstd, st.rstd - lo)[:, None]
+    e1 = xc * dr + hi[:, None] * (bm + E32 * (xc + bm))
+    e2 = g.abs() * (e1 + gam(2) * (xc * rstd + e1))
+    bound = e2 + E32 * (y.abs() + e2)
+    return y, bound + U16 * (y.abs() + bound) if out_bf16 else bound
+
+
+def ratio(got, ref, bound):
+    """(max |got - ref| / bound, flat index), 0 / 0 = 0, NaN = inf."""
+    q = _over((got.double() - ref).abs(), bound)
+    q = torch.where(torch.isnan(q), torch.full_like(q, float("inf")), q).reshape(-1)
+    k = int(q.argmax())
+    return float(q[k]), k
+
+
+LADDER = (0.0, 1.0, 8.0, 64.0, 512.0)     # mean / std of the statistics' rows
+CONST_ROW = 100.0                         # the constant row's value: Q / D and mean^2 are 1e4, their roundings far above eps
+
+
+def spiked_rows_case(rows, D, seed, f32=False):
+    """(x [rows, D] bf16 or fp32, gamma, beta fp32) for ov_layernorm / ov_rowstats: x = 0.4 + 1.7 N(0, 1); the last 8 columns -- the
+    chunk of the last live lane of the last c -- carry +40; the last row (in the grid-stride tail where there is one) has
+    mean / std = 8; row 0 has spread 8; row 1 (rows >= 3) is constant.  beta's last 8 entries sit 2 higher: the outputs there are
+    large (the +40), and a beta of 0.1 would hide in their bf16 rounding."""
+    g = torch.Generator().manual_seed(7919 * D + rows + seed)
+    x = torch.randn(rows, D, generator=g) * 1.7 + 0.4
+    if rows > 1:
+        x[0] = torch.randn(D, generator=g) * 8.0 + 0.4
+    x[rows - 1] = torch.randn(D, generator=g) * 1.7 + 8 * 1.7
+    x[:, D - 8:] += 40.0
+    if rows >= 3:
+        x[1] = CONST_ROW
+    gamma, beta = torch.randn(D, generator=g) * 0.1 + 1, torch.randn(D, generator=g) * 0.1
+    beta[D - 8:] += 2.0
+    return (x if f32 else x.to(torch.bfloat16)), gamma, beta
+
+
+def ladder_rows_case(rows, D, seed=0):
+    """x bf16 [rows, D] for the statistics: row i = 1.7 N(0, 1) + 1.7 LADDER[i mod 5], +40 on the last eight channels; the row before
+    the last (rows >= 7) is constant, and the one before that nearly so: 1000 with the last two channels one bf16 step higher, 1004
+    (var = 0.03 against mean^2 = 1e6: the one-pass difference is all rounding there, and this is the row on which the clamp at 0
+    acts -- an exactly constant row is summed exactly by any tree).  ladder_of(rows) gives each row's rung (-1, -2: these two)."""
+    g = torch.Generator().manual_seed(104729 * D + rows + seed)
+    x = torch.randn(rows, D, generator=g) * 1.7 + 1.7 * torch.tensor(LADDER)[torch.arange(rows) % 5, None]
+    x[:, D - 8:] += 40.0
+    if rows >= 7:
+        x[rows - 2] = CONST_ROW
+        x[rows - 3] = 1000.0
+        x[rows - 3, D - 2:] = 1004.0
+    return x.to(torch.bfloat16)
+
+
+def ladder_of(rows):
+    r = torch.arange(rows) % 5
+    if rows >= 7:
+        r[rows - 2], r[rows - 3] = -1, -2
+    return r
+
+
+LN_EDGE_D = [8, 192, 512, 520, 1152, 2048, 2056, 4304, 8192]      # NCH 1, 1, 1 full, 2 (one lane), 3, 4 full, 8 (one lane), 16, 16 full
+LN_EDGE_ROWS = (1, 3, 5)
+LN_LAP_CASE = (65541, 64)                 # 16384 workgroups x 4 rows + 5: the second grid-stride lap
+LN_ALL_DTYPES_D = (520, 1152)
+FINALIZE_G = [1, 6, 8, 9, 36, 128, 256]
+FINALIZE_ROWS = (1, 31, 32, 33)
+POOL_L = (2, 4, 5, 257)
+POOL_D = (8, 520, 1152)
+L2_E = (1, 40, 64, 65, 768)
+L2_LAP_CASE = (32771, 40)                 # 8192 workgroups x 4 rows + 3
+
+
+def parts_ref64(x):
+    """(S, Q fp64 [R, D / 32], their bounds): a 32-term fp32 sum in any order, gamma_31 sum|x| and gamma_31 sum x^2 (the squares of
+    bf16 values are exact in fp32)."""
+    c = x.double().unflatten(1, (x.shape[1] // 32, 32))
+    return c.sum(-1), (c * c).sum(-1), gam(31) * c.abs().sum(-1), gam(31) * (c * c).sum(-1)
+
+
+def fold_chain_ratios(x, wg, colsum, cvec, outs, onepass, eps=1e-6):
+    """outs: name -> (bf16 [M, >= N], epi) of ov_gemm_ln run on a statistics kernel's {mean, rstd}.  name -> (max err / bound, row,
+    column) against Linear(LayerNorm(x)) in fp64 on the folded operands, ref = xhat W'^T + cvec: fold_bound at the fp64 statistics
+    with the statistics' own bounds carried through (its stat_err)."""
+    res = {}
+    for i in range(0, x.shape[0], CHUNK):
+        sl = slice(i, min(x.shape[0], i + CHUNK))
+        st = row_stats_ref64(x[sl], eps)
+        lo, hi = st.rstd1 if onepass else st.rstd2
+        err = (st.b_mean, torch.maximum(hi - st.rstd, st.rstd - lo))
+        for name, (got, epi) in outs.items():
+            ref, bound = fold_bound(x[sl], wg, colsum, cvec, torch.stack([st.mean, st.rstd], 1), epi, stat_err=err)
+            _merge(res, name, _worst((got[sl, :wg.shape[0]].double() - ref).abs(), bound, i))
+    return res
+
+
+def pool_case(B, L, D, seed=0):
+    """x bf16 [B L, D] = 0.4 + 1.7 N(0, 1), each sequence's row 0 (the class row) 40 higher."""
+    g = torch.Generator().manual_seed(31 * L + D + B + seed)
+    x = torch.randn(B, L, D, generator=g) * 1.7 + 0.4
+    x[:, 0] += 40.0
+    return x.reshape(B * L, D).to(torch.bfloat16)
+
+
+def mean_pool_ref64(x, B, L, first):
+    """(ref, bound) fp64 [B, D]: the mean over tokens first .. L - 1, n = L - first terms in any order, 1 / n rounded, one product:
+    gamma_n mean_t|x| + e |ref|."""
+    t = x.double().unflatten(0, (B, L))[:, first:]
+    ref = t.mean(1)
+    return ref, gam(L - first) * t.abs().mean(1) + E32 * ref.abs()
+
+
+def l2norm_case(rows, E, f32, seed=0):
+    """x [rows, E] ~ N(0, 1), the last element of every row 8 times larger (in the lanes' tail when E % 64 != 0); with rows >= 3,
+    row 1 is all zero and row 2 holds 1e-20 N(0, 1) (norm far below the 1e-12 clamp)."""
+    g = torch.Generator().manual_seed(53 * E + rows + seed)
+    x = torch.randn(rows, E, generator=g)
+    x[:, E - 1] *= 8.0
+    if rows >= 3:
+        x[1] = 0.0
+        x[2] = torch.randn(E, generator=g) * 1e-20
+    return x if f32 else x.to(torch.bfloat16)
+
+
+def l2norm_ref64(x):
+    """(ref, bound) fp64 of ov_l2norm, y = x / max(|x|_2, 1e-12).  ss = sum x^2: products and E - 1 additions, gamma_E; sqrt halves it
+    and rounds, the reciprocal and the product round: |y| (gamma_E / 2 + 4 e) (the second-order 3/8 gamma_E^2 sits inside the fourth
+    e up to E = 6700).  Under the clamp y = x / fl32(1e-12): the division and the product round, 4 e |y| again; an all-zero row
+    is 0 exactly (bound 0)."""
+    xd = x.double()
+    nrm = xd.pow(2).sum(1, keepdim=True).sqrt()
+    clamp = float(torch.tensor(1e-12, dtype=torch.float32))
+    ref = xd / nrm.clamp_min(clamp)
+    return ref, ref.abs() * torch.where(nrm < clamp, torch.full_like(nrm, 4 * E32), torch.full_like(nrm, gam(x.shape[1]) / 2 + 4 * E32))
+
+
+def cls_rows_ref(cls, pos0):
+    return (cls.to(torch.bfloat16).float() + pos0.to(torch.bfloat16).float()).to(torch.bfloat16)
+
+
+def mean_pool(x, B, L, first, out=None):
+    """ov_mean_pool on x [B L, D] (any row pitch); out: a caller-owned contiguous fp32 [B, D]."""
+    lib = _lib.load()
+    D = x.shape[1]
+    if out is None:
+        out = torch.empty(B, D, dtype=torch.float32, device=x.device)
+    check(lib.ov_mean_pool(ptr(x), x.stride(0), ptr(out), B, L, D, first, stream_ptr()), "ov_mean_pool")
+    return out
+
+
+def l2norm(x, out=None):
+    """ov_l2norm on x [rows, E] bf16 or fp32 (any row pitch); out: a caller-owned fp32 [rows, >= E] view with its own pitch."""
+    lib = _lib.load()
+    if out is None:
+        out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    check(lib.ov_l2norm(ptr(x), _flag(x), x.stride(0), ptr(out), out.stride(0), x.shape[0], x.shape[1], stream_ptr()), "ov_l2norm")
+    return out
+
+
+def gather_rows(x, B, L, t, out=None):
+    lib = _lib.load()
+    D = x.shape[1]
+    if out is None:
+        out = torch.empty(B, D, dtype=torch.bfloat16, device=x.device)
+    check(lib.ov_gather_rows(ptr(x), x.stride(0), ptr(out), out.stride(0), B, L, t, D, stream_ptr()), "ov_gather_rows")
+    return out
+
+
+def cls_rows(x, cls, pos0, B, L):
+    """ov_cls_rows in place on x [B L, >= D] bf16 (D = cls.numel())."""
+    lib = _lib.load()
+    check(lib.ov_cls_rows(ptr(x), x.stride(0), ptr(cls), ptr(pos0), B, L, cls.numel(), stream_ptr()), "ov_cls_rows")
+    return x

@@ -3,6 +3,7 @@ import ctypes as C
 import math
 from types import SimpleNamespace
 
+import numpy as np
 import torch
 
 from openvision_amd import _lib
@@ -1297,3 +1298,428 @@ def cls_rows(x, cls, pos0, B, L):
     lib = _lib.load()
     check(lib.ov_cls_rows(ptr(x), x.stride(0), ptr(cls), ptr(pos0), B, L, cls.numel(), stream_ptr()), "ov_cls_rows")
     return x
+
+
+# ---- the optimiser and the embedding / patch-dropout glue, bit for bit (test_gpu_optim_glue_edges.py on the device,
+# test_optim_glue_cpu.py restated without one; tables and derivations: DESIGN.md §4, "The update and the glue, bit for bit").
+# Every comparand is independent of the kernels' code: oracle/optim_ref.py for the update, integer sums and an fp64 sum for
+# ov_sumsq, torch on the CPU (F.unfold, indexing, .to(bfloat16)) for the glue.  Inputs and comparands are CPU tensors.
+
+LAP = 8192 * 256                          # work items of one grid-stride lap: grids are capped at 8192 workgroups of 256
+ADAM_LAP_N = LAP * 4 + 1024 + 3           # four elements per work item: a second lap of 256 work items, then the n & 3 tail
+SUMSQ_THREADS, SUMSQ_VEC, SUMSQ_PARTS = 256, 4, 1024      # optim.hip: 256 threads x one float4 per load, at most 1024 partial sums
+SUMSQ_CAP = SUMSQ_VEC * SUMSQ_THREADS * SUMSQ_PARTS       # 1 048 576 elements: the largest n of a single lap
+GUARD = 16                                # elements behind every optimiser state buffer, which must keep GUARD_VALUE
+GUARD_VALUE = 77.0
+INT_MAX = 2 ** 31 - 1
+
+
+def bits(t):
+    """A tensor's storage as integers of its element size."""
+    t = t.detach().cpu().contiguous()
+    return t.view({1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()])
+
+
+def same_bits(a, b, nan_ok=False):
+    """Bit equality of two tensors of one shape and dtype; nan_ok: NaN matches NaN whatever its payload."""
+    a, b = a.detach().cpu(), b.detach().cpu()
+    if a.shape != b.shape or a.dtype != b.dtype:
+        return False
+    if nan_ok:
+        na, nb = torch.isnan(a), torch.isnan(b)
+        return bool(torch.equal(na, nb)) and bool(torch.equal(bits(a)[~na], bits(b)[~na]))
+    return bool(torch.equal(bits(a), bits(b)))
+
+
+def same_outputs(got, ref, nan_ok=False):
+    """{name: tensor} against {name: tensor}: the names whose bits differ (empty: all equal)."""
+    assert set(got) == set(ref), (sorted(got), sorted(ref))
+    return sorted(k for k in ref if not same_bits(got[k], ref[k], nan_ok))
+
+
+def f32c(v):
+    """v as a C float argument arrives: rounded to fp32, returned as a Python double."""
+    return float(np.float32(v))
+
+
+def np_bf16(x):
+    """fp32 numpy -> the nearest-even bfloat16 values, as fp32 (torch's rounding, not the oracle's helper)."""
+    return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(torch.bfloat16).float().numpy()
+
+
+# ---- ov_adamw_step
+
+def _ac(n, steps=1, t0=1, b1=0.9, b2=0.95, wd=0.2, lr=1e-3, eps=1e-8, gs=1.0, clip="none", ties=False, mu_off=0, tiny=False, seed=0):
+    return SimpleNamespace(n=n, steps=steps, t0=t0, b1=b1, b2=b2, wd=wd, lr=lr, eps=eps, gs=gs, clip=clip, ties=ties, mu_off=mu_off,
+                           tiny=tiny, seed=seed)
+
+
+CLIP_NORM = 0.25
+GN_SQ = {"above": 7.3, "below": 1e-4, "zero": 0.0}        # sqrt(7.3) / 3 = 0.90 > 0.25 at the smallest grad_scale; sqrt(1e-4) = 0.01 < 0.25
+ADAM_CASES = [_ac(1), _ac(2, wd=0.0), _ac(3), _ac(3, b1=0.5, b2=0.5, ties=True), _ac(4), _ac(5), _ac(7, gs=0.5),
+              _ac(1023, t0=2, b2=0.999, wd=0.0, gs=0.5, clip="above"),
+              _ac(2051, steps=3, gs=1 / 3, clip="above"),                       # three steps at a mid size
+              _ac(2051, t0=1000, b2=0.999, eps=0.0),
+              _ac(2051, t0=100000),                                             # both bias corrections are exactly 1
+              _ac(2051, b1=0.5, b2=0.5, ties=True),
+              _ac(2051, b1=0.5, b2=0.5, ties=True, gs=0.5, wd=0.0, t0=2),
+              _ac(2051, b1=0.0, b2=0.0, t0=2),
+              _ac(2051, lr=0.0),
+              _ac(2051, clip="below", gs=0.5),
+              _ac(2051, clip="zero"),
+              _ac(1027, mu_off=4, clip="above"),                                # mu 8 bytes past a 16-byte boundary
+              _ac(37, tiny=True),                                               # g^2 and (1 - b2) g^2 subnormal
+              _ac(ADAM_LAP_N, clip="above")]                                    # second grid-stride lap + tail, one step
+ADAM_MIN_N = 1023                         # below it a case holds too few elements for a value-only mistake to be sure to show
+ADAM_CHAIN = (2051, 1023)                 # the two groups of the chained ov_sumsq -> ov_adamw_step case
+
+
+def adam_id(c):
+    return (f"n{c.n}-t{c.t0}x{c.steps}-b{c.b1}-{c.b2}-wd{c.wd}-lr{c.lr}-eps{c.eps}-gs{c.gs:.3f}-{c.clip}" +
+            ("-ties" * c.ties) + ("-mu8" * bool(c.mu_off)) + ("-tiny" * c.tiny))
+
+
+def adam_inputs(c):
+    """p, mu (bf16 values held in fp32), nu and one g per step, numpy fp32: p of both signs, a third of it down to 1e-7 so that
+    the last bit of the update shows in it; mu nonzero; g with exact zeros, +-1e4
+    and +-1e-20; nu >= 0, exactly 0 where the first g is 0 (eps > 0 only: with eps = 0 the quotient needs nu > 0).  ties: the
+    first min(n, 256) elements hold mu = 0 and g = +-2 (1 + (2k + 1) 2^-8) 2^e, k = 0 .. 127, e = 0 and -3: under b1 = 0.5 and a
+    power-of-two gradient factor the fp32 moment is an exact bf16 tie, the kept bit of both parities.  tiny: |g| = j 1e-21, so
+    that g^2 and (1 - b2) g^2 are subnormal, over nu = 0 and a subnormal nu."""
+    r = np.random.default_rng(1000 + c.seed + c.n % 9973)
+    n, idx = c.n, np.arange(c.n)
+    sign = np.where(idx & 1, -1.0, 1.0).astype(np.float32)
+    p = r.standard_normal(n)
+    p = np.where(idx % 3 == 0, p * 10.0 ** (-7 * r.random(n)), p).astype(np.float32)      # a third of it small against lr u: the update's last bits show
+    mu = np_bf16(r.standard_normal(n) * 0.05)
+    mu[mu == 0] = 2.0 ** -7
+    nu = ((r.standard_normal(n) * 0.1) ** 2).astype(np.float32) + np.float32(1e-12)
+    gs = []
+    for _ in range(c.steps):
+        g = (r.standard_normal(n) * 0.1).astype(np.float32)
+        g[idx % 11 == 3] = 0.0
+        g[idx % 53 == 7] = (1e4 * sign)[idx % 53 == 7]
+        g[idx % 59 == 9] = (1e-20 * sign)[idx % 59 == 9]
+        if c.tiny:
+            g = (sign * (idx + 1) * 1e-21).astype(np.float32)
+        if c.ties:
+            k = np.arange(256)
+            t = (2.0 * (1 + (2 * (k % 128) + 1) * 2.0 ** -8) * np.where(k < 128, 1.0, 2.0 ** -3)).astype(np.float32)
+            m = min(n, 256)
+            g[:m] = (t * np.where(k % 3 == 0, -1, 1))[:m]
+        gs.append(g)
+    if c.eps > 0:
+        nu[gs[0] == 0] = 0.0
+    if c.tiny:
+        nu = np.where(idx & 2, 0.0, 1e-41).astype(np.float32)
+    if c.ties:
+        mu[:256] = 0.0
+    return SimpleNamespace(p=p, mu=mu, nu=nu, g=gs)
+
+
+def adam_gnorm_sq(c):
+    """The device scalar the test writes for the clip (fp32), or None without clipping."""
+    return None if c.clip == "none" else np.float32(GN_SQ[c.clip])
+
+
+def adam_ref(c, x, gn_sq="case"):
+    """oracle.optim_ref.adamw_step over the case's steps, given what the kernel is given: the betas as the C ABI carries them
+    (fp32), and the global norm as sqrt(fp32 gnorm_sq) * fp32 grad_scale.  -> {p, mu, nu} as torch tensors (mu bfloat16)."""
+    from oracle import optim_ref as O
+    gn_sq = adam_gnorm_sq(c) if isinstance(gn_sq, str) else gn_sq
+    p, mu, nu = x.p, x.mu, x.nu
+    for i, g in enumerate(x.g):
+        clip = {} if gn_sq is None else dict(clip_norm=CLIP_NORM, gnorm=np.sqrt(np.float32(gn_sq)) * np.float32(c.gs))
+        p, mu, nu = O.adamw_step(p, g, mu, nu, c.t0 + i, c.lr, f32c(c.b1), f32c(c.b2), c.eps, c.wd, c.gs, **clip)
+    return adam_out(p, mu, nu)
+
+
+def adam_out(p, mu, nu):
+    assert p.dtype == np.float32 and mu.dtype == np.float32 and nu.dtype == np.float32
+    mu_t = torch.from_numpy(np.ascontiguousarray(mu))
+    assert bool(torch.equal(mu_t.to(torch.bfloat16).float(), mu_t) | bool(torch.isnan(mu_t).any())), "mu does not hold bf16 values"
+    return dict(p=torch.from_numpy(np.ascontiguousarray(p)), mu=mu_t.to(torch.bfloat16), nu=torch.from_numpy(np.ascontiguousarray(nu)))
+
+
+class AdamState:
+    """p, nu (fp32) and mu (bf16) on the device, each with GUARD elements behind its n that must keep GUARD_VALUE; mu starts
+    mu_off elements (2 bytes each) past a 256-byte boundary."""
+
+    def __init__(self, x, mu_off=0):
+        self.n = n = x.p.size
+        def buf(a, dtype, off=0):
+            b = torch.full((off + n + GUARD,), GUARD_VALUE, dtype=dtype, device=DEV)
+            b[off:off + n] = torch.from_numpy(a).to(dtype)
+            return b[off:]
+        self.p, self.nu, self.mu = buf(x.p, torch.float32), buf(x.nu, torch.float32), buf(x.mu, torch.bfloat16, mu_off)
+        assert self.p.data_ptr() % 16 == 0 and self.mu.data_ptr() % 16 == (2 * mu_off) % 16
+
+    def step(self, g, c, t, gn_sq=None):
+        """One ov_adamw_step; g: numpy fp32; gn_sq: None, or a device fp32 scalar handed over by pointer."""
+        gd = torch.from_numpy(g).to(DEV)
+        adamw_step(self.p, gd, self.mu, self.nu, self.n, c.lr, c.b1, c.b2, c.eps, c.wd, t, c.gs, gn_sq, CLIP_NORM if gn_sq is not None else 0.0)
+        assert same_bits(gd, torch.from_numpy(g)), "g was written"
+
+    def read(self):
+        n = self.n
+        for name in ("p", "nu", "mu"):
+            assert bool((getattr(self, name)[n:] == GUARD_VALUE).all()), f"{name}: written past n"
+        return dict(p=self.p[:n].cpu(), mu=self.mu[:n].cpu(), nu=self.nu[:n].cpu())
+
+
+def adamw_step(p, g, mu, nu, n, lr, b1, b2, eps, wd, step, grad_scale, gnorm_sq=None, clip_norm=0.0):
+    """ov_adamw_step in place on the caller's flat device buffers (views with guard elements behind n allowed)."""
+    lib = _lib.load()
+    check(lib.ov_adamw_step(ptr(p), ptr(g), ptr(mu), ptr(nu), n, lr, b1, b2, eps, wd, step, grad_scale, ptr(gnorm_sq), clip_norm,
+                            stream_ptr()), "ov_adamw_step")
+
+
+def sumsq(g, out, accumulate=0):
+    """ov_sumsq into the caller's device scalar `out`; the workspace is exactly ov_sumsq_workspace_bytes() long, and the GUARD
+    floats behind it must stay as they were."""
+    lib = _lib.load()
+    nb = lib.ov_sumsq_workspace_bytes()
+    ws = torch.full((nb // 4 + GUARD,), GUARD_VALUE, dtype=torch.float32, device=g.device)
+    check(lib.ov_sumsq(ptr(g), g.numel(), ptr(out), accumulate, ptr(ws), nb, stream_ptr()), "ov_sumsq")
+    assert bool((ws[nb // 4:] == GUARD_VALUE).all()), "ov_sumsq wrote past its workspace"
+    return out
+
+
+# ---- ov_sumsq
+
+SUMSQ_INT_N = [1, 2, 3, 4, 5, 1027, SUMSQ_CAP - 1, SUMSQ_CAP, SUMSQ_CAP + 1, SUMSQ_CAP + 3, ADAM_LAP_N]
+SUMSQ_PRIOR = 12345.0
+SUMSQ_NORMAL_N = (1 << 20) + 3
+
+
+def sumsq_blocks(n):
+    return min(max((n // 4 + SUMSQ_THREADS - 1) // SUMSQ_THREADS, 1), SUMSQ_PARTS)
+
+
+def sumsq_int_case(n):
+    """g in {0, +-1} (half of it 0) with +-2 on the tail, the last float4, and the element at 4 x 256 x blocks (the first of the
+    second lap) where that lies inside n; -> (g numpy fp32, the exact integer sum of squares, < 2^24)."""
+    r = np.random.default_rng(n)
+    g = r.choice(np.array([0, 0, 1, -1], dtype=np.float32), size=n)
+    probes = list(range(n - (n & 3), n)) + list(range(max(n - (n & 3) - 4, 0), n - (n & 3)))
+    probes += [q for q in (SUMSQ_VEC * SUMSQ_THREADS * sumsq_blocks(n), SUMSQ_CAP) if q < n]
+    for j, q in enumerate(probes):
+        g[q] = 2.0 if j & 1 else -2.0
+    total = int((g.astype(np.int64) ** 2).sum())
+    assert total + int(SUMSQ_PRIOR) < 2 ** 24
+    return g, total
+
+
+def sumsq_chain_length(n, accumulate):
+    """The most fp32 roundings a square passes through on its way into ov_sumsq's result, from n and the header's constants alone
+    (derivation: DESIGN.md): per lap four fused multiply-adds into the thread's sum, one more for a tail element, six adds of the
+    wave's exchange tree and two across the four waves; then ceil(blocks / 256) adds of the finishing thread over the partial
+    sums, the same six and two, and the add onto the prior value."""
+    blocks = sumsq_blocks(n)
+    laps = -(-(n // 4) // (blocks * SUMSQ_THREADS))
+    return SUMSQ_VEC * laps + (1 if n & 3 else 0) + 6 + 2 + -(-blocks // SUMSQ_THREADS) + 6 + 2 + (1 if accumulate else 0)
+
+
+# ---- the glue of embed.hip: inputs on the CPU, comparands from torch alone
+
+IM2COL_GEOM = [(28, 14, 592), (28, 14, 640), (160, 16, 768), (16, 8, 192)]       # (S, P, Kpad); 3 P^2 = 588, 588, 768, 192
+IM2COL_LAP = (21850, 16, 8, 192)                                                 # B x 4 patches x 24 chunks = 2 097 600 > LAP
+KEEP_GEOM = [(28, 14, 592), (56, 14, 640), (160, 16, 768)]                       # G = 4, 16, 100
+COL2IM_GEOM = [(28, 14), (56, 14), (160, 16)]
+INVERSE_G = (4, 100, 16384)
+ASSEMBLE_D = (8, 192, 1152)
+ASSEMBLE_BWD_B = (1, 3, 5, 9)
+TEXT_CASES = [(3, 1, 8, 40000), (2, 80, 8, 40000), (3, 80, 192, 1000), (2, 80, 1152, 300), (5, 1, 1152, 300)]     # (B, T, D, V)
+TEXT_LAP = (1093, 80, 192, 1000)                                                 # 87 440 rows x 24 chunks = 2 098 560 > LAP
+CONVERT_COLS = (1, 7, 193, 1024)
+CONVERT_LAP = (2049, 1024)                                                       # 2 098 176 elements > LAP
+DTYPE_PAIRS = [(torch.float32, torch.bfloat16), (torch.bfloat16, torch.float32), (torch.float32, torch.float32),
+               (torch.bfloat16, torch.bfloat16)]
+
+
+def image_case(B, S, dtype, seed=0):
+    """[B, 3, S, S]: Gaussian values over sixteen binades, so that (nearly) every pixel has its own value, in bf16 as far as its
+    4096 values of that range allow, and any permutation of pixels shows; the fp32 values are no bf16 values."""
+    g = torch.Generator().manual_seed(seed)
+    n = B * 3 * S * S
+    img = torch.randn(n, generator=g) * 2.0 ** torch.randint(-8, 8, (n,), generator=g)
+    return img.view(B, 3, S, S).to(dtype)
+
+
+def im2col_ref(img, P, Kpad):
+    """F.unfold's (c, ii, jj) columns per patch, patches row-major, rounded to bf16 once, zeros up to Kpad."""
+    B = img.shape[0]
+    cols = torch.nn.functional.unfold(img.float(), P, stride=P).transpose(1, 2).reshape(-1, 3 * P * P).to(torch.bfloat16)
+    out = torch.zeros(cols.shape[0], Kpad, dtype=torch.bfloat16)
+    out[:, :3 * P * P] = cols
+    return out
+
+
+def keep_table(B, G, K, seed=0):
+    """[B, K] int32: per image the first K of a random order of its G patches."""
+    g = torch.Generator().manual_seed(seed + 17 * G + K)
+    return torch.stack([torch.randperm(G, generator=g)[:K] for _ in range(B)]).to(torch.int32)
+
+
+def keep_ks(G):
+    return sorted({1, G // 2, G})
+
+
+def gather_keep(rows, keep, G):
+    """rows [B G, C] -> [B K, C]: image b's rows keep[b, :] in that order."""
+    B, K = keep.shape
+    idx = (torch.arange(B)[:, None] * G + keep.long()).reshape(-1)
+    return rows[idx]
+
+
+def inverse_ref(keep, G):
+    inv = [[-1] * G for _ in range(keep.shape[0])]
+    for b, row in enumerate(keep.tolist()):
+        for j, idx in enumerate(row):
+            inv[b][idx] = j
+    return torch.tensor(inv, dtype=torch.int32)
+
+
+def assemble_case(B, G, K, D, seed=0):
+    g = torch.Generator().manual_seed(seed + D)
+    return SimpleNamespace(B=B, G=G, K=K, D=D, y=torch.randn(B * K, D, generator=g).to(torch.bfloat16),
+                           cls=torch.randn(D, generator=g), pos=torch.randn(1 + G, D, generator=g), keep=keep_table(B, G, K, seed))
+
+
+def assemble_ref(c):
+    y = c.y.float().view(c.B, c.K, c.D)
+    return torch.cat([(c.cls + c.pos[0]).expand(c.B, 1, c.D), y + c.pos[1 + c.keep.long()]], dim=1)
+
+
+def assemble_bwd_case(B, G, K, D, seed=0):
+    """dx [B, 1 + K, D] fp32 over six decades of magnitude, so that the order of an fp32 sum over b shows in its bits."""
+    g = torch.Generator().manual_seed(seed + 31 * B + D)
+    dx = torch.randn(B, 1 + K, D, generator=g) * 10.0 ** (torch.rand(B, 1 + K, D, generator=g) * 6 - 3)
+    keep = keep_table(B, G, K, seed + B)
+    return SimpleNamespace(B=B, G=G, K=K, D=D, dx=dx, keep=keep, inv=inverse_ref(keep, G))
+
+
+def assemble_bwd_ref(c):
+    """dpos: zeros, then image 0, 1, ..., B - 1 added in that order, each to row 0 and to the rows 1 + keep[b, :]."""
+    dpos = torch.zeros(1 + c.G, c.D)
+    for b in range(c.B):
+        dpos[0] += c.dx[b, 0]
+        dpos[1 + c.keep[b].long()] += c.dx[b, 1:]
+    return dict(dpos=dpos, dcls=dpos[0].clone(), dy=c.dx[:, 1:].reshape(c.B * c.K, c.D).to(torch.bfloat16))
+
+
+def col2im_case(B, S, P, K, seed=0):
+    g = torch.Generator().manual_seed(seed + S + K)
+    G = (S // P) ** 2
+    keep = keep_table(B, G, K, seed)
+    dcols = torch.randn(B * K, 3 * P * P, generator=g).to(torch.bfloat16)
+    dcols[0, :5] = torch.tensor([-0.0, 0.0, 1e-40, -1e-40, 3e38]).to(torch.bfloat16)
+    return SimpleNamespace(B=B, S=S, P=P, K=K, G=G, keep=keep, inv=inverse_ref(keep, G), dcols=dcols)
+
+
+def col2im_ref(c, dtype):
+    """A pure gather: the kept rows scattered into [B, G, 3 P^2] zeros, then the axes (gy, gx, c, ii, jj) -> (c, gy, ii, gx, jj)."""
+    g = c.S // c.P
+    full = torch.zeros(c.B * c.G, 3 * c.P * c.P, dtype=torch.bfloat16)
+    full[(torch.arange(c.B)[:, None] * c.G + c.keep.long()).reshape(-1)] = c.dcols
+    return full.view(c.B, g, g, 3, c.P, c.P).permute(0, 3, 1, 4, 2, 5).reshape(c.B, 3, c.S, c.S).to(dtype)
+
+
+def text_case(B, T, D, V, seed=0, bad=False):
+    """tokens int64 [B, T] with 0 and V - 1 among them; bad: -1, V and 2^40 + 5 as well (three rows that must clamp)."""
+    g = torch.Generator().manual_seed(seed + V + D + T)
+    tok = torch.randint(0, V, (B * T,), generator=g)
+    tok[0], tok[-1] = V - 1, 0
+    if bad:
+        assert B * T >= 5
+        tok[1], tok[2], tok[3] = -1, V, 2 ** 40 + 5
+    return SimpleNamespace(B=B, T=T, D=D, V=V, tokens=tok.view(B, T), table=torch.randn(V, D, generator=g).to(torch.bfloat16),
+                           pos=torch.randn(T, D, generator=g).to(torch.bfloat16), bad=bad)
+
+
+def text_ref(c):
+    ids = c.tokens.clamp(0, c.V - 1).reshape(-1)
+    t = torch.arange(c.B * c.T) % c.T
+    return dict(x=(c.table[ids].float() + c.pos[t].float()).to(torch.bfloat16),
+                err=torch.tensor([int(bool(((c.tokens < 0) | (c.tokens >= c.V)).any()))], dtype=torch.int32))
+
+
+def convert_values(dtype):
+    """Every bf16 bit pattern (both zeros, the subnormals, both infinities, the NaNs); as fp32, each pattern exact, just below the
+    tie to the next one, on the tie, and just above it (low half 0, 0x7fff, 0x8000, 0x8001): 65 536 or 262 144 values."""
+    hi = torch.arange(65536, dtype=torch.int64)
+    if dtype == torch.bfloat16:
+        return hi.to(torch.int32).to(torch.int16).view(torch.bfloat16)
+    words = torch.cat([(hi << 16) | low for low in (0, 0x7FFF, 0x8000, 0x8001)])
+    return (words - ((words >> 31) << 32)).to(torch.int32).view(torch.float32)
+
+
+def convert_case(rows, cols, dtype):
+    """[rows, cols]: convert_values(dtype), repeated from its start to fill the shape."""
+    v = convert_values(dtype)
+    n = rows * cols
+    return v.repeat(-(-n // v.numel()))[:n].view(rows, cols)
+
+
+def convert_rows(cols, dtype):
+    return -(-convert_values(dtype).numel() // cols)
+
+
+# thin wrappers: caller-owned outputs, every pointer and pitch as the caller's tensors have them
+
+def im2col_patches(img, P, out):
+    lib = _lib.load()
+    B, _, S, _ = img.shape
+    check(lib.ov_im2col_patches(ptr(img), _flag(img), ptr(out), B, S, P, out.stride(0), stream_ptr()), "ov_im2col_patches")
+    return out
+
+
+def im2col_patches_keep(img, keep, P, out):
+    lib = _lib.load()
+    B, _, S, _ = img.shape
+    check(lib.ov_im2col_patches_keep(ptr(img), _flag(img), ptr(keep), ptr(out), B, S, P, keep.shape[1], out.stride(0), stream_ptr()),
+          "ov_im2col_patches_keep")
+    return out
+
+
+def patch_keep_inverse(keep, inv, G, err):
+    """-> the status (OV_OK, or OV_ERR_UNSUPPORTED above the LDS limit), unchecked."""
+    return _lib.load().ov_patch_keep_inverse(ptr(keep), ptr(inv), keep.shape[0], keep.shape[1], G, ptr(err), stream_ptr())
+
+
+def patch_keep_assemble(y, cls, pos, keep, x, G):
+    lib = _lib.load()
+    B, K = keep.shape
+    check(lib.ov_patch_keep_assemble(ptr(y), y.stride(0), ptr(cls), ptr(pos), ptr(keep), ptr(x), B, K, G, cls.numel(), stream_ptr()),
+          "ov_patch_keep_assemble")
+    return x
+
+
+def patch_keep_assemble_backward(dx, inv, K, dpos=None, dcls=None, dy=None):
+    lib = _lib.load()
+    B, _, D = dx.shape
+    check(lib.ov_patch_keep_assemble_backward(ptr(dx), ptr(inv), B, K, inv.shape[1], D, ptr(dpos), ptr(dcls), ptr(dy),
+                                              dy.stride(0) if dy is not None else 0, stream_ptr()), "ov_patch_keep_assemble_backward")
+
+
+def col2im_patches_keep(dcols, inv, dimg, P, K):
+    lib = _lib.load()
+    B, _, S, _ = dimg.shape
+    check(lib.ov_col2im_patches_keep(ptr(dcols), dcols.stride(0), ptr(inv), ptr(dimg), _flag(dimg), B, S, P, K, stream_ptr()),
+          "ov_col2im_patches_keep")
+    return dimg
+
+
+def text_embed(tokens, table, pos, x, err=None):
+    lib = _lib.load()
+    B, T = tokens.shape
+    check(lib.ov_text_embed(ptr(tokens), ptr(table), ptr(pos), ptr(x), x.stride(0), B, T, table.shape[1], table.shape[0], ptr(err),
+                            stream_ptr()), "ov_text_embed")
+    return x
+
+
+def convert(src, dst):
+    lib = _lib.load()
+    check(lib.ov_convert(ptr(src), _flag(src), src.stride(0), ptr(dst), _flag(dst), dst.stride(0), src.shape[0], src.shape[1],
+                         stream_ptr()), "ov_convert")
+    return dst

@@ -135,6 +135,35 @@ int ov_rowstats_finalize(const float* parts, float* rowstats, int64_t rows, int 
 int ov_gemm_rowparts(const ov_bf16* A, int64_t lda, const ov_bf16* W, int64_t ldw, const float* bias, ov_bf16* C, int64_t ldc,
                      int64_t M, int N, int K, const ov_bf16* R, int64_t ldr, float* parts, ov_stream_t stream);
 
+/* What ov_gemm / ov_gemm_ln / ov_gemm_keep / ov_gemm_rowparts launch for a shape: the launcher's own decision, reported without
+ * launching anything (tests and tools ask this instead of restating the rules). */
+enum ov_gemm_kernel {
+    OV_GEMM_SKINNY = 0,               /* 64 x 64 tiles, LDS ring: small shapes */
+    OV_GEMM_PLAIN = 1,                /* 256 x 256 tiles, one workgroup per tile */
+    OV_GEMM_PERSISTENT = 2            /* 256 x 256 tiles, one workgroup per CU walking the tiles */
+};
+typedef struct {
+    int kernel;                       /* enum ov_gemm_kernel */
+    /* the persistent kernel's instantiation (all 0 for the other two kernels) */
+    int fold;                         /* LN-folded weights (ov_gemm_ln) */
+    int direct;                       /* the register-exchange epilogue with row-per-lane stores; 0 = the LDS-transposed one */
+    int mapped;                       /* row maps (out_group / resid_mod) */
+    int keep;                         /* the pre-activation is kept (ov_gemm_keep), from the same launch */
+    int stats;                        /* the row statistics' partial sums are fused into the epilogue (ov_gemm_rowparts) */
+    /* walk and store policy: computed for every shape, MEANINGFUL FOR THE PERSISTENT KERNEL ONLY (the others never read them) */
+    int ngroup;                       /* n-tiles per group of the tile walk; == the number of 256-column n-tiles: plain n-fastest walk */
+    int rotmask;                      /* != 0: the rotated plain walk (half last n-tile), n index rotated under this mask */
+    int rev;                          /* row tiles from the last to the first */
+    int st_plain;                     /* bias / GELU outputs stored plainly; 0 = streaming stores */
+    /* further launches */
+    int keep_prepass;                 /* plain kernel + ov_gemm_keep: a bias-only launch writes the pre-activation first */
+    int rowparts_pass;                /* ov_gemm_rowparts: the kernel does not produce the partial sums, ov_rowparts follows */
+} ov_gemm_route_t;
+/* fold / keep / rowparts / row_maps != 0: the call is ov_gemm_ln / ov_gemm_keep / ov_gemm_rowparts / has out_group or resid_mod set.
+ * cus <= 0: the current device's CU count; > 0: used as given (no device needed).  The OVHIP_GEMM_* environment switches are those
+ * the process read at its first GEMM or route call.  OV_ERR_UNSUPPORTED: a combination or shape no entry point admits. */
+int ov_gemm_route(int64_t M, int N, int K, int epilogue, int fold, int keep, int rowparts, int row_maps, int cus, ov_gemm_route_t* route);
+
 /* Non-causal, unmasked multi-head self-attention on a packed qkv activation.
  * qkv: [B*L, 3*H*hd] bf16 (q | k | v column blocks, heads contiguous inside each, ld = ld_qkv);
  * out: [B*L, H*hd] bf16 (heads merged, ld = ld_out).  scale multiplies q.k (hd^-0.5).

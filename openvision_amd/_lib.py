@@ -43,6 +43,11 @@ class BlockFp8(C.Structure):
     _fields_ = [(n, c_void_p) for n in ("qkv_w8", "qkv_s", "qkv_b", "out_w8", "out_s", "fc_w8", "fc_s", "fc_b", "proj_w8", "proj_s")]
 
 
+class GemmRoute(C.Structure):        # ov_gemm_route_t: what the bf16 GEMM launcher decides for a shape (ov_gemm_route)
+    _fields_ = [(n, c_int) for n in ("kernel", "fold", "direct", "mapped", "keep", "stats", "ngroup", "rotmask", "rev", "st_plain",
+                                     "keep_prepass", "rowparts_pass")]
+
+
 class VisionHead(C.Structure):
     _fields_ = [("image_size", c_int), ("patch_size", c_int), ("kpad", c_int), ("pool_avg", c_int),
                 ("final_ln_after_pool", c_int), ("embed_dim", c_int), ("embed_pad", c_int),
@@ -85,6 +90,7 @@ SIGNATURES = {
     "ov_rowstats_finalize": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_float, c_void_p]),
     "ov_gemm_rowparts": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_void_p, c_int64,
                                  c_void_p, c_void_p]),
+    "ov_gemm_route": (c_int, [c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "ov_attention": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_float, c_void_p]),
     "ov_attention_prefix": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p]),
     "ov_attention_prefix_backward_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),

@@ -1298,76 +1298,106 @@ __global__ __launch_bounds__(256) void gemm_bf16_skinny(const GemmArgs g) {
 // at 108 / 144 (M = 2056), out_proj / c_proj win at 68 (M = 4112) and lose at 132 (M = 8224).
 constexpr int SKINNY_TILES = 96;
 
-int num_cus() { return ov_num_cus(); }
-
-thread_local const float* g_colsum = nullptr;      // set by ov_gemm_ln around its call into ov_gemm
-thread_local const float* g_rowstats = nullptr;
-thread_local ov_bf16* g_keep = nullptr;            // set by ov_gemm_keep around its call into ov_gemm
-thread_local int64_t g_ldkeep = 0;
-thread_local float* g_rowpart = nullptr;           // set by ov_gemm_rowparts around its call into ov_gemm
 unsigned long long* g_stamps = nullptr;
 unsigned long long* g_wstamps = nullptr;
 int g_stamp_slots = 0;
 
-int gemm_variant() {       // 0 = default (persistent ping-pong; skinny kernel for small M), 2 = non-persistent ping-pong for every shape,
-    static int v = -1;     // 4 = skinny kernel for EVERY shape (tests: bitwise against the default); any other value = 0
-    if (v < 0) {
-        const char* e = getenv("OVHIP_GEMM_VARIANT");
-        v = (e && (e[0] == '2' || e[0] == '4')) ? e[0] - '0' : 0;
-    }
-    return v;
+// The process's three switches, read once (the tests drive them from child processes).
+struct GemmSwitches {
+    int variant;           // OVHIP_GEMM_VARIANT: 2 = the plain, 4 = the skinny kernel for EVERY shape (tests: bitwise against the default); else 0
+    int64_t nt_min;        // OVHIP_GEMM_NT_MIN_MB (192), in bytes: persistent outputs of at least this size are streamed
+    int gelu_lds;          // OVHIP_GEMM_GELU_LDS=0|1 forces the LN-folded GELU's direct | LDS-transposed form; -1 (unset): by store policy
+};
+const GemmSwitches& gemm_switches() {
+    static const GemmSwitches s = [] {
+        const char *v = getenv("OVHIP_GEMM_VARIANT"), *nt = getenv("OVHIP_GEMM_NT_MIN_MB"), *gl = getenv("OVHIP_GEMM_GELU_LDS");
+        return GemmSwitches{(v && (v[0] == '2' || v[0] == '4')) ? v[0] - '0' : 0, (int64_t)(nt ? atoi(nt) : 192) << 20,
+                            gl ? (gl[0] == '1' ? 1 : 0) : -1};
+    }();
+    return s;
 }
 
-// n-tiles per group of the persistent walk: groups of 4 once W no longer fits an XCD's L2 next to the streaming A panels
-int gemm_ngroup(int tiles_m, int tiles_n, int K) {
-    const int64_t wbytes = (int64_t)tiles_n * BN * K * 2;
-    if (wbytes <= (3 << 20) || tiles_n <= 4 || tiles_n % 4 || tiles_m < 16) return tiles_n;
-    return 4;
-}
-
-// Per-launch policy of the persistent kernel: the rotated walk, store policy by output size, reverse row walk.
-template <int EPI>
-void persist_policy(GemmArgs& a, int grid_x) {
-    static const int64_t nt_min = [] { const char* e = getenv("OVHIP_GEMM_NT_MIN_MB"); return (int64_t)(e ? atoi(e) : 192) << 20; }();
-    // outputs of at least OVHIP_GEMM_NT_MIN_MB (192) MB are streamed, smaller ones stored plainly: their consumer finds them in the
-    // 256 MB Infinity Cache (gemm_bf16_persist, "Store policy")
-    a.st_plain = (int64_t)a.M * a.N * 2 < nt_min ? 1 : 0;
+// THE decision of what a bf16 GEMM launches, as a value: a pure function of the shape, the epilogue, which optional operands are
+// present (fold: colsum / rowstats, keep: C2, rowparts, mapped: out_group / resid_mod), the CU count and the switches.  launch<EPI>
+// carries it out, ov_gemm_route reports it.  The combination must be one the entry points admit.
+ov_gemm_route_t gemm_route(int64_t M, int N, int K, int epi, bool fold, bool keep, bool rowparts, bool mapped, int cus,
+                           const GemmSwitches& sw) {
+    ov_gemm_route_t r = {};
+    const int64_t tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN, nwg = tiles_m * tiles_n;
+    const bool gelu = epi == OV_EPI_BIAS_GELU_ERF || epi == OV_EPI_BIAS_GELU_TANH, resid = epi == OV_EPI_BIAS_RESIDUAL;
+    // ---- walk and stores (read by the persistent kernel only).  n-tiles per group: groups of 4 once W no longer fits an XCD's L2 next to
+    // the streaming A panels
+    const int64_t wbytes = tiles_n * BN * K * 2;
+    r.ngroup = (wbytes <= (3 << 20) || tiles_n <= 4 || tiles_n % 4 || tiles_m < 16) ? (int)tiles_n : 4;
+    // a half last n-tile under the plain walk with a workgroup stride that is a multiple of tiles_n: rotate (GemmArgs::rotmask)
+    const int rem = N % BN, nper = cus >> 3;
+    if (rem > 0 && rem <= 128 && r.ngroup >= tiles_n && tiles_n > 1 && (tiles_n & (tiles_n - 1)) == 0 && cus % 8 == 0 && nper % tiles_n == 0)
+        r.rotmask = (int)tiles_n - 1;
     // Row tiles from the last to the first for the residual GEMM that reads a wide hidden activation (c_proj: K >= 2 N): its
     // producer (c_fc) wrote the rows in ascending order, so the ones it wrote last are those the Infinity Cache still holds.
-    // S/8@384 (906 MB hidden per layer) 35.03 -> 34.80 ms per step, L/14 (537 MB) 44.78 -> 44.70: small, free, bitwise the same
-    // results.
-    a.rev = (EPI == OV_EPI_BIAS_RESIDUAL && a.K >= 2 * a.N && a.out_group == 0 && a.resid_mod == 0) ? 1 : 0;
-    // a half last n-tile under the plain walk with a workgroup stride that is a multiple of tiles_n: rotate (GemmArgs::rotmask)
-    const int rem = a.N % BN, nper = grid_x >> 3;
-    a.rotmask = 0;
-    if (rem > 0 && rem <= 128 && a.ngroup >= a.tiles_n && a.tiles_n > 1 && (a.tiles_n & (a.tiles_n - 1)) == 0 &&
-        grid_x % 8 == 0 && nper % a.tiles_n == 0)
-        a.rotmask = a.tiles_n - 1;
+    // S/8@384 (906 MB hidden per layer) 35.03 -> 34.80 ms per step, L/14 (537 MB) 44.78 -> 44.70: small, free, bitwise the same results.
+    r.rev = resid && K >= 2 * N && !mapped;
+    // outputs of at least OVHIP_GEMM_NT_MIN_MB (192) MB are streamed, smaller ones stored plainly: their consumer finds them in the
+    // 256 MB Infinity Cache (gemm_bf16_persist, "Store policy")
+    r.st_plain = M * N * 2 < sw.nt_min;
+    // ---- skinny: small M (or every shape under OVHIP_GEMM_VARIANT=4); never with a kept pre-activation.  (Writes rowparts itself.)
+    r.kernel = OV_GEMM_SKINNY;
+    if (!keep && (sw.variant == 4 || (sw.variant == 0 && nwg <= SKINNY_TILES))) return r;
+    // ---- plain (gemm_bf16_pp): fewer tiles than CUs (pooled heads, the tower's tail images), where persistence buys nothing; fewer
+    // than 3 K-tiles; row maps with an epilogue other than bias / residual (the only ones with a MAPPED persistent form)
+    if (sw.variant == 2 || nwg < cus || K < 3 * BK || (mapped && epi != OV_EPI_BIAS && !resid)) {
+        r.kernel = OV_GEMM_PLAIN;
+        r.keep_prepass = keep; r.rowparts_pass = rowparts;         // (keep: the pre-activation from a bias-only product, launched first)
+        return r;
+    }
+    // ---- persistent: one workgroup per CU.  The instantiation follows from the epilogue and the operands:
+    // FOLD = LN-folded weights (colsum), DIRECT = the v_permlane16_swap epilogue instead of the LDS-transposed one,
+    // MAPPED = row maps, KEEP = the kept pre-activation, STATS = fused row statistics.
+    r.kernel = OV_GEMM_PERSISTENT; r.fold = fold; r.mapped = mapped; r.keep = keep;
+    if (gelu) {
+        // GELU with the LN fold (vision / text c_fc).  Default: the LDS-transposed form when the output is streamed (whole
+        // 128-byte lines leave L2; the direct form's 16-byte streaming stores leave as partial lines: WRITE_SIZE 0.69 against
+        // 0.54 GB per L/14 launch) -- L/14 45.1 -> 44.9 ms, S/8 35.7 -> 35.4; the direct form for small, plainly stored outputs
+        // (Ti/16: 0.71 against 0.73 ms).  OVHIP_GEMM_GELU_LDS=0|1 forces.  Unfolded and KEEP: the direct form only.
+        r.direct = fold ? !(sw.gelu_lds >= 0 ? sw.gelu_lds : !r.st_plain) : 1;
+    } else if (resid) {
+        // row-statistic partial sums: fused into the direct residual epilogue.  Without them and without row maps: the LDS-transposed
+        // form (whole-line stores, 16 instead of ~70 TA cycles per store instruction) since the register diet of round 3 made it fit
+        // (246 VGPRs, zero scratch): out-proj 4.26 -> 4.10 ms per L/14 step, step -0.5 % (Ti/16 -1.8 %)
+        r.stats = rowparts && !mapped; r.direct = mapped || r.stats;
+    }
+    // (bias: LDS-transposed coalesced stores measure faster in the model than the direct form, 9.5-9.8 against 10.0-10.3 ms per step
+    // for the QKV GEMMs; GELU gradient: the LDS-transposed form is the only one)
+    // a kernel that did not fuse the statistics is followed by the stand-alone pass (the same arithmetic, common.h: bitwise the same sums)
+    r.rowparts_pass = rowparts && !r.stats;
+    return r;
+}
+
+enum { F_FOLD = 1, F_DIRECT = 2, F_MAPPED = 4, F_KEEP = 8, F_STATS = 16 };       // a persistent form = the route's flags as bits
+template <int EPI, int FORM>
+void persist(const GemmArgs& a, int cus, hipStream_t st) {
+    hipLaunchKernelGGL((gemm_bf16_persist<EPI, (FORM & F_FOLD) != 0, (FORM & F_DIRECT) != 0, (FORM & F_MAPPED) != 0, (FORM & F_KEEP) != 0,
+                                          (FORM & F_STATS) != 0>), dim3(cus), dim3(NTHREADS), 0, st, a);
+}
+// Launches the one of FORMS... that `form` names; false: none does.  FORMS = the instantiations the epilogue family has.
+template <int EPI, int... FORMS>
+bool persist_one_of(int form, const GemmArgs& a, int cus, hipStream_t st) {
+    return ((form == FORMS && (persist<EPI, FORMS>(a, cus, st), true)) || ...);
 }
 
 template <int EPI>
 int launch(GemmArgs a, hipStream_t st) {
-    const int var = gemm_variant();
-    const int nwg = a.tiles_m * a.tiles_n;
-    const bool mapped = a.out_group != 0 || a.resid_mod != 0;          // row maps: the patch embedding's GEMM only
-    // ---- skinny: small M (or every shape under OVHIP_GEMM_VARIANT=4); never with a kept pre-activation
-    if (a.C2 == nullptr && (var == 4 || (var == 0 && nwg <= SKINNY_TILES))) {
+    const int nwg = a.tiles_m * a.tiles_n, cus = ov_num_cus();
+    const ov_gemm_route_t r = gemm_route(a.M, a.N, a.K, EPI, a.colsum != nullptr, a.C2 != nullptr, a.rowpart != nullptr,
+                                         a.out_group != 0 || a.resid_mod != 0, cus, gemm_switches());     // (row maps: the patch embedding)
+    a.ngroup = r.ngroup; a.rotmask = r.rotmask; a.rev = r.rev; a.st_plain = r.st_plain;
+    if (r.kernel == OV_GEMM_SKINNY) {
         GemmArgs b = a;
-        b.tiles_m = (int)((a.M + SK_BM - 1) / SK_BM);
-        b.tiles_n = (a.N + SK_BN - 1) / SK_BN;
+        b.tiles_m = (int)((a.M + SK_BM - 1) / SK_BM); b.tiles_n = (a.N + SK_BN - 1) / SK_BN;
         if ((int64_t)b.tiles_m * b.tiles_n > 0x7fffffffLL) return OV_ERR_UNSUPPORTED;
-        hipLaunchKernelGGL(gemm_bf16_skinny<EPI>, dim3((unsigned)(b.tiles_m * b.tiles_n)), dim3(256), 0, st, b);     // (writes a.rowpart itself)
-        OV_LAUNCH_CHECK();
-        return OV_OK;
-    }
-    // row-statistic partial sums: fused into the persistent kernel's direct residual epilogue; every other kernel is followed by the
-    // stand-alone pass over its output (the same arithmetic, common.h: bitwise the same sums)
-    float* const rowpart = a.rowpart;
-    bool stats_fused = false;
-    // ---- plain (gemm_bf16_pp): fewer tiles than CUs (pooled heads, the tower's tail images), where persistence buys nothing; fewer
-    // than 3 K-tiles; row maps with an epilogue other than bias / residual (the only ones with a MAPPED persistent form)
-    if (var == 2 || nwg < num_cus() || a.K < 3 * BK || (mapped && EPI != OV_EPI_BIAS && EPI != OV_EPI_BIAS_RESIDUAL)) {
-        if (a.C2 != nullptr) {
+        hipLaunchKernelGGL(gemm_bf16_skinny<EPI>, dim3((unsigned)(b.tiles_m * b.tiles_n)), dim3(256), 0, st, b);
+    } else if (r.kernel == OV_GEMM_PLAIN) {
+        if (r.keep_prepass) {
             // the pre-activation from a second, bias-only product -- the same fp32 accumulators and the same rounding as the fused form
             GemmArgs b = a;
             b.C = a.C2; b.ldc = a.ldc2; b.C2 = nullptr;
@@ -1377,86 +1407,44 @@ int launch(GemmArgs a, hipStream_t st) {
         }
         hipLaunchKernelGGL(gemm_bf16_pp<EPI>, dim3(nwg), dim3(NTHREADS), 0, st, a);
     } else {
-        // ---- persistent: one workgroup per CU.  The instantiation follows from the epilogue and the operands:
-        // FOLD = LN-folded weights (colsum), DIRECT = the v_permlane16_swap epilogue instead of the LDS-transposed one,
-        // MAPPED = row maps, KEEP = the kept pre-activation, STATS = fused row statistics.
-        const dim3 grid(num_cus()), blk(NTHREADS);
-        persist_policy<EPI>(a, (int)grid.x);
-        if constexpr (EPI == OV_EPI_BIAS) {
-            // LDS-transposed coalesced stores measure faster in the model than the direct form (9.5-9.8 against 10.0-10.3 ms per step
-            // for the QKV GEMMs)
-            if (a.colsum != nullptr)            // LN fold: never with row maps
-                hipLaunchKernelGGL((gemm_bf16_persist<OV_EPI_BIAS, true, false, false>), grid, blk, 0, st, a);
-            else if (mapped)
-                hipLaunchKernelGGL((gemm_bf16_persist<OV_EPI_BIAS, false, false, true>), grid, blk, 0, st, a);
-            else
-                hipLaunchKernelGGL((gemm_bf16_persist<OV_EPI_BIAS, false, false, false>), grid, blk, 0, st, a);
-        } else if constexpr (EPI == OV_EPI_BIAS_GELU_ERF || EPI == OV_EPI_BIAS_GELU_TANH) {
-            if (a.C2 != nullptr) {              // ov_gemm_keep (unfolded weights: checked by the caller)
-                hipLaunchKernelGGL((gemm_bf16_persist<EPI, false, true, false, true>), grid, blk, 0, st, a);
-            } else if (a.colsum != nullptr) {
-                // GELU with the LN fold (vision / text c_fc).  Default: the LDS-transposed form when the output is streamed (whole
-                // 128-byte lines leave L2; the direct form's 16-byte streaming stores leave as partial lines: WRITE_SIZE 0.69 against
-                // 0.54 GB per L/14 launch) -- L/14 45.1 -> 44.9 ms, S/8 35.7 -> 35.4; the direct form for small, plainly stored outputs
-                // (Ti/16: 0.71 against 0.73 ms).  OVHIP_GEMM_GELU_LDS=0|1 forces.
-                static int gelu_env = -2;
-                if (gelu_env == -2) { const char* e = getenv("OVHIP_GEMM_GELU_LDS"); gelu_env = e ? (e[0] == '1' ? 1 : 0) : -1; }
-                const int gelu_lds = gelu_env >= 0 ? gelu_env : (a.st_plain ? 0 : 1);
-                if (gelu_lds) hipLaunchKernelGGL((gemm_bf16_persist<EPI, true, false, false>), grid, blk, 0, st, a);
-                else hipLaunchKernelGGL((gemm_bf16_persist<EPI, true, true, false>), grid, blk, 0, st, a);
-            } else {
-                hipLaunchKernelGGL((gemm_bf16_persist<EPI, false, true, false>), grid, blk, 0, st, a);
-            }
-        } else if constexpr (EPI == OV_EPI_BIAS_RESIDUAL) {
-            if (mapped) {
-                hipLaunchKernelGGL((gemm_bf16_persist<OV_EPI_BIAS_RESIDUAL, false, true, true>), grid, blk, 0, st, a);
-            } else if (rowpart != nullptr) {
-                hipLaunchKernelGGL((gemm_bf16_persist<OV_EPI_BIAS_RESIDUAL, false, true, false, false, true>), grid, blk, 0, st, a);
-                stats_fused = true;
-            } else {
-                // the LDS-transposed form (whole-line stores, 16 instead of ~70 TA cycles per store instruction) since the register diet
-                // of round 3 made it fit (246 VGPRs, zero scratch): out-proj 4.26 -> 4.10 ms per L/14 step, step -0.5 % (Ti/16 -1.8 %)
-                hipLaunchKernelGGL((gemm_bf16_persist<OV_EPI_BIAS_RESIDUAL, false, false, false>), grid, blk, 0, st, a);
-            }
-        } else {                                // GELU gradient: ov_gemm admits no fold, row maps, kept pre-activation or statistics
-            hipLaunchKernelGGL((gemm_bf16_persist<EPI, false, false, false>), grid, blk, 0, st, a);
-        }
+        // ---- persistent: the instantiations each epilogue family has (GELU gradient: no fold, row maps, kept pre-activation or statistics)
+        const int form = r.fold * F_FOLD | r.direct * F_DIRECT | r.mapped * F_MAPPED | r.keep * F_KEEP | r.stats * F_STATS;
+        bool found;
+        if constexpr (EPI == OV_EPI_BIAS)
+            found = persist_one_of<EPI, 0, F_MAPPED, F_FOLD>(form, a, cus, st);
+        else if constexpr (EPI == OV_EPI_BIAS_GELU_ERF || EPI == OV_EPI_BIAS_GELU_TANH)
+            found = persist_one_of<EPI, F_DIRECT, F_FOLD | F_DIRECT, F_FOLD, F_DIRECT | F_KEEP>(form, a, cus, st);
+        else if constexpr (EPI == OV_EPI_BIAS_RESIDUAL)
+            found = persist_one_of<EPI, 0, F_DIRECT | F_STATS, F_DIRECT | F_MAPPED>(form, a, cus, st);
+        else
+            found = persist_one_of<EPI, 0>(form, a, cus, st);
+        if (!found) return OV_ERR_UNSUPPORTED;          // (a combination no entry point admits)
     }
     OV_LAUNCH_CHECK();
-    if (rowpart != nullptr && !stats_fused) return ov_rowparts(a.C, a.ldc, rowpart, a.M, a.N, (ov_stream_t)st);
-    return OV_OK;
+    return r.rowparts_pass ? ov_rowparts(a.C, a.ldc, a.rowpart, a.M, a.N, (ov_stream_t)st) : OV_OK;
 }
 
-}  // namespace
-
-extern "C" int ov_gemm(const ov_bf16* A, int64_t lda, const ov_bf16* W, int64_t ldw, const float* bias,
-                       ov_bf16* C, int64_t ldc, int64_t M, int N, int K, int epilogue,
-                       const ov_bf16* R, int64_t ldr, int out_group, int resid_mod, int resid_off,
-                       ov_stream_t stream) {
+// The one way into the kernels, for ov_gemm and its siblings: `a` arrives with the optional operands (colsum / rowstats, C2 / ldc2,
+// rowpart) its entry point owns and has checked; here the common operands are checked and filled in, launch<EPI> decides the route.
+int gemm_run(GemmArgs& a, const ov_bf16* A, int64_t lda, const ov_bf16* W, int64_t ldw, const float* bias, ov_bf16* C, int64_t ldc,
+             int64_t M, int N, int K, int epilogue, const ov_bf16* R, int64_t ldr, int out_group, int resid_mod, int resid_off,
+             ov_stream_t stream) {
     if (!A || !W || !C || M <= 0 || N <= 0 || K <= 0) return OV_ERR_INVALID;
     if (K % BK || N % 8 || lda % 8 || ldw % 8 || ldc % 8) return OV_ERR_UNSUPPORTED;
     if (lda < K || ldw < K || ldc < N) return OV_ERR_INVALID;
     if (((uintptr_t)A | (uintptr_t)W | (uintptr_t)C) & 15) return OV_ERR_INVALID;
     if (bias && ((uintptr_t)bias & 15)) return OV_ERR_INVALID;
-    if (epilogue >= OV_EPI_BIAS_RESIDUAL) {
-        if (!R || ldr % 8 || ldr < N || ((uintptr_t)R & 15)) return OV_ERR_INVALID;
-    }
+    if (epilogue >= OV_EPI_BIAS_RESIDUAL && (!R || ldr % 8 || ldr < N || ((uintptr_t)R & 15))) return OV_ERR_INVALID;
     if (epilogue > OV_EPI_BIAS_RESIDUAL && (out_group || resid_mod)) return OV_ERR_UNSUPPORTED;      // row maps: bias / residual only
     if (out_group < 0 || resid_mod < 0 || resid_off < 0) return OV_ERR_INVALID;
-    if (g_rowpart != nullptr && (epilogue != OV_EPI_BIAS_RESIDUAL || out_group || resid_mod || N % 32)) return OV_ERR_UNSUPPORTED;
-    const int64_t tiles_m = (M + BM - 1) / BM;
-    const int64_t tiles_n = (N + BN - 1) / BN;
+    if (a.rowpart != nullptr && (epilogue != OV_EPI_BIAS_RESIDUAL || out_group || resid_mod || N % 32)) return OV_ERR_UNSUPPORTED;
+    const int64_t tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
     if (tiles_m * tiles_n > 0x7fffffffLL || M > 0x7fff0000LL) return OV_ERR_UNSUPPORTED;    // 32-bit row indices in the kernels
-    GemmArgs a;
     a.A = A; a.W = W; a.bias = bias; a.C = C; a.R = R;
     a.lda = lda; a.ldw = ldw; a.ldc = ldc; a.ldr = ldr; a.M = M; a.N = N; a.K = K;
     a.tiles_m = (int)tiles_m; a.tiles_n = (int)tiles_n;
     a.out_group = out_group; a.resid_mod = resid_mod; a.resid_off = resid_off;
-    a.colsum = g_colsum; a.rowstats = g_rowstats;
     a.stamps = g_stamps; a.stamp_slots = g_stamp_slots; a.wstamps = g_wstamps;
-    a.ngroup = gemm_ngroup((int)tiles_m, (int)tiles_n, K);
-    a.C2 = g_keep; a.ldc2 = g_ldkeep;
-    a.rowpart = g_rowpart;
     hipStream_t st = (hipStream_t)stream;
     switch (epilogue) {
         case OV_EPI_BIAS: return launch<OV_EPI_BIAS>(a, st);
@@ -1469,16 +1457,32 @@ extern "C" int ov_gemm(const ov_bf16* A, int64_t lda, const ov_bf16* W, int64_t 
     }
 }
 
+}  // namespace
+
+extern "C" int ov_gemm(const ov_bf16* A, int64_t lda, const ov_bf16* W, int64_t ldw, const float* bias, ov_bf16* C, int64_t ldc,
+                       int64_t M, int N, int K, int epilogue, const ov_bf16* R, int64_t ldr, int out_group, int resid_mod, int resid_off,
+                       ov_stream_t stream) {
+    GemmArgs a;
+    return gemm_run(a, A, lda, W, ldw, bias, C, ldc, M, N, K, epilogue, R, ldr, out_group, resid_mod, resid_off, stream);
+}
+
+extern "C" int ov_gemm_ln(const ov_bf16* X, int64_t ldx, const ov_bf16* Wg, int64_t ldw, const float* cvec, const float* colsum,
+                          const float* rowstats, ov_bf16* C, int64_t ldc, int64_t M, int N, int K, int epilogue, ov_stream_t stream) {
+    if (!colsum || !rowstats || !cvec) return OV_ERR_INVALID;
+    if (epilogue >= OV_EPI_BIAS_RESIDUAL) return OV_ERR_UNSUPPORTED;
+    if ((((uintptr_t)colsum | (uintptr_t)cvec) & 15) || ((uintptr_t)rowstats & 7)) return OV_ERR_INVALID;
+    GemmArgs a; a.colsum = colsum; a.rowstats = rowstats;
+    return gemm_run(a, X, ldx, Wg, ldw, cvec, C, ldc, M, N, K, epilogue, nullptr, 0, 0, 0, 0, stream);
+}
+
 // ov_gemm with a GELU epilogue that also keeps the pre-activation: C = gelu(A W^T + bias), C2 = bf16(A W^T + bias) -- the training
 // forward's c_fc, so that the backward does not run this product a second time.
 extern "C" int ov_gemm_keep(const ov_bf16* A, int64_t lda, const ov_bf16* W, int64_t ldw, const float* bias, ov_bf16* C, int64_t ldc,
                             ov_bf16* C2, int64_t ldc2, int64_t M, int N, int K, int epilogue, ov_stream_t stream) {
     if (epilogue != OV_EPI_BIAS_GELU_ERF && epilogue != OV_EPI_BIAS_GELU_TANH) return OV_ERR_INVALID;
     if (!C2 || ldc2 % 8 || ldc2 < N || ((uintptr_t)C2 & 15)) return OV_ERR_INVALID;
-    g_keep = C2; g_ldkeep = ldc2;
-    const int rc = ov_gemm(A, lda, W, ldw, bias, C, ldc, M, N, K, epilogue, nullptr, 0, 0, 0, 0, stream);
-    g_keep = nullptr; g_ldkeep = 0;
-    return rc;
+    GemmArgs a; a.C2 = C2; a.ldc2 = ldc2;
+    return gemm_run(a, A, lda, W, ldw, bias, C, ldc, M, N, K, epilogue, nullptr, 0, 0, 0, 0, stream);
 }
 
 // ov_gemm with the residual epilogue that also leaves the row statistics' partial sums of its OUTPUT: rowparts[m][N / 32] = {sum, sum
@@ -1487,10 +1491,20 @@ extern "C" int ov_gemm_keep(const ov_bf16* A, int64_t lda, const ov_bf16* W, int
 extern "C" int ov_gemm_rowparts(const ov_bf16* A, int64_t lda, const ov_bf16* W, int64_t ldw, const float* bias, ov_bf16* C, int64_t ldc,
                                 int64_t M, int N, int K, const ov_bf16* R, int64_t ldr, float* rowparts, ov_stream_t stream) {
     if (!rowparts || ((uintptr_t)rowparts & 7)) return OV_ERR_INVALID;
-    g_rowpart = rowparts;
-    const int rc = ov_gemm(A, lda, W, ldw, bias, C, ldc, M, N, K, OV_EPI_BIAS_RESIDUAL, R, ldr, 0, 0, 0, stream);
-    g_rowpart = nullptr;
-    return rc;
+    GemmArgs a; a.rowpart = rowparts;
+    return gemm_run(a, A, lda, W, ldw, bias, C, ldc, M, N, K, OV_EPI_BIAS_RESIDUAL, R, ldr, 0, 0, 0, stream);
+}
+
+// What the four entry points above would launch (ovhip.h); launches nothing.  cus <= 0: the current device's CU count.
+extern "C" int ov_gemm_route(int64_t M, int N, int K, int epilogue, int fold, int keep, int rowparts, int row_maps, int cus,
+                             ov_gemm_route_t* route) {
+    if (!route || M <= 0 || N <= 0 || K <= 0 || epilogue < OV_EPI_BIAS || epilogue > OV_EPI_GELU_GRAD_TANH) return OV_ERR_INVALID;
+    const bool gelu = epilogue == OV_EPI_BIAS_GELU_ERF || epilogue == OV_EPI_BIAS_GELU_TANH;
+    if (K % BK || N % 8 || (fold && (epilogue >= OV_EPI_BIAS_RESIDUAL || keep || row_maps)) || (keep && (!gelu || row_maps)) ||
+        (row_maps && epilogue > OV_EPI_BIAS_RESIDUAL) || (rowparts && (epilogue != OV_EPI_BIAS_RESIDUAL || row_maps || N % 32)))
+        return OV_ERR_UNSUPPORTED;             // no entry point admits the combination
+    *route = gemm_route(M, N, K, epilogue, fold != 0, keep != 0, rowparts != 0, row_maps != 0, cus > 0 ? cus : ov_num_cus(), gemm_switches());
+    return OV_OK;
 }
 
 // `batch` independent products C_z = A_z . W_z^T (bf16 out, no bias) in ONE launch of the non-persistent kernel, blockIdx.y = z.
@@ -1550,18 +1564,4 @@ extern "C" int ov_debug_gemm_stamps(unsigned long long* buf, int slots) {
 extern "C" int ov_debug_gemm_wave_stamps(unsigned long long* wbuf) {
     g_wstamps = wbuf;
     return OV_OK;
-}
-
-extern "C" int ov_gemm_ln(const ov_bf16* X, int64_t ldx, const ov_bf16* Wg, int64_t ldw, const float* cvec, const float* colsum,
-                          const float* rowstats, ov_bf16* C, int64_t ldc, int64_t M, int N, int K, int epilogue,
-                          ov_stream_t stream) {
-    if (!colsum || !rowstats || !cvec) return OV_ERR_INVALID;
-    if (epilogue >= OV_EPI_BIAS_RESIDUAL) return OV_ERR_UNSUPPORTED;
-    if ((((uintptr_t)colsum | (uintptr_t)cvec) & 15) || ((uintptr_t)rowstats & 7)) return OV_ERR_INVALID;
-    g_colsum = colsum;
-    g_rowstats = rowstats;
-    const int rc = ov_gemm(X, ldx, Wg, ldw, cvec, C, ldc, M, N, K, epilogue, nullptr, 0, 0, 0, 0, stream);
-    g_colsum = nullptr;
-    g_rowstats = nullptr;
-    return rc;
 }

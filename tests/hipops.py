@@ -774,30 +774,26 @@ def gelu_all_values_case():
 
 DEV = "cuda:0"
 BM = BN = 256
-BK = 64
-SKINNY_TILES = 96
 SENT = 77.0
 E_TANH = 1.1e-6
 CHUNK = 4096                      # rows per fp64 chunk: 4096 x 4096 x 8 B = 128 MB for the widest N of the routes test
 
 
-def route(M, N, K, epi=0, keep=False, nt_min_mb=192):
-    """What gemm.hip's launcher selects for this shape on this device (launch<EPI>, gemm_ngroup, persist_policy)."""
-    cus = torch.cuda.get_device_properties(0).multi_processor_count
+KERNELS = ("skinny", "plain", "persistent")            # enum ov_gemm_kernel
+
+
+def route(M, N, K, epi=0, keep=False, fold=False, rowparts=False, mapped=False, cus=0):
+    """What gemm.hip's launcher decides for this call, from the library itself (ov_gemm_route; cus = 0: this device's CU count, under
+    the OVHIP_GEMM_* switches of THIS process), beside the shape arithmetic of the case: tm x tn = nwg tiles, rem columns in the last
+    n-tile, pr = tm mod 8, W's bytes.  The instantiation flags and extra launches ride along under the names of ov_gemm_route_t."""
+    r = _lib.GemmRoute()
+    check(_lib.load().ov_gemm_route(M, N, K, epi, int(fold), int(keep), int(rowparts), int(mapped), cus, C.addressof(r)), "ov_gemm_route")
+    cus = cus or torch.cuda.get_device_properties(0).multi_processor_count
     tm, tn = -(-M // BM), -(-N // BN)
-    nwg = tm * tn
-    if not keep and nwg <= SKINNY_TILES:
-        kernel = "skinny"
-    elif nwg < cus or K < 3 * BK:
-        kernel = "plain"
-    else:
-        kernel = "persistent"
-    wbytes = tn * BN * K * 2
-    ngroup = tn if (wbytes <= (3 << 20) or tn <= 4 or tn % 4 or tm < 16) else 4
-    rem, nper = N % BN, cus >> 3
-    rot = tn - 1 if (0 < rem <= 128 and ngroup >= tn and tn > 1 and tn & (tn - 1) == 0 and cus % 8 == 0 and nper % tn == 0) else 0
-    return SimpleNamespace(cus=cus, tm=tm, tn=tn, nwg=nwg, kernel=kernel, grouped=ngroup < tn, groups=tn // ngroup, rot=rot, rem=rem,
-                           pr=tm & 7, rev=epi == 3 and K >= 2 * N, st_plain=M * N * 2 < (nt_min_mb << 20), wbytes=wbytes)
+    return SimpleNamespace(cus=cus, tm=tm, tn=tn, nwg=tm * tn, rem=N % BN, pr=tm & 7, wbytes=tn * BN * K * 2,
+                           kernel=KERNELS[r.kernel], grouped=r.ngroup < tn, groups=tn // r.ngroup, rot=r.rotmask, rev=bool(r.rev),
+                           st_plain=bool(r.st_plain), **{n: bool(getattr(r, n)) for n in ("fold", "direct", "mapped", "keep", "stats",
+                                                                                           "keep_prepass", "rowparts_pass")})
 
 
 def gelu64(x, tanh):

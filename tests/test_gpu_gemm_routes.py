@@ -2,7 +2,7 @@
 
 The other GEMM tests compare sibling launches bit for bit (persistent against plain, ov_gemm_keep against two ov_gemm calls), which
 is blind to anything both get wrong alike: a tile the walk skips or visits twice, a store form that drops columns.  Here every
-form the launcher selects by size (gemm.hip: launch<EPI>, persist_policy, gemm_ngroup) is compared with
+form the launcher selects by size (gemm.hip: gemm_route) is compared with
 A.double() @ W.double().T (+ bias) (+ R) computed by torch ON THE DEVICE (rocBLAS fp64: the fp64-on-device route of the two the
 plan allowed), in row chunks so that no fp64 temporary exceeds 1 GB.
 
@@ -37,13 +37,15 @@ Bound per element, derived, not tuned (REL = 2^-8 = hipops.REL: one bf16 roundin
 The helpers (route, linear_ratios, report, ...) live in hipops.py, shared with test_gpu_gemm_small_routes.py.
 
 Every output starts as the bf16 sentinel 77, so a skipped tile fails the bound instead of passing as zeros, and padding behind the
-last valid column must still hold it.  Every case asserts, from a restatement of the launcher's rules and the device's CU count,
-that the form it names is the one selected."""
+last valid column must still hold it.  Every case asserts, on what the library itself reports for the call (ov_gemm_route through
+hipops.route: the launcher's own decision for this device's CU count), that the form it names is the one selected; what the launcher
+decides at each rule's edge is pinned without a GPU by test_gemm_route_cpu.py."""
 import functools
 import os
 import subprocess
 import sys
 import tempfile
+from types import SimpleNamespace
 
 import pytest
 import torch
@@ -75,16 +77,21 @@ CASES = {
 }
 
 
-def selected(case, epi=0, keep=False, nt_min_mb=192, rev=False):
-    """Asserts that `case` reaches the kernel form it is in the table for; returns its shape."""
+def check_route(case, r, rev=False):
+    """Asserts that `r`, what the library reports for a call at `case`'s shape, is the kernel form the case is in the table for."""
     (M, N, K), walk, extra = CASES[case]
-    r = route(M, N, K, epi, keep, nt_min_mb)
     assert r.kernel == "persistent", f"case {case} {(M, N, K)}: {r.nwg} tiles on {r.cus} CUs, K = {K} selects the {r.kernel} kernel"
     got = "grouped" if r.grouped else "rotated" if r.rot else "plain"
     assert got == walk, f"case {case} {(M, N, K)}: the launcher selects the {got} walk, the case is there for the {walk} walk"
     for what, holds in extra:
         assert holds(r), f"case {case} {(M, N, K)} on {r.cus} CUs no longer has: {what}"
-    assert r.rev == rev, f"case {case} {(M, N, K)} epilogue {epi}: descending row walk {r.rev}, wanted {rev}"
+    assert r.rev == rev, f"case {case} {(M, N, K)}: descending row walk {r.rev}, wanted {rev}"
+
+
+def selected(case, epi=0, keep=False, rev=False, **operands):
+    """Asserts that `case` reaches the kernel form it is in the table for; returns its shape.  operands: fold= / rowparts= of the call."""
+    M, N, K = CASES[case][0]
+    check_route(case, route(M, N, K, epi, keep, **operands), rev)
     return M, N, K
 
 
@@ -169,7 +176,7 @@ def test_grouped_walk_keep_both_outputs(case):
 @pytest.mark.parametrize("epi", [0, 1])
 @pytest.mark.parametrize("case", [4, 6])
 def test_grouped_walk_ln_fold(case, epi):
-    M, N, K = selected(case, epi)
+    M, N, K = selected(case, epi, fold=True)
     x, wg, cvec, colsum = fold_operands(M, N, K)[:4]
     st = H.rowstats(x)
     out = H.gemm_ln(x, wg, cvec, colsum, st, epi=epi, out=sentinel(M, N + 8))
@@ -189,7 +196,7 @@ def test_walk_rowparts(case):
         a2, w2, b2 = operands(M2, N2, K2)
         with pytest.raises(H._lib.OvhipError):
             H.gemm_rowparts(a2, w2, b2, residual(M2, N2), parts=torch.empty(M2, N2 // 32, 2, device=DEV))
-    M, N, K = selected(case, 3, rev=case == 8)
+    M, N, K = selected(case, 3, rev=case == 8, rowparts=True)
     a, w, bias = operands(M, N, K)
     r = residual(M, N)
     out = r.clone()
@@ -231,11 +238,18 @@ SETTINGS = {
 }
 
 
+ROUTE_CALLS = {"bias": dict(epi=0), "gelu erf": dict(epi=1), "gelu tanh": dict(epi=2), "keep gelu erf": dict(epi=1, keep=True),
+               "fold bias": dict(epi=0, fold=True), "fold gelu erf": dict(epi=1, fold=True), "fold gelu tanh": dict(epi=2, fold=True)}
+
+
 def child_main(path, which):
-    """(In the child process.)  Every entry point over CHILD_CASES, outputs to `path`; which = foldgelu: the LN-folded GELUs only."""
-    outs = {}
+    """(In the child process.)  Every entry point over CHILD_CASES, outputs to `path`; which = foldgelu: the LN-folded GELUs only.
+    Beside them what the library reports, under this process's switches, for every call of ROUTE_CALLS."""
+    outs, routes = {}, {}
     for case in CHILD_CASES:
         M, N, K = CASES[case][0]
+        for name, call in ROUTE_CALLS.items():
+            routes[case, name] = vars(route(M, N, K, **call))
         if which == "all":
             a, w, bias = operands(M, N, K)
             for name, epi in (("bias", 0), ("gelu erf", 1), ("gelu tanh", 2)):
@@ -247,12 +261,12 @@ def child_main(path, which):
         for name, epi in FOLD_FORMS.items():
             if which == "all" or epi:
                 outs[case, name] = H.gemm_ln(x, wg, cvec, colsum, st, epi=epi, out=sentinel(M, N)).cpu()
-    torch.save(outs, path)
+    torch.save({"outs": outs, "routes": routes}, path)
 
 
 @functools.lru_cache(maxsize=None)
 def child_outputs(setting):
-    """Runs the child of `setting` (once per session, one child at a time) and returns what it saved."""
+    """Runs the child of `setting` (once per session, one child at a time) and returns what it saved: (outputs, routes)."""
     env_add, which = SETTINGS[setting]
     tests = os.path.dirname(os.path.abspath(__file__))
     env = {k: v for k, v in os.environ.items() if k not in ("OVHIP_GEMM_NT_MIN_MB", "OVHIP_GEMM_GELU_LDS")}
@@ -262,22 +276,30 @@ def child_outputs(setting):
     with tempfile.TemporaryDirectory() as d:
         path = os.path.join(d, "outs.pt")
         subprocess.run([sys.executable, "-c", code, path, which], check=True, env=env, timeout=300)
-        return torch.load(path)
+        saved = torch.load(path)
+        return saved["outs"], saved["routes"]
 
 
 @pytest.mark.parametrize("setting", list(SETTINGS))
 def test_store_policy_outputs_within_the_fp64_bound(setting):
     """Every output of the child under `setting` -- plain stores (default), every bias / GELU output streamed
     (OVHIP_GEMM_NT_MIN_MB=0; the folded GELU then in its LDS-transposed form: the production combination), the LDS form with plain
-    stores (OVHIP_GEMM_GELU_LDS=1), the direct form streamed (GELU_LDS=0, NT_MIN_MB=0) -- within its bound."""
+    stores (OVHIP_GEMM_GELU_LDS=1), the direct form streamed (GELU_LDS=0, NT_MIN_MB=0) -- within its bound.  First, on what the
+    library reported IN THE CHILD for each of its calls: the case's kernel form, the store policy of the setting, and the folded
+    GELU's form -- LDS-transposed under GELU_LDS=1, direct under =0, and without the switch direct exactly when stored plainly."""
     env_add, which = SETTINGS[setting]
     nt = int(env_add.get("OVHIP_GEMM_NT_MIN_MB", 192))
-    outs = child_outputs(setting)
+    outs, routes = child_outputs(setting)
+    gelu_lds = env_add.get("OVHIP_GEMM_GELU_LDS")
     for case in CHILD_CASES:
-        for epi in (0, 1, 2):
-            M, N, K = selected(case, epi, nt_min_mb=nt)
-        assert route(M, N, K, nt_min_mb=nt).st_plain == (nt != 0), (case, nt)
-        selected(case, 1, keep=True, nt_min_mb=nt)
+        M, N, K = CASES[case][0]
+        for name in ROUTE_CALLS:
+            r = SimpleNamespace(**routes[case, name])
+            check_route(case, r)
+            assert r.st_plain == (nt != 0), (case, name, nt)
+            assert (r.fold, r.keep) == (name.startswith("fold"), name.startswith("keep")), (case, name)
+            if name in ("fold gelu erf", "fold gelu tanh"):
+                assert r.direct == (gelu_lds == "0" if gelu_lds is not None else r.st_plain), (case, name, setting, r.direct)
         dev = {name: t.to(DEV) for (c, name), t in outs.items() if c == case}
         assert set(dev) == (set(LINEAR_FORMS) | set(FOLD_FORMS) if which == "all" else {"fold gelu erf", "fold gelu tanh"})
         tag = f"[{setting}] case {case} {(M, N, K)}"
@@ -297,14 +319,14 @@ def _bitwise(x, y, names):
 def test_streamed_stores_are_bitwise_the_plain_stores():
     """OVHIP_GEMM_NT_MIN_MB=0 changes only the store instruction of the forms whose instantiation it leaves alone: bias, unfolded GELU,
     KEEP (both outputs, padding included) and fold + bias equal the default process's outputs bit for bit."""
-    _bitwise(child_outputs("default"), child_outputs("streamed"), list(LINEAR_FORMS) + ["fold bias"])
+    _bitwise(child_outputs("default")[0], child_outputs("streamed")[0], list(LINEAR_FORMS) + ["fold bias"])
 
 
 def test_lds_gelu_form_plain_stores_bitwise_the_streamed():
     """OVHIP_GEMM_GELU_LDS=1 under the default threshold (LDS form, plain stores) against NT_MIN_MB=0 (LDS form by default, streamed)."""
-    _bitwise(child_outputs("lds form, plain stores"), child_outputs("streamed"), ["fold gelu erf", "fold gelu tanh"])
+    _bitwise(child_outputs("lds form, plain stores")[0], child_outputs("streamed")[0], ["fold gelu erf", "fold gelu tanh"])
 
 
 def test_direct_gelu_form_streamed_bitwise_the_default():
     """OVHIP_GEMM_GELU_LDS=0 with NT_MIN_MB=0 (direct form, streamed) against the default process (direct form, plain stores)."""
-    _bitwise(child_outputs("direct form, streamed"), child_outputs("default"), ["fold gelu erf", "fold gelu tanh"])
+    _bitwise(child_outputs("direct form, streamed")[0], child_outputs("default")[0], ["fold gelu erf", "fold gelu tanh"])

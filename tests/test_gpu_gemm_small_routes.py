@@ -9,7 +9,8 @@ epilogues; hipops.fold_bound for the LN fold, in every kernel), at the shapes wh
 prefetch depth, the ring's length, its first slot reuse and two laps; ragged last row and column tiles down to one row and one
 8-column quad; tile counts that leave the XCD map's runs unequal.
 
-Every case first asserts, from hipops.route and the device's CU count, that the kernel it names is the one selected.  Outputs start
+Every case first asserts, on what the library itself reports for the call (hipops.route: ov_gemm_route, the launcher's own decision
+on this device), that the kernel it names is the one selected.  Outputs start
 as the bf16 sentinel 77 in buffers wider than N, whose padding must keep it; operands sit in buffers whose padding is NaN.  The fp64
 references are torch's, on the device.  What the bounds tell apart is pinned without a GPU by test_gemm_small_bound.py."""
 import functools
@@ -29,10 +30,10 @@ PLAIN_TILES = {(24827, 8, 64): 97, (1, 24584, 128): 97, (2500, 2568, 192): 110, 
                (25000, 200, 64): 98}
 
 
-def selected(shape, kernel, epi=0, keep=False):
-    """Asserts that the launcher sends `shape` to `kernel` on this device."""
+def selected(shape, kernel, epi=0, keep=False, **operands):
+    """Asserts that the launcher sends `shape` to `kernel` on this device.  operands: fold= / rowparts= / mapped= of the call."""
     M, N, K = shape
-    r = route(M, N, K, epi, keep)
+    r = route(M, N, K, epi, keep, **operands)
     assert r.kernel == kernel, (f"{shape}: {r.nwg} tiles on {r.cus} CUs, K = {K} selects the {r.kernel} kernel; the case is there for the "
                                 f"{kernel} kernel")
     if kernel == "plain":
@@ -86,7 +87,8 @@ def test_skinny_row_maps():
     """The patch embedding's launches at a small batch: out_group = g^2 leaves every image's class row alone (bias epilogue), and with
     resid_mod = g^2, resid_off = 1 patch p of every image adds row 1 + p of the [g^2 + 1, D] position table."""
     B, g2, D, K = H.ROWMAP_CASE
-    selected((B * g2, D, K), "skinny")
+    for epi in (0, 3):
+        selected((B * g2, D, K), "skinny", epi, mapped=True)
     a, w, bias, pos = operands(B * g2, D, K, g2 + 1)
     res = {}
     for epi in (0, 3):
@@ -101,7 +103,7 @@ def test_skinny_row_maps():
 def test_plain_gelu_with_out_group():
     """GELU-erf with out_group: the ABI admits it, and no persistent form has it, so the plain kernel runs it at any size."""
     M, N, K, group = H.MAPPED_GELU_CASE
-    selected((M, N, K), "plain", 1)
+    selected((M, N, K), "plain", 1, mapped=True)
     a, w, bias, _ = operands(M, N, K, 1)
     out = H.gemm(a, w, bias, epi=1, out=sentinel(M + M // group, N + 8), out_group=group)
     assert bool((H.class_rows(out, M // group, group) == SENT).all()) and padding_kept(out, N)
@@ -171,7 +173,7 @@ def test_ln_fold_within_fold_bound(shape):
     """Epilogues 0, 1, 2 of ov_gemm_ln in the skinny and plain kernels on spiked inputs (hipops.spiked_fold_case), under fold_bound."""
     kernel = "plain" if shape in H.PLAIN_SHAPES else "skinny"
     for epi in (0, 1, 2):
-        selected(shape, kernel, epi)
+        selected(shape, kernel, epi, fold=True)
     ops, st, outs = run_fold(shape)
     report(f"{kernel} {shape} LN fold", fold_ratios_bound(ops[0], ops[1], ops[3], ops[2], st, outs))
 
@@ -179,7 +181,7 @@ def test_ln_fold_within_fold_bound(shape):
 def test_ln_fold_persistent_within_both_rules():
     """Case 1 of the routes table (the persistent kernel, K = 192) on the spiked inputs: fold_bound, and beside it the tuned rule."""
     for epi in (0, 1, 2):
-        shape = RT.selected(1, epi)
+        shape = RT.selected(1, epi, fold=True)
     ops, st, outs = run_fold(shape)
     report(f"persistent {shape} LN fold", fold_ratios_bound(ops[0], ops[1], ops[3], ops[2], st, outs))
     report(f"persistent {shape} LN fold, tuned rule", ln_linear_ratios(ops, outs))
@@ -196,7 +198,7 @@ def test_rowparts_output_and_sums(shape):
     kernel computes them in its epilogue, the plain kernel is followed by that pass -- and each {sum, sum of squares} within
     32 e sum|c| resp. 32 e sum c^2 of the fp64 sums of the stored bf16 values (a 32-term fp32 sum in any order; the bf16 products
     are exact in fp32); the word behind the parts buffer survives."""
-    M, N, K = selected(shape, "plain" if shape[0] > 2000 else "skinny", 3)
+    M, N, K = selected(shape, "plain" if shape[0] > 2000 else "skinny", 3, rowparts=True)
     assert (N // 32) % 2 == 1
     a, w, bias, r = operands(M, N, K)
     buf = sentinel(M, N + 8)

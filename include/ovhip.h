@@ -167,11 +167,12 @@ int ov_gemm_route(int64_t M, int N, int K, int epilogue, int fold, int keep, int
 /* Non-causal, unmasked multi-head self-attention on a packed qkv activation.
  * qkv: [B*L, 3*H*hd] bf16 (q | k | v column blocks, heads contiguous inside each, ld = ld_qkv);
  * out: [B*L, H*hd] bf16 (heads merged, ld = ld_out).  scale multiplies q.k (hd^-0.5).
- * hd == 64 takes the tuned kernels; any other multiple of 8 up to 96 (So400m: 72, H/14: 80) a generic one. */
+ * hd % 8 == 0, hd <= 96; which kernel a shape takes: ov_attention_route. */
 int ov_attention(const ov_bf16* qkv, int64_t ld_qkv, ov_bf16* out, int64_t ld_out,
                  int B, int L, int H, int hd, float scale, ov_stream_t stream);
 /* ov_attention that also keeps lse[B*H][Lp] (Lp = L rounded up to 32, fp32): the log-sum-exp of every query row's scaled scores in
- * log2 units, for ov_attention_backward_saved.  head_dim 64 and L <= 288 only (OV_ERR_UNSUPPORTED otherwise). */
+ * log2 units, for ov_attention_backward_saved.  Only where the backward reads it (ov_attention_route_t::keep_lse);
+ * OV_ERR_UNSUPPORTED otherwise. */
 int ov_attention_lse(const ov_bf16* qkv, int64_t ld_qkv, ov_bf16* out, int64_t ld_out, float* lse, int B, int L, int H, int hd, float scale,
                      ov_stream_t stream);
 /* Prefix-causal attention (the text decoder's prefix-LM mask, text_transformer.py:418-442 with li = prefix; make_causal_mask for
@@ -180,6 +181,53 @@ int ov_attention_lse(const ov_bf16* qkv, int64_t ld_qkv, ov_bf16* out, int64_t l
  * layouts, head dims and argument checks as ov_attention.  No e4m3-output form. */
 int ov_attention_prefix(const ov_bf16* qkv, int64_t ld_qkv, ov_bf16* out, int64_t ld_out, int B, int L, int H, int hd, float scale,
                         int prefix, ov_stream_t stream);
+
+/* What the attention entry points launch for a shape, forward (ov_attention / _lse / _fp8out / _prefix) and backward
+ * (ov_attention_backward / _saved / ov_attention_prefix_backward): the launchers' own decision, reported without launching anything
+ * (tests and tools ask this instead of restating the rules; DESIGN.md section 4 states them). */
+enum ov_attn_fwd_kernel {
+    OV_ATTN_FWD_PERSISTENT = 0,       /* head_dim 64, the head's K / V resident in LDS, workgroups walk the heads */
+    OV_ATTN_FWD_STREAMING = 1,        /* head_dim 64, longer sequences: 64-key chunks streamed through LDS, 256 queries per workgroup */
+    OV_ATTN_FWD_GENERIC = 2           /* every head_dim (padded to hdp in LDS), every row pitch, the prefix mask */
+};
+enum ov_attn_bwd_kernel {
+    OV_ATTN_BWD_RESIDENT = 0,         /* head_dim 64: Q, K, V and dO of a head resident in LDS, one launch, no workspace */
+    OV_ATTN_BWD_STREAMING = 1         /* the dQ and the dK / dV kernel over 256-row chunks, row lse and delta in the workspace */
+};
+typedef struct {
+    /* ---- forward */
+    int fwd_kernel;                   /* enum ov_attn_fwd_kernel */
+    int deep;                         /* persistent: the instantiation for workgroups of at most 8 waves */
+    int out8;                         /* persistent / streaming: e4m3 output (ov_attention_fp8out) */
+    int lse;                          /* persistent: the row log-sum-exp is written (ov_attention_lse) */
+    int mask;                         /* generic: the prefix mask (prefix < L) */
+    int hdp;                          /* generic: the head_dim the LDS image is padded to (64 or 96); 0 for the other kernels */
+    int resident;                     /* the whole (padded) sequence of a head is staged once; 0 = in chunks of kc keys */
+    int kc;                           /* keys per LDS stage */
+    int waves;                        /* waves per workgroup (32 queries each) */
+    int grid_x, grid_y;               /* workgroups */
+    int lds_bytes;                    /* dynamic LDS per workgroup */
+    int lone_valu;                    /* persistent / streaming: a single-key last tile / chunk is folded in on the VALU
+                                         (OVHIP_ATTN_LONEKEY=0: a tile step); the generic kernel always folds: 1 */
+    /* ---- backward (saved = the call passes the forward's lse) */
+    int bwd_kernel;                   /* enum ov_attn_bwd_kernel */
+    int bwd_saved;                    /* resident: the row statistics are read from lse, not recomputed */
+    int bwd_mask;                     /* streaming: the prefix mask */
+    int ndh;                          /* streaming: 32-column d-blocks of a head in LDS (2: head_dim <= 64, 3: up to 96); 0 for resident */
+    int bwd_kc;                       /* rows per LDS stage */
+    int bwd_waves;
+    int bwd_grid;
+    int bwd_lds_bytes;
+    int keep_lse;                     /* the backward reads the forward's lse: the training forward keeps it (ov_attention_lse) */
+    size_t bwd_workspace_bytes;       /* what ov_attention[_prefix]_backward_workspace_bytes reports (0: none needed) */
+} ov_attention_route_t;
+/* ld_qkv / ld_out: the forward's row pitches in elements (0: dense, 3 H hd / H hd).  prefix < 0: no mask (ov_attention); 0 <= prefix
+ * <= L: ov_attention_prefix and its backward (prefix == L is the unmasked route).  out8 / lse != 0: ov_attention_fp8out /
+ * ov_attention_lse and ov_attention_backward_saved with an lse.  cus <= 0: the current device's CU count; > 0: used as given (no
+ * device needed).  OVHIP_ATTN_LONEKEY is what the process read at its first attention or route call.  OV_ERR_UNSUPPORTED: a
+ * combination or shape the entry points of either direction do not admit. */
+int ov_attention_route(int B, int L, int H, int hd, int64_t ld_qkv, int64_t ld_out, int prefix, int out8, int lse, int cus,
+                       ov_attention_route_t* route);
 
 /* Patch gather for conv1: image [B,3,S,S] (img_dtype) -> P[B*g*g, Kpad] bf16,
  * column index c*P*P + i*P + j (the flattening of conv1.weight[D,3,P,P]); columns >= 3*P*P zeroed. */
@@ -483,15 +531,16 @@ int ov_layernorm_backward(const ov_bf16* x, int64_t ldx, const float* gamma, con
 
 /* Backward of ov_attention (unmasked softmax attention of nn.MultiheadAttention, transformer.py:225,239-252): from the packed
  * qkv [B*L, 3*H*hd], the forward output out [B*L, H*hd] and the upstream gradient dout, writes dqkv [B*L, 3*H*hd] = (dQ | dK | dV).
- * The row log-sum-exp is recomputed (the forward keeps none).  hd % 8 == 0, hd <= 96.  hd == 64 and L <= 288: one kernel with the
- * head resident in LDS, no workspace; otherwise (long sequences; head dims 72 / 80 of So400m / H-14, zero-padded to 96 in LDS) two
- * streaming kernels and a workspace of ov_attention_backward_workspace_bytes (row lse and delta).  Deterministic. */
+ * The row log-sum-exp is recomputed (the forward keeps none).  hd % 8 == 0, hd <= 96.  Short head_dim 64 sequences: one kernel with
+ * the head resident in LDS, no workspace; otherwise (long sequences; head dims 72 / 80 of So400m / H-14, zero-padded to 96 in LDS) two
+ * streaming kernels and a workspace of ov_attention_backward_workspace_bytes (row lse and delta); ov_attention_route reports which.
+ * Deterministic. */
 size_t ov_attention_backward_workspace_bytes(int B, int L, int H, int hd);
 int ov_attention_backward(const ov_bf16* qkv, int64_t ld_qkv, const ov_bf16* out, int64_t ld_out, const ov_bf16* dout, int64_t ld_dout,
                           ov_bf16* dqkv, int64_t ld_dqkv, int B, int L, int H, int hd, float scale, void* workspace,
                           size_t workspace_bytes, ov_stream_t stream);
 /* The same with the forward's row statistics kept by ov_attention_lse (lse [B*H][L rounded up to 32] fp32, or NULL): the resident
- * kernel (head_dim 64, L <= 288) then skips its own score pass; the streaming kernels ignore it. */
+ * kernel then skips its own score pass; the streaming kernels ignore it. */
 int ov_attention_backward_saved(const ov_bf16* qkv, int64_t ld_qkv, const ov_bf16* out, int64_t ld_out, const ov_bf16* dout, int64_t ld_dout,
                                 ov_bf16* dqkv, int64_t ld_dqkv, const float* lse, int B, int L, int H, int hd, float scale, void* workspace,
                                 size_t workspace_bytes, ov_stream_t stream);
@@ -707,7 +756,7 @@ int    ov_tower_backward_checkpointed(const ov_tower* t, int first, const ov_bf1
 
 /* ---- MLP-feature objective (feature visualisation: a forward hook on resblocks[layer].mlp.gelu, ov-feature-visualization.py:211) --
  * The attention half of one block, x1 = x + out_proj(attn(ln_1(x))) (transformer.py:263), keeping qkv [B*L, 3D], attn_out [B*L, D],
- * x1 [B*L, D] and, where the resident attention backward reads it (head_dim 64, L <= 288), lse [B*heads][L rounded up to 32] fp32
+ * x1 [B*L, D] and, where the resident attention backward reads it (ov_attention_route_t::keep_lse), lse [B*heads][L rounded up to 32] fp32
  * (NULL = not kept).  `w` holds the module's own weights; only ln_1, in_proj and out_proj are read. */
 int ov_block_attn_forward_saving(const ov_tower_cfg* cfg, const ov_block_weights* w, const ov_bf16* x, ov_bf16* qkv, ov_bf16* attn_out,
                                  ov_bf16* x1, float* lse, int B, int L, ov_stream_t stream);

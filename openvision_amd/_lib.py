@@ -48,6 +48,12 @@ class GemmRoute(C.Structure):        # ov_gemm_route_t: what the bf16 GEMM launc
                                      "keep_prepass", "rowparts_pass")]
 
 
+class AttentionRoute(C.Structure):   # ov_attention_route_t: what the attention launchers decide for a shape (ov_attention_route)
+    _fields_ = [(n, c_int) for n in ("fwd_kernel", "deep", "out8", "lse", "mask", "hdp", "resident", "kc", "waves", "grid_x", "grid_y",
+                                     "lds_bytes", "lone_valu", "bwd_kernel", "bwd_saved", "bwd_mask", "ndh", "bwd_kc", "bwd_waves",
+                                     "bwd_grid", "bwd_lds_bytes", "keep_lse")] + [("bwd_workspace_bytes", c_size_t)]
+
+
 class VisionHead(C.Structure):
     _fields_ = [("image_size", c_int), ("patch_size", c_int), ("kpad", c_int), ("pool_avg", c_int),
                 ("final_ln_after_pool", c_int), ("embed_dim", c_int), ("embed_pad", c_int),
@@ -91,6 +97,7 @@ SIGNATURES = {
     "ov_gemm_rowparts": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_void_p, c_int64,
                                  c_void_p, c_void_p]),
     "ov_gemm_route": (c_int, [c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "ov_attention_route": (c_int, [c_int, c_int, c_int, c_int, c_int64, c_int64, c_int, c_int, c_int, c_int, c_void_p]),
     "ov_attention": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_float, c_void_p]),
     "ov_attention_prefix": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p]),
     "ov_attention_prefix_backward_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),

@@ -37,7 +37,8 @@ def _digest(paths) -> str:
 def build(force: bool = False, verbose: bool = True) -> str:
     bdir = os.path.join(CSRC, "build")
     os.makedirs(bdir, exist_ok=True)
-    deps = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "strip.h"), os.path.join(PKG, "..", "include", "ovhip.h")]
+    # every header under csrc (common.h, strip.h, attention_route.h, ...) and the C ABI: an edit to any of them recompiles every object
+    deps = sorted(os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h")) + [os.path.join(PKG, "..", "include", "ovhip.h")]
     cc = hipcc()
 
     def compile_one(src):

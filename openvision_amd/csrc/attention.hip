@@ -988,23 +988,79 @@ __global__ __launch_bounds__(640) void attn_fwd_generic(const AttnArgs a, int hd
 
 }  // namespace
 
+#include "attention_route.h"
+
 namespace {
-int attention_impl(const ov_bf16* qkv, int64_t ld_qkv, ov_bf16* out, int64_t ld_out, int B, int L, int H, int hd, float scale,
-                   const float* out_amax, float* amax_next, float* lse, ov_stream_t stream);
+const AttnSwitches& attn_switches() {
+    static const AttnSwitches s = [] { const char* e = getenv("OVHIP_ATTN_LONEKEY"); return AttnSwitches{(e && e[0] == '0') ? 0 : 1}; }();
+    return s;
 }
+
+// The instantiations each kernel has; a form = the route's flags as bits.
+enum { F_DEEP = 1, F_OUT8 = 2, F_LSE = 4, F_MASK = 8, F_HDP64 = 16 };
+const OvKernelForm<AttnPArgs> PERSIST[] = {{0, attn_fwd_hd64_persist<false, false>},          {F_DEEP, attn_fwd_hd64_persist<true, false>},
+                                           {F_OUT8, attn_fwd_hd64_persist<false, true>},      {F_DEEP | F_OUT8, attn_fwd_hd64_persist<true, true>},
+                                           {F_LSE, attn_fwd_hd64_persist<false, false, true>}, {F_DEEP | F_LSE, attn_fwd_hd64_persist<true, false, true>}};
+const OvKernelForm<AttnSArgs> STREAM[] = {{0, attn_fwd_hd64_stream<false>}, {F_OUT8, attn_fwd_hd64_stream<true>}};
+const OvKernelForm<AttnArgs, int> GENERIC[] = {{0, attn_fwd_generic<96>}, {F_MASK | F_HDP64, attn_fwd_generic<64, true>}, {F_MASK, attn_fwd_generic<96, true>}};
+
+// The one way into the kernels, for ov_attention and its siblings: the entry points have checked the operands they own (lse,
+// out_amax); here the common ones are checked, attn_fwd_route (attention_route.h) decides, and the route is carried out.
+// prefix == L: no mask.
+int attention_run(const ov_bf16* qkv, int64_t ld_qkv, ov_bf16* out, int64_t ld_out, int B, int L, int H, int hd, float scale, int prefix,
+                  const float* out_amax, float* amax_next, float* lse, ov_stream_t stream) {
+    if (!qkv || !out || B <= 0 || L <= 0 || H <= 0) return OV_ERR_INVALID;
+    if (prefix < 0 || prefix > L) return OV_ERR_INVALID;
+    if (hd <= 0 || hd % 8 || hd > 96) return OV_ERR_UNSUPPORTED;
+    if (ld_qkv % 8 || ld_out % 8 || ld_qkv < 3 * H * hd || ld_out < H * hd) return OV_ERR_INVALID;
+    if (((uintptr_t)qkv | (uintptr_t)out) & 15) return OV_ERR_INVALID;
+    ov_attention_route_t r = {};
+    const int rc = attn_fwd_route(r, B, L, H, hd, ld_qkv, ld_out, prefix, out_amax != nullptr, lse != nullptr, ov_num_cus(), attn_switches());
+    if (rc != OV_OK) return rc;
+    static OvPerDeviceOnce once[3];
+    const int nqt = (L + 31) / 32;
+    const float scale_log2 = scale * 1.4426950408889634f;
+    const dim3 grid((unsigned)r.grid_x, (unsigned)r.grid_y), blk((unsigned)(r.waves * 64));
+    if (r.fwd_kernel == OV_ATTN_FWD_PERSISTENT) {
+        AttnPArgs p;
+        p.qkv = qkv; p.ldq = ld_qkv; p.out = out; p.ldo = ld_out;
+        p.L = L; p.H = H; p.nqt = nqt; p.KC = r.kc; p.nheads = B * H; p.scale_log2 = scale_log2; p.out_amax = out_amax; p.amax_next = amax_next; p.lse = lse;
+        p.lone_valu = r.lone_valu;
+        return ov_launch_form(PERSIST, once[0], OV_ATTN_LDS, r.deep * F_DEEP | r.out8 * F_OUT8 | r.lse * F_LSE, grid, blk, r.lds_bytes,
+                              (hipStream_t)stream, p);
+    }
+    if (r.fwd_kernel == OV_ATTN_FWD_STREAMING) {
+        AttnSArgs sa;
+        sa.qkv = qkv; sa.ldq = ld_qkv; sa.out = out; sa.ldo = ld_out;
+        sa.L = L; sa.H = H; sa.nqt = nqt; sa.nqb = (nqt + 7) / 8; sa.nheads = B * H; sa.nchunks = (L + 63) / 64;
+        sa.scale_log2 = scale_log2;
+        sa.out_amax = out_amax;
+        sa.amax_next = amax_next;
+        sa.lone_valu = r.lone_valu;
+        return ov_launch_form(STREAM, once[1], OV_ATTN_LDS, r.out8 * F_OUT8, grid, blk, r.lds_bytes, (hipStream_t)stream, sa);
+    }
+    AttnArgs g;
+    g.qkv = qkv; g.ldq = ld_qkv; g.out = out; g.ldo = ld_out;
+    g.B = B; g.L = L; g.H = H; g.nqt = nqt; g.KC = r.kc;
+    g.scale_log2 = scale_log2;
+    g.prefix = prefix;
+    return ov_launch_form(GENERIC, once[2], OV_ATTN_LDS, r.mask * F_MASK | (r.hdp == 64) * F_HDP64, grid, blk, r.lds_bytes,
+                          (hipStream_t)stream, g, hd);
+}
+}  // namespace
 
 extern "C" int ov_attention(const ov_bf16* qkv, int64_t ld_qkv, ov_bf16* out, int64_t ld_out, int B, int L,
                             int H, int hd, float scale, ov_stream_t stream) {
-    return attention_impl(qkv, ld_qkv, out, ld_out, B, L, H, hd, scale, nullptr, nullptr, nullptr, stream);
+    return attention_run(qkv, ld_qkv, out, ld_out, B, L, H, hd, scale, L, nullptr, nullptr, nullptr, stream);
 }
 
 // ov_attention that also keeps the softmax statistics for ov_attention_backward_saved: lse[B*H][Lp] (Lp = L rounded up to 32) = the
 // log-sum-exp of every query row's scaled scores, in log2 units (m + log2 l of the online softmax).  Only for the shapes the resident
-// backward kernel takes (head_dim 64, L <= 288); OV_ERR_UNSUPPORTED otherwise -- call ov_attention and let the backward recompute.
+// backward kernel takes (the route's keep_lse); OV_ERR_UNSUPPORTED otherwise -- call ov_attention and let the backward recompute.
 extern "C" int ov_attention_lse(const ov_bf16* qkv, int64_t ld_qkv, ov_bf16* out, int64_t ld_out, float* lse, int B, int L, int H, int hd,
                                 float scale, ov_stream_t stream) {
     if (!lse || ((uintptr_t)lse & 3)) return OV_ERR_INVALID;
-    return attention_impl(qkv, ld_qkv, out, ld_out, B, L, H, hd, scale, nullptr, nullptr, lse, stream);
+    return attention_run(qkv, ld_qkv, out, ld_out, B, L, H, hd, scale, L, nullptr, nullptr, lse, stream);
 }
 
 // Same attention, output written as e4m3 bytes out8[B*L, H*64] (ld_out in bytes) with the static scale 2 * (*out_amax) / 448
@@ -1013,161 +1069,29 @@ extern "C" int ov_attention_fp8out(const ov_bf16* qkv, int64_t ld_qkv, unsigned 
                                    int hd, float scale, const float* out_amax, float* out_amax_next, ov_stream_t stream) {
     if (!out_amax) return OV_ERR_INVALID;
     if (hd != 64) return OV_ERR_UNSUPPORTED;
-    return attention_impl(qkv, ld_qkv, (ov_bf16*)out8, ld_out, B, L, H, hd, scale, out_amax, out_amax_next, nullptr, stream);
+    return attention_run(qkv, ld_qkv, (ov_bf16*)out8, ld_out, B, L, H, hd, scale, L, out_amax, out_amax_next, nullptr, stream);
 }
-
-namespace {
-// OVHIP_ATTN_LONEKEY=0: a single-key last tile / chunk takes a tile step instead of the VALU fold (the tests run both branches)
-int attn_lone_valu() {
-    static const int v = [] { const char* e = getenv("OVHIP_ATTN_LONEKEY"); return (e && e[0] == '0') ? 0 : 1; }();
-    return v;
-}
-
-int attention_impl(const ov_bf16* qkv, int64_t ld_qkv, ov_bf16* out, int64_t ld_out, int B, int L, int H, int hd, float scale,
-                   const float* out_amax, float* amax_next, float* lse, ov_stream_t stream) {
-    if (!qkv || !out || B <= 0 || L <= 0 || H <= 0) return OV_ERR_INVALID;
-    if (hd <= 0 || hd % 8 || hd > 96) return OV_ERR_UNSUPPORTED;
-    if (ld_qkv % 8 || ld_out % 8 || ld_qkv < 3 * H * hd || ld_out < H * hd) return OV_ERR_INVALID;
-    if (((uintptr_t)qkv | (uintptr_t)out) & 15) return OV_ERR_INVALID;
-    const bool out8 = out_amax != nullptr;
-    if (lse != nullptr && (!ov_attn_bwd_resident(hd, L) || out8)) return OV_ERR_UNSUPPORTED;   // the resident backward's shapes only
-    const int nqt = (L + 31) / 32, lp = nqt * 32;
-    const float scale_log2 = scale * 1.4426950408889634f;
-    // the persistent kernel's row offsets are 32-bit: an image spanning 2 GiB of rows or more (a caller's huge row pitch) goes to the
-    // generic kernel below
-    const bool narrow = (int64_t)L * ld_qkv * 2 < 0x7fffffffLL && (int64_t)L * ld_out * 2 < 0x7fffffffLL;
-    if (hd == 64 && lp <= 320 && narrow) {
-        AttnPArgs p;
-        p.qkv = qkv; p.ldq = ld_qkv; p.out = out; p.ldo = ld_out;
-        p.L = L; p.H = H; p.nqt = nqt; p.KC = lp; p.nheads = B * H; p.scale_log2 = scale_log2; p.out_amax = out_amax; p.amax_next = amax_next; p.lse = lse;
-        p.lone_valu = attn_lone_valu();
-        static OvPerDeviceOnce attr2;
-        const int dev_attr2 = ov_current_device();
-        if (attr2.need(dev_attr2)) {
-            hipError_t e = hipFuncSetAttribute((const void*)attn_fwd_hd64_persist<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               160 * 1024);
-            if (e == hipSuccess)
-                e = hipFuncSetAttribute((const void*)attn_fwd_hd64_persist<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e == hipSuccess)
-                e = hipFuncSetAttribute((const void*)attn_fwd_hd64_persist<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e == hipSuccess)
-                e = hipFuncSetAttribute((const void*)attn_fwd_hd64_persist<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e == hipSuccess)
-                e = hipFuncSetAttribute((const void*)attn_fwd_hd64_persist<false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e == hipSuccess)
-                e = hipFuncSetAttribute((const void*)attn_fwd_hd64_persist<true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return OV_ERR_HIP - (int)e;
-            attr2.mark(dev_attr2);
-        }
-        const int ncu = ov_num_cus();
-        const size_t smem = (size_t)2 * lp * 256;
-        int per_cu = (int)((160 * 1024) / smem);                  // workgroups per CU by LDS ...
-        const int by_waves = (nqt <= 8 ? 8 : 12) / nqt;           // ... and by waves (2 per SIMD for the DEEP variant, else 3)
-        if (per_cu > by_waves) per_cu = by_waves;
-        if (per_cu < 1) per_cu = 1;
-        const int cap = ncu * per_cu;
-        const int grid = p.nheads < cap ? p.nheads : cap;
-        const dim3 pg((unsigned)grid), pb(nqt * 64);
-        if (nqt <= 8) {
-            if (out8) hipLaunchKernelGGL((attn_fwd_hd64_persist<true, true>), pg, pb, smem, (hipStream_t)stream, p);
-            else if (lse) hipLaunchKernelGGL((attn_fwd_hd64_persist<true, false, true>), pg, pb, smem, (hipStream_t)stream, p);
-            else hipLaunchKernelGGL((attn_fwd_hd64_persist<true, false>), pg, pb, smem, (hipStream_t)stream, p);
-        } else {
-            if (out8) hipLaunchKernelGGL((attn_fwd_hd64_persist<false, true>), pg, pb, smem, (hipStream_t)stream, p);
-            else if (lse) hipLaunchKernelGGL((attn_fwd_hd64_persist<false, false, true>), pg, pb, smem, (hipStream_t)stream, p);
-            else hipLaunchKernelGGL((attn_fwd_hd64_persist<false, false>), pg, pb, smem, (hipStream_t)stream, p);
-        }
-        OV_LAUNCH_CHECK();
-        return OV_OK;
-    }
-    if (hd == 64 && lp > 320) {
-        AttnSArgs sa;
-        sa.qkv = qkv; sa.ldq = ld_qkv; sa.out = out; sa.ldo = ld_out;
-        sa.L = L; sa.H = H; sa.nqt = nqt; sa.nqb = (nqt + 7) / 8; sa.nheads = B * H; sa.nchunks = (L + 63) / 64;
-        sa.scale_log2 = scale_log2;
-        sa.out_amax = out_amax;
-        sa.amax_next = amax_next;
-        sa.lone_valu = attn_lone_valu();
-        static OvPerDeviceOnce attr4;
-        const int dev_attr4 = ov_current_device();
-        if (attr4.need(dev_attr4)) {
-            hipError_t e = hipFuncSetAttribute((const void*)attn_fwd_hd64_stream<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e == hipSuccess)
-                e = hipFuncSetAttribute((const void*)attn_fwd_hd64_stream<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return OV_ERR_HIP - (int)e;
-            attr4.mark(dev_attr4);
-        }
-        const int64_t heads8 = ((int64_t)sa.nheads + 7) / 8 * 8;             // whole rounds of 8 XCDs; surplus ids exit at once
-        const int64_t nwg = heads8 * sa.nqb;
-        if (nwg > 0x7fffffffLL) return OV_ERR_UNSUPPORTED;
-        if (out8) hipLaunchKernelGGL(attn_fwd_hd64_stream<true>, dim3((unsigned)nwg), dim3(512), 4 * 16384, (hipStream_t)stream, sa);
-        else hipLaunchKernelGGL(attn_fwd_hd64_stream<false>, dim3((unsigned)nwg), dim3(512), 4 * 16384, (hipStream_t)stream, sa);
-        OV_LAUNCH_CHECK();
-        return OV_OK;
-    }
-    // Generic padded-head kernel: head_dim 72 (So400m) / 80 (H/14), and head_dim 64 images beyond the persistent kernel's 2 GiB.
-    if (lse != nullptr || out8) return OV_ERR_UNSUPPORTED;   // (no kept lse, no e4m3 epilogue in this kernel)
-    AttnArgs g;
-    g.qkv = qkv; g.ldq = ld_qkv; g.out = out; g.ldo = ld_out;
-    g.B = B; g.L = L; g.H = H; g.nqt = nqt;
-    g.scale_log2 = scale_log2;
-    g.prefix = L;
-    // up to 320 (padded) keys: the whole head resident in LDS (123 KB at 320) and one wave per query tile (<= 10), so a head is
-    // staged once by one workgroup (L = 257 used to take two 256-key chunks and a second workgroup for the 257th query row: So400m's
-    // attention 8.0 ms per step); longer sequences: 256-key chunks, 8 waves
-    const bool resident = lp <= 320;
-    g.KC = resident ? lp : 256;
-    const int nwg = resident ? g.nqt : 8;
-    const size_t smem = (size_t)g.KC * 96 * 4;       // K (KC x 192 B) + V (3 x KC x 64 B)
-    static OvPerDeviceOnce attr3;
-    const int dev_attr3 = ov_current_device();
-    if (attr3.need(dev_attr3)) {
-        hipError_t e = hipFuncSetAttribute((const void*)attn_fwd_generic<96>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           160 * 1024);
-        if (e != hipSuccess) return OV_ERR_HIP - (int)e;
-        attr3.mark(dev_attr3);
-    }
-    hipLaunchKernelGGL(attn_fwd_generic<96>, dim3((unsigned)(B * H), (unsigned)((g.nqt + nwg - 1) / nwg)), dim3(nwg * 64), smem,
-                       (hipStream_t)stream, g, hd);
-    OV_LAUNCH_CHECK();
-    return OV_OK;
-}
-}  // namespace
 
 // Prefix-causal attention (the text decoder's prefix-LM mask; prefix = 0: causal, prefix = L: unmasked = ov_attention itself).
 // Every head_dim takes the generic kernel's MASK form: 64 at its own width (HDP = 64), 72 / 80 / ... padded to 96.
 extern "C" int ov_attention_prefix(const ov_bf16* qkv, int64_t ld_qkv, ov_bf16* out, int64_t ld_out, int B, int L, int H, int hd, float scale,
                                    int prefix, ov_stream_t stream) {
-    if (!qkv || !out || B <= 0 || L <= 0 || H <= 0) return OV_ERR_INVALID;
-    if (prefix < 0 || prefix > L) return OV_ERR_INVALID;
-    if (prefix == L) return ov_attention(qkv, ld_qkv, out, ld_out, B, L, H, hd, scale, stream);
-    if (hd <= 0 || hd % 8 || hd > 96) return OV_ERR_UNSUPPORTED;
-    if (ld_qkv % 8 || ld_out % 8 || ld_qkv < 3 * H * hd || ld_out < H * hd) return OV_ERR_INVALID;
-    if (((uintptr_t)qkv | (uintptr_t)out) & 15) return OV_ERR_INVALID;
-    if ((int64_t)B * H > 0x7fffffffLL) return OV_ERR_UNSUPPORTED;
-    AttnArgs g;
-    g.qkv = qkv; g.ldq = ld_qkv; g.out = out; g.ldo = ld_out;
-    g.B = B; g.L = L; g.H = H; g.nqt = (L + 31) / 32;
-    g.scale_log2 = scale * 1.4426950408889634f;
-    g.prefix = prefix;
-    const int lp = g.nqt * 32;
-    const bool resident = lp <= 320;                  // as the unmasked generic launch: the head resident, one wave per query tile
-    g.KC = resident ? lp : 256;
-    const int nwg = resident ? g.nqt : 8;
-    const int hdp = hd == 64 ? 64 : 96;
-    const size_t smem = (size_t)g.KC * hdp * 4;       // K (KC x 2 hdp B) + V (hdp / 32 x KC x 64 B)
-    static OvPerDeviceOnce attr;
-    const int dev = ov_current_device();
-    if (attr.need(dev)) {
-        hipError_t e = hipFuncSetAttribute((const void*)attn_fwd_generic<64, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute((const void*)attn_fwd_generic<96, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return OV_ERR_HIP - (int)e;
-        attr.mark(dev);
-    }
-    const dim3 grid((unsigned)(B * H), (unsigned)((g.nqt + nwg - 1) / nwg)), blk(nwg * 64);
-    if (hdp == 64) hipLaunchKernelGGL((attn_fwd_generic<64, true>), grid, blk, smem, (hipStream_t)stream, g, hd);
-    else hipLaunchKernelGGL((attn_fwd_generic<96, true>), grid, blk, smem, (hipStream_t)stream, g, hd);
-    OV_LAUNCH_CHECK();
-    return OV_OK;
+    return attention_run(qkv, ld_qkv, out, ld_out, B, L, H, hd, scale, prefix, nullptr, nullptr, nullptr, stream);
+}
+
+// What the entry points above and those of attention_bwd.hip would launch (ovhip.h); launches nothing.  cus <= 0: the current
+// device's CU count.
+extern "C" int ov_attention_route(int B, int L, int H, int hd, int64_t ld_qkv, int64_t ld_out, int prefix, int out8, int lse, int cus,
+                                  ov_attention_route_t* route) {
+    if (!route || B <= 0 || L <= 0 || H <= 0 || prefix > L) return OV_ERR_INVALID;
+    if (hd <= 0 || hd % 8 || hd > 96 || (out8 && hd != 64)) return OV_ERR_UNSUPPORTED;
+    if (ld_qkv == 0) ld_qkv = (int64_t)3 * H * hd;
+    if (ld_out == 0) ld_out = (int64_t)H * hd;
+    if (ld_qkv % 8 || ld_out % 8 || ld_qkv < (int64_t)3 * H * hd || ld_out < (int64_t)H * hd) return OV_ERR_INVALID;
+    if (prefix < 0) prefix = L;
+    ov_attention_route_t r = {};
+    int rc = attn_fwd_route(r, B, L, H, hd, ld_qkv, ld_out, prefix, out8 != 0, lse != 0, cus > 0 ? cus : ov_num_cus(), attn_switches());
+    if (rc == OV_OK) rc = attn_bwd_route(r, B, L, H, hd, prefix, lse != 0);
+    if (rc == OV_OK) *route = r;
+    return rc;
 }

@@ -549,120 +549,96 @@ __global__ __launch_bounds__(512) void attn_bwd_stream_kv(const AttnBwdSArgs g) 
 
 }  // namespace
 
-extern "C" size_t ov_attention_backward_workspace_bytes(int B, int L, int H, int hd) {
-    if (B <= 0 || L <= 0 || H <= 0 || ov_attn_bwd_resident(hd, L)) return 0;  // the resident kernel needs none
-    const int64_t lpad = (int64_t)(L + CH - 1) / CH * CH;
-    return (size_t)2 * B * H * lpad * sizeof(float);
-}
+#include "attention_route.h"
+static_assert(CH == OV_ATTN_BWD_CH, "the route's chunk is the kernels'");
 
-namespace {
-template <int NDH, bool MASK = false>
-int launch_stream(const AttnBwdSArgs& g, int B, hipStream_t st) {
-    static OvPerDeviceOnce attr;
-    const int dev = ov_current_device();
-    const size_t smem = (size_t)2 * Stream<NDH>::IMG + (size_t)2 * CH * sizeof(float);
-    if (attr.need(dev)) {
-        hipError_t e = hipFuncSetAttribute((const void*)attn_bwd_stream_q<NDH, MASK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)attn_bwd_stream_kv<NDH, MASK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) return ov_hip(e);
-        attr.mark(dev);
-    }
-    const dim3 grid((unsigned)(B * g.a.H * g.nblk));
-    hipLaunchKernelGGL((attn_bwd_stream_q<NDH, MASK>), grid, dim3(512), smem, st, g);
-    OV_LAUNCH_CHECK();
-    hipLaunchKernelGGL((attn_bwd_stream_kv<NDH, MASK>), grid, dim3(512), smem, st, g);
-    OV_LAUNCH_CHECK();
-    return OV_OK;
+// 0 where the resident kernel runs: it needs none
+extern "C" size_t ov_attention_backward_workspace_bytes(int B, int L, int H, int hd) {
+    ov_attention_route_t r = {};
+    if (B > 0 && L > 0 && H > 0) attn_bwd_route(r, B, L, H, hd, L, false);
+    return r.bwd_workspace_bytes;
 }
-}  // namespace
 
 // The masked backward always takes the streaming kernels (row lse and delta in the workspace), also where the unmasked one is resident.
 extern "C" size_t ov_attention_prefix_backward_workspace_bytes(int B, int L, int H, int hd) {
-    (void)hd;
-    if (B <= 0 || L <= 0 || H <= 0) return 0;
-    const int64_t lpad = (int64_t)(L + CH - 1) / CH * CH;
-    return (size_t)2 * B * H * lpad * sizeof(float);
+    ov_attention_route_t r = {};
+    if (B > 0 && L > 0 && H > 0) attn_bwd_route(r, B, L, H, hd, 0, false);
+    return r.bwd_workspace_bytes;
 }
 
-// lse (or NULL): the forward's row statistics from ov_attention_lse, [B*H][L rounded up to 32]; used by the resident kernel
-// (head_dim 64, L <= 288), ignored by the streaming kernels
-extern "C" int ov_attention_backward_saved(const ov_bf16* qkv, int64_t ld_qkv, const ov_bf16* out, int64_t ld_out, const ov_bf16* dout,
-                                           int64_t ld_dout, ov_bf16* dqkv, int64_t ld_dqkv, const float* lse, int B, int L, int H, int hd,
-                                           float scale, void* workspace, size_t workspace_bytes, ov_stream_t stream) {
-    if (!qkv || !out || !dout || !dqkv || B <= 0 || L <= 0 || H <= 0) return OV_ERR_INVALID;
-    if (hd <= 0 || hd % 8 || hd > 96) return OV_ERR_UNSUPPORTED;
-    if (ld_qkv % 8 || ld_out % 8 || ld_dout % 8 || ld_dqkv % 8 || ld_qkv < 3 * H * hd || ld_dqkv < 3 * H * hd || ld_out < H * hd ||
-        ld_dout < H * hd)
-        return OV_ERR_UNSUPPORTED;
-    if (((uintptr_t)qkv | (uintptr_t)out | (uintptr_t)dout | (uintptr_t)dqkv) & 15) return OV_ERR_INVALID;
-    if ((int64_t)B * H > 0x7fffffffLL) return OV_ERR_UNSUPPORTED;
-    AttnBwdArgs a;
-    a.qkv = qkv; a.ldq = ld_qkv; a.out = out; a.ldo = ld_out; a.dout = dout; a.lddo = ld_dout; a.dqkv = dqkv; a.lddq = ld_dqkv;
-    a.L = L; a.H = H; a.KC = (L + 31) / 32 * 32;
-    a.scale = scale; a.scale_log2 = scale * 1.4426950408889634f;
-    a.lse_in = lse;
-    if (ov_attn_bwd_resident(hd, L)) {                          // Q, K, V, dO of a head resident in LDS
-        static OvPerDeviceOnce attr;
-        const int dev = ov_current_device();
-        if (attr.need(dev)) {
-            hipError_t e = hipFuncSetAttribute((const void*)attn_bwd_hd64<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e == hipSuccess) e = hipFuncSetAttribute((const void*)attn_bwd_hd64<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return ov_hip(e);
-            attr.mark(dev);
-        }
-        const size_t smem = (size_t)4 * a.KC * 128 + (size_t)2 * a.KC * sizeof(float);
-        const dim3 grid((unsigned)(B * H)), blk((unsigned)(a.KC / 32 * 64));
-        if (lse != nullptr) hipLaunchKernelGGL(attn_bwd_hd64<true>, grid, blk, smem, (hipStream_t)stream, a);
-        else hipLaunchKernelGGL(attn_bwd_hd64<false>, grid, blk, smem, (hipStream_t)stream, a);
-        OV_LAUNCH_CHECK();
-        return OV_OK;
-    }
-    if (!workspace || ((uintptr_t)workspace & 15)) return OV_ERR_INVALID;
-    if (workspace_bytes < ov_attention_backward_workspace_bytes(B, L, H, hd)) return OV_ERR_WORKSPACE;
-    AttnBwdSArgs g;
-    g.a = a;
-    g.hd = hd;
-    g.prefix = L;
-    g.nblk = (L + CH - 1) / CH;
-    g.Lpad = g.nblk * CH;
-    g.lse = (float*)workspace;
-    g.dlt = g.lse + (size_t)B * H * g.Lpad;
-    if ((int64_t)B * H * g.nblk > 0x7fffffffLL) return OV_ERR_UNSUPPORTED;
-    return hd <= 64 ? launch_stream<2>(g, B, (hipStream_t)stream) : launch_stream<3>(g, B, (hipStream_t)stream);
-}
+namespace {
+// The instantiations each kernel has; a form = the route's flags as bits (F_KV: the dK / dV kernel of the streaming pair).
+enum { F_SAVED = 1 };                              // RESIDENT's
+enum { F_NDH3 = 1, F_MASK = 2, F_KV = 4 };         // STREAM's
+const OvKernelForm<AttnBwdArgs> RESIDENT[] = {{0, attn_bwd_hd64<false>}, {F_SAVED, attn_bwd_hd64<true>}};
+const OvKernelForm<AttnBwdSArgs> STREAM[] = {
+    {0, attn_bwd_stream_q<2>},                   {F_KV, attn_bwd_stream_kv<2>},
+    {F_NDH3, attn_bwd_stream_q<3>},              {F_NDH3 | F_KV, attn_bwd_stream_kv<3>},
+    {F_MASK, attn_bwd_stream_q<2, true>},        {F_MASK | F_KV, attn_bwd_stream_kv<2, true>},
+    {F_NDH3 | F_MASK, attn_bwd_stream_q<3, true>}, {F_NDH3 | F_MASK | F_KV, attn_bwd_stream_kv<3, true>}};
 
-extern "C" int ov_attention_backward(const ov_bf16* qkv, int64_t ld_qkv, const ov_bf16* out, int64_t ld_out, const ov_bf16* dout,
-                                     int64_t ld_dout, ov_bf16* dqkv, int64_t ld_dqkv, int B, int L, int H, int hd, float scale,
-                                     void* workspace, size_t workspace_bytes, ov_stream_t stream) {
-    return ov_attention_backward_saved(qkv, ld_qkv, out, ld_out, dout, ld_dout, dqkv, ld_dqkv, nullptr, B, L, H, hd, scale, workspace,
-                                       workspace_bytes, stream);
-}
-
-extern "C" int ov_attention_prefix_backward(const ov_bf16* qkv, int64_t ld_qkv, const ov_bf16* out, int64_t ld_out, const ov_bf16* dout,
-                                            int64_t ld_dout, ov_bf16* dqkv, int64_t ld_dqkv, int B, int L, int H, int hd, float scale,
-                                            int prefix, void* workspace, size_t workspace_bytes, ov_stream_t stream) {
+// The one way into the kernels, for ov_attention_backward and its siblings: the common operands are checked, attn_bwd_route
+// (attention_route.h) decides, and the route is carried out.  prefix == L: no mask.  lse (or NULL): read by the resident kernel only.
+int attention_bwd_run(const ov_bf16* qkv, int64_t ld_qkv, const ov_bf16* out, int64_t ld_out, const ov_bf16* dout, int64_t ld_dout,
+                      ov_bf16* dqkv, int64_t ld_dqkv, const float* lse, int B, int L, int H, int hd, float scale, int prefix,
+                      void* workspace, size_t workspace_bytes, ov_stream_t stream) {
     if (!qkv || !out || !dout || !dqkv || B <= 0 || L <= 0 || H <= 0) return OV_ERR_INVALID;
     if (prefix < 0 || prefix > L) return OV_ERR_INVALID;
-    if (prefix == L)
-        return ov_attention_backward(qkv, ld_qkv, out, ld_out, dout, ld_dout, dqkv, ld_dqkv, B, L, H, hd, scale, workspace, workspace_bytes, stream);
     if (hd <= 0 || hd % 8 || hd > 96) return OV_ERR_UNSUPPORTED;
     if (ld_qkv % 8 || ld_out % 8 || ld_dout % 8 || ld_dqkv % 8 || ld_qkv < 3 * H * hd || ld_dqkv < 3 * H * hd || ld_out < H * hd ||
         ld_dout < H * hd)
         return OV_ERR_UNSUPPORTED;
     if (((uintptr_t)qkv | (uintptr_t)out | (uintptr_t)dout | (uintptr_t)dqkv) & 15) return OV_ERR_INVALID;
-    if (!workspace || ((uintptr_t)workspace & 15)) return OV_ERR_INVALID;
-    if (workspace_bytes < ov_attention_prefix_backward_workspace_bytes(B, L, H, hd)) return OV_ERR_WORKSPACE;
+    // The route refuses a grid beyond 2^31 - 1 workgroups (rc).  The unmasked call answers more than 2^31 - 1 heads here, before it
+    // looks at the workspace; every other refusal, and the masked call's, comes after the workspace checks below.
+    if (prefix == L && (int64_t)B * H > OV_ATTN_I32) return OV_ERR_UNSUPPORTED;
+    ov_attention_route_t r = {};
+    const int rc = attn_bwd_route(r, B, L, H, hd, prefix, lse != nullptr);
+    static OvPerDeviceOnce once[2];
     AttnBwdSArgs g;
     g.a.qkv = qkv; g.a.ldq = ld_qkv; g.a.out = out; g.a.ldo = ld_out; g.a.dout = dout; g.a.lddo = ld_dout; g.a.dqkv = dqkv; g.a.lddq = ld_dqkv;
     g.a.L = L; g.a.H = H; g.a.KC = (L + 31) / 32 * 32;
     g.a.scale = scale; g.a.scale_log2 = scale * 1.4426950408889634f;
-    g.a.lse_in = nullptr;
+    g.a.lse_in = lse;
+    const dim3 grid((unsigned)r.bwd_grid), blk((unsigned)(r.bwd_waves * 64));
+    if (r.bwd_kernel == OV_ATTN_BWD_RESIDENT)          // (unmasked only, so rc is OK here: the line above has ruled its one refusal out)
+        return rc != OV_OK ? rc : ov_launch_form(RESIDENT, once[0], OV_ATTN_LDS, r.bwd_saved * F_SAVED, grid, blk, r.bwd_lds_bytes,
+                                                 (hipStream_t)stream, g.a);
+    if (!workspace || ((uintptr_t)workspace & 15)) return OV_ERR_INVALID;
+    if (workspace_bytes < r.bwd_workspace_bytes) return OV_ERR_WORKSPACE;
+    if (rc != OV_OK) return rc;
     g.hd = hd;
     g.prefix = prefix;
     g.nblk = (L + CH - 1) / CH;
     g.Lpad = g.nblk * CH;
     g.lse = (float*)workspace;
     g.dlt = g.lse + (size_t)B * H * g.Lpad;
-    if ((int64_t)B * H * g.nblk > 0x7fffffffLL) return OV_ERR_UNSUPPORTED;
-    return hd <= 64 ? launch_stream<2, true>(g, B, (hipStream_t)stream) : launch_stream<3, true>(g, B, (hipStream_t)stream);
+    const int form = (r.ndh == 3) * F_NDH3 | r.bwd_mask * F_MASK;
+    const int rq = ov_launch_form(STREAM, once[1], OV_ATTN_LDS, form, grid, blk, r.bwd_lds_bytes, (hipStream_t)stream, g);
+    return rq != OV_OK ? rq : ov_launch_form(STREAM, once[1], OV_ATTN_LDS, form | F_KV, grid, blk, r.bwd_lds_bytes, (hipStream_t)stream, g);
 }
+}  // namespace
+
+// lse (or NULL): the forward's row statistics from ov_attention_lse, [B*H][L rounded up to 32]; used by the resident kernel, ignored
+// by the streaming kernels
+extern "C" int ov_attention_backward_saved(const ov_bf16* qkv, int64_t ld_qkv, const ov_bf16* out, int64_t ld_out, const ov_bf16* dout,
+                                           int64_t ld_dout, ov_bf16* dqkv, int64_t ld_dqkv, const float* lse, int B, int L, int H, int hd,
+                                           float scale, void* workspace, size_t workspace_bytes, ov_stream_t stream) {
+    return attention_bwd_run(qkv, ld_qkv, out, ld_out, dout, ld_dout, dqkv, ld_dqkv, lse, B, L, H, hd, scale, L, workspace, workspace_bytes,
+                             stream);
+}
+
+extern "C" int ov_attention_backward(const ov_bf16* qkv, int64_t ld_qkv, const ov_bf16* out, int64_t ld_out, const ov_bf16* dout,
+                                     int64_t ld_dout, ov_bf16* dqkv, int64_t ld_dqkv, int B, int L, int H, int hd, float scale,
+                                     void* workspace, size_t workspace_bytes, ov_stream_t stream) {
+    return attention_bwd_run(qkv, ld_qkv, out, ld_out, dout, ld_dout, dqkv, ld_dqkv, nullptr, B, L, H, hd, scale, L, workspace,
+                             workspace_bytes, stream);
+}
+
+extern "C" int ov_attention_prefix_backward(const ov_bf16* qkv, int64_t ld_qkv, const ov_bf16* out, int64_t ld_out, const ov_bf16* dout,
+                                            int64_t ld_dout, ov_bf16* dqkv, int64_t ld_dqkv, int B, int L, int H, int hd, float scale,
+                                            int prefix, void* workspace, size_t workspace_bytes, ov_stream_t stream) {
+    return attention_bwd_run(qkv, ld_qkv, out, ld_out, dout, ld_dout, dqkv, ld_dqkv, nullptr, B, L, H, hd, scale, prefix, workspace,
+                             workspace_bytes, stream);
+}
+

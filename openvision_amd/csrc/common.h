@@ -52,6 +52,34 @@ static inline int ov_num_cus() {
     return n;
 }
 
+// A kernel template's instantiations as one flat list, form (the launcher's flags as bits) -> kernel.  ov_launch_form raises the
+// dynamic-LDS limit of the whole list to max_lds (per device, once: `once` belongs to the list) and launches the one `form` names;
+// OV_ERR_UNSUPPORTED: none does.
+template <typename... A>
+struct OvKernelForm {
+    int form;
+    void (*kernel)(A...);
+};
+template <size_t N, typename... A>
+int ov_launch_form(const OvKernelForm<A...> (&forms)[N], OvPerDeviceOnce& once, int max_lds, int form, dim3 grid, dim3 block, size_t lds,
+                   hipStream_t st, const A&... args) {
+    const int dev = ov_current_device();
+    if (once.need(dev)) {
+        for (const OvKernelForm<A...>& f : forms) {
+            const hipError_t e = hipFuncSetAttribute((const void*)f.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
+            if (e != hipSuccess) return ov_hip(e);
+        }
+        once.mark(dev);
+    }
+    for (const OvKernelForm<A...>& f : forms)
+        if (f.form == form) {
+            hipLaunchKernelGGL(f.kernel, grid, block, lds, st, args...);
+            OV_LAUNCH_CHECK();
+            return OV_OK;
+        }
+    return OV_ERR_UNSUPPORTED;
+}
+
 __device__ __forceinline__ float bf16_bits_to_f32(unsigned short h) {
     return __uint_as_float(((unsigned int)h) << 16);
 }

@@ -65,6 +65,29 @@ def attention(qkv, B, L, H, hd=64, out=None):
     return out
 
 
+ATTN_FWD_KERNELS = ("persistent", "streaming", "generic")           # enum ov_attn_fwd_kernel
+ATTN_BWD_KERNELS = ("resident", "streaming")                        # enum ov_attn_bwd_kernel
+
+
+def attn_route(B, L, Hh, hd=64, prefix=None, out8=False, lse=False, ld_qkv=0, ld_out=0, cus=0):
+    """What attention.hip / attention_bwd.hip decide for this call, from the library itself (ov_attention_route; it launches nothing;
+    cus = 0: this device's CU count; under the OVHIP_ATTN_LONEKEY of THIS process).  prefix None: the unmasked entry points; ld_* 0:
+    dense rows.  The fields of ov_attention_route_t under their own names, the two kernels as names (kernel: forward, bwd: backward),
+    grid as a tuple, and the two forms as the tests' comments write them: form = persistent | streaming | generic resident | generic
+    chunked (+ " mask"), bwd_form = resident | resident saved | stream<2> | stream<3> (+ " mask").  A combination no entry point
+    admits raises (check)."""
+    r = _lib.AttentionRoute()
+    check(_lib.load().ov_attention_route(B, L, Hh, hd, ld_qkv, ld_out, -1 if prefix is None else prefix, int(out8), int(lse), cus,
+                                         C.addressof(r)), "ov_attention_route")
+    d = {n: getattr(r, n) for n, _ in r._fields_}
+    for n in ("deep", "out8", "lse", "mask", "resident", "bwd_saved", "bwd_mask", "keep_lse"):
+        d[n] = bool(d[n])
+    kernel, bwd = ATTN_FWD_KERNELS[r.fwd_kernel], ATTN_BWD_KERNELS[r.bwd_kernel]
+    form = kernel + ((" resident" if r.resident else " chunked") if kernel == "generic" else "") + (" mask" if r.mask else "")
+    bwd_form = ("resident" + (" saved" if r.bwd_saved else "")) if bwd == "resident" else f"stream<{r.ndh}>" + (" mask" if r.bwd_mask else "")
+    return SimpleNamespace(kernel=kernel, bwd=bwd, form=form, bwd_form=bwd_form, grid=(r.grid_x, r.grid_y), **d)
+
+
 def clip_loss(img, txt, all_img, all_txt, scale, label_offset):
     lib = _lib.load()
     b, e = img.shape

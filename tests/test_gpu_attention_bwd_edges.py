@@ -1,6 +1,6 @@
 """Attention backward at its edges, against an fp64 closed form with per-element bounds on dQ, dK and dV.
 
-attention_bwd.hip holds the resident kernel (head_dim 64, L <= 288; recomputing and saved-lse forms) and the two streaming kernels in
+attention_bwd.hip holds the resident kernel (head_dim 64, short sequences; recomputing and saved-lse forms) and the two streaming kernels in
 NDH = 2 / 3 form, each with and without the prefix mask.  The rule of the older backward tests, max|got - want| < 2e-2 max|want| +
 1e-3 per component, cannot see anything below 2 % of the largest gradient element: a key missing from the normaliser only, a wrong
 d slice of a small row, whole rows beside one large dout row.  These tests hold every element to
@@ -43,21 +43,27 @@ def check_ratios(tag, got, ref, bounds):
 # ------------------------------------------------------------------------------------------------------------------------------
 # A. every kernel and tail
 
-BWD_SHAPES = [
-    # resident (head_dim 64, L <= 288): one partial tile; a last tile of one row (33, 65, 257); full, nine waves
-    (1, 31, 2, 64), (2, 33, 2, 64), (1, 65, 3, 64), (2, 257, 4, 64), (1, 288, 1, 64),
+# shape -> what the library's route must name for it (hipops.attn_route(...).bwd_form)
+RES, S2, S3 = "resident", "stream<2>", "stream<3>"
+BWD_FORMS = {
+    # resident (head_dim 64, up to nine waves): one partial tile; a last tile of one row (33, 65, 257); full, nine waves
+    (1, 31, 2, 64): RES, (2, 33, 2, 64): RES, (1, 65, 3, 64): RES, (2, 257, 4, 64): RES, (1, 288, 1, 64): RES,
     # Stream<2>: the first streaming L (second chunk of 33 rows); a last chunk of one row (513, 2305); the batch offset
-    (1, 289, 2, 64), (1, 513, 2, 64), (2, 513, 2, 64), (1, 2305, 1, 64),
+    (1, 289, 2, 64): S2, (1, 513, 2, 64): S2, (2, 513, 2, 64): S2, (1, 2305, 1, 64): S2,
     # Stream<2>, head_dim < 64 at one chunk plus one row: the zero-fill paths (col < hd, 16 st + 8 h2 < hd, d0 < hd)
-    (1, 257, 2, 8), (1, 257, 2, 32), (1, 257, 2, 56),
+    (1, 257, 2, 8): S2, (1, 257, 2, 32): S2, (1, 257, 2, 56): S2,
     # Stream<3>: 730 a ragged last chunk; 769 at 96 no zero padding and a last chunk of one row
-    (1, 257, 2, 72), (1, 257, 2, 88), (1, 257, 2, 96), (1, 321, 2, 80), (3, 257, 2, 80), (1, 577, 2, 80), (1, 730, 2, 72),
-    (1, 769, 1, 96),
-]
+    (1, 257, 2, 72): S3, (1, 257, 2, 88): S3, (1, 257, 2, 96): S3, (1, 321, 2, 80): S3, (3, 257, 2, 80): S3, (1, 577, 2, 80): S3,
+    (1, 730, 2, 72): S3, (1, 769, 1, 96): S3,
+}
+BWD_SHAPES = list(BWD_FORMS)
+PITCH_FORMS = {(2, 257, 4, 64, None): "resident", (1, 513, 2, 64, None): "stream<2>", (2, 257, 3, 80, None): "stream<3>",
+               (2, 307, 2, 64, 179): "stream<2> mask"}
 
 
 @pytest.mark.parametrize("B,L,Hh,hd", BWD_SHAPES)
 def test_attention_backward_edges(B, L, Hh, hd):
+    assert H.attn_route(B, L, Hh, hd).bwd_form == BWD_FORMS[B, L, Hh, hd]      # the kernel the case is here for (a host call: no launch)
     qkv, dout, _ = spiked_bwd_case(B, L, Hh, hd, seed=L * 131 + hd)
     ref, bounds, out = reference(qkv, dout, B, L, Hh, hd)
     got = H.attention_backward(qkv.to(DEV), out, dout.to(DEV), B, L, Hh, hd)
@@ -88,6 +94,8 @@ def test_attention_backward_pitches_and_neighbours(B, L, Hh, hd, P):
     bitwise the dense call's and inside the bound."""
     D = Hh * hd
     lib = H._lib.load()
+    route = H.attn_route(B, L, Hh, hd, prefix=P, ld_qkv=3 * D + 64, ld_out=D + 64)
+    assert route.bwd_form == PITCH_FORMS[B, L, Hh, hd, P]
     if P is None:
         qkv, dout, _ = spiked_bwd_case(B, L, Hh, hd, seed=L + hd + 7)
         mask = None
@@ -108,7 +116,7 @@ def test_attention_backward_pitches_and_neighbours(B, L, Hh, hd, P):
     assert (qkv_p.stride(0), out_p.stride(0), dout_p.stride(0)) == (3 * D + 64, D + 64, D + 32)
     dq_w = torch.full((B * L, 3 * D + 64), PAD_SENTINEL, dtype=torch.bfloat16, device=DEV)
     buf = torch.full((nb + 256,), WS_SENTINEL, dtype=torch.uint8, device=DEV)
-    assert buf.data_ptr() % 16 == 0
+    assert buf.data_ptr() % 16 == 0 and nb == route.bwd_workspace_bytes
     got = call(qkv_p, out_p, dout_p, dqkv=dq_w[:, :3 * D], ws=buf[:nb])
     torch.cuda.synchronize()
     assert got.stride(0) == 3 * D + 64
@@ -126,6 +134,8 @@ def test_attention_backward_pitches_and_neighbours(B, L, Hh, hd, P):
 def test_attention_backward_saved_lse_within_bound(B, L, Hh, hd):
     """out and lse from ov_attention_lse (lse entries [L, KC) hold NaN: hipops.attention_lse), so |out - O| is what the forward's own
     enforced bound allows: eo = hipops.bound(O, P.|V|)."""
+    route = H.attn_route(B, L, Hh, hd, lse=True)
+    assert route.bwd_form == "resident saved" and route.keep_lse and route.form == "persistent" and route.lse
     qkv, dout, _ = spiked_bwd_case(B, L, Hh, hd, seed=L * 131 + hd + 1)
     ref = attn_grads_ref64(qkv, dout, B, L, Hh, hd)
     bounds = bwd_bound(ref, ref.q, ref.k, ref.v, ref.do, ref.scale, H.bound(ref.o, ref.pv))
@@ -143,6 +153,7 @@ PREFIX_BWD_SHAPES = [s for s in PREFIX_SHAPES if s[1] >= 4] + [(1, 513, 2, 64, 2
 
 @pytest.mark.parametrize("B,L,Hh,hd,P", PREFIX_BWD_SHAPES)
 def test_prefix_backward_edges(B, L, Hh, hd, P):
+    assert H.attn_route(B, L, Hh, hd, prefix=P).bwd_form == ("stream<2> mask" if hd == 64 else "stream<3> mask")    # always the streaming pair
     qkv = PR.boundary_spiked_qkv(B, L, Hh, hd, P, seed=L * 131 + hd + P)[0]
     dout = H.rnd(B * L, Hh * hd, seed=L * 131 + hd + P + 1).to(torch.bfloat16)
     ref, bounds, out = reference(qkv, dout, B, L, Hh, hd, PR.rule_mask(L, P))

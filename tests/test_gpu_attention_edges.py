@@ -2,7 +2,7 @@
 
 Every L = 32 k + 1 (patches + CLS) ends in a key tile -- or, in the streaming kernel, a 64-key chunk -- that holds ONE key; the three
 forward kernels fold that key in on the VALU (its own dot product, its own lazy rescale, its own rule that the two lane halves count it
-once).  The generic head_dim kernel stages 256-key chunks once the padded L exceeds 320.  A fixed absolute tolerance cannot see a
+once).  The generic head_dim kernel stages 256-key chunks where the route says chunked.  A fixed absolute tolerance cannot see a
 mistake in either: the output scale shrinks as L grows, and the lone key is one of L terms.  So these tests compare with
 
     |got - ref| <= 2^-8 |ref| + 2^-8 (P.|V|) + 1e-6          (ref = softmax(Q K^T * scale) V in fp64 on the bf16 inputs)
@@ -32,6 +32,7 @@ DEV = "cuda:0"
 
 
 def check_forward(qkv, B, L, Hh, hd, ratio_max=1.0, tag=""):
+    assert H.attn_route(B, L, Hh, hd).form == FWD_FORMS[B, L, Hh, hd]         # the kernel the case is here for (a host call: no launch)
     got = H.attention(qkv.to(DEV), B, L, Hh, hd).cpu()
     ref, pv = attn_ref64(qkv, B, L, Hh, hd)
     r = err_ratio(got, ref, pv)
@@ -40,20 +41,24 @@ def check_forward(qkv, B, L, Hh, hd, ratio_max=1.0, tag=""):
     return got
 
 
-FWD_SHAPES = [
-    # generic head_dim, chunked (padded L > 320): 256-key chunks, 8 waves per workgroup
-    (1, 321, 2, 72), (3, 321, 1, 80),           # first chunked L: last chunk of 65 keys (lone fold); 2nd workgroup: 3 of 8 waves
-    (1, 513, 2, 80), (1, 1025, 1, 72),          # last chunk of ONE key: a masked tile step, not the fold (nk = 1)
-    (1, 577, 3, 80), (2, 737, 1, 72),           # lone fold at nk = 65 / 225 (577: H/14 at 336 px)
-    (2, 730, 2, 72), (1, 768, 2, 80),           # ragged last chunk (218 keys: So400m at 27 x 27 patches); whole chunks only
+# shape -> what the library's route must name for it (hipops.attn_route(...).form)
+GC, GR, PERS, STRM = "generic chunked", "generic resident", "persistent", "streaming"
+FWD_FORMS = {
+    # generic head_dim, chunked (longer sequences): 256-key chunks, 8 waves per workgroup
+    (1, 321, 2, 72): GC, (3, 321, 1, 80): GC,           # first chunked L: last chunk of 65 keys (lone fold); 2nd workgroup: 3 of 8 waves
+    (1, 513, 2, 80): GC, (1, 1025, 1, 72): GC,          # last chunk of ONE key: a masked tile step, not the fold (nk = 1)
+    (1, 577, 3, 80): GC, (2, 737, 1, 72): GC,           # lone fold at nk = 65 / 225 (577: H/14 at 336 px)
+    (2, 730, 2, 72): GC, (1, 768, 2, 80): GC,           # ragged last chunk (218 keys: So400m at 27 x 27 patches); whole chunks only
     # generic head_dim: the other multiples of 8, resident (257) and chunked (577); 96 = no zero padding of the head in LDS
-    (1, 257, 2, 8), (1, 257, 2, 32), (1, 257, 2, 56), (1, 257, 2, 88), (1, 257, 2, 96),
-    (1, 577, 2, 8), (1, 577, 2, 32), (1, 577, 2, 56), (1, 577, 2, 88), (1, 577, 2, 96),
-    # head_dim 64, persistent kernel (padded L <= 320): an odd tile count folds the lone key, an even one keeps it in a tile step
-    (2, 65, 3, 64), (1, 193, 2, 64), (4, 257, 16, 64), (1, 97, 2, 64), (1, 289, 1, 64),
-    # head_dim 64, streaming kernel (padded L > 320): a last 64-key chunk of one key is folded in
-    (1, 321, 2, 64), (1, 385, 3, 64), (1, 577, 2, 64), (1, 2305, 2, 64),
-]
+    (1, 257, 2, 8): GR, (1, 257, 2, 32): GR, (1, 257, 2, 56): GR, (1, 257, 2, 88): GR, (1, 257, 2, 96): GR,
+    (1, 577, 2, 8): GC, (1, 577, 2, 32): GC, (1, 577, 2, 56): GC, (1, 577, 2, 88): GC, (1, 577, 2, 96): GC,
+    # head_dim 64, persistent kernel (short sequences): an odd tile count folds the lone key, an even one keeps it in a tile step
+    (2, 65, 3, 64): PERS, (1, 193, 2, 64): PERS, (4, 257, 16, 64): PERS, (1, 97, 2, 64): PERS, (1, 289, 1, 64): PERS,
+    # head_dim 64, streaming kernel (longer sequences): a last 64-key chunk of one key is folded in
+    (1, 321, 2, 64): STRM, (1, 385, 3, 64): STRM, (1, 577, 2, 64): STRM, (1, 2305, 2, 64): STRM,
+}
+FWD_SHAPES = list(FWD_FORMS)
+PITCH_FORMS = {(2, 257, 4, 64): "persistent", (1, 577, 2, 64): "streaming", (2, 257, 3, 80): "generic resident", (1, 577, 2, 72): "generic chunked"}
 
 
 @pytest.mark.parametrize("B,L,Hh,hd", FWD_SHAPES)
@@ -67,6 +72,7 @@ def test_attention_padded_row_pitches(B, L, Hh, hd):
     """The tower calls attention with row pitches 3D + 64 (qkv) and D + 64 (out): persistent, streaming, generic resident and
     generic chunked kernel.  The pad columns of qkv hold NaN (a read of them would show), those of out a sentinel that must survive."""
     D = Hh * hd
+    assert H.attn_route(B, L, Hh, hd, ld_qkv=3 * D + 64, ld_out=D + 64).form == PITCH_FORMS[B, L, Hh, hd]
     dense = rnd(B * L, 3 * D, seed=L + hd + 7).to(torch.bfloat16)
     qkv = torch.full((B * L, 3 * D + 64), float("nan"), dtype=torch.bfloat16)
     qkv[:, :3 * D] = dense
@@ -85,11 +91,12 @@ def test_attention_padded_row_pitches(B, L, Hh, hd):
 
 
 def test_attention_huge_row_pitch():
-    """head_dim 64, padded L <= 320, but the qkv image spans more than 2 GiB of rows (L * ld * 2 > 2^31, a C-API caller's pitch): the
+    """head_dim 64, a persistent-kernel L, but the qkv image spans more than 2 GiB of rows (L * ld * 2 > 2^31, a C-API caller's pitch): the
     persistent kernel's 32-bit row offsets cannot reach it, so the generic kernel (64-bit offsets) computes it.  Pad columns hold NaN."""
     B, L, Hh, hd, ld = 2, 257, 2, 64, 1 << 22
     D = Hh * hd
     assert L * ld * 2 > 2 ** 31
+    assert H.attn_route(B, L, Hh, hd).form == "persistent" and H.attn_route(B, L, Hh, hd, ld_qkv=ld).form == "generic resident"
     dense = rnd(B * L, 3 * D, seed=L + hd + 11).to(torch.bfloat16)
     qkv = torch.full((B * L, ld), float("nan"), dtype=torch.bfloat16, device=DEV)       # 4.3 GB
     qkv[:, :3 * D] = dense.to(DEV)
@@ -105,12 +112,14 @@ def test_attention_huge_row_pitch():
 # ------------------------------------------------------------------------------------------------------------------------------
 # C. the lone key as the row maximum, with the fold (default) and with the tile step (OVHIP_ATTN_LONEKEY=0, read once per process)
 
+LONE_FORMS = ["persistent", "streaming", "streaming", "generic chunked", "generic chunked"]          # of LONE_SPIKED, as the docstring says
 _CHILD = r"""
 import os, sys, torch
 sys.path.insert(0, os.environ["OV_ROOT"]); sys.path.insert(0, os.path.join(os.environ["OV_ROOT"], "tests"))
 import hipops as H
 cases = torch.load(sys.argv[1])
-torch.save([H.attention(q.cuda(), B, L, Hh, hd).cpu() for (q, B, L, Hh, hd) in cases], sys.argv[2])
+torch.save({"outs": [H.attention(q.cuda(), B, L, Hh, hd).cpu() for (q, B, L, Hh, hd) in cases],
+            "lone_valu": [H.attn_route(B, L, Hh, hd).lone_valu for (q, B, L, Hh, hd) in cases]}, sys.argv[2])
 """
 
 
@@ -118,7 +127,8 @@ def test_lone_key_as_the_row_max():
     """Spiked inputs (spiked_qkv): for one row per head the lone key is the row maximum by 4 (no rescale, p > 1) or 20 (rescale) log2
     units, at L = 257 (hd 64 persistent), 321 and 2305 (hd 64 streaming), 321 (hd 72) and 577 (hd 80, generic chunked).  The default
     fold and the tile step forced by OVHIP_ATTN_LONEKEY=0 (hd 64 kernels; the generic kernel always folds) are each within the bound,
-    and within twice the bound of each other."""
+    and within twice the bound of each other.  Each child records the lone_valu its library's route reports: 1 and 0 in the two runs
+    for the hd 64 kernels."""
     cases = []
     for (B, L, Hh, hd) in LONE_SPIKED:
         qkv, _ = spiked_qkv(B, L, Hh, hd, seed=L + hd)
@@ -134,7 +144,9 @@ def test_lone_key_as_the_row_max():
             subprocess.run([sys.executable, "-c", _CHILD, src, path], check=True, env=env, timeout=600)
             res[lk] = torch.load(path)
     ratios = []
-    for (qkv, B, L, Hh, hd), fold, tile in zip(cases, res["1"], res["0"]):
+    assert res["1"]["lone_valu"] == [1] * len(cases) and res["0"]["lone_valu"] == [int(hd != 64) for (_, _, _, _, hd) in cases]
+    assert [H.attn_route(B, L, Hh, hd).form for (_, B, L, Hh, hd) in cases] == LONE_FORMS
+    for (qkv, B, L, Hh, hd), fold, tile in zip(cases, res["1"]["outs"], res["0"]["outs"]):
         ref, pv = attn_ref64(qkv, B, L, Hh, hd)
         rf, rt = err_ratio(fold, ref, pv), err_ratio(tile, ref, pv)
         rx = float(((fold.double() - tile.double()).abs() / bound(ref, pv)).max())

@@ -186,7 +186,9 @@ def _block_digests(tag):
         for n in (M * D, 3 * M * D, M * D, M * D, M * D, M * D, M * F, M * F):
             p.append(base + 2 * off)
             off += n
-        lse = base + 2 * off if D // heads == 64 and L <= 288 else None
+        route = _lib.AttentionRoute()                                  # the lse is kept where the library says the backward reads it
+        check(lib.ov_attention_route(B, L, heads, D // heads, 0, 0, -1, 0, 0, 0, C.addressof(route)), "ov_attention_route")
+        lse = base + 2 * off if route.keep_lse else None
         sv = _lib.BlockSaved(qkv=p[1], attn_out=p[2], x1=p[3], fc_pre=p[6], ln1_out=p[4], ln2_out=p[5], fc_act=p[7], attn_lse=lse)
         run("block_saved", sv, None)
         # the attention half alone (feature visualisation)

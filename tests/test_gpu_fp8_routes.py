@@ -364,11 +364,13 @@ def test_gemm_fp8_amax_next_is_the_maximum_over_real_elements(case):
 # ---- ov_attention_fp8out ----
 
 
-def attn_kernel(L):
-    lp = -(-L // 32) * 32
-    if lp <= 320:
-        return ("persistent, <= 8 waves" if lp // 32 <= 8 else "persistent, 9+ waves"), lp - L
-    return "streaming", -(-L // 256) * 256 - L
+def attn_kernel(B, L, Hh, cus=0):
+    """(the kernel ov_attention_fp8out takes, as the library reports it; the query rows it pads the sequence with: to whole waves of
+    32 queries, in the streaming kernel to whole workgroups)."""
+    r = H.attn_route(B, L, Hh, 64, out8=True, cus=cus)
+    assert r.out8 and r.waves == (8 if r.kernel == "streaming" else -(-L // 32)), vars(r)
+    name = r.kernel if r.kernel == "streaming" else f"{r.kernel}, {'<= 8' if r.deep else '9+'} waves"
+    return name, -(-L // (32 * r.waves)) * 32 * r.waves - L
 
 
 def peaked_qkv(B, L, Hh):
@@ -399,7 +401,7 @@ def peaked_qkv(B, L, Hh):
 def test_attention_fp8out_amax_next_and_pitch(B, L, Hh, kernel, padded_rows):
     """amax_next = max |out| over the real rows (within 2^-20 relative + the softmax leak L e^-40 8), as a running maximum; the e4m3
     output within the element bound test_attention_fp8_output asserts; contiguous and with ld_out = H 64 + 16."""
-    assert attn_kernel(L) == (kernel, padded_rows)
+    assert attn_kernel(B, L, Hh) == (kernel, padded_rows)
     D = Hh * 64
     qkv = peaked_qkv(B, L, Hh)
     ref = H.attn_ref64(qkv, B, L, Hh, 64)[0]

@@ -21,6 +21,15 @@ SHAPES = [(2, 80, 2, 64, 0), (2, 307, 2, 64, 179), (2, 463, 2, 64, 335), (1, 257
           (1, 207, 2, 72, 79), (1, 463, 2, 72, 335), (1, 207, 2, 80, 79), (1, 463, 2, 80, 335)]
 
 
+def masked_route(B, L, Hh, hd, P, cus=0):
+    """What the library reports for the masked call, held to what DESIGN.md states for every masked shape: the generic forward
+    kernel's MASK form (head_dim 64 at its own width, the others padded to 96) and the masked streaming pair in the backward."""
+    r = H.attn_route(B, L, Hh, hd, prefix=P, cus=cus)
+    assert (r.kernel, r.mask, r.hdp) == ("generic", True, 64 if hd == 64 else 96), vars(r)
+    assert (r.bwd, r.bwd_mask, r.keep_lse) == ("streaming", True, False) and r.bwd_workspace_bytes > 0, vars(r)
+    return r
+
+
 def inputs(B, L, Hh, hd, P, seed=0):
     if L >= 4:
         return PR.boundary_spiked_qkv(B, L, Hh, hd, P, seed)[0]
@@ -29,6 +38,7 @@ def inputs(B, L, Hh, hd, P, seed=0):
 
 @pytest.mark.parametrize("B,L,Hh,hd,P", SHAPES)
 def test_prefix_forward_within_bound(B, L, Hh, hd, P):
+    masked_route(B, L, Hh, hd, P)
     qkv = inputs(B, L, Hh, hd, P)
     got = PR.attention_prefix(qkv.to(DEV), B, L, Hh, hd, P).cpu()
     ref, pv = PR.masked_attn_ref64(qkv, B, L, Hh, hd, PR.rule_mask(L, P))
@@ -39,6 +49,7 @@ def test_prefix_forward_within_bound(B, L, Hh, hd, P):
 
 def test_prefix_forward_padded_pitch():
     B, L, Hh, hd, P = 2, 307, 2, 64, 179
+    assert H.attn_route(B, L, Hh, hd, prefix=P, ld_qkv=3 * Hh * hd + 64, ld_out=Hh * hd + 32).form == masked_route(B, L, Hh, hd, P).form
     qkv = inputs(B, L, Hh, hd, P, seed=3)
     wide = torch.zeros(B * L, 3 * Hh * hd + 64, dtype=torch.bfloat16, device=DEV)
     wide[:, :3 * Hh * hd] = qkv.to(DEV)
@@ -53,6 +64,7 @@ def test_prefix_forward_padded_pitch():
 
 @pytest.mark.parametrize("B,L,Hh,hd", [(2, 257, 3, 64), (1, 463, 2, 64), (1, 207, 2, 72), (1, 463, 2, 80)])
 def test_prefix_equal_L_is_bitwise_the_unmasked_call(B, L, Hh, hd):
+    assert vars(H.attn_route(B, L, Hh, hd, prefix=L)) == vars(H.attn_route(B, L, Hh, hd)) and not H.attn_route(B, L, Hh, hd, prefix=L).mask
     qkv = H.rnd(B * L, 3 * Hh * hd, seed=5).to(torch.bfloat16).to(DEV)
     a = H.attention(qkv, B, L, Hh, hd)
     b = PR.attention_prefix(qkv, B, L, Hh, hd, L)
@@ -105,6 +117,7 @@ def test_backward_zero_structure_and_determinism(B, L, Hh, hd, P):
 @pytest.mark.parametrize("B,L,Hh,hd,P", SHAPES)
 def test_prefix_backward_vs_fp64_autograd(B, L, Hh, hd, P):
     D = Hh * hd
+    masked_route(B, L, Hh, hd, P)
     qkv = H.rnd(B * L, 3 * D, seed=11).to(torch.bfloat16)
     dout = H.rnd(B * L, D, seed=12).to(torch.bfloat16)
     out = PR.attention_prefix(qkv.to(DEV), B, L, Hh, hd, P)

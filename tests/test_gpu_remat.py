@@ -62,7 +62,7 @@ def _assert_same(a, b, what):
 
 # (width, layers, heads, gelu_tanh, B, L)
 TOWERS = {
-    "l14_4blk_b8_l257": (1024, 4, 16, False, 8, 257),      # head_dim 64, L <= 288: resident attention backward over the kept lse
+    "l14_4blk_b8_l257": (1024, 4, 16, False, 8, 257),      # head_dim 64, short L (the route's keep_lse): resident attention backward over the kept lse
     "hd80_b3_l257": (640, 3, 8, False, 3, 257),            # head_dim 80: streaming attention backward, no lse
     "text_b6_l80": (192, 4, 3, True, 6, 80),
 }

@@ -3,22 +3,23 @@
 Data-parallel InfoNCE: each rank holds ``[b, E]`` L2-normalised image and text embeddings; ONE RCCL all-gather of
 the packed ``[b, 2E]`` buffer (``torch.distributed`` backend "nccl" == RCCL over xGMI) yields the rank-ordered global
 sets (loss.py:52-61), then the fused HIP kernel computes the local ``[b, N]`` logit strips both ways with labels
-``i + b*rank`` (loss.py:93-94,108-110) without materialising them.
-
-Gradients: when a feature tensor or ``logit_scale`` requires grad, the loss is an autograd node whose backward is the
-HIP kernel behind ``ov_clip_loss_backward`` (d loss / d features and d loss / d logit_scale); ``openvision_amd.training``
-carries the gradient on through the towers.  The gathered-side terms are routed as
-``gather_features`` does (loss.py:19-63): own chunk only, or summed over ranks (reduce-scatter) with ``gather_with_grad``.
-``use_horovod`` is rejected (RCCL via torch.distributed is the only transport here).
+``i + b*rank`` (loss.py:93-94,108-110) without materialising them, reading the gathered buffer in place.
 
 ``MultiCaptionClipLoss`` is the InfoNCE OpenVision trains with: C caption sets per image (src/losses/common.py:120-189, C = 2), the
 mean over the sets of ``ClipLoss(image, text_c)`` in one fused forward and backward (``ov_clip_loss_multi*``) on one packed gather.
+``ClipLoss`` is its C = 1 case: both are ``_InfoNCELoss``, one forward launch and one autograd node.
 
 ``DistillClipLoss`` (loss.py:180-216) adds the cross entropy under a frozen teacher's softmax to ``ClipLoss``: two outputs from one fused
 forward and backward (``ov_distill_loss*``) on one packed gather of the student's and the teacher's rows.
 
 ``SigLipLoss`` (loss.py:307-414) is the pairwise sigmoid objective on the same transport: one all-gather of the text features,
 one fused strip kernel (``ov_siglip_loss``), and in the backward the gathered side summed over ranks.
+
+Gradients: when a feature tensor or ``logit_scale`` requires grad, a loss is an autograd node whose forward is the launch the
+no-grad call makes and whose backward is the matching HIP kernel; ``openvision_amd.training`` carries the gradient on through the
+towers.  What reaches a rank's own features from the gathered side is decided in ONE place, ``route_gradient``, the way
+``gather_features`` makes it flow in the reference (loss.py:19-63): own chunk only, or summed over ranks (reduce-scatter) with
+``gather_with_grad``.  ``use_horovod`` is rejected (RCCL via torch.distributed is the only transport here).
 """
 from __future__ import annotations
 
@@ -30,38 +31,25 @@ from torch import nn
 
 from . import _lib
 from ._lib import ptr, stream_ptr, check
+from .model import _Workspace
 
 
-_COMM_LOG = None      # diagnostics (bench.py --gpus N): a list that gather_features appends one (start, end) pair per collective to
+_COMM_LOG = None      # diagnostics (bench.py --gpus N): a list that every all-gather appends one (start, end) pair to
 
 
 def record_comm(log) -> None:
-    """Diagnostics: pass a list to have every all-gather of gather_features bracketed by a pair of timing marks appended to it --
+    """Diagnostics: pass a list to have every all-gather of this module bracketed by a pair of timing marks appended to it --
     ``torch.cuda.Event``s recorded on the current stream for device tensors (the collective is stream-ordered: the current stream waits
     for it), ``time.perf_counter()`` floats on the CPU (gloo rehearsal).  ``None`` turns it off.  Nothing is synchronised here."""
     global _COMM_LOG
     _COMM_LOG = log
 
 
-def gather_features(image_features: torch.Tensor, text_features: torch.Tensor, local_loss: bool = False,
-                    gather_with_grad: bool = False, rank: int = 0, world_size: int = 1, use_horovod: bool = False,
-                    group=None, force: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
-    """loss.py:19-63.  One all_gather_into_tensor of the packed [b, 2E] buffer instead of two list gathers;
-    the result is identical: rows in rank order (torch.cat(gathered, dim=0), loss.py:60-61)."""
-    if use_horovod:
-        raise NotImplementedError("horovod transport is not supported; use torch.distributed (RCCL)")
-    if world_size == 1 and not force:          # force: run the collective anyway (tests drive the RCCL path in a world of one)
-        return image_features, text_features
+def _all_gather_rows(x: torch.Tensor, world_size: int, group=None) -> torch.Tensor:
+    """[b, C] on every rank -> [world_size * b, C] in rank order: one all_gather_into_tensor, bracketed for record_comm.  Every
+    gather of this module ends here, so this is where the process group is asked for."""
     if not (dist.is_available() and dist.is_initialized()):
         raise RuntimeError("world_size > 1 needs an initialised torch.distributed process group (caller owns init)")
-    b, e = image_features.shape
-    packed = torch.cat([image_features.detach().float(), text_features.detach().float()], dim=1).contiguous()
-    out = _all_gather_rows(packed, world_size, group)
-    return out[:, :e].contiguous(), out[:, e:].contiguous()
-
-
-def _all_gather_rows(x: torch.Tensor, world_size: int, group=None) -> torch.Tensor:
-    """[b, C] on every rank -> [world_size * b, C] in rank order: one all_gather_into_tensor, bracketed for record_comm."""
     out = torch.empty(world_size * x.shape[0], x.shape[1], dtype=x.dtype, device=x.device)
     if _COMM_LOG is None:
         dist.all_gather_into_tensor(out, x, group=group)
@@ -79,153 +67,36 @@ def _all_gather_rows(x: torch.Tensor, world_size: int, group=None) -> torch.Tens
     return out
 
 
-class ClipLoss(nn.Module):
-    """Same constructor and call signature as the reference (loss.py:68-83,120-131)."""
-
-    def __init__(self, local_loss: bool = False, gather_with_grad: bool = False, cache_labels: bool = False,
-                 rank: int = 0, world_size: int = 1, use_horovod: bool = False, group=None):
-        super().__init__()
-        self.group = group          # process group of the gather / reduce-scatter (None = the default group, as the reference)
-        if use_horovod:
-            raise NotImplementedError("horovod transport is not supported; use torch.distributed (RCCL)")
-        self.local_loss, self.gather_with_grad, self.cache_labels = local_loss, gather_with_grad, cache_labels
-        self.rank, self.world_size, self.use_horovod = rank, world_size, use_horovod
-        self.always_collective = False   # tests only: take the world_size > 1 path (gather / reduce-scatter) in a world of one rank
-        self._ws: Optional[torch.Tensor] = None
-        self.last_terms: Optional[torch.Tensor] = None     # [4, b]: lse_img, diag_img, lse_txt, diag_txt
-
-    @staticmethod
-    def _device_scale(logit_scale, device) -> torch.Tensor:
-        """The logit multiplier as a 1-element fp32 DEVICE tensor.  It never visits the host (ovhip.h ABI 2): `float(logit_scale)`
-        would drain the stream after both towers before the loss could be enqueued."""
-        if isinstance(logit_scale, torch.Tensor):
-            if not logit_scale.is_cuda:
-                return logit_scale.detach().float().reshape(1).to(device, non_blocking=True)
-            return logit_scale.detach().float().reshape(1)
-        return torch.full((1,), float(logit_scale), dtype=torch.float32, device=device)
-
-    def _loss_strips(self, img, txt, all_img, all_txt, scale: torch.Tensor, label_offset: int) -> torch.Tensor:
-        if not img.is_cuda:
-            raise _lib.OvhipError("ClipLoss: features must live on an MI355X device (no CPU fallback)")
-        lib = _lib.load()
-        img, txt = img.detach().float().contiguous(), txt.detach().float().contiguous()
-        all_img, all_txt = all_img.detach().float().contiguous(), all_txt.detach().float().contiguous()
-        b, e = img.shape
-        n = all_img.shape[0]
-        nbytes = lib.ov_clip_loss_workspace_bytes(b, n)
-        if self._ws is None or self._ws.device != img.device or self._ws.numel() < nbytes:
-            self._ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=img.device)
-        out = torch.empty(1, dtype=torch.float32, device=img.device)
-        terms = torch.empty(4, b, dtype=torch.float32, device=img.device)
-        check(lib.ov_clip_loss(ptr(img), ptr(txt), ptr(all_img), ptr(all_txt), b, n, e, ptr(scale), int(label_offset),
-                               ptr(out), ptr(terms), ptr(self._ws), nbytes, stream_ptr()), "ov_clip_loss")
-        self.last_terms = terms
-        return out[0]
-
-    def forward(self, image_features, text_features, logit_scale, output_dict: bool = False):
-        needs_grad = torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad
-                                                     for t in (image_features, text_features, logit_scale))
-        if needs_grad:
-            if not isinstance(logit_scale, torch.Tensor):
-                logit_scale = torch.tensor(float(logit_scale), device=image_features.device)
-            loss = _ClipLossFn.apply(self, image_features, text_features, logit_scale)
-            return {"contrastive_loss": loss} if output_dict else loss
-        if not image_features.is_cuda:
-            raise _lib.OvhipError("ClipLoss: features must live on an MI355X device (no CPU fallback)")
-        scale = self._device_scale(logit_scale, image_features.device)
-        if self.world_size > 1 or self.always_collective:
-            all_img, all_txt = gather_features(image_features, text_features, self.local_loss, self.gather_with_grad,
-                                               self.rank, self.world_size, self.use_horovod, self.group, self.always_collective)
-            if self.local_loss:
-                loss = self._loss_strips(image_features, text_features, all_img, all_txt, scale,
-                                         image_features.shape[0] * self.rank)
-            else:   # global [N,N] logits on every rank (loss.py:111-113): the strips of the full set
-                loss = self._loss_strips(all_img, all_txt, all_img, all_txt, scale, 0)
-        else:
-            loss = self._loss_strips(image_features, text_features, image_features, text_features, scale, 0)
-        return {"contrastive_loss": loss} if output_dict else loss
+def _gather_packed(blocks, world_size: int, group=None):
+    """[b, w_k] column blocks -> (the [world_size * b, sum w_k] rows of ONE all-gather of their concatenation, in rank order, and
+    that buffer's column views, one per block: what the kernels read in place with ld = sum w_k)."""
+    packed = torch.cat([t.detach().float() for t in blocks], dim=1).contiguous()
+    out = _all_gather_rows(packed, world_size, group)
+    return out, out.split([t.shape[1] for t in blocks], dim=1)
 
 
-def _sum_over_ranks_own_chunk(full: torch.Tensor, b: int, rank: int, group=None) -> torch.Tensor:
-    """Backward of ``torch.distributed.nn.all_gather`` (loss.py:49-50): every rank's [N, 2E] gathered-side gradient summed,
-    this rank keeps rows [rank*b, (rank+1)*b).  One reduce-scatter on RCCL; gloo has none, so all-reduce + slice there."""
-    if dist.get_backend(group) == "nccl":
-        out = torch.empty(b, full.shape[1], dtype=full.dtype, device=full.device)
-        dist.reduce_scatter_tensor(out, full.contiguous(), group=group)
-        return out
-    full = full.contiguous()
-    dist.all_reduce(full, group=group)
-    return full[rank * b:(rank + 1) * b]
+def gather_features(image_features: torch.Tensor, text_features: torch.Tensor, local_loss: bool = False,
+                    gather_with_grad: bool = False, rank: int = 0, world_size: int = 1, use_horovod: bool = False,
+                    group=None, force: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """loss.py:19-63.  One all-gather of the packed [b, 2E] buffer instead of two list gathers;
+    the result is identical: rows in rank order (torch.cat(gathered, dim=0), loss.py:60-61)."""
+    if use_horovod:
+        raise NotImplementedError("horovod transport is not supported; use torch.distributed (RCCL)")
+    if world_size == 1 and not force:          # force: run the collective anyway (tests drive the RCCL path in a world of one)
+        return image_features, text_features
+    all_img, all_txt = _gather_packed([image_features, text_features], world_size, group)[1]
+    return all_img.contiguous(), all_txt.contiguous()
 
 
-class _ClipLossFn(torch.autograd.Function):
-    """ClipLoss as an autograd node.  forward = the fused strip kernel; backward = ov_clip_loss_backward plus the routing of
-    the gathered-side gradient that the reference gets from autograd through gather_features (loss.py:19-63)."""
-
-    @staticmethod
-    def forward(ctx, mod: "ClipLoss", image_features, text_features, logit_scale):
-        ws, rank = mod.world_size, mod.rank
-        img, txt = image_features.detach().float().contiguous(), text_features.detach().float().contiguous()
-        b = img.shape[0]
-        multi = ws > 1 or mod.always_collective
-        if multi:
-            all_img, all_txt = gather_features(img, txt, mod.local_loss, mod.gather_with_grad, rank, ws, mod.use_horovod, mod.group,
-                                               mod.always_collective)
-        else:
-            all_img, all_txt = img, txt
-        if multi and not mod.local_loss:
-            x_img, x_txt, off = all_img, all_txt, 0          # every rank evaluates the global loss (loss.py:111-113)
-        else:
-            x_img, x_txt, off = img, txt, b * rank
-        scale = mod._device_scale(logit_scale, img.device)
-        loss = mod._loss_strips(x_img, x_txt, all_img, all_txt, scale, off)
-        ctx.mod, ctx.off, ctx.b, ctx.multi = mod, off, b, multi
-        ctx.in_dtypes = (image_features.dtype, text_features.dtype, logit_scale.dtype)
-        ctx.save_for_backward(x_img, x_txt, all_img, all_txt, mod.last_terms, scale)
-        return loss
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        mod: "ClipLoss" = ctx.mod
-        x_img, x_txt, all_img, all_txt, terms, scale = ctx.saved_tensors
-        lib = _lib.load()
-        ws, rank, b = mod.world_size, mod.rank, ctx.b
-        bx, e = x_img.shape
-        n = all_img.shape[0]
-        # the gathered side carries gradient when it IS the local tensor (world_size 1), when the own chunk was put back
-        # (not local_loss, loss.py:57-59) or when the gather itself is differentiable (gather_with_grad)
-        single = not ctx.multi                      # world of one without the collectives: both sides are the same tensors
-        gathered_grad = single or not mod.local_loss or mod.gather_with_grad
-        d_img, d_txt = torch.empty_like(x_img), torch.empty_like(x_txt)
-        d_all = torch.empty(2, n, e, dtype=torch.float32, device=x_img.device) if gathered_grad else None
-        d_scale = torch.empty(1, dtype=torch.float32, device=x_img.device)
-        grad = grad_out.detach().float().reshape(1).contiguous()        # device scalar: no host round trip
-        nbytes = lib.ov_clip_loss_backward_workspace_bytes(bx, n)
-        wsb = torch.empty(nbytes + 256, dtype=torch.uint8, device=x_img.device)
-        check(lib.ov_clip_loss_backward(ptr(x_img), ptr(x_txt), ptr(all_img), ptr(all_txt), bx, n, e, ptr(scale), ctx.off, ptr(terms),
-                                        ptr(grad), ptr(d_img), ptr(d_txt), ptr(d_all[0]) if gathered_grad else None,
-                                        ptr(d_all[1]) if gathered_grad else None, ptr(d_scale), ptr(wsb), nbytes, stream_ptr()),
-              "ov_clip_loss_backward")
-        if single:
-            g_img, g_txt = d_img + d_all[0], d_txt + d_all[1]
-        elif mod.local_loss:
-            g_img, g_txt = d_img, d_txt
-            if mod.gather_with_grad:
-                own = _sum_over_ranks_own_chunk(torch.cat([d_all[0], d_all[1]], dim=1), b, rank, mod.group)
-                g_img, g_txt = g_img + own[:, :e], g_txt + own[:, e:]
-        else:
-            tot = torch.cat([d_img + d_all[0], d_txt + d_all[1]], dim=1)          # [N, 2E]: both sides are the global set
-            own = _sum_over_ranks_own_chunk(tot, b, rank, mod.group) if mod.gather_with_grad else tot[rank * b:(rank + 1) * b]
-            g_img, g_txt = own[:, :e], own[:, e:]
-        dt_i, dt_t, dt_s = ctx.in_dtypes
-        return None, g_img.to(dt_i), g_txt.to(dt_t), d_scale[0].to(dt_s)
+def _caption_blocks(image_features: torch.Tensor, text_features: torch.Tensor, num_captions: int):
+    b = image_features.shape[0]
+    return [image_features] + [text_features[c * b:(c + 1) * b] for c in range(num_captions)]
 
 
 def pack_caption_features(image_features: torch.Tensor, text_features: torch.Tensor, num_captions: int) -> torch.Tensor:
     """[b, E] image rows and the stacked [C b, E] text rows (set c in rows c b ...) -> one [b, (1 + C) E] buffer: the image in
     columns 0 ... E, set c in columns (1 + c) E ...  The layout ``ov_clip_loss_multi`` reads in place after the all-gather."""
-    b = image_features.shape[0]
-    return torch.cat([image_features] + [text_features[c * b:(c + 1) * b] for c in range(num_captions)], dim=1)
+    return torch.cat(_caption_blocks(image_features, text_features, num_captions), dim=1)
 
 
 def unpack_caption_features(packed: torch.Tensor, num_captions: int) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -236,11 +107,42 @@ def unpack_caption_features(packed: torch.Tensor, num_captions: int) -> Tuple[to
 
 def gather_caption_features(image_features: torch.Tensor, text_features: torch.Tensor, num_captions: int, world_size: int,
                             group=None) -> torch.Tensor:
-    """ONE all_gather_into_tensor of the packed rows -> [world_size * b, (1 + C) E] in rank order (seen by ``record_comm``)."""
-    if not (dist.is_available() and dist.is_initialized()):
-        raise RuntimeError("world_size > 1 needs an initialised torch.distributed process group (caller owns init)")
-    packed = pack_caption_features(image_features.detach().float(), text_features.detach().float(), num_captions).contiguous()
-    return _all_gather_rows(packed, world_size, group)
+    """ONE all-gather of the packed rows -> [world_size * b, (1 + C) E] in rank order (seen by ``record_comm``)."""
+    return _gather_packed(_caption_blocks(image_features, text_features, num_captions), world_size, group)[0]
+
+
+def pack_distill_features(image_features: torch.Tensor, text_features: torch.Tensor, dist_image_features: torch.Tensor,
+                          dist_text_features: torch.Tensor) -> torch.Tensor:
+    """Student rows [b, E] (image, text) and teacher rows [b, Et] (image, text) -> one [b, 2E + 2Et] buffer: student image in columns
+    0 ... E, student text in E ... 2E, teacher image in 2E ... 2E + Et, teacher text behind it.  The layout ``ov_distill_loss`` reads
+    in place after the all-gather (ld = ldt = 2E + 2Et)."""
+    return torch.cat([image_features, text_features, dist_image_features, dist_text_features], dim=1)
+
+
+def unpack_distill_features(packed: torch.Tensor, embed_dim: int):
+    """Inverse of ``pack_distill_features`` on [n, 2E + 2Et] rows, E = ``embed_dim``: four column views (student image, student text,
+    teacher image, teacher text)."""
+    e = embed_dim
+    et = (packed.shape[1] - 2 * e) // 2
+    return packed[:, :e], packed[:, e:2 * e], packed[:, 2 * e:2 * e + et], packed[:, 2 * e + et:]
+
+
+def gather_distill_features(image_features, text_features, dist_image_features, dist_text_features, world_size: int,
+                            group=None) -> torch.Tensor:
+    """ONE all-gather of the packed rows -> [world_size * b, 2E + 2Et] in rank order (seen by ``record_comm``)."""
+    return _gather_packed([image_features, text_features, dist_image_features, dist_text_features], world_size, group)[0]
+
+
+def _sum_over_ranks_own_chunk(full: torch.Tensor, b: int, rank: int, group=None) -> torch.Tensor:
+    """Backward of ``torch.distributed.nn.all_gather`` (loss.py:49-50): every rank's [N, W] gathered-side gradient summed,
+    this rank keeps rows [rank*b, (rank+1)*b).  One reduce-scatter on RCCL; gloo has none, so all-reduce + slice there."""
+    if dist.get_backend(group) == "nccl":
+        out = torch.empty(b, full.shape[1], dtype=full.dtype, device=full.device)
+        dist.reduce_scatter_tensor(out, full.contiguous(), group=group)
+        return out
+    full = full.contiguous()
+    dist.all_reduce(full, group=group)
+    return full[rank * b:(rank + 1) * b]
 
 
 def route_packed_gradient(full: torch.Tensor, b: int, rank: int, gather_with_grad: bool, group=None) -> torch.Tensor:
@@ -252,7 +154,188 @@ def route_packed_gradient(full: torch.Tensor, b: int, rank: int, gather_with_gra
     return full[rank * b:(rank + 1) * b]
 
 
-class MultiCaptionClipLoss(nn.Module):
+def route_gradient(d_local: torch.Tensor, d_gathered: Optional[torch.Tensor], b: int, rank: int, collective: bool, local_loss: bool,
+                   gather_with_grad: bool, group=None) -> torch.Tensor:
+    """The gradient of this rank's own features, packed [b, W], from the two sides of an InfoNCE-type backward: ``d_local`` is the
+    packed gradient of the rows this rank evaluated (its own [b, W], or all [N, W] for the global loss), ``d_gathered`` the packed
+    [N, W] gradient of the gathered rows (None where a detached gather under ``local_loss`` carries none).  As autograd through
+    ``gather_features`` (loss.py:19-63):
+      * no collective: both sides are the same tensors, local + gathered (any common layout);
+      * ``local_loss``: local (as it stands, in whatever layout), plus with ``gather_with_grad`` every rank's gathered side summed,
+        own rows kept (one reduce-scatter);
+      * global loss: both sides are the global set; own rows of local + gathered, summed over ranks under ``gather_with_grad``.
+    Works on CPU tensors over gloo."""
+    assert (d_gathered is None) == (collective and local_loss and not gather_with_grad), "gathered side: given iff it carries gradient"
+    if not collective:
+        return d_local + d_gathered
+    if local_loss:
+        return d_local + _sum_over_ranks_own_chunk(d_gathered, b, rank, group) if gather_with_grad else d_local
+    return route_packed_gradient(d_local + d_gathered, b, rank, gather_with_grad, group)
+
+
+def gathered_gradient_buffer(n: int, e: int, num_captions: int, packed: bool, device):
+    """Where a backward kernel writes the gradient of the n gathered rows, and how it addresses it: (buffer, pointer to the image
+    part, pointer to caption set 0, ldg, gset_stride), in floats; element k of row j lies ldg j + k behind its part's pointer and
+    set c a further c gset_stride.  Not ``packed``: the features' own layout [(1 + C) n, E], image rows first, then set c in rows
+    (1 + c) n ... (a world of one adds it to the local side as it stands).  ``packed``: [n, (1 + C) E], the layout of the gather, for
+    one reduce-scatter.  DistillClipLoss's student half is the C = 1 case."""
+    c = num_captions
+    if packed:
+        buf = torch.empty(n, (1 + c) * e, dtype=torch.float32, device=device)
+        return buf, ptr(buf), ptr(buf[:, e:]), (1 + c) * e, e
+    buf = torch.empty((1 + c) * n, e, dtype=torch.float32, device=device)
+    return buf, ptr(buf), ptr(buf[n:]), e, n * e
+
+
+def _collective(mod) -> bool:
+    return mod.world_size > 1 or mod.always_collective
+
+
+def _needs_grad(*inputs) -> bool:
+    return torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in inputs)
+
+
+def _device_scalar(x, device) -> torch.Tensor:
+    """A logit multiplier or bias as a 1-element fp32 DEVICE tensor.  It never visits the host (ovhip.h ABI 2): `float(logit_scale)`
+    would drain the stream after both towers before the loss could be enqueued."""
+    if isinstance(x, torch.Tensor):
+        if not x.is_cuda:
+            return x.detach().float().reshape(1).to(device, non_blocking=True)
+        return x.detach().float().reshape(1)
+    return torch.full((1,), float(x), dtype=torch.float32, device=device)
+
+
+def _as_node_input(x, device):
+    """A float handed to an autograd node becomes a 0-d tensor: the node returns a gradient of its dtype.  None stays None."""
+    return x if x is None or isinstance(x, torch.Tensor) else torch.tensor(float(x), device=device)
+
+
+def _backward_buffers(mod, collective: bool, bx: int, n: int, e: int, num_captions: int, device):
+    """The feature-gradient outputs of an InfoNCE-type backward: (d_local [(1 + C) bx, E], the local side in the features' own
+    layout; d_gathered or None; (image pointer, text pointer, ldg, gset_stride) of d_gathered for the kernel).  The gathered side
+    carries gradient when it IS the local tensor (no collective), when the own chunk was put back (not local_loss, loss.py:57-59)
+    or when the gather itself is differentiable (gather_with_grad)."""
+    d_local = torch.empty((1 + num_captions) * bx, e, dtype=torch.float32, device=device)
+    if collective and mod.local_loss and not mod.gather_with_grad:
+        return d_local, None, (None, None, 0, 0)
+    d_gathered, *addr = gathered_gradient_buffer(n, e, num_captions, collective, device)
+    return d_local, d_gathered, addr
+
+
+def _own_gradients(mod, collective: bool, d_local: torch.Tensor, d_gathered: Optional[torch.Tensor], b: int, num_captions: int):
+    """(d image_features [b, E], d text_features [C b, E]) of this rank from the buffers of ``_backward_buffers`` after the kernel.
+    Where nothing is exchanged (no collective, or no gathered side) the rule is applied in the features' own layout; otherwise the
+    local side is packed like the gather first: one copy, and the results are column views or a copy of the packed rows."""
+    if not collective or d_gathered is None:
+        own = route_gradient(d_local, d_gathered, b, mod.rank, collective, mod.local_loss, mod.gather_with_grad, mod.group)
+        return own[:b], own[b:]
+    bx = d_local.shape[0] // (1 + num_captions)
+    own = route_gradient(pack_caption_features(d_local[:bx], d_local[bx:], num_captions), d_gathered, b, mod.rank, True,
+                         mod.local_loss, mod.gather_with_grad, mod.group)
+    return unpack_caption_features(own, num_captions)
+
+
+class _InfoNCELoss(nn.Module):
+    """``ClipLoss`` and ``MultiCaptionClipLoss``: InfoNCE over ``num_captions`` caption sets, the reference's constructor
+    (loss.py:68-83) plus ``group``.  One forward launch (``ov_clip_loss_multi``), one autograd node (``_InfoNCEFn``)."""
+
+    num_captions = 1
+
+    def __init__(self, local_loss: bool = False, gather_with_grad: bool = False, cache_labels: bool = False,
+                 rank: int = 0, world_size: int = 1, use_horovod: bool = False, group=None):
+        super().__init__()
+        if use_horovod:
+            raise NotImplementedError("horovod transport is not supported; use torch.distributed (RCCL)")
+        self.group = group          # process group of the gather / reduce-scatter (None = the default group, as the reference)
+        self.local_loss, self.gather_with_grad, self.cache_labels = local_loss, gather_with_grad, cache_labels
+        self.rank, self.world_size, self.use_horovod = rank, world_size, use_horovod
+        self.always_collective = False   # tests only: take the world_size > 1 path (gather / reduce-scatter) in a world of one rank
+        self._ws, self._ws_bwd = _Workspace(), _Workspace()
+        self.last_terms: Optional[torch.Tensor] = None     # [4 C, b]: per set lse_img, diag_img, lse_txt, diag_txt
+
+    def _check(self, image_features, text_features):
+        name = type(self).__name__
+        if image_features.dim() != 2 or text_features.dim() != 2 or image_features.shape[1] != text_features.shape[1] \
+                or text_features.shape[0] != self.num_captions * image_features.shape[0]:
+            raise ValueError(f"{name}: text_features must be [{self.num_captions} * b, E] for image_features [b, E], "
+                             f"got {tuple(text_features.shape)} for {tuple(image_features.shape)}")
+        if not (image_features.is_cuda and text_features.is_cuda):
+            raise _lib.OvhipError(f"{name}: features must live on an MI355X device (no CPU fallback)")
+
+    def _operands(self, img: torch.Tensor, txt: torch.Tensor):
+        """(x_img, x_txt, gathered operand, its text view, ld, set_stride, label offset) for this rank."""
+        c, b, e = self.num_captions, img.shape[0], img.shape[1]
+        if not _collective(self):
+            return img, txt, img, txt, e, b * e, 0
+        packed = gather_caption_features(img, txt, c, self.world_size, self.group)
+        if self.local_loss:
+            x_img, x_txt, off = img, txt, b * self.rank
+        else:                       # the global loss on every rank (loss.py:111-113): the local rows are the gathered rows
+            x_img, x_txt = (t.contiguous() for t in unpack_caption_features(packed, c))
+            off = 0
+        return x_img, x_txt, packed, packed[:, e:], (1 + c) * e, e, off
+
+    def _launch(self, image_features, text_features, logit_scale):
+        """The forward, with or without grad: (loss, what the backward needs as tensors, (ld, set_stride, label offset))."""
+        lib = _lib.load()
+        img, txt = image_features.detach().float().contiguous(), text_features.detach().float().contiguous()
+        scale = _device_scalar(logit_scale, img.device)
+        x_img, x_txt, all_img, all_txt, ld, ss, off = self._operands(img, txt)
+        (b, e), n, c = x_img.shape, all_img.shape[0], self.num_captions
+        nbytes = lib.ov_clip_loss_multi_workspace_bytes(b, n, c)
+        out = torch.empty(1, dtype=torch.float32, device=img.device)
+        terms = torch.empty(4 * c, b, dtype=torch.float32, device=img.device)
+        check(lib.ov_clip_loss_multi(ptr(x_img), ptr(x_txt), ptr(all_img), ptr(all_txt), ld, ss, b, n, e, c, ptr(scale), int(off),
+                                     ptr(out), ptr(terms), ptr(self._ws.get(nbytes, img.device)), nbytes, stream_ptr()),
+              "ov_clip_loss_multi")
+        self.last_terms = terms
+        return out[0], (x_img, x_txt, all_img, all_txt, terms, scale), (ld, ss, off)
+
+    def forward(self, image_features, text_features, logit_scale, output_dict: bool = False):
+        self._check(image_features, text_features)
+        if _needs_grad(image_features, text_features, logit_scale):
+            loss = _InfoNCEFn.apply(self, image_features, text_features, _as_node_input(logit_scale, image_features.device))
+        else:
+            loss = self._launch(image_features, text_features, logit_scale)[0]
+        return {"contrastive_loss": loss} if output_dict else loss
+
+
+class _InfoNCEFn(torch.autograd.Function):
+    """``_InfoNCELoss`` as an autograd node.  forward = the module's launch; backward = ov_clip_loss_multi_backward, the gathered
+    side written in the layout ``route_gradient`` wants it in."""
+
+    @staticmethod
+    def forward(ctx, mod: _InfoNCELoss, image_features, text_features, logit_scale):
+        loss, saved, ctx.lay = mod._launch(image_features, text_features, logit_scale)
+        ctx.mod, ctx.b, ctx.collective = mod, image_features.shape[0], _collective(mod)
+        ctx.in_dtypes = (image_features.dtype, text_features.dtype, logit_scale.dtype)
+        ctx.save_for_backward(*saved)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        mod: _InfoNCELoss = ctx.mod
+        x_img, x_txt, all_img, all_txt, terms, scale = ctx.saved_tensors
+        lib = _lib.load()
+        (bx, e), n, c, dev = x_img.shape, all_img.shape[0], mod.num_captions, x_img.device
+        ld, ss, off = ctx.lay
+        d_local, d_all, (p_ai, p_at, ldg, gss) = _backward_buffers(mod, ctx.collective, bx, n, e, c, dev)
+        d_scale = torch.empty(1, dtype=torch.float32, device=dev)
+        grad = grad_out.detach().float().reshape(1).contiguous()        # device scalar: no host round trip
+        nbytes = lib.ov_clip_loss_multi_backward_workspace_bytes(bx, n, c)
+        check(lib.ov_clip_loss_multi_backward(ptr(x_img), ptr(x_txt), ptr(all_img), ptr(all_txt), ld, ss, bx, n, e, c, ptr(scale), off,
+                                              ptr(terms), ptr(grad), ptr(d_local), ptr(d_local[bx:]), p_ai, p_at, ldg, gss, ptr(d_scale),
+                                              ptr(mod._ws_bwd.get(nbytes, dev)), nbytes, stream_ptr()), "ov_clip_loss_multi_backward")
+        g_img, g_txt = _own_gradients(mod, ctx.collective, d_local, d_all, ctx.b, c)
+        dt_i, dt_t, dt_s = ctx.in_dtypes
+        return None, g_img.to(dt_i), g_txt.to(dt_t), d_scale[0].to(dt_s)
+
+
+class ClipLoss(_InfoNCELoss):
+    """Same constructor and call signature as the reference (loss.py:68-83,120-131).  ``last_terms`` is [4, b]."""
+
+
+class MultiCaptionClipLoss(_InfoNCELoss):
     """InfoNCE with ``num_captions`` caption sets per image: what OpenVision trains with (``bidirectional_contrastive_loss``,
     src/losses/common.py:120-189, two sets, ``local_loss=True``).  ``text_features`` holds the sets stacked ``[C b, E]`` (set c in
     rows ``c b ...``, the reference's ``ztxt[:half] / ztxt[half:]``); the loss is the mean over the sets of ``ClipLoss(image, text_c)``,
@@ -263,128 +346,10 @@ class MultiCaptionClipLoss(nn.Module):
 
     def __init__(self, num_captions: int = 2, local_loss: bool = False, gather_with_grad: bool = False, cache_labels: bool = False,
                  rank: int = 0, world_size: int = 1, use_horovod: bool = False, group=None):
-        super().__init__()
-        if use_horovod:
-            raise NotImplementedError("horovod transport is not supported; use torch.distributed (RCCL)")
+        super().__init__(local_loss, gather_with_grad, cache_labels, rank, world_size, use_horovod, group)
         if not 1 <= int(num_captions) <= 4:
             raise ValueError("num_captions must be 1 ... 4")
         self.num_captions = int(num_captions)
-        self.group = group
-        self.local_loss, self.gather_with_grad, self.cache_labels = local_loss, gather_with_grad, cache_labels
-        self.rank, self.world_size, self.use_horovod = rank, world_size, use_horovod
-        self.always_collective = False   # tests only: take the world_size > 1 path (gather / reduce-scatter) in a world of one rank
-        self._ws: Optional[torch.Tensor] = None
-        self.last_terms: Optional[torch.Tensor] = None     # [4 C, b]: per set lse_img, diag_img, lse_txt, diag_txt
-
-    def _operands(self, img: torch.Tensor, txt: torch.Tensor):
-        """(x_img, x_txt, gathered operand, its image / text views, ld, set_stride, label offset) for this rank."""
-        c, b, e = self.num_captions, img.shape[0], img.shape[1]
-        if not (self.world_size > 1 or self.always_collective):
-            return img, txt, img, txt, e, b * e, 0
-        packed = gather_caption_features(img, txt, c, self.world_size, self.group)
-        if self.local_loss:
-            x_img, x_txt, off = img, txt, b * self.rank
-        else:                       # the global loss on every rank (loss.py:111-113): the local rows are the gathered rows
-            x_img, x_txt = (t.contiguous() for t in unpack_caption_features(packed, c))
-            off = 0
-        return x_img, x_txt, packed, packed[:, e:], (1 + c) * e, e, off
-
-    def _loss_strips(self, x_img, x_txt, all_img, all_txt, ld: int, set_stride: int, scale: torch.Tensor, off: int) -> torch.Tensor:
-        lib = _lib.load()
-        b, e = x_img.shape
-        n = all_img.shape[0]
-        nbytes = lib.ov_clip_loss_multi_workspace_bytes(b, n, self.num_captions)
-        if self._ws is None or self._ws.device != x_img.device or self._ws.numel() < nbytes:
-            self._ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=x_img.device)
-        out = torch.empty(1, dtype=torch.float32, device=x_img.device)
-        terms = torch.empty(4 * self.num_captions, b, dtype=torch.float32, device=x_img.device)
-        check(lib.ov_clip_loss_multi(ptr(x_img), ptr(x_txt), ptr(all_img), ptr(all_txt), ld, set_stride, b, n, e, self.num_captions,
-                                     ptr(scale), int(off), ptr(out), ptr(terms), ptr(self._ws), nbytes, stream_ptr()),
-              "ov_clip_loss_multi")
-        self.last_terms = terms
-        return out[0]
-
-    def _check(self, image_features, text_features):
-        if image_features.dim() != 2 or text_features.dim() != 2 or image_features.shape[1] != text_features.shape[1] \
-                or text_features.shape[0] != self.num_captions * image_features.shape[0]:
-            raise ValueError(f"MultiCaptionClipLoss: text_features must be [{self.num_captions} * b, E] for image_features [b, E], "
-                             f"got {tuple(text_features.shape)} for {tuple(image_features.shape)}")
-        if not (image_features.is_cuda and text_features.is_cuda):
-            raise _lib.OvhipError("MultiCaptionClipLoss: features must live on an MI355X device (no CPU fallback)")
-
-    def forward(self, image_features, text_features, logit_scale, output_dict: bool = False):
-        self._check(image_features, text_features)
-        needs_grad = torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad
-                                                     for t in (image_features, text_features, logit_scale))
-        if needs_grad:
-            if not isinstance(logit_scale, torch.Tensor):
-                logit_scale = torch.tensor(float(logit_scale), device=image_features.device)
-            loss = _MultiCaptionClipLossFn.apply(self, image_features, text_features, logit_scale)
-        else:
-            img, txt = image_features.detach().float().contiguous(), text_features.detach().float().contiguous()
-            scale = ClipLoss._device_scale(logit_scale, img.device)
-            x_img, x_txt, all_img, all_txt, ld, ss, off = self._operands(img, txt)
-            loss = self._loss_strips(x_img, x_txt, all_img, all_txt, ld, ss, scale, off)
-        return {"contrastive_loss": loss} if output_dict else loss
-
-
-class _MultiCaptionClipLossFn(torch.autograd.Function):
-    """MultiCaptionClipLoss as an autograd node.  forward = ov_clip_loss_multi on the packed gather; backward =
-    ov_clip_loss_multi_backward, the gathered side written as one packed [N, (1 + C) E] gradient and routed as ``_ClipLossFn``
-    routes its two halves (own chunk, or one reduce-scatter with gather_with_grad)."""
-
-    @staticmethod
-    def forward(ctx, mod: "MultiCaptionClipLoss", image_features, text_features, logit_scale):
-        img, txt = image_features.detach().float().contiguous(), text_features.detach().float().contiguous()
-        scale = ClipLoss._device_scale(logit_scale, img.device)
-        x_img, x_txt, all_img, all_txt, ld, ss, off = mod._operands(img, txt)
-        loss = mod._loss_strips(x_img, x_txt, all_img, all_txt, ld, ss, scale, off)
-        ctx.mod, ctx.off, ctx.b, ctx.lay = mod, off, img.shape[0], (ld, ss)
-        ctx.multi = mod.world_size > 1 or mod.always_collective
-        ctx.in_dtypes = (image_features.dtype, text_features.dtype, logit_scale.dtype)
-        ctx.save_for_backward(x_img, x_txt, all_img, all_txt, mod.last_terms, scale)
-        return loss
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        mod: "MultiCaptionClipLoss" = ctx.mod
-        x_img, x_txt, all_img, all_txt, terms, scale = ctx.saved_tensors
-        lib = _lib.load()
-        c, rank, b = mod.num_captions, mod.rank, ctx.b
-        bx, e = x_img.shape
-        n = all_img.shape[0]
-        ld, ss = ctx.lay
-        single = not ctx.multi                      # world of one without the collectives: both sides are the same tensors
-        gathered_grad = single or not mod.local_loss or mod.gather_with_grad
-        dev = x_img.device
-        d_img, d_txt = torch.empty_like(x_img), torch.empty_like(x_txt)
-        d_scale = torch.empty(1, dtype=torch.float32, device=dev)
-        if not gathered_grad:
-            d_all, p_ai, p_at, ldg, gss = None, None, None, 0, 0
-        elif single:                                # laid out as the features themselves: [b, E] and [C b, E]
-            d_all = torch.empty((1 + c) * n, e, dtype=torch.float32, device=dev)
-            p_ai, p_at, ldg, gss = ptr(d_all), ptr(d_all[n:]), e, n * e
-        else:                                       # packed as the gather: [N, (1 + C) E]
-            d_all = torch.empty(n, (1 + c) * e, dtype=torch.float32, device=dev)
-            p_ai, p_at, ldg, gss = ptr(d_all), ptr(d_all[:, e:]), (1 + c) * e, e
-        grad = grad_out.detach().float().reshape(1).contiguous()        # device scalar: no host round trip
-        nbytes = lib.ov_clip_loss_multi_backward_workspace_bytes(bx, n, c)
-        wsb = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
-        check(lib.ov_clip_loss_multi_backward(ptr(x_img), ptr(x_txt), ptr(all_img), ptr(all_txt), ld, ss, bx, n, e, c, ptr(scale),
-                                              ctx.off, ptr(terms), ptr(grad), ptr(d_img), ptr(d_txt), p_ai, p_at, ldg, gss,
-                                              ptr(d_scale), ptr(wsb), nbytes, stream_ptr()), "ov_clip_loss_multi_backward")
-        if single:
-            g_img, g_txt = d_img + d_all[:n], d_txt + d_all[n:]
-        elif mod.local_loss:
-            g_img, g_txt = d_img, d_txt
-            if mod.gather_with_grad:
-                o_img, o_txt = unpack_caption_features(route_packed_gradient(d_all, b, rank, True, mod.group), c)
-                g_img, g_txt = g_img + o_img, g_txt + o_txt
-        else:                                       # both sides are the global set: [N, (1 + C) E] in all
-            tot = d_all + pack_caption_features(d_img, d_txt, c)
-            g_img, g_txt = unpack_caption_features(route_packed_gradient(tot, b, rank, mod.gather_with_grad, mod.group), c)
-        dt_i, dt_t, dt_s = ctx.in_dtypes
-        return None, g_img.to(dt_i), g_txt.to(dt_t), d_scale[0].to(dt_s)
 
 
 class SigLipLoss(nn.Module):
@@ -408,72 +373,51 @@ class SigLipLoss(nn.Module):
         self.cache_labels, self.rank, self.world_size, self.bidir, self.use_horovod = cache_labels, rank, world_size, bidir, use_horovod
         self.group = group
         self.always_collective = False   # tests only: take the world_size > 1 path (gather / reduce-scatter) in a world of one rank
-        self._ws: Optional[torch.Tensor] = None
+        self._ws, self._ws_bwd = _Workspace(), _Workspace()
 
-    def _gather_text(self, text: torch.Tensor) -> torch.Tensor:
-        if self.world_size == 1 and not self.always_collective:
-            return text
-        if not (dist.is_available() and dist.is_initialized()):
-            raise RuntimeError("world_size > 1 needs an initialised torch.distributed process group (caller owns init)")
-        return _all_gather_rows(text, self.world_size, self.group)
-
-    def _loss_strip(self, img, all_txt, scale: torch.Tensor, bias: Optional[torch.Tensor], label_offset: int) -> torch.Tensor:
+    def _launch(self, image_features, text_features, logit_scale, logit_bias):
+        """The forward, with or without grad: (loss, what the backward needs as tensors, label offset)."""
         lib = _lib.load()
-        b, e = img.shape
-        n = all_txt.shape[0]
+        img, txt = image_features.detach().float().contiguous(), text_features.detach().float().contiguous()
+        all_txt = _all_gather_rows(txt, self.world_size, self.group) if _collective(self) else txt
+        scale = _device_scalar(logit_scale, img.device)
+        bias = _device_scalar(logit_bias, img.device) if logit_bias is not None else None
+        (b, e), n, off = img.shape, all_txt.shape[0], img.shape[0] * self.rank
         nbytes = lib.ov_siglip_loss_workspace_bytes(b, n)
-        if self._ws is None or self._ws.device != img.device or self._ws.numel() < nbytes:
-            self._ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=img.device)
         out = torch.empty(1, dtype=torch.float32, device=img.device)
-        check(lib.ov_siglip_loss(ptr(img), ptr(all_txt), b, n, e, ptr(scale), ptr(bias) if bias is not None else None,
-                                 int(label_offset), ptr(out), ptr(self._ws), nbytes, stream_ptr()), "ov_siglip_loss")
-        return out[0]
+        check(lib.ov_siglip_loss(ptr(img), ptr(all_txt), b, n, e, ptr(scale), ptr(bias) if bias is not None else None, int(off),
+                                 ptr(out), ptr(self._ws.get(nbytes, img.device)), nbytes, stream_ptr()), "ov_siglip_loss")
+        return out[0], (img, all_txt, scale, bias), off
 
     def forward(self, image_features, text_features, logit_scale, logit_bias=None, output_dict: bool = False):
         if not (image_features.is_cuda and text_features.is_cuda):
             raise _lib.OvhipError("SigLipLoss: features must live on an MI355X device (no CPU fallback)")
-        needs_grad = torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad
-                                                     for t in (image_features, text_features, logit_scale, logit_bias))
-        if needs_grad:
+        if _needs_grad(image_features, text_features, logit_scale, logit_bias):
             dev = image_features.device
-            if not isinstance(logit_scale, torch.Tensor):
-                logit_scale = torch.tensor(float(logit_scale), device=dev)
-            if logit_bias is not None and not isinstance(logit_bias, torch.Tensor):
-                logit_bias = torch.tensor(float(logit_bias), device=dev)
-            loss = _SigLipLossFn.apply(self, image_features, text_features, logit_scale, logit_bias)
+            loss = _SigLipLossFn.apply(self, image_features, text_features, _as_node_input(logit_scale, dev),
+                                       _as_node_input(logit_bias, dev))
         else:
-            img = image_features.detach().float().contiguous()
-            all_txt = self._gather_text(text_features.detach().float().contiguous())
-            scale = ClipLoss._device_scale(logit_scale, img.device)
-            bias = ClipLoss._device_scale(logit_bias, img.device) if logit_bias is not None else None
-            loss = self._loss_strip(img, all_txt, scale, bias, img.shape[0] * self.rank)
+            loss = self._launch(image_features, text_features, logit_scale, logit_bias)[0]
         return {"contrastive_loss": loss} if output_dict else loss
 
 
 class _SigLipLossFn(torch.autograd.Function):
-    """SigLipLoss as an autograd node.  forward = the fused strip kernel; backward = ov_siglip_loss_backward, then the gathered
+    """SigLipLoss as an autograd node.  forward = the module's launch; backward = ov_siglip_loss_backward, then the gathered
     side's gradient summed over ranks (own chunk kept): what the reference's NeighbourExchange backward returns to each block's
     owner (loss.py:273-280)."""
 
     @staticmethod
-    def forward(ctx, mod: "SigLipLoss", image_features, text_features, logit_scale, logit_bias):
-        img, txt = image_features.detach().float().contiguous(), text_features.detach().float().contiguous()
-        b = img.shape[0]
-        ctx.multi = mod.world_size > 1 or mod.always_collective
-        all_txt = mod._gather_text(txt)
-        off = b * mod.rank
-        scale = ClipLoss._device_scale(logit_scale, img.device)
-        bias = ClipLoss._device_scale(logit_bias, img.device) if logit_bias is not None else None
-        loss = mod._loss_strip(img, all_txt, scale, bias, off)
-        ctx.mod, ctx.off, ctx.has_bias = mod, off, bias is not None
+    def forward(ctx, mod: SigLipLoss, image_features, text_features, logit_scale, logit_bias):
+        loss, saved, ctx.off = mod._launch(image_features, text_features, logit_scale, logit_bias)
+        ctx.mod, ctx.collective, ctx.has_bias = mod, _collective(mod), logit_bias is not None
         ctx.in_dtypes = (image_features.dtype, text_features.dtype, logit_scale.dtype,
                          logit_bias.dtype if logit_bias is not None else None)
-        ctx.save_for_backward(img, all_txt, scale, bias)
+        ctx.save_for_backward(*saved)
         return loss
 
     @staticmethod
     def backward(ctx, grad_out):
-        mod: "SigLipLoss" = ctx.mod
+        mod: SigLipLoss = ctx.mod
         img, all_txt, scale, bias = ctx.saved_tensors
         lib = _lib.load()
         b, e = img.shape
@@ -482,40 +426,14 @@ class _SigLipLossFn(torch.autograd.Function):
         d_sc = torch.empty(2, dtype=torch.float32, device=img.device)            # d scale, d bias
         grad = grad_out.detach().float().reshape(1).contiguous()                  # device scalar: no host round trip
         nbytes = lib.ov_siglip_loss_backward_workspace_bytes(b, n)
-        wsb = torch.empty(nbytes + 256, dtype=torch.uint8, device=img.device)
         check(lib.ov_siglip_loss_backward(ptr(img), ptr(all_txt), b, n, e, ptr(scale), ptr(bias) if ctx.has_bias else None, ctx.off,
                                           ptr(grad), ptr(d_img), ptr(d_all), ptr(d_sc[0:]), ptr(d_sc[1:]) if ctx.has_bias else None,
-                                          ptr(wsb), nbytes, stream_ptr()), "ov_siglip_loss_backward")
-        # text appears on the gathered side only: at world_size 1 its gradient IS d_all (nothing to add)
-        d_txt = _sum_over_ranks_own_chunk(d_all, b, mod.rank, mod.group) if ctx.multi else d_all
+                                          ptr(mod._ws_bwd.get(nbytes, img.device)), nbytes, stream_ptr()), "ov_siglip_loss_backward")
+        # text appears on the gathered side only: at world_size 1 its gradient IS d_all (nothing to add); under a collective the
+        # gather is always differentiable here
+        d_txt = _sum_over_ranks_own_chunk(d_all, b, mod.rank, mod.group) if ctx.collective else d_all
         dt_i, dt_t, dt_s, dt_b = ctx.in_dtypes
         return (None, d_img.to(dt_i), d_txt.to(dt_t), d_sc[0].to(dt_s), d_sc[1].to(dt_b) if ctx.has_bias else None)
-
-
-def pack_distill_features(image_features: torch.Tensor, text_features: torch.Tensor, dist_image_features: torch.Tensor,
-                          dist_text_features: torch.Tensor) -> torch.Tensor:
-    """Student rows [b, E] (image, text) and teacher rows [b, Et] (image, text) -> one [b, 2E + 2Et] buffer: student image in columns
-    0 ... E, student text in E ... 2E, teacher image in 2E ... 2E + Et, teacher text behind it.  The layout ``ov_distill_loss`` reads
-    in place after the all-gather (ld = ldt = 2E + 2Et)."""
-    return torch.cat([image_features, text_features, dist_image_features, dist_text_features], dim=1)
-
-
-def unpack_distill_features(packed: torch.Tensor, embed_dim: int):
-    """Inverse of ``pack_distill_features`` on [n, 2E + 2Et] rows, E = ``embed_dim``: four column views (student image, student text,
-    teacher image, teacher text)."""
-    e = embed_dim
-    et = (packed.shape[1] - 2 * e) // 2
-    return packed[:, :e], packed[:, e:2 * e], packed[:, 2 * e:2 * e + et], packed[:, 2 * e + et:]
-
-
-def gather_distill_features(image_features, text_features, dist_image_features, dist_text_features, world_size: int,
-                            group=None) -> torch.Tensor:
-    """ONE all_gather_into_tensor of the packed rows -> [world_size * b, 2E + 2Et] in rank order (seen by ``record_comm``)."""
-    if not (dist.is_available() and dist.is_initialized()):
-        raise RuntimeError("world_size > 1 needs an initialised torch.distributed process group (caller owns init)")
-    packed = pack_distill_features(*(t.detach().float() for t in (image_features, text_features, dist_image_features,
-                                                                  dist_text_features))).contiguous()
-    return _all_gather_rows(packed, world_size, group)
 
 
 class DistillClipLoss(ClipLoss):
@@ -523,17 +441,14 @@ class DistillClipLoss(ClipLoss):
     call takes the student's features and multiplier, then the teacher's, and returns ``(contrastive_loss, distill_loss)``: the
     student's InfoNCE and the cross entropy of the student's log-softmax under the teacher's softmax, both ways.  One fused forward
     and one backward (``ov_distill_loss*``) on ONE all-gather of the packed ``[b, 2E + 2Et]`` rows read in place; the teacher's
-    embedding width may differ from the student's.  The student's gathered-side gradient is routed as ``ClipLoss`` routes it (own
-    chunk, or one reduce-scatter of the packed ``[N, 2E]`` gradient under ``gather_with_grad``); the teacher's share of the gather is
-    never exchanged back.
+    embedding width may differ from the student's.  The student's gathered-side gradient is routed as ``ClipLoss`` routes it
+    (``route_gradient`` on the packed ``[N, 2E]`` student half); the teacher's share of the gather is never exchanged back.
 
     The teacher is frozen HERE: the reference would differentiate through teacher tensors that require grad, this build computes no
     such gradient and therefore refuses them (``ValueError``) instead of returning none silently.
 
     ``last_terms`` is the forward's [12, b] block: the student's lse_img, diag_img, lse_txt, diag_txt, then the teacher's lse and the
     cross sum of the image strip and of the text strip, then the low parts of the four lse (ovhip.h)."""
-
-    _ws_bwd: Optional[torch.Tensor] = None      # the backward's workspace, kept like the forward's ``_ws``
 
     def _check(self, image_features, text_features, dist_image_features, dist_text_features, dist_logit_scale):
         s, t = (image_features, text_features), (dist_image_features, dist_text_features)
@@ -550,7 +465,7 @@ class DistillClipLoss(ClipLoss):
         """(local student rows, local teacher rows, the four gathered operands, ld, ldt, label offset) for this rank."""
         b, e = img.shape
         et = t_img.shape[1]
-        if not (self.world_size > 1 or self.always_collective):
+        if not _collective(self):
             return (img, txt), (t_img, t_txt), (img, txt, t_img, t_txt), e, et, 0
         packed = gather_distill_features(img, txt, t_img, t_txt, self.world_size, self.group)
         views = unpack_distill_features(packed, e)
@@ -560,99 +475,67 @@ class DistillClipLoss(ClipLoss):
             x, u, off = (views[0].contiguous(), views[1].contiguous()), (views[2].contiguous(), views[3].contiguous()), 0
         return x, u, views, packed.shape[1], packed.shape[1], off
 
-    def _distill_strips(self, x, u, g, ld: int, ldt: int, scale: torch.Tensor, t_scale: torch.Tensor, off: int):
+    def _launch(self, image_features, text_features, logit_scale, dist_image_features, dist_text_features, dist_logit_scale):
+        """The forward, with or without grad: ((contrastive, distill), what the backward needs as tensors, (ld, ldt, label offset))."""
         lib = _lib.load()
-        b, e = x[0].shape
-        et, n, dev = u[0].shape[1], g[0].shape[0], x[0].device
+        img, txt, t_img, t_txt = (t.detach().float().contiguous() for t in (image_features, text_features, dist_image_features,
+                                                                             dist_text_features))
+        dev = img.device
+        scale, t_scale = _device_scalar(logit_scale, dev), _device_scalar(dist_logit_scale, dev)
+        x, u, g, ld, ldt, off = self._operands(img, txt, t_img, t_txt)
+        (b, e), et, n = x[0].shape, u[0].shape[1], g[0].shape[0]
         nbytes = lib.ov_distill_loss_workspace_bytes(b, n)
-        if self._ws is None or self._ws.device != dev or self._ws.numel() < nbytes:
-            self._ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
         out = torch.empty(2, dtype=torch.float32, device=dev)
         terms = torch.empty(12, b, dtype=torch.float32, device=dev)
         check(lib.ov_distill_loss(ptr(x[0]), ptr(x[1]), ptr(g[0]), ptr(g[1]), ld, ptr(u[0]), ptr(u[1]), ptr(g[2]), ptr(g[3]), ldt, b, n, e,
-                                  et, ptr(scale), ptr(t_scale), int(off), ptr(out[0:]), ptr(out[1:]), ptr(terms), ptr(self._ws), nbytes,
-                                  stream_ptr()), "ov_distill_loss")
+                                  et, ptr(scale), ptr(t_scale), int(off), ptr(out[0:]), ptr(out[1:]), ptr(terms),
+                                  ptr(self._ws.get(nbytes, dev)), nbytes, stream_ptr()), "ov_distill_loss")
         self.last_terms = terms
-        return out[0], out[1]
+        return (out[0], out[1]), (*x, *u, *g, terms, scale, t_scale), (ld, ldt, off)
 
     def forward(self, image_features, text_features, logit_scale, dist_image_features, dist_text_features, dist_logit_scale,
                 output_dict: bool = False):
         self._check(image_features, text_features, dist_image_features, dist_text_features, dist_logit_scale)
-        needs_grad = torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad
-                                                     for t in (image_features, text_features, logit_scale))
-        if needs_grad:
-            if not isinstance(logit_scale, torch.Tensor):
-                logit_scale = torch.tensor(float(logit_scale), device=image_features.device)
-            c, d = _DistillClipLossFn.apply(self, image_features, text_features, logit_scale, dist_image_features, dist_text_features,
-                                            dist_logit_scale)
+        args = (image_features, text_features, logit_scale, dist_image_features, dist_text_features, dist_logit_scale)
+        if _needs_grad(image_features, text_features, logit_scale):
+            c, d = _DistillClipLossFn.apply(self, image_features, text_features, _as_node_input(logit_scale, image_features.device),
+                                            *args[3:])
         else:
-            img, txt, t_img, t_txt = (t.detach().float().contiguous() for t in (image_features, text_features, dist_image_features,
-                                                                                 dist_text_features))
-            scale, t_scale = self._device_scale(logit_scale, img.device), self._device_scale(dist_logit_scale, img.device)
-            x, u, g, ld, ldt, off = self._operands(img, txt, t_img, t_txt)
-            c, d = self._distill_strips(x, u, g, ld, ldt, scale, t_scale, off)
+            c, d = self._launch(*args)[0]
         return {"contrastive_loss": c, "distill_loss": d} if output_dict else (c, d)
 
 
 class _DistillClipLossFn(torch.autograd.Function):
-    """DistillClipLoss as an autograd node with two outputs.  forward = ov_distill_loss on the packed gather; backward =
-    ov_distill_loss_backward with both upstream gradients as device scalars, the student's gathered side written as one packed
-    [N, 2E] gradient and routed as ``_ClipLossFn`` routes its two halves.  The teacher inputs get None."""
+    """DistillClipLoss as an autograd node with two outputs.  forward = the module's launch; backward = ov_distill_loss_backward
+    with both upstream gradients as device scalars, the student's gathered side written and routed as ``_InfoNCEFn`` does at
+    C = 1.  The teacher inputs get None."""
 
     @staticmethod
-    def forward(ctx, mod: "DistillClipLoss", image_features, text_features, logit_scale, dist_image_features, dist_text_features,
+    def forward(ctx, mod: DistillClipLoss, image_features, text_features, logit_scale, dist_image_features, dist_text_features,
                 dist_logit_scale):
-        img, txt, t_img, t_txt = (t.detach().float().contiguous() for t in (image_features, text_features, dist_image_features,
-                                                                             dist_text_features))
-        scale, t_scale = mod._device_scale(logit_scale, img.device), mod._device_scale(dist_logit_scale, img.device)
-        x, u, g, ld, ldt, off = mod._operands(img, txt, t_img, t_txt)
-        c, d = mod._distill_strips(x, u, g, ld, ldt, scale, t_scale, off)
-        ctx.mod, ctx.off, ctx.b, ctx.lay = mod, off, img.shape[0], (ld, ldt)
-        ctx.multi = mod.world_size > 1 or mod.always_collective
+        (c, d), saved, ctx.lay = mod._launch(image_features, text_features, logit_scale, dist_image_features, dist_text_features,
+                                             dist_logit_scale)
+        ctx.mod, ctx.b, ctx.collective = mod, image_features.shape[0], _collective(mod)
         ctx.in_dtypes = (image_features.dtype, text_features.dtype, logit_scale.dtype)
-        ctx.save_for_backward(*x, *u, *g, mod.last_terms, scale, t_scale)
+        ctx.save_for_backward(*saved)
         return c, d
 
     @staticmethod
     def backward(ctx, grad_c, grad_d):
-        mod: "DistillClipLoss" = ctx.mod
+        mod: DistillClipLoss = ctx.mod
         x_img, x_txt, u_img, u_txt, y_img, y_txt, v_img, v_txt, terms, scale, t_scale = ctx.saved_tensors
         lib = _lib.load()
-        rank, b = mod.rank, ctx.b
-        bx, e = x_img.shape
-        et, n, dev = u_img.shape[1], y_img.shape[0], x_img.device
-        ld, ldt = ctx.lay
-        single = not ctx.multi                      # world of one without the collectives: both sides are the same tensors
-        gathered_grad = single or not mod.local_loss or mod.gather_with_grad
-        d_img, d_txt = torch.empty_like(x_img), torch.empty_like(x_txt)
+        (bx, e), et, n, dev = x_img.shape, u_img.shape[1], y_img.shape[0], x_img.device
+        ld, ldt, off = ctx.lay
+        d_local, d_all, (p_ai, p_at, ldg, _) = _backward_buffers(mod, ctx.collective, bx, n, e, 1, dev)
         d_scale = torch.empty(1, dtype=torch.float32, device=dev)
-        if not gathered_grad:
-            d_all, p_ai, p_at, ldg = None, None, None, 0
-        elif single:                                # laid out as the features themselves: two [b, E] arrays
-            d_all = torch.empty(2, n, e, dtype=torch.float32, device=dev)
-            p_ai, p_at, ldg = ptr(d_all[0]), ptr(d_all[1]), e
-        else:                                       # packed [N, 2E]: the student's half of the gather's layout, for one reduce-scatter
-            d_all = torch.empty(n, 2 * e, dtype=torch.float32, device=dev)
-            p_ai, p_at, ldg = ptr(d_all), ptr(d_all[:, e:]), 2 * e
         g_c = grad_c.detach().float().reshape(1).contiguous()           # device scalars: no host round trip
         g_d = grad_d.detach().float().reshape(1).contiguous()
         nbytes = lib.ov_distill_loss_backward_workspace_bytes(bx, n)
-        wsb = mod._ws_bwd
-        if wsb is None or wsb.device != dev or wsb.numel() < nbytes:
-            wsb = mod._ws_bwd = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
         check(lib.ov_distill_loss_backward(ptr(x_img), ptr(x_txt), ptr(y_img), ptr(y_txt), ld, ptr(u_img), ptr(u_txt), ptr(v_img),
-                                           ptr(v_txt), ldt, bx, n, e, et, ptr(scale), ptr(t_scale), ctx.off, ptr(terms), ptr(g_c), ptr(g_d),
-                                           ptr(d_img), ptr(d_txt), p_ai, p_at, ldg, ptr(d_scale), ptr(wsb), nbytes, stream_ptr()),
-              "ov_distill_loss_backward")
-        if single:
-            g_img, g_txt = d_img + d_all[0], d_txt + d_all[1]
-        elif mod.local_loss:
-            g_img, g_txt = d_img, d_txt
-            if mod.gather_with_grad:
-                own = route_packed_gradient(d_all, b, rank, True, mod.group)
-                g_img, g_txt = g_img + own[:, :e], g_txt + own[:, e:]
-        else:                                       # both sides are the global set: [N, 2E] in all
-            own = route_packed_gradient(d_all + torch.cat([d_img, d_txt], dim=1), b, rank, mod.gather_with_grad, mod.group)
-            g_img, g_txt = own[:, :e], own[:, e:]
+                                           ptr(v_txt), ldt, bx, n, e, et, ptr(scale), ptr(t_scale), off, ptr(terms), ptr(g_c), ptr(g_d),
+                                           ptr(d_local), ptr(d_local[bx:]), p_ai, p_at, ldg, ptr(d_scale),
+                                           ptr(mod._ws_bwd.get(nbytes, dev)), nbytes, stream_ptr()), "ov_distill_loss_backward")
+        g_img, g_txt = _own_gradients(mod, ctx.collective, d_local, d_all, ctx.b, 1)
         dt_i, dt_t, dt_s = ctx.in_dtypes
         return None, g_img.to(dt_i), g_txt.to(dt_t), d_scale[0].to(dt_s), None, None, None

@@ -791,6 +791,10 @@ typedef struct {      /* VisionTransformer front/back ends (OpenVision: no ln_pr
 } ov_vision_head;
 
 size_t ov_vision_workspace_bytes(const ov_tower* t, const ov_vision_head* h, int B);
+/* The workspace of ov_vision_embed (K = 0) or of ov_vision_embed_keep with K kept patches (1 <= K <= G); 0 for bad arguments. */
+size_t ov_vision_embed_workspace_bytes(const ov_tower* t, const ov_vision_head* h, int B, int K);
+/* The workspace of ov_vision_head_forward[_tokens]; 0 for bad arguments. */
+size_t ov_vision_head_workspace_bytes(const ov_tower* t, const ov_vision_head* h, int B);
 /* image [B,3,S,S] -> tokens x[B*L, D] bf16 (patch embed + cls + pos); x caller-provided. */
 int ov_vision_embed(const ov_tower* t, const ov_vision_head* h, const void* image, int img_dtype, int B,
                     ov_bf16* x, void* workspace, size_t workspace_bytes, ov_stream_t stream);

@@ -222,6 +222,8 @@ SIGNATURES = {
     "ov_tower_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "ov_tower_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "ov_vision_workspace_bytes": (c_size_t, [c_void_p, C.POINTER(VisionHead), c_int]),
+    "ov_vision_embed_workspace_bytes": (c_size_t, [c_void_p, C.POINTER(VisionHead), c_int, c_int]),
+    "ov_vision_head_workspace_bytes": (c_size_t, [c_void_p, C.POINTER(VisionHead), c_int]),
     "ov_vision_embed": (c_int, [c_void_p, C.POINTER(VisionHead), c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t,
                                 c_void_p]),
     "ov_vision_head_forward": (c_int, [c_void_p, C.POINTER(VisionHead), c_void_p, c_int, c_void_p, c_int, c_void_p,

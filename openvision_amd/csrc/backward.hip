@@ -10,31 +10,6 @@
 // rows are two-stage with a fixed order (no atomics): results are deterministic.
 #include "common.h"
 
-extern "C" int ov_gemm(const ov_bf16* A, int64_t lda, const ov_bf16* W, int64_t ldw, const float* bias, ov_bf16* C, int64_t ldc,
-                       int64_t M, int N, int K, int epilogue, const ov_bf16* R, int64_t ldr, int out_group, int resid_mod,
-                       int resid_off, ov_stream_t stream);
-extern "C" int ov_layernorm(const void* x, int x_dtype, int64_t ldx, const float* gamma, const float* beta, void* y, int y_dtype,
-                            int64_t ldy, int64_t rows, int D, float eps, ov_stream_t stream);
-extern "C" int ov_attention(const ov_bf16* qkv, int64_t ld_qkv, ov_bf16* out, int64_t ld_out, int B, int L, int H, int hd, float scale,
-                            ov_stream_t stream);
-extern "C" int ov_attention_backward(const ov_bf16* qkv, int64_t ld_qkv, const ov_bf16* out, int64_t ld_out, const ov_bf16* dout,
-                                     int64_t ld_dout, ov_bf16* dqkv, int64_t ld_dqkv, int B, int L, int H, int hd, float scale,
-                                     void* workspace, size_t workspace_bytes, ov_stream_t stream);
-extern "C" int ov_attention_backward_saved(const ov_bf16* qkv, int64_t ld_qkv, const ov_bf16* out, int64_t ld_out, const ov_bf16* dout,
-                                           int64_t ld_dout, ov_bf16* dqkv, int64_t ld_dqkv, const float* lse, int B, int L, int H, int hd,
-                                           float scale, void* workspace, size_t workspace_bytes, ov_stream_t stream);
-extern "C" size_t ov_attention_backward_workspace_bytes(int B, int L, int H, int hd);
-extern "C" int ov_attention_prefix(const ov_bf16* qkv, int64_t ld_qkv, ov_bf16* out, int64_t ld_out, int B, int L, int H, int hd, float scale,
-                                   int prefix, ov_stream_t stream);
-extern "C" size_t ov_attention_prefix_backward_workspace_bytes(int B, int L, int H, int hd);
-extern "C" int ov_attention_prefix_backward(const ov_bf16* qkv, int64_t ld_qkv, const ov_bf16* out, int64_t ld_out, const ov_bf16* dout,
-                                            int64_t ld_dout, ov_bf16* dqkv, int64_t ld_dqkv, int B, int L, int H, int hd, float scale,
-                                            int prefix, void* workspace, size_t workspace_bytes, ov_stream_t stream);
-extern "C" int ov_gemm_batched(const ov_bf16* A, int64_t lda, int64_t stride_a, const ov_bf16* W, int64_t ldw, int64_t stride_w,
-                               ov_bf16* C, int64_t ldc, int64_t stride_c, int64_t M, int N, int K, int batch, ov_stream_t stream);
-extern "C" int ov_gemm_tn_batched(const ov_bf16* P, int64_t ldp, const ov_bf16* Q, int64_t ldq, ov_bf16* C, int64_t ldc, int64_t stride_c,
-                                  int64_t Mc, int NI, int NJ, int64_t chunk, int batch, float* psum, ov_stream_t stream);
-
 namespace {
 
 // out[c, r] = in[r, c] for r < R, 0 for R <= r < Rpad (Rpad = R rounded up to 64: the GEMM's K granule).  64 x 64 tiles.

@@ -27,6 +27,21 @@ static inline int ov_hip(hipError_t e) { return e == hipSuccess ? OV_OK : OV_ERR
 // decides where the training forward keeps it and the backward passes it on.
 static inline bool ov_attn_bwd_resident(int hd, int L) { return hd == 64 && L <= 288; }
 
+// ---- host functions that cross files without being part of the C ABI (ovhip.h holds the public ones) --------------------------------
+// backward.hip, one block over its kept activations (arguments checked by the caller), both the block's one backward chain:
+// block_backward_partial with the requested pairs of g (block_grad_pairs: bit k = pair k, -1 for a half-NULL or misaligned pair) and
+// dx unless NULL; block_backward_input with no pair, dx alone, in a smaller workspace.
+int block_grad_pairs(const ov_block_grads* g);
+int block_backward_partial(const ov_tower_cfg* cfg, const ov_block_weights* w, const ov_bf16* x, const ov_block_saved* s, const ov_bf16* dy,
+                           ov_bf16* dx, const ov_block_grads* g, int prefix, int B, int L, void* workspace, size_t workspace_bytes,
+                           ov_stream_t stream);
+size_t block_backward_input_workspace_bytes(const ov_tower_cfg* cfg, int B, int L);
+int block_backward_input(const ov_tower_cfg* cfg, const ov_block_weights* w, const ov_bf16* x, const ov_block_saved* s, const ov_bf16* dy,
+                         ov_bf16* dx, int prefix, int B, int L, void* workspace, ov_stream_t stream);
+// embed.hip: ov_im2col_patches_keep with the kept rows' positional-embedding rows gathered into posk in the same launch
+int ov_im2col_patches_keep_pos(const void* image, int img_dtype, const int* keep, ov_bf16* out, int B, int S, int P, int K, int Kpad,
+                               const ov_bf16* pos, ov_bf16* posk, int D, int* err_flag, ov_stream_t stream);
+
 // ---- per-device host state: function attributes (hipFuncSetAttribute) and device properties belong to ONE device; a process
 // may drive several (one host thread each).  Device ids beyond OV_MAX_DEVICES - 1 share the last slot's "not yet done" answer
 // (the attribute is then set on every launch: correct, just slower).

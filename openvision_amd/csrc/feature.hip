@@ -14,16 +14,6 @@
 // ov_block_attn_backward_input (backward.hip) reads.
 #include "common.h"
 
-extern "C" int ov_gemm(const ov_bf16* A, int64_t lda, const ov_bf16* W, int64_t ldw, const float* bias, ov_bf16* C, int64_t ldc,
-                       int64_t M, int N, int K, int epilogue, const ov_bf16* R, int64_t ldr, int out_group, int resid_mod,
-                       int resid_off, ov_stream_t stream);
-extern "C" int ov_layernorm(const void* x, int x_dtype, int64_t ldx, const float* gamma, const float* beta, void* y, int y_dtype,
-                            int64_t ldy, int64_t rows, int D, float eps, ov_stream_t stream);
-extern "C" int ov_attention(const ov_bf16* qkv, int64_t ld_qkv, ov_bf16* out, int64_t ld_out, int B, int L, int H, int hd, float scale,
-                            ov_stream_t stream);
-extern "C" int ov_attention_lse(const ov_bf16* qkv, int64_t ld_qkv, ov_bf16* out, int64_t ld_out, float* lse, int B, int L, int H, int hd,
-                                float scale, ov_stream_t stream);
-
 namespace {
 
 __device__ __forceinline__ float gelu_exact(float a, bool tanh_form) {

@@ -10,7 +10,15 @@
 // Per block, seven launches on the caller's stream (all asynchronous, nothing allocated):
 //   LN1 -> QKV GEMM(+bias) -> attention -> out-proj GEMM(+bias +residual, in place)
 //   LN2 -> FC GEMM(+bias +GELU) -> proj GEMM(+bias +residual, in place)
-// Workspace per tower call: h [M, D] | big [M, max(3D, mlp_pad)]  (qkv and the MLP hidden alias).
+// An encoder's last block computes only what its pooling head reads: the image tower (avg pool) stops after c_fc and pools in front of
+// c_proj (encode_image); the text tower stops after the attention, and the text tail is run_block from past the attention on B rows.
+// Workspaces, each laid out by one function below, regions in order, every region 256-byte aligned (M = B L rows):
+//   tower_ws       h [M, D] | big [M, big_pitch] (qkv and the MLP hidden alias) | stats [M, 2] fp32 | parts [M, D / 32, 2] fp32 |
+//                  fp8 towers only: q8 [M, max(D, mlp_pad)] e4m3 | qs [M] fp32
+//   embed_ws       im2col rows [B n, kpad] | keep form only: their pos-emb rows [B K, D]
+//   head_ws        pooled rows [B, D] (fp32 image, bf16 text) | ln rows [B, D] | projected rows [B, embed_pad]
+//   vision_ws / text_ws   x [M, D] | tower (image: embed_ws aliases it until the blocks run) | head
+//   text_tail_ws   inside the tower's big region, past the last attention: a [B, D] | n [B, D] | hid [B, mlp_pad] | stats [B, 2] fp32
 #include "common.h"
 #include <new>
 #include <vector>
@@ -97,50 +105,6 @@ struct ProfScope {
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 inline int max_i(int a, int b) { return a > b ? a : b; }
 
-struct VisionWs { size_t x, tower, pooled, lnrow, feat, total; };
-inline VisionWs vision_ws(const ov_tower* t, const ov_vision_head* h, int B) {
-    const int g = h->image_size / h->patch_size, L = g * g + 1, D = t->cfg.width;
-    VisionWs w;
-    size_t off = 0;
-    w.x = off;      off += align_up((size_t)B * L * D * 2, 256);
-    w.tower = off;  off += align_up(ov_tower_workspace_bytes(t, B, L), 256);
-    w.pooled = off; off += align_up((size_t)B * D * 4, 256);
-    w.lnrow = off;  off += align_up((size_t)B * D * 2, 256);
-    w.feat = off;   off += align_up((size_t)B * h->embed_pad * 2, 256);
-    w.total = off;
-    return w;
-}
-// patch dropout: tokens [B, 1 + K, D]; the im2col rows and their pos-emb rows alias the tower workspace until the blocks run
-inline size_t keep_embed_bytes(const ov_tower* t, const ov_vision_head* h, int B, int K) {
-    return align_up((size_t)B * K * h->kpad * 2, 256) + (size_t)B * K * t->cfg.width * 2;
-}
-inline VisionWs vision_keep_ws(const ov_tower* t, const ov_vision_head* h, int B, int K) {
-    const int L = K + 1, D = t->cfg.width;
-    VisionWs w;
-    size_t off = 0;
-    const size_t tower = ov_tower_workspace_bytes(t, B, L), embed = keep_embed_bytes(t, h, B, K);
-    w.x = off;      off += align_up((size_t)B * L * D * 2, 256);
-    w.tower = off;  off += align_up(tower > embed ? tower : embed, 256);
-    w.pooled = off; off += align_up((size_t)B * D * 4, 256);
-    w.lnrow = off;  off += align_up((size_t)B * D * 2, 256);
-    w.feat = off;   off += align_up((size_t)B * h->embed_pad * 2, 256);
-    w.total = off;
-    return w;
-}
-struct TextWs { size_t x, tower, last, lnrow, feat, total; };
-inline TextWs text_ws(const ov_tower* t, const ov_text_head* h, int B) {
-    const int T = h->context_length, D = t->cfg.width;
-    const int epad = (h->embed_dim + 7) / 8 * 8;
-    TextWs w;
-    size_t off = 0;
-    w.x = off;     off += align_up((size_t)B * T * D * 2, 256);
-    w.tower = off; off += align_up(ov_tower_workspace_bytes(t, B, T), 256);
-    w.last = off;  off += align_up((size_t)B * D * 2, 256);
-    w.lnrow = off; off += align_up((size_t)B * D * 2, 256);
-    w.feat = off;  off += align_up((size_t)B * epad * 2, 256);
-    w.total = off;
-    return w;
-}
 }  // namespace
 
 extern "C" int ov_abi_version(void) { return OV_ABI_VERSION; }
@@ -309,21 +273,90 @@ extern "C" int ov_tower_set_prefix(ov_tower* t, int prefix) {
     return OV_OK;
 }
 
+namespace {
+// ---- workspace layouts (regions: see the head of the file): every inference workspace is sized and carved here, and nowhere else ------
+struct Carver {                                 // hands out consecutive 256-byte aligned regions; a braced list evaluates left to right
+    size_t off = 0;
+    size_t take(size_t bytes) { const size_t at = off; off += align_up(bytes, 256); return at; }
+};
+
+// ldb: row pitch of big; qw: row pitch of q8.  stats: {mean, rstd} per row (LN fold); parts: ov_rowparts layout (OVHIP_ROWPARTS).
+struct TowerWs { size_t h, big, stats, parts, q8, qs, total; int ldb, qw; bool fp8; };
+TowerWs tower_ws(const ov_tower* t, int B, int L) {
+    const size_t M = (size_t)B * L, D = t->cfg.width;
+    const int ldb = big_pitch(t->cfg), qw = max_i(t->cfg.width, t->cfg.mlp_pad);
+    const bool fp8 = tower_fp8(t);
+    Carver c;
+    return {c.take(M * D * 2), c.take(M * ldb * 2), c.take(M * 8), c.take(M * (D / 32) * 8), c.take(fp8 ? M * qw : 0), c.take(fp8 ? M * 4 : 0),
+            c.off, ldb, qw, fp8};
+}
+
+// K = 0: all G patches (ov_vision_embed); K >= 1: the K kept ones and their pos-emb rows at posk (ov_vision_embed_keep)
+struct EmbedWs { size_t posk, total; };
+EmbedWs embed_ws(const ov_tower* t, const ov_vision_head* h, int B, int K) {
+    const int g = h->image_size / h->patch_size;
+    const size_t cols = (size_t)B * (K ? K : g * g) * h->kpad * 2, posk = align_up(cols, 256);
+    return K ? EmbedWs{posk, posk + (size_t)B * K * t->cfg.width * 2} : EmbedWs{cols, cols};
+}
+
+struct HeadWs { size_t rows, ln, feat, total; };             // row_bytes per pooled element: 4 (fp32, image) or 2 (bf16, text)
+HeadWs head_ws(int B, int D, int EP, int row_bytes) {
+    Carver c;
+    HeadWs w = {c.take((size_t)B * D * row_bytes), c.take((size_t)B * D * 2), c.take((size_t)B * EP * 2), 0};
+    w.total = w.feat + (size_t)B * EP * 2;
+    return w;
+}
+inline int text_embed_pad(const ov_text_head* h) { return (h->embed_dim + 7) / 8 * 8; }
+HeadWs text_head_ws(const ov_tower* t, const ov_text_head* h, int B) { return head_ws(B, t->cfg.width, text_embed_pad(h), 2); }
+
+// Image encoder, plain (K = 0, L = G + 1) or keeping K patches (L = K + 1): the embedding's buffers alias the tower region, which nothing
+// uses until the blocks run.
+struct EncoderWs { size_t x, tower, head, total; };
+EncoderWs encoder_ws(size_t x_bytes, size_t tower_bytes, const HeadWs& head) {
+    Carver c;
+    return {c.take(x_bytes), c.take(tower_bytes), c.take(head.total), c.off};
+}
+EncoderWs vision_ws(const ov_tower* t, const ov_vision_head* h, int B, int K) {
+    const int g = h->image_size / h->patch_size, L = (K ? K : g * g) + 1, D = t->cfg.width;
+    const size_t tower = tower_ws(t, B, L).total, embed = embed_ws(t, h, B, K).total;
+    return encoder_ws((size_t)B * L * D * 2, tower > embed ? tower : embed, head_ws(B, D, h->embed_pad, 4));
+}
+EncoderWs text_ws(const ov_tower* t, const ov_text_head* h, int B) {
+    const int T = h->context_length;
+    return encoder_ws((size_t)B * T * t->cfg.width * 2, tower_ws(t, B, T).total, text_head_ws(t, h, B));
+}
+
+// The text tail's buffers (ov_encode_text) in the tower's big region, free once the last attention has read qkv: a holds the gathered
+// attention rows, then the LN2 rows; n is spare (counted so that the same shapes fit as when the LN2 rows had a region of their own);
+// hid is the MLP hidden at pitch mlp_pad.
+struct TextTailWs { size_t a, n, hid, stats, total; };
+TextTailWs text_tail_ws(const ov_tower_cfg& c, int B) {
+    Carver cv;
+    TextTailWs w = {cv.take((size_t)B * c.width * 2), cv.take((size_t)B * c.width * 2), cv.take((size_t)B * c.mlp_pad * 2), cv.off, 0};
+    w.total = w.stats + (size_t)B * 8;
+    return w;
+}
+inline bool text_tail_fits(const TextTailWs& tail, const TowerWs& w) { return tail.total <= w.stats - w.big; }
+}  // namespace
+
 extern "C" size_t ov_tower_workspace_bytes(const ov_tower* t, int B, int L) {
     if (!t || B <= 0 || L <= 0) return 0;
-    const size_t M = (size_t)B * L;
-    const int D = t->cfg.width;
-    size_t n = align_up(M * D * 2, 256) + align_up(M * (size_t)big_pitch(t->cfg) * 2, 256) + align_up(M * 8, 256) +
-               align_up(M * (size_t)(D / 32) * 8, 256);            // h | big | row statistics | their partial sums (last)
-    if (tower_fp8(t)) n += align_up(M * (size_t)max_i(D, t->cfg.mlp_pad), 256) + align_up(M * 4, 256);   // fp8 activations + row scales
-    return n;
+    return tower_ws(t, B, L).total;
 }
 
 namespace {
 // One part of the batch (the main part on the caller's stream, or the tail images on the side stream): its rows of the token stream
-// and of every workspace region.  `parts` (or NULL): partial sums of x's row statistics (ov_rowparts layout; NULL under fp8); q8 / qs:
-// the fp8 activation buffer and its row scales (fp8 towers).  prof = record in-situ timings for these launches.
-struct BlockPart { ov_bf16 *x, *h, *big; float *stats, *parts; unsigned char* q8; float* qs; int B; ov_stream_t stream; bool prof; };
+// and of every workspace region.  ldb: the row pitch of `big`; `parts` (or NULL): partial sums of x's row statistics (NULL under fp8);
+// q8 / qs: the fp8 activation buffer and its row scales (fp8 towers, else NULL).  prof = record in-situ timings for these launches.
+struct BlockPart { ov_bf16 *x, *h, *big; int ldb; float *stats, *parts; unsigned char* q8; float* qs; int B; ov_stream_t stream; bool prof; };
+// B images from token row `row` on: their rows of x and of every region of the tower workspace ws laid out by w
+BlockPart tower_part(const ov_tower_cfg& c, const TowerWs& w, char* ws, ov_bf16* x, int64_t row, int B, bool parts, ov_stream_t stream,
+                     bool prof) {
+    const int D = c.width;
+    return {x + row * D, (ov_bf16*)(ws + w.h) + row * D, (ov_bf16*)(ws + w.big) + row * w.ldb, w.ldb, (float*)(ws + w.stats) + 2 * row,
+            parts ? (float*)(ws + w.parts) + 2 * row * (D / 32) : nullptr, w.fp8 ? (unsigned char*)(ws + w.q8) + row * w.qw : nullptr,
+            w.fp8 ? (float*)(ws + w.qs) + row : nullptr, B, stream, prof};
+}
 // fp8 path: one layer's scale maxima (MLP hidden | attention out), the running ones, and the tower's h_mode (0 = none set)
 struct Fp8Scales { float *h_amax, *a_amax, *h_next, *a_next; int h_mode; };
 
@@ -333,14 +366,17 @@ struct Fp8Scales { float *h_amax, *a_amax, *h_next, *a_next; int h_mode; };
 // -- so mask 0 is the bf16 block.  In front of an fp8 QKV / c_fc the LayerNorm is fused with the row quantisation; in front of an fp8
 // out_proj / c_proj the attention output / MLP hidden is written as e4m3 by its producer where that producer has a static scale
 // (h_mode >= 2: attention epilogue for head_dim 64, an fp8 c_fc's epilogue) and re-quantised row by row otherwise.
-// stop (bf16 blocks only, mask 0): where a block whose token output nobody reads ends -- BLOCK_TO_ATTN after the attention (its output in
-// p.h, x untouched), BLOCK_TO_FC after c_fc (x = the stream after out-proj, the MLP hidden in p.big).
-enum BlockStop { BLOCK_FULL = 0, BLOCK_TO_ATTN = 1, BLOCK_TO_FC = 2 };
+// span (anything but the whole block: bf16 blocks only, mask 0): the part of the launch sequence that runs.  It ends at the block's end,
+// past the attention (its output in p.h, x untouched) or past c_fc (x = the stream after out-proj, the MLP hidden in p.big) -- a block
+// whose token output nobody reads -- and starts at the block's start or past the attention (p.h holds the attention output of x's rows).
+enum BlockPoint { BLOCK_START = 0, BLOCK_PAST_ATTN = 1, BLOCK_PAST_FC = 2, BLOCK_END = 3 };
+struct BlockSpan { int from, to; };
+constexpr BlockSpan BLOCK_FULL = {BLOCK_START, BLOCK_END};
 int run_block(const ov_tower_cfg& c, const ov_block_weights& w, const ov_block_fp8* q, int mask, const Fp8Scales& sc, const BlockPart& p,
-              bool parts_in, int L, int prefix, int stop = BLOCK_FULL) {
+              bool parts_in, int L, int prefix, BlockSpan span = BLOCK_FULL) {
     const int D = c.width, H = c.heads, hd = D / H, F = c.mlp_pad, B = p.B;
     const int64_t M = (int64_t)B * L;
-    const int ldb = big_pitch(c);                               // row pitch of `big` (shared by qkv and the MLP hidden)
+    const int ldb = p.ldb;                                      // row pitch of `big` (shared by qkv and the MLP hidden)
     const float scale = 1.0f / sqrtf((float)hd);
     const int gelu = c.gelu_tanh ? OV_EPI_BIAS_GELU_TANH : OV_EPI_BIAS_GELU_ERF;
     const int fc_cls = c.gelu_tanh ? OV_PROF_GEMM_FC_TANH : OV_PROF_GEMM_FC;
@@ -359,7 +395,9 @@ int run_block(const ov_tower_cfg& c, const ov_block_weights& w, const ov_block_f
         if (rc) return rc;                                             \
     } while (0)
     // ---- attention half ----
-    if (f_qkv) {
+    const bool from_attn = span.from == BLOCK_PAST_ATTN;        // p.h holds the attention output: nothing launches up to it
+    if (from_attn) {
+    } else if (f_qkv) {
         OV_STEP(OV_PROF_LN, ov_layernorm_quant_fp8(x, D, w.ln1_w, w.ln1_b, q8, D, qs, M, D, c.ln_eps, stream));
         OV_STEP(OV_PROF_GEMM_QKV, ov_gemm_fp8(q8, D, q->qkv_w8, D, qs, q->qkv_s, q->qkv_b, big, ldb, M, 3 * D, D, OV_EPI_BIAS, nullptr, 0, stream));
     } else if (fold) {
@@ -376,9 +414,10 @@ int run_block(const ov_tower_cfg& c, const ov_block_weights& w, const ov_block_f
         OV_STEP(OV_PROF_GEMM_OUT, ov_gemm_fp8_static(q8, D, q->out_w8, D, nullptr, sc.a_amax, q->out_s, w.out_b, x, D, nullptr, nullptr, M, D, D,
                                                      OV_EPI_BIAS_RESIDUAL, x, D, stream));
     } else {
-        if (prefix >= 0) OV_STEP(OV_PROF_ATTN, ov_attention_prefix(big, ldb, h, D, B, L, H, hd, scale, prefix, stream));
+        if (from_attn) {
+        } else if (prefix >= 0) OV_STEP(OV_PROF_ATTN, ov_attention_prefix(big, ldb, h, D, B, L, H, hd, scale, prefix, stream));
         else OV_STEP(OV_PROF_ATTN, ov_attention(big, ldb, h, D, B, L, H, hd, scale, stream));
-        if (stop == BLOCK_TO_ATTN) return OV_OK;
+        if (span.to == BLOCK_PAST_ATTN) return OV_OK;
         if (f_out) {
             OV_STEP(OV_PROF_LN, ov_quant_rows_fp8(h, D, q8, D, qs, M, D, sc.h_mode == 1 ? sc.a_amax : nullptr, stream));
             OV_STEP(OV_PROF_GEMM_OUT, ov_gemm_fp8(q8, D, q->out_w8, D, qs, q->out_s, w.out_b, x, D, M, D, D, OV_EPI_BIAS_RESIDUAL, x, D, stream));
@@ -408,7 +447,7 @@ int run_block(const ov_tower_cfg& c, const ov_block_weights& w, const ov_block_f
         if (f_fc) OV_STEP(fc_cls, ov_gemm_fp8(q8, D, q->fc_w8, D, qs, q->fc_s, q->fc_b, big, ldb, M, F, D, gelu, nullptr, 0, stream));
         else if (fold) OV_STEP(fc_cls, ov_gemm_ln(x, D, w.fc_w, D, w.fc_b, w.fc_colsum, stats, big, ldb, M, F, D, gelu, stream));
         else OV_STEP(fc_cls, ov_gemm(h, D, w.fc_w, D, w.fc_b, big, ldb, M, F, D, gelu, nullptr, 0, 0, 0, 0, stream));
-        if (stop == BLOCK_TO_FC) return OV_OK;
+        if (span.to == BLOCK_PAST_FC) return OV_OK;
         if (f_proj) {
             OV_STEP(OV_PROF_LN, ov_quant_rows_fp8(big, ldb, q8, F, qs, M, F, (sc.h_mode == 1 && f_fc) ? sc.h_amax : nullptr, stream));
             OV_STEP(OV_PROF_GEMM_PROJ, ov_gemm_fp8(q8, F, q->proj_w8, F, qs, q->proj_s, w.proj_b, x, D, M, D, F, OV_EPI_BIAS_RESIDUAL, x, D, stream));
@@ -460,19 +499,14 @@ int tail_images(int B, int L) {
 // image(s) are peeled off and run, layer by layer, on an internal side stream: rows are independent through LN/GEMM and
 // attention never crosses images, so the split is exact; the main part then fills whole rounds and the tail's small
 // kernels slot into idle CUs.  Fork/join by events; everything remains ordered with respect to the caller's stream.
-// last_stop: where the LAST block ends (BlockStop; anything but BLOCK_FULL needs a bf16 tower, and leaves that block to the caller).
+// last_to: where the LAST block ends (BlockPoint; anything but BLOCK_END needs a bf16 tower, and leaves the rest of it to the caller).
 static int tower_walk(const ov_tower* t, ov_bf16* x, int B, int L, void* workspace, size_t workspace_bytes, ov_stream_t stream,
-                      int last_stop) {
+                      int last_to) {
     if (!t || !x || !workspace || B <= 0 || L <= 0) return OV_ERR_INVALID;
-    if (workspace_bytes < ov_tower_workspace_bytes(t, B, L)) return OV_ERR_WORKSPACE;
+    const TowerWs w = tower_ws(t, B, L);
+    if (workspace_bytes < w.total) return OV_ERR_WORKSPACE;
     if (((uintptr_t)x | (uintptr_t)workspace) & 15) return OV_ERR_INVALID;
     const ov_tower_cfg& c = t->cfg;
-    const int D = c.width;
-    const int64_t M = (int64_t)B * L;
-    const int ldb = big_pitch(c);
-    ov_bf16* h = (ov_bf16*)workspace;
-    ov_bf16* big = (ov_bf16*)((char*)workspace + align_up((size_t)M * D * 2, 256));
-    float* stats = (float*)((char*)big + align_up((size_t)M * ldb * 2, 256));   // {mean, rstd} per row (LN fold)
     for (int i = 0; i < c.layers; ++i)
         if (!t->set[i]) return OV_ERR_INVALID;
 
@@ -489,30 +523,24 @@ static int tower_walk(const ov_tower* t, ov_bf16* x, int B, int L, void* workspa
         if (e == hipSuccess) e = hipStreamWaitEvent(tc->stream, tc->fork, 0);
         if (e != hipSuccess) return OV_ERR_HIP - (int)e;
     }
-    const int64_t off = (int64_t)Bm * L;
-    const bool fp8 = tower_fp8(t);
+    const bool fp8 = w.fp8;
     if (t->prefix >= 0 && fp8) return OV_ERR_UNSUPPORTED;          // no fp8 under a mask
-    if (last_stop != BLOCK_FULL && fp8) return OV_ERR_UNSUPPORTED;
+    if (last_to != BLOCK_END && fp8) return OV_ERR_UNSUPPORTED;
     if (t->prefix > L) return OV_ERR_INVALID;
     int rc = OV_OK;
     if (fp8 && t->h_amax && t->h_mode == 2)            // delayed scaling: last forward's maxima become this forward's scales
         rc = ov_amax_roll(t->h_amax, t->h_amax + 2 * c.layers, 2 * c.layers, stream);
-    const int G = D / 32;
-    float* parts = use_rowparts() && !fp8 ? (float*)((char*)workspace + ov_tower_workspace_bytes(t, B, L) - align_up((size_t)M * G * 8, 256)) : nullptr;
-    const int qw = D > c.mlp_pad ? D : c.mlp_pad;                 // row pitch reserved per token in the fp8 activation buffer
-    unsigned char* q8 = (unsigned char*)stats + align_up((size_t)M * 8, 256);
-    float* qs = (float*)(q8 + align_up((size_t)M * qw, 256));
-    const BlockPart main_part = {x, h, big, stats, parts, q8, qs, Bm, stream, true};
-    const BlockPart tail_part = {x + off * D, h + off * D, big + off * ldb, stats + 2 * off, parts ? parts + 2 * off * G : nullptr,
-                                 q8 + off * qw, qs + off, nt, (ov_stream_t)(nt > 0 ? tc->stream : nullptr), false};
+    const bool parts = use_rowparts() && !fp8;
+    const BlockPart main_part = tower_part(c, w, (char*)workspace, x, 0, Bm, parts, stream, true);
+    const BlockPart tail_part = tower_part(c, w, (char*)workspace, x, (int64_t)Bm * L, nt, parts, (ov_stream_t)(nt > 0 ? tc->stream : nullptr), false);
     for (int i = 0; i < c.layers && rc == OV_OK; ++i) {
         Fp8Scales sc = {nullptr, nullptr, nullptr, nullptr, 0};
         if (t->h_amax) sc = {t->h_amax + i, t->h_amax + c.layers + i, t->h_amax + 2 * c.layers + i, t->h_amax + 3 * c.layers + i, t->h_mode};
         const ov_block_fp8* q = fp8 ? &t->fp8[i] : nullptr;
         const int mask = fp8 ? t->mask8[i] : 0;
-        const int stop = i == c.layers - 1 ? last_stop : BLOCK_FULL;
-        rc = run_block(c, t->blocks[i], q, mask, sc, main_part, i > 0, L, t->prefix, stop);
-        if (rc == OV_OK && nt > 0) rc = run_block(c, t->blocks[i], q, mask, sc, tail_part, i > 0, L, t->prefix, stop);
+        const BlockSpan span = {BLOCK_START, i == c.layers - 1 ? last_to : BLOCK_END};
+        rc = run_block(c, t->blocks[i], q, mask, sc, main_part, i > 0, L, t->prefix, span);
+        if (rc == OV_OK && nt > 0) rc = run_block(c, t->blocks[i], q, mask, sc, tail_part, i > 0, L, t->prefix, span);
     }
     if (nt > 0) {
         // always join, also after an error between fork and here: whatever the side stream got stays ordered before the
@@ -526,27 +554,11 @@ static int tower_walk(const ov_tower* t, ov_bf16* x, int B, int L, void* workspa
 
 extern "C" int ov_tower_forward(const ov_tower* t, ov_bf16* x, int B, int L, void* workspace, size_t workspace_bytes,
                                 ov_stream_t stream) {
-    return tower_walk(t, x, B, L, workspace, workspace_bytes, stream, BLOCK_FULL);
-}
-
-// OVHIP_LAST_BLOCK_FULL=1: ov_encode_image / ov_encode_text run the last block in full, as ov_tower_forward does (A/B and tests).
-static inline bool last_block_full() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("OVHIP_LAST_BLOCK_FULL"); v = (e && e[0] == '1') ? 1 : 0; }
-    return v != 0;
+    return tower_walk(t, x, B, L, workspace, workspace_bytes, stream, BLOCK_END);
 }
 
 // ---- training-side entry points: keep every block's input, run the blocks' backward in reverse -------------
-// backward.hip, one block over its kept activations (arguments checked here), both the block's one backward chain:
-// block_backward_partial called with the requested pairs of g (block_grad_pairs: bit k = pair k, -1 for a half-NULL or misaligned
-// pair) and dx unless NULL; block_backward_input with no pair, dx alone, in a smaller workspace.
-int block_grad_pairs(const ov_block_grads* g);
-int block_backward_partial(const ov_tower_cfg* cfg, const ov_block_weights* w, const ov_bf16* x, const ov_block_saved* s, const ov_bf16* dy,
-                           ov_bf16* dx, const ov_block_grads* g, int prefix, int B, int L, void* workspace, size_t workspace_bytes,
-                           ov_stream_t stream);
-size_t block_backward_input_workspace_bytes(const ov_tower_cfg* cfg, int B, int L);
-int block_backward_input(const ov_tower_cfg* cfg, const ov_block_weights* w, const ov_bf16* x, const ov_block_saved* s, const ov_bf16* dy,
-                         ov_bf16* dx, int prefix, int B, int L, void* workspace, ov_stream_t stream);
+// (backward.hip's block_backward_partial / block_backward_input / block_grad_pairs: common.h)
 
 // saved activations of one layer: [x | qkv | attention out | x1 | ln_1 out | ln_2 out | c_fc pre-activation | c_fc activation],
 // 8 D + 2 mlp_pad bf16 per token (the default keeps them all; ov_tower_forward_checkpointed keeps only x and recomputes the rest
@@ -839,27 +851,94 @@ extern "C" int ov_tower_backward_checkpointed(const ov_tower* t, int first, cons
                                    B, L, workspace, workspace_bytes, stream);
 }
 
+// ---- the encoders ------------------------------------------------------------------------------------------------------------------------
+static inline bool grid_ok(const ov_vision_head* h, int K) {      // K = 0 (every patch) or 1 <= K <= G kept ones
+    const int g = h->patch_size > 0 ? h->image_size / h->patch_size : 0;
+    return h->patch_size > 0 && K >= 0 && K <= g * g;
+}
+
 extern "C" size_t ov_vision_workspace_bytes(const ov_tower* t, const ov_vision_head* h, int B) {
     if (!t || !h || B <= 0 || h->patch_size <= 0) return 0;
-    return vision_ws(t, h, B).total;
+    return vision_ws(t, h, B, 0).total;
 }
+
+extern "C" size_t ov_vision_keep_workspace_bytes(const ov_tower* t, const ov_vision_head* h, int B, int K) {
+    if (!t || !h || B <= 0 || K < 1 || !grid_ok(h, K)) return 0;
+    return vision_ws(t, h, B, K).total;
+}
+
+extern "C" size_t ov_vision_embed_workspace_bytes(const ov_tower* t, const ov_vision_head* h, int B, int K) {
+    if (!t || !h || B <= 0 || !grid_ok(h, K)) return 0;
+    return embed_ws(t, h, B, K).total;
+}
+
+extern "C" size_t ov_vision_head_workspace_bytes(const ov_tower* t, const ov_vision_head* h, int B) {
+    if (!t || !h || B <= 0) return 0;
+    return head_ws(B, t->cfg.width, h->embed_pad, 4).total;
+}
+
+// The patch embedding in its workspace (embed_ws; arguments checked by the callers): im2col rows -> conv1 as a GEMM whose epilogue skips
+// one cls row per image and adds the pos-emb rows (K = 0: rows 1..G, broadcast over the batch; keep form: the kept patches' rows, gathered
+// into posk by the im2col launch, one to one) -> the cls rows.
+static int vision_embed(const ov_tower* t, const ov_vision_head* h, const void* image, int img_dtype, const int* keep, int B, int K,
+                        ov_bf16* x, int* err_flag, void* workspace, ov_stream_t stream) {
+    const int g = h->image_size / h->patch_size, n = K ? K : g * g, D = t->cfg.width;
+    ov_bf16 *patches = (ov_bf16*)workspace, *posk = (ov_bf16*)((char*)workspace + embed_ws(t, h, B, K).posk);
+    int rc = K ? ov_im2col_patches_keep_pos(image, img_dtype, keep, patches, B, h->image_size, h->patch_size, K, h->kpad, h->pos, posk, D,
+                                            err_flag, stream)
+               : ov_im2col_patches(image, img_dtype, patches, B, h->image_size, h->patch_size, h->kpad, stream);
+    if (rc) return rc;
+    if ((rc = ov_gemm(patches, h->kpad, h->conv_w, h->kpad, nullptr, x, D, (int64_t)B * n, D, h->kpad, OV_EPI_BIAS_RESIDUAL, K ? posk : h->pos,
+                      D, n, K ? 0 : n, K ? 0 : 1, stream)))
+        return rc;
+    return ov_cls_rows(x, D, h->cls, h->pos_f32, B, n + 1, D, stream);
+}
+static inline bool kpad_ok(const ov_vision_head* h) { return h->kpad % 64 == 0 && h->kpad >= 3 * h->patch_size * h->patch_size; }
 
 extern "C" int ov_vision_embed(const ov_tower* t, const ov_vision_head* h, const void* image, int img_dtype, int B,
                                ov_bf16* x, void* workspace, size_t workspace_bytes, ov_stream_t stream) {
     if (!t || !h || !image || !x || !workspace || B <= 0) return OV_ERR_INVALID;
-    const int g = h->image_size / h->patch_size, L = g * g + 1, D = t->cfg.width;
-    const size_t need = (size_t)B * g * g * h->kpad * 2;
-    if (workspace_bytes < need) return OV_ERR_WORKSPACE;
-    if (h->kpad % 64 || h->kpad < 3 * h->patch_size * h->patch_size) return OV_ERR_INVALID;
-    ov_bf16* patches = (ov_bf16*)workspace;
-    int rc;
-    if ((rc = ov_im2col_patches(image, img_dtype, patches, B, h->image_size, h->patch_size, h->kpad, stream))) return rc;
-    // conv1 as a GEMM; epilogue adds pos-emb rows 1..g*g (broadcast over the batch) and skips one cls row per image
-    if ((rc = ov_gemm(patches, h->kpad, h->conv_w, h->kpad, nullptr, x, D, (int64_t)B * g * g, D, h->kpad,
-                      OV_EPI_BIAS_RESIDUAL, h->pos, D, g * g, g * g, 1, stream)))
-        return rc;
-    return ov_cls_rows(x, D, h->cls, h->pos_f32, B, L, D, stream);
+    if (workspace_bytes < embed_ws(t, h, B, 0).total) return OV_ERR_WORKSPACE;
+    if (!kpad_ok(h)) return OV_ERR_INVALID;
+    return vision_embed(t, h, image, img_dtype, nullptr, B, 0, x, nullptr, workspace, stream);
 }
+
+extern "C" int ov_vision_embed_keep(const ov_tower* t, const ov_vision_head* h, const void* image, int img_dtype, const int* keep, int B,
+                                    int K, ov_bf16* x, int* err_flag, void* workspace, size_t workspace_bytes, ov_stream_t stream) {
+    if (!t || !h || !image || !keep || !x || !workspace || B <= 0 || K < 1 || !grid_ok(h, K) || !kpad_ok(h)) return OV_ERR_INVALID;
+    if (workspace_bytes < embed_ws(t, h, B, K).total) return OV_ERR_WORKSPACE;
+    return vision_embed(t, h, image, img_dtype, keep, B, K, x, err_flag, workspace, stream);
+}
+
+namespace {
+struct HeadBufs { void* rows; ov_bf16 *ln, *feat; };             // head_ws's regions in a workspace
+inline HeadBufs head_bufs(const HeadWs& w, char* ws) { return {ws + w.rows, (ov_bf16*)(ws + w.ln), (ov_bf16*)(ws + w.feat)}; }
+// the image head's buffers, after the checks of the head itself
+int vision_head_bufs(const ov_tower* t, const ov_vision_head* h, int B, void* workspace, size_t workspace_bytes, HeadBufs* hb) {
+    if (h->embed_pad % 8 || h->embed_pad < h->embed_dim) return OV_ERR_INVALID;
+    if (!h->final_ln_after_pool) return OV_ERR_UNSUPPORTED;       // OpenVision: pool -> LN (transformer.py:638-640)
+    const HeadWs w = head_ws(B, t->cfg.width, h->embed_pad, 4);
+    if (workspace_bytes < w.total) return OV_ERR_WORKSPACE;
+    *hb = head_bufs(w, (char*)workspace);
+    return OV_OK;
+}
+// A head past its pooling, for both encoders: LayerNorm of the pooled rows hb.rows (of rows_dtype; -1: hb.ln is filled already)
+// -> @ proj_t [EP, D] (-> F.normalize) -> features [B, E] fp32
+int head_finish(const ov_tower_cfg& c, const float* ln_w, const float* ln_b, const ov_bf16* proj_t, int E, int EP, const HeadBufs& hb,
+                int rows_dtype, int B, float* features, int normalize, ov_stream_t stream) {
+    const int D = c.width;
+    int rc;
+    if (rows_dtype >= 0 && (rc = ov_layernorm(hb.rows, rows_dtype, D, ln_w, ln_b, hb.ln, OV_BF16, D, B, D, c.ln_eps, stream))) return rc;
+    if ((rc = ov_gemm(hb.ln, D, proj_t, D, nullptr, hb.feat, EP, B, EP, D, OV_EPI_BIAS, nullptr, 0, 0, 0, 0, stream))) return rc;
+    if (normalize) return ov_l2norm(hb.feat, OV_BF16, EP, features, E, B, E, stream);
+    return ov_convert(hb.feat, OV_BF16, EP, features, OV_F32, E, B, E, stream);
+}
+inline int vision_head_finish(const ov_tower* t, const ov_vision_head* h, const HeadBufs& hb, bool pooled, int B, float* features,
+                              int normalize, ov_stream_t stream) {
+    return head_finish(t->cfg, h->ln_post_w, h->ln_post_b, h->proj_t, h->embed_dim, h->embed_pad, hb, pooled ? OV_F32 : -1, B, features,
+                       normalize, stream);
+}
+}  // namespace
 
 extern "C" int ov_vision_head_forward(const ov_tower* t, const ov_vision_head* h, const ov_bf16* x, int B, float* features,
                                       int normalize, void* workspace, size_t workspace_bytes, ov_stream_t stream) {
@@ -868,144 +947,82 @@ extern "C" int ov_vision_head_forward(const ov_tower* t, const ov_vision_head* h
     return ov_vision_head_forward_tokens(t, h, x, B, g * g + 1, features, normalize, workspace, workspace_bytes, stream);
 }
 
-namespace {
-// The head's workspace (pooled fp32 [B, D] | ln_post rows | projected rows) and its part past the pooling.
-struct HeadBufs { float* pooled; ov_bf16 *ln, *feat; };
-int head_bufs(const ov_tower* t, const ov_vision_head* h, int B, void* workspace, size_t workspace_bytes, HeadBufs* hb) {
-    const int D = t->cfg.width, E = h->embed_dim, EP = h->embed_pad;
-    if (EP % 8 || EP < E) return OV_ERR_INVALID;
-    if (!h->final_ln_after_pool) return OV_ERR_UNSUPPORTED;       // OpenVision: pool -> LN (transformer.py:638-640)
-    const size_t o_pooled = 0, o_ln = align_up((size_t)B * D * 4, 256), o_feat = o_ln + align_up((size_t)B * D * 2, 256);
-    if (workspace_bytes < o_feat + (size_t)B * EP * 2) return OV_ERR_WORKSPACE;
-    hb->pooled = (float*)((char*)workspace + o_pooled);
-    hb->ln = (ov_bf16*)((char*)workspace + o_ln);
-    hb->feat = (ov_bf16*)((char*)workspace + o_feat);
-    return OV_OK;
-}
-// ln_post of the pooled rows (pooled = true; else hb.ln is filled already) -> @ proj (-> F.normalize)
-int head_finish(const ov_tower* t, const ov_vision_head* h, const HeadBufs& hb, bool pooled, int B, float* features, int normalize,
-                ov_stream_t stream) {
-    const int D = t->cfg.width, E = h->embed_dim, EP = h->embed_pad;
-    int rc;
-    if (pooled && (rc = ov_layernorm(hb.pooled, OV_F32, D, h->ln_post_w, h->ln_post_b, hb.ln, OV_BF16, D, B, D, t->cfg.ln_eps, stream)))
-        return rc;
-    if ((rc = ov_gemm(hb.ln, D, h->proj_t, D, nullptr, hb.feat, EP, B, EP, D, OV_EPI_BIAS, nullptr, 0, 0, 0, 0, stream))) return rc;
-    if (normalize) return ov_l2norm(hb.feat, OV_BF16, EP, features, E, B, E, stream);
-    return ov_convert(hb.feat, OV_BF16, EP, features, OV_F32, E, B, E, stream);
-}
-}  // namespace
-
 extern "C" int ov_vision_head_forward_tokens(const ov_tower* t, const ov_vision_head* h, const ov_bf16* x, int B, int L, float* features,
                                              int normalize, void* workspace, size_t workspace_bytes, ov_stream_t stream) {
     if (!t || !h || !x || !features || !workspace || B <= 0 || L < 2) return OV_ERR_INVALID;
     const int D = t->cfg.width;
     HeadBufs hb;
     int rc;
-    if ((rc = head_bufs(t, h, B, workspace, workspace_bytes, &hb))) return rc;
+    if ((rc = vision_head_bufs(t, h, B, workspace, workspace_bytes, &hb))) return rc;
     if (h->pool_avg) {
-        if ((rc = ov_mean_pool(x, D, hb.pooled, B, L, D, 1, stream))) return rc;
+        if ((rc = ov_mean_pool(x, D, (float*)hb.rows, B, L, D, 1, stream))) return rc;
     } else {
         if ((rc = ov_layernorm(x, OV_BF16, (int64_t)L * D, h->ln_post_w, h->ln_post_b, hb.ln, OV_BF16, D, B, D, t->cfg.ln_eps, stream)))
             return rc;
     }
-    return head_finish(t, h, hb, h->pool_avg != 0, B, features, normalize, stream);
+    return vision_head_finish(t, h, hb, h->pool_avg != 0, B, features, normalize, stream);
 }
 
-// The blocks and the head of ov_encode_image / ov_encode_image_keep on the embedded tokens x [B, L, D].
+// OVHIP_LAST_BLOCK_FULL=1: ov_encode_image / ov_encode_text run the last block in full, as ov_tower_forward does (A/B and tests).
+static inline bool last_block_full() {
+    static int v = -1;
+    if (v < 0) { const char* e = getenv("OVHIP_LAST_BLOCK_FULL"); v = (e && e[0] == '1') ? 1 : 0; }
+    return v != 0;
+}
+
+// The embedding, the blocks and the head of ov_encode_image (K = 0) / ov_encode_image_keep (K kept patches) in the workspace ws.
 // avg pooling reads the last block's output through its mean over the patch tokens alone, and the mean commutes with c_proj: the last
 // block stops after c_fc, and ov_mlp_out_pooled forms mean(x1) + mean(hidden) . W2^T + b in fp32 on B rows (the pooled hidden in the
 // tower workspace's h region, free once c_fc has run) -- closer to the unrounded mean than the mean of L bf16-rounded token rows.
-// bf16 towers under pool -> LN; everything else runs the full block.
-static int blocks_and_head(const ov_tower* t, const ov_vision_head* h, ov_bf16* x, int B, int L, char* tower_ws, size_t tower_bytes,
-                           char* head_ws, size_t head_bytes, float* features, int normalize, ov_stream_t stream) {
+// bf16 towers under pool -> LN; everything else runs the full block.  So does a call that drops patches (the training-mode forward):
+// its pooled output stays bitwise what the head makes of the token stream (output_tokens).  K = G drops nothing and is ov_encode_image
+// on reordered patches: it takes that entry point's tail.
+static int encode_image(const ov_tower* t, const ov_vision_head* h, const void* image, int img_dtype, const int* keep, int B, int K,
+                        float* features, int normalize, int* err_flag, void* workspace, size_t workspace_bytes, ov_stream_t stream) {
+    const EncoderWs w = vision_ws(t, h, B, K);
+    if (workspace_bytes < w.total) return OV_ERR_WORKSPACE;
     const ov_tower_cfg& c = t->cfg;
-    const int D = c.width, F = c.mlp_pad;
-    const size_t h_bytes = align_up((size_t)B * L * D * 2, 256);            // the workspace's h region, in front of big
-    const bool pooled_tail = !last_block_full() && h->pool_avg && h->final_ln_after_pool && L >= 2 && !tower_fp8(t) && F % 32 == 0 &&
-                             ov_mlp_out_pooled_workspace_bytes(B, F) <= h_bytes;
+    const int g = h->image_size / h->patch_size, L = (K ? K : g * g) + 1, D = c.width, F = c.mlp_pad;
+    char *ws = (char*)workspace, *tower = ws + w.tower, *head = ws + w.head;
+    const size_t tower_bytes = w.head - w.tower, head_bytes = w.total - w.head;
+    ov_bf16* x = (ov_bf16*)(ws + w.x);
     int rc;
+    // the embedding's buffers alias the (not yet used) tower workspace
+    rc = K ? ov_vision_embed_keep(t, h, image, img_dtype, keep, B, K, x, err_flag, tower, tower_bytes, stream)
+           : ov_vision_embed(t, h, image, img_dtype, B, x, tower, tower_bytes, stream);
+    if (rc) return rc;
+    const TowerWs tw = tower_ws(t, B, L);
+    const size_t h_bytes = tw.big - tw.h;
+    const bool pooled_tail = (K == 0 || K == g * g) && !last_block_full() && h->pool_avg && h->final_ln_after_pool && L >= 2 && !tw.fp8 &&
+                             F % 32 == 0 && ov_mlp_out_pooled_workspace_bytes(B, F) <= h_bytes;
     if (!pooled_tail) {
-        if ((rc = ov_tower_forward(t, x, B, L, tower_ws, tower_bytes, stream))) return rc;
-        return ov_vision_head_forward_tokens(t, h, x, B, L, features, normalize, head_ws, head_bytes, stream);
+        if ((rc = ov_tower_forward(t, x, B, L, tower, tower_bytes, stream))) return rc;
+        return ov_vision_head_forward_tokens(t, h, x, B, L, features, normalize, head, head_bytes, stream);
     }
     HeadBufs hb;
-    if ((rc = head_bufs(t, h, B, head_ws, head_bytes, &hb))) return rc;
-    if ((rc = tower_walk(t, x, B, L, tower_ws, tower_bytes, stream, BLOCK_TO_FC))) return rc;
+    if ((rc = vision_head_bufs(t, h, B, head, head_bytes, &hb))) return rc;
+    if ((rc = tower_walk(t, x, B, L, tower, tower_bytes, stream, BLOCK_PAST_FC))) return rc;
     const ov_block_weights& lw = t->blocks[c.layers - 1];
-    const ov_bf16* hidden = (const ov_bf16*)(tower_ws + h_bytes);
     {   // in-situ profile: the pooled c_proj counts as the c_proj class, with the B rows it produces
         ProfScope ps(OV_PROF_GEMM_PROJ, stream, B);
-        rc = ov_mlp_out_pooled(x, D, hidden, big_pitch(c), lw.proj_w, F, lw.proj_b, hb.pooled, B, L, D, F, 1, tower_ws, h_bytes, stream);
+        rc = ov_mlp_out_pooled(x, D, (const ov_bf16*)(tower + tw.big), tw.ldb, lw.proj_w, F, lw.proj_b, (float*)hb.rows, B, L, D, F, 1,
+                               tower + tw.h, h_bytes, stream);
     }
     if (rc) return rc;
-    return head_finish(t, h, hb, true, B, features, normalize, stream);
+    return vision_head_finish(t, h, hb, true, B, features, normalize, stream);
 }
 
 extern "C" int ov_encode_image(const ov_tower* t, const ov_vision_head* h, const void* image, int img_dtype, int B,
                                float* features, int normalize, void* workspace, size_t workspace_bytes, ov_stream_t stream) {
     if (!t || !h || !image || !features || !workspace || B <= 0) return OV_ERR_INVALID;
-    const VisionWs w = vision_ws(t, h, B);
-    if (workspace_bytes < w.total) return OV_ERR_WORKSPACE;
-    const int g = h->image_size / h->patch_size, L = g * g + 1;
-    char* ws = (char*)workspace;
-    ov_bf16* x = (ov_bf16*)(ws + w.x);
-    const size_t tower_bytes = ov_tower_workspace_bytes(t, B, L);
-    int rc;
-    // the im2col buffer aliases the (not yet used) tower workspace
-    if ((size_t)B * g * g * h->kpad * 2 > tower_bytes) return OV_ERR_WORKSPACE;
-    if ((rc = ov_vision_embed(t, h, image, img_dtype, B, x, ws + w.tower, tower_bytes, stream))) return rc;
-    return blocks_and_head(t, h, x, B, L, ws + w.tower, tower_bytes, ws + w.pooled, w.total - w.pooled, features, normalize, stream);
-}
-
-int ov_im2col_patches_keep_pos(const void* image, int img_dtype, const int* keep, ov_bf16* out, int B, int S, int P, int K, int Kpad,
-                               const ov_bf16* pos, ov_bf16* posk, int D, int* err_flag, ov_stream_t stream);
-
-extern "C" size_t ov_vision_keep_workspace_bytes(const ov_tower* t, const ov_vision_head* h, int B, int K) {
-    if (!t || !h || B <= 0 || h->patch_size <= 0) return 0;
-    const int g = h->image_size / h->patch_size;
-    if (K < 1 || K > g * g) return 0;
-    return vision_keep_ws(t, h, B, K).total;
-}
-
-extern "C" int ov_vision_embed_keep(const ov_tower* t, const ov_vision_head* h, const void* image, int img_dtype, const int* keep, int B,
-                                    int K, ov_bf16* x, int* err_flag, void* workspace, size_t workspace_bytes, ov_stream_t stream) {
-    if (!t || !h || !image || !keep || !x || !workspace || B <= 0 || h->patch_size <= 0) return OV_ERR_INVALID;
-    const int g = h->image_size / h->patch_size, D = t->cfg.width;
-    if (K < 1 || K > g * g) return OV_ERR_INVALID;
-    if (h->kpad % 64 || h->kpad < 3 * h->patch_size * h->patch_size) return OV_ERR_INVALID;
-    if (workspace_bytes < keep_embed_bytes(t, h, B, K)) return OV_ERR_WORKSPACE;
-    ov_bf16* patches = (ov_bf16*)workspace;
-    ov_bf16* posk = (ov_bf16*)((char*)workspace + align_up((size_t)B * K * h->kpad * 2, 256));
-    int rc;
-    if ((rc = ov_im2col_patches_keep_pos(image, img_dtype, keep, patches, B, h->image_size, h->patch_size, K, h->kpad, h->pos, posk, D,
-                                         err_flag, stream)))
-        return rc;
-    // the GEMM of ov_vision_embed on the kept rows: the epilogue adds the gathered pos-emb rows one to one and skips a cls row per image
-    if ((rc = ov_gemm(patches, h->kpad, h->conv_w, h->kpad, nullptr, x, D, (int64_t)B * K, D, h->kpad, OV_EPI_BIAS_RESIDUAL, posk, D, K, 0,
-                      0, stream)))
-        return rc;
-    return ov_cls_rows(x, D, h->cls, h->pos_f32, B, K + 1, D, stream);
+    return encode_image(t, h, image, img_dtype, nullptr, B, 0, features, normalize, nullptr, workspace, workspace_bytes, stream);
 }
 
 extern "C" int ov_encode_image_keep(const ov_tower* t, const ov_vision_head* h, const void* image, int img_dtype, const int* keep, int B,
                                     int K, float* features, int normalize, int* err_flag, void* workspace, size_t workspace_bytes,
                                     ov_stream_t stream) {
-    if (!t || !h || !image || !keep || !features || !workspace || B <= 0 || h->patch_size <= 0) return OV_ERR_INVALID;
-    const int g = h->image_size / h->patch_size;
-    if (K < 1 || K > g * g) return OV_ERR_INVALID;
-    const VisionWs w = vision_keep_ws(t, h, B, K);
-    if (workspace_bytes < w.total) return OV_ERR_WORKSPACE;
-    const int L = K + 1;
-    char* ws = (char*)workspace;
-    ov_bf16* x = (ov_bf16*)(ws + w.x);
-    int rc;
-    if ((rc = ov_vision_embed_keep(t, h, image, img_dtype, keep, B, K, x, err_flag, ws + w.tower, w.pooled - w.tower, stream))) return rc;
-    // Patches dropped (the training-mode forward): the full block, so that the pooled output stays bitwise what the head makes of the
-    // token stream (output_tokens).  K = G drops nothing and is ov_encode_image on reordered patches: it takes that entry point's tail.
-    if (K == g * g)
-        return blocks_and_head(t, h, x, B, L, ws + w.tower, w.pooled - w.tower, ws + w.pooled, w.total - w.pooled, features, normalize, stream);
-    if ((rc = ov_tower_forward(t, x, B, L, ws + w.tower, w.pooled - w.tower, stream))) return rc;
-    return ov_vision_head_forward_tokens(t, h, x, B, L, features, normalize, ws + w.pooled, w.total - w.pooled, stream);
+    if (!t || !h || !image || !keep || !features || !workspace || B <= 0 || K < 1 || !grid_ok(h, K)) return OV_ERR_INVALID;
+    return encode_image(t, h, image, img_dtype, keep, B, K, features, normalize, err_flag, workspace, workspace_bytes, stream);
 }
 
 extern "C" size_t ov_text_workspace_bytes(const ov_tower* t, const ov_text_head* h, int B) {
@@ -1016,60 +1033,40 @@ extern "C" size_t ov_text_workspace_bytes(const ov_tower* t, const ov_text_head*
 extern "C" int ov_encode_text(const ov_tower* t, const ov_text_head* h, const int64_t* tokens, int B, float* features,
                               int normalize, int* err_flag, void* workspace, size_t workspace_bytes, ov_stream_t stream) {
     if (!t || !h || !tokens || !features || !workspace || B <= 0) return OV_ERR_INVALID;
-    const TextWs w = text_ws(t, h, B);
+    const EncoderWs w = text_ws(t, h, B);
     if (workspace_bytes < w.total) return OV_ERR_WORKSPACE;
-    const int T = h->context_length, D = t->cfg.width, E = h->embed_dim, EP = (E + 7) / 8 * 8;
-    char* ws = (char*)workspace;
+    const ov_tower_cfg& c = t->cfg;
+    const int T = h->context_length, D = c.width;
+    char *ws = (char*)workspace, *tower = ws + w.tower;
+    const size_t tower_bytes = w.head - w.tower;
     ov_bf16* x = (ov_bf16*)(ws + w.x);
-    ov_bf16* last = (ov_bf16*)(ws + w.last);
-    ov_bf16* ln = (ov_bf16*)(ws + w.lnrow);
-    ov_bf16* feat = (ov_bf16*)(ws + w.feat);
+    const HeadBufs hb = head_bufs(text_head_ws(t, h, B), ws + w.head);
+    ov_bf16* last = (ov_bf16*)hb.rows;                            // the pooled row of each caption
     int rc;
     if ((rc = ov_text_embed(tokens, h->token_embedding, h->pos, x, D, B, T, D, h->vocab_size, err_flag, stream))) return rc;
-    const size_t tower_bytes = ov_tower_workspace_bytes(t, B, T);
     const int row = h->pool_last ? T - 1 : 0;
-    const ov_tower_cfg& c = t->cfg;
-    const int F = c.mlp_pad;
-    // Past the last block's attention only the pooled row of each caption is read: out-proj, LN2, c_fc and c_proj of that block run on
-    // the B gathered rows (same GEMM entry points, and a GEMM row does not depend on the kernel form that computes it).  Their buffers
-    // (attention rows | LN2 rows | hidden | row statistics) lie in the workspace's big region, free once the attention has read qkv.
-    const size_t o_n = align_up((size_t)B * D * 2, 256), o_hid = 2 * o_n, o_stats = o_hid + align_up((size_t)B * F * 2, 256);
-    const size_t h_bytes = align_up((size_t)B * T * D * 2, 256), big_bytes = align_up((size_t)B * T * big_pitch(c) * 2, 256);
-    if (last_block_full() || tower_fp8(t) || o_stats + (size_t)B * 8 > big_bytes) {
-        if ((rc = ov_tower_forward(t, x, B, T, ws + w.tower, tower_bytes, stream))) return rc;
+    const TowerWs tw = tower_ws(t, B, T);
+    const TextTailWs tail = text_tail_ws(c, B);
+    if (last_block_full() || tw.fp8 || !text_tail_fits(tail, tw)) {
+        if ((rc = ov_tower_forward(t, x, B, T, tower, tower_bytes, stream))) return rc;
         // ln_final is per-token, so only the pooled row needs it (model.py:276-277)
         if ((rc = ov_gather_rows(x, D, last, D, B, T, row, D, stream))) return rc;
     } else {
-        if ((rc = tower_walk(t, x, B, T, ws + w.tower, tower_bytes, stream, BLOCK_TO_ATTN))) return rc;
-        const ov_block_weights& lw = t->blocks[c.layers - 1];
-        const ov_bf16* attn = (const ov_bf16*)(ws + w.tower);
-        char* big = ws + w.tower + h_bytes;
-        ov_bf16 *a = (ov_bf16*)big, *n = (ov_bf16*)(big + o_n), *hid = (ov_bf16*)(big + o_hid);
-        float* stats = (float*)(big + o_stats);
-        const int gelu = c.gelu_tanh ? OV_EPI_BIAS_GELU_TANH : OV_EPI_BIAS_GELU_ERF;
-        // in-situ profile: each launch under the class of the full block's launch it replaces, with its B rows (the gathers with the
-        // out-proj they feed)
-#define OV_TAIL_STEP(cls, call)                                    \
-        do {                                                       \
-            { ProfScope ps__(cls, stream, B); rc = (call); }       \
-            if (rc) return rc;                                     \
-        } while (0)
-        const int fc_cls = c.gelu_tanh ? OV_PROF_GEMM_FC_TANH : OV_PROF_GEMM_FC;
-        if ((rc = ov_gather_rows(attn, D, a, D, B, T, row, D, stream))) return rc;
+        // Past the last block's attention only the pooled row of each caption is read: the rest of that block is run_block from past the
+        // attention on the B gathered rows as one "image" of L = 1 (same GEMM entry points, and a GEMM row does not depend on the kernel
+        // form that computes it).  In-situ profile: each launch under its class in the full block, with its B rows.
+        if ((rc = tower_walk(t, x, B, T, tower, tower_bytes, stream, BLOCK_PAST_ATTN))) return rc;
+        char* big = tower + tw.big;
+        ov_bf16* a = (ov_bf16*)(big + tail.a);
+        if ((rc = ov_gather_rows((const ov_bf16*)(tower + tw.h), D, a, D, B, T, row, D, stream))) return rc;
         if ((rc = ov_gather_rows(x, D, last, D, B, T, row, D, stream))) return rc;
-        OV_TAIL_STEP(OV_PROF_GEMM_OUT, ov_gemm(a, D, lw.out_w, D, lw.out_b, last, D, B, D, D, OV_EPI_BIAS_RESIDUAL, last, D, 0, 0, 0, stream));
-        if (lw.fc_colsum) {
-            OV_TAIL_STEP(OV_PROF_LN, ov_rowstats(last, D, stats, B, D, c.ln_eps, stream));
-            OV_TAIL_STEP(fc_cls, ov_gemm_ln(last, D, lw.fc_w, D, lw.fc_b, lw.fc_colsum, stats, hid, F, B, F, D, gelu, stream));
-        } else {
-            OV_TAIL_STEP(OV_PROF_LN, ov_layernorm(last, OV_BF16, D, lw.ln2_w, lw.ln2_b, n, OV_BF16, D, B, D, c.ln_eps, stream));
-            OV_TAIL_STEP(fc_cls, ov_gemm(n, D, lw.fc_w, D, lw.fc_b, hid, F, B, F, D, gelu, nullptr, 0, 0, 0, 0, stream));
-        }
-        OV_TAIL_STEP(OV_PROF_GEMM_PROJ, ov_gemm(hid, F, lw.proj_w, F, lw.proj_b, last, D, B, D, F, OV_EPI_BIAS_RESIDUAL, last, D, 0, 0, 0, stream));
-#undef OV_TAIL_STEP
+        const BlockPart rows = {last, a, (ov_bf16*)(big + tail.hid), c.mlp_pad, (float*)(big + tail.stats), nullptr, nullptr, nullptr, B,
+                                stream, true};
+        if ((rc = run_block(c, t->blocks[c.layers - 1], nullptr, 0, Fp8Scales{nullptr, nullptr, nullptr, nullptr, 0}, rows, false, 1,
+                            t->prefix, {BLOCK_PAST_ATTN, BLOCK_END})))
+            return rc;
     }
-    if ((rc = ov_layernorm(last, OV_BF16, D, h->ln_final_w, h->ln_final_b, ln, OV_BF16, D, B, D, t->cfg.ln_eps, stream))) return rc;
-    if ((rc = ov_gemm(ln, D, h->proj_t, D, nullptr, feat, EP, B, EP, D, OV_EPI_BIAS, nullptr, 0, 0, 0, 0, stream))) return rc;
-    if (normalize) return ov_l2norm(feat, OV_BF16, EP, features, E, B, E, stream);
-    return ov_convert(feat, OV_BF16, EP, features, OV_F32, E, B, E, stream);
+    return head_finish(c, h->ln_final_w, h->ln_final_b, h->proj_t, h->embed_dim, text_embed_pad(h), hb, OV_BF16, B, features, normalize,
+                       stream);
 }
+

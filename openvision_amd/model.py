@@ -53,6 +53,11 @@ def _dtype_flag(t: torch.Tensor) -> int:
     raise TypeError(f"unsupported dtype {t.dtype} (float32 or bfloat16)")
 
 
+def _kernel_input(t: torch.Tensor) -> torch.Tensor:
+    """t as the kernels read it: contiguous, in float32 or bfloat16 (any other dtype is converted to float32)."""
+    return t.contiguous() if t.dtype in (torch.float32, torch.bfloat16) else t.float().contiguous()
+
+
 class _Workspace:
     """Grow-only device scratch buffer, one per module tree and device."""
 
@@ -163,8 +168,7 @@ class LayerNorm(nn.LayerNorm):
         if x.shape[-1] != d:
             raise ValueError(f"LayerNorm: last dim {x.shape[-1]} != {d}")
         lib = _lib.load()
-        xin = x if x.dtype in (torch.float32, torch.bfloat16) else x.float()
-        xin = xin.contiguous().view(-1, d)
+        xin = _kernel_input(x).view(-1, d)
         y = torch.empty_like(xin)
         g, b = self.packed()
         check(lib.ov_layernorm(ptr(xin), _dtype_flag(xin), d, ptr(g), ptr(b), ptr(y), _dtype_flag(y), d,
@@ -265,7 +269,7 @@ class PatchConv(nn.Module):
         p = self.kernel_size[0]
         bsz, _, s, _ = image.shape
         g = s // p
-        img = image.contiguous() if image.dtype in (torch.float32, torch.bfloat16) else image.float().contiguous()
+        img = _kernel_input(image)
         cols = torch.empty(bsz * g * g, self.kpad, dtype=torch.bfloat16, device=image.device)
         check(lib.ov_im2col_patches(ptr(img), _dtype_flag(img), ptr(cols), bsz, s, p, self.kpad, stream_ptr()), "ov_im2col")
         w = self.packed()
@@ -699,74 +703,55 @@ class VisionTransformer(nn.Module):
     def _draw_keep(self, bsz: int, device) -> torch.Tensor:
         return keep_to_device(self.patch_dropout.sample(bsz, self.num_patches), device)
 
-    def _encode(self, x: torch.Tensor, normalize: bool) -> torch.Tensor:
+    def _encode(self, x: torch.Tensor, normalize: bool, keep: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Image features [B, output_dim].  keep (int32 device table [B, K]; drawn here when patch dropout is active): the tower runs on
+        the kept patches only, L' = 1 + K tokens per image."""
         self._check_image(x)
-        if self.dropout_active():
-            return self._encode_keep(x, self._draw_keep(x.shape[0], x.device), normalize)
+        if keep is None and self.dropout_active():
+            keep = self._draw_keep(x.shape[0], x.device)
         lib = _lib.load()
         head, _keep = self._head()
         tower = self.transformer.tower()
-        img = x.detach()
-        img = img.contiguous() if img.dtype in (torch.float32, torch.bfloat16) else img.float().contiguous()
+        img = _kernel_input(x.detach())
         bsz = img.shape[0]
         out = torch.empty(bsz, self.output_dim, dtype=torch.float32, device=x.device)
         st = stream_ptr()
         for b0 in range(0, bsz, MAX_MICRO_BATCH):
             nb = min(MAX_MICRO_BATCH, bsz - b0)
-            nbytes = lib.ov_vision_workspace_bytes(tower.handle, C.byref(head), nb)
-            ws = self._ws.get(nbytes, x.device)
-            if isinstance(self.ln_pre, nn.Identity):
+            kb = None if keep is None else keep[b0:b0 + nb]
+            if not isinstance(self.ln_pre, nn.Identity):
+                tok = self._embed_tokens(img[b0:b0 + nb], kb)
+                tok = self.transformer(self.ln_pre(tok))
+                out[b0:b0 + nb] = self._head_forward(tok, normalize)
+            elif kb is None:
+                nbytes = lib.ov_vision_workspace_bytes(tower.handle, C.byref(head), nb)
+                ws = self._ws.get(nbytes, x.device)
                 check(lib.ov_encode_image(tower.handle, C.byref(head), ptr(img[b0:]), _dtype_flag(img), nb, ptr(out[b0:]),
                                           int(normalize), ptr(ws), nbytes, st), "ov_encode_image")
             else:
-                tok = self._embed_tokens(img[b0:b0 + nb])
-                tok = self.transformer(self.ln_pre(tok))
-                out[b0:b0 + nb] = self._head_forward(tok, normalize)
-        return out
-
-    def _encode_keep(self, x: torch.Tensor, keep: torch.Tensor, normalize: bool) -> torch.Tensor:
-        """The tower on the kept patches only (int32 device keep [B, K]): L' = 1 + K tokens per image."""
-        lib = _lib.load()
-        head, _keep = self._head()
-        tower = self.transformer.tower()
-        img = x.detach()
-        img = img.contiguous() if img.dtype in (torch.float32, torch.bfloat16) else img.float().contiguous()
-        bsz, nk = keep.shape
-        out = torch.empty(bsz, self.output_dim, dtype=torch.float32, device=x.device)
-        st = stream_ptr()
-        for b0 in range(0, bsz, MAX_MICRO_BATCH):
-            nb = min(MAX_MICRO_BATCH, bsz - b0)
-            kb = keep[b0:b0 + nb]
-            if isinstance(self.ln_pre, nn.Identity):
+                nk = kb.shape[1]
                 nbytes = lib.ov_vision_keep_workspace_bytes(tower.handle, C.byref(head), nb, nk)
                 ws = self._ws.get(nbytes, x.device)
                 check(lib.ov_encode_image_keep(tower.handle, C.byref(head), ptr(img[b0:]), _dtype_flag(img), ptr(kb), nb, nk, ptr(out[b0:]),
                                                int(normalize), None, ptr(ws), nbytes, st), "ov_encode_image_keep")
-            else:
-                tok = self._embed_tokens(img[b0:b0 + nb], kb)
-                tok = self.transformer(self.ln_pre(tok))
-                out[b0:b0 + nb] = self._head_forward(tok, normalize)
         return out
 
     def _embed_tokens(self, img: torch.Tensor, keep: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Tokens [B, L, D] bf16; keep (patch dropout): the kept patches' tokens, in keep order, behind the CLS token."""
         lib = _lib.load()
         head, _ = self._head()
         tower = self.transformer.tower()
         bsz = img.shape[0]
-        if keep is not None:                    # patch dropout: the kept patches' tokens, in keep order, behind the CLS token
-            nk = keep.shape[1]
-            tok = torch.empty(bsz, 1 + nk, tower.width, dtype=torch.bfloat16, device=img.device)
-            nbytes = lib.ov_vision_keep_workspace_bytes(tower.handle, C.byref(head), bsz, nk)
-            ws = self._ws.get(nbytes, img.device)
+        nk = 0 if keep is None else keep.shape[1]
+        tok = torch.empty(bsz, 1 + (nk or self.num_patches), tower.width, dtype=torch.bfloat16, device=img.device)
+        nbytes = lib.ov_vision_embed_workspace_bytes(tower.handle, C.byref(head), bsz, nk)
+        ws = self._ws.get(nbytes, img.device)
+        if keep is not None:
             check(lib.ov_vision_embed_keep(tower.handle, C.byref(head), ptr(img), _dtype_flag(img), ptr(keep), bsz, nk, ptr(tok), None,
                                            ptr(ws), nbytes, stream_ptr()), "ov_vision_embed_keep")
-            return tok
-        seq = self.grid_size[0] * self.grid_size[1] + 1
-        tok = torch.empty(bsz, seq, tower.width, dtype=torch.bfloat16, device=img.device)
-        nbytes = bsz * (seq - 1) * self.conv1.kpad * 2
-        ws = self._ws.get(nbytes, img.device)
-        check(lib.ov_vision_embed(tower.handle, C.byref(head), ptr(img), _dtype_flag(img), bsz, ptr(tok), ptr(ws), nbytes,
-                                  stream_ptr()), "ov_vision_embed")
+        else:
+            check(lib.ov_vision_embed(tower.handle, C.byref(head), ptr(img), _dtype_flag(img), bsz, ptr(tok), ptr(ws), nbytes,
+                                      stream_ptr()), "ov_vision_embed")
         return tok
 
     def _head_forward(self, tok: torch.Tensor, normalize: bool) -> torch.Tensor:
@@ -776,7 +761,7 @@ class VisionTransformer(nn.Module):
         bsz, seq = tok.shape[0], tok.shape[1]
         tokb = tok.detach().to(torch.bfloat16).contiguous()
         out = torch.empty(bsz, self.output_dim, dtype=torch.float32, device=tok.device)
-        nbytes = bsz * tower.width * 8 + bsz * self.output_dim * 2 + 4096
+        nbytes = lib.ov_vision_head_workspace_bytes(tower.handle, C.byref(head), bsz)
         ws = self._ws.get(nbytes, tok.device)
         check(lib.ov_vision_head_forward_tokens(tower.handle, C.byref(head), ptr(tokb), bsz, seq, ptr(out), int(normalize), ptr(ws),
                                                 nbytes, stream_ptr()), "ov_vision_head_forward_tokens")
@@ -785,9 +770,8 @@ class VisionTransformer(nn.Module):
     def forward(self, x: torch.Tensor):
         if self.output_tokens:
             self._check_image(x)
-            img = x.detach().contiguous()
             keep = self._draw_keep(x.shape[0], x.device) if self.dropout_active() else None
-            tok = self._embed_tokens(img if img.dtype in (torch.float32, torch.bfloat16) else img.float(), keep)
+            tok = self._embed_tokens(_kernel_input(x.detach()), keep)
             tok = self.transformer(self.ln_pre(tok))
             pooled = self._head_forward(tok, False)
             tokens = tok[:, 1:]
@@ -887,8 +871,7 @@ class CLIP(nn.Module):
         if (0 < image.shape[0] <= self.graph_max_batch and image.is_cuda and not torch.cuda.is_current_stream_capturing()
                 and not self.visual.dropout_active()):               # a captured graph would replay one draw of kept patches
             self.visual._check_image(image)
-            x = image.detach()
-            x = x.contiguous() if x.dtype in (torch.float32, torch.bfloat16) else x.float().contiguous()
+            x = _kernel_input(image.detach())
             return self._graphs.run(("img", tuple(x.shape), x.dtype, bool(normalize), self.visual.transformer._cache.precision,
                                      self.visual.transformer.causal_prefix),
                                     self._weights_sig, x, lambda t: self.visual._encode(t, normalize))
@@ -1008,8 +991,7 @@ def logits(a: torch.Tensor, b: torch.Tensor, scale=1.0) -> torch.Tensor:
 def l2_normalize(x: torch.Tensor) -> torch.Tensor:
     """F.normalize(x, dim=-1) on device -> fp32."""
     _require_cuda(x, "l2_normalize")
-    xin = x.detach()
-    xin = xin.contiguous() if xin.dtype in (torch.float32, torch.bfloat16) else xin.float().contiguous()
+    xin = _kernel_input(x.detach())
     x2 = xin.view(-1, xin.shape[-1])
     out = torch.empty(x2.shape, dtype=torch.float32, device=x.device)
     check(_lib.load().ov_l2norm(ptr(x2), _dtype_flag(x2), x2.shape[1], ptr(out), x2.shape[1], x2.shape[0], x2.shape[1],

@@ -31,6 +31,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from ._lib import check, ptr, stream_ptr
+from .model import _kernel_input
 
 _NAMES = ("ln1_w", "ln1_b", "qkv_w", "qkv_b", "out_w", "out_b", "ln2_w", "ln2_b", "fc_w", "fc_b", "proj_w", "proj_b")
 
@@ -388,8 +389,7 @@ class _PatchKeepFn(torch.autograd.Function):
         nk = keep.shape[1]
         d = w.shape[0]
         k, kp, npad = 3 * patch * patch, _round_up(3 * patch * patch, 64), _round_up(d, 64)
-        img = image.detach()
-        img = img.contiguous() if img.dtype in (torch.float32, torch.bfloat16) else img.float().contiguous()
+        img = _kernel_input(image.detach())
         st = stream_ptr()
         m = bsz * nk
         cols = torch.empty(m, kp, dtype=torch.bfloat16, device=image.device)

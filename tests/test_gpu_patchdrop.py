@@ -70,7 +70,7 @@ def test_identity_keep_encode_image_bitwise():
     kd = keep_to_device(torch.arange(100).repeat(5, 1), DEV)
     for norm in (False, True):
         a = m.visual._encode(img, norm)
-        b = m.visual._encode_keep(img, kd, norm)
+        b = m.visual._encode(img, norm, keep=kd)
         assert torch.equal(a, b)
 
 

@@ -134,14 +134,20 @@ class _GraphCache:
 
 
 def _pack_matrix(w: torch.Tensor, n_pad: int, k_pad: int) -> torch.Tensor:
-    """[N,K] any float dtype -> zero-padded bf16 [n_pad, k_pad], contiguous."""
+    """[N,K] any float dtype -> zero-padded bf16 [n_pad, k_pad], contiguous.  Nothing to pad: one cast, no zero fill and no second copy
+    (a block's weights are re-packed after every optimiser step)."""
     n, k = w.shape
+    if (n, k) == (n_pad, k_pad):
+        return w.detach().to(torch.bfloat16).contiguous()
     out = torch.zeros(n_pad, k_pad, dtype=torch.bfloat16, device=w.device)
-    out[:n, :k] = w.detach().to(torch.bfloat16)
+    out[:n, :k] = w.detach()                   # the copy rounds as .to(torch.bfloat16) does
     return out
 
 
 def _pack_vec(v: Optional[torch.Tensor], n_pad: int, device) -> torch.Tensor:
+    """fp32 [n_pad], zero behind v's entries (all zero without v); an fp32 vector of that length is used as it lies."""
+    if v is not None and v.numel() == n_pad:
+        return v.detach().float().contiguous()
     out = torch.zeros(n_pad, dtype=torch.float32, device=device)
     if v is not None:
         out[: v.numel()] = v.detach().float()
@@ -384,28 +390,29 @@ class ResidualAttentionBlock(nn.Module):
 
 
 class _TowerHandle:
-    """ov_tower handle + the packed tensors it borrows (kept alive here)."""
+    """ov_tower handle + the packed tensors it borrows (kept alive here: `keep[i]` are block i's, in ov_block_weights order), its
+    `cfg`, and the library object that created it, through which it is destroyed."""
 
     def __init__(self, blocks, fp8: bool = False, mask=None, prefix: Optional[int] = None, fold_ln: bool = True):
-        lib = _lib.load()
+        self.lib = lib = _lib.load()
         if prefix is not None and fp8:
             raise _lib.OvhipError("a causal prefix needs bf16 precision (no fp8 under an attention mask)")
         b0 = blocks[0]
         d = b0.attn.embed_dim
         if d % 64:
             raise _lib.OvhipError(f"width {d} must be a multiple of 64 for the gfx950 kernels")
-        cfg = _lib.TowerCfg(d, len(blocks), b0.attn.num_heads, b0.mlp_dim, b0.mlp_pad, int(b0.gelu_tanh), float(b0.ln_1.eps))
+        self.cfg = cfg = _lib.TowerCfg(d, len(blocks), b0.attn.num_heads, b0.mlp_dim, b0.mlp_pad, int(b0.gelu_tanh), float(b0.ln_1.eps))
         self.handle = lib.ov_tower_create(C.byref(cfg))
         if not self.handle:
             raise _lib.OvhipError("ov_tower_create failed (invalid tower configuration)")
-        self.keep = []
+        self.keep, self.keep8 = [], []
         for i, blk in enumerate(blocks):
             bw, keep = blk.packed_block(fold_ln=fold_ln and os.environ.get("OVHIP_NO_LN_FOLD", "0") != "1")
             self.keep.append(keep)
             check(lib.ov_tower_set_block(self.handle, i, C.byref(bw)), "ov_tower_set_block")
             if fp8:
                 b8, keep8 = blk.packed_block_fp8()
-                self.keep.append(keep8)
+                self.keep8.append(keep8)
                 check(lib.ov_tower_set_block_fp8(self.handle, i, C.byref(b8)), "ov_tower_set_block_fp8")
         self.width, self.layers, self.fp8 = d, len(blocks), fp8
         self.prefix = prefix
@@ -430,12 +437,12 @@ class _TowerHandle:
         seen = (self.h_amax[: 2 * self.layers] > 0).tolist()
         if any(n and not s_ for n, s_ in zip(need, seen)):
             raise _lib.OvhipError("freeze_fp8_scales: run at least one forward in fp8 precision first (calibration)")
-        check(_lib.load().ov_tower_set_fp8_hidden_scale(self.handle, ptr(self.h_amax), 2 if delayed else 3), "ov_tower_set_fp8_hidden_scale")
+        check(self.lib.ov_tower_set_fp8_hidden_scale(self.handle, ptr(self.h_amax), 2 if delayed else 3), "ov_tower_set_fp8_hidden_scale")
 
     def __del__(self):
         try:
             if getattr(self, "handle", None):
-                _lib.load().ov_tower_destroy(self.handle)
+                self.lib.ov_tower_destroy(self.handle)
                 self.handle = None
         except Exception:
             pass
@@ -471,22 +478,32 @@ def default_precision() -> str:
 
 
 class _TowerCache:
+    """The one place tower handles are built: inference, the autograd nodes of ``openvision_amd.training`` and the feature objective
+    of ``openvision_amd.visualize`` all take theirs here.  One entry per span of blocks (index of its first block, count) and form
+    (fp8, fold_ln), each rebuilt on its own when a parameter under it, the pack epoch, the fp8 mask or the prefix changes (``_Packed``);
+    so inference and training of one tower, the chunks of ``set_backward_chunk_layers`` and the [0, layer) spans of feature visualisation
+    do not evict each other.  The per-leaf packed tensors below the handles are shared between the forms.  Whoever still holds a replaced
+    ``_TowerHandle`` (an autograd ctx) keeps it, and the weights it was built from, alive; it is destroyed with its last holder."""
+
     def __init__(self):
-        self._pk = _Packed()
+        self._entries = {}           # (first block, count, fp8, fold_ln) -> _Packed of a _TowerHandle
         self.precision = default_precision()
         self.mask = None             # explicit per-layer OV_FP8_* masks (set_fp8_mask); None = what the precision name implies
         self.fold_ln = True          # False: the module's own LayerNorms and weights, the launches of the training forward (caption decoder)
 
-    def get(self, blocks, prefix: Optional[int] = None) -> _TowerHandle:
-        fp8 = self.precision != "bf16"
+    def get(self, blocks, prefix: Optional[int] = None, first: int = 0, plain: bool = False) -> _TowerHandle:
+        """The handle over `blocks` (`first`: the index of blocks[0] in its tower).  `plain`: bf16 over the module's own LayerNorms and
+        weights whatever `precision` and `fold_ln` say -- the form training and feature visualisation are defined on."""
+        fp8 = not plain and self.precision != "bf16"
+        fold_ln = not plain and self.fold_ln
         mask = None
         if fp8:
             mask = self.mask if self.mask is not None else (fp8_mixed_mask(len(blocks)) if self.precision == "fp8-mixed" else None)
             if mask is not None and len(mask) != len(blocks):
                 mask = (list(mask) + [mask[-1]] * len(blocks))[: len(blocks)]        # sub-stacks (exploded forward): layer-wise prefix
-        key = (fp8, None if mask is None else tuple(mask), prefix, self.fold_ln)
-        return self._pk.get(_block_params(blocks), lambda: _TowerHandle(blocks, fp8=fp8, mask=mask, prefix=prefix, fold_ln=self.fold_ln),
-                            extra=key)
+        entry = self._entries.setdefault((first, len(blocks), fp8, fold_ln), _Packed())
+        return entry.get(_block_params(blocks), lambda: _TowerHandle(blocks, fp8=fp8, mask=mask, prefix=prefix, fold_ln=fold_ln),
+                         extra=(None if mask is None else tuple(mask), prefix))
 
 
 def _check_prefix(prefix: Optional[int], seq: Optional[int] = None) -> Optional[int]:
@@ -544,7 +561,8 @@ class Transformer(nn.Module):
 
     def set_precision(self, precision: str, mask=None) -> None:
         """"bf16", "fp8" (all four GEMMs of every block in e4m3) or "fp8-mixed" (fp8_mixed_mask); `mask`: an OV_FP8_* bit set for
-        every layer, or one per layer, instead of what the name implies.  The tower is re-packed on next use."""
+        every layer, or one per layer, instead of what the name implies.  The tower is packed for it on next use; the bf16 and the fp8
+        handle are separate entries of the cache, so coming back to fp8 with the same mask and weights finds its recorded maxima."""
         if precision not in PRECISIONS:
             raise ValueError(f"precision must be one of {PRECISIONS}")
         if mask is not None and precision == "bf16":

@@ -1,8 +1,9 @@
 """Training-side forward with gradients: the block stacks and the InfoNCE loss are autograd nodes whose
 forward AND backward are the HIP kernels (``ov_tower_forward_saving_from`` / ``ov_tower_backward_partial`` or, under recomputation,
-``ov_tower_forward_checkpointed`` / ``ov_tower_backward_checkpointed``; ``ov_clip_loss`` / ``ov_clip_loss_backward``).  The light
-ends around the towers run on the HIP operators too: the patch projection and the output projections are autograd nodes over
-``ov_gemm`` / ``ov_linear_backward``, ``ln_post`` / ``ln_final`` over ``ov_layernorm`` / ``ov_layernorm_backward``
+``ov_tower_forward_checkpointed`` / ``ov_tower_backward_checkpointed``; ``ov_clip_loss_multi`` / ``ov_clip_loss_multi_backward`` at
+C = 1, ``openvision_amd.loss``).  The tower handles and the packed weights they borrow are ``model._TowerCache``'s.  The light ends
+around the towers run on the HIP operators too: the patch projection and the output projections are autograd nodes over ``ov_gemm`` /
+``ov_linear_backward``, ``ln_post`` / ``ln_final`` over ``ov_layernorm`` / ``ov_layernorm_backward``
 (open_clip/transformer.py:609-651, model.py:265-315); what is left to torch autograd is data movement and element-wise plumbing
 (class / positional embedding adds, token gather, mean pooling, L2 normalisation) -- no aten GEMM.
 
@@ -23,7 +24,6 @@ width that is not a multiple of 64 (So400m) is zero-padded.
 from __future__ import annotations
 
 import os
-import ctypes as C
 from typing import List, Tuple
 
 import torch
@@ -31,7 +31,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from ._lib import check, ptr, stream_ptr
-from .model import _kernel_input
+from .model import _kernel_input, _pack_matrix, _pack_vec, _round_up
 
 _NAMES = ("ln1_w", "ln1_b", "qkv_w", "qkv_b", "out_w", "out_b", "ln2_w", "ln2_b", "fc_w", "fc_b", "proj_w", "proj_b")
 
@@ -41,23 +41,6 @@ def _block_tensors(blk) -> List[torch.Tensor]:
     return [blk.ln_1.weight, blk.ln_1.bias, blk.attn.in_proj_weight, blk.attn.in_proj_bias, blk.attn.out_proj.weight,
             blk.attn.out_proj.bias, blk.ln_2.weight, blk.ln_2.bias, blk.mlp.c_fc.weight, blk.mlp.c_fc.bias,
             blk.mlp.c_proj.weight, blk.mlp.c_proj.bias]
-
-
-def _device_copy(p: torch.Tensor) -> torch.Tensor:
-    """Kernel layout of one parameter: weight matrices bf16 [out, in], vectors fp32."""
-    return (p.detach().to(torch.bfloat16) if p.dim() == 2 else p.detach().float()).contiguous()
-
-
-def _pad_mlp(ts: List[torch.Tensor], mlp: int, mlp_pad: int) -> List[torch.Tensor]:
-    """Zero-pad c_fc rows / bias and c_proj columns to the kernels' hidden pitch (a multiple of 64; So400m: 4304 -> 4352)."""
-    if mlp_pad == mlp:
-        return ts
-    pad = mlp_pad - mlp
-    ts = list(ts)
-    ts[8] = torch.cat([ts[8], ts[8].new_zeros(pad, ts[8].shape[1])]).contiguous()
-    ts[9] = torch.cat([ts[9], ts[9].new_zeros(pad)]).contiguous()
-    ts[10] = torch.cat([ts[10], ts[10].new_zeros(ts[10].shape[0], pad)], dim=1).contiguous()
-    return ts
 
 
 class _Pool:
@@ -105,44 +88,13 @@ class _Pool:
         del lst[:-max(1, self.peak.get(kind, 1))]        # too many: the smallest go (a grown request made them useless)
 
 
-def _train_state(transformer):
-    st = getattr(transformer, "_ovhip_train_state", None)
-    if st is None:
-        st = {"chunks": {}, "pool": _Pool()}            # chunks: (first layer, last layer + 1) -> {"sig", "keep"}
-        object.__setattr__(transformer, "_ovhip_train_state", st)
-    return st
-
-
-def _packed_blocks(transformer, params, mlp: int, mlp_pad: int, span=(0, -1)):
-    """Kernel-layout copies of every block's parameters, rebuilt only when a parameter changed: keyed, as the inference path's
-    cache is, by (data_ptr, _version) of the sources (an optimiser step bumps _version; frozen weights -- gradient ascent on the
-    inputs, ov-gradient-ascent.py -- hit the cache every step).  `model.invalidate_packed()` drops it (writes through .data)."""
-    from .model import _PACK_EPOCH
-    st = _train_state(transformer)["chunks"].setdefault(tuple(span), {"sig": None, "keep": None})
-    sig = (_PACK_EPOCH[0], mlp_pad) + tuple((p.data_ptr(), p._version, p.dtype, p.device) for p in params)
-    if st["sig"] != sig:
-        st["keep"] = [_pad_mlp([_device_copy(p) for p in params[12 * i:12 * i + 12]], mlp, mlp_pad) for i in range(len(params) // 12)]
-        st["sig"] = sig
-    return st["keep"]
-
-
-def _weights(ts) -> _lib.BlockWeights:
-    return _lib.BlockWeights(*[C.c_void_p(t.data_ptr()) for t in ts], None, None)
-
-
-def _tower_handle(lib, cfg, keep, prefix=None):
-    handle = lib.ov_tower_create(C.byref(cfg))
-    if not handle:
-        raise _lib.OvhipError("ov_tower_create failed")
-    try:
-        if prefix is not None:
-            check(lib.ov_tower_set_prefix(handle, int(prefix)), "ov_tower_set_prefix")
-        for i in range(cfg.layers):
-            check(lib.ov_tower_set_block(handle, i, C.byref(_weights(keep[i]))), "ov_tower_set_block")
-    except Exception:
-        lib.ov_tower_destroy(handle)
-        raise
-    return handle
+def _pool(transformer) -> _Pool:
+    """The tower's pool, made on first use and kept on the module."""
+    pool = getattr(transformer, "_ovhip_pool", None)
+    if pool is None:
+        pool = _Pool()
+        object.__setattr__(transformer, "_ovhip_pool", pool)
+    return pool
 
 
 class _TowerFn(torch.autograd.Function):
@@ -161,8 +113,9 @@ class _TowerFn(torch.autograd.Function):
     recompute of that block); every other node hands its slot back after the forward.  Loss and gradients are bitwise those without
     it.  In both modes a failed native call hands every pool buffer it took back.
 
-    ``_PrefixTowerFn`` below is the same node with a prefix-causal attention mask (``ov_tower_set_prefix`` on the handle of the
-    forward and, from the ctx, on the handle of the backward)."""
+    The handle is ``transformer._cache``'s over the span [lo, hi), bf16 over the module's own LayerNorms; the ctx keeps it, so the
+    backward runs the very handle of the forward.  ``_PrefixTowerFn`` below is the same node with a prefix-causal attention mask,
+    which is part of what the cache builds the handle for."""
 
     NARGS = 3            # non-tensor arguments in front of x
 
@@ -174,10 +127,9 @@ class _TowerFn(torch.autograd.Function):
     def forward(cls, ctx, transformer, lo, hi, *args):
         prefix, x, params = cls._split(args)
         ctx.nargs = cls.NARGS
-        lib = _lib.load()
         blocks = list(transformer.resblocks)[lo:hi]
         b0 = blocks[0]
-        d, heads, mlp, mlp_pad = b0.attn.embed_dim, b0.attn.num_heads, b0.mlp_dim, b0.mlp_pad
+        d, heads = b0.attn.embed_dim, b0.attn.num_heads
         if d % 64 or d % heads or (d // heads) % 8 or d // heads > 96:
             raise _lib.OvhipError("training path: width % 64 == 0 and head_dim % 8 == 0, <= 96 are required")
         bsz, seq, _ = x.shape
@@ -187,11 +139,10 @@ class _TowerFn(torch.autograd.Function):
             raise ValueError(f"causal prefix {prefix} outside [0, {seq}]")
         pairs = [[need_p[12 * i + 2 * k] or need_p[12 * i + 2 * k + 1] for k in range(6)] for i in range(layers)]
         first = 0 if need_x else next((i for i, pr in enumerate(pairs) if any(pr)), layers)
-        cfg = _lib.TowerCfg(d, layers, heads, mlp, mlp_pad, int(b0.gelu_tanh), float(b0.ln_1.eps))
-        keep = _packed_blocks(transformer, params, mlp, mlp_pad, (lo, hi))
-        pool = _train_state(transformer)["pool"]
+        tower = transformer._cache.get(blocks, prefix, first=lo, plain=True)      # built when a weight or the prefix changed, not per step
+        lib, handle = tower.lib, tower.handle
+        pool = _pool(transformer)
         remat = bool(getattr(transformer, "grad_checkpointing", False))
-        handle = _tower_handle(lib, cfg, keep, prefix)
         saved = slot = None
         try:
             xb = x.detach().to(torch.bfloat16).contiguous().clone()
@@ -216,14 +167,11 @@ class _TowerFn(torch.autograd.Function):
                 if t is not None:
                     pool.give(t)
             raise
-        finally:
-            lib.ov_tower_destroy(handle)
         if slot is not None and (not remat or saved is None or hi < len(transformer.resblocks)):
             pool.give(slot)                   # only the top node under recomputation keeps its slot for the backward
             slot = None
-        ctx.cfg, ctx.keep, ctx.saved, ctx.shape, ctx.mlp, ctx.pool = cfg, keep, saved, (bsz, seq, d), mlp, pool
-        ctx.first, ctx.pairs, ctx.need = first, pairs, (need_x, need_p)
-        ctx.prefix = prefix                   # the backward masks as the forward did
+        ctx.tower, ctx.saved, ctx.shape, ctx.pool = tower, saved, (bsz, seq, d), pool      # the backward runs the forward's handle:
+        ctx.first, ctx.pairs, ctx.need = first, pairs, (need_x, need_p)                    # its weights and its mask
         ctx.saved_gen = saved._ovhip_gen if saved is not None else None
         ctx.remat, ctx.slot = remat, slot
         ctx.x_dtype, ctx.p_dtypes = x.dtype, [p.dtype for p in params]
@@ -231,9 +179,9 @@ class _TowerFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        lib = _lib.load()
+        tower = ctx.tower
+        lib, handle, layers = tower.lib, tower.handle, tower.layers
         bsz, seq, d = ctx.shape
-        layers = len(ctx.keep)
         if ctx.saved is None or ctx.saved._ovhip_gen != ctx.saved_gen:
             raise _lib.OvhipError("training path: the saved activations of this graph were recycled by a later forward; a second "
                                   "backward over the same graph must come before the next forward of this tower")
@@ -241,14 +189,13 @@ class _TowerFn(torch.autograd.Function):
         first, pool = ctx.first, ctx.pool
         # frozen pairs: NULL in ov_block_grads, no buffers, no work; with everything trainable every pair is requested
         grads = [[None] * 12 for _ in range(first)]
-        grads += [[torch.empty_like(t) if ctx.pairs[i][j // 2] else None for j, t in enumerate(ctx.keep[i])] for i in range(first, layers)]
+        grads += [[torch.empty_like(t) if ctx.pairs[i][j // 2] else None for j, t in enumerate(tower.keep[i])] for i in range(first, layers)]
         garr = (_lib.BlockGrads * (layers - first))(*[_lib.BlockGrads(*[ptr(t) for t in g]) for g in grads[first:]])
         dx = grad_out.detach().to(torch.bfloat16).contiguous().clone()
         slot, holds = ctx.slot, ctx.slot is not None
         ctx.slot = None                       # the backward overwrites it: a second backward over this graph recomputes the top block
-        handle = ws = None
+        ws = None
         try:
-            handle = _tower_handle(lib, ctx.cfg, ctx.keep, ctx.prefix)
             nbytes = lib.ov_tower_backward_partial_workspace_bytes(handle, bsz, seq)
             ws = pool.take(nbytes, dx.device)
             if ctx.remat:
@@ -265,9 +212,7 @@ class _TowerFn(torch.autograd.Function):
             for t in (slot, ws, ctx.saved):   # after this backward's reads
                 if t is not None:
                     pool.give(t)
-            if handle is not None:
-                lib.ov_tower_destroy(handle)
-        mlp = ctx.mlp                                             # drop the (exactly zero) gradients of the MLP padding
+        mlp = tower.cfg.mlp                                       # drop the (exactly zero) gradients of the MLP padding
         for gs in grads:
             if gs[8] is not None:
                 gs[8], gs[9] = gs[8][:mlp], gs[9][:mlp]
@@ -289,10 +234,6 @@ class _PrefixTowerFn(_TowerFn):
         return int(args[0]), args[1], args[2:]
 
 
-def _round_up(x: int, m: int) -> int:
-    return (x + m - 1) // m * m
-
-
 class _LinearFn(torch.autograd.Function):
     """y = x W^T (+ b) on ov_gemm, backward on ov_linear_backward: the light-end projections of the towers (patch projection
     transformer.py:610-612 as a GEMM over patch rows, `@ proj` :645-646, `@ text_projection` model.py:282) -- no aten / hipBLASLt GEMM
@@ -306,12 +247,8 @@ class _LinearFn(torch.autograd.Function):
         kp, npad = _round_up(k, 64), _round_up(n, 64)
         xb = torch.zeros(m, kp, dtype=torch.bfloat16, device=x.device)
         xb[:, :k] = x.detach()
-        wb = torch.zeros(npad, kp, dtype=torch.bfloat16, device=x.device)
-        wb[:n, :k] = w.detach()
-        bb = None
-        if bias is not None:
-            bb = torch.zeros(npad, dtype=torch.float32, device=x.device)
-            bb[:n] = bias.detach().float()
+        wb = _pack_matrix(w, npad, kp)
+        bb = _pack_vec(bias, npad, x.device) if bias is not None else None
         out = torch.empty(m, npad, dtype=torch.bfloat16, device=x.device)
         check(lib.ov_gemm(ptr(xb), kp, ptr(wb), kp, ptr(bb), ptr(out), npad, m, npad, kp, _lib.EPI_BIAS, None, 0, 0, 0, 0, stream_ptr()),
               "ov_gemm")
@@ -395,8 +332,7 @@ class _PatchKeepFn(torch.autograd.Function):
         cols = torch.empty(m, kp, dtype=torch.bfloat16, device=image.device)
         check(lib.ov_im2col_patches_keep(ptr(img), _lib.OV_F32 if img.dtype == torch.float32 else _lib.OV_BF16, ptr(keep), ptr(cols), bsz,
                                          s, patch, nk, kp, st), "ov_im2col_patches_keep")
-        wb = torch.zeros(npad, kp, dtype=torch.bfloat16, device=image.device)
-        wb[:d, :k] = w.detach()
+        wb = _pack_matrix(w, npad, kp)
         y = torch.empty(m, npad, dtype=torch.bfloat16, device=image.device)
         check(lib.ov_gemm(ptr(cols), kp, ptr(wb), kp, None, ptr(y), npad, m, npad, kp, _lib.EPI_BIAS, None, 0, 0, 0, 0, st), "ov_gemm")
         cls32, pos32 = cls.detach().float().contiguous(), pos.detach().float().contiguous()

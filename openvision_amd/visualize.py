@@ -22,7 +22,7 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr, stream_ptr
-from .training import _block_tensors, _LinearFn, _packed_blocks, _tower_handle, _train_state, _weights
+from .training import _LinearFn, _pool
 
 __all__ = ["mlp_feature", "MLPFeatureLoss"]
 
@@ -44,24 +44,17 @@ class _FeatureFn(torch.autograd.Function):
         eps, tanh = float(b0.ln_2.eps), int(b0.gelu_tanh)
         bsz, seq, _ = x.shape
         m = bsz * seq
-        params = [p for blk in blocks for p in _block_tensors(blk)]
-        keep = _packed_blocks(tr, params, mlp, mlp_pad, (0, layer + 1))
-        st = _train_state(tr)
-        pool = st["pool"]
+        pool = _pool(tr)
         xb = x.detach().to(torch.bfloat16).contiguous().clone()
-        saved = None
-        cfg = _lib.TowerCfg(d, layer, heads, mlp, mlp_pad, tanh, float(b0.ln_1.eps))
+        saved = tower = None
         if layer > 0:                                   # blocks [0, layer): xb becomes the tap block's input
-            handle = _tower_handle(lib, cfg, keep)
-            try:
-                saved = pool.take(lib.ov_tower_saved_bytes(handle, bsz, seq), x.device, "saved")
-                nbytes = lib.ov_tower_workspace_bytes(handle, bsz, seq)
-                ws = pool.take(nbytes, x.device)
-                check(lib.ov_tower_forward_saving(handle, ptr(xb), ptr(saved), bsz, seq, ptr(ws), nbytes, stream_ptr()),
-                      "ov_tower_forward_saving")
-                pool.give(ws)
-            finally:
-                lib.ov_tower_destroy(handle)
+            tower = tr._cache.get(blocks[:layer], plain=True)
+            saved = pool.take(lib.ov_tower_saved_bytes(tower.handle, bsz, seq), x.device, "saved")
+            nbytes = lib.ov_tower_workspace_bytes(tower.handle, bsz, seq)
+            ws = pool.take(nbytes, x.device)
+            check(lib.ov_tower_forward_saving(tower.handle, ptr(xb), ptr(saved), bsz, seq, ptr(ws), nbytes, stream_ptr()),
+                  "ov_tower_forward_saving")
+            pool.give(ws)
         # the tap block: qkv | attention out | x1 | lse | pre, one pooled buffer
         lp = (seq + 31) // 32 * 32
         offs, total = [], 0
@@ -72,10 +65,10 @@ class _FeatureFn(torch.autograd.Function):
         base = tap.data_ptr()
         qkv, attn_out, x1, lse, pre = [C.c_void_p(base + o) for o in offs]
         cfg1 = _lib.TowerCfg(d, 1, heads, mlp, mlp_pad, tanh, float(b0.ln_1.eps))
-        wt = _weights(keep[layer])
+        wt, keep = blocks[layer].packed_block(fold_ln=False)          # the tap block's own LayerNorms and weights, ov_block_weights order
         check(lib.ov_block_attn_forward_saving(C.byref(cfg1), C.byref(wt), ptr(xb), qkv, attn_out, x1, lse, bsz, seq, stream_ptr()),
               "ov_block_attn_forward_saving")
-        fc_w, fc_b, ln2_w, ln2_b = keep[layer][8], keep[layer][9], keep[layer][6], keep[layer][7]
+        fc_w, fc_b, ln2_w, ln2_b = keep[8], keep[9], keep[6], keep[7]
         mean = torch.empty(bsz, dtype=torch.float32, device=x.device)
         check(lib.ov_mlp_feature_forward(x1, d, ptr(ln2_w), ptr(ln2_b), ptr(fc_w), d, ptr(fc_b), feature, mlp, tanh, bsz, seq, d, eps, pre,
                                          ptr(mean), stream_ptr()), "ov_mlp_feature_forward")
@@ -84,7 +77,8 @@ class _FeatureFn(torch.autograd.Function):
             if saved is not None:
                 pool.give(saved)
             return mean
-        ctx.pool, ctx.keep, ctx.cfg, ctx.cfg1, ctx.meta = pool, keep, cfg, cfg1, (layer, feature, bsz, seq, d, mlp, tanh, eps, offs)
+        ctx.pool, ctx.tower, ctx.tap_weights, ctx.cfg1 = pool, tower, (wt, keep), cfg1       # the backward runs the forward's handle and weights
+        ctx.meta = (layer, feature, bsz, seq, d, mlp, tanh, eps, offs)
         ctx.xb, ctx.tap, ctx.saved, ctx.x_dtype = xb, tap, saved, x.dtype
         ctx.gens = (tap._ovhip_gen, saved._ovhip_gen if saved is not None else None)
         return mean
@@ -100,32 +94,28 @@ class _FeatureFn(torch.autograd.Function):
         m = bsz * seq
         base = tap.data_ptr()
         qkv, attn_out, x1, lse, pre = [C.c_void_p(base + o) for o in offs]
-        keep = ctx.keep
+        wt, keep = ctx.tap_weights
+        handle = ctx.tower.handle if ctx.tower is not None else None
         dm = dmean.detach().float().contiguous()
-        handle = _tower_handle(lib, ctx.cfg, keep) if layer > 0 else None
-        try:
-            attn_bytes = lib.ov_block_attn_backward_input_workspace_bytes(C.byref(ctx.cfg1), bsz, seq)
-            tower_bytes = lib.ov_tower_backward_input_workspace_bytes(handle, bsz, seq) if handle else 0
-            if attn_bytes == 0 or (handle and tower_bytes == 0):
-                raise _lib.OvhipError("feature objective: width % 64 == 0 and head_dim % 8 == 0, <= 96 are required")
-            dx1_off = _a256(max(attn_bytes, tower_bytes))
-            ws = pool.take(dx1_off + m * d * 2, dm.device)
-            dx1 = C.c_void_p(ws.data_ptr() + dx1_off)
-            dx = torch.empty(m, d, dtype=torch.bfloat16, device=dm.device)
-            check(lib.ov_mlp_feature_backward(x1, d, ptr(keep[layer][6]), ptr(keep[layer][8]), d, feature, mlp, tanh, pre, ptr(dm), dx1, d,
-                                              bsz, seq, d, eps, stream_ptr()), "ov_mlp_feature_backward")
-            check(lib.ov_block_attn_backward_input(C.byref(ctx.cfg1), C.byref(_weights(keep[layer])), ptr(ctx.xb), qkv, attn_out, lse, dx1,
-                                                   ptr(dx), bsz, seq, ptr(ws), attn_bytes, stream_ptr()), "ov_block_attn_backward_input")
-            if handle:
-                check(lib.ov_tower_backward_input(handle, ptr(saved), ptr(dx), bsz, seq, ptr(ws), tower_bytes, stream_ptr()),
-                      "ov_tower_backward_input")
-            pool.give(ws)             # ordered on the stream: the next forward's writes come after this backward's reads
-            pool.give(tap)
-            if saved is not None:
-                pool.give(saved)
-        finally:
-            if handle:
-                lib.ov_tower_destroy(handle)
+        attn_bytes = lib.ov_block_attn_backward_input_workspace_bytes(C.byref(ctx.cfg1), bsz, seq)
+        tower_bytes = lib.ov_tower_backward_input_workspace_bytes(handle, bsz, seq) if handle else 0
+        if attn_bytes == 0 or (handle and tower_bytes == 0):
+            raise _lib.OvhipError("feature objective: width % 64 == 0 and head_dim % 8 == 0, <= 96 are required")
+        dx1_off = _a256(max(attn_bytes, tower_bytes))
+        ws = pool.take(dx1_off + m * d * 2, dm.device)
+        dx1 = C.c_void_p(ws.data_ptr() + dx1_off)
+        dx = torch.empty(m, d, dtype=torch.bfloat16, device=dm.device)
+        check(lib.ov_mlp_feature_backward(x1, d, ptr(keep[6]), ptr(keep[8]), d, feature, mlp, tanh, pre, ptr(dm), dx1, d, bsz, seq, d, eps,
+                                          stream_ptr()), "ov_mlp_feature_backward")
+        check(lib.ov_block_attn_backward_input(C.byref(ctx.cfg1), C.byref(wt), ptr(ctx.xb), qkv, attn_out, lse, dx1, ptr(dx), bsz, seq,
+                                               ptr(ws), attn_bytes, stream_ptr()), "ov_block_attn_backward_input")
+        if handle:
+            check(lib.ov_tower_backward_input(handle, ptr(saved), ptr(dx), bsz, seq, ptr(ws), tower_bytes, stream_ptr()),
+                  "ov_tower_backward_input")
+        pool.give(ws)             # ordered on the stream: the next forward's writes come after this backward's reads
+        pool.give(tap)
+        if saved is not None:
+            pool.give(saved)
         return None, None, None, dx.view(bsz, seq, d).to(ctx.x_dtype)
 
 

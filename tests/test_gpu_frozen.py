@@ -176,7 +176,7 @@ def test_lock_image_tower_gradients_bitwise(reference_step, k):
         else:
             assert p.grad is None, (k, n)
     assert n_unlocked == sum(1 for n in ref_grads if not n.startswith("visual.")) + {0: 0, 1: 1, 2: 15, 13: 147}[k]
-    pool = m.visual.transformer._ovhip_train_state["pool"]
+    pool = training._pool(m.visual.transformer)
     if k <= 1:                          # the whole tower is frozen and its input needs no gradient: nothing is kept
         assert pool.peak.get("saved", 0) == 0 and not pool.lists.get("saved"), k
     # one optimiser step (built after locking) moves only what is unlocked

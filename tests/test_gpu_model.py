@@ -761,10 +761,11 @@ def test_training_soft_token_entry_gradient(tiny):
             tf = training.encode_text(tiny, sp, normalize=True)
             loss = -(tf * target.to(DEV)).sum(-1).mean()
             loss.backward()
-        (st,) = tiny.transformer._ovhip_train_state["chunks"].values()      # one autograd node per tower: one packed chunk
-        sig0 = st["sig"]
+        # one autograd node per tower: one unfolded bf16 handle over all its blocks -- (first block, count, fp8, fold_ln)
+        entry = tiny.transformer._cache._entries[(0, tiny.transformer.layers, False, False)]
+        handle = entry.val
         training.encode_text(tiny, sp.detach(), normalize=True)
-        assert st["sig"] is sig0                                   # cache hit: nothing re-packed
+        assert entry.val is handle                                 # cache hit: nothing re-packed, the same _TowerHandle object
     finally:
         for p in tiny.parameters():
             p.requires_grad_(True)

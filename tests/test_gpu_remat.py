@@ -132,7 +132,7 @@ def test_pool_holds_checkpoints_and_one_slot_and_peak_memory_drops():
     try:
         for remat in (False, True, False, True):                # the second of each: packed weights and .grad already exist
             tr.grad_checkpointing = remat
-            pool = training._train_state(tr)["pool"] = training._Pool()     # every buffer of this step is allocated within it
+            pool = tr._ovhip_pool = training._Pool()            # every buffer of this step is allocated within it
             torch.cuda.synchronize()
             base = torch.cuda.memory_allocated()
             torch.cuda.reset_peak_memory_stats()

@@ -212,7 +212,8 @@ class _FailingTowerLib:
             return lambda *a: 4096
         if name.startswith(("ov_tower_forward", "ov_tower_backward")):
             return lambda *a: -1 if name.startswith(self.fail) else 0
-        return {"ov_tower_create": lambda cfg: 1, "ov_tower_set_block": lambda *a: 0, "ov_tower_destroy": lambda t: None}[name]
+        return {"ov_tower_create": lambda cfg: 1, "ov_tower_set_block": lambda *a: 0, "ov_tower_set_prefix": lambda *a: 0,
+                "ov_tower_destroy": lambda t: None}[name]
 
 
 @pytest.mark.parametrize("remat", [False, True], ids=["saving", "remat"])
@@ -232,7 +233,7 @@ def test_tower_node_hands_its_pool_buffers_back_when_a_native_call_fails(monkeyp
     fake = _FailingTowerLib("ov_tower_forward")
     monkeypatch.setattr(_lib, "load", lambda: fake)
     monkeypatch.setattr(training, "stream_ptr", lambda: None)
-    pool = training._train_state(tr)["pool"]
+    pool = training._pool(tr)
     with pytest.raises(OvhipError):
         training._TowerFn.apply(tr, 0, len(blocks), x, *params)
     assert pool.out and not any(pool.out.values()), pool.out
@@ -242,6 +243,90 @@ def test_tower_node_hands_its_pool_buffers_back_when_a_native_call_fails(monkeyp
     with pytest.raises(OvhipError):
         y.sum().backward()
     assert not any(pool.out.values()), pool.out
+
+
+class _CountingTowerLib(_FailingTowerLib):
+    """The fake above with nothing failing: numbers the tower handles it creates and records every destroy it is asked for."""
+
+    def __init__(self):
+        super().__init__("nothing")
+        self.created, self.destroyed = [], []
+
+    def ov_tower_create(self, cfg):
+        self.created.append(len(self.created) + 1)
+        return self.created[-1]
+
+    def ov_tower_destroy(self, t):
+        self.destroyed.append(t)
+
+
+class _OnDevice(torch.Tensor):
+    """A CPU tensor that passes the entry points' device checks, so that they run against a fake library."""
+    is_cuda = True
+
+
+def test_tower_handles_are_built_when_weights_change_and_destroyed_once():
+    """model._TowerCache is the one owner of tower handles: a training step with unchanged weights creates none, a changed parameter
+    version or invalidate_packed() exactly one, every span of set_backward_chunk_layers and the folded inference form have their own
+    entry beside the training one, and every handle is destroyed once, by the library that created it, after its last holder."""
+    import gc
+    from openvision_amd import _lib, training, model as M
+    fake = _CountingTowerLib()
+    x = torch.randn(2, 5, 64).as_subclass(_OnDevice)
+
+    def forward(tr):
+        xx = x.clone().requires_grad_(True)
+        return training.tower_forward(tr, xx)
+
+    def step(tr):
+        forward(tr).sum().backward()
+
+    with pytest.MonkeyPatch.context() as mp:
+        mp.setattr(_lib, "load", lambda: fake)
+        mp.setattr(training, "stream_ptr", lambda: None)
+        mp.setattr(M, "stream_ptr", lambda: None)
+        mp.setattr(training, "CHUNK_LAYERS", [0])
+        tr = M.Transformer(64, 3, 1)
+        step(tr)
+        step(tr)
+        assert fake.created == [1] and not fake.destroyed
+        with torch.no_grad():
+            tr.resblocks[1].ln_2.bias.add_(1.0)                              # an optimiser step: _version moves
+        step(tr)
+        assert fake.created == [1, 2] and fake.destroyed == [1]
+        M.invalidate_packed()
+        step(tr)
+        assert fake.created == [1, 2, 3] and fake.destroyed == [1, 2]
+        # a graph that is still alive keeps the handle of its forward, and its backward runs it
+        y = forward(tr)
+        with torch.no_grad():
+            tr.resblocks[0].attn.in_proj_weight.mul_(0.5)
+        step(tr)
+        assert fake.created == [1, 2, 3, 4] and fake.destroyed == [1, 2]
+        y.sum().backward()
+        assert fake.created == [1, 2, 3, 4] and fake.destroyed == [1, 2]
+        del y
+        gc.collect()
+        assert fake.destroyed == [1, 2, 3]
+        # one node per block: three more handles, beside the one over the whole tower; a second step creates none
+        training.set_backward_chunk_layers(1)
+        step(tr)
+        assert len(fake.created) == 7
+        step(tr)
+        training.set_backward_chunk_layers(0)
+        step(tr)
+        assert len(fake.created) == 7 and fake.destroyed == [1, 2, 3]
+        # folded inference and training of one tower: two handles, however often they alternate
+        tr2 = M.Transformer(64, 2, 1)
+        for _ in range(3):
+            with torch.no_grad():
+                tr2(x)
+            step(tr2)
+        assert len(fake.created) == 9 and fake.destroyed == [1, 2, 3]
+    # the patch is undone: what is left is destroyed through the library that created it all the same
+    del tr, tr2
+    gc.collect()
+    assert sorted(fake.destroyed) == fake.created
 
 
 def test_fused_adamw_state_dict_hooks_and_none_gradients():

@@ -9,9 +9,6 @@ Part 2 walks each rule of attention_route.h at its edge, with pairs of calls tha
 values are read off the rules as DESIGN.md section 4 states them (a head of up to 320 padded keys stays resident; 160 KiB of LDS and 8
 or 12 waves per CU; 2 GiB of rows; the resident backward up to L = 288; 256-row backward chunks), not off what the library returns."""
 import json
-import os
-import subprocess
-import sys
 
 import pytest
 
@@ -22,6 +19,7 @@ import test_gpu_fp8_routes as F8
 import test_gpu_ops as OPS
 import test_gpu_prefix_attention as PT
 from hipops import attn_route
+from ranks import run_child
 
 CUS = 256
 KIB = 1024
@@ -258,15 +256,11 @@ def test_what_the_entry_points_refuse():
 
 # ---- the switch: read once per process, so each setting is asked in a child process (CPU only)
 
-CHILD = ("import json, os, sys; sys.path[:0] = [os.environ['OV_ROOT'], os.path.join(os.environ['OV_ROOT'], 'tests')]; "
-         "import hipops as H; print(json.dumps([H.attn_route(*s, cus=256).lone_valu for s in json.loads(sys.argv[1])]))")
+CHILD = ("import json; import hipops as H; print(json.dumps([H.attn_route(*s, cus=256).lone_valu for s in json.loads(sys.argv[1])]))")
 
 
 @pytest.mark.parametrize("setting,hd64", [(None, 1), ("1", 1), ("0", 0)])
 def test_lone_key_switch(setting, hd64):
     """OVHIP_ATTN_LONEKEY=0 turns the hd 64 kernels' VALU fold of a lone last key into a tile step; the generic kernel always folds."""
-    tests = os.path.dirname(os.path.abspath(__file__))
-    env = {k: v for k, v in os.environ.items() if k != "OVHIP_ATTN_LONEKEY"}
-    env.update({"OVHIP_ATTN_LONEKEY": setting} if setting else {}, OV_ROOT=os.path.dirname(tests))
-    out = subprocess.run([sys.executable, "-c", CHILD, json.dumps(H.LONE_SPIKED)], check=True, env=env, capture_output=True, text=True, timeout=120)
+    out = run_child(CHILD, json.dumps(H.LONE_SPIKED), env={"OVHIP_ATTN_LONEKEY": setting}, timeout=120)
     assert json.loads(out.stdout.strip().splitlines()[-1]) == [hd64 if hd == 64 else 1 for (_, _, _, hd) in H.LONE_SPIKED]

@@ -1,21 +1,14 @@
 """CPU, world_size 2 over gloo: the N>1 host path — rank-ordered all-gather of packed [b, 2E] embeddings
 (openvision_amd.loss.gather_features), label offsets b*rank, and the data-parallel batch sharding bench.py uses.
 The loss arithmetic itself is HIP-only (no CPU fallback), so the oracle stands in as the checker here."""
-import os
-import tempfile
-
 import numpy as np
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
 
 from conftest import golden
+from ranks import run_ranks
 
 
-def _worker(rank, ws, store, q):
-    import sys
-    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    dist.init_process_group("gloo", init_method=f"file://{store}", rank=rank, world_size=ws)
+def _worker(rank, ws):
     from openvision_amd.loss import gather_features, ClipLoss
     from oracle import clip_ref as R
     g = golden("cliploss_ws.npz")
@@ -30,20 +23,12 @@ def _worker(rank, ws, store, q):
         refused = False
     except RuntimeError:
         refused = True
-    q.put((rank, ok_order, loss, refused))
-    dist.barrier()
-    dist.destroy_process_group()
+    return rank, ok_order, loss, refused
 
 
 def test_gather_and_local_loss_world_size_2():
     ws = 2
-    ctx = mp.get_context("spawn")
-    with tempfile.TemporaryDirectory() as d:
-        q = ctx.Queue()
-        ps = [ctx.Process(target=_worker, args=(r, ws, os.path.join(d, "store"), q)) for r in range(ws)]
-        [p.start() for p in ps]
-        res = sorted(q.get(timeout=300) for _ in range(ws))
-        [p.join(60) for p in ps]
+    res = run_ranks(_worker, ws, timeout=300, backend="gloo")
     g = golden("cliploss_ws.npz")
     for rank, ok_order, loss, refused in res:
         assert ok_order and refused
@@ -60,10 +45,7 @@ def test_gather_requires_process_group():
     assert a.shape == (2, 8)
 
 
-def _grad_worker(rank, ws, store, q):
-    import sys
-    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    dist.init_process_group("gloo", init_method=f"file://{store}", rank=rank, world_size=ws)
+def _grad_worker(rank, ws):
     from openvision_amd import preset, synth, training
     from openvision_amd.model import create_model
     from openvision_amd._lib import OvhipError
@@ -82,9 +64,7 @@ def _grad_worker(rank, ws, store, q):
         refused = False
     except OvhipError:
         refused = True
-    q.put((rank, nb, scale, refused, {k: v.numpy() for k, v in gsum.items()} if rank == 0 else None))
-    dist.barrier()
-    dist.destroy_process_group()
+    return rank, nb, scale, refused, {k: v.numpy() for k, v in gsum.items()} if rank == 0 else None
 
 
 def test_bucketed_gradient_all_reduce_world_size_2():
@@ -92,13 +72,7 @@ def test_bucketed_gradient_all_reduce_world_size_2():
     ranks (the reference averages with the 1/world_size factor, returned for the update kernel), a replaced .grad is folded back in,
     and the HIP update refuses CPU tensors."""
     ws = 2
-    ctx = mp.get_context("spawn")
-    with tempfile.TemporaryDirectory() as d:
-        q = ctx.Queue()
-        ps = [ctx.Process(target=_grad_worker, args=(r, ws, os.path.join(d, "store"), q)) for r in range(ws)]
-        [p.start() for p in ps]
-        res = sorted((q.get(timeout=300) for _ in range(ws)), key=lambda r: r[0])
-        [p.join(60) for p in ps]
+    res = run_ranks(_grad_worker, ws, timeout=300, backend="gloo")
     assert all(r[1] > 5 and r[2] == 0.5 and r[3] for r in res)
     got = res[0][4]
     from openvision_amd import preset, synth
@@ -114,10 +88,7 @@ def test_bucketed_gradient_all_reduce_world_size_2():
         np.testing.assert_allclose(got[n], ref, rtol=1e-6, atol=1e-6, err_msg=n)
 
 
-def _overlap_worker(rank, ws, store, q):
-    import sys
-    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    dist.init_process_group("gloo", init_method=f"file://{store}", rank=rank, world_size=ws)
+def _overlap_worker(rank, ws):
     from openvision_amd import preset, synth, training
     from openvision_amd.model import create_model
     cfg = preset("vit-tiny-patch16-160")
@@ -135,9 +106,7 @@ def _overlap_worker(rank, ws, store, q):
         launched = sum(opt._ov["launched"])                                   # buckets already in flight when backward returns
         scale = opt.all_reduce_gradients(ws)
         res.append((launched, scale, {n: p.grad.clone().numpy() for n, p in m.named_parameters()} if rank == 0 else None))
-    q.put((rank, nb, res))
-    dist.barrier()
-    dist.destroy_process_group()
+    return rank, nb, res
 
 
 def test_overlapped_gradient_exchange_world_size_2():
@@ -145,13 +114,7 @@ def test_overlapped_gradient_exchange_world_size_2():
     post-accumulate hooks (all of them are in flight when backward returns), the sums are those of the plain exchange, and the
     buckets re-arm for the next backward."""
     ws = 2
-    ctx = mp.get_context("spawn")
-    with tempfile.TemporaryDirectory() as d:
-        q = ctx.Queue()
-        ps = [ctx.Process(target=_overlap_worker, args=(r, ws, os.path.join(d, "store"), q)) for r in range(ws)]
-        [p.start() for p in ps]
-        out = sorted((q.get(timeout=300) for _ in range(ws)), key=lambda r: r[0])
-        [p.join(60) for p in ps]
+    out = run_ranks(_overlap_worker, ws, timeout=300, backend="gloo")
     from openvision_amd import preset
     from openvision_amd.model import create_model
     m = create_model(preset("vit-tiny-patch16-160"))

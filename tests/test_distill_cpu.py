@@ -13,6 +13,7 @@ from openvision_amd.loss import DistillClipLoss
 
 import distill_restate as DR
 from conftest import golden
+from ranks import run_ranks
 
 IDS = [c[0] for c in DR.CASES]
 KEYS = ("img", "txt", "timg", "ttxt")
@@ -180,12 +181,7 @@ def test_loss_module_refusals_and_surface():
         DistillClipLoss()(img[0], txt[0], 10.0, t_img, t_txt, 20.0)             # not 2-d
 
 
-def _gloo_rank(rank, ws, store, q):
-    import sys
-    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    import torch.distributed as dist
-    from openvision_amd import loss as L
-    dist.init_process_group("gloo", init_method=f"file://{store}", rank=rank, world_size=ws)
+def _gloo_rank(rank, ws):
     b, e, et = 3, 8, 4
     log = []
     L.record_comm(log)
@@ -198,24 +194,14 @@ def _gloo_rank(rank, ws, store, q):
     fulls = [torch.randn(ws * b, 2 * e, generator=g) for _ in range(ws)]
     summed = L.route_packed_gradient(fulls[rank].clone(), b, rank, True)
     own = L.route_packed_gradient(fulls[rank].clone(), b, rank, False)
-    q.put((rank, packed, len(log), summed.clone(), own.clone(), fulls))
-    dist.barrier()
-    dist.destroy_process_group()
+    return packed, len(log), summed.clone(), own.clone(), fulls
 
 
 def test_packed_gather_and_gradient_routing_over_gloo():
     """Two gloo ranks on CPU tensors: ONE collective gathers the packed [b, 2E + 2Et] rows in rank order, the columns split into the
     four operands, and a packed [N, 2E] gradient of the student's gathered rows is routed as each mode prescribes."""
-    import tempfile
-    import torch.multiprocessing as mp
-    ctx = mp.get_context("spawn")
     ws, b, e, et = 2, 3, 8, 4
-    with tempfile.TemporaryDirectory() as d:
-        q = ctx.Queue()
-        ps = [ctx.Process(target=_gloo_rank, args=(r, ws, os.path.join(d, "store"), q)) for r in range(ws)]
-        [p.start() for p in ps]
-        res = {r[0]: r[1:] for r in (q.get(timeout=300) for _ in range(ws))}
-        [p.join(60) for p in ps]
+    res = run_ranks(_gloo_rank, ws, timeout=300, backend="gloo")
     for rank in range(ws):
         packed, ncoll, summed, own, fulls = res[rank]
         assert ncoll == 1 and packed.shape == (ws * b, 2 * e + 2 * et)

@@ -8,14 +8,13 @@ expected values are read off the rules as the code and DESIGN.md state them (96 
 n-tile of at most 128 columns, K >= 2 N, 192 MiB of output), not off what the library returns."""
 import json
 import os
-import subprocess
-import sys
 
 import pytest
 
 import hipops as H
 import test_gpu_gemm_routes as RT
 from hipops import route
+from ranks import run_child
 
 CUS = 256
 MIB = 1 << 20
@@ -207,16 +206,13 @@ def test_persistent_forms_of_each_epilogue_family():
 
 # ---- the switches: read once per process, so each setting is asked in a child process (CPU only)
 
-CHILD = ("import ctypes, json, os, sys; sys.path[:0] = [os.environ['OV_ROOT'], os.path.join(os.environ['OV_ROOT'], 'tests')]; "
-         "import hipops as H; calls = json.loads(sys.argv[1]); "
+CHILD = ("import ctypes, json; import hipops as H; calls = json.loads(sys.argv[1]); "
          "print(json.dumps([vars(H.route(*c[0], cus=256, **c[1])) for c in calls]))")
 
 
 def ask_child(env_add, calls):
-    tests = os.path.dirname(os.path.abspath(__file__))
-    env = {k: v for k, v in os.environ.items() if not k.startswith("OVHIP_GEMM_")}
-    env.update(env_add, OV_ROOT=os.path.dirname(tests))
-    out = subprocess.run([sys.executable, "-c", CHILD, json.dumps(calls)], check=True, env=env, capture_output=True, text=True, timeout=120)
+    env = {**{k: None for k in os.environ if k.startswith("OVHIP_GEMM_")}, **env_add}
+    out = run_child(CHILD, json.dumps(calls), env=env, timeout=120)
     return [H.SimpleNamespace(**d) for d in json.loads(out.stdout.strip().splitlines()[-1])]
 
 

@@ -13,8 +13,6 @@ the bound can see: an emulation of the kernel arithmetic stays well inside it, a
 double-counted or unrescaled lone key lands outside it."""
 import json
 import os
-import subprocess
-import sys
 import tempfile
 
 import pytest
@@ -22,6 +20,7 @@ import torch
 
 import hipops as H
 from hipops import LONE_SPIKED, attn_ref64, bound, err_ratio, rnd, spiked_qkv
+from ranks import run_child
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -114,8 +113,7 @@ def test_attention_huge_row_pitch():
 
 LONE_FORMS = ["persistent", "streaming", "streaming", "generic chunked", "generic chunked"]          # of LONE_SPIKED, as the docstring says
 _CHILD = r"""
-import os, sys, torch
-sys.path.insert(0, os.environ["OV_ROOT"]); sys.path.insert(0, os.path.join(os.environ["OV_ROOT"], "tests"))
+import torch
 import hipops as H
 cases = torch.load(sys.argv[1])
 torch.save({"outs": [H.attention(q.cuda(), B, L, Hh, hd).cpu() for (q, B, L, Hh, hd) in cases],
@@ -133,15 +131,13 @@ def test_lone_key_as_the_row_max():
     for (B, L, Hh, hd) in LONE_SPIKED:
         qkv, _ = spiked_qkv(B, L, Hh, hd, seed=L + hd)
         cases.append((qkv, B, L, Hh, hd))
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     res = {}
     with tempfile.TemporaryDirectory() as d:
         src = os.path.join(d, "cases.pt")
         torch.save(cases, src)
         for lk in ("1", "0"):
             path = os.path.join(d, f"lk{lk}.pt")
-            env = dict(os.environ, OVHIP_ATTN_LONEKEY=lk, OV_ROOT=root)
-            subprocess.run([sys.executable, "-c", _CHILD, src, path], check=True, env=env, timeout=600)
+            run_child(_CHILD, src, path, env={"OVHIP_ATTN_LONEKEY": lk}, timeout=600, gpu=True)
             res[lk] = torch.load(path)
     ratios = []
     assert res["1"]["lone_valu"] == [1] * len(cases) and res["0"]["lone_valu"] == [int(hd != 64) for (_, _, _, _, hd) in cases]

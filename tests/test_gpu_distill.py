@@ -8,7 +8,6 @@ gradient to 1e-5 of its largest entry, d logit_scale to 1e-5 relative.  Two depa
     makes against float64 on the same inputs (the factor 4: another summation order and the hardware v_exp);
   * N = 1 makes both losses and every gradient exactly zero (P = Q = onehot = 1): there is no largest entry, so the error is
     measured against the size of one term of the cancelling sum."""
-import os
 
 import pytest
 import torch
@@ -21,6 +20,7 @@ from openvision_amd.model import create_model
 import distill_restate as DR
 import hipops as H
 from conftest import golden
+from ranks import run_ranks
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -307,14 +307,8 @@ def test_module_world_size_1(local_loss, gwg):
     assert abs(got[0] - float(ref)) <= 1e-6 * float(ref)
 
 
-def _nccl_ws1_rank(store, q):
-    import sys
-    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-    import torch.distributed as dist
+def _nccl_ws1_rank(rank, ws):
     from openvision_amd import loss as L
-    torch.cuda.set_device(0)
-    dist.init_process_group("nccl", init_method=f"file://{store}", rank=0, world_size=1, device_id=torch.device(DEV))
     inputs = _module_inputs()
     out = {}
     for local_loss, gwg in MODES:
@@ -325,23 +319,13 @@ def _nccl_ws1_rank(store, q):
         c, d, gi, gt, gs = _module_run(fn, inputs)
         L.record_comm(None)
         out[(local_loss, gwg)] = (c, d, gi.numpy(), gt.numpy(), gs, len(log))
-    q.put(out)
-    dist.barrier()
-    dist.destroy_process_group()
+    return out
 
 
 def test_rccl_branch_of_the_module_at_world_size_1():
     """The RCCL code path (ONE packed all-gather per call read in place, packed [N, 2E] gathered-side gradient, reduce-scatter) in a
     world of one rank.  A detached gather with local_loss returns the local-side gradient alone; the other two modes the whole one."""
-    import tempfile
-    import torch.multiprocessing as mp
-    ctx = mp.get_context("spawn")
-    with tempfile.TemporaryDirectory() as d:
-        q = ctx.Queue()
-        p = ctx.Process(target=_nccl_ws1_rank, args=(os.path.join(d, "store"), q))
-        p.start()
-        out = q.get(timeout=600)
-        p.join(120)
+    out, = run_ranks(_nccl_ws1_rank, 1, timeout=600, backend="nccl", gpu=True)
     inputs = _module_inputs()
     for (local_loss, gwg), (c, d_, gi, gt, gs, ncoll) in out.items():
         assert ncoll == 2                                        # one gather in the differentiated call, one in the no_grad call

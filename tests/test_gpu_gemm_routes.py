@@ -42,8 +42,6 @@ hipops.route: the launcher's own decision for this device's CU count), that the 
 decides at each rule's edge is pinned without a GPU by test_gemm_route_cpu.py."""
 import functools
 import os
-import subprocess
-import sys
 import tempfile
 from types import SimpleNamespace
 
@@ -52,6 +50,7 @@ import torch
 
 import hipops as H
 from hipops import BM, BN, DEV, SENT, fold_ratios_bound, linear_ratios, ln_linear_ratios, padding_kept, report, route, sentinel
+from ranks import run_child
 
 pytestmark = pytest.mark.gpu
 
@@ -268,14 +267,11 @@ def child_main(path, which):
 def child_outputs(setting):
     """Runs the child of `setting` (once per session, one child at a time) and returns what it saved: (outputs, routes)."""
     env_add, which = SETTINGS[setting]
-    tests = os.path.dirname(os.path.abspath(__file__))
-    env = {k: v for k, v in os.environ.items() if k not in ("OVHIP_GEMM_NT_MIN_MB", "OVHIP_GEMM_GELU_LDS")}
-    env.update(env_add, OV_ROOT=os.path.dirname(tests))
-    code = ("import os, sys; sys.path[:0] = [os.environ['OV_ROOT'], os.path.join(os.environ['OV_ROOT'], 'tests')]; "
-            "import test_gpu_gemm_routes as T; T.child_main(sys.argv[1], sys.argv[2])")
+    env = {"OVHIP_GEMM_NT_MIN_MB": None, "OVHIP_GEMM_GELU_LDS": None, **env_add}
     with tempfile.TemporaryDirectory() as d:
         path = os.path.join(d, "outs.pt")
-        subprocess.run([sys.executable, "-c", code, path, which], check=True, env=env, timeout=300)
+        code = "import test_gpu_gemm_routes as T; T.child_main(sys.argv[1], sys.argv[2])"
+        run_child(code, path, which, env=env, timeout=300, gpu=True)
         saved = torch.load(path)
         return saved["outs"], saved["routes"]
 

@@ -5,8 +5,6 @@ Text tower (last / first pool): past the last block's attention, out-proj .. c_p
 OVHIP_LAST_BLOCK_FULL=1 restores the full block in both; it is read once per process, so that side runs in ONE child process
 (`full`, module scope) whose results every test below shares."""
 import os
-import subprocess
-import sys
 import tempfile
 
 import numpy as np
@@ -16,6 +14,7 @@ import torch
 from openvision_amd import _lib, preset, synth
 from openvision_amd._lib import ptr, stream_ptr, check
 from openvision_amd.model import create_model
+from ranks import run_child
 from test_gpu_model import COS_TOL
 
 pytestmark = pytest.mark.gpu
@@ -76,8 +75,7 @@ def compute_all():
 
 
 _CHILD = r"""
-import os, sys, torch
-sys.path.insert(0, os.environ["OV_ROOT"]); sys.path.insert(0, os.path.join(os.environ["OV_ROOT"], "tests"))
+import torch
 import test_gpu_last_block as T
 torch.save(T.compute_all(), sys.argv[1])
 """
@@ -87,8 +85,7 @@ torch.save(T.compute_all(), sys.argv[1])
 def full():
     with tempfile.TemporaryDirectory() as d:
         path = os.path.join(d, "full.pt")
-        env = dict(os.environ, OVHIP_LAST_BLOCK_FULL="1", OV_ROOT=ROOT)
-        subprocess.run([sys.executable, "-c", _CHILD, path], check=True, env=env, timeout=600)
+        run_child(_CHILD, path, env={"OVHIP_LAST_BLOCK_FULL": "1"}, timeout=600, gpu=True)
         return torch.load(path)
 
 

@@ -3,10 +3,7 @@ CUDA tensors -- against the float64 restatements' per_rank (tests/multicap_resta
 every (local_loss, gather_with_grad) mode.  b = 40 rows per rank: every 32-row tile is ragged and rank 1's own chunk of the N = 80
 gathered rows lies across a tile boundary.  Tolerances are each loss's own module tolerances (test_gpu_multicap.py,
 test_gpu_distill.py, test_gpu_siglip.py); ClipLoss takes the multi-caption loss's."""
-import os
-import queue
 import time
-import traceback
 
 import numpy as np
 import pytest
@@ -15,6 +12,7 @@ import torch
 import distill_restate as DR
 import multicap_restate as MR
 import siglip_restate as SR
+from ranks import run_ranks
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -35,9 +33,10 @@ def _leaf(x):
     return x.float().to(DEV).requires_grad_(True)
 
 
-def _rank_runs(rank):
+def _world2_rank(rank, ws):
     """Every module once on this rank's rows: name -> (loss(es), d image_features, d text_features, d scale (, d bias))."""
     from openvision_amd.loss import ClipLoss, DistillClipLoss, MultiCaptionClipLoss, SigLipLoss
+    torch.cuda.set_device(0)
     own, inputs, out = slice(rank * B, (rank + 1) * B), _inputs(), {}
     for local_loss, gwg in MODES:
         kw = dict(local_loss=local_loss, gather_with_grad=gwg, rank=rank, world_size=WS)
@@ -62,50 +61,11 @@ def _rank_runs(rank):
     return out
 
 
-def _world2_rank(rank, store, q):
-    import sys
-    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-    import torch.distributed as dist
-    try:
-        torch.cuda.set_device(0)
-        dist.init_process_group("gloo", init_method=f"file://{store}", rank=rank, world_size=WS)
-        q.put((rank, _rank_runs(rank), None))
-        dist.barrier()
-        dist.destroy_process_group()
-    except Exception:
-        q.put((rank, None, traceback.format_exc()))
-        raise
-
-
 @pytest.fixture(scope="module")
 def world2():
     """One spawned pair of ranks runs every case; a rank that dies or raises fails the tests at once, nothing is retried."""
-    import tempfile
-    import torch.multiprocessing as mp
-    ctx = mp.get_context("spawn")
     t0 = time.monotonic()
-    with tempfile.TemporaryDirectory() as d:
-        q = ctx.Queue()
-        ps = [ctx.Process(target=_world2_rank, args=(r, os.path.join(d, "store"), q)) for r in range(WS)]
-        [p.start() for p in ps]
-        res = {}
-        try:
-            while len(res) < WS:
-                try:
-                    rank, out, err = q.get(timeout=1.0)
-                except queue.Empty:
-                    assert all(p.exitcode in (None, 0) for p in ps), f"a rank died: exit codes {[p.exitcode for p in ps]}"
-                    assert time.monotonic() - t0 < 300, "the ranks did not answer in 300 s"
-                    continue
-                assert err is None, f"rank {rank} raised:\n{err}"
-                res[rank] = out
-            [p.join(120) for p in ps]
-        finally:
-            for p in ps:
-                if p.is_alive():
-                    p.kill()
-                    p.join()
+    res = run_ranks(_world2_rank, WS, timeout=300, backend="gloo", gpu=True)
     print(f"two ranks, {3 * len(MODES) + 1} module runs each: {time.monotonic() - t0:.1f} s")
     return res, _inputs()
 

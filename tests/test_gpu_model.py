@@ -13,6 +13,7 @@ from openvision_amd import preset, synth
 from openvision_amd.model import create_model, logits
 from openvision_amd.loss import ClipLoss
 from conftest import golden
+from ranks import run_child, run_ranks
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -128,11 +129,8 @@ def test_row_statistics_from_the_residual_epilogues_opt_in():
     over the residual stream.  Same parity bar as the default path (L/14 golden, fp32 reference, 1e-3 cosine on both weight sets'
     image embeddings) and rows stay bitwise batch-invariant across the three producers of the sums (skinny kernel at batch 1,
     stand-alone pass behind the non-persistent kernel at batch 40, persistent kernel's epilogue at batch 256)."""
-    import subprocess
-    import sys
     code = r"""
-import os, sys, numpy as np, torch
-sys.path.insert(0, os.environ["OV_ROOT"]); sys.path.insert(0, os.path.join(os.environ["OV_ROOT"], "tests"))
+import numpy as np, torch
 from openvision_amd import preset, synth
 from openvision_amd.model import create_model
 cfg = preset("vit-large-patch14-224")
@@ -150,10 +148,8 @@ for variant, gname in (("v1", "large14_224.npz"), ("sharp", "large14_224_sharp.n
         assert torch.equal(fb[:40], m.encode_image(big[:40])), "batch 40 vs 256"
 print("ok")
 """
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    p = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, OVHIP_ROWPARTS="1", OV_ROOT=root), stdout=subprocess.PIPE,
-                       stderr=subprocess.PIPE, text=True, timeout=900)
-    assert p.returncode == 0 and "ok" in p.stdout, p.stderr[-3000:]
+    p = run_child(code, env={"OVHIP_ROWPARTS": "1"}, timeout=900, gpu=True)
+    assert "ok" in p.stdout, p.stderr[-3000:]
 
 
 def test_zero_shot_cli_from_checkpoint_directory(tmp_path):
@@ -840,13 +836,9 @@ def test_chunked_tower_backward_is_bitwise_the_single_node_backward():
         assert all(torch.equal(a, b) for a, b in zip(outs[0], other))
 
 
-def _ddp_rank(rank, ws, store, q):
-    import sys
-    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+def _ddp_rank(rank, ws):
     import torch.distributed as dist
     from openvision_amd import training
-    from openvision_amd.loss import ClipLoss
-    dist.init_process_group("gloo", init_method=f"file://{store}", rank=rank, world_size=ws)
     cfg = preset("vit-tiny-patch16-160")
     m = create_model(cfg, device=DEV, state_dict=synth.make_state_dict(cfg))
     img, tok = synth.make_images(8, 160, seed=41), synth.make_captions(8, seed=41)
@@ -861,25 +853,14 @@ def _ddp_rank(rank, ws, store, q):
         out[name] = g / ws
     lt_ = loss.detach().float().cpu()
     dist.all_reduce(lt_)
-    q.put((rank, float(lt_ / ws), {k: v.numpy() for k, v in out.items()} if rank == 0 else None))
-    dist.barrier()
-    dist.destroy_process_group()
+    return rank, float(lt_ / ws), {k: v.numpy() for k, v in out.items()} if rank == 0 else None
 
 
 def test_data_parallel_training_matches_single_process():
     """The reference's training configuration (--local-loss --gather-with-grad, scripts/project/openvision/train.sh) on two ranks,
     gradients averaged as DDP does, against one process on the whole batch: same loss and the same gradients up to bf16 noise."""
-    import tempfile
-    import torch.multiprocessing as mp
     from openvision_amd import training
-    from openvision_amd.loss import ClipLoss
-    ctx = mp.get_context("spawn")
-    with tempfile.TemporaryDirectory() as d:
-        q = ctx.Queue()
-        ps = [ctx.Process(target=_ddp_rank, args=(r, 2, os.path.join(d, "store"), q)) for r in range(2)]
-        [p.start() for p in ps]
-        res = [q.get(timeout=600) for _ in range(2)]
-        [p.join(60) for p in ps]
+    res = run_ranks(_ddp_rank, 2, timeout=600, backend="gloo", gpu=True)
     dp_loss = res[0][1]
     dp_grads = next(r[2] for r in res if r[2] is not None)
     cfg = preset("vit-tiny-patch16-160")
@@ -950,13 +931,8 @@ def test_step_enqueues_without_host_synchronisation(tiny):
     assert torch.isfinite(li).all()
 
 
-def _nccl_ws1_rank(store, q):
-    import sys
-    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    import torch.distributed as dist
-    from openvision_amd.loss import ClipLoss, gather_features, _sum_over_ranks_own_chunk
-    torch.cuda.set_device(0)
-    dist.init_process_group("nccl", init_method=f"file://{store}", rank=0, world_size=1, device_id=torch.device(DEV))
+def _nccl_ws1_rank(rank, ws):
+    from openvision_amd.loss import gather_features, _sum_over_ranks_own_chunk
     g = torch.Generator().manual_seed(5)
     img = torch.nn.functional.normalize(torch.randn(24, 192, generator=g), dim=-1).to(DEV)
     txt = torch.nn.functional.normalize(img.cpu() * 0.5 + torch.randn(24, 192, generator=g) * 0.08, dim=-1).to(DEV)
@@ -974,19 +950,11 @@ def _nccl_ws1_rank(store, q):
         loss = fn(a, b, c)
         loss.backward()
         out[name] = (float(loss.detach()), a.grad.cpu().numpy(), b.grad.cpu().numpy(), float(c.grad))
-    q.put(out)
-    dist.barrier()
-    dist.destroy_process_group()
+    return out
 
 
-def _nccl_overlap_rank(store, q):
-    import sys
-    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    import torch.distributed as dist
+def _nccl_overlap_rank(rank, ws):
     from openvision_amd import training
-    from openvision_amd.loss import ClipLoss
-    torch.cuda.set_device(0)
-    dist.init_process_group("nccl", init_method=f"file://{store}", rank=0, world_size=1, device_id=torch.device(DEV))
     cfg = preset("vit-tiny-patch16-160")
     img, tok = synth.make_structured_images(8, 160, seed=11).to(DEV), synth.make_captions(8, seed=11).to(DEV)
     res = {}
@@ -1006,24 +974,14 @@ def _nccl_overlap_rank(store, q):
         torch.cuda.synchronize()
         res[mode] = (float(loss.detach()), launched, nb, {n: p.detach().float().cpu().numpy() for n, p in m.named_parameters()})
         training.set_backward_chunk_layers(0)
-    q.put(res)
-    dist.barrier()
-    dist.destroy_process_group()
+    return res
 
 
 def test_overlapped_gradient_exchange_on_rccl_world_size_1():
     """FusedAdamW.overlap_gradient_exchange with the collectives forced in a world of one rank on the 'nccl' backend: the RCCL
     all-reduces are issued from autograd's hooks while the chunked backward is still running, on the one GPU there is.  Loss and the
     UPDATED parameters (one AdamW step) must equal those of the plain sequence bit for bit (a sum over one rank is the identity)."""
-    import tempfile
-    import torch.multiprocessing as mp
-    ctx = mp.get_context("spawn")
-    with tempfile.TemporaryDirectory() as d:
-        q = ctx.Queue()
-        p = ctx.Process(target=_nccl_overlap_rank, args=(os.path.join(d, "store"), q))
-        p.start()
-        out = q.get(timeout=600)
-        p.join(120)
+    out, = run_ranks(_nccl_overlap_rank, 1, timeout=600, backend="nccl", gpu=True)
     l0, _, _, p0 = out["plain"]
     l1, launched, nb, p1 = out["overlap"]
     assert l0 == l1 and nb >= 2 and launched == nb
@@ -1036,15 +994,7 @@ def test_rccl_branch_of_the_loss_at_world_size_1():
     reduce_scatter_tensor in the gathered-side gradient routing -- executed on the one GPU there is: a world of one rank, with
     ClipLoss forced through its world_size > 1 branch.  Loss and every gradient must equal the plain single-process ClipLoss.
     (N > 1 scaling is unmeasured: no multi-GPU node was available to this build.)"""
-    import tempfile
-    import torch.multiprocessing as mp
-    ctx = mp.get_context("spawn")
-    with tempfile.TemporaryDirectory() as d:
-        q = ctx.Queue()
-        p = ctx.Process(target=_nccl_ws1_rank, args=(os.path.join(d, "store"), q))
-        p.start()
-        out = q.get(timeout=600)
-        p.join(120)
+    out, = run_ranks(_nccl_ws1_rank, 1, timeout=600, backend="nccl", gpu=True)
     assert out["gather_ok"] and out["rs_ok"]
     l0, gi0, gt0, gs0 = out["plain"]
     for name in ("coll_local", "coll_global"):

@@ -1,7 +1,6 @@
 """GPU: the fused multi-caption InfoNCE (csrc/multicap.hip behind openvision_amd.loss.MultiCaptionClipLoss) against the reference's
 ClipLoss run per caption set (tests/golden/multicap_grad.npz, made over gloo in float64), the float64 restatement of the JAX
 function (tests/multicap_restate.py) on the device, ov_clip_loss per set, and the two-caption training step."""
-import os
 
 import numpy as np
 import pytest
@@ -16,6 +15,7 @@ from openvision_amd.model import create_model
 import hipops as H
 import multicap_restate as MR
 from conftest import golden
+from ranks import run_ranks
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -222,13 +222,7 @@ def test_module_world_size_1(local_loss, gwg):
     np.testing.assert_allclose(one.last_terms.cpu().numpy(), ref.last_terms.cpu().numpy(), rtol=1e-5, atol=2e-5)
 
 
-def _nccl_ws1_rank(store, q):
-    import sys
-    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-    import torch.distributed as dist
-    torch.cuda.set_device(0)
-    dist.init_process_group("nccl", init_method=f"file://{store}", rank=0, world_size=1, device_id=torch.device(DEV))
+def _nccl_ws1_rank(rank, ws):
     img, sets, s = _module_inputs()
     out = {}
     for local_loss, gwg in MODES:
@@ -236,23 +230,13 @@ def _nccl_ws1_rank(store, q):
         fn.always_collective = True                          # all_gather_into_tensor (+ reduce_scatter_tensor) at world 1
         loss, gi, gt, gs = _module_run(fn, img, sets, s)
         out[(local_loss, gwg)] = (loss, gi.numpy(), gt.numpy(), gs)
-    q.put(out)
-    dist.barrier()
-    dist.destroy_process_group()
+    return out
 
 
 def test_rccl_branch_of_the_module_at_world_size_1():
     """The RCCL code path (packed all-gather read in place, packed gathered-side gradient, reduce-scatter) in a world of one rank.
     A detached gather with local_loss returns the local-side gradient alone; the other two modes return the whole gradient."""
-    import tempfile
-    import torch.multiprocessing as mp
-    ctx = mp.get_context("spawn")
-    with tempfile.TemporaryDirectory() as d:
-        q = ctx.Queue()
-        p = ctx.Process(target=_nccl_ws1_rank, args=(os.path.join(d, "store"), q))
-        p.start()
-        out = q.get(timeout=600)
-        p.join(120)
+    out, = run_ranks(_nccl_ws1_rank, 1, timeout=600, backend="nccl", gpu=True)
     img, sets, s = _module_inputs()
     for (local_loss, gwg), (loss, gi, gt, gs) in out.items():
         got = (loss, torch.from_numpy(gi), torch.from_numpy(gt), gs)

@@ -11,6 +11,7 @@ import torch
 
 from oracle import clip_ref as R
 import hipops as H
+from ranks import run_child, run_ranks
 H_ = H          # the attention tests use H for the head count
 
 pytestmark = pytest.mark.gpu
@@ -289,13 +290,9 @@ def test_clip_loss_autograd_golden_world_size_1():
         assert abs(float(ClipLoss()(img, txt, s)) - float(g["loss_ws1"])) < 1e-5
 
 
-def _lossgrad_rank(rank, ws, store, q):
-    import sys
-    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    import torch.distributed as dist
+def _lossgrad_rank(rank, ws):
     from conftest import golden
     from openvision_amd.loss import ClipLoss
-    dist.init_process_group("gloo", init_method=f"file://{store}", rank=rank, world_size=ws)
     g = golden("cliploss_grad.npz")
     b = g["img"].shape[0] // ws
     worst = {}
@@ -311,23 +308,13 @@ def _lossgrad_rank(rank, ws, store, q):
                           float((img.grad.cpu() - torch.from_numpy(g[tag + "_dimg"][rank])).abs().max()),
                           float((txt.grad.cpu() - torch.from_numpy(g[tag + "_dtxt"][rank])).abs().max()),
                           abs(float(s.grad) - float(g[tag + "_dscale"][rank])))
-    q.put((rank, worst))
-    dist.barrier()
-    dist.destroy_process_group()
+    return worst
 
 
 def test_clip_loss_autograd_golden_world_size_2():
     """Two ranks (gloo rendezvous, both on this one GPU): loss and gradients per rank vs the reference's, for every
     local_loss x gather_with_grad routing of gather_features (loss.py:19-63)."""
-    import tempfile
-    import torch.multiprocessing as mp
-    ctx = mp.get_context("spawn")
-    with tempfile.TemporaryDirectory() as d:
-        q = ctx.Queue()
-        ps = [ctx.Process(target=_lossgrad_rank, args=(r, 2, os.path.join(d, "store"), q)) for r in range(2)]
-        [p.start() for p in ps]
-        res = dict(q.get(timeout=300) for _ in range(2))
-        [p.join(60) for p in ps]
+    res = run_ranks(_lossgrad_rank, 2, timeout=300, backend="gloo", gpu=True)
     for rank in range(2):
         for tag, (dl, di, dt, ds) in res[rank].items():
             assert dl < 1e-5 and di < 2e-6 and dt < 2e-6 and ds < 2e-6, (rank, tag, dl, di, dt, ds)
@@ -772,10 +759,9 @@ def test_gemm_kernel_variants_agree_bitwise_with_the_default(variant):
     and the skinny small-M kernel forced onto every shape (4: by default it serves grids of <= 96 of the big kernels' tiles)
     accumulate the same products in the same order and share the epilogue arithmetic: every epilogue's output must equal the default
     persistent kernel's bit for bit, on ragged shapes too."""
-    import subprocess, sys, tempfile
+    import tempfile
     code = r"""
-import os, sys, torch
-sys.path.insert(0, os.environ["OV_ROOT"]); sys.path.insert(0, os.path.join(os.environ["OV_ROOT"], "tests"))
+import torch
 import hipops as H
 g = torch.Generator().manual_seed(3)
 outs = []
@@ -793,13 +779,11 @@ for (M, N, K) in ((2048, 1024, 256), (65792, 1024, 256), (1500, 776, 320), (7000
             outs.append(H.gemm_ln(a, w, b, cs, st, epi=epi).cpu())
 torch.save(outs, sys.argv[1])
 """
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     res = {}
     with tempfile.TemporaryDirectory() as d:
         for v in ("0", variant):
             path = os.path.join(d, f"v{v}.pt")
-            env = dict(os.environ, OVHIP_GEMM_VARIANT=v, OV_ROOT=root)
-            subprocess.run([sys.executable, "-c", code, path], check=True, env=env, timeout=600)
+            run_child(code, path, env={"OVHIP_GEMM_VARIANT": v}, timeout=600, gpu=True)
             res[v] = torch.load(path)
     assert len(res["0"]) == 49
     for i, (x, y) in enumerate(zip(res["0"], res[variant])):

@@ -18,8 +18,6 @@ test_param_grad_bound.py (CPU) pins what the bounds can see."""
 import functools
 import hashlib
 import os
-import subprocess
-import sys
 import tempfile
 
 import pytest
@@ -27,6 +25,7 @@ import torch
 
 import hipops as H
 from hipops import GELU_DH, LINEAR_NK, LINEAR_TN_M, LINEAR_TR_M, LN_SHAPES
+from ranks import run_child
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -151,8 +150,7 @@ def test_linear_backward_subsets(N, K):
 
 
 _CHILD = r"""
-import hashlib, os, sys, torch
-sys.path.insert(0, os.environ["OV_ROOT"]); sys.path.insert(0, os.path.join(os.environ["OV_ROOT"], "tests"))
+import hashlib, torch
 import hipops as H
 sha = lambda t: hashlib.sha256(t.cpu().contiguous().view(torch.uint8).numpy().tobytes()).hexdigest()
 res = []
@@ -171,12 +169,10 @@ def test_linear_backward_routes_agree_bitwise_on_dw():
     the same dW".  db is summed per 64-row tile there and per range here: inside its bound, not necessarily the same bits."""
     N, K = 192, 320
     cases = [linear_case(M, N, K) for M in (1088, 512)]
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     with tempfile.TemporaryDirectory() as d:
         src, path = os.path.join(d, "cases.pt"), os.path.join(d, "out.pt")
         torch.save([c[0] for c in cases], src)
-        env = dict(os.environ, OVHIP_DW_TRANSPOSE="1", OV_ROOT=root)
-        subprocess.run([sys.executable, "-c", _CHILD, src, path], check=True, env=env, timeout=300)
+        run_child(_CHILD, src, path, env={"OVHIP_DW_TRANSPOSE": "1"}, timeout=300, gpu=True)
         res = torch.load(path)
     for ((dy, x, w), ref, bounds), child in zip(cases, res):
         M = dy.shape[0]

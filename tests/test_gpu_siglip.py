@@ -2,7 +2,6 @@
 (tests/golden/siglip_grad.npz, made over gloo in float64) and the float64 restatement (tests/siglip_restate.py), and the SigLIP
 training path: CLIP's logit_bias through training.clip_forward, FusedAdamW and two data-parallel ranks."""
 import math
-import os
 
 import numpy as np
 import pytest
@@ -15,6 +14,7 @@ from openvision_amd.model import create_model
 
 import siglip_restate as SR
 from conftest import golden
+from ranks import run_ranks
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -145,13 +145,7 @@ def test_siglip_loss_module_world_size_1():
             close(bi.grad.reshape(1), [float(rdb)], 1e-5, "d bias")
 
 
-def _nccl_ws1_rank(store, q):
-    import sys
-    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    import torch.distributed as dist
-    from openvision_amd.loss import SigLipLoss
-    torch.cuda.set_device(0)
-    dist.init_process_group("nccl", init_method=f"file://{store}", rank=0, world_size=1, device_id=torch.device(DEV))
+def _nccl_ws1_rank(rank, ws):
     g = torch.Generator().manual_seed(5)
     img = torch.nn.functional.normalize(torch.randn(24, 192, generator=g), dim=-1).to(DEV)
     txt = torch.nn.functional.normalize(img.cpu() + torch.randn(24, 192, generator=g) * 0.1, dim=-1).to(DEV)
@@ -164,23 +158,13 @@ def _nccl_ws1_rank(store, q):
         loss = fn(a, b, c, d)
         loss.backward()
         out[name] = (float(loss.detach()), a.grad.cpu().numpy(), b.grad.cpu().numpy(), float(c.grad), float(d.grad))
-    q.put(out)
-    dist.barrier()
-    dist.destroy_process_group()
+    return out
 
 
 def test_rccl_branch_of_siglip_loss_at_world_size_1():
     """The RCCL code path of SigLipLoss (text all-gather, reduce-scatter of the gathered-side gradient) in a world of one rank:
     loss and every gradient equal the plain single-process call."""
-    import tempfile
-    import torch.multiprocessing as mp
-    ctx = mp.get_context("spawn")
-    with tempfile.TemporaryDirectory() as d:
-        q = ctx.Queue()
-        p = ctx.Process(target=_nccl_ws1_rank, args=(os.path.join(d, "store"), q))
-        p.start()
-        out = q.get(timeout=600)
-        p.join(120)
+    out, = run_ranks(_nccl_ws1_rank, 1, timeout=600, backend="nccl", gpu=True)
     l0, gi0, gt0, gs0, gb0 = out["plain"]
     l, gi, gt, gs, gb = out["coll"]
     assert l == l0 and gs == gs0 and gb == gb0
@@ -254,14 +238,9 @@ def test_siglip_training_step_gradients_tiny():
     assert float(m.logit_bias.detach()) != -10.0
 
 
-def _ddp_rank(rank, ws, store, q):
-    import sys
-    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+def _ddp_rank(rank, ws):
     import torch.distributed as dist
     from openvision_amd import training
-    from openvision_amd.loss import SigLipLoss
-    dist.init_process_group("gloo", init_method=f"file://{store}", rank=rank, world_size=ws)
     cfg, sd = _siglip_cfg_sd()
     m = create_model(cfg, device=DEV, state_dict=sd)
     img, tok = synth.make_images(8, 160, seed=41), synth.make_captions(8, seed=41)
@@ -276,24 +255,14 @@ def _ddp_rank(rank, ws, store, q):
         out[name] = g / ws
     lt_ = loss.detach().float().cpu()
     dist.all_reduce(lt_)
-    q.put((rank, float(lt_ / ws), {k: v.numpy() for k, v in out.items()} if rank == 0 else None))
-    dist.barrier()
-    dist.destroy_process_group()
+    return rank, float(lt_ / ws), {k: v.numpy() for k, v in out.items()} if rank == 0 else None
 
 
 def test_data_parallel_siglip_matches_single_process():
     """Two ranks (gloo, one GPU) on half batches, gradients averaged as DDP does, against one process on the whole batch: the
     mean of the ranks' losses is the whole-batch loss, and the gradients agree up to bf16 noise."""
-    import tempfile
-    import torch.multiprocessing as mp
     from openvision_amd import training
-    ctx = mp.get_context("spawn")
-    with tempfile.TemporaryDirectory() as d:
-        q = ctx.Queue()
-        ps = [ctx.Process(target=_ddp_rank, args=(r, 2, os.path.join(d, "store"), q)) for r in range(2)]
-        [p.start() for p in ps]
-        res = [q.get(timeout=600) for _ in range(2)]
-        [p.join(60) for p in ps]
+    res = run_ranks(_ddp_rank, 2, timeout=600, backend="gloo", gpu=True)
     dp_loss = res[0][1]
     dp_grads = next(r[2] for r in res if r[2] is not None)
     cfg, sd = _siglip_cfg_sd()

@@ -1,12 +1,12 @@
 """CPU: the one statement of the gathered-side gradient routing (openvision_amd.loss.route_gradient) on two gloo ranks against the
 sums written out, and the two layouts of the gathered-gradient buffer (openvision_amd.loss.gathered_gradient_buffer) element by
 element.  The three InfoNCE-type backwards (ClipLoss / MultiCaptionClipLoss / DistillClipLoss) call exactly these two."""
-import os
-
 import pytest
 import torch
 
 from openvision_amd import loss as L
+
+from ranks import run_ranks
 
 WS, B, E = 2, 3, 8
 WIDTHS = (2 * E, 3 * E)                     # ClipLoss / DistillClipLoss's student half, and two caption sets
@@ -23,12 +23,7 @@ def _grads(w):
     return loc, glo, gat
 
 
-def _gloo_rank(rank, ws, store, q):
-    import sys
-    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    import torch.distributed as dist
-    from openvision_amd import loss as L
-    dist.init_process_group("gloo", init_method=f"file://{store}", rank=rank, world_size=ws)
+def _gloo_rank(rank, ws):
     out = {}
     for w in WIDTHS:
         loc, glo, gat = _grads(w)
@@ -40,23 +35,13 @@ def _gloo_rank(rank, ws, store, q):
             out[(w, local_loss, gwg, "single")] = L.route_gradient(loc[rank].clone(), gat[rank][:B].clone(), B, rank, False,
                                                                    local_loss, gwg)
     # plain arrays on the queue: a tensor travels as a shared file descriptor, which needs this process alive when the parent reads
-    q.put((rank, {k: v.numpy().copy() for k, v in out.items()}))
-    dist.barrier()
-    dist.destroy_process_group()
+    return {k: v.numpy().copy() for k, v in out.items()}
 
 
 def test_route_gradient_in_every_mode_over_gloo():
     """Two gloo ranks on CPU tensors, b = 3, W = 2 E and 3 E: what route_gradient returns on each rank in the four collective modes
     and without a collective, against the sums it stands for."""
-    import tempfile
-    import torch.multiprocessing as mp
-    ctx = mp.get_context("spawn")
-    with tempfile.TemporaryDirectory() as d:
-        q = ctx.Queue()
-        ps = [ctx.Process(target=_gloo_rank, args=(r, WS, os.path.join(d, "store"), q)) for r in range(WS)]
-        [p.start() for p in ps]
-        res = {rank: {k: torch.from_numpy(v) for k, v in out.items()} for rank, out in (q.get(timeout=300) for _ in range(WS))}
-        [p.join(60) for p in ps]
+    res = [{k: torch.from_numpy(v) for k, v in out.items()} for out in run_ranks(_gloo_rank, WS, timeout=300, backend="gloo")]
     for w in WIDTHS:
         loc, glo, gat = _grads(w)
         for rank in range(WS):

@@ -16,6 +16,7 @@ from oracle import clip_ref as R
 
 import multicap_restate as MR
 from conftest import golden
+from ranks import run_ranks
 
 IDS = [c[0] for c in MR.CASES]
 
@@ -230,12 +231,7 @@ def test_forwards_refuse_a_text_batch_that_is_no_multiple(monkeypatch):
         assert nb == 4 and seen.shape[0] == 4 and torch.equal(seen[:, 0, 0], torch.arange(4.0))     # the first set's tokens only
 
 
-def _gloo_rank(rank, ws, store, q):
-    import sys
-    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    import torch.distributed as dist
-    from openvision_amd import loss as L
-    dist.init_process_group("gloo", init_method=f"file://{store}", rank=rank, world_size=ws)
+def _gloo_rank(rank, ws):
     b, e, c = 3, 8, 2
     log = []
     L.record_comm(log)
@@ -248,24 +244,14 @@ def _gloo_rank(rank, ws, store, q):
     fulls = [torch.randn(ws * b, (1 + c) * e, generator=g) for _ in range(ws)]
     summed = L.route_packed_gradient(fulls[rank].clone(), b, rank, True)
     own = L.route_packed_gradient(fulls[rank].clone(), b, rank, False)
-    q.put((rank, packed, len(log), summed.clone(), own.clone(), fulls))
-    dist.barrier()
-    dist.destroy_process_group()
+    return packed, len(log), summed.clone(), own.clone(), fulls
 
 
 def test_packed_gather_and_gradient_routing_over_gloo():
     """Two gloo ranks on CPU tensors: ONE collective gathers the packed [b, (1 + C) E] rows in rank order, the columns split into
     the image and the C sets, and a packed gathered-side gradient is routed as each mode prescribes."""
-    import tempfile
-    import torch.multiprocessing as mp
-    ctx = mp.get_context("spawn")
     ws, b, e, c = 2, 3, 8, 2
-    with tempfile.TemporaryDirectory() as d:
-        q = ctx.Queue()
-        ps = [ctx.Process(target=_gloo_rank, args=(r, ws, os.path.join(d, "store"), q)) for r in range(ws)]
-        [p.start() for p in ps]
-        res = {r[0]: r[1:] for r in (q.get(timeout=300) for _ in range(ws))}
-        [p.join(60) for p in ps]
+    res = run_ranks(_gloo_rank, ws, timeout=300, backend="gloo")
     for rank in range(ws):
         packed, ncoll, summed, own, fulls = res[rank]
         assert ncoll == 1 and packed.shape == (ws * b, (1 + c) * e)

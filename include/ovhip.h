@@ -23,6 +23,7 @@
  *   ov_siglip_loss      SigLipLoss._loss summed over every text block          loss.py:307-414
  *   ov_gemm_fp8         the same nn.Linear on fp8 e4m3 operands (config #5)           transformer.py:225,232-236
  *   ov_preprocess_image transforms.Resize -> ToTensor -> Normalize (Pillow-exact)  ov-zero-shot-test.py:72-77, transform.py:355-392
+ *   ov_train_transform  RandomResizedCrop -> color_jitter -> gray_scale -> ToTensor -> Normalize, a batch per call   transform.py:307-358
  *   ov_class_mean_normalize / ov_topk   zero-shot classifier weights, argmax / recall@k ranking   zero_shot_classifier.py:54-57,
  *                       src/evaluators/proj/image_text/{discriminative_classifier.py:305-323, image_text_retrieval.py:24-87}
  *   ov_tower_*          Transformer.forward (the resblock loop)               transformer.py:355-366, 254-265
@@ -341,6 +342,35 @@ int ov_preprocess_image(const unsigned char* src, int H, int W, const int* bound
                         const int* bounds_y, const int* coef_y, int ksize_y, int Hr, int row0, int nrows, unsigned char* tmp,
                         int crop_x, int crop_y, int out_h, int out_w, const float* mean, const float* stdv, void* out,
                         int out_dtype, ov_stream_t stream);
+
+/* ---- training image transform: batched crop, resize, colour jitter, grayscale, ToTensor, Normalize ------------------------
+ * The training branch of open_clip.transform.image_transform (transform.py:307-358) on PIL images, after its random numbers are
+ * drawn: img.crop(box).resize((out_w, out_h)) in Pillow's fixed-point arithmetic, ImageEnhance.Brightness / Contrast / Color and
+ * convert("L") in Pillow's, then x / 255 and (x - mean) / std in IEEE fp32.  One call per batch of variable-sized images, at
+ * most 4 + contrast_passes launches whatever B is.
+ *   pixels   uint8, the images packed back to back, pixel_bytes in all; image b is RGB [H_b, W_b, 3] at pixels + offsets[b]
+ *   offsets  int64 [B]; shapes int32 [B, 2] = (H, W); boxes int32 [B, 4] = (top, left, h, w), inside the image and h, w > 0
+ *            (the caller checks; an image whose box is not is never read and comes out as the normalised black image)
+ *   ops      int32 [B, 4]: the colour operations in application order (enum ov_color_op); factors fp32 [B, 4]: the blend factor
+ *            of a brightness / contrast / saturation operation (unused for the others)
+ *   max_rows >= every box's h.  max_taps_x / max_taps_y >= ceil(fsupport * max(extent / out, 1)) * 2 + 1 over the boxes' w / h,
+ *            fsupport = 1 (bilinear) or 2 (bicubic): the row length of the coefficient tables.
+ *   contrast_passes  the largest number of contrast operations any one image carries (0: the statistics launch is skipped)
+ *   mean / stdv  HOST float[3];  out: [B, 3, out_h, out_w] in out_dtype (OV_F32 / OV_BF16)
+ *   workspace    ov_train_transform_workspace_bytes(...) bytes, 16-byte aligned: the tables, the horizontal intermediate
+ *                [B, max_rows, out_w, 3], the resized uint8 image [B, out_h, out_w, 3] and the per-image sums of L.
+ * ov_train_transform_plan is the first launch on its own: bounds_x int32 [B, out_w, 2] = (first source index relative to the
+ * crop, tap count) and taps_x int32 [B, out_w, max_taps_x] (22-bit fixed point, zero padded) for extent w_b -> out_w, the same
+ * for y over h_b -> out_h; Resample.c precompute_coeffs + normalize_coeffs_8bpc in fp64 without contraction. */
+enum ov_interp { OV_INTERP_BILINEAR = 0, OV_INTERP_BICUBIC = 1 };
+enum ov_color_op { OV_COLOR_NONE = 0, OV_COLOR_BRIGHTNESS = 1, OV_COLOR_CONTRAST = 2, OV_COLOR_SATURATION = 3, OV_COLOR_GRAYSCALE = 4 };
+size_t ov_train_transform_workspace_bytes(int B, int out_h, int out_w, int max_rows, int max_taps_x, int max_taps_y);
+int ov_train_transform_plan(const int* boxes, int B, int out_h, int out_w, int interpolation, int max_taps_x, int max_taps_y,
+                            int* bounds_x, int* taps_x, int* bounds_y, int* taps_y, ov_stream_t stream);
+int ov_train_transform(const unsigned char* pixels, int64_t pixel_bytes, const int64_t* offsets, const int* shapes, const int* boxes,
+                       const int* ops, const float* factors, int B, int out_h, int out_w, int max_rows, int interpolation,
+                       int max_taps_x, int max_taps_y, int contrast_passes, const float* mean, const float* stdv, void* out,
+                       int out_dtype, void* workspace, size_t workspace_bytes, ov_stream_t stream);
 
 /* ---- consumers of encode + logits: zero-shot classifier weights and ranking ------------
  * out[c,:] = normalize(mean_t emb[c*T + t, :])   (open_clip/zero_shot_classifier.py:54-57).  fp32 in/out. */

@@ -21,6 +21,7 @@
 //   P^T = exp2(S^T - m)    packed pairwise to bf16: the accumulator tile IS the next B operand
 //   O^T += V^T . P^T       (V^T fragments via the transposing LDS read)
 #include "common.h"
+#include "attn_tile.h"
 #include <stdlib.h>
 
 namespace {
@@ -52,24 +53,7 @@ __device__ __forceinline__ bf16x8_t tr_pair(const char* p0, const char* p1) {
 // of head j+1 into the other slot is issued and runs under the MFMAs/softmax of head j -- HBM reads overlap compute.
 // The kernel is sized for <= 168 VGPRs (3 waves on the busiest SIMD at L = 257), which leaves room to fetch all K and V
 // fragments of a key tile ahead of the MFMAs that use them.
-// Transposing LDS reads issued from inline asm: hipcc treats the ds_read_tr builtin as possibly aliasing the LDS-DMA
-// (global_load_lds) writes of the NEXT head and would drain them with vmcnt(0) before every V read, serialising the
-// prefetch.  The asm forms are invisible to its memory model; completion is enforced by tr_wait(), which names every
-// destination "+v" (cdna guide 5.7 form ii) so no consumer can be scheduled above the lgkmcnt wait.
-__device__ __forceinline__ u32x2_t tr_read_asm(const char* p) {
-    u32x2_t v;
-    const unsigned addr = (unsigned)(uintptr_t)(__attribute__((address_space(3))) const char*)p;
-    asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v) : "v"(addr));
-    return v;
-}
-__device__ __forceinline__ void tr_wait(u32x2_t (&t)[8]) {
-    asm volatile("s_waitcnt lgkmcnt(0)"
-                 : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]), "+v"(t[4]), "+v"(t[5]), "+v"(t[6]), "+v"(t[7]));
-}
-__device__ __forceinline__ bf16x8_t tr_join(u32x2_t a, u32x2_t b) {
-    const u32x4_t w = {a[0], a[1], b[0], b[1]};
-    return __builtin_bit_cast(bf16x8_t, w);
-}
+// The V fragments come by transposing LDS reads issued from inline asm (attn::read_v, completed by attn::tr_wait).
 
 // 4 floats -> 4 e4m3 bytes (saturating)
 __device__ __forceinline__ unsigned pack_fp8x4(float a, float b, float c, float d) {
@@ -120,11 +104,6 @@ __device__ __forceinline__ void stage_head(const AttnPArgs& a, int bh, char* slo
     }
 }
 
-__device__ __forceinline__ float max3_asm(float x, float y, float z) {       // no canonicalising v_max in front
-    float d;
-    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(d) : "v"(x), "v"(y), "v"(z));
-    return d;
-}
 typedef float f32x2_t __attribute__((ext_vector_type(2)));
 // p = exp2(s * c - m) on 16 scores, two per v_pk_fma_f32 / v_pk_add_f32 (the softmax is VALU-issue bound; v_exp has no
 // packed form); acc collects the two interleaved partial row sums.
@@ -140,12 +119,6 @@ __device__ __forceinline__ void exp_rows(f32x16_t& s, float c, float nm, f32x2_t
         s[2 * i] = v[0];
         s[2 * i + 1] = v[1];
     }
-}
-template <int OFF>
-__device__ __forceinline__ u32x2_t tr_read_off(unsigned addr) {
-    u32x2_t v;
-    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
-    return v;
 }
 
 // DEEP = workgroups of <= 8 waves (2 per SIMD, 256 VGPRs each): both K tiles of the next step are fetched behind the S MFMAs
@@ -246,24 +219,6 @@ __global__ __launch_bounds__(DEEP ? 512 : 640, DEEP ? 2 : 3) void attn_fwd_hd64_
 #pragma unroll
             for (int st = 0; st < 4; ++st) kf[st] = *(const bf16x8_t*)(ks + (kp ^ (unsigned)(st * 32)));
         };
-        auto mask_tail = [&](f32x16_t& sc, int kt) {
-            if (kt * 32 + 32 > L) {
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const int key = kt * 32 + (i & 3) + 8 * (i >> 2) + 4 * h2;
-                    if (key >= L) sc[i] = -INFINITY;
-                }
-            }
-        };
-        auto tile_max = [&](const f32x16_t& sc) {
-            float mx = max3_asm(max3_asm(sc[0], sc[1], sc[2]), max3_asm(sc[3], sc[4], sc[5]), max3_asm(sc[6], sc[7], sc[8]));
-            return max3_asm(mx, max3_asm(sc[9], sc[10], sc[11]), max3_asm(max3_asm(sc[12], sc[13], sc[14]), sc[15], sc[15]));
-        };
-        auto pack_p = [&](const f32x16_t& sc, int st) {
-            const u32x4_t w = {pack_bf16x2(sc[8 * st + 0], sc[8 * st + 1]), pack_bf16x2(sc[8 * st + 2], sc[8 * st + 3]),
-                               pack_bf16x2(sc[8 * st + 4], sc[8 * st + 5]), pack_bf16x2(sc[8 * st + 6], sc[8 * st + 7])};
-            return __builtin_bit_cast(bf16x8_t, w);
-        };
         const int npair = nk_tiles >> 1;
         load_k(kfa, 0);
         if (DEEP && npair > 0) load_k(kfb, 1);
@@ -272,22 +227,11 @@ __global__ __launch_bounds__(DEEP ? 512 : 640, DEEP ? 2 : 3) void attn_fwd_hd64_
             const unsigned va0 = ks_u + kt * 2048 + v_lane0, va1 = ks_u + kt * 2048 + v_lane1;
             if (!DEEP) load_k(kfb, kt + 1);                            // second tile's K: covered by the first tile's MFMAs
             u32x2_t vt[8], vu[8];
-            auto read_vt = [&]() {
-                vt[0] = tr_read_off<0>(va0);    vt[1] = tr_read_off<512>(va0);
-                vt[2] = tr_read_off<0>(va1);    vt[3] = tr_read_off<512>(va1);
-                vt[4] = tr_read_off<1024>(va0); vt[5] = tr_read_off<1536>(va0);
-                vt[6] = tr_read_off<1024>(va1); vt[7] = tr_read_off<1536>(va1);
-            };
             // 9+ waves (3 per SIMD: 168 VGPRs): the first tile's V fragments are fetched behind the S MFMAs instead of in front
             // of them -- still a whole softmax ahead of their use, and 16 registers fewer while both K tiles are live (the kernel
             // spilled 10 VGPRs otherwise, which the inline-asm loads and counted waits must not meet: tests/test_build_scratch.py)
-            if (DEEP) read_vt();
-            if (DEEP) {
-                vu[0] = tr_read_off<2048>(va0); vu[1] = tr_read_off<2560>(va0);
-                vu[2] = tr_read_off<2048>(va1); vu[3] = tr_read_off<2560>(va1);
-                vu[4] = tr_read_off<3072>(va0); vu[5] = tr_read_off<3584>(va0);
-                vu[6] = tr_read_off<3072>(va1); vu[7] = tr_read_off<3584>(va1);
-            }
+            if (DEEP) attn::read_v<0>(vt, va0, va1);
+            if (DEEP) attn::read_v<2048>(vu, va0, va1);
             f32x16_t sa, sb;
 #pragma unroll
             for (int i = 0; i < 16; ++i) { sa[i] = 0.f; sb[i] = 0.f; }
@@ -295,49 +239,27 @@ __global__ __launch_bounds__(DEEP ? 512 : 640, DEEP ? 2 : 3) void attn_fwd_hd64_
             for (int st = 0; st < 4; ++st) sa = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfa[st], qf[st], sa, 0, 0, 0);
 #pragma unroll
             for (int st = 0; st < 4; ++st) sb = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfb[st], qf[st], sb, 0, 0, 0);
-            if (!DEEP) read_vt();
+            if (!DEEP) attn::read_v<0>(vt, va0, va1);
             if (kt + 2 < nk_tiles) load_k(kfa, kt + 2);                // next step's first tile, fetched under the softmax
             else if (DEEP) asm volatile("s_nop 7" : "+v"(sb));         // last step of an even tile count: nothing else separates the sb
-                                                                       // MFMAs from tile_max's inline-asm reads (see the single-tile step)
+                                                                       // MFMAs from tile_max's inline-asm reads (see attn::tile_max)
             if (DEEP && kt + 3 < nk_tiles) load_k(kfb, kt + 3);
-            mask_tail(sb, kt + 1);
-            float mx = fmaxf(tile_max(sa), tile_max(sb));
-            {
-                const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(mx), __float_as_uint(mx), false, false);
-                mx = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1])) * a.scale_log2;
-            }
-            if (!__all(mx - m <= 8.0f)) {
-                const float mn = fmaxf(m, mx);
-                const float alpha = __builtin_amdgcn_exp2f(m - mn);
-                m = mn;
-                lsum *= alpha;
-#pragma unroll
-                for (int i = 0; i < 16; ++i) { o0[i] *= alpha; o1[i] *= alpha; }
-            }
+            attn::mask_tail(sb, kt + 1, h2, L);
+            const float mx = attn::half_max(fmaxf(attn::tile_max(sa), attn::tile_max(sb)), a.scale_log2);
+            OV_ATTN_RESCALE(mx, m, lsum, o0, o1)
             const float nm = -m;
             f32x2_t ps = {0.f, 0.f};
             exp_rows(sa, a.scale_log2, nm, ps);
             exp_rows(sb, a.scale_log2, nm, ps);
             lsum += ps[0] + ps[1];
-            const bf16x8_t pa0 = pack_p(sa, 0), pa1 = pack_p(sa, 1), pb0 = pack_p(sb, 0), pb1 = pack_p(sb, 1);
-            tr_wait(vt);
+            const bf16x8_t pa0 = attn::pack_p(sa, 0), pa1 = attn::pack_p(sa, 1), pb0 = attn::pack_p(sb, 0), pb1 = attn::pack_p(sb, 1);
+            attn::tr_wait(vt);
             __builtin_amdgcn_sched_barrier(0);
-            if (!DEEP) {   // second tile's V fragments: their LDS latency hides under the first tile's four P.V MFMAs
-                vu[0] = tr_read_off<2048>(va0); vu[1] = tr_read_off<2560>(va0);
-                vu[2] = tr_read_off<2048>(va1); vu[3] = tr_read_off<2560>(va1);
-                vu[4] = tr_read_off<3072>(va0); vu[5] = tr_read_off<3584>(va0);
-                vu[6] = tr_read_off<3072>(va1); vu[7] = tr_read_off<3584>(va1);
-            }
-            o0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_join(vt[0], vt[1]), pa0, o0, 0, 0, 0);
-            o1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_join(vt[2], vt[3]), pa0, o1, 0, 0, 0);
-            o0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_join(vt[4], vt[5]), pa1, o0, 0, 0, 0);
-            o1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_join(vt[6], vt[7]), pa1, o1, 0, 0, 0);
-            tr_wait(vu);
+            if (!DEEP) attn::read_v<2048>(vu, va0, va1);   // second tile's V fragments: their LDS latency hides under the first tile's four P.V MFMAs
+            attn::pv_mma(vt, pa0, pa1, o0, o1);
+            attn::tr_wait(vu);
             __builtin_amdgcn_sched_barrier(0);
-            o0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_join(vu[0], vu[1]), pb0, o0, 0, 0, 0);
-            o1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_join(vu[2], vu[3]), pb0, o1, 0, 0, 0);
-            o0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_join(vu[4], vu[5]), pb1, o0, 0, 0, 0);
-            o1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_join(vu[6], vu[7]), pb1, o1, 0, 0, 0);
+            attn::pv_mma(vu, pb0, pb1, o0, o1);
         }
         if (j + 1 < n) load_q(qn, bh + gridDim.x);                   // next head's Q rows, live only across the tail step
         if (lone_key) {
@@ -347,55 +269,23 @@ __global__ __launch_bounds__(DEEP ? 512 : 640, DEEP ? 2 : 3) void attn_fwd_hd64_
             // (its d range), 16 v_dot2 give q.k, then one exp2 and 32 FMAs with the key's V row.
             float s0 = 0.f, s1 = 0.f;
 #pragma unroll
-            for (int st = 0; st < 4; ++st) {
-                const u32x4_t kq = __builtin_bit_cast(u32x4_t, kfa[st]), qq = __builtin_bit_cast(u32x4_t, qf[st]);
-                // inline asm: hipcc's lowering of the fdot2 builtin on dwords extracted from the fragments picked dword 0 of every
-                // fragment for all four products (checked in the ISA)
-                asm("v_dot2c_f32_bf16 %0, %1, %2" : "+v"(s0) : "v"(qq[0]), "v"(kq[0]));
-                asm("v_dot2c_f32_bf16 %0, %1, %2" : "+v"(s1) : "v"(qq[1]), "v"(kq[1]));
-                asm("v_dot2c_f32_bf16 %0, %1, %2" : "+v"(s0) : "v"(qq[2]), "v"(kq[2]));
-                asm("v_dot2c_f32_bf16 %0, %1, %2" : "+v"(s1) : "v"(qq[3]), "v"(kq[3]));
-            }
-            asm("s_nop 2" : "+v"(s0), "+v"(s1));                      // DOT result -> ordinary VALU read: 3 wait states the assembler
-                                                                      // does not insert inside inline asm
-            float sd = s0 + s1;                                       // this lane's half of d; the other half sits in lane ^ 32
-            {
-                const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(sd), __float_as_uint(sd), false, false);
-                sd = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
-            }
-            // the key's V row: d = 8 g + 4 h2 + e (o0), + 32 (o1): four 8-byte reads per d-half of the V image
-            const char* vrow = ks + KC * 128 + (L - 1) * 64 + 8 * h2;
-            u32x2_t v0[4];                                            // d-half 0 now, d-half 1 into the same registers afterwards
+            for (int st = 0; st < 4; ++st) attn::lone_dot(s0, s1, qf[st], kfa[st]);
+            const float sd = attn::lone_sum(s0, s1);
+            const char* vrow = ks + KC * 128 + (L - 1) * 64 + 8 * h2;    // the key's V row, d-half 0 (half 1: + KC * 64)
+            u32x2_t v0[4];                                              // d-half 0 now, d-half 1 into the same registers afterwards
 #pragma unroll
-            for (int g = 0; g < 4; ++g) v0[g] = *(const u32x2_t*)(vrow + g * 16);
+            for (int g = 0; g < 4; ++g) v0[g] = attn::vrow_piece(vrow, g);
             const float mx = sd * a.scale_log2;
-            if (!__all(mx - m <= 8.0f)) {
-                const float mn = fmaxf(m, mx);
-                const float alpha = __builtin_amdgcn_exp2f(m - mn);
-                m = mn;
-                lsum *= alpha;
+            OV_ATTN_RESCALE(mx, m, lsum, o0, o1)
+            const float pk = attn::lone_weight(mx, m);
+            lsum += attn::count_once(pk, h2);
 #pragma unroll
-                for (int i = 0; i < 16; ++i) { o0[i] *= alpha; o1[i] *= alpha; }
-            }
-            const float pk = __builtin_amdgcn_exp2f(mx - m);
-            lsum += h2 ? 0.f : pk;                                    // the halves' sums are added at the end: count the key once
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                o0[4 * g + 0] = fmaf(pk, bf16lo_to_f32(v0[g][0]), o0[4 * g + 0]);
-                o0[4 * g + 1] = fmaf(pk, bf16hi_to_f32(v0[g][0]), o0[4 * g + 1]);
-                o0[4 * g + 2] = fmaf(pk, bf16lo_to_f32(v0[g][1]), o0[4 * g + 2]);
-                o0[4 * g + 3] = fmaf(pk, bf16hi_to_f32(v0[g][1]), o0[4 * g + 3]);
-            }
+            for (int g = 0; g < 4; ++g) attn::fold4(o0, g, pk, v0[g]);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int g = 0; g < 4; ++g) v0[g] = *(const u32x2_t*)(vrow + KC * 64 + g * 16);
+            for (int g = 0; g < 4; ++g) v0[g] = attn::vrow_piece(vrow + KC * 64, g);
 #pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                o1[4 * g + 0] = fmaf(pk, bf16lo_to_f32(v0[g][0]), o1[4 * g + 0]);
-                o1[4 * g + 1] = fmaf(pk, bf16hi_to_f32(v0[g][0]), o1[4 * g + 1]);
-                o1[4 * g + 2] = fmaf(pk, bf16lo_to_f32(v0[g][1]), o1[4 * g + 2]);
-                o1[4 * g + 3] = fmaf(pk, bf16hi_to_f32(v0[g][1]), o1[4 * g + 3]);
-            }
+            for (int g = 0; g < 4; ++g) attn::fold4(o1, g, pk, v0[g]);
         } else if (nk_tiles & 1) {
             const int kt = nk_tiles - 1;
             // the lane's V-image offset, re-derived behind an opaque asm (see row_offset: not a second live copy of v_lane0)
@@ -405,52 +295,26 @@ __global__ __launch_bounds__(DEEP ? 512 : 640, DEEP ? 2 : 3) void attn_fwd_hd64_
             const unsigned vl0 = (unsigned)KC * 128u + (4u * h2f + (vif >> 2)) * 64u + (16u * vgf + 4u * (vif & 3u)) * 2u;
             const unsigned va0 = ks_u + kt * 2048 + vl0, va1 = va0 + (unsigned)KC * 64u;
             u32x2_t vt[8];
-            vt[0] = tr_read_off<0>(va0);    vt[1] = tr_read_off<512>(va0);
-            vt[2] = tr_read_off<0>(va1);    vt[3] = tr_read_off<512>(va1);
-            vt[4] = tr_read_off<1024>(va0); vt[5] = tr_read_off<1536>(va0);
-            vt[6] = tr_read_off<1024>(va1); vt[7] = tr_read_off<1536>(va1);
+            attn::read_v<0>(vt, va0, va1);
             f32x16_t sa;
 #pragma unroll
             for (int i = 0; i < 16; ++i) sa[i] = 0.f;
 #pragma unroll
             for (int st = 0; st < 4; ++st) sa = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfa[st], qf[st], sa, 0, 0, 0);
-            mask_tail(sa, kt);
-            // tile_max reads the accumulator from inline asm (v_max3): the wait states an MFMA result needs before a VALU read are
-            // not inserted in front of inline asm, and when the tile is full (mask_tail reads nothing) no other instruction separates
-            // the two here.  (In the pair loop a dozen LDS reads and the other tile's maximum sit in between.)  Read too early the
-            // maximum is some older value: harmless for the softmax -- any shift m gives the same result up to rounding -- but
-            // the output then differs in the last bit from run to run (seen in an experiment of round 2 with this very pattern).
-            asm volatile("s_nop 15" : "+v"(sa));
-            float mx = tile_max(sa);
-            {
-                const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(mx), __float_as_uint(mx), false, false);
-                mx = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1])) * a.scale_log2;
-            }
-            if (!__all(mx - m <= 8.0f)) {
-                const float mn = fmaxf(m, mx);
-                const float alpha = __builtin_amdgcn_exp2f(m - mn);
-                m = mn;
-                lsum *= alpha;
-#pragma unroll
-                for (int i = 0; i < 16; ++i) { o0[i] *= alpha; o1[i] *= alpha; }
-            }
+            attn::mask_tail(sa, kt, h2, L);
+            asm volatile("s_nop 15" : "+v"(sa));                         // a full tile: nothing else in front of attn::tile_max
+            const float mx = attn::half_max(attn::tile_max(sa), a.scale_log2);
+            OV_ATTN_RESCALE(mx, m, lsum, o0, o1)
             const float nm = -m;
             f32x2_t ps = {0.f, 0.f};
             exp_rows(sa, a.scale_log2, nm, ps);
             lsum += ps[0] + ps[1];
-            const bf16x8_t pa0 = pack_p(sa, 0), pa1 = pack_p(sa, 1);
-            tr_wait(vt);
+            const bf16x8_t pa0 = attn::pack_p(sa, 0), pa1 = attn::pack_p(sa, 1);
+            attn::tr_wait(vt);
             __builtin_amdgcn_sched_barrier(0);
-            o0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_join(vt[0], vt[1]), pa0, o0, 0, 0, 0);
-            o1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_join(vt[2], vt[3]), pa0, o1, 0, 0, 0);
-            o0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_join(vt[4], vt[5]), pa1, o0, 0, 0, 0);
-            o1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_join(vt[6], vt[7]), pa1, o1, 0, 0, 0);
+            attn::pv_mma(vt, pa0, pa1, o0, o1);
         }
-        float l;
-        {
-            const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(lsum), __float_as_uint(lsum), false, false);
-            l = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
-        }
+        const float l = attn::half_sum(lsum);
         float inv = 1.0f / l;
         if (OUT8) {
             if (a.amax_next != nullptr) {          // delayed scaling; the (rare) atomic is issued AHEAD of the 8 stores the vmcnt(8) below counts
@@ -476,7 +340,7 @@ __global__ __launch_bounds__(DEEP ? 512 : 640, DEEP ? 2 : 3) void attn_fwd_hd64_
 #undef OV_ST8
         } else {
             // Widened store tail: after packing, a query row is split over the two half-waves (lane r: d 8g..8g+3, lane r+32:
-            // d 8g+4..8g+7 of group g).  One v_permlane32_swap per dword and pair of groups (g, g+1) leaves 16 contiguous bytes in
+            // d 8g+4..8g+7 of group g).  One half-wave swap (attn::half_swap) per dword and pair of groups (g, g+1) leaves 16 contiguous bytes in
             // every lane (lower half: d 8g..8g+7, upper half: d 8g+8..8g+15): FOUR global_store_dwordx4 per head instead of eight
             // dwordx2 -- the tail is store-issue bound (each row-per-lane store is 64 separate requests), so half the instructions
             // is half the time.
@@ -486,8 +350,8 @@ __global__ __launch_bounds__(DEEP ? 512 : 640, DEEP ? 2 : 3) void attn_fwd_hd64_
             {                                                                                                               \
                 const unsigned ax = pack_bf16x2(O[8 * P + 0] * inv, O[8 * P + 1] * inv), ay = pack_bf16x2(O[8 * P + 2] * inv, O[8 * P + 3] * inv); \
                 const unsigned bx = pack_bf16x2(O[8 * P + 4] * inv, O[8 * P + 5] * inv), by = pack_bf16x2(O[8 * P + 6] * inv, O[8 * P + 7] * inv); \
-                const auto sx = __builtin_amdgcn_permlane32_swap(ax, bx, false, false);                                       \
-                const auto sy = __builtin_amdgcn_permlane32_swap(ay, by, false, false);                                       \
+                const u32x2_t sx = attn::half_swap(ax, bx);                                                                   \
+                const u32x2_t sy = attn::half_swap(ay, by);                                                                   \
                 const u32x4_t w = {sx[0], sy[0], sx[1], sy[1]};                                                               \
                 /* s_nop 1: a store of more than 8 bytes reads its data VGPRs late -- the next VALU write of them needs 2 wait states, and */ \
                 /* the assembler's hazard recogniser does not look inside inline asm */                                      \
@@ -598,16 +462,6 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_hd64_stream(const AttnSArgs a
     f32x16_t o0, o1;
 #pragma unroll
     for (int i = 0; i < 16; ++i) { o0[i] = 0.f; o1[i] = 0.f; }
-    auto tile_max = [&](const f32x16_t& sc) {
-        float mx = max3_asm(max3_asm(sc[0], sc[1], sc[2]), max3_asm(sc[3], sc[4], sc[5]), max3_asm(sc[6], sc[7], sc[8]));
-        return max3_asm(mx, max3_asm(sc[9], sc[10], sc[11]), max3_asm(max3_asm(sc[12], sc[13], sc[14]), sc[15], sc[15]));
-    };
-    auto pack_p = [&](const f32x16_t& sc, int st) {
-        const u32x4_t w = {pack_bf16x2(sc[8 * st + 0], sc[8 * st + 1]), pack_bf16x2(sc[8 * st + 2], sc[8 * st + 3]),
-                           pack_bf16x2(sc[8 * st + 4], sc[8 * st + 5]), pack_bf16x2(sc[8 * st + 6], sc[8 * st + 7])};
-        return __builtin_bit_cast(bf16x8_t, w);
-    };
-
     // L = 64 k + 1 (every ViT grid of a multiple of 8 plus the class token: 577, 1025, 2305): the last chunk holds ONE key.  It is staged
     // like any other chunk but folded in on the VALU behind the loop (its K / V rows are row 0 of its ring slot), as the persistent
     // kernel does for its single-key tile: a chunk step for it is a whole barrier + 16 MFMAs + 32 exps per lane (2.8 % of the launch at
@@ -639,54 +493,24 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_hd64_stream(const AttnSArgs a
         for (int st = 0; st < 4; ++st) sb = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfb[st], qf[st], sb, 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
         u32x2_t vt[8], vu[8];
-        vt[0] = tr_read_off<0>(va0);    vt[1] = tr_read_off<512>(va0);
-        vt[2] = tr_read_off<0>(va1);    vt[3] = tr_read_off<512>(va1);
-        vt[4] = tr_read_off<1024>(va0); vt[5] = tr_read_off<1536>(va0);
-        vt[6] = tr_read_off<1024>(va1); vt[7] = tr_read_off<1536>(va1);
-        if (c * 64 + 64 > L) {                                    // last chunk: keys past the sequence score -inf (P = 0)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const int key = c * 64 + (i & 3) + 8 * (i >> 2) + 4 * h2;
-                if (key >= L) sa[i] = -INFINITY;
-                if (key + 32 >= L) sb[i] = -INFINITY;
-            }
-        }
-        float mx = fmaxf(tile_max(sa), tile_max(sb));
-        {
-            const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(mx), __float_as_uint(mx), false, false);
-            mx = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1])) * a.scale_log2;
-        }
-        if (!__all(mx - m <= 8.0f)) {
-            const float mn = fmaxf(m, mx);
-            const float alpha = __builtin_amdgcn_exp2f(m - mn);
-            m = mn;
-            lsum *= alpha;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) { o0[i] *= alpha; o1[i] *= alpha; }
-        }
+        attn::read_v<0>(vt, va0, va1);
+        OV_ATTN_MASK_TAIL2(sa, sb, 2 * c, h2, L)                  // last chunk: keys past the sequence
+        const float mx = attn::half_max(fmaxf(attn::tile_max(sa), attn::tile_max(sb)), a.scale_log2);
+        OV_ATTN_RESCALE(mx, m, lsum, o0, o1)
         const float nm = -m;
         f32x2_t ps = {0.f, 0.f};
         exp_rows(sa, a.scale_log2, nm, ps);
-        const bf16x8_t pa0 = pack_p(sa, 0), pa1 = pack_p(sa, 1);     // packed at once: the fp32 tile's registers retire early
+        const bf16x8_t pa0 = attn::pack_p(sa, 0), pa1 = attn::pack_p(sa, 1);     // packed at once: the fp32 tile's registers retire early
         exp_rows(sb, a.scale_log2, nm, ps);
-        const bf16x8_t pb0 = pack_p(sb, 0), pb1 = pack_p(sb, 1);
+        const bf16x8_t pb0 = attn::pack_p(sb, 0), pb1 = attn::pack_p(sb, 1);
         lsum += ps[0] + ps[1];
-        tr_wait(vt);
+        attn::tr_wait(vt);
         __builtin_amdgcn_sched_barrier(0);
-        vu[0] = tr_read_off<2048>(va0); vu[1] = tr_read_off<2560>(va0);
-        vu[2] = tr_read_off<2048>(va1); vu[3] = tr_read_off<2560>(va1);
-        vu[4] = tr_read_off<3072>(va0); vu[5] = tr_read_off<3584>(va0);
-        vu[6] = tr_read_off<3072>(va1); vu[7] = tr_read_off<3584>(va1);
-        o0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_join(vt[0], vt[1]), pa0, o0, 0, 0, 0);
-        o1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_join(vt[2], vt[3]), pa0, o1, 0, 0, 0);
-        o0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_join(vt[4], vt[5]), pa1, o0, 0, 0, 0);
-        o1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_join(vt[6], vt[7]), pa1, o1, 0, 0, 0);
-        tr_wait(vu);
+        attn::read_v<2048>(vu, va0, va1);
+        attn::pv_mma(vt, pa0, pa1, o0, o1);
+        attn::tr_wait(vu);
         __builtin_amdgcn_sched_barrier(0);
-        o0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_join(vu[0], vu[1]), pb0, o0, 0, 0, 0);
-        o1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_join(vu[2], vu[3]), pb0, o1, 0, 0, 0);
-        o0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_join(vu[4], vu[5]), pb1, o0, 0, 0, 0);
-        o1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_join(vu[6], vu[7]), pb1, o1, 0, 0, 0);
+        attn::pv_mma(vu, pb0, pb1, o0, o1);
     }
     if (lone_key) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the last chunk's two pieces (issued three chunks ago)
@@ -697,49 +521,20 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_hd64_stream(const AttnSArgs a
         const char* ks = smem + ((nc - 1) & 3) * 16384;           // key L-1 = row 0 of the slot: K chunk c at byte 16 c, V d-half h at 8192 + 4096 h
         float s0 = 0.f, s1 = 0.f;
 #pragma unroll
-        for (int st = 0; st < 4; ++st) {
-            const u32x4_t kq = *(const u32x4_t*)(ks + (2 * st + h2) * 16), qq = __builtin_bit_cast(u32x4_t, qf[st]);
-            asm("v_dot2c_f32_bf16 %0, %1, %2" : "+v"(s0) : "v"(qq[0]), "v"(kq[0]));
-            asm("v_dot2c_f32_bf16 %0, %1, %2" : "+v"(s1) : "v"(qq[1]), "v"(kq[1]));
-            asm("v_dot2c_f32_bf16 %0, %1, %2" : "+v"(s0) : "v"(qq[2]), "v"(kq[2]));
-            asm("v_dot2c_f32_bf16 %0, %1, %2" : "+v"(s1) : "v"(qq[3]), "v"(kq[3]));
-        }
-        asm("s_nop 2" : "+v"(s0), "+v"(s1));                      // DOT result -> ordinary VALU read (not inserted inside inline asm)
-        float sd = s0 + s1;                                       // this lane's half of d; the other half sits in lane ^ 32
-        {
-            const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(sd), __float_as_uint(sd), false, false);
-            sd = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
-        }
-        const float mx = sd * a.scale_log2;
-        if (!__all(mx - m <= 8.0f)) {
-            const float mn = fmaxf(m, mx);
-            const float alpha = __builtin_amdgcn_exp2f(m - mn);
-            m = mn;
-            lsum *= alpha;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) { o0[i] *= alpha; o1[i] *= alpha; }
-        }
-        const float pk = __builtin_amdgcn_exp2f(mx - m);
-        lsum += h2 ? 0.f : pk;                                    // the halves' sums are added below: count the key once
-        const char* vrow = ks + 8192 + 8 * h2;                    // o0[4 g + e]: d = 8 g + 4 h2 + e; o1: + 32 (the other d-half)
+        for (int st = 0; st < 4; ++st) attn::lone_dot(s0, s1, qf[st], *(const u32x4_t*)(ks + (2 * st + h2) * 16));
+        const float mx = attn::lone_sum(s0, s1) * a.scale_log2;
+        OV_ATTN_RESCALE(mx, m, lsum, o0, o1)
+        const float pk = attn::lone_weight(mx, m);
+        lsum += attn::count_once(pk, h2);
+        const char* vrow = ks + 8192 + 8 * h2;                    // d-half 0; half 1 = + 4096
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-            const u32x2_t v0 = *(const u32x2_t*)(vrow + g * 16), v1 = *(const u32x2_t*)(vrow + 4096 + g * 16);
-            o0[4 * g + 0] = fmaf(pk, bf16lo_to_f32(v0[0]), o0[4 * g + 0]);
-            o0[4 * g + 1] = fmaf(pk, bf16hi_to_f32(v0[0]), o0[4 * g + 1]);
-            o0[4 * g + 2] = fmaf(pk, bf16lo_to_f32(v0[1]), o0[4 * g + 2]);
-            o0[4 * g + 3] = fmaf(pk, bf16hi_to_f32(v0[1]), o0[4 * g + 3]);
-            o1[4 * g + 0] = fmaf(pk, bf16lo_to_f32(v1[0]), o1[4 * g + 0]);
-            o1[4 * g + 1] = fmaf(pk, bf16hi_to_f32(v1[0]), o1[4 * g + 1]);
-            o1[4 * g + 2] = fmaf(pk, bf16lo_to_f32(v1[1]), o1[4 * g + 2]);
-            o1[4 * g + 3] = fmaf(pk, bf16hi_to_f32(v1[1]), o1[4 * g + 3]);
+            const u32x2_t v0 = attn::vrow_piece(vrow, g), v1 = attn::vrow_piece(vrow + 4096, g);
+            attn::fold4(o0, g, pk, v0);
+            attn::fold4(o1, g, pk, v1);
         }
     }
-    float l;
-    {
-        const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(lsum), __float_as_uint(lsum), false, false);
-        l = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
-    }
+    const float l = attn::half_sum(lsum);
     float inv = 1.0f / l;
     if (OUT8 && a.amax_next != nullptr) {                         // delayed scaling: running maximum of |output| (all lanes take part)
         float lm = 0.f;
@@ -860,13 +655,7 @@ __global__ __launch_bounds__(640) void attn_fwd_generic(const AttnArgs a, int hd
                 const bf16x8_t kf = *(const bf16x8_t*)(kp + ((SWZ ? c ^ ((r >> 1) & 7) : c) << 4));
                 s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[st], s, 0, 0, 0);
             }
-            if (kt * 32 + 32 > nk) {
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const int key = kt * 32 + (i & 3) + 8 * (i >> 2) + 4 * h2;
-                    if (key >= nk) s[i] = -INFINITY;
-                }
-            }
+            OV_ATTN_MASK_TAIL(s, kt, h2, nk)
             if (MASK && kc0 + kt * 32 + 31 >= a.prefix && kc0 + kt * 32 + 31 > q0) {   // the tile straddles the boundary (wave-uniform)
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {
@@ -874,38 +663,16 @@ __global__ __launch_bounds__(640) void attn_fwd_generic(const AttnArgs a, int hd
                     if (key >= a.prefix && key > q0 + r) s[i] = -INFINITY;
                 }
             }
-            // (the maximum reads the accumulator from inline asm: the MFMA -> VALU wait states are not inserted in front of inline asm,
-            // and a full tile leaves no other instruction in between -- see the single-tile step of attn_fwd_hd64_persist)
-            asm volatile("s_nop 15" : "+v"(s));
-            float mx = max3_asm(max3_asm(s[0], s[1], s[2]), max3_asm(s[3], s[4], s[5]), max3_asm(s[6], s[7], s[8]));
-            mx = max3_asm(mx, max3_asm(s[9], s[10], s[11]), max3_asm(max3_asm(s[12], s[13], s[14]), s[15], s[15]));
-            {
-                const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(mx), __float_as_uint(mx), false, false);
-                mx = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1])) * a.scale_log2;
-            }
-            // MASK: each row decides by its own scores alone (alpha = 1 exactly otherwise), so that keys a row cannot see -- which move
-            // the maxima of the rows below it in the tile -- leave its result bitwise unchanged
-            if (MASK ? __any(mx - m > 8.0f) : !__all(mx - m <= 8.0f)) {
-                const float mn = (!MASK || mx - m > 8.0f) ? fmaxf(m, mx) : m;
-                const float alpha = __builtin_amdgcn_exp2f(m - mn);
-                m = mn;
-                lsum *= alpha;
-#pragma unroll
-                for (int t = 0; t < DT; ++t)
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) o[t][i] *= alpha;
-            }
+            asm volatile("s_nop 15" : "+v"(s));                          // a full tile: nothing else in front of attn::tile_max
+            const float mx = attn::half_max(attn::tile_max(s), a.scale_log2);
+            OV_ATTN_RESCALE_ROWS(MASK, mx, m, lsum, o, DT)
             const float nm = -m;
             f32x2_t ps = {0.f, 0.f};
             exp_rows(s, a.scale_log2, nm, ps);
             lsum += ps[0] + ps[1];
             bf16x8_t pf[2];
 #pragma unroll
-            for (int st = 0; st < 2; ++st) {
-                u32x4_t w = {pack_bf16x2(s[8 * st + 0], s[8 * st + 1]), pack_bf16x2(s[8 * st + 2], s[8 * st + 3]),
-                             pack_bf16x2(s[8 * st + 4], s[8 * st + 5]), pack_bf16x2(s[8 * st + 6], s[8 * st + 7])};
-                pf[st] = __builtin_bit_cast(bf16x8_t, w);
-            }
+            for (int st = 0; st < 2; ++st) pf[st] = attn::pack_p(s, st);
             const char* vp = vs + kt * 32 * 64 + v_lane_off;
 #pragma unroll
             for (int st = 0; st < 2; ++st) {
@@ -923,51 +690,25 @@ __global__ __launch_bounds__(640) void attn_fwd_generic(const AttnArgs a, int hd
 #pragma unroll
             for (int st = 0; st < KS; ++st) {
                 const int c = 2 * st + h2;
-                const u32x4_t kq = *(const u32x4_t*)(kp + ((SWZ ? c ^ ((key >> 1) & 7) : c) << 4)), qq = __builtin_bit_cast(u32x4_t, qf[st]);
-                asm("v_dot2c_f32_bf16 %0, %1, %2" : "+v"(s0) : "v"(qq[0]), "v"(kq[0]));
-                asm("v_dot2c_f32_bf16 %0, %1, %2" : "+v"(s1) : "v"(qq[1]), "v"(kq[1]));
-                asm("v_dot2c_f32_bf16 %0, %1, %2" : "+v"(s0) : "v"(qq[2]), "v"(kq[2]));
-                asm("v_dot2c_f32_bf16 %0, %1, %2" : "+v"(s1) : "v"(qq[3]), "v"(kq[3]));
+                attn::lone_dot(s0, s1, qf[st], *(const u32x4_t*)(kp + ((SWZ ? c ^ ((key >> 1) & 7) : c) << 4)));
             }
-            asm("s_nop 2" : "+v"(s0), "+v"(s1));                      // DOT result -> ordinary VALU read (not inserted inside inline asm)
-            float sd = s0 + s1;                                       // this lane's d chunks; the others sit in lane ^ 32
-            {
-                const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(sd), __float_as_uint(sd), false, false);
-                sd = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
-            }
+            const float sd = attn::lone_sum(s0, s1);
             // MASK: the lone key is visible to this lane's query like any other key (weight exactly 0 otherwise)
             const bool seen = !MASK || kc0 + key < a.prefix || kc0 + key <= q0 + r;
             const float mx = seen ? sd * a.scale_log2 : -INFINITY;
-            // MASK: each row decides by its own scores alone (alpha = 1 exactly otherwise), so that keys a row cannot see -- which move
-            // the maxima of the rows below it in the tile -- leave its result bitwise unchanged
-            if (MASK ? __any(mx - m > 8.0f) : !__all(mx - m <= 8.0f)) {
-                const float mn = (!MASK || mx - m > 8.0f) ? fmaxf(m, mx) : m;
-                const float alpha = __builtin_amdgcn_exp2f(m - mn);
-                m = mn;
-                lsum *= alpha;
+            OV_ATTN_RESCALE_ROWS(MASK, mx, m, lsum, o, DT)
+            const float pk = attn::lone_weight(mx, m);
+            lsum += attn::count_once(pk, h2);
 #pragma unroll
-                for (int t = 0; t < DT; ++t)
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) o[t][i] *= alpha;
-            }
-            const float pk = __builtin_amdgcn_exp2f(mx - m);
-            lsum += h2 ? 0.f : pk;                                    // the halves' sums are added at the end: count the key once
-#pragma unroll
-            for (int t = 0; t < DT; ++t) {                            // o[t][4 g + e]: d = 32 t + 8 g + 4 h2 + e
+            for (int t = 0; t < DT; ++t) {                            // o[t]: d = 32 t + ...
                 const char* vrow = vs + t * (KC * 64) + key * 64 + 8 * h2;
 #pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const u32x2_t v = *(const u32x2_t*)(vrow + g * 16);
-                    o[t][4 * g + 0] = fmaf(pk, bf16lo_to_f32(v[0]), o[t][4 * g + 0]);
-                    o[t][4 * g + 1] = fmaf(pk, bf16hi_to_f32(v[0]), o[t][4 * g + 1]);
-                    o[t][4 * g + 2] = fmaf(pk, bf16lo_to_f32(v[1]), o[t][4 * g + 2]);
-                    o[t][4 * g + 3] = fmaf(pk, bf16hi_to_f32(v[1]), o[t][4 * g + 3]);
-                }
+                for (int g = 0; g < 4; ++g) attn::fold4(o[t], g, pk, attn::vrow_piece(vrow, g));
             }
         }
     }
     if (!active) return;
-    const float l = lsum + __shfl_xor(lsum, 32, 64);
+    const float l = lsum + __shfl_xor(lsum, 32, 64);      // (as written: through attn::swap_halves the HDP = 64 form came out different)
     const float inv = 1.0f / l;
     const int q = q0 + r;
     if (q < L) {

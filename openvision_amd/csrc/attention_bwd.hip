@@ -16,6 +16,7 @@
 // 16-byte chunks are XOR-swizzled by (row >> 2) & 3 so that the ds_read_b128 lane groups are bank-conflict free.
 // First version: correct and deterministic, not yet tuned (plain staging, serial LDS waits).
 #include "common.h"
+#include "attn_tile.h"
 
 namespace {
 
@@ -29,10 +30,6 @@ struct AttnBwdArgs {
     const float* lse_in;                      // optional: [B*H][KC] row lse kept by the forward (ov_attention_lse): pass 1 is skipped
 };
 
-__device__ __forceinline__ bf16x8_t join8(u32x2_t a, u32x2_t b) {
-    const u32x4_t w = {a[0], a[1], b[0], b[1]};
-    return __builtin_bit_cast(bf16x8_t, w);
-}
 // A-operand fragments of X^T for one 32-row tile: (d half 0, rows 0-15), (half 1, rows 0-15), (half 0, rows 16-31), (half 1,
 // rows 16-31); each is two ds_read_b64_tr_b16 (rows r.. and 8 rows further, offset 512 B), transposed by the LDS unit.  All eight
 // reads and their wait sit in ONE asm statement: the destination registers are complete when the statement ends.
@@ -47,15 +44,9 @@ __device__ __forceinline__ TrFrags tr_frags(unsigned a0, unsigned b0, unsigned a
                  : "=&v"(v0), "=&v"(v1), "=&v"(v2), "=&v"(v3), "=&v"(v4), "=&v"(v5), "=&v"(v6), "=&v"(v7)
                  : "v"(a0), "v"(b0), "v"(a1), "v"(b1) : "memory");
     TrFrags t;
-    t.f[0] = join8(v0, v1); t.f[1] = join8(v2, v3); t.f[2] = join8(v4, v5); t.f[3] = join8(v6, v7);
+    t.f[0] = attn::tr_join(v0, v1); t.f[1] = attn::tr_join(v2, v3); t.f[2] = attn::tr_join(v4, v5); t.f[3] = attn::tr_join(v6, v7);
     return t;
 }
-__device__ __forceinline__ bf16x8_t pack8(const f32x16_t& t, int s) {
-    const u32x4_t w = {pack_bf16x2(t[8 * s + 0], t[8 * s + 1]), pack_bf16x2(t[8 * s + 2], t[8 * s + 3]),
-                       pack_bf16x2(t[8 * s + 4], t[8 * s + 5]), pack_bf16x2(t[8 * s + 6], t[8 * s + 7])};
-    return __builtin_bit_cast(bf16x8_t, w);
-}
-__device__ __forceinline__ float swap_halves(float v) { return __shfl_xor(v, 32, 64); }
 
 template <bool SAVED>
 __global__ __launch_bounds__(640) void attn_bwd_hd64(const AttnBwdArgs a) {
@@ -149,7 +140,7 @@ __global__ __launch_bounds__(640) void attn_bwd_hd64(const AttnBwdArgs a) {
             // whatever the recycled buffer held, possibly NaN / Inf -- never read them (p = 0 is selected for q >= L further down)
             lse2 = query < L ? a.lse_in[(int64_t)blockIdx.x * KC + query] : 0.f;
         } else {
-            const float mo = swap_halves(m), lo = swap_halves(l);
+            const float mo = attn::swap_halves(m), lo = attn::swap_halves(l);
             const float mn = fmaxf(m, mo);                       // finite: key 0 is always valid for one of the halves
             l = l * (m > -INFINITY ? __builtin_amdgcn_exp2f(m - mn) : 0.f) + lo * (mo > -INFINITY ? __builtin_amdgcn_exp2f(mo - mn) : 0.f);
             m = mn;
@@ -171,7 +162,7 @@ __global__ __launch_bounds__(640) void attn_bwd_hd64(const AttnBwdArgs a) {
                     delta = fmaf(bf16hi_to_f32(ov[e]), bf16hi_to_f32(dv[e]), delta);
                 }
             }
-            delta += swap_halves(delta);
+            delta += attn::swap_halves(delta);
         }
         if (h2 == 0) { lse[query] = lse2; dlt[query] = delta; }
 
@@ -193,12 +184,9 @@ __global__ __launch_bounds__(640) void attn_bwd_hd64(const AttnBwdArgs a) {
                 const float p = key < L ? __builtin_amdgcn_exp2f(fmaf(s[t], a.scale_log2, -lse2)) : 0.f;
                 s[t] = p * (dp[t] - delta);                      // dS^T
             }
-            const bf16x8_t b0 = pack8(s, 0), b1 = pack8(s, 1);
+            const bf16x8_t b0 = attn::pack_p(s, 0), b1 = attn::pack_p(s, 1);
             const TrFrags kt = tr_tile(kimg, j);
-            dq0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kt.f[0], b0, dq0, 0, 0, 0);
-            dq1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kt.f[1], b0, dq1, 0, 0, 0);
-            dq0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kt.f[2], b1, dq0, 0, 0, 0);
-            dq1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kt.f[3], b1, dq1, 0, 0, 0);
+            OV_ATTN_TILE_MMA(kt.f[0], kt.f[1], kt.f[2], kt.f[3], b0, b1, dq0, dq1)
         }
         if (query < L) {                                         // rows d = 8 g + 4 h2 + e (dq0), + 32 (dq1)
             ov_bf16* op = a.dqkv + ((int64_t)b * L + query) * a.lddq + h * 64 + 4 * h2;
@@ -239,17 +227,11 @@ __global__ __launch_bounds__(640) void attn_bwd_hd64(const AttnBwdArgs a) {
                 s[t] = p;                                        // P
                 dp[t] = p * (dp[t] - dlt[q]);                    // dS
             }
-            const bf16x8_t p0 = pack8(s, 0), p1 = pack8(s, 1), g0 = pack8(dp, 0), g1 = pack8(dp, 1);
+            const bf16x8_t p0 = attn::pack_p(s, 0), p1 = attn::pack_p(s, 1), g0 = attn::pack_p(dp, 0), g1 = attn::pack_p(dp, 1);
             const TrFrags dt = tr_tile(dimg, i);
-            dv0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dt.f[0], p0, dv0, 0, 0, 0);
-            dv1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dt.f[1], p0, dv1, 0, 0, 0);
-            dv0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dt.f[2], p1, dv0, 0, 0, 0);
-            dv1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dt.f[3], p1, dv1, 0, 0, 0);
+            OV_ATTN_TILE_MMA(dt.f[0], dt.f[1], dt.f[2], dt.f[3], p0, p1, dv0, dv1)
             const TrFrags qt = tr_tile(qimg, i);
-            dk0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qt.f[0], g0, dk0, 0, 0, 0);
-            dk1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qt.f[1], g0, dk1, 0, 0, 0);
-            dk0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qt.f[2], g1, dk0, 0, 0, 0);
-            dk1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qt.f[3], g1, dk1, 0, 0, 0);
+            OV_ATTN_TILE_MMA(qt.f[0], qt.f[1], qt.f[2], qt.f[3], g0, g1, dk0, dk1)
         }
         if (key < L) {
             ov_bf16* kp = a.dqkv + ((int64_t)b * L + key) * a.lddq + HD + h * 64 + 4 * h2;
@@ -340,8 +322,8 @@ __device__ __forceinline__ void tr_half(unsigned a0, unsigned b0, bf16x8_t& f0, 
                  "ds_read_b64_tr_b16 %2, %4 offset:1024\n\tds_read_b64_tr_b16 %3, %5 offset:1536\n\t"
                  "s_waitcnt lgkmcnt(0)"
                  : "=&v"(v0), "=&v"(v1), "=&v"(v2), "=&v"(v3) : "v"(a0), "v"(b0) : "memory");
-    f0 = join8(v0, v1);
-    f1 = join8(v2, v3);
+    f0 = attn::tr_join(v0, v1);
+    f1 = attn::tr_join(v2, v3);
 }
 
 #define OV_CHUNK_HELPERS()                                                                                                            \
@@ -421,7 +403,7 @@ __global__ __launch_bounds__(512) void attn_bwd_stream_q(const AttnBwdSArgs g) {
         }
     }
     {
-        const float mo = swap_halves(m), lo = swap_halves(l);
+        const float mo = attn::swap_halves(m), lo = attn::swap_halves(l);
         const float mn = fmaxf(m, mo);
         l = l * (m > -INFINITY ? __builtin_amdgcn_exp2f(m - mn) : 0.f) + lo * (mo > -INFINITY ? __builtin_amdgcn_exp2f(mo - mn) : 0.f);
         m = mn;
@@ -440,7 +422,7 @@ __global__ __launch_bounds__(512) void attn_bwd_stream_q(const AttnBwdSArgs g) {
                 delta = fmaf(bf16hi_to_f32(ov[e]), bf16hi_to_f32(dv[e]), delta);
             }
         }
-        delta += swap_halves(delta);
+        delta += attn::swap_halves(delta);
     }
     if (h2 == 0 && query < g.Lpad) { g.lse[(int64_t)bh * g.Lpad + query] = lse2; g.dlt[(int64_t)bh * g.Lpad + query] = delta; }
 
@@ -470,7 +452,7 @@ __global__ __launch_bounds__(512) void attn_bwd_stream_q(const AttnBwdSArgs g) {
                 const float p = seen ? __builtin_amdgcn_exp2f(fmaf(s[t], a.scale_log2, -lse2)) : 0.f;
                 s[t] = p * (dp[t] - delta);
             }
-            tr_mma(img0, j, pack8(s, 0), pack8(s, 1), dq);
+            tr_mma(img0, j, attn::pack_p(s, 0), attn::pack_p(s, 1), dq);
         }
     }
     if (query < L) St::store(a.dqkv + ((int64_t)b * L + query) * a.lddq + h * hd, dq, a.scale, h2, hd);
@@ -535,8 +517,8 @@ __global__ __launch_bounds__(512) void attn_bwd_stream_kv(const AttnBwdSArgs g) 
                 s[t] = p;
                 dp[t] = p * (dp[t] - dlt_s[ql]);
             }
-            tr_mma(img1, i, pack8(s, 0), pack8(s, 1), dv);
-            tr_mma(img0, i, pack8(dp, 0), pack8(dp, 1), dk);
+            tr_mma(img1, i, attn::pack_p(s, 0), attn::pack_p(s, 1), dv);
+            tr_mma(img0, i, attn::pack_p(dp, 0), attn::pack_p(dp, 1), dk);
         }
     }
     if (key < L) {

@@ -3,6 +3,7 @@ must not use scratch.  Once the register allocator spills, a spill store can cop
 data has landed and a spill reload adds memory operations the hand counts do not know (found the hard way in
 the streaming attention experiments).  hipcc --cuda-device-only -S writes the code-object metadata per kernel; the test fails if
 `.private_segment_fixed_size` (bytes of scratch per lane) is non-zero for any such kernel."""
+import importlib.util
 import os
 import re
 import subprocess
@@ -134,3 +135,51 @@ def test_the_hazard_scanner_sees_a_planted_hazard():
 """
     bad = inline_asm_mfma_hazards(planted, r"planted")
     assert len(bad) == 3 and all(b[1].startswith("v_max3_f32 v50") for b in bad), bad
+
+
+# ---- the ISA comparison of tools/kernel_resources.py --against: its normalise-and-split step on planted text ------------------------
+def _kernel_resources():
+    path = os.path.join(os.path.dirname(B.PKG), "tools", "kernel_resources.py")
+    spec = importlib.util.spec_from_file_location("kernel_resources", path)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+_PLANTED_A = """	.file	"a.hip"
+_Zplanted_a:                            ; @_Zplanted_a
+	.loc	1 10 0
+; %bb.0:
+	s_load_dwordx2 s[0:1], s[4:5], 0x0     ; a comment
+	v_add_f32_e32 v1, v2, v3
+	s_getpc_b64 s[2:3]
+	s_add_u32 s2, s2, __hip_cuid_1234abcd@rel32@lo+4
+	;;#ASMSTART
+	v_max3_f32 v4, v1, v2, v3
+	;;#ASMEND
+.LBB0_1:
+	s_endpgm
+	.ident	"clang version 1"
+_Zplanted_b:
+	v_mov_b32_e32 v0, 0
+	s_endpgm
+"""
+
+
+def test_the_isa_comparison_ignores_comments_debug_lines_and_the_cuid_symbol():
+    kr = _kernel_resources()
+    other = (_PLANTED_A.replace("; a comment", "; another comment").replace(".loc\t1 10 0", ".loc\t1 99 3")
+             .replace("__hip_cuid_1234abcd", "__hip_cuid_9876fedc").replace("; %bb.0:", "; %bb.0: entry"))
+    assert other != _PLANTED_A
+    a, b = kr.kernel_bodies(_PLANTED_A), kr.kernel_bodies(other)
+    assert sorted(a) == ["_Zplanted_a", "_Zplanted_b"] and a == b
+    assert a["_Zplanted_a"][:2] == ["s_load_dwordx2 s[0:1], s[4:5], 0x0", "v_add_f32_e32 v1, v2, v3"] and a["_Zplanted_a"][-1] == "s_endpgm"
+    assert all(kr.differing_lines(a[k], b[k]) == 0 for k in a)
+
+
+def test_the_isa_comparison_sees_one_changed_register():
+    kr = _kernel_resources()
+    other = _PLANTED_A.replace("v_max3_f32 v4, v1, v2, v3", "v_max3_f32 v4, v1, v2, v5")
+    a, b = kr.kernel_bodies(_PLANTED_A), kr.kernel_bodies(other)
+    assert kr.differing_lines(a["_Zplanted_a"], b["_Zplanted_a"]) == 1
+    assert kr.differing_lines(a["_Zplanted_b"], b["_Zplanted_b"]) == 0

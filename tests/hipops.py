@@ -262,15 +262,16 @@ def _own_ws(ws, nb, device):
 
 def linear_backward(dy, x, w, want=("dx", "dw", "db"), dx=None, dw=None, db=None, ws=None):
     """ov_linear_backward for y = x w^T + b: returns (dX bf16 [M,K] | None, dW bf16 [N,K] | None, db fp32 [N] | None).  dx= / dw= /
-    db=: caller-owned outputs for the gradients named in `want` (dx, dw with their own row pitch); ws=: a caller-owned workspace."""
+    db=: caller-owned outputs for the gradients named in `want` (dx, dw with their own row pitch); ws=: a caller-owned workspace.
+    x may be None when dX alone is wanted (the block chain's c_proj dX)."""
     lib = _lib.load()
     M, N = dy.shape
-    K = x.shape[1]
+    K = w.shape[1]
     dx = _out_buf(dx, M, K, torch.bfloat16, None, dy.device) if "dx" in want else None
     dw = _out_buf(dw, N, K, torch.bfloat16, None, dy.device) if "dw" in want else None
     db = (db if db is not None else torch.empty(N, dtype=torch.float32, device=dy.device)) if "db" in want else None
     ws, nb = _own_ws(ws, lib.ov_linear_backward_workspace_bytes(M, N, K), dy.device)
-    check(lib.ov_linear_backward(ptr(dy), dy.stride(0), ptr(x), x.stride(0), ptr(w), w.stride(0), M, N, K,
+    check(lib.ov_linear_backward(ptr(dy), dy.stride(0), ptr(x), x.stride(0) if x is not None else K, ptr(w), w.stride(0), M, N, K,
                                  ptr(dx) if dx is not None else None, dx.stride(0) if dx is not None else K,
                                  ptr(dw) if dw is not None else None, dw.stride(0) if dw is not None else K,
                                  ptr(db) if db is not None else None, ptr(ws), nb, stream_ptr()), "ov_linear_backward")
@@ -323,9 +324,9 @@ def gelu_backward(a, dh, tanh, with_h=False, da=None, h=None, inplace=False):
     return (da, h) if with_h else da
 
 
-def block_backward(cfg, weights, x, dy, B, L):
-    """ov_block_backward.  weights: dict of the module's own tensors (ln1_w, ln1_b fp32; qkv_w bf16 [3D, D]; qkv_b fp32; ...).
-    Returns (dx bf16, grads dict)."""
+def block_backward(cfg, weights, x, dy, B, L, saved=None, prefix=None):
+    """ov_block_backward (prefix: ov_block_backward_prefix).  weights: dict of the module's own tensors (ln1_w, ln1_b fp32; qkv_w bf16
+    [3D, D]; qkv_b fp32; ...); saved: an ov_block_saved (block_saved_of) or None, everything recomputed.  Returns (dx bf16, grads dict)."""
     import ctypes as C
     lib = _lib.load()
     names = ("ln1_w", "ln1_b", "qkv_w", "qkv_b", "out_w", "out_b", "ln2_w", "ln2_b", "fc_w", "fc_b", "proj_w", "proj_b")
@@ -336,8 +337,13 @@ def block_backward(cfg, weights, x, dy, B, L):
     nb = lib.ov_block_backward_workspace_bytes(C.byref(cfg), B, L)
     assert nb > 0
     ws = torch.empty(nb + 256, dtype=torch.uint8, device=x.device)
-    check(lib.ov_block_backward(C.byref(cfg), C.byref(wst), ptr(x), None, ptr(dy), ptr(dx), C.byref(gst), B, L, ptr(ws), nb, stream_ptr()),
-          "ov_block_backward")
+    sv = C.byref(saved) if saved is not None else None
+    if prefix is None:
+        check(lib.ov_block_backward(C.byref(cfg), C.byref(wst), ptr(x), sv, ptr(dy), ptr(dx), C.byref(gst), B, L, ptr(ws), nb, stream_ptr()),
+              "ov_block_backward")
+    else:
+        check(lib.ov_block_backward_prefix(C.byref(cfg), C.byref(wst), ptr(x), sv, ptr(dy), ptr(dx), C.byref(gst), prefix, B, L, ptr(ws), nb,
+                                           stream_ptr()), "ov_block_backward_prefix")
     return dx, grads
 
 
@@ -1742,3 +1748,308 @@ def convert(src, dst):
     check(lib.ov_convert(ptr(src), _flag(src), src.stride(0), ptr(dst), _flag(dst), dst.stride(0), src.shape[0], src.shape[1],
                          stream_ptr()), "ov_convert")
     return dst
+
+
+# ---- the training block chain, stage by stage (test_gpu_block_chain.py; what the stage checks tell apart: test_block_chain_cpu.py).
+# forward_saving_layer (tower.hip) and block_backward_chain (backward.hip) are sequences of launches of operators that each have an
+# fp64 reference and a derived bound above.  Every stage is held to its operator's bound ON THE STAGE'S OWN INPUTS AS THE RUN PRODUCED
+# THEM, so no bf16 error compounds from one stage into the next one's tolerance.
+
+BLOCK_NAMES = ("ln1_w", "ln1_b", "qkv_w", "qkv_b", "out_w", "out_b", "ln2_w", "ln2_b", "fc_w", "fc_b", "proj_w", "proj_b")
+SLOT_FIELDS = ("x", "qkv", "o", "x1", "ln_1", "ln_2", "pre", "act")        # ov_tower_forward_saving's slot, in its order; then the lse
+
+
+def block_case(D, heads, mlp, B, L, tanh, seed, mlp_pad=None, device=DEV):
+    """Random block: returns (reference-named fp32 state dict of bf16-rounded weights, C-ABI weight dict on `device`, x, dy)."""
+    names = {"ln1_w": ("ln_1.weight", (D,), 1.0, 0.1), "ln1_b": ("ln_1.bias", (D,), 0.0, 0.1),
+             "qkv_w": ("attn.in_proj_weight", (3 * D, D), 0.0, D ** -0.5), "qkv_b": ("attn.in_proj_bias", (3 * D,), 0.0, 0.05),
+             "out_w": ("attn.out_proj.weight", (D, D), 0.0, D ** -0.5), "out_b": ("attn.out_proj.bias", (D,), 0.0, 0.05),
+             "ln2_w": ("ln_2.weight", (D,), 1.0, 0.1), "ln2_b": ("ln_2.bias", (D,), 0.0, 0.1),
+             "fc_w": ("mlp.c_fc.weight", (mlp, D), 0.0, D ** -0.5), "fc_b": ("mlp.c_fc.bias", (mlp,), 0.0, 0.05),
+             "proj_w": ("mlp.c_proj.weight", (D, mlp), 0.0, mlp ** -0.5), "proj_b": ("mlp.c_proj.bias", (D,), 0.0, 0.05)}
+    bf = lambda t: t.to(torch.bfloat16)
+    sd, dev = {}, {}
+    for i, (k, (ref, shape, mean, std)) in enumerate(names.items()):
+        t = rnd(*shape, seed=seed + i) * std + mean
+        if len(shape) == 2:
+            t = bf(t)
+            dev[k] = t.to(device)
+        else:
+            dev[k] = t.to(device)
+        sd["b." + ref] = t.float()
+    if mlp_pad and mlp_pad > mlp:                 # device copies zero-padded to the kernels' hidden pitch (as the forward packs them)
+        pad = mlp_pad - mlp
+        dev["fc_w"] = torch.cat([dev["fc_w"], torch.zeros(pad, D, dtype=torch.bfloat16, device=device)]).contiguous()
+        dev["fc_b"] = torch.cat([dev["fc_b"], torch.zeros(pad, device=device)]).contiguous()
+        dev["proj_w"] = torch.cat([dev["proj_w"], torch.zeros(D, pad, dtype=torch.bfloat16, device=device)], dim=1).contiguous()
+    x, dy = bf(rnd(B, L, D, seed=seed + 20)), bf(rnd(B, L, D, seed=seed + 21))
+    return names, sd, dev, x, dy
+
+
+def slot_layout(D, F, heads, B, L):
+    """One layer's slot of `saved` as tower.hip lays it out: ({field: (byte offset, rows, columns)}, bytes per layer).  The eight bf16
+    fields of SLOT_FIELDS, then "lse": fp32 [B * heads, L rounded up to 32], its section rounded up to 16 bytes."""
+    M, lp = B * L, (L + 31) // 32 * 32
+    lay, off = {}, 0
+    for name, cols in zip(SLOT_FIELDS, (D, 3 * D, D, D, D, D, F, F)):
+        lay[name] = (2 * off, M, cols)
+        off += M * cols
+    lay["lse"] = (2 * off, B * heads, lp)
+    off += (2 * B * heads * lp + 7) // 8 * 8
+    return lay, 2 * off
+
+
+def saved_slots(saved, D, F, heads, B, L, layers=1):
+    """Views of a uint8 `saved` buffer (ov_tower_forward_saving), one dict per layer: the fields of SLOT_FIELDS as bf16 [M, columns]
+    and "lse" as fp32 [B * heads, L rounded up to 32] (written only where the library keeps it: attn_route(...).keep_lse)."""
+    lay, nb = slot_layout(D, F, heads, B, L)
+    out = []
+    for i in range(layers):
+        s = {}
+        for name, (off, rows, cols) in lay.items():
+            dt, es = (torch.float32, 4) if name == "lse" else (torch.bfloat16, 2)
+            s[name] = saved[i * nb + off:i * nb + off + rows * cols * es].view(dt).view(rows, cols)
+        out.append(s)
+    return out
+
+
+def block_saved_of(slot, keep_lse):
+    """The full ov_block_saved over one slot (tower.hip's block_saved_of)."""
+    return _lib.BlockSaved(qkv=slot["qkv"].data_ptr(), attn_out=slot["o"].data_ptr(), x1=slot["x1"].data_ptr(), fc_pre=slot["pre"].data_ptr(),
+                           ln1_out=slot["ln_1"].data_ptr(), ln2_out=slot["ln_2"].data_ptr(), fc_act=slot["act"].data_ptr(),
+                           attn_lse=slot["lse"].data_ptr() if keep_lse else None)
+
+
+class Tower:
+    """An ov_tower over a list of per-layer weight dicts (block_case's), as the training step drives it."""
+
+    def __init__(self, cfg, layer_weights):
+        self.lib, self.cfg, self.w = _lib.load(), cfg, layer_weights
+        assert cfg.layers == len(layer_weights)
+        self.h = self.lib.ov_tower_create(C.byref(cfg))
+        assert self.h
+        for i, w in enumerate(layer_weights):
+            wst = _lib.BlockWeights(*[ptr(w[n]) for n in BLOCK_NAMES], None, None)
+            check(self.lib.ov_tower_set_block(self.h, i, C.byref(wst)), "ov_tower_set_block")
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.lib.ov_tower_destroy(self.h)
+
+    def forward_saving(self, x, B, L):
+        """(y, saved uint8 with a 256-byte 0xA5 tail that must survive)."""
+        nbs = self.lib.ov_tower_saved_bytes(self.h, B, L)
+        saved = torch.full((nbs + 256,), 0xA5, dtype=torch.uint8, device=x.device)
+        nb = self.lib.ov_tower_workspace_bytes(self.h, B, L)
+        ws = torch.empty(nb + 256, dtype=torch.uint8, device=x.device)
+        y = x.clone()
+        check(self.lib.ov_tower_forward_saving(self.h, ptr(y), ptr(saved), B, L, ptr(ws), nb, stream_ptr()), "ov_tower_forward_saving")
+        torch.cuda.synchronize()
+        assert bool((saved[nbs:] == 0xA5).all()), "ov_tower_forward_saving wrote past ov_tower_saved_bytes"
+        return y, saved
+
+    def backward(self, saved, dy, B, L):
+        """(dx, [grads dict per layer]) of ov_tower_backward."""
+        grads = [{n: torch.full_like(w[n], float("nan")) for n in BLOCK_NAMES} for w in self.w]
+        garr = (_lib.BlockGrads * len(grads))(*[_lib.BlockGrads(*[ptr(g[n]) for n in BLOCK_NAMES]) for g in grads])
+        nb = self.lib.ov_tower_backward_workspace_bytes(self.h, B, L)
+        ws = torch.empty(nb + 256, dtype=torch.uint8, device=dy.device)
+        dx = dy.clone()
+        check(self.lib.ov_tower_backward(self.h, ptr(saved), ptr(dx), garr, B, L, ptr(ws), nb, stream_ptr()), "ov_tower_backward")
+        torch.cuda.synchronize()
+        return dx, grads
+
+
+def block_chain_replay(cfg, w, x, slot, dy, B, L, prefix=None):
+    """block_backward_chain (backward.hip), launch by launch through the operators the C ABI exports, in the chain's order: c_proj dX
+    with the GELU derivative, c_proj dW / db, c_fc dX / dW / db, LN_2 backward with dres = dy, out_proj dX / dW / db, attention backward
+    (over the kept lse; under a prefix the masked one), QKV dX / dW / db, LN_1 backward with dres = dx1.
+
+    slot: one layer's dict out of saved_slots (the chain with a full ov_block_saved: the derivative rides on the epilogue of dy Wproj^T,
+    which the ABI exports as ov_gemm over the transposed weight -- what ov_linear_backward itself launches for a dX), or None: the
+    recomputing entry, whose forward is replayed first (ov_layernorm, ov_gemm, ov_attention[_prefix], ov_gemm + residual, ov_layernorm,
+    ov_gemm) and whose GELU derivative is the element-wise ov_gelu_backward over dh = dy Wproj^T, which also leaves gelu(pre) for the
+    c_proj dW.  Operands sit in buffers 8 columns wider whose padding holds NaN; every output starts as SENT in a buffer 8 columns
+    wider.  Returns a namespace: f (the forward tensors the stages read: SLOT_FIELDS and lse), dh_lin (None on the fused route), dh,
+    act (what the c_proj dW read), dn2, dx1, do, dqkv, dn1, dx, grads (the twelve, BLOCK_NAMES) and wides [(buffer, columns used)]."""
+    import prefix_restate as PR
+    D, Hh, F, tanh, eps = cfg.width, cfg.heads, cfg.mlp_pad, bool(cfg.gelu_tanh), cfg.ln_eps
+    M, hd = B * L, cfg.width // cfg.heads
+    r = SimpleNamespace(wides=[], grads={})
+
+    def outb(rows, cols):
+        wide = torch.full((rows, cols + 8), SENT, dtype=torch.bfloat16, device=x.device)
+        r.wides.append((wide, cols))
+        return wide[:, :cols]
+
+    xp, dyp = pitched(x), pitched(dy)
+    if slot is None:
+        n1 = layernorm(xp, w["ln1_w"], w["ln1_b"], eps, out=outb(M, D))
+        qkv = gemm(n1, w["qkv_w"], w["qkv_b"], 0, out=outb(M, 3 * D))
+        o = attention(qkv, B, L, Hh, hd, out=outb(M, D)) if prefix is None else PR.attention_prefix(qkv, B, L, Hh, hd, prefix, out=outb(M, D))
+        x1 = gemm(o, w["out_w"], w["out_b"], 3, resid=xp, out=outb(M, D))
+        n2 = layernorm(x1, w["ln2_w"], w["ln2_b"], eps, out=outb(M, D))
+        pre = gemm(n2, w["fc_w"], w["fc_b"], 0, out=outb(M, F))
+        f = {"x": xp, "qkv": qkv, "o": o, "x1": x1, "ln_1": n1, "ln_2": n2, "pre": pre, "act": None, "lse": None}
+    else:
+        f = {k: pitched(slot[k]) for k in SLOT_FIELDS}
+        f["x"] = xp
+        f["lse"] = slot["lse"] if prefix is None and attn_route(B, L, Hh, hd).keep_lse else None
+    r.f = f
+    g = r.grads
+    if f["act"] is not None:
+        wt = transpose(w["proj_w"])                                    # [F, D]: the staging ov_linear_backward makes for a dX
+        r.dh_lin, r.act = None, f["act"]
+        r.dh = gemm(dyp, wt, None, 5 if tanh else 4, resid=f["pre"], out=outb(M, F))
+    else:
+        r.dh_lin = linear_backward(dyp, None, w["proj_w"], want=("dx",), dx=outb(M, F))[0]
+        r.dh, r.act = gelu_backward(f["pre"], r.dh_lin, tanh, da=outb(M, F), h=outb(M, F))
+    _, g["proj_w"], g["proj_b"] = linear_backward(dyp, r.act, w["proj_w"], want=("dw", "db"), dw=outb(D, F))
+    r.dn2, g["fc_w"], g["fc_b"] = linear_backward(r.dh, f["ln_2"], w["fc_w"], dx=outb(M, D), dw=outb(F, D))
+    r.dx1, g["ln2_w"], g["ln2_b"] = layernorm_backward(f["x1"], w["ln2_w"], r.dn2, eps, dres=dyp, dx=outb(M, D))
+    r.do, g["out_w"], g["out_b"] = linear_backward(r.dx1, f["o"], w["out_w"], dx=outb(M, D), dw=outb(D, D))
+    if prefix is None:
+        r.dqkv = attention_backward_saved(f["qkv"], f["o"], r.do, f["lse"], B, L, Hh, hd, dqkv=outb(M, 3 * D))
+    else:
+        r.dqkv = PR.attention_prefix_backward(f["qkv"], f["o"], r.do, B, L, Hh, hd, prefix, dqkv=outb(M, 3 * D))
+    r.dn1, g["qkv_w"], g["qkv_b"] = linear_backward(r.dqkv, f["ln_1"], w["qkv_w"], dx=outb(M, D), dw=outb(3 * D, D))
+    r.dx, g["ln1_w"], g["ln1_b"] = layernorm_backward(f["x"], w["ln1_w"], r.dn1, eps, dres=r.dx1, dx=outb(M, D))
+    return r
+
+
+def _cpu(t):
+    return None if t is None else t.detach().cpu()
+
+
+def lse_ref64(qkv, B, L, Hh, hd, mask=None):
+    """(lse, bound) fp64 [B * Hh, L] of the kept row log-sum-exp in log2 units, lse = log2 sum_j 2^(s_j), s = scale log2(e) Q K^T.
+    s_j is an hd-term fp32 dot product times a rounded constant: off by at most (hd + 3) e scale log2(e) (|Q| . |K_j|); d lse / d s_j
+    = P_j.  exp2 (one ulp each), the L-term fp32 sum and log2 move the sum by at most (L + 8) e relatively, log2(e) times that in
+    lse; the max is added back with one rounding and the result stored: 2 e |lse|."""
+    q, k, _ = _split(qkv, B, L, Hh, hd)
+    s = q @ k.transpose(-1, -2) * hd ** -0.5
+    if mask is not None:
+        s = s.masked_fill(~mask, float("-inf"))
+    lse = torch.logsumexp(s, dim=-1) * LOG2E
+    p = torch.softmax(s, dim=-1)
+    ds = (hd + 3) * E32 * hd ** -0.5 * LOG2E * (p * (q.abs() @ k.abs().transpose(-1, -2))).sum(-1)
+    bound = ds + (L + 8) * E32 * LOG2E + 2 * E32 * lse.abs()
+    return lse.reshape(B * Hh, L), bound.reshape(B * Hh, L)
+
+
+def chain_forward_ratios(w, f, y, dims, prefix=None):
+    """Every forward stage of one block against fp64 of that stage applied to the stage's own stored input.  w: the block's weights
+    (BLOCK_NAMES); f: the slot's tensors (SLOT_FIELDS; "act" and "lse" may be None), y: the block output or None; dims = (D, heads,
+    mlp, mlp_pad, tanh, B, L).  Tensors on any device: the references run in fp64 on the CPU.  Returns stage -> max err / bound;
+    "mlp padding" is 0 when columns [mlp, mlp_pad) of pre and act hold exactly zero and inf otherwise."""
+    import prefix_restate as PR
+    D, Hh, mlp, F, tanh, B, L = dims
+    hd = D // Hh
+    w = {k: _cpu(v) for k, v in w.items()}
+    f = {k: _cpu(v) for k, v in f.items()}
+    mask = None if prefix is None else PR.rule_mask(L, prefix)
+    res = {}
+    res["ln_1"] = ratio(f["ln_1"], *ln_ref64(f["x"], w["ln1_w"], w["ln1_b"]))[0]
+    res["qkv"] = linear_ratios(f["ln_1"], w["qkv_w"], w["qkv_b"], {"qkv": (f["qkv"], "pre")})["qkv"][0]
+    ref, pv = attn_ref64(f["qkv"], B, L, Hh, hd) if mask is None else PR.masked_attn_ref64(f["qkv"], B, L, Hh, hd, mask)
+    res["attn"] = err_ratio(f["o"], ref, pv)
+    if f.get("lse") is not None:
+        want, bd = lse_ref64(f["qkv"], B, L, Hh, hd, mask)
+        res["lse"] = ratio(f["lse"][:, :L], want, bd)[0]
+    res["x1"] = linear_ratios(f["o"], w["out_w"], w["out_b"], {"x1": (f["x1"], "res")}, r=f["x"])["x1"][0]
+    res["ln_2"] = ratio(f["ln_2"], *ln_ref64(f["x1"], w["ln2_w"], w["ln2_b"]))[0]
+    outs = {"pre": (f["pre"], "pre")}
+    if f.get("act") is not None:
+        outs["act"] = (f["act"], "tanh" if tanh else "erf")
+    for k, v in linear_ratios(f["ln_2"], w["fc_w"], w["fc_b"], outs).items():
+        res[k] = v[0]
+    pads = [f[k][:, mlp:F] for k in ("pre", "act") if f.get(k) is not None]
+    res["mlp padding"] = 0.0 if all(bool((t.float() == 0).all()) for t in pads) else float("inf")
+    if y is not None:
+        res["y"] = linear_ratios(f["act"], w["proj_w"], w["proj_b"], {"y": (_cpu(y), "res")}, r=f["x1"])["y"][0]
+    return res
+
+
+def _q(got, ref, bd):
+    """|got - ref| / bound per element, 0 / 0 = 0, NaN = inf."""
+    q = _over((got.double() - ref).abs(), bd)
+    return torch.where(torch.isnan(q), torch.full_like(q, float("inf")), q)
+
+
+def chain_backward_ratios(w, r, dy, dims, prefix=None):
+    """Every stage of the backward chain against fp64 of that stage on the stage's own inputs.  r: what block_chain_replay returns (or
+    an emulation of it); dy: the chain's input.  Returns (stage -> max err / bound, {"dx1" | "dqkv" | "dx": err / bound per element}).
+    The stages: dh (fused: linear_ratios' gerf / gtanh on dy Wproj^T at pre; else dh_lin under the dX bound, then dh and act under
+    gelu_bounds), the four linear backwards (dX, dW, db under linear_bounds), the two LayerNorm backwards (ln_grads_ref64), the
+    attention backward (bwd_bound with eo = the forward's own enforced bound on the kept out).  "grad padding": 0 when rows [mlp,
+    mlp_pad) of fc_w / fc_b and columns [mlp, mlp_pad) of proj_w hold exactly zero, inf otherwise."""
+    import prefix_restate as PR
+    D, Hh, mlp, F, tanh, B, L = dims
+    hd = D // Hh
+    w = {k: _cpu(v) for k, v in w.items()}
+    f = {k: _cpu(v) for k, v in r.f.items()}
+    g = {k: _cpu(v) for k, v in r.grads.items()}
+    dy, dh, dn2, dx1, do, dqkv, dn1, dx = (_cpu(t) for t in (dy, r.dh, r.dn2, r.dx1, r.do, r.dqkv, r.dn1, r.dx))
+    res, elem = {}, {}
+
+    def lin(tag, dyy, xx, ww, dX, dW, db):
+        ref, bd = linear_grads_ref64(dyy, xx, ww), linear_bounds(dyy, xx, ww)
+        if dX is not None:
+            res[tag + " dX"] = float(_q(dX, ref[0], bd[0]).max())
+        res[tag + " dW"] = float(_q(dW, ref[1], bd[1]).max())
+        res[tag + " db"] = float(_q(db, ref[2], bd[2]).max())
+
+    def ln(tag, xx, gamma, dyy, dres, got, dgamma, dbeta):
+        ref = ln_grads_ref64(xx, gamma, dyy, dres, 1e-6)
+        q = _q(got, ref.dx, ref.bdx)
+        res[tag + " dx"], res[tag + " dgamma"], res[tag + " dbeta"] = float(q.max()), float(_q(dgamma, ref.dgamma, ref.bdg).max()), \
+            float(_q(dbeta, ref.dbeta, ref.bdb).max())
+        return q
+
+    if r.dh_lin is None:
+        wt = w["proj_w"].T.contiguous()
+        res["dh"] = linear_ratios(dy, wt, torch.zeros(F), {"dh": (dh, "gtanh" if tanh else "gerf")}, r=f["pre"])["dh"][0]
+    else:
+        dh_lin = _cpu(r.dh_lin)
+        ref, bd = linear_grads_ref64(dy, torch.zeros(dy.shape[0], F), w["proj_w"]), linear_bounds(dy, torch.zeros(dy.shape[0], F), w["proj_w"])
+        res["dh_lin"] = float(_q(dh_lin, ref[0], bd[0]).max())
+        res["dh"], res["act"] = gelu_err_ratio(dh, _cpu(r.act), f["pre"], dh_lin, tanh)
+    lin("c_proj", dy, _cpu(r.act), w["proj_w"], None, g["proj_w"], g["proj_b"])
+    lin("c_fc", dh, f["ln_2"], w["fc_w"], dn2, g["fc_w"], g["fc_b"])
+    elem["dx1"] = ln("ln_2", f["x1"], w["ln2_w"], dn2, dy, dx1, g["ln2_w"], g["ln2_b"])
+    lin("out_proj", dx1, f["o"], w["out_w"], do, g["out_w"], g["out_b"])
+    mask = None if prefix is None else PR.rule_mask(L, prefix)
+    ref = attn_grads_ref64(f["qkv"], do, B, L, Hh, hd, mask)
+    bds = bwd_bound(ref, ref.q, ref.k, ref.v, ref.do, ref.scale, bound(ref.o, ref.pv))
+    qs = [_q(dqkv[:, j * D:(j + 1) * D], want, bd) for j, (want, bd) in enumerate(zip((ref.dq, ref.dk, ref.dv), bds))]
+    res["attn dq"], res["attn dk"], res["attn dv"] = (float(q.max()) for q in qs)
+    elem["dqkv"] = torch.cat(qs, dim=1)
+    lin("qkv", dqkv, f["ln_1"], w["qkv_w"], dn1, g["qkv_w"], g["qkv_b"])
+    elem["dx"] = ln("ln_1", f["x"], w["ln1_w"], dn1, dx1, dx, g["ln1_w"], g["ln1_b"])
+    pads = (g["fc_w"][mlp:], g["fc_b"][mlp:], g["proj_w"][:, mlp:])
+    res["grad padding"] = 0.0 if all(bool((t.float() == 0).all()) for t in pads) else float("inf")
+    return res, elem
+
+
+def chain_dy(kind, B, L, D, tanh, seed):
+    """The two upstream gradients of the chain tests, bf16 [B * L, D].  "dense": Gaussian with rows 0, 63, 64 and M - 1 eight times
+    larger (spiked_linear_case's rows) and rows 0 and M - 1 four times larger again (32 x in all: spiked_ln_case's).  "pooled": what a
+    pooling head sends down -- non-zero on token 0 of each sequence only (class pooling), or, for the tanh (text-like) block, the
+    constant 1 / L on tokens 1... and zero on token 0 (the mean pool)."""
+    M = B * L
+    if kind == "dense":
+        dy = rnd(M, D, seed=seed)
+        for row in sorted({0, 63, 64, M - 1}):
+            if row < M:
+                dy[row] *= 8.0
+        dy[0] *= 4.0
+        dy[M - 1] *= 4.0
+        return dy.to(torch.bfloat16)
+    dy = torch.zeros(B, L, D)
+    if tanh:
+        dy[:, 1:] = 1.0 / L
+    else:
+        dy[:, 0] = rnd(B, D, seed=seed)
+    return dy.view(M, D).to(torch.bfloat16)

@@ -25,6 +25,7 @@ if ROOT not in sys.path:
 
 from openvision_amd import _lib, synth  # noqa: E402
 from openvision_amd._lib import ptr, stream_ptr, check  # noqa: E402
+import hipops  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -182,14 +183,9 @@ def _block_digests(tag):
         y = x.clone()
         check(lib.ov_tower_forward_saving(t.h, ptr(y), ptr(saved), B, L, ptr(wsf), nbf, stream_ptr()), "ov_tower_forward_saving")
         out["block_saved.y"] = _sha(y)
-        base, off, p = saved.data_ptr(), 0, []
-        for n in (M * D, 3 * M * D, M * D, M * D, M * D, M * D, M * F, M * F):
-            p.append(base + 2 * off)
-            off += n
         route = _lib.AttentionRoute()                                  # the lse is kept where the library says the backward reads it
         check(lib.ov_attention_route(B, L, heads, D // heads, 0, 0, -1, 0, 0, 0, C.addressof(route)), "ov_attention_route")
-        lse = base + 2 * off if route.keep_lse else None
-        sv = _lib.BlockSaved(qkv=p[1], attn_out=p[2], x1=p[3], fc_pre=p[6], ln1_out=p[4], ln2_out=p[5], fc_act=p[7], attn_lse=lse)
+        sv = hipops.block_saved_of(hipops.saved_slots(saved, D, F, heads, B, L)[0], route.keep_lse)
         run("block_saved", sv, None)
         # the attention half alone (feature visualisation)
         qkv = torch.full((M, 3 * D), float("nan"), dtype=torch.bfloat16, device=DEV)

@@ -684,7 +684,8 @@ def test_training_step_gradients_tiny(tiny):
     """One training step on the Tiny model: openvision_amd.training.clip_forward + ClipLoss + backward (HIP tower and loss nodes, torch
     autograd for the light ends) against torch autograd through the oracle's fp32 restatement of the reference on the CPU.  The tower
     works in bf16 (12 blocks, every intermediate rounded), so gradients are compared by direction and size: cosine >= 0.99 and norm
-    within 5 % for every parameter tensor whose gradient is not negligible."""
+    within 5 % for every parameter tensor whose gradient is not negligible.  (The sharp check of the block chain, stage by stage
+    against fp64 on each stage's own inputs: test_gpu_block_chain.py.)"""
     from oracle import clip_ref as R
     from openvision_amd import training
     from openvision_amd.loss import ClipLoss

@@ -450,30 +450,7 @@ def test_attention_backward_golden_reference():
     assert float((dx - g["mha_dx"]).abs().max()) < 3e-2 * float(g["mha_dx"].abs().max()) + 2e-3
 
 
-def _block_case(D, heads, mlp, B, L, tanh, seed, mlp_pad=None):
-    """Random block: returns (reference-named fp32 state dict of bf16-rounded weights, C-ABI weight dict on the device, x, dy)."""
-    names = {"ln1_w": ("ln_1.weight", (D,), 1.0, 0.1), "ln1_b": ("ln_1.bias", (D,), 0.0, 0.1),
-             "qkv_w": ("attn.in_proj_weight", (3 * D, D), 0.0, D ** -0.5), "qkv_b": ("attn.in_proj_bias", (3 * D,), 0.0, 0.05),
-             "out_w": ("attn.out_proj.weight", (D, D), 0.0, D ** -0.5), "out_b": ("attn.out_proj.bias", (D,), 0.0, 0.05),
-             "ln2_w": ("ln_2.weight", (D,), 1.0, 0.1), "ln2_b": ("ln_2.bias", (D,), 0.0, 0.1),
-             "fc_w": ("mlp.c_fc.weight", (mlp, D), 0.0, D ** -0.5), "fc_b": ("mlp.c_fc.bias", (mlp,), 0.0, 0.05),
-             "proj_w": ("mlp.c_proj.weight", (D, mlp), 0.0, mlp ** -0.5), "proj_b": ("mlp.c_proj.bias", (D,), 0.0, 0.05)}
-    sd, dev = {}, {}
-    for i, (k, (ref, shape, mean, std)) in enumerate(names.items()):
-        t = rnd(*shape, seed=seed + i) * std + mean
-        if len(shape) == 2:
-            t = bf(t)
-            dev[k] = t.to(DEV)
-        else:
-            dev[k] = t.to(DEV)
-        sd["b." + ref] = t.float()
-    if mlp_pad and mlp_pad > mlp:                 # device copies zero-padded to the kernels' hidden pitch (as the forward packs them)
-        pad = mlp_pad - mlp
-        dev["fc_w"] = torch.cat([dev["fc_w"], torch.zeros(pad, D, dtype=torch.bfloat16, device=DEV)]).contiguous()
-        dev["fc_b"] = torch.cat([dev["fc_b"], torch.zeros(pad, device=DEV)]).contiguous()
-        dev["proj_w"] = torch.cat([dev["proj_w"], torch.zeros(D, pad, dtype=torch.bfloat16, device=DEV)], dim=1).contiguous()
-    x, dy = bf(rnd(B, L, D, seed=seed + 20)), bf(rnd(B, L, D, seed=seed + 21))
-    return names, sd, dev, x, dy
+_block_case = H_.block_case          # (the chain tests draw the same blocks: hipops.block_case)
 
 
 @pytest.mark.parametrize("D,heads,mlp,B,L,tanh", [(1024, 16, 4096, 72, 257, False), (768, 12, 3072, 256, 80, True), (192, 3, 768, 4, 101, False),
@@ -506,7 +483,8 @@ def test_kept_activation_backward_matches_the_recomputing_backward(D, heads, mlp
 def test_block_backward_vs_oracle(D, heads, mlp, B, L, tanh):
     """ov_block_backward (recompute + chain rule through the HIP operators) vs the oracle's closed-form block backward in fp32 on the
     same bf16 weights and inputs.  Every intermediate of the HIP path is bf16, so the comparison is relative to each gradient's
-    scale: 4e-2 of its maximum (weights: Frobenius-relative 2e-2)."""
+    scale: 4e-2 of its maximum (weights: Frobenius-relative 2e-2).  (Every stage of the chain under its operator's per-element fp64
+    bound, on the stage's own inputs: test_gpu_block_chain.py.)"""
     from openvision_amd import _lib as L_
     names, sd, dev, x, dy = _block_case(D, heads, mlp, B, L, tanh, 60)
     cfg = L_.TowerCfg(D, 1, heads, mlp, mlp, int(tanh), 1e-6)
@@ -525,7 +503,8 @@ def test_block_backward_vs_oracle(D, heads, mlp, B, L, tanh):
 
 
 def test_block_backward_head_dim_72_and_padded_mlp():
-    """So400m-like block: head_dim 72 and an MLP width (int(D * 3.7362)) that the kernels pad to a multiple of 64."""
+    """So400m-like block: head_dim 72 and an MLP width (int(D * 3.7362)) that the kernels pad to a multiple of 64.  (The padded chain
+    stage by stage under per-element fp64 bounds: test_gpu_block_chain.py, shape hd80_l257_padmlp.)"""
     from openvision_amd import _lib as L_
     D, heads, mlp, B, L = 576, 8, 2152, 2, 257
     mlp_pad = 2176

@@ -15,6 +15,8 @@
  *   ov_mlp_out_pooled   _global_pool 'avg' of the last block's output, through its c_proj   transformer.py:264,599-603
  *   ov_text_embed       token_embedding(text) + positional_embedding         model.py:272-274
  *   ov_gather_rows      text_global_pool 'last' / 'first'                     transformer.py:655-658
+ *   ov_token_argmax     text.argmax(dim=-1), the EOT position of each caption transformer.py:655-658
+ *   ov_gather_rows_at   text_global_pool 'argmax': one row per caption        transformer.py:655-658
  *   ov_l2norm           F.normalize(x, dim=-1)                                model.py:267,284
  *   ov_logits           CLIP.get_logits (scale * img @ txt^T)                 model.py:286-293
  *   ov_clip_loss        ClipLoss.get_logits + cross_entropy both ways         loss.py:102-131
@@ -282,6 +284,15 @@ int ov_text_embed(const int64_t* tokens, const ov_bf16* table, const ov_bf16* po
 /* out[b, :] = x[b*L + t, :] (row gather; t = L-1 for text 'last' pooling). bf16 -> bf16. */
 int ov_gather_rows(const ov_bf16* x, int64_t ldx, ov_bf16* out, int64_t ldo, int B, int L, int t, int D,
                    ov_stream_t stream);
+
+/* idx[b] = the smallest t with tokens[b, t] == max_t tokens[b, :]  (text.argmax(dim=-1) with ties going to the first position; the
+ * compare runs on the full int64).  tokens int64 [B, T], idx int32 [B]. */
+int ov_token_argmax(const int64_t* tokens, int* idx, int B, int T, ov_stream_t stream);
+
+/* out[b, :] = x[b*L + clamp(idx[b], 0, L-1), :]  (row gather at a per-batch position: text 'argmax' pooling).  bf16 -> bf16, 16-byte
+ * copies: D % 8 == 0, pitches % 8 == 0.  idx int32 [B] on the device; the clamp is for memory safety only. */
+int ov_gather_rows_at(const ov_bf16* x, int64_t ldx, const int* idx, ov_bf16* out, int64_t ldo, int B, int L, int D,
+                      ov_stream_t stream);
 
 /* bf16 <-> fp32 row conversion helpers (strided rows). */
 int ov_convert(const void* src, int src_dtype, int64_t lds, void* dst, int dst_dtype, int64_t ldd,
@@ -810,7 +821,8 @@ int ov_mlp_feature_backward(const ov_bf16* x1, int64_t ldx, const float* ln2_w, 
 typedef struct {      /* VisionTransformer front/back ends (OpenVision: no ln_pre, no conv bias) */
     int image_size, patch_size, kpad;              /* kpad = roundup(3*P*P, 64) */
     int pool_avg;                                  /* 1 = 'avg' (skip cls), 0 = 'tok' */
-    int final_ln_after_pool;                       /* 1 for OpenVision */
+    int final_ln_after_pool;                       /* 1 for OpenVision; 0 (ln_post before the pool) under 'tok' pooling only,
+                                                      where it is the same arithmetic, else OV_ERR_UNSUPPORTED */
     int embed_dim, embed_pad;                      /* E, roundup(E, 8) */
     const ov_bf16* conv_w;                         /* [D, kpad] bf16, pad cols = 0 */
     const float* cls;                              /* [D] */
@@ -850,9 +862,12 @@ int ov_encode_image_keep(const ov_tower* t, const ov_vision_head* h, const void*
                          int K, float* features, int normalize, int* err_flag, void* workspace, size_t workspace_bytes,
                          ov_stream_t stream);
 
+enum ov_text_pool { OV_TEXT_POOL_FIRST = 0, OV_TEXT_POOL_LAST = 1, OV_TEXT_POOL_ARGMAX = 2 };   /* text_global_pool, transformer.py:655-658 */
+
 typedef struct {      /* CLIP text front/back ends */
     int context_length, vocab_size;
-    int pool_last;                                 /* 1 = 'last', 0 = 'first' */
+    int pool_last;                                 /* enum ov_text_pool: 0 = 'first', 1 = 'last', 2 = 'argmax' (the row of the
+                                                      largest token id of each caption, the first of equals: ov_token_argmax) */
     int embed_dim;
     const ov_bf16* token_embedding;                /* [V, D] bf16 */
     const ov_bf16* pos;                            /* [T, D] bf16 */
@@ -862,7 +877,10 @@ typedef struct {      /* CLIP text front/back ends */
 
 size_t ov_text_workspace_bytes(const ov_tower* t, const ov_text_head* h, int B);
 /* CLIP.encode_text: tokens int64 [B, T] -> [B, E] fp32.  *err_flag (device int, may be NULL) is set
- * to 1 when a token id is outside [0, V). */
+ * to 1 when a token id is outside [0, V).  'argmax' pooling finds each caption's row on the device (an int32 [B] behind the head's
+ * buffers: the workspace is that much larger, and only then), so the call stays capturable; a pool mode outside ov_text_pool is
+ * OV_ERR_INVALID.  A causal tower (ov_tower_set_prefix(t, 0)) is exact on the pooled-rows tail too: the rows past the last
+ * attention are per-token. */
 int ov_encode_text(const ov_tower* t, const ov_text_head* h, const int64_t* tokens, int B,
                    float* features, int normalize, int* err_flag, void* workspace,
                    size_t workspace_bytes, ov_stream_t stream);

@@ -61,6 +61,9 @@ class VisionHead(C.Structure):
                 ("ln_post_w", c_void_p), ("ln_post_b", c_void_p), ("proj_t", c_void_p)]
 
 
+TEXT_POOL = {"first": 0, "last": 1, "argmax": 2}          # ovhip.h enum ov_text_pool: what TextHead.pool_last holds
+
+
 class TextHead(C.Structure):
     _fields_ = [("context_length", c_int), ("vocab_size", c_int), ("pool_last", c_int), ("embed_dim", c_int),
                 ("token_embedding", c_void_p), ("pos", c_void_p), ("ln_final_w", c_void_p), ("ln_final_b", c_void_p),
@@ -125,6 +128,8 @@ SIGNATURES = {
     "ov_text_embed": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p,
                               c_void_p]),
     "ov_gather_rows": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p]),
+    "ov_token_argmax": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "ov_gather_rows_at": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
     "ov_convert": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_int, c_int64, c_int64, c_int, c_void_p]),
     "ov_l2norm": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p]),
     "ov_logits": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),

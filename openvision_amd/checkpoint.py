@@ -45,7 +45,13 @@ def read_state_dict(path: str) -> Dict[str, torch.Tensor]:
 
 
 def from_pretrained(path: str, device: Optional[str] = "cuda:0") -> Tuple[CLIP, dict]:
-    """Returns (model.eval() on ``device``, preprocess_cfg).  Strict key/shape match, as the reference's loader."""
+    """Returns (model.eval() on ``device``, preprocess_cfg).  Strict key/shape match, as the reference's loader.
+
+    A stock ``open_clip_config.json`` directory loads too (``text_cfg`` defaults: causal mask, 'argmax' pooling; ``vision_cfg``
+    defaults: ln_pre, 'tok' pooling): the LAION / DataComp ViT-B/32 ... bigG checkpoints.  ``quick_gelu: true`` (the OpenAI weights)
+    is refused.  LayerNorm eps: the vendored reference builds every LayerNorm with eps = 1e-6 (transformer.py:458,690) and so does
+    this loader, while upstream open_clip uses torch's 1e-5; for weights trained upstream add ``"norm_kwargs": {"eps": 1e-5}`` to
+    both ``vision_cfg`` and ``text_cfg``."""
     model_cfg, pp = ovcfg.load_config_dir(path)
     sd = read_state_dict(path)
     core = {k: v for k, v in model_cfg.items() if k in ("embed_dim", "vision_cfg", "text_cfg")}

@@ -3,9 +3,10 @@
 Mirrors the dataclasses the reference builds its towers from
 (``src/convert_upload/open_clip/model.py:27-84`` ``CLIPVisionCfg`` / ``CLIPTextCfg``) and the
 size tables of the JAX->HF converter (``src/convert_upload/transfer_jax2hf.py:76-92``).
-Only the fields the OpenVision encode-and-contrast path reads are kept; anything that would
+Only the fields the encode-and-contrast path reads are kept: the OpenVision towers and the stock
+open_clip ones (causal text with 'argmax' pooling, ln_pre, 'tok' pooling).  Anything that would
 select a different architecture (attentional pooling, timm/HF towers, quick_gelu, layer-scale,
-patch dropout > 0) is rejected loudly instead of being silently ignored.
+embed_cls, proj_bias) is rejected loudly instead of being silently ignored.
 """
 from __future__ import annotations
 
@@ -92,13 +93,20 @@ def vision_cfg_from(d) -> CLIPVisionCfg:
 
 def text_cfg_from(d) -> CLIPTextCfg:
     c = _from_dict(CLIPTextCfg, d)
-    if c.hf_model_name or c.ls_init_value is not None or c.embed_cls or c.proj_bias:
-        raise ValueError("text_cfg selects a tower outside the OpenVision text path")
-    if not c.no_causal_mask:
-        raise ValueError("OpenVision text towers are unmasked (no_causal_mask=true); "
-                         "causal text attention is not on this path")
-    if c.pool_type not in ("last", "first"):
-        raise ValueError(f"text pool_type {c.pool_type!r} not supported (OpenVision uses 'last')")
+    for key, bad, what in (("hf_model_name", bool(c.hf_model_name), "a Hugging Face text tower"),
+                           ("ls_init_value", c.ls_init_value is not None, "layer scale"),
+                           ("embed_cls", bool(c.embed_cls), "the appended CLS embedding of CoCa text towers"),
+                           ("proj_bias", bool(c.proj_bias), "a biased text projection")):
+        if bad:
+            raise ValueError(f"text_cfg.{key}={getattr(c, key)!r}: {what} is not built here (supported: the OpenVision text "
+                             f"tower, unmasked with 'last' / 'first' pooling, and the stock open_clip one, causal with 'argmax')")
+    if c.pool_type not in ("last", "first", "argmax"):
+        raise ValueError(f"text pool_type {c.pool_type!r} not supported: 'last' / 'first' (OpenVision) or 'argmax' (stock "
+                         f"open_clip: the EOT token's row); attentional and no pooling are not built")
+    if not c.no_causal_mask and c.pool_type != "argmax":
+        # the stock pair is causal + 'argmax'; a causal tower pooled at a fixed position appears in open_clip only with embed_cls
+        raise ValueError(f"causal text attention (no_causal_mask=false) is built for pool_type 'argmax', the stock open_clip "
+                         f"text tower; with pool_type {c.pool_type!r} set no_causal_mask=true (OpenVision towers are unmasked)")
     if c.width % c.heads:
         raise ValueError("text width must be a multiple of heads")
     return c

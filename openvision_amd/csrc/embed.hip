@@ -5,6 +5,7 @@
 //   ov_mean_pool       _global_pool 'avg' (cls excluded) / 'tok'          transformer.py:599-603
 //   ov_text_embed      token_embedding(text) + positional_embedding      model.py:272-274
 //   ov_gather_rows     text_global_pool 'last' / 'first'                  transformer.py:655-658
+//   ov_token_argmax + ov_gather_rows_at   text_global_pool 'argmax' (the EOT row of each caption)
 //   ov_convert         dtype casts (.to(cast_dtype))
 //   ov_l2norm          F.normalize(x, dim=-1)                             model.py:267,284
 // Patch dropout (PatchDropout, transformer.py:49-86: the image keeps K of its G patch tokens, in the order of keep[b, :]):
@@ -335,6 +336,40 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const ov_bf16* __restr
     }
 }
 
+// One wave per caption: every lane keeps the (value, first position) pair of its strided share, then a butterfly over the pairs.  The
+// order (larger value, then smaller position) is total, so every lane ends with the same pair whatever the order of the exchanges.
+__global__ __launch_bounds__(256) void token_argmax_kernel(const int64_t* __restrict__ tokens, int* __restrict__ idx, int B, int T) {
+    const int lane = threadIdx.x & 63, wpb = blockDim.x >> 6;
+    for (int b = blockIdx.x * wpb + (threadIdx.x >> 6); b < B; b += gridDim.x * wpb) {
+        const int64_t* row = tokens + (int64_t)b * T;
+        int64_t best = INT64_MIN;
+        int at = T;                                           // a lane without an element: loses every comparison against a real one
+        for (int t = lane; t < T; t += 64) {
+            const int64_t v = row[t];
+            if (at == T || v > best) { best = v; at = t; }    // ascending t: strict > keeps the first of equal values
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const int64_t ov = __shfl_xor(best, o, 64);
+            const int oa = __shfl_xor(at, o, 64);
+            if (oa < T && (at == T || ov > best || (ov == best && oa < at))) { best = ov; at = oa; }
+        }
+        if (lane == 0) idx[b] = at;
+    }
+}
+
+__global__ __launch_bounds__(256) void gather_rows_at_kernel(const ov_bf16* __restrict__ x, int64_t ldx, const int* __restrict__ idx,
+                                                             ov_bf16* __restrict__ out, int64_t ldo, int B, int L, int D) {
+    const int cpr = D >> 3;
+    const int64_t total = (int64_t)B * cpr;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int b = (int)(i / cpr), ch = (int)(i - (int64_t)b * cpr);
+        int t = idx[b];
+        t = t < 0 ? 0 : (t > L - 1 ? L - 1 : t);              // memory safety only: ov_token_argmax never leaves [0, L)
+        *(u32x4_t*)(out + (int64_t)b * ldo + ch * 8) = *(const u32x4_t*)(x + ((int64_t)b * L + t) * ldx + ch * 8);
+    }
+}
+
 template <bool SRC_F32, bool DST_F32>
 __global__ __launch_bounds__(256) void convert_kernel(const void* __restrict__ src, int64_t lds, void* __restrict__ dst,
                                                       int64_t ldd, int64_t rows, int cols) {
@@ -479,6 +514,23 @@ extern "C" int ov_gather_rows(const ov_bf16* x, int64_t ldx, ov_bf16* out, int64
     if (D % 8 || ldx % 8 || ldo % 8 || ldx < D || ldo < D || (((uintptr_t)x | (uintptr_t)out) & 15)) return OV_ERR_INVALID;
     hipLaunchKernelGGL(gather_rows_kernel, dim3(grid_for((int64_t)B * (D / 8), 256)), dim3(256), 0, (hipStream_t)stream, x, ldx,
                        out, ldo, B, L, t, D);
+    OV_LAUNCH_CHECK();
+    return OV_OK;
+}
+
+extern "C" int ov_token_argmax(const int64_t* tokens, int* idx, int B, int T, ov_stream_t stream) {
+    if (!tokens || !idx || B <= 0 || T <= 0) return OV_ERR_INVALID;
+    hipLaunchKernelGGL(token_argmax_kernel, dim3(grid_for(B, 4)), dim3(256), 0, (hipStream_t)stream, tokens, idx, B, T);
+    OV_LAUNCH_CHECK();
+    return OV_OK;
+}
+
+extern "C" int ov_gather_rows_at(const ov_bf16* x, int64_t ldx, const int* idx, ov_bf16* out, int64_t ldo, int B, int L, int D,
+                                 ov_stream_t stream) {
+    if (!x || !idx || !out || B <= 0 || L <= 0 || D <= 0) return OV_ERR_INVALID;
+    if (D % 8 || ldx % 8 || ldo % 8 || ldx < D || ldo < D || (((uintptr_t)x | (uintptr_t)out) & 15)) return OV_ERR_INVALID;
+    hipLaunchKernelGGL(gather_rows_at_kernel, dim3(grid_for((int64_t)B * (D / 8), 256)), dim3(256), 0, (hipStream_t)stream, x, ldx, idx,
+                       out, ldo, B, L, D);
     OV_LAUNCH_CHECK();
     return OV_OK;
 }

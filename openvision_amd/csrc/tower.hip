@@ -321,9 +321,12 @@ EncoderWs vision_ws(const ov_tower* t, const ov_vision_head* h, int B, int K) {
     const size_t tower = tower_ws(t, B, L).total, embed = embed_ws(t, h, B, K).total;
     return encoder_ws((size_t)B * L * D * 2, tower > embed ? tower : embed, head_ws(B, D, h->embed_pad, 4));
 }
-EncoderWs text_ws(const ov_tower* t, const ov_text_head* h, int B) {
+// 'argmax' pooling alone: the pooled position of each caption, int32 [B], behind the head's buffers (idx = the old total)
+struct TextWs { size_t x, tower, head, idx, total; };
+TextWs text_ws(const ov_tower* t, const ov_text_head* h, int B) {
     const int T = h->context_length;
-    return encoder_ws((size_t)B * T * t->cfg.width * 2, tower_ws(t, B, T).total, text_head_ws(t, h, B));
+    const EncoderWs e = encoder_ws((size_t)B * T * t->cfg.width * 2, tower_ws(t, B, T).total, text_head_ws(t, h, B));
+    return {e.x, e.tower, e.head, e.total, e.total + (h->pool_last == OV_TEXT_POOL_ARGMAX ? align_up((size_t)B * sizeof(int), 256) : 0)};
 }
 
 // The text tail's buffers (ov_encode_text) in the tower's big region, free once the last attention has read qkv: a holds the gathered
@@ -916,7 +919,9 @@ inline HeadBufs head_bufs(const HeadWs& w, char* ws) { return {ws + w.rows, (ov_
 // the image head's buffers, after the checks of the head itself
 int vision_head_bufs(const ov_tower* t, const ov_vision_head* h, int B, void* workspace, size_t workspace_bytes, HeadBufs* hb) {
     if (h->embed_pad % 8 || h->embed_pad < h->embed_dim) return OV_ERR_INVALID;
-    if (!h->final_ln_after_pool) return OV_ERR_UNSUPPORTED;       // OpenVision: pool -> LN (transformer.py:638-640)
+    // OpenVision: pool -> LN (transformer.py:638-640).  LN -> pool (:641-643) is the same arithmetic under 'tok' pooling, where the
+    // pool picks one row and LayerNorm is per row; under 'avg' it is another function, which is not built.
+    if (!h->final_ln_after_pool && h->pool_avg) return OV_ERR_UNSUPPORTED;
     const HeadWs w = head_ws(B, t->cfg.width, h->embed_pad, 4);
     if (workspace_bytes < w.total) return OV_ERR_WORKSPACE;
     *hb = head_bufs(w, (char*)workspace);
@@ -1026,14 +1031,15 @@ extern "C" int ov_encode_image_keep(const ov_tower* t, const ov_vision_head* h, 
 }
 
 extern "C" size_t ov_text_workspace_bytes(const ov_tower* t, const ov_text_head* h, int B) {
-    if (!t || !h || B <= 0) return 0;
+    if (!t || !h || B <= 0 || h->pool_last < OV_TEXT_POOL_FIRST || h->pool_last > OV_TEXT_POOL_ARGMAX) return 0;
     return text_ws(t, h, B).total;
 }
 
 extern "C" int ov_encode_text(const ov_tower* t, const ov_text_head* h, const int64_t* tokens, int B, float* features,
                               int normalize, int* err_flag, void* workspace, size_t workspace_bytes, ov_stream_t stream) {
     if (!t || !h || !tokens || !features || !workspace || B <= 0) return OV_ERR_INVALID;
-    const EncoderWs w = text_ws(t, h, B);
+    if (h->pool_last < OV_TEXT_POOL_FIRST || h->pool_last > OV_TEXT_POOL_ARGMAX) return OV_ERR_INVALID;
+    const TextWs w = text_ws(t, h, B);
     if (workspace_bytes < w.total) return OV_ERR_WORKSPACE;
     const ov_tower_cfg& c = t->cfg;
     const int T = h->context_length, D = c.width;
@@ -1044,13 +1050,22 @@ extern "C" int ov_encode_text(const ov_tower* t, const ov_text_head* h, const in
     ov_bf16* last = (ov_bf16*)hb.rows;                            // the pooled row of each caption
     int rc;
     if ((rc = ov_text_embed(tokens, h->token_embedding, h->pos, x, D, B, T, D, h->vocab_size, err_flag, stream))) return rc;
-    const int row = h->pool_last ? T - 1 : 0;
+    // the pooled row: one fixed position, or ('argmax') each caption's own, found once on the device
+    const int row = h->pool_last == OV_TEXT_POOL_LAST ? T - 1 : 0;
+    const int* idx = nullptr;
+    if (h->pool_last == OV_TEXT_POOL_ARGMAX) {
+        if ((rc = ov_token_argmax(tokens, (int*)(ws + w.idx), B, T, stream))) return rc;
+        idx = (const int*)(ws + w.idx);
+    }
+    const auto gather = [&](const ov_bf16* src, ov_bf16* dst) {
+        return idx ? ov_gather_rows_at(src, D, idx, dst, D, B, T, D, stream) : ov_gather_rows(src, D, dst, D, B, T, row, D, stream);
+    };
     const TowerWs tw = tower_ws(t, B, T);
     const TextTailWs tail = text_tail_ws(c, B);
     if (last_block_full() || tw.fp8 || !text_tail_fits(tail, tw)) {
         if ((rc = ov_tower_forward(t, x, B, T, tower, tower_bytes, stream))) return rc;
         // ln_final is per-token, so only the pooled row needs it (model.py:276-277)
-        if ((rc = ov_gather_rows(x, D, last, D, B, T, row, D, stream))) return rc;
+        if ((rc = gather(x, last))) return rc;
     } else {
         // Past the last block's attention only the pooled row of each caption is read: the rest of that block is run_block from past the
         // attention on the B gathered rows as one "image" of L = 1 (same GEMM entry points, and a GEMM row does not depend on the kernel
@@ -1058,8 +1073,8 @@ extern "C" int ov_encode_text(const ov_tower* t, const ov_text_head* h, const in
         if ((rc = tower_walk(t, x, B, T, tower, tower_bytes, stream, BLOCK_PAST_ATTN))) return rc;
         char* big = tower + tw.big;
         ov_bf16* a = (ov_bf16*)(big + tail.a);
-        if ((rc = ov_gather_rows((const ov_bf16*)(tower + tw.h), D, a, D, B, T, row, D, stream))) return rc;
-        if ((rc = ov_gather_rows(x, D, last, D, B, T, row, D, stream))) return rc;
+        if ((rc = gather((const ov_bf16*)(tower + tw.h), a))) return rc;
+        if ((rc = gather(x, last))) return rc;
         const BlockPart rows = {last, a, (ov_bf16*)(big + tail.hid), c.mlp_pad, (float*)(big + tail.stats), nullptr, nullptr, nullptr, B,
                                 stream, true};
         if ((rc = run_block(c, t->blocks[c.layers - 1], nullptr, 0, Fp8Scales{nullptr, nullptr, nullptr, nullptr, 0}, rows, false, 1,

@@ -547,6 +547,7 @@ class Transformer(nn.Module):
         self._cache = _TowerCache()
         self._ws = _Workspace()
         self.causal_prefix: Optional[int] = None      # None = unmasked; see set_causal_prefix
+        self._causal_mask = None                      # see adopt_causal_mask
 
     def set_causal_prefix(self, prefix: Optional[int]) -> None:
         """Attention mask of every block: None (default) = unmasked; an int P >= 0 = prefix-causal, key j is visible to query i iff
@@ -578,10 +579,31 @@ class Transformer(nn.Module):
         delayed=False (serving): the scales stay as they are: repeatable and independent of the batch composition."""
         self.tower().freeze_fp8_scales(delayed)
 
+    def adopt_causal_mask(self, mask: Optional[torch.Tensor]) -> None:
+        """The owning model's causal ``attn_mask`` buffer: the one tensor ``forward(x, attn_mask=...)`` accepts.  The owner adopts
+        it again whenever ``.to()`` / ``.cuda()`` replace the buffer (``CLIP._apply``)."""
+        self._causal_mask = mask
+
+    def _is_own_causal_mask(self, attn_mask: torch.Tensor) -> bool:
+        """attn_mask is the adopted buffer: same storage, offset, shape and strides -- no device read."""
+        own = self._causal_mask
+        return (own is not None and isinstance(attn_mask, torch.Tensor) and attn_mask.dtype == own.dtype
+                and attn_mask.device == own.device and attn_mask.shape == own.shape and attn_mask.stride() == own.stride()
+                and attn_mask.storage_offset() == own.storage_offset()
+                and attn_mask.untyped_storage().data_ptr() == own.untyped_storage().data_ptr())
+
     def forward(self, x: torch.Tensor, attn_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+        prefix = self.causal_prefix
         if attn_mask is not None:
-            raise NotImplementedError("attn_mask is None on the OpenVision path (no_causal_mask=True)")
-        return _run_blocks(list(self.resblocks), x, self._cache, self._ws, self.causal_prefix)
+            # an arbitrary additive mask is not built; the owning CLIP's causal buffer (model.attn_mask, the exploded forward of
+            # ov-zero-shot-test.py:103-155) is the mask of prefix 0
+            if not self._is_own_causal_mask(attn_mask):
+                raise NotImplementedError("attn_mask: only the owning model's causal `attn_mask` buffer is accepted (it runs as "
+                                          "set_causal_prefix(0)); arbitrary additive masks are not built")
+            if x.dim() == 3 and x.shape[1] > attn_mask.shape[0]:
+                raise ValueError(f"sequence of {x.shape[1]} tokens under a causal mask for {attn_mask.shape[0]}")
+            prefix = 0
+        return _run_blocks(list(self.resblocks), x, self._cache, self._ws, prefix)
 
 
 class PatchDropout(nn.Module):
@@ -803,7 +825,8 @@ class VisionTransformer(nn.Module):
 # CLIP
 # ------------------------------------------------------------------------------------------------------
 class CLIP(nn.Module):
-    """Drop-in for ``open_clip.model.CLIP`` (model.py:220-315) on OpenVision configs."""
+    """Drop-in for ``open_clip.model.CLIP`` (model.py:220-315) on OpenVision configs and on the stock open_clip ones (a causal text
+    tower pooled at the EOT token, an image tower with ln_pre and 'tok' pooling); ``quick_gelu`` is not built."""
     output_dict: torch.jit.Final[bool]
 
     def __init__(self, embed_dim: int, vision_cfg: Union[dict, CLIPVisionCfg], text_cfg: Union[dict, CLIPTextCfg],
@@ -812,7 +835,9 @@ class CLIP(nn.Module):
                  output_dict: bool = False):
         super().__init__()
         if quick_gelu:
-            raise NotImplementedError("quick_gelu is not used by OpenVision configs")
+            raise NotImplementedError("quick_gelu=True (the OpenAI CLIP weights: x * sigmoid(1.702 x) in every MLP) is not built: the "
+                                      "GEMM epilogues carry erf and tanh GELU only.  Stock open_clip models trained with nn.GELU "
+                                      "(the LAION / DataComp checkpoints) load with quick_gelu=False")
         self.output_dict = output_dict
         v = vision_cfg_from(vision_cfg)
         t = text_cfg_from(text_cfg)
@@ -833,7 +858,15 @@ class CLIP(nn.Module):
         self.text_projection = nn.Parameter(torch.empty(t.width, embed_dim))
         nn.init.normal_(self.text_projection, std=t.width ** -0.5)
         self.text_pool_type = t.pool_type
-        self.register_buffer("attn_mask", None, persistent=False)     # no_causal_mask -> None (transformer.py:722-725)
+        if t.no_causal_mask:
+            self.register_buffer("attn_mask", None, persistent=False)     # no_causal_mask -> None (transformer.py:722-725)
+        else:
+            # the stock open_clip text tower: the reference's additive mask (build_causal_mask, transformer.py:761-767: -inf strictly
+            # above the diagonal) as the same non-persistent buffer; the kernels run it as the prefix-causal mask with prefix 0
+            mask = torch.full((t.context_length, t.context_length), float("-inf")).triu_(1)
+            self.register_buffer("attn_mask", mask, persistent=False)
+            self.transformer.set_causal_prefix(0)
+            self.transformer.adopt_causal_mask(self.attn_mask)
         self.logit_scale = nn.Parameter(torch.ones([]) * float(init_logit_scale))
         # SigLIP (model.py:251-254): a learned scalar added to every logit; the loss is openvision_amd.loss.SigLipLoss
         self.logit_bias = nn.Parameter(torch.ones([]) * float(init_logit_bias)) if init_logit_bias is not None else None
@@ -855,7 +888,7 @@ class CLIP(nn.Module):
                         proj_t=self.text_projection.detach().t().to(torch.bfloat16).contiguous())
             if self.embed_dim % 8:
                 raise _lib.OvhipError("embed_dim must be a multiple of 8")
-            h = _lib.TextHead(self.context_length, self.vocab_size, int(self.text_pool_type == "last"), self.embed_dim,
+            h = _lib.TextHead(self.context_length, self.vocab_size, _lib.TEXT_POOL[self.text_pool_type], self.embed_dim,
                               ptr(keep["tok"]), ptr(keep["pos"]), ptr(keep["ln"][0]), ptr(keep["ln"][1]), ptr(keep["proj_t"]))
             return h, keep
         return self._pk.get((self.token_embedding.weight, self.positional_embedding, self.ln_final.weight,
@@ -865,7 +898,14 @@ class CLIP(nn.Module):
     def set_precision(self, precision: str, mask=None) -> None:
         """GEMM operand precision of both block stacks: "bf16" (default), "fp8" (e4m3 weights and activations on the MX-scaled MFMA
         for all four GEMMs of every block) or "fp8-mixed" (e4m3 for the MLP products only: model.fp8_mixed_mask); `mask` = an explicit
-        OV_FP8_* bit set instead.  Embedding, heads, attention, LayerNorm statistics and the loss stay as they are."""
+        OV_FP8_* bit set instead.  Embedding, heads, attention, LayerNorm statistics and the loss stay as they are.
+
+        A causal text tower (the stock open_clip configuration) has no fp8 form: the masked attention runs in bf16 only."""
+        if precision not in PRECISIONS:
+            raise ValueError(f"precision must be one of {PRECISIONS}")
+        if precision != "bf16" and self.transformer.causal_prefix is not None:
+            raise ValueError(f"set_precision({precision!r}): the text tower is causal, and there is no fp8 under an attention mask.  "
+                             f"model.visual.transformer.set_precision({precision!r}) puts the image tower alone in fp8")
         self.visual.transformer.set_precision(precision, mask)
         self.transformer.set_precision(precision, mask)
 
@@ -972,6 +1012,12 @@ class CLIP(nn.Module):
         """Forget the bf16 / fp8 packed copies, folded LayerNorm weights and tower handles (see ``_Packed``): required after
         in-place parameter writes through ``.data``, which leave ``_version`` unchanged."""
         invalidate_packed()
+
+    def _apply(self, fn, *a, **k):
+        out = super()._apply(fn, *a, **k)          # .to() / .cuda() / .float() replace the buffers: follow the causal mask
+        if self.attn_mask is not None:
+            self.transformer.adopt_causal_mask(self.attn_mask)
+        return out
 
     def load_state_dict(self, *a, **k):
         out = super().load_state_dict(*a, **k)

@@ -109,6 +109,9 @@ def _make_v1(model_cfg: Dict[str, Any], seed: int = 0) -> Dict[str, torch.Tensor
     sd["visual.proj"] = _normal("visual.proj", (d, e), 1.0 / math.sqrt(d), seed)
     sd["visual.conv1.weight"] = _normal("visual.conv1.weight", (d, 3, v.patch_size, v.patch_size),
                                         1.0 / math.sqrt(3 * v.patch_size ** 2), seed)
+    if not v.no_ln_pre:                       # the stock open_clip image tower (transformer.py:491); OpenVision has none
+        sd["visual.ln_pre.weight"] = _normal("visual.ln_pre.weight", (d,), 0.1, seed, 1.0)
+        sd["visual.ln_pre.bias"] = _normal("visual.ln_pre.bias", (d,), 0.1, seed)
     for i in range(v.layers):
         _block(sd, f"visual.transformer.resblocks.{i}.", d, mlp_width(d, v.mlp_ratio), seed)
     sd["visual.ln_post.weight"] = _normal("visual.ln_post.weight", (d,), 0.1, seed, 1.0)

@@ -427,8 +427,8 @@ def tower_forward(transformer, x: torch.Tensor, prefix=_OWN) -> torch.Tensor:
 
 
 def encode_image(model, image: torch.Tensor, normalize: bool = True, keep: torch.Tensor = None, output_tokens: bool = False):
-    """CLIP.encode_image (model.py:265-267) with gradients.  VisionTransformer.forward, transformer.py:609-651, for the
-    OpenVision configuration (no ln_pre, pool -> ln_post -> proj).
+    """CLIP.encode_image (model.py:265-267) with gradients.  VisionTransformer.forward, transformer.py:609-651: the OpenVision
+    configuration (no ln_pre, pool -> ln_post -> proj) and the stock one (ln_pre, ln_post -> 'tok' pool -> proj).
 
     Patch dropout (transformer.py:619): when the vision tower is in training mode with ``patch_dropout`` p > 0, the kept patches are
     drawn as the reference draws them (``PatchDropout.sample``: CPU default generator) and the tower runs on those 1 + K tokens.
@@ -438,8 +438,6 @@ def encode_image(model, image: torch.Tensor, normalize: bool = True, keep: torch
     ``output_tokens``: also return what the reference hands to the caption decoder (vit.py:753,786): the block stack's output without
     the CLS token and BEFORE ln_post, [B, L - 1, width] (the kept patches under patch dropout), with gradients into the tower."""
     v = model.visual
-    if not isinstance(v.ln_pre, torch.nn.Identity):
-        raise _lib.OvhipError("training path: ln_pre is Identity for OpenVision towers")
     p = v.patch_size[0]
     w = v.conv1.weight
     bsz, _, hh, ww = image.shape
@@ -464,6 +462,8 @@ def encode_image(model, image: torch.Tensor, normalize: bool = True, keep: torch
         x = _LinearFn.apply(patches, w.reshape(w.shape[0], -1), None).view(bsz, gh * gw, -1)
         cls = v.class_embedding.float().expand(x.shape[0], 1, -1)
         x = torch.cat([cls, x], dim=1) + v.positional_embedding.float()                            # :615-617
+    if not isinstance(v.ln_pre, torch.nn.Identity):                # :620, after the patch dropout: on the kept tokens only
+        x = _LayerNormFn.apply(x, v.ln_pre.weight, v.ln_pre.bias, v.ln_pre.eps)
     x = tower_forward(v.transformer, x)
     tokens = x[:, 1:]
     if v.final_ln_after_pool:
@@ -502,7 +502,9 @@ def encode_text_embeddings(model, x: torch.Tensor, normalize: bool = True, pool_
 
 
 def encode_text(model, text: torch.Tensor, normalize: bool = True, output_tokens: bool = False):
-    """CLIP.encode_text (model.py:269-284) with gradients: no mask, ln_final on all tokens, pool per text_pool_type.  `text`: int64
+    """CLIP.encode_text (model.py:269-284) with gradients: the tower's own mask (none for OpenVision; causal for a stock open_clip
+    config, whose ``CLIP`` sets ``transformer.causal_prefix = 0``), ln_final on all tokens, pool per text_pool_type ('argmax': the row
+    of each caption's largest id, ``text.argmax(-1)``, the first of equals as on the inference path).  `text`: int64
     token ids [B, T], or a float [B, T, vocab] matrix of (soft) one-hot rows (ov-gradient-ascent.py:105: `text @ token_embedding.weight`,
     gradients flow to the rows)."""
     if text.is_floating_point():

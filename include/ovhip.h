@@ -818,6 +818,35 @@ int ov_mlp_feature_backward(const ov_bf16* x1, int64_t ldx, const float* ln2_w, 
                             int gelu_tanh, const float* pre, const float* dmean, ov_bf16* dx1, int64_t lddx, int B, int L, int D, float eps,
                             ov_stream_t stream);
 
+/* ---- the feature-visualisation loop around that objective (ov-feature-visualization.py:120-136, 214-215; csrc/vizloop.hip).  img fp32
+ * [N,3,S,S]; B = R N batch rows, row b = r N + n (img.repeat(R,1,1,1)); table: the step's fp32 [3][3B] = mean | std | noise of row b,
+ * channel c at b*3 + c (device); off1 / off2: the step's roll (any int, taken mod S).  All four enqueue on `stream`, allocate nothing,
+ * use no atomics (fixed-order sums: bitwise repeatable).  Null pointers, non-positive sizes and misaligned buffers are OV_ERR_INVALID:
+ * 16 bytes for the image-shaped buffers, cols, norms and the optimiser state, 4 bytes for table, m and history_row (a step's row of a
+ * packed [steps + 1][3][3B] table or [steps + 1][3] history starts wherever it falls).  Then S % P != 0, S outside [P, 1024] and
+ * R N > 4096 are OV_ERR_UNSUPPORTED. */
+
+/* aug[b,c,y,x] = ((img[n,c,(y-off1) mod S,(x-off2) mod S] - mean) / std) + noise: fp32 in that order, a true division.  cols [B*g*g, Kpad]
+ * = bf16(aug) as conv1 operand rows (ov_im2col_patches' layout, the columns past 3 P^2 zero; Kpad % 8 == 0); aug fp32 [B,3,S,S] or NULL. */
+int ov_viz_augment(const float* img, const float* table, int N, int R, int S, int P, int Kpad, int off1, int off2, ov_bf16* cols,
+                   float* aug, ov_stream_t stream);
+/* BaseTotalVariation's four difference fields of aug fp32 [B,3,S,S] (x, y, the two diagonals; none across the plane's border):
+ * norms[dir*3B + b*3 + c] = the plane's L2 norm of field dir (fp32 [4][3B]); *tv (device scalar, NULL = skipped) = sum_dir
+ * mean_planes(norm) * S^2 / size^2 (TotalVariation(2, size)). */
+int ov_viz_tv(const float* aug, int B, int S, int size, float* norms, float* tv, ov_stream_t stream);
+/* dimg[n,c,y',x'] = sum_{r ascending} d_aug[b,c,(y'+off1) mod S,(x'+off2) mod S] / std[b,c], d_aug = fp32(dcols entry of that pixel)
+ * + c_tv * d tv / d aug (+-diff / (norm 3B) * S^2 / size^2 over the up to eight differences the pixel ends; 0 where norm == 0).  dcols
+ * bf16 [B*g*g, ldc] in cols' layout; aug, norms, table as above.  history_row (device fp32 [3], NULL together with m = skipped) =
+ * (loss, c_feat * -(1/B^2) sum_b m[b], c_tv * tv), loss their sum; m device fp32 [B]. */
+int ov_viz_augment_backward(const ov_bf16* dcols, int64_t ldc, const float* aug, const float* norms, const float* table, const float* m,
+                            int N, int R, int S, int P, int off1, int off2, int size, float c_feat, float c_tv, float* dimg,
+                            float* history_row, ov_stream_t stream);
+/* One step of torch.optim.Adamax (torch 2.10 _single_tensor_adamax, no weight decay) followed by the script's Clip, on flat fp32 [n]:
+ * ea += (g - ea) (1 - b1);  ei = max(b2 ei, |g| + eps);  img = clamp(img - clr ea / ei, lo, hi), clr = lr_t / (1 - b1^t) from the host.
+ * 0 <= b1, b2 < 1, eps >= 0, lo <= hi. */
+int ov_adamax_clip_step(float* img, const float* dimg, float* ea, float* ei, int64_t n, double clr, double b1, double b2, double eps,
+                        float lo, float hi, ov_stream_t stream);
+
 typedef struct {      /* VisionTransformer front/back ends (OpenVision: no ln_pre, no conv bias) */
     int image_size, patch_size, kpad;              /* kpad = roundup(3*P*P, 64) */
     int pool_avg;                                  /* 1 = 'avg' (skip cls), 0 = 'tok' */

@@ -215,6 +215,12 @@ SIGNATURES = {
                                        c_int, c_float, c_void_p, c_void_p, c_void_p]),
     "ov_mlp_feature_backward": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                         c_int64, c_int, c_int, c_int, c_float, c_void_p]),
+    "ov_viz_augment": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "ov_viz_tv": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "ov_viz_augment_backward": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                        c_int, c_float, c_float, c_void_p, c_void_p, c_void_p]),
+    "ov_adamax_clip_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, C.c_double, C.c_double, C.c_double, C.c_double,
+                                    c_float, c_float, c_void_p]),
     "ov_clip_loss_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p,
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "ov_adamw_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float, c_float, c_int, c_float,

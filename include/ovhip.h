@@ -847,6 +847,46 @@ int ov_viz_augment_backward(const ov_bf16* dcols, int64_t ldc, const float* aug,
 int ov_adamax_clip_step(float* img, const float* dimg, float* ea, float* ei, int64_t n, double clr, double b1, double b2, double eps,
                         float lo, float hi, ov_stream_t stream);
 
+/* ---- the gradient-ascent loop around the frozen text tower (ov-gradient-ascent.py:226-259, 380-381; csrc/ascent.hip).  normu fp32
+ * [R, V] is what is learned, R = B K rows (row r = b K + k); e fp32 [R, V] the step's Exp(1) draws; z = (normu - log e) / tau, ys =
+ * softmax(z), both fp32 with true divisions, log e the correctly rounded fp32 logarithm (taken in double).  All five enqueue on `stream`, allocate nothing and use no atomics (fixed-order sums:
+ * bitwise repeatable); nothing is flushed to zero.  Null pointers, non-positive sizes, tau <= 0 and misaligned buffers are
+ * OV_ERR_INVALID: 16 bytes for dX and W, 8 for ids, 4 for everything else (a step's row of a packed history starts wherever it
+ * falls).  R > 4096 is OV_ERR_UNSUPPORTED. */
+
+/* out[b,c,y,x] = (bilinear(img[c]; sx, sy) - mean[c]) / stdv[c] with (sx, sy) = (a0 x + a1 y + a2, a3 x + a4 y + a5), mats[b] = a0..a5
+ * the INVERSE map in pixel coordinates (destination -> source): the four taps around (sx, sy), each zero outside the image, weights
+ * (x1 - sx)(y1 - sy) ... as F.grid_sample('bilinear', 'zeros', align_corners=False) forms them; fp32, a true division.  img fp32
+ * [3,S,S]; mats fp32 [B,6], mean / stdv fp32 [3] (device); out [B,3,S,S] in out_dtype (OV_F32 / OV_BF16).  The identity matrix gives
+ * the normalised source bit for bit.  S <= 4096. */
+int ov_ga_affine(const float* img, const float* mats, const float* mean, const float* stdv, void* out, int out_dtype, int B, int S,
+                 ov_stream_t stream);
+/* Per row r: z[r,v] = (normu - log e) / tau (fp32 [R,V], kept for the two kernels below: the double logarithm is formed once), idx[r] =
+ * the first position of max_v z, zmax[r] = that maximum, zsum[r] = sum_v exp(z - zmax) (one workgroup per row, one order).
+ * history_row (int32 [R], NULL = skipped) receives idx as well; ids (int64 [R / K, T], NULL = skipped) receives idx[b K + k] at
+ * [b, T - K + k]: the K learned positions close each row of the id matrix, the others are the caller's. */
+int ov_ga_sample(const float* normu, const float* e, float tau, int R, int V, int K, int T, float* z, int* idx, float* zmax, float* zsum,
+                 int* history_row, int64_t* ids, ov_stream_t stream);
+/* ceil(V / 128): the slabs of the vocabulary, one partial sum per row and slab (parts [R, that many]); 0 for V <= 0. */
+int ov_ga_parts_blocks(int V);
+/* gy[r,v] = sum_d dX[r,d] W[v,d] (fp32 [R,V]; bf16 operands, fp32 accumulation on the MFMA) and parts[r, blk] = sum over slab blk of
+ * gy[r,v] ys[r,v], ys = exp(z - zmax) / zsum.  dX bf16 [R,D], W bf16 [V,D], both dense; z / zmax / zsum from ov_ga_sample.  R and V of
+ * any size; D % 64 == 0 and D <= 1216, OV_ERR_UNSUPPORTED otherwise.  W is read once for every 64 rows of dX. */
+int ov_ga_token_grad(const ov_bf16* dX, const ov_bf16* W, const float* z, const float* zmax, const float* zsum, int R, int V, int D,
+                     float* gy, float* parts, ov_stream_t stream);
+/* c_r = sum_blk parts[r, blk] (ascending), g = ys (gy - c_r) / tau, then one step of torch.optim.Adam (_single_tensor_adam, no weight
+ * decay, no amsgrad) on normu in its own operation order: ea += (g - ea)(1 - b1); es = b2 es + (1 - b2) g g; denom = sqrt(es) /
+ * sqrt(bias_correction2) + eps; normu -= (lr / bias_correction1) ea / denom.  bias_correction{1,2} = 1 - b{1,2}^t from the host, in
+ * double.  g (fp32 [R,V], NULL = skipped) receives the gradient. */
+int ov_ga_adam(const float* gy, const float* parts, float* normu, const float* z, const float* zmax, const float* zsum, float tau, int R,
+               int V, float* exp_avg, float* exp_avg_sq, double lr, double b1, double b2, double eps, double bias_correction1,
+               double bias_correction2, float* g, ov_stream_t stream);
+/* loss1_row[j] = -100 mean_i cos(tx_j, img_i), cos = x.y / (max(|x|, 1e-8) max(|y|, 1e-8)) (torch.cosine_similarity); dtx = d mean_j
+ * loss1[j] / d tx.  tx, img, dtx, best_tx fp32 [B,E]; any E >= 1, B <= 64 (OV_ERR_UNSUPPORTED above).  If the mean is below best[0]
+ * (device fp32; start it at +inf): best[0] = mean, best_step[0] = step, best_tx = tx.  One launch, one workgroup. */
+int ov_ga_cosine_loss(const float* tx, const float* img, int B, int E, int step, float* loss1_row, float* dtx, float* best, int* best_step,
+                      float* best_tx, ov_stream_t stream);
+
 typedef struct {      /* VisionTransformer front/back ends (OpenVision: no ln_pre, no conv bias) */
     int image_size, patch_size, kpad;              /* kpad = roundup(3*P*P, 64) */
     int pool_avg;                                  /* 1 = 'avg' (skip cls), 0 = 'tok' */

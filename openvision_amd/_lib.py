@@ -221,6 +221,14 @@ SIGNATURES = {
                                         c_int, c_float, c_float, c_void_p, c_void_p, c_void_p]),
     "ov_adamax_clip_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, C.c_double, C.c_double, C.c_double, C.c_double,
                                     c_float, c_float, c_void_p]),
+    "ov_ga_affine": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "ov_ga_sample": (c_int, [c_void_p, c_void_p, c_float, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                             c_void_p, c_void_p]),
+    "ov_ga_parts_blocks": (c_int, [c_int]),
+    "ov_ga_token_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "ov_ga_adam": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_void_p, c_void_p,
+                           C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, c_void_p, c_void_p]),
+    "ov_ga_cosine_loss": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ov_clip_loss_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p,
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "ov_adamw_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float, c_float, c_int, c_float,

@@ -110,6 +110,8 @@ class WordPieceTokenizer:
         # the library registers these as special tokens: matched verbatim in the raw text, never normalised or split
         special = [t for t in (unk_token, "[SEP]", "[CLS]", "[PAD]", "[MASK]") if t in self.vocab]
         self._special = re.compile("(" + "|".join(re.escape(t) for t in special) + ")")
+        self._special_ids = frozenset(self.vocab[t] for t in special)
+        self._tokens: Optional[List[str]] = None         # id -> token, built by the first decode
         self.context_length = context_length
         self.bos_token, self.eos_token, self.class_token, self.pad_token = bos_token, eos_token, class_token, pad_token
 
@@ -141,6 +143,30 @@ class WordPieceTokenizer:
             for w in pre_tokenize(normalize(part)):
                 ids.extend(self._wordpiece(w))
         return ids
+
+    def decode(self, ids: Sequence[int], skip_special_tokens: bool = True, clean_up_tokenization_spaces: bool = True) -> str:
+        """``transformers``' ``BertTokenizer.decode`` on this vocabulary (what ov-gradient-ascent.py:159 prints): the tokens joined by
+        spaces, ``##`` continuations merged into the piece before them, the special tokens ([UNK], [SEP], [PAD], [CLS], [MASK]; not the
+        framing's [bos] / [eos], which that library does not know as special) dropped on request, then ``clean_up_tokenization``'s
+        replacements (no space before ``. ? ! ,`` and the English contractions).  An id outside the vocabulary file decodes as [UNK], as in that library."""
+        if self._tokens is None:
+            self._tokens = [None] * (max(self.vocab.values()) + 1)
+            for t, i in self.vocab.items():
+                self._tokens[i] = t
+        ids = [int(i) for i in (ids.tolist() if hasattr(ids, "tolist") else ids)]
+        skip = self._special_ids if skip_special_tokens else ()
+        tokens = []
+        for i in ids:
+            if not 0 <= i < len(self._tokens) or self._tokens[i] is None:
+                i = self.unk_id                      # ids_to_tokens.get(index, unk_token): a model's vocabulary may be padded past the file
+            if i not in skip:
+                tokens.append(self._tokens[i])
+        text = " ".join(tokens).replace(" " + self.prefix, "").strip()
+        if clean_up_tokenization_spaces:
+            for a, b in ((" .", "."), (" ?", "?"), (" !", "!"), (" ,", ","), (" ' ", "'"), (" n't", "n't"), (" 'm", "'m"), (" 's", "'s"),
+                         (" 've", "'ve"), (" 're", "'re")):
+                text = text.replace(a, b)
+        return text
 
     def frame(self, ids: Sequence[int], context_length: int) -> List[int]:
         """CustomTokenizer.tokenize + pad_and_add_class_token (tokenizer.py:534-550); the reference truncates to its own

@@ -44,8 +44,18 @@ def read_state_dict(path: str) -> Dict[str, torch.Tensor]:
     raise FileNotFoundError(f"no {BIN_NAME} / {SAFETENSORS_NAMES[0]} under {path}")
 
 
-def from_pretrained(path: str, device: Optional[str] = "cuda:0") -> Tuple[CLIP, dict]:
+def from_pretrained(path: str, device: Optional[str] = "cuda:0", force_image_size: Optional[int] = None,
+                    pos_embed_type: Optional[str] = None) -> Tuple[CLIP, dict]:
     """Returns (model.eval() on ``device``, preprocess_cfg).  Strict key/shape match, as the reference's loader.
+
+    ``force_image_size`` (a multiple of the patch size): the model is built at that size instead of the config's (factory.py:195,
+    246-248), the checkpoint's position tables are brought to the model's shapes on the host (``posembed.resize_for``: a fixed image
+    table regenerated after a check of its form, a learned one resampled bicubic / antialiased, the text table linear), then the
+    load is strict.  This is how a stage of the recipe starts from the previous one, and how a 224 px model is evaluated at 336.
+    ``pos_embed_type`` overrides the config's value.  Converted OpenVision configs say 'learnable' although the table they carry is
+    the recipe's fixed 'sincos2d' one: ``from_pretrained(dir, force_image_size=224, pos_embed_type='sincos2d')`` continues such a
+    checkpoint the recipe's way, with the table regenerated and kept out of training.  Without either argument nothing changes:
+    a checkpoint of another resolution raises on its shapes.
 
     A stock ``open_clip_config.json`` directory loads too (``text_cfg`` defaults: causal mask, 'argmax' pooling; ``vision_cfg``
     defaults: ln_pre, 'tok' pooling): the LAION / DataComp ViT-B/32 ... bigG checkpoints.  ``quick_gelu: true`` (the OpenAI weights)
@@ -57,7 +67,15 @@ def from_pretrained(path: str, device: Optional[str] = "cuda:0") -> Tuple[CLIP, 
     core = {k: v for k, v in model_cfg.items() if k in ("embed_dim", "vision_cfg", "text_cfg")}
     extra = {k: v for k, v in model_cfg.items() if k not in core and k not in ("quick_gelu",) or (k == "quick_gelu" and v)}
     extra = {k: v for k, v in extra.items() if k in ("quick_gelu", "init_logit_scale", "init_logit_bias", "output_dict")}
-    model = create_model({**core, **extra}, device=device, state_dict=sd)
+    resize = force_image_size is not None or pos_embed_type is not None
+    if resize:
+        vcfg = dict(core["vision_cfg"])
+        if force_image_size is not None:
+            vcfg["image_size"] = force_image_size
+        if pos_embed_type is not None:
+            vcfg["pos_embed_type"] = pos_embed_type
+        core["vision_cfg"] = vcfg
+    model = create_model({**core, **extra}, device=device, state_dict=sd, resize_pos_embed=resize)
     return model, pp
 
 

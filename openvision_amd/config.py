@@ -7,6 +7,16 @@ Only the fields the encode-and-contrast path reads are kept: the OpenVision towe
 open_clip ones (causal text with 'argmax' pooling, ln_pre, 'tok' pooling).  Anything that would
 select a different architecture (attentional pooling, timm/HF towers, quick_gelu, layer-scale,
 embed_cls, proj_bias) is rejected loudly instead of being silently ignored.
+
+``vision_cfg.pos_embed_type`` selects the image position table (``openvision_amd.posembed``):
+
+    'learnable'    (default) a trained table, as before.
+    'sin_cos_2d'   the reference's torch meaning (transformer.py:477-484): the fixed MAE-form table, ``requires_grad=False``.
+    'sincos2d'     an EXTENSION, the JAX recipe's own name (configs/openvision.py:164): the fixed MoCo-v3-form table the
+                   converter writes into OpenVision checkpoints.  The vendored open_clip raises on this value, so a config
+                   handed back to the reference's loader says 'learnable' (the table is in the state dict either way).
+
+Any other value raises.  Both fixed forms need a width that is a multiple of 4.
 """
 from __future__ import annotations
 
@@ -62,6 +72,9 @@ class CLIPTextCfg:
     hf_model_name: Optional[str] = None
 
 
+POS_EMBED_TYPES = ("learnable", "sin_cos_2d", "sincos2d")      # posembed.py: trained | fixed MAE form | fixed MoCo-v3 form
+
+
 def _from_dict(cls, d: Union[dict, Any]):
     if isinstance(d, cls):
         return d
@@ -88,6 +101,10 @@ def vision_cfg_from(d) -> CLIPVisionCfg:
         raise ValueError("vision width must be a multiple of head_width")
     if c.image_size % c.patch_size:
         raise ValueError("image_size must be a multiple of patch_size")
+    if c.pos_embed_type not in POS_EMBED_TYPES:
+        raise ValueError(f"vision pos_embed_type {c.pos_embed_type!r}: expected one of {POS_EMBED_TYPES}")
+    if c.pos_embed_type != "learnable" and c.width % 4:
+        raise ValueError(f"vision pos_embed_type {c.pos_embed_type!r} needs a width that is a multiple of 4, got {c.width}")
     return c
 
 
@@ -142,10 +159,11 @@ _SIZES = {
 
 
 def openvision_model_cfg(size: str, patch: int, image: int, *, context_length: int = 80,
-                         vocab_size: int = 32000) -> Dict[str, Any]:
-    """``model_cfg`` block of an OpenVision ``open_clip_config.json``."""
+                         vocab_size: int = 32000, pos_embed_type: Optional[str] = None) -> Dict[str, Any]:
+    """``model_cfg`` block of an OpenVision ``open_clip_config.json``.  ``pos_embed_type``: added to ``vision_cfg``
+    only when given (converted checkpoints carry none: 'learnable'); 'sincos2d' keeps the recipe's table fixed in training."""
     s = _SIZES[size]
-    return {
+    cfg = {
         "embed_dim": s["e"],
         "vision_cfg": {
             "image_size": image, "patch_size": patch, "layers": s["vl"], "width": s["vw"],
@@ -159,6 +177,11 @@ def openvision_model_cfg(size: str, patch: int, image: int, *, context_length: i
             "act_kwargs": {"approximate": "tanh"},
         },
     }
+    if pos_embed_type is not None:
+        if pos_embed_type not in POS_EMBED_TYPES:
+            raise ValueError(f"pos_embed_type {pos_embed_type!r}: expected one of {POS_EMBED_TYPES}")
+        cfg["vision_cfg"]["pos_embed_type"] = pos_embed_type
+    return cfg
 
 
 PRESETS = {

@@ -18,8 +18,10 @@ There is NO CPU / eager fallback: calling any forward with CPU tensors, or witho
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import math
 import os
+import types
 from collections import OrderedDict
 from typing import Optional, Tuple, Union
 
@@ -29,7 +31,8 @@ from torch import nn
 
 from . import _lib
 from ._lib import OV_BF16, OV_F32, EPI_BIAS, EPI_GELU_ERF, EPI_GELU_TANH, EPI_RESIDUAL, ptr, stream_ptr, check
-from .config import (CLIPVisionCfg, CLIPTextCfg, vision_cfg_from, text_cfg_from, gelu_is_tanh, ln_eps,
+from . import posembed
+from .config import (CLIPVisionCfg, CLIPTextCfg, POS_EMBED_TYPES, vision_cfg_from, text_cfg_from, gelu_is_tanh, ln_eps,
                      mlp_width)
 
 MAX_MICRO_BATCH = 1024          # encode_* split larger batches so the workspace stays bounded
@@ -664,8 +667,11 @@ class VisionTransformer(nn.Module):
     def __init__(self, image_size: int, patch_size: int, width: int, layers: int, heads: int, mlp_ratio: float,
                  output_dim: int, pool_type: str = "avg", final_ln_after_pool: bool = True, no_ln_pre: bool = True,
                  act_kwargs: Optional[dict] = None, eps: float = 1e-6, output_tokens: bool = False,
-                 patch_dropout: float = 0.0):
+                 patch_dropout: float = 0.0, pos_embed_type: str = "learnable"):
         super().__init__()
+        if pos_embed_type not in POS_EMBED_TYPES:
+            raise ValueError(f"pos_embed_type {pos_embed_type!r}: expected one of {POS_EMBED_TYPES}")
+        self.pos_embed_type = pos_embed_type
         self.output_tokens = output_tokens
         self.image_size = (image_size, image_size)
         self.patch_size = (patch_size, patch_size)
@@ -675,7 +681,13 @@ class VisionTransformer(nn.Module):
         self.conv1 = PatchConv(width, patch_size)
         scale = width ** -0.5
         self.class_embedding = nn.Parameter(scale * torch.randn(width))
-        self.positional_embedding = nn.Parameter(scale * torch.randn(self.grid_size[0] * self.grid_size[1] + 1, width))
+        if pos_embed_type == "learnable":
+            self.positional_embedding = nn.Parameter(scale * torch.randn(self.grid_size[0] * self.grid_size[1] + 1, width))
+        else:
+            # transformer.py:477-484: a fixed table under the same name, in the state dict, never trained.  'sin_cos_2d' is the
+            # reference's MAE form, 'sincos2d' the recipe's MoCo-v3 form (posembed.py)
+            self.positional_embedding = nn.Parameter(posembed.fixed_table(pos_embed_type, self.grid_size[0], width),
+                                                     requires_grad=False)
         # transformer.py:481: dropout only when p > 0 (the module has no parameters: the state dict is the same either way)
         self.patch_dropout = PatchDropout(patch_dropout) if patch_dropout > 0. else nn.Identity()
         self.ln_pre = nn.Identity() if no_ln_pre else LayerNorm(width, eps=eps)
@@ -723,9 +735,43 @@ class VisionTransformer(nn.Module):
         """Parameters of the locking groups, input side first: the patch embedding with class / positional embeddings and ln_pre,
         one group per block, the last block together with ln_post, and the output projection."""
         blocks = list(self.transformer.resblocks)
-        embed = [*self.conv1.parameters(), self.class_embedding, self.positional_embedding, *self.ln_pre.parameters()]
+        # a fixed sin-cos table (transformer.py:481-482: requires_grad=False from birth) is in no group: unlocking never trains it
+        pos = [self.positional_embedding] if self.pos_embed_type == "learnable" else []
+        embed = [*self.conv1.parameters(), self.class_embedding, *pos, *self.ln_pre.parameters()]
         top = [*blocks[-1].parameters(), *self.ln_post.parameters()]
         return [embed] + [list(b.parameters()) for b in blocks[:-1]] + [top, [self.proj]]
+
+    def set_input_size(self, image_size: int) -> None:
+        """Run this tower at another resolution (the stages of the reference's recipe: 84 -> 224 -> 336 px): ``image_size`` is a
+        square size in pixels, a positive multiple of the patch size, else ValueError.  Updates ``image_size``, ``grid_size`` and the
+        position table:
+
+        * a fixed table ('sin_cos_2d' / 'sincos2d') is regenerated for the new grid (vit.py:922-927), bitwise the table of a model
+          built at that size;
+        * a 'learnable' one is resampled as ``posembed.resize_pos_embed`` does on load (bicubic, antialiased, class row kept).
+
+        The table arithmetic is host work: a model that lives on the device is resized through ONE host round trip of the table (a
+        few MB at most), nothing else moves.  The new table is a NEW ``nn.Parameter`` with the old one's ``requires_grad``, dtype
+        and device; packed copies and captured graphs are dropped and rebuilt on next use.  An optimiser built before the call
+        still holds the old parameter: build the optimiser of a stage AFTER ``set_input_size`` (as the recipe does, whose
+        ``ft_from`` carries parameters only, no optimiser state)."""
+        p = self.patch_size[0]
+        if isinstance(image_size, bool) or not isinstance(image_size, int) or image_size <= 0 or image_size % p:
+            raise ValueError(f"set_input_size: expected a square size as an int, a positive multiple of the patch size {p}, "
+                             f"got {image_size!r}")
+        g = image_size // p
+        old = self.positional_embedding
+        if g * g + 1 != old.shape[0]:
+            if self.pos_embed_type == "learnable":
+                sd = {"visual.positional_embedding": old.detach().float().cpu()}
+                posembed.resize_pos_embed(sd, types.SimpleNamespace(visual=types.SimpleNamespace(grid_size=(g, g))))
+                table = sd["visual.positional_embedding"]
+            else:
+                table = posembed.fixed_table(self.pos_embed_type, g, old.shape[1])
+            self.positional_embedding = nn.Parameter(table.to(device=old.device, dtype=old.dtype).contiguous(),
+                                                     requires_grad=old.requires_grad)
+        self.image_size, self.grid_size = (image_size, image_size), (g, g)
+        invalidate_packed()          # the head bakes the image size and the table's address in; graphs hold both
 
     def _check_image(self, x: torch.Tensor):
         _require_cuda(x, "VisionTransformer")
@@ -846,7 +892,8 @@ class CLIP(nn.Module):
             image_size=v.image_size, patch_size=v.patch_size, width=v.width, layers=v.layers,
             heads=v.width // v.head_width, mlp_ratio=v.mlp_ratio, output_dim=embed_dim, pool_type=v.pool_type,
             final_ln_after_pool=v.final_ln_after_pool, no_ln_pre=v.no_ln_pre, act_kwargs=v.act_kwargs,
-            eps=ln_eps(v.norm_kwargs), output_tokens=v.output_tokens, patch_dropout=float(v.patch_dropout))
+            eps=ln_eps(v.norm_kwargs), output_tokens=v.output_tokens, patch_dropout=float(v.patch_dropout),
+            pos_embed_type=v.pos_embed_type)
         # text tower parts are adopted at the top level, as the reference does (model.py:239-248)
         self.transformer = Transformer(t.width, t.layers, t.heads, t.mlp_ratio, t.act_kwargs, ln_eps(t.norm_kwargs))
         self.context_length = t.context_length
@@ -1029,6 +1076,12 @@ class CLIP(nn.Module):
         afterwards: ``FusedAdamW`` collects the parameters that require grad when it is constructed."""
         self.visual.lock(unlocked_groups=unlocked_groups, freeze_bn_stats=freeze_bn_stats)
 
+    def set_input_size(self, image_size: int) -> None:
+        """Run the image tower at another resolution: ``VisionTransformer.set_input_size`` (one host round trip of the position
+        table; build the stage's optimiser afterwards).  The text tower is untouched."""
+        self.visual.set_input_size(image_size)
+        self.vision_cfg = dataclasses.replace(self.vision_cfg, image_size=int(image_size))
+
     def set_grad_checkpointing(self, enable=True):
         """Activation recomputation on the training path (model.py:261-263 of the reference; its trainer's remat='full' per block):
         ``openvision_amd.training`` then keeps only each block's input and recomputes the block's intermediates just before its
@@ -1063,10 +1116,18 @@ def l2_normalize(x: torch.Tensor) -> torch.Tensor:
     return out.view(x.shape)
 
 
-def create_model(model_cfg: dict, device=None, state_dict: Optional[dict] = None, **kw) -> CLIP:
-    """``CLIP(**model_cfg)`` + optional strict ``load_state_dict`` (ov-zero-shot-test.py:52-56)."""
+def create_model(model_cfg: dict, device=None, state_dict: Optional[dict] = None, resize_pos_embed: bool = False, **kw) -> CLIP:
+    """``CLIP(**model_cfg)`` + optional strict ``load_state_dict`` (ov-zero-shot-test.py:52-56).
+
+    ``resize_pos_embed=True``: a state dict from another resolution (or text context length) loads, as the reference's
+    ``load_checkpoint`` does it (factory.py:178): on a shallow copy of the dict, a fixed image table is regenerated for the model's
+    grid after a check of its form, a learned one is resampled (bicubic, antialiased), the text table is resampled (linear) --
+    ``posembed.resize_for`` -- and then the load is strict as ever.  Default False: a shape mismatch raises."""
     m = CLIP(embed_dim=model_cfg["embed_dim"], vision_cfg=model_cfg["vision_cfg"], text_cfg=model_cfg["text_cfg"],
              **{k: v for k, v in model_cfg.items() if k not in ("embed_dim", "vision_cfg", "text_cfg")}, **kw)
+    if state_dict is not None and resize_pos_embed:
+        state_dict = dict(state_dict)
+        posembed.resize_for(state_dict, m)
     if state_dict is not None:
         m.load_state_dict(state_dict, strict=True)
     if device is not None:

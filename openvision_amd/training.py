@@ -440,6 +440,9 @@ def encode_image(model, image: torch.Tensor, normalize: bool = True, keep: torch
     v = model.visual
     p = v.patch_size[0]
     w = v.conv1.weight
+    if image.dim() != 4 or image.shape[1] != 3 or tuple(image.shape[2:]) != tuple(v.image_size):
+        raise ValueError(f"expected images [B,3,{v.image_size[0]},{v.image_size[1]}] (the model's size; model.set_input_size changes "
+                         f"it), got {tuple(image.shape)}")
     bsz, _, hh, ww = image.shape
     gh, gw = hh // p, ww // p
     explicit = keep is not None

@@ -70,17 +70,21 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("--prompts", default="", help="'|'-separated prompt texts (tokenised here)")
     ap.add_argument("--labels", default="")
     ap.add_argument("--synthetic", action="store_true", help="formula weights instead of open_clip_pytorch_model.bin")
+    ap.add_argument("--force_image_size", type=int, default=None,
+                    help="run the image tower at this size (a multiple of the patch size): the position table is resized on load")
     a = ap.parse_args(argv)
     model_cfg, pp = ovcfg.load_config_dir(a.use_model)
     if a.synthetic:
         model = create_model({k: v for k, v in model_cfg.items() if k in ("embed_dim", "vision_cfg", "text_cfg")},
                              device="cuda:0", state_dict=synth.make_state_dict(model_cfg))
+        if a.force_image_size is not None:
+            model.set_input_size(a.force_image_size)
     else:
-        from .checkpoint import from_pretrained
-        model, pp = from_pretrained(a.use_model, device="cuda:0")     # .bin (weights_only) or safetensors, wrappers unwrapped
+        from .checkpoint import from_pretrained        # .bin (weights_only) or safetensors, wrappers unwrapped
+        model, pp = from_pretrained(a.use_model, device="cuda:0", force_image_size=a.force_image_size)
     model.use_graphs(8)          # one image per encode call: ~170 launches each, replayed as one hipGraph
     print(describe(model))
-    names, imgs = load_images(a.image_dir, model_cfg["vision_cfg"]["image_size"], pp["mean"], pp["std"])
+    names, imgs = load_images(a.image_dir, model.visual.image_size[0], pp["mean"], pp["std"])
     if bool(a.tokens) == bool(a.prompts):
         ap.error("give exactly one of --tokens / --prompts")
     if a.prompts:

@@ -15,23 +15,13 @@ from __future__ import annotations
 
 import argparse
 import os
-import random
 import re
 from typing import List, Optional, Sequence
 
 import numpy as np
 import torch
 
-from .visualize import FeatureVisualizer, new_init
-
-SEED = 6247423
-
-
-def fix_random_seed(seed: int = SEED) -> None:
-    torch.manual_seed(seed)
-    torch.cuda.manual_seed(seed)
-    random.seed(seed)
-    np.random.seed(seed)
+from .visualize import SEED, FeatureVisualizer, fix_random_seed, new_init  # noqa: F401  (SEED, fix_random_seed: this module's names too)
 
 
 def parse_range(text: str) -> List[int]:

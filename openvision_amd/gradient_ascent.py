@@ -38,8 +38,9 @@ from typing import List, Optional, Sequence
 import torch
 import torch.nn.functional as F
 
-from . import _lib, config as ovcfg
+from . import _lib, config as ovcfg, training
 from ._lib import check, ptr, stream_ptr
+from .visualize import _LoopState, fix_random_seed
 
 __all__ = ["GradientAscent", "draw_affine", "inverse_matrices", "affine_theta", "checkin", "mean_loss", "load_image", "main"]
 
@@ -149,10 +150,6 @@ def checkin(ids_history: torch.Tensor, history: torch.Tensor, tokenizer, name: s
 
 
 # ---- the loop ----------------------------------------------------------------------------------------------------------------------------
-class _LoopState:
-    pass
-
-
 class GradientAscent:
     """The script's ``generate_target_text_embeddings`` body for one image.  ``begin(image)`` draws every affine parameter of the run
     on the host (``draw_affine``: torch's CPU generator, in double; kornia's own draw order cannot be pinned, it is not a dependency)
@@ -251,7 +248,6 @@ class GradientAscent:
     # -- one iteration -------------------------------------------------------------------------------------
     def step(self, i: int) -> None:
         """Iteration i (0 .. steps - 1) of the run ``begin`` prepared: launches only."""
-        from . import training
         lib, s, st, model = _lib.load(), self._s, stream_ptr(), self.model
         b, k, r, vocab, d, t, e = self.batch, self.k, s.r, s.vocab, s.d, s.t, s.e
         normu = self.normu
@@ -339,7 +335,6 @@ def image_paths(args) -> List[str]:
 def main(argv: Optional[Sequence[str]] = None) -> int:
     args = parse_arguments(argv)
     from .checkpoint import from_pretrained
-    from .feature_visualization import fix_random_seed
     from .tokenizer import WordPieceTokenizer, clean
     if args.deterministic:
         fix_random_seed()

@@ -56,6 +56,11 @@ def _dtype_flag(t: torch.Tensor) -> int:
     raise TypeError(f"unsupported dtype {t.dtype} (float32 or bfloat16)")
 
 
+def _gemm_bias(a, lda: int, w, ldw: int, bias, out, ldo: int, m: int, n: int, k: int, stream, what: str = "ov_gemm") -> None:
+    """out [m, n] = a [m, k] w [n, k]^T (+ bias fp32 [n], or None) on ov_gemm: pointers and row pitches of bf16 operands padded already."""
+    check(_lib.load().ov_gemm(a, lda, w, ldw, bias, out, ldo, m, n, k, EPI_BIAS, None, 0, 0, 0, 0, stream), what)
+
+
 def _kernel_input(t: torch.Tensor) -> torch.Tensor:
     """t as the kernels read it: contiguous, in float32 or bfloat16 (any other dtype is converted to float32)."""
     return t.contiguous() if t.dtype in (torch.float32, torch.bfloat16) else t.float().contiguous()
@@ -205,7 +210,7 @@ class Linear(nn.Module):
         return self._pk.get(ps, lambda: (_pack_matrix(self.weight, n_pad, k_pad),
                                          _pack_vec(self.bias, n_pad, self.weight.device)), extra=(n_pad, k_pad))
 
-    def forward(self, x: torch.Tensor, epilogue: int = EPI_BIAS) -> torch.Tensor:
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
         _require_cuda(x, "Linear")
         k = self.in_features
         w, b = self.packed()
@@ -215,8 +220,7 @@ class Linear(nn.Module):
             a = torch.nn.functional.pad(a, (0, k_pad - k))
         a = a.contiguous()
         out = torch.empty(a.shape[0], n_pad, dtype=torch.bfloat16, device=x.device)
-        check(_lib.load().ov_gemm(ptr(a), k_pad, ptr(w), k_pad, ptr(b), ptr(out), n_pad, a.shape[0], n_pad, k_pad,
-                                  epilogue, None, 0, 0, 0, 0, stream_ptr()), "ov_gemm")
+        _gemm_bias(ptr(a), k_pad, ptr(w), k_pad, ptr(b), ptr(out), n_pad, a.shape[0], n_pad, k_pad, stream_ptr())
         return out[:, : self.out_features].reshape(*x.shape[:-1], self.out_features).to(x.dtype)
 
     def extra_repr(self) -> str:
@@ -283,8 +287,8 @@ class PatchConv(nn.Module):
         check(lib.ov_im2col_patches(ptr(img), _dtype_flag(img), ptr(cols), bsz, s, p, self.kpad, stream_ptr()), "ov_im2col")
         w = self.packed()
         out = torch.empty(bsz * g * g, self.out_channels, dtype=torch.bfloat16, device=image.device)
-        check(lib.ov_gemm(ptr(cols), self.kpad, ptr(w), self.kpad, None, ptr(out), self.out_channels, bsz * g * g,
-                          self.out_channels, self.kpad, EPI_BIAS, None, 0, 0, 0, 0, stream_ptr()), "ov_gemm(conv1)")
+        _gemm_bias(ptr(cols), self.kpad, ptr(w), self.kpad, None, ptr(out), self.out_channels, bsz * g * g, self.out_channels, self.kpad,
+                   stream_ptr(), "ov_gemm(conv1)")
         return out.view(bsz, g, g, self.out_channels).permute(0, 3, 1, 2).to(image.dtype)
 
 

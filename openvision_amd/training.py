@@ -31,7 +31,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from ._lib import check, ptr, stream_ptr
-from .model import _kernel_input, _pack_matrix, _pack_vec, _round_up
+from .model import _dtype_flag, _gemm_bias, _kernel_input, _pack_matrix, _pack_vec, _round_up
 
 _NAMES = ("ln1_w", "ln1_b", "qkv_w", "qkv_b", "out_w", "out_b", "ln2_w", "ln2_b", "fc_w", "fc_b", "proj_w", "proj_b")
 
@@ -250,8 +250,7 @@ class _LinearFn(torch.autograd.Function):
         wb = _pack_matrix(w, npad, kp)
         bb = _pack_vec(bias, npad, x.device) if bias is not None else None
         out = torch.empty(m, npad, dtype=torch.bfloat16, device=x.device)
-        check(lib.ov_gemm(ptr(xb), kp, ptr(wb), kp, ptr(bb), ptr(out), npad, m, npad, kp, _lib.EPI_BIAS, None, 0, 0, 0, 0, stream_ptr()),
-              "ov_gemm")
+        _gemm_bias(ptr(xb), kp, ptr(wb), kp, ptr(bb), ptr(out), npad, m, npad, kp, stream_ptr())
         ctx.save_for_backward(xb, wb)
         ctx.dims = (m, n, k, kp, npad, bias is not None, x.dtype, w.dtype, bias.dtype if bias is not None else None)
         return out[:, :n].float()
@@ -308,15 +307,31 @@ class _LayerNormFn(torch.autograd.Function):
         return dx.view(shape).to(xd), dg.to(wd), db.to(bd), None
 
 
-class _PatchKeepFn(torch.autograd.Function):
-    """Patch dropout's front end (transformer.py:610-619 with PatchDropout): the conv1 operand rows of the kept patches only
-    (``ov_im2col_patches_keep``), the patch GEMM over those B K rows (``ov_gemm``, as ``_LinearFn``), and the fp32 token assembly
-    ``x[b, 0] = cls + pos[0]``, ``x[b, 1 + j] = y[b, j] + pos[1 + keep[b, j]]`` (``ov_patch_keep_assemble``) -> x [B, 1 + K, D].
+def _patch_tokens_forward(cols, w, cls, pos, keep, gg: int, y, x, st) -> None:
+    """The launch form of the image front end on the caller's buffers (no autograd, allocation or host read): y [B K, npad] = cols [B K,
+    kp] w^T in bf16 (``_gemm_bias``), then ``x[b, 0] = cls + pos[0]``, ``x[b, 1 + j] = y[b, j] + pos[1 + keep[b, j]]`` in fp32
+    (``ov_patch_keep_assemble``) -> x [B, 1 + K, D].  ``_PatchKeepFn`` and ``visualize.FeatureVisualizer.step`` run it."""
+    (bsz, seq, d), (npad, kp) = x.shape, w.shape
+    _gemm_bias(ptr(cols), kp, ptr(w), kp, None, ptr(y), npad, cols.shape[0], npad, kp, st)
+    check(_lib.load().ov_patch_keep_assemble(ptr(y), npad, ptr(cls), ptr(pos), ptr(keep), ptr(x), bsz, seq - 1, gg, d, st), "ov_patch_keep_assemble")
 
-    Backward: ``ov_patch_keep_assemble_backward`` gives dpos / dcls as fixed-order sums over the batch (bitwise reproducible; 0 for a
-    position no image kept) and the GEMM's output gradient; ``ov_linear_backward`` over the K kept rows gives the conv1 weight gradient
-    (from the forward's operand rows) and, when the image needs one, the rows that ``ov_col2im_patches_keep`` puts back into the image
-    (dropped patches 0).  keep / inv: int32 device tensors [B, K] / [B, G] (``ov_patch_keep_inverse``)."""
+
+def _patch_tokens_backward(dx, inv, gg: int, dy, w, ws, ws_bytes: int, st, dpos=None, dcls=None, cols=None, dcols=None, dw=None) -> None:
+    """Its backward, on the same terms: dx fp32 [B, 1 + K, D] -> ``ov_patch_keep_assemble_backward`` -> dy [B K, npad] bf16 and the
+    optional dpos / dcls (fixed-order sums over the batch; 0 for a position no image kept), then ``ov_linear_backward`` -> the optional
+    dcols [B K, kp] and dw [npad, kp] (dw from the forward's ``cols``).  Without dy the assembly's backward runs alone."""
+    lib, (bsz, seq, d), (npad, kp) = _lib.load(), dx.shape, w.shape
+    check(lib.ov_patch_keep_assemble_backward(ptr(dx), ptr(inv), bsz, seq - 1, gg, d, ptr(dpos), ptr(dcls), ptr(dy), npad, st),
+          "ov_patch_keep_assemble_backward")
+    if dy is not None:
+        check(lib.ov_linear_backward(ptr(dy), npad, ptr(cols), kp if cols is not None else 0, ptr(w), kp, dy.shape[0], npad, kp, ptr(dcols), kp,
+                                     ptr(dw), kp if dw is not None else 0, None, ptr(ws), ws_bytes, st), "ov_linear_backward")
+
+
+class _PatchKeepFn(torch.autograd.Function):
+    """Patch dropout's front end (transformer.py:610-619 with PatchDropout): the kept patches' conv1 operand rows (``ov_im2col_patches_keep``)
+    through ``_patch_tokens_forward`` -> x [B, 1 + K, D].  Backward: ``_patch_tokens_backward`` (its GEMM half only when the image or the
+    weight needs a gradient), then ``ov_col2im_patches_keep`` for the image (dropped patches 0).  keep / inv: int32 [B, K] / [B, G] on the device."""
 
     @staticmethod
     def forward(ctx, image, w, cls, pos, keep, inv, patch):
@@ -328,17 +343,13 @@ class _PatchKeepFn(torch.autograd.Function):
         k, kp, npad = 3 * patch * patch, _round_up(3 * patch * patch, 64), _round_up(d, 64)
         img = _kernel_input(image.detach())
         st = stream_ptr()
-        m = bsz * nk
-        cols = torch.empty(m, kp, dtype=torch.bfloat16, device=image.device)
-        check(lib.ov_im2col_patches_keep(ptr(img), _lib.OV_F32 if img.dtype == torch.float32 else _lib.OV_BF16, ptr(keep), ptr(cols), bsz,
-                                         s, patch, nk, kp, st), "ov_im2col_patches_keep")
+        cols = torch.empty(bsz * nk, kp, dtype=torch.bfloat16, device=image.device)
+        check(lib.ov_im2col_patches_keep(ptr(img), _dtype_flag(img), ptr(keep), ptr(cols), bsz, s, patch, nk, kp, st), "ov_im2col_patches_keep")
         wb = _pack_matrix(w, npad, kp)
-        y = torch.empty(m, npad, dtype=torch.bfloat16, device=image.device)
-        check(lib.ov_gemm(ptr(cols), kp, ptr(wb), kp, None, ptr(y), npad, m, npad, kp, _lib.EPI_BIAS, None, 0, 0, 0, 0, st), "ov_gemm")
+        y = torch.empty(bsz * nk, npad, dtype=torch.bfloat16, device=image.device)
         cls32, pos32 = cls.detach().float().contiguous(), pos.detach().float().contiguous()
         x = torch.empty(bsz, 1 + nk, d, dtype=torch.float32, device=image.device)
-        check(lib.ov_patch_keep_assemble(ptr(y), npad, ptr(cls32), ptr(pos32), ptr(keep), ptr(x), bsz, nk, g * g, d, st),
-              "ov_patch_keep_assemble")
+        _patch_tokens_forward(cols, wb, cls32, pos32, keep, g * g, y, x, st)
         ctx.save_for_backward(cols, wb, keep, inv)
         ctx.dims = (bsz, s, patch, g * g, nk, d, k, kp, npad, img.dtype, image.dtype, w.dtype, cls.dtype, pos.dtype)
         return x
@@ -355,27 +366,20 @@ class _PatchKeepFn(torch.autograd.Function):
         dx = dx.detach().float().contiguous()
         dpos = torch.empty(1 + gg, d, dtype=torch.float32, device=dev) if need_pos else None
         dcls = torch.empty(d, dtype=torch.float32, device=dev) if need_cls else None
-        dyb = None
+        nb, dyb, dcols, dwb, ws = 0, None, None, None, None
         if need_img or need_w:
             dyb = (torch.empty if npad == d else torch.zeros)(m, npad, dtype=torch.bfloat16, device=dev)
-        check(lib.ov_patch_keep_assemble_backward(ptr(dx), ptr(inv), bsz, nk, gg, d, ptr(dpos), ptr(dcls), ptr(dyb), npad, st),
-              "ov_patch_keep_assemble_backward")
-        dimg = dw = None
-        if dyb is not None:
             dcols = torch.empty(m, kp, dtype=torch.bfloat16, device=dev) if need_img else None
             dwb = torch.empty(npad, kp, dtype=torch.bfloat16, device=dev) if need_w else None
             nb = lib.ov_linear_backward_workspace_bytes(m, npad, kp)
             ws = torch.empty(nb + 256, dtype=torch.uint8, device=dev)
-            check(lib.ov_linear_backward(ptr(dyb), npad, ptr(cols), kp, ptr(wb), kp, m, npad, kp, ptr(dcols), kp, ptr(dwb), kp, None, ptr(ws),
-                                         nb, st), "ov_linear_backward")
-            if need_w:
-                dw = dwb[:d, :k].to(wd)
-            if need_img:
-                dimg = torch.empty(bsz, 3, s, s, dtype=img_dt, device=dev)
-                check(lib.ov_col2im_patches_keep(ptr(dcols), kp, ptr(inv), ptr(dimg), _lib.OV_F32 if img_dt == torch.float32 else _lib.OV_BF16,
-                                                 bsz, s, patch, nk, st), "ov_col2im_patches_keep")
-                dimg = dimg.to(xd)
-        return (dimg, dw, dcls.to(cd) if need_cls else None, dpos.to(pd) if need_pos else None, None, None, None)
+        _patch_tokens_backward(dx, inv, gg, dyb, wb, ws, nb, st, dpos, dcls, cols, dcols, dwb)
+        dimg = None
+        if need_img:
+            dimg = torch.empty(bsz, 3, s, s, dtype=img_dt, device=dev)
+            check(lib.ov_col2im_patches_keep(ptr(dcols), kp, ptr(inv), ptr(dimg), _dtype_flag(dimg), bsz, s, patch, nk, st), "ov_col2im_patches_keep")
+            dimg = dimg.to(xd)
+        return dimg, dwb[:d, :k].to(wd) if need_w else None, dcls.to(cd) if need_cls else None, dpos.to(pd) if need_pos else None, None, None, None
 
 
 def patch_keep_tables(model, keep: torch.Tensor, batch: int, device, validate: bool = True):
@@ -393,6 +397,18 @@ def patch_keep_tables(model, keep: torch.Tensor, batch: int, device, validate: b
     if validate and int(err.item()) != 0:
         raise IndexError(f"keep: a patch index is repeated within an image or lies outside [0, {gg})")
     return kd, inv
+
+
+def _patch_tokens_eager(image, p: int, w, cls, pos) -> torch.Tensor:
+    """The eager form of the image front end, every patch: conv1 (transformer.py:610-612, stride = kernel, no bias) as patch rows times W^T
+    (F.conv2d's sums as a plain GEMM for autograd: MIOpen's fp32 convolution costs tens of ms per step here), then [cls; y] + pos in fp32
+    (:615-617).  Dense training is NOT on the launch form above: its fixed-order dpos / dcls sums differ from torch's broadcast reduction
+    and the launch count changes -- new results and speed, for a change of its own that re-records the pinned digests."""
+    bsz, _, hh, ww = image.shape
+    gh, gw = hh // p, ww // p
+    patches = image.reshape(bsz, 3, gh, p, gw, p).permute(0, 2, 4, 1, 3, 5).reshape(bsz * gh * gw, 3 * p * p)
+    x = _LinearFn.apply(patches, w.reshape(w.shape[0], -1), None).view(bsz, gh * gw, -1)
+    return torch.cat([cls.float().expand(bsz, 1, -1), x], dim=1) + pos.float()
 
 
 CHUNK_LAYERS = [max(0, int(os.environ.get("OVHIP_TRAIN_CHUNK_LAYERS", "0") or 0))]   # > 0: towers run as consecutive autograd nodes of that many blocks
@@ -459,12 +475,7 @@ def encode_image(model, image: torch.Tensor, normalize: bool = True, keep: torch
         kd, inv = patch_keep_tables(model, keep, bsz, image.device, validate=explicit)
         x = _PatchKeepFn.apply(image, w.reshape(w.shape[0], -1), v.class_embedding, v.positional_embedding, kd, inv, p)
     else:
-        # conv1 (:610-612, stride = kernel, no bias) as patch rows times W^T: the same sums as F.conv2d, and a plain GEMM for autograd
-        # (MIOpen's fp32 convolution path costs tens of ms per step at this shape)
-        patches = image.reshape(bsz, 3, gh, p, gw, p).permute(0, 2, 4, 1, 3, 5).reshape(bsz * gh * gw, 3 * p * p)
-        x = _LinearFn.apply(patches, w.reshape(w.shape[0], -1), None).view(bsz, gh * gw, -1)
-        cls = v.class_embedding.float().expand(x.shape[0], 1, -1)
-        x = torch.cat([cls, x], dim=1) + v.positional_embedding.float()                            # :615-617
+        x = _patch_tokens_eager(image, p, w, v.class_embedding, v.positional_embedding)
     if not isinstance(v.ln_pre, torch.nn.Identity):                # :620, after the patch dropout: on the kept tokens only
         x = _LayerNormFn.apply(x, v.ln_pre.weight, v.ln_pre.bias, v.ln_pre.eps)
     x = tower_forward(v.transformer, x)

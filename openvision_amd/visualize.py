@@ -18,10 +18,10 @@ model's parameters are constants: the backward computes input gradients only and
 the augmentations, losses and optimiser of :203-221) as HIP launches: per step
 
     ov_viz_augment                 RepeatBatch -> ColorJitter -> GaussianNoise -> Tile(1) -> Jitter, written as conv1 operand rows
-    ov_gemm, ov_patch_keep_assemble, ov_convert        the patch projection, cls + pos, the bf16 tokens (mlp_feature's arithmetic)
+    training._patch_tokens_forward, ov_convert         ov_gemm, ov_patch_keep_assemble (mlp_feature's arithmetic); the bf16 tokens
     _feature_forward / _feature_backward               the objective's own launches, as under ``mlp_feature``
     ov_viz_tv                      TotalVariation's plane norms
-    ov_convert, ov_patch_keep_assemble_backward, ov_linear_backward       the patch rows' gradient, dcols only
+    ov_convert, training._patch_tokens_backward        ov_patch_keep_assemble_backward, ov_linear_backward: the patch rows' dcols only
     ov_viz_augment_backward        d loss / d img and the step's (loss, feature term, tv term) row of ``history``
     ov_adamax_clip_step            torch.optim.Adamax + CosineAnnealingLR + Clip
 
@@ -34,14 +34,15 @@ import ctypes as C
 import math
 import random
 
+import numpy as np
 import torch
 
 from . import _lib
 from ._lib import check, ptr, stream_ptr
 from .model import _pack_matrix, _round_up
-from .training import _LinearFn, _pool
+from .training import _patch_tokens_backward, _patch_tokens_eager, _patch_tokens_forward, _pool
 
-__all__ = ["mlp_feature", "MLPFeatureLoss", "FeatureVisualizer", "draw_tables", "new_init"]
+__all__ = ["mlp_feature", "MLPFeatureLoss", "FeatureVisualizer", "draw_tables", "new_init", "fix_random_seed"]
 
 
 def _a256(n: int) -> int:
@@ -49,8 +50,8 @@ def _a256(n: int) -> int:
 
 
 class _FeatureState:
-    """What _feature_forward keeps for _feature_backward: the forward's handle, weights and pooled buffers."""
-    __slots__ = ("pool", "tower", "tap_weights", "cfg1", "meta", "xb", "tap", "saved", "gens")
+    """What _feature_forward keeps for _feature_backward: the forward's handle, weights, pooled buffers and the tap buffer's sections."""
+    __slots__ = ("pool", "tower", "tap_weights", "cfg1", "meta", "xb", "tap", "sections", "saved", "gens")
 
 
 def _feature_forward(visual, layer, feature, xb, keep_state):
@@ -81,8 +82,7 @@ def _feature_forward(visual, layer, feature, xb, keep_state):
         offs.append(total)
         total += _a256(n)
     tap = pool.take(total, xb.device, "featviz")
-    base = tap.data_ptr()
-    qkv, attn_out, x1, lse, pre = [C.c_void_p(base + o) for o in offs]
+    sections = qkv, attn_out, x1, lse, pre = [C.c_void_p(tap.data_ptr() + o) for o in offs]
     cfg1 = _lib.TowerCfg(d, 1, heads, mlp, mlp_pad, tanh, float(b0.ln_1.eps))
     wt, keep = blocks[layer].packed_block(fold_ln=False)          # the tap block's own LayerNorms and weights, ov_block_weights order
     check(lib.ov_block_attn_forward_saving(C.byref(cfg1), C.byref(wt), ptr(xb), qkv, attn_out, x1, lse, bsz, seq, stream_ptr()),
@@ -98,8 +98,8 @@ def _feature_forward(visual, layer, feature, xb, keep_state):
         return mean, None
     st = _FeatureState()
     st.pool, st.tower, st.tap_weights, st.cfg1 = pool, tower, (wt, keep), cfg1       # the backward runs the forward's handle and weights
-    st.meta = (layer, feature, bsz, seq, d, mlp, tanh, eps, offs)
-    st.xb, st.tap, st.saved = xb, tap, saved
+    st.meta = (layer, feature, bsz, seq, d, mlp, tanh, eps)
+    st.xb, st.tap, st.sections, st.saved = xb, tap, sections, saved
     st.gens = (tap._ovhip_gen, saved._ovhip_gen if saved is not None else None)
     return mean, st
 
@@ -107,14 +107,13 @@ def _feature_forward(visual, layer, feature, xb, keep_state):
 def _feature_backward(st, dm):
     """d sum_b dm[b] m[b] / d x as bf16 [B * L, D] (dm: device fp32 [B], contiguous); hands the forward's buffers back."""
     lib = _lib.load()
-    layer, feature, bsz, seq, d, mlp, tanh, eps, offs = st.meta
+    layer, feature, bsz, seq, d, mlp, tanh, eps = st.meta
     tap, saved, pool = st.tap, st.saved, st.pool
     if tap._ovhip_gen != st.gens[0] or (saved is not None and saved._ovhip_gen != st.gens[1]):
         raise _lib.OvhipError("feature objective: the saved activations of this graph were recycled by a later forward; a second "
                               "backward over the same graph must come before the next forward")
     m = bsz * seq
-    base = tap.data_ptr()
-    qkv, attn_out, x1, lse, pre = [C.c_void_p(base + o) for o in offs]
+    qkv, attn_out, x1, lse, pre = st.sections
     wt, keep = st.tap_weights
     handle = st.tower.handle if st.tower is not None else None
     attn_bytes = lib.ov_block_attn_backward_input_workspace_bytes(C.byref(st.cfg1), bsz, seq)
@@ -180,15 +179,9 @@ def mlp_feature(model, image: torch.Tensor, layer: int, feature: int) -> torch.T
     to ``image`` ([B, 3, H, W], fp32 or bf16, on the device).  ``model``: a CLIP model or its ``visual`` tower."""
     visual = getattr(model, "visual", model)
     _check_args(visual, image, layer, feature)
-    p = visual.patch_size[0]
-    w = visual.conv1.weight.detach()
-    bsz, _, hh, ww = image.shape
-    gh, gw = hh // p, ww // p
-    # conv1 (transformer.py:610-612) as patch rows times W^T, the weight a constant; cls + pos (:615-617); ln_pre = Identity
-    patches = image.reshape(bsz, 3, gh, p, gw, p).permute(0, 2, 4, 1, 3, 5).reshape(bsz * gh * gw, 3 * p * p)
-    x = _LinearFn.apply(patches, w.reshape(w.shape[0], -1), None).view(bsz, gh * gw, -1)
-    cls = visual.class_embedding.detach().float().expand(bsz, 1, -1)
-    x = torch.cat([cls, x], dim=1) + visual.positional_embedding.detach().float()
+    # training's eager front end with the parameters as constants; ln_pre = Identity
+    x = _patch_tokens_eager(image, visual.patch_size[0], visual.conv1.weight.detach(), visual.class_embedding.detach(),
+                            visual.positional_embedding.detach())
     return _FeatureFn.apply(visual, int(layer), int(feature), x)
 
 
@@ -219,6 +212,16 @@ class MLPFeatureLoss:
 
 
 # ---- the script's loop on HIP ----------------------------------------------------------------------------------------------------------
+SEED = 6247423
+
+
+def fix_random_seed(seed: int = SEED) -> None:
+    torch.manual_seed(seed)
+    torch.cuda.manual_seed(seed)
+    random.seed(seed)
+    np.random.seed(seed)
+
+
 def new_init(size: int, batch: int = 1, device="cuda:0") -> torch.Tensor:
     """The script's starting image (cliptoolsoptimized.py:136-150 with its defaults): ``torch.rand(batch, 3, size, size)`` from torch's
     CPU default generator, moved to the device."""
@@ -266,7 +269,7 @@ def step_sizes(steps: int, lr: float, beta1: float):
 
 
 class _LoopState:
-    pass
+    """A run's buffers and constants, as ``begin`` of either loop (this one, ``gradient_ascent.GradientAscent``) names them."""
 
 
 class FeatureVisualizer:
@@ -336,7 +339,7 @@ class FeatureVisualizer:
         s.cols, s.dcols = new(rows, s.kp, dtype=torch.bfloat16), new(rows, s.kp, dtype=torch.bfloat16)
         s.y, s.dy = new(rows, s.npad, dtype=torch.bfloat16), new(rows, s.npad, dtype=torch.bfloat16)
         s.aug, s.norms = new(batch, 3, size, size), new(4, 3 * batch)
-        s.x32, s.dxf = new(batch, s.seq, d), new(batch * s.seq, d)
+        s.x32, s.dxf = new(batch, s.seq, d), new(batch, s.seq, d)
         s.xb = new(batch, s.seq, d, dtype=torch.bfloat16)
         s.dimg, s.ea, s.ei = new(n, 3, size, size), new(n, 3, size, size), new(n, 3, size, size)
         s.ws_bytes = lib.ov_linear_backward_workspace_bytes(rows, s.npad, s.kp)
@@ -347,25 +350,20 @@ class FeatureVisualizer:
     def step(self, i: int) -> None:
         """Iteration i (0 .. steps) of the run ``begin`` prepared: launches only."""
         lib, s, st = _lib.load(), self._s, stream_ptr()
-        n, r, size, p, grid, batch, d, kp, npad = s.n, self.repeat, s.size, s.p, s.grid, s.batch, s.d, s.kp, s.npad
-        rows, tokens = batch * grid, batch * s.seq
+        n, r, size, p, grid, batch, d, kp = s.n, self.repeat, s.size, s.p, s.grid, s.batch, s.d, s.kp
+        tokens = batch * s.seq
         off1, off2 = s.offsets[i]
         table = C.c_void_p(s.table.data_ptr() + i * 9 * batch * 4)
         check(lib.ov_viz_augment(ptr(s.img), table, n, r, size, p, kp, off1, off2, ptr(s.cols), ptr(s.aug), st), "ov_viz_augment")
         # mlp_feature's front end on the same operand rows: y = cols W^T (bf16), x = [cls; y] + pos in fp32, then the bf16 tokens
-        check(lib.ov_gemm(ptr(s.cols), kp, ptr(s.w), kp, None, ptr(s.y), npad, rows, npad, kp, _lib.EPI_BIAS, None, 0, 0, 0, 0, st), "ov_gemm")
-        check(lib.ov_patch_keep_assemble(ptr(s.y), npad, ptr(s.cls), ptr(s.pos), ptr(s.keep), ptr(s.x32), batch, grid, grid, d, st),
-              "ov_patch_keep_assemble")
+        _patch_tokens_forward(s.cols, s.w, s.cls, s.pos, s.keep, grid, s.y, s.x32, st)
         check(lib.ov_convert(ptr(s.x32), _lib.OV_F32, d, ptr(s.xb), _lib.OV_BF16, d, tokens, d, st), "ov_convert")
         m, state = _feature_forward(self.visual, self.layer, self.feature, s.xb, True)
         check(lib.ov_viz_tv(ptr(s.aug), batch, size, size, ptr(s.norms), None, st), "ov_viz_tv")
         dx = _feature_backward(state, s.dm)
         # back through the bf16 tokens, the fp32 assembly (the patch rows only) and the projection: dcols, nothing for the weight
         check(lib.ov_convert(ptr(dx), _lib.OV_BF16, d, ptr(s.dxf), _lib.OV_F32, d, tokens, d, st), "ov_convert")
-        check(lib.ov_patch_keep_assemble_backward(ptr(s.dxf), ptr(s.keep), batch, grid, grid, d, None, None, ptr(s.dy), npad, st),
-              "ov_patch_keep_assemble_backward")
-        check(lib.ov_linear_backward(ptr(s.dy), npad, None, 0, ptr(s.w), kp, rows, npad, kp, ptr(s.dcols), kp, None, 0, None, ptr(s.ws),
-                                     s.ws_bytes, st), "ov_linear_backward")
+        _patch_tokens_backward(s.dxf, s.keep, grid, s.dy, s.w, s.ws, s.ws_bytes, st, dcols=s.dcols)
         row = C.c_void_p(self.history.data_ptr() + i * 12)
         check(lib.ov_viz_augment_backward(ptr(s.dcols), kp, ptr(s.aug), ptr(s.norms), table, ptr(m), n, r, size, p, off1, off2, size,
                                           self.c_feat, self.c_tv, ptr(s.dimg), row, st), "ov_viz_augment_backward")

@@ -12,13 +12,15 @@ plan depends on the CU count only.
 The cases are the smallest that reach each branch of the nodes: one node per tower, recomputation, a locked image tower (nothing kept;
 and, unlocked further, a partial backward that stops above frozen blocks), several spans per tower, an explicit keep table, frozen
 weights under an input gradient, the caption decoder under its prefix mask, the feature objective with and without a lower tower, and
-a bare tower at head_dim 80 with a padded MLP.
+a bare tower at head_dim 80 with a padded MLP.  The two loops built on these paths (visualize.FeatureVisualizer,
+gradient_ascent.GradientAscent) run a few seeded iterations each, and what they leave behind is hashed.
 
 A change that is meant to alter the arithmetic of any of these paths regenerates the fixture on purpose:
     python tests/test_gpu_train_pinned.py tests/golden/train_digests.json
 and says so; a host-side refactor must pass with the fixture untouched."""
 import json
 import os
+import random
 import sys
 
 import pytest
@@ -31,6 +33,7 @@ for _p in (ROOT, os.path.join(ROOT, "tests")):
 
 from openvision_amd import preset, synth, training, visualize  # noqa: E402
 from openvision_amd.caption import CaptionLoss, TextDecoder  # noqa: E402
+from openvision_amd.gradient_ascent import GradientAscent  # noqa: E402
 from openvision_amd.loss import ClipLoss  # noqa: E402
 from openvision_amd.model import Transformer, create_model  # noqa: E402
 from test_gpu_block_pinned import _draw, _sha, SEED  # noqa: E402
@@ -65,12 +68,14 @@ def _fill(module, tag):
     return module
 
 
+def _grads(modules):
+    """'grad.<module>.<parameter>' -> digest of .grad ('none' where nothing left a gradient)."""
+    return {f"grad.{tag}.{n}": "none" if p.grad is None else _sha(p.grad) for tag, mod in modules for n, p in mod.named_parameters()}
+
+
 def _digests(loss, modules, inputs=()):
     """loss + '<module>.<parameter>' -> digest of .grad ('none' where the step left no gradient) + '<input>.grad'."""
-    out = {"loss": _sha(loss.detach())}
-    for tag, mod in modules:
-        for n, p in mod.named_parameters():
-            out[f"grad.{tag}.{n}"] = "none" if p.grad is None else _sha(p.grad)
+    out = {"loss": _sha(loss.detach()), **_grads(modules)}
     for tag, t in inputs:
         out[f"grad.{tag}"] = _sha(t.grad)
     return out
@@ -138,6 +143,40 @@ def _feature(layer):
     return out
 
 
+def _seed():
+    """The loops draw on the host (torch's CPU generator, Python's) and, the ascent's Gumbel noise, on the device."""
+    torch.manual_seed(SEED)
+    random.seed(SEED)
+
+
+def _viz_loop():
+    """Three iterations at a batch of 6 = 3 repeats of 2 images: the packed table's step rows are not 16-byte aligned, the rows run
+    b = r N + n, and layer 2 runs a lower tower under the tap block."""
+    m = _tiny().eval()
+    _seed()
+    viz = visualize.FeatureVisualizer(m, layer=2, feature=5, steps=2, repeat=3, images=2)
+    viz.begin(visualize.new_init(160, 2))
+    for i in range(3):
+        viz.step(i)
+    return {"history": _sha(viz.history), "image": _sha(viz.image), "dcols": _sha(viz._s.dcols)}
+
+
+def _ascent():
+    m = _tiny()
+    image = synth.make_images(1, 160, seed=4)[0]
+    image = ((image - image.min()) / (image.max() - image.min())).to(DEV)
+    _seed()
+    loop = GradientAscent(m, batch_size=3, tokens=2, steps=2)
+    loop.begin(image)
+    try:
+        loop.step(0)
+        loop.step(1)
+    finally:
+        loop.end()
+    return {"history": _sha(loop.history), "ids_history": _sha(loop.ids_history), "normu": _sha(loop.normu),
+            "best_text_embedding": _sha(loop.best_text_embedding), **_grads((("clip", m),))}
+
+
 def _bare_tower():
     """head_dim 80 (the streaming attention backward over d padded to 96) and an MLP of 1076 columns padded to 1088."""
     tr = Transformer(320, 2, 4, (1076 + 0.5) / 320)
@@ -162,6 +201,8 @@ CASES = {
     "featviz/layer0": (_feature, dict(layer=0)),
     "featviz/layer2": (_feature, dict(layer=2)),
     "tower/hd80_l257_padmlp": (_bare_tower, {}),
+    "vizloop/three_steps_n2_r3": (_viz_loop, {}),
+    "ascent/two_steps_b3_k2": (_ascent, {}),
 }
 
 

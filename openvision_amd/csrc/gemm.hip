@@ -18,10 +18,14 @@
 //     kernel's other epilogues); the residual is added on the way out.  All forms perform the same arithmetic in the same order;
 //   * workgroup id -> tile map is XCD-aware: each XCD's L2 sees a contiguous run of tiles that walk n
 //     fastest, so the 32 tiles resident on an XCD share A row-panels and the whole of W.
-#include "common.h"
+// What the ping-pong kernels share -- the epilogue's element function, the XCD run split, the swizzle and fragment addresses, the phase
+// skeleton with its hazard rules, the persistent K-tile schedule and tile hand-over -- is stated once in gemm_tile.h.
+#include "gemm_tile.h"
 #include <stdlib.h>
 
 namespace {
+
+using namespace gemm;
 
 constexpr int BM = 256, BN = 256, BK = 64;
 constexpr int NTHREADS = 512;
@@ -51,10 +55,6 @@ struct GemmArgs {
     float* rowpart = nullptr;            // residual epilogue (persistent direct form, skinny kernel): {sum, sum of squares} of every
                                          // 32-column group of every OUTPUT row, [M][N / 32][2] fp32 (common.h: row statistics); NULL = off
 };
-
-template <int V> struct IntC { static constexpr int value = V; };
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 
 // ---- shared epilogue: acc[i][j][r] = C[m0 + wm*128 + i*16 + fr][n0 + wn*64 + j*16 + fq*4 + r] -------------------
 template <int EPI>
@@ -101,22 +101,8 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, f32x4_t (&acc)[
         }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            // same arithmetic (packed fp32) as epilogue_2pass: results must not depend on which kernel variant ran
-            f32x2_t v01 = f32x2_t{acc[i][j][0], acc[i][j][1]};
-            f32x2_t v23 = f32x2_t{acc[i][j][2], acc[i][j][3]};
-            if (fold) {
-                const f32x2_t nm = {-rmean, -rmean}, rs = {rrstd, rrstd};
-                v01 = __builtin_elementwise_fma(f32x2_t{sv[j][0], sv[j][1]}, nm, v01);
-                v23 = __builtin_elementwise_fma(f32x2_t{sv[j][2], sv[j][3]}, nm, v23);
-                v01 = __builtin_elementwise_fma(v01, rs, f32x2_t{bv[j][0], bv[j][1]});
-                v23 = __builtin_elementwise_fma(v23, rs, f32x2_t{bv[j][2], bv[j][3]});
-            } else {
-                v01 += f32x2_t{bv[j][0], bv[j][1]};
-                v23 += f32x2_t{bv[j][2], bv[j][3]};
-            }
-            if (EPI == OV_EPI_BIAS_GELU_ERF) gelu_erf_f2x2(v01, v23);
-            if (EPI == OV_EPI_BIAS_GELU_TANH) { v01 = gelu_tanh_f2(v01); v23 = gelu_tanh_f2(v23); }
-            u32x2_t p = {pack_bf16x2(v01[0], v01[1]), pack_bf16x2(v23[0], v23[1])};
+            u32x2_t p;
+            OV_GEMM_EPI_QUAD(EPI, false, acc[i][j], bv[j], fold, sv[j], rmean, rrstd, p, p);
             const int c = j * 2 + (fq >> 1);
             *(u32x2_t*)(ep + ml * 128 + ((c ^ (ml & 7)) << 4) + (fq & 1) * 8) = p;
         }
@@ -154,15 +140,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, f32x4_t (&acc)[
 //     both waves stalling on LDS at once.
 // LDS map (128 KiB): buffer b in {0,1} at b*64 KiB, then [A k0][W k0][A k1][W k1] x 16 KiB; a piece is 256 rows x 64 B,
 // 16-B chunk c of row r stored at chunk c ^ f((r >> 2) & 3), f = {0,2,3,1}: conflict-free for the 16x16x32 operand reads.
-// Hazards (interval = span between two consecutive barriers; wave group 1 lags group 0 by one interval):
-//   RAW  a piece issued in phase p of tile T is waited for (counted vmcnt) in phase 3 (p<2) or phase 1 of T+1 (p>=2),
-//        and first read >= one barrier after EVERY wave has passed that wait;
-//   WAR  a slot is re-staged >= 4 intervals after its last ds_read was issued (those reads are consumed by the
-//        MFMAs of the reader's next COMPUTE segment, i.e. before its next barrier).
-constexpr int PIECE_BYTES = 256 * 64;          // 16 KiB
-
-__device__ __forceinline__ int swz4(int row) { return (0x78 >> (((row >> 2) & 3) * 2)) & 3; }
-
+// The phase skeleton and its RAW / WAR hazard rules: gemm_tile.h.
 template <int EPI>
 __global__ __launch_bounds__(NTHREADS, 2) void gemm_bf16_pp(const GemmArgs g_in) {
     __shared__ __attribute__((aligned(16))) char smem[SMEM_BYTES];
@@ -180,12 +158,11 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_bf16_pp(const GemmArgs g_in)
     const int nwg = g.tiles_m * g.tiles_n;
     const int bid = blockIdx.x;
     const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    const int wgid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
+    const int wgid = OV_GEMM_XCD_START(q8, r8, xcd) + idx;
     const int tm = wgid / g.tiles_n, tn = wgid - tm * g.tiles_n;
     const int64_t m0 = (int64_t)tm * BM;
     const int n0 = tn * BN;
 
-    // staging: LDS chunk q = i*512 + tid of a piece holds row q>>2, logical chunk (q&3) ^ f(row)
     const int srow = tid >> 2;
     const int schunk = (tid & 3) ^ swz4(srow);
     const ov_bf16* asrc[2];
@@ -214,23 +191,16 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_bf16_pp(const GemmArgs g_in)
     };
 
     const int wm = wave >> 2, wn = wave & 3;
-    const int fr = lane & 15, fq = lane >> 4;
-    const int lsw = (fq ^ swz4(fr)) << 4;
-    const int a_lane = (wm * 128 + fr) * 64 + lsw;                 // + piece(A,kh) + i*1024
-    const int w_lane = PIECE_BYTES + (wn * 64 + fr) * 64 + lsw;    // + piece pair(kh) + j*1024
+    int a_lane, w_lane;                                            // + piece pair(kh) + i*1024 / j*1024
+    OV_GEMM_FRAG_LANES(a_lane, w_lane, lane, wm * 128, wn * 64);
 
     f32x4_t acc[8][4];
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    OV_GEMM_CLEAR_ACC(acc);
 
     const int nt = g.K / BK;
 #pragma unroll
     for (int j = 0; j < 4; ++j) stage_piece(0, j, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    if (wm == 1) __builtin_amdgcn_s_barrier();                     // stagger the lower wave group by one interval
+    prologue_sync(wm);
 
     bf16x8_t af[4], wf[4];
     for (int t = 0; t < nt; ++t) {
@@ -252,23 +222,11 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_bf16_pp(const GemmArgs g_in)
                 if (more) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
                 else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             }
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_sched_barrier(0);
-            // ---------------- COMPUTE segment ----------------
-            __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    acc[mh * 4 + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j], af[i], acc[mh * 4 + i][j], 0, 0, 0);
-            __builtin_amdgcn_s_setprio(0);
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_sched_barrier(0);
+            phase_fence();
+            compute_segment([&] { OV_GEMM_MMA16(acc, mh * 4, wf[j_], af[i_], false); });
         }
     }
-    if (wm == 0) __builtin_amdgcn_s_barrier();                     // re-align the two wave groups
+    OV_GEMM_REALIGN(wm);
     gemm_epilogue<EPI>(g, acc, smem, m0, n0, wave, lane);
 }
 
@@ -317,7 +275,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_bf16_pp_tn(const GemmArgs g_
     const int nwg = g.tiles_m * g.tiles_n;
     const int bid = blockIdx.x;
     const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    const int wgid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
+    const int wgid = OV_GEMM_XCD_START(q8, r8, xcd) + idx;
     const int tm = wgid / g.tiles_n, tn = wgid - tm * g.tiles_n;
     const int64_t m0 = (int64_t)tm * BM;                            // first column of P = first output row
     const int n0 = tn * BN;                                         // first column of Q = first output column
@@ -361,16 +319,11 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_bf16_pp_tn(const GemmArgs g_
     const unsigned w_lane = lbase + PIECE_BYTES + mrow * 512 + (((wn * 4) ^ key) << 5) + (fp >> 1) * 16 + (fp & 1) * 8;
 
     f32x4_t acc[8][4];
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    OV_GEMM_CLEAR_ACC(acc);
 
 #pragma unroll
     for (int j = 0; j < 4; ++j) stage_piece(0, j, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    if (wm == 1) __builtin_amdgcn_s_barrier();                     // stagger the lower wave group by one interval
+    prologue_sync(wm);
 
     u32x2_t wr[8], ar[8];                                          // 4 W-role / 4 A-role fragments, two transposed reads each
     const bool colsums = g.psum != nullptr && tn == 0;             // block-uniform
@@ -403,19 +356,12 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_bf16_pp_tn(const GemmArgs g_
                 if (more) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
                 else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             }
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_sched_barrier(0);
+            phase_fence();
             asm volatile("s_waitcnt lgkmcnt(0)"
                          : "+v"(wr[0]), "+v"(wr[1]), "+v"(wr[2]), "+v"(wr[3]), "+v"(wr[4]), "+v"(wr[5]), "+v"(wr[6]), "+v"(wr[7]),
                            "+v"(ar[0]), "+v"(ar[1]), "+v"(ar[2]), "+v"(ar[3]), "+v"(ar[4]), "+v"(ar[5]), "+v"(ar[6]), "+v"(ar[7]));
-            __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    acc[mh * 4 + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tn_join(wr[2 * j], wr[2 * j + 1]),
-                                                                                 tn_join(ar[2 * i], ar[2 * i + 1]), acc[mh * 4 + i][j], 0, 0, 0);
+            compute_segment([&] {
+            OV_GEMM_MMA16(acc, mh * 4, tn_join(wr[2 * j_], wr[2 * j_ + 1]), tn_join(ar[2 * i_], ar[2 * i_ + 1]), false);
             if (colsums) {      // D[r][c] = sum_k 1 * P[k, c]: every row of the 16 x 16 result holds the 16 column sums
                 switch (wn) {
                     case 0: accs[mh] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, tn_join(ar[0], ar[1]), accs[mh], 0, 0, 0); break;
@@ -424,13 +370,10 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_bf16_pp_tn(const GemmArgs g_
                     default: accs[mh] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, tn_join(ar[6], ar[7]), accs[mh], 0, 0, 0); break;
                 }
             }
-            __builtin_amdgcn_s_setprio(0);
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_sched_barrier(0);
+            });
         }
     }
-    if (wm == 0) __builtin_amdgcn_s_barrier();                     // re-align the two wave groups
+    OV_GEMM_REALIGN(wm);
     if (colsums && lane < 16) {                                    // row 0 of the result: lane c holds the sum of column c
 #pragma unroll
         for (int mh = 0; mh < 2; ++mh) {
@@ -477,15 +420,6 @@ constexpr int SMEM_PERSIST = IMG_OFF + 8 * 2048;     // 152 KiB of the CU's 160 
 // Measured in the model: QKV 9.59 -> 9.41 ms, c_fc 12.55 -> 12.24 ms per step (-2 %); all eight passes at priority 1 just swaps the
 // roles (no gain).
 constexpr int EPI_PRIO = 4;
-template <int N> __device__ __forceinline__ void wait_vmcnt() {          // literal counts only (the hand-counted waits of the epilogues)
-    static_assert(N == 8 || N == 14 || N == 22 || N == 24 || N == 26 || N == 28, "add the literal");
-    if (N == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else if (N == 14) asm volatile("s_waitcnt vmcnt(14)" ::: "memory");
-    else if (N == 22) asm volatile("s_waitcnt vmcnt(22)" ::: "memory");
-    else if (N == 24) asm volatile("s_waitcnt vmcnt(24)" ::: "memory");
-    else if (N == 26) asm volatile("s_waitcnt vmcnt(26)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(28)" ::: "memory");
-}
 
 // STATS (residual epilogue only): every pass also forms the row statistics' partial sums of its 16 rows x 64 columns (two 32-column
 // groups per wave: common.h) and leaves them in an LDS image of the tile; gemm_bf16_persist writes the image out behind the tile
@@ -611,29 +545,10 @@ __device__ __forceinline__ void epilogue_stream(const GemmArgs& g, f32x4_t (&acc
 #pragma unroll
             for (int k = 4; k < 8; ++k) load_resid(k);
         }
-        f32x2_t nm = {0.f, 0.f}, rs = {1.f, 1.f};
-        if (FOLD) {
-            nm = f32x2_t{-stq[i][0], -stq[i][0]};
-            rs = f32x2_t{stq[i][1], stq[i][1]};
-        }
         u32x2_t pk[4], pk2[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            f32x2_t v01 = f32x2_t{acc[i][j][0], acc[i][j][1]};
-            f32x2_t v23 = f32x2_t{acc[i][j][2], acc[i][j][3]};
-            if (FOLD) {      // rstd * (acc - mean * colsum) + cvec, as two explicit FMAs (identical in every kernel variant)
-                v01 = __builtin_elementwise_fma(f32x2_t{sv[j][0], sv[j][1]}, nm, v01);
-                v23 = __builtin_elementwise_fma(f32x2_t{sv[j][2], sv[j][3]}, nm, v23);
-                v01 = __builtin_elementwise_fma(v01, rs, f32x2_t{bv[j][0], bv[j][1]});
-                v23 = __builtin_elementwise_fma(v23, rs, f32x2_t{bv[j][2], bv[j][3]});
-            } else {
-                v01 += f32x2_t{bv[j][0], bv[j][1]};
-                v23 += f32x2_t{bv[j][2], bv[j][3]};
-            }
-            if (KEEP) pk2[j] = u32x2_t{pack_bf16x2(v01[0], v01[1]), pack_bf16x2(v23[0], v23[1])};
-            if (EPI == OV_EPI_BIAS_GELU_ERF) gelu_erf_f2x2(v01, v23);
-            if (EPI == OV_EPI_BIAS_GELU_TANH) { v01 = gelu_tanh_f2(v01); v23 = gelu_tanh_f2(v23); }
-            pk[j] = u32x2_t{pack_bf16x2(v01[0], v01[1]), pack_bf16x2(v23[0], v23[1])};
+            OV_GEMM_EPI_QUAD(EPI, KEEP, acc[i][j], bv[j], FOLD, sv[j], stq[i][0], stq[i][1], pk[j], pk2[j]);
         }
         if (KEEP) {          // the pre-activation rows, same lane -> chunk map as the output (never MAPPED, never residual)
             const unsigned m = (unsigned)m0 + rb + i * 16 + fr;
@@ -765,27 +680,10 @@ __device__ __forceinline__ void epilogue_stream_lds(const GemmArgs& g, f32x4_t (
             for (int k = 4; k < 8; ++k) load_resid(k);
         }
         if (i < 8) {
-            f32x2_t nm = {0.f, 0.f}, rs = {1.f, 1.f};
-            if (FOLD) {
-                nm = f32x2_t{-stq[i][0], -stq[i][0]};
-                rs = f32x2_t{stq[i][1], stq[i][1]};
-            }
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                f32x2_t v01 = f32x2_t{acc[i][j][0], acc[i][j][1]};
-                f32x2_t v23 = f32x2_t{acc[i][j][2], acc[i][j][3]};
-                if (FOLD) {      // rstd * (acc - mean * colsum) + cvec, as two explicit FMAs (identical in every kernel variant)
-                    v01 = __builtin_elementwise_fma(f32x2_t{sv[j][0], sv[j][1]}, nm, v01);
-                    v23 = __builtin_elementwise_fma(f32x2_t{sv[j][2], sv[j][3]}, nm, v23);
-                    v01 = __builtin_elementwise_fma(v01, rs, f32x2_t{bv[j][0], bv[j][1]});
-                    v23 = __builtin_elementwise_fma(v23, rs, f32x2_t{bv[j][2], bv[j][3]});
-                } else {
-                    v01 += f32x2_t{bv[j][0], bv[j][1]};
-                    v23 += f32x2_t{bv[j][2], bv[j][3]};
-                }
-                if (EPI == OV_EPI_BIAS_GELU_ERF) gelu_erf_f2x2(v01, v23);
-                if (EPI == OV_EPI_BIAS_GELU_TANH) { v01 = gelu_tanh_f2(v01); v23 = gelu_tanh_f2(v23); }
-                const u32x2_t pk = {pack_bf16x2(v01[0], v01[1]), pack_bf16x2(v23[0], v23[1])};
+                u32x2_t pk;
+                OV_GEMM_EPI_QUAD(EPI, false, acc[i][j], bv[j], FOLD, sv[j], stq[i][0], stq[i][1], pk, pk);
                 *(u32x2_t*)(wr + (((j * 2 + (fq >> 1)) ^ wsw) << 4)) = pk;
             }
         }
@@ -807,8 +705,6 @@ __device__ __forceinline__ void epilogue_stream_lds(const GemmArgs& g, f32x4_t (
     }
     if (wst != nullptr && lane == 0) wst[5] = __builtin_amdgcn_s_memtime();
 }
-
-struct TileSrc { const ov_bf16* a0; const ov_bf16* a1; const ov_bf16* w0; const ov_bf16* w1; };   // per-lane staging sources
 
 template <int EPI, bool FOLD, bool DIRECT, bool MAPPED, bool KEEP = false, bool STATS = false>
 __global__ __launch_bounds__(NTHREADS, 2) void gemm_bf16_persist(const GemmArgs g) {
@@ -838,9 +734,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_bf16_persist(const GemmArgs 
         xstart = (xcd * pq + (xcd < pr ? xcd : pr)) * g.tiles_n;
         xcnt = (pq + (xcd < pr ? 1 : 0)) * g.tiles_n;
     } else {
-        const int q8 = nwg >> 3, r8 = nwg & 7;
-        xstart = xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8;
-        xcnt = q8 + (xcd < r8 ? 1 : 0);
+        xstart = xcd_run(nwg, xcd).start;
+        xcnt = xcd_run(nwg, xcd).count;
     }
     const int nper = (G - xcd + 7) >> 3;
     int tcur = li;
@@ -868,8 +763,6 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_bf16_persist(const GemmArgs 
         s2 = grouped ? qs / rad1 : 0;
     }
     auto set_tile = [&](TileSrc& ts, int64_t& mm, int& nn) {      // sets up the tile the counter points at, then steps the counter
-        // the lane's staging row / chunk, rebuilt per tile from an opaque lane id: as loop invariants hipcc kept the 64-bit per-lane
-        // offsets (row * ld + chunk) live through the whole tile loop -- and spilled them in the variant with row statistics
         const int tid_f = wave * 64 + fresh_lane();
         const int srow = tid_f >> 2;
         const int schunk = (tid_f & 3) ^ swz4(srow);
@@ -885,6 +778,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_bf16_persist(const GemmArgs 
         d2 += s2;
         mm = (int64_t)tm * BM;
         nn = tn * BN;
+        // the lane's staging row / chunk, rebuilt per tile from an opaque lane id: as loop invariants hipcc kept the 64-bit per-lane
+        // offsets (row * ld + chunk) live through the whole tile loop -- and spilled them in the variant with row statistics
         int64_t ar0 = mm + srow, ar1 = mm + 128 + srow;
         ar0 = ar0 < g.M ? ar0 : g.M - 1;
         ar1 = ar1 < g.M ? ar1 : g.M - 1;
@@ -952,10 +847,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_bf16_persist(const GemmArgs 
     auto set_lanes = [&](int nn) {
         htile = g.N - nn <= 128;
         const int lf = fresh_lane();
-        const int fr = lf & 15, fq = lf >> 4;
-        const int lsw = (fq ^ swz4(fr)) << 4;
-        a_lane = ((htile ? (wave >> 1) * 64 : wm * 128) + fr) * 64 + lsw;
-        w_lane = PIECE_BYTES + ((htile ? (wave & 1) : (wave & 3)) * 64 + fr) * 64 + lsw;
+        OV_GEMM_FRAG_LANES(a_lane, w_lane, lf, (htile ? (wave >> 1) * 64 : wm * 128), (htile ? (wave & 1) : (wave & 3)) * 64);
     };
     const int nt = g.K / BK;                                       // >= 3 (launcher)
     set_tile(cur, m0, n0);
@@ -967,9 +859,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_bf16_persist(const GemmArgs 
     for (int j = 0; j < 4; ++j) stage_piece(cur, STAGE_BYTES, j);
     advance(cur);                                                  // invariant at tile start: `cur` points at K-tile 2
     stage_params(0, m0, n0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    if (wm == 1) __builtin_amdgcn_s_barrier();                     // stagger the lower wave group by one interval
+    prologue_sync(wm);
 
     int cb = 0, pslot = 0;   // LDS buffer (byte offset) of the K-tile being consumed; parameter block of the current tile
     bool strict = true;      // K-tile 1 wait of this tile must not count on 16 younger stores (first tile / after an edge tile)
@@ -984,12 +874,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_bf16_persist(const GemmArgs 
     };
     f32x4_t acc[8][4];
     bf16x8_t af[4], wf[4];
-    // One K-tile = four phases (k-half x m-half), each a LOAD segment (LDS fragment reads, one piece of the K-tile after
-    // next by LDS-DMA) and a COMPUTE segment (16 MFMAs) between barriers.  KIND selects what is staged and waited for, at
-    // compile time, so the steady-state body carries no branch:
-    //   0: K-tile 0 of a tile -- K-tile 1 is already in flight (previous epilogue / prologue), nothing is staged; its
-    //      wait leaves the previous epilogue's 16 stores outstanding;   1: K-tile 1 -- stages K-tile 2, first wait at p 3;
-    //   2: steady state;   3: last K-tile -- stages K-tile 0 of the next tile, if any.
+    // One K-tile = four phases (k-half x m-half) (0,0) (0,1) (1,0) (1,1); KIND 0-3 and the schedule they select: gemm_tile.h.
     auto ktile = [&](auto kind) {
         constexpr int KIND = decltype(kind)::value;
         const char* s = smem + cb;
@@ -1006,43 +891,13 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_bf16_persist(const GemmArgs 
 #pragma unroll
                 for (int i = 0; i < 4; ++i) af[i] = *(const bf16x8_t*)(sp + a_lane + (mh * 4 + i) * 1024);
             }
-            if (KIND == 1 || KIND == 2) stage_piece(cur, nb, p);
-            if (KIND == 3) { if (has_next) stage_piece(nxt, nb, p); }
-            if (p & 1) {
-                if (KIND == 0) {
-                    if (p == 3) {
-                        if (strict) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                        else asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-                    }
-                } else if (KIND == 1) {
-                    if (p == 3) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-                } else if (KIND == 2) {
-                    asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-                } else {
-                    if (has_next) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-                    else if (p == 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            OV_GEMM_KTILE_STAGE_WAIT(KtileBf16, KIND, p, strict, has_next, cur, nxt, nb, stage_piece);
+            phase_fence();
+            compute_segment([&] {
+                if (mh == 0 || !htile) {
+                    OV_GEMM_MMA16(acc, mh * 4, wf[j_], af[i_], KIND == 0 && kh == 0);
                 }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_setprio(1);
-            if (mh == 0 || !htile) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        // a tile's first products start from a literal zero C operand: no 128 v_mov per tile to clear the accumulators
-                        if (KIND == 0 && kh == 0)
-                            acc[mh * 4 + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j], af[i], f32x4_t{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-                        else
-                            acc[mh * 4 + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j], af[i], acc[mh * 4 + i][j], 0, 0, 0);
-                    }
-            }
-            __builtin_amdgcn_s_setprio(0);
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_sched_barrier(0);
+            });
         }
     };
     for (;;) {
@@ -1073,17 +928,9 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_bf16_persist(const GemmArgs 
         unsigned long long* wst = (OVHIP_STAMPS && g.wstamps != nullptr && titer < g.stamp_slots)
                                       ? g.wstamps + (((size_t)bid * g.stamp_slots + titer) * 8 + wave) * 8 : nullptr;
         if (wst != nullptr && lane == 0) wst[0] = __builtin_amdgcn_s_memtime();
-        if (wm == 0) __builtin_amdgcn_s_barrier();                 // re-align: every wave is past its last COMPUTE segment
+        OV_GEMM_REALIGN(wm);
         stamp(2);
-        if (has_next) {
-            // the buffer of the last K-tile is free: K-tile 1 of the next tile and its parameters go out ahead of the stores
-            advance(nxt);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) stage_piece(nxt, cb, j);
-            advance(nxt);
-            asm volatile("s_waitcnt vmcnt(8)" ::: "memory");       // K-tile 0 of the next tile (issued a K-tile ago) has landed
-            stage_params(pslot ^ 1, nm0, nn0);
-        }
+        if (has_next) OV_GEMM_HANDOVER_STAGE(nxt, cb, advance, stage_piece, stage_params(pslot ^ 1, nm0, nn0));
         __builtin_amdgcn_sched_barrier(0);
         const bool edge = (m0 + BM > g.M) || (n0 + BN > g.N);      // an edge tile issues fewer than 16 stores per wave
         if (wst != nullptr && lane == 0) wst[1] = __builtin_amdgcn_s_memtime();
@@ -1127,16 +974,11 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_bf16_persist(const GemmArgs 
             if (STATS) { __builtin_amdgcn_s_barrier(); flush_stats(); }
             break;
         }
-        strict = edge;
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();                               // next K-tile 0 visible to all
+        handover_barrier(edge, strict);
         if (STATS) flush_stats();
         if (wst != nullptr && lane == 0) wst[6] = __builtin_amdgcn_s_memtime();
-        if (wm == 1) __builtin_amdgcn_s_barrier();                  // re-stagger
-        cb ^= STAGE_BYTES;
-        pslot ^= 1;
-        cur = nxt;
-        m0 = nm0; n0 = nn0;
+        OV_GEMM_STAGGER(wm);
+        OV_GEMM_HANDOVER_SWAP(cb, STAGE_BYTES, pslot, cur, nxt, m0, nm0, n0, nn0);
         set_lanes(n0);
         tcur = tnext;
     }
@@ -1226,7 +1068,7 @@ __global__ __launch_bounds__(256) void gemm_bf16_skinny(const GemmArgs g) {
                 }
         }
     }
-    // ---- epilogue: acc[i][j][e] = C[m0 + wm*32 + i*16 + fr][n0 + wn*32 + j*16 + fq*4 + e]; the arithmetic of gemm_epilogue, per element
+    // ---- epilogue: acc[i][j][e] = C[m0 + wm*32 + i*16 + fr][n0 + wn*32 + j*16 + fq*4 + e]; the element function of every bf16 epilogue
     const bool fold = (EPI < OV_EPI_BIAS_RESIDUAL) && g.colsum != nullptr;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -1248,6 +1090,7 @@ __global__ __launch_bounds__(256) void gemm_bf16_skinny(const GemmArgs g) {
                 const float4 b4 = *(const float4*)(g.bias + nc);
                 b01 = f32x2_t{b4.x, b4.y}; b23 = f32x2_t{b4.z, b4.w};
             }
+            // (its own statement of OV_GEMM_EPI_QUAD, gemm_tile.h: with the macro in place this kernel's v_pk_add_f32 / bias loads changed order)
             f32x2_t v01 = f32x2_t{acc[i][j][0], acc[i][j][1]};
             f32x2_t v23 = f32x2_t{acc[i][j][2], acc[i][j][3]};
             if (fold) {
@@ -1261,9 +1104,8 @@ __global__ __launch_bounds__(256) void gemm_bf16_skinny(const GemmArgs g) {
                 v01 += b01;
                 v23 += b23;
             }
-            if (EPI == OV_EPI_BIAS_GELU_ERF) gelu_erf_f2x2(v01, v23);
-            if (EPI == OV_EPI_BIAS_GELU_TANH) { v01 = gelu_tanh_f2(v01); v23 = gelu_tanh_f2(v23); }
-            u32x2_t pk = {pack_bf16x2(v01[0], v01[1]), pack_bf16x2(v23[0], v23[1])};
+            OV_GEMM_ACTIVATE(EPI, v01, v23);
+            u32x2_t pk = OV_GEMM_PACK_QUAD(v01, v23);
             if (EPI >= OV_EPI_BIAS_RESIDUAL) {
                 const int64_t rrow = g.resid_mod ? (mc % g.resid_mod) + g.resid_off : mc;
                 const u32x2_t rv = *(const u32x2_t*)(g.R + rrow * g.ldr + nc);

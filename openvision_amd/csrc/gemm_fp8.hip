@@ -18,7 +18,7 @@
 //   * LDS rows are 128 bytes (8 chunks): chunk ^= row & 7, on the DMA source side and on the ds_read side (conflict-free).
 //   * per-row (activation) and per-column (weight) dequantisation scales ride in the parameter block and are applied in fp32
 //     in the epilogue: v = (acc * rowscale[m]) * colscale[n] + bias[n].
-#include "common.h"
+#include "gemm_tile.h"
 #include <stdlib.h>
 
 #ifndef OVHIP_ST_FP8OUT
@@ -26,6 +26,8 @@
 #endif
 
 namespace {
+
+using namespace gemm;
 
 constexpr int BM = 256, BN = 256, BKB = 128;       // K-tile: 128 bytes of K per row
 constexpr int NTHREADS = 512;
@@ -35,8 +37,6 @@ constexpr int IMG_OFF = 2 * STAGE;                 // 8 wave-local 2-KiB transpo
 constexpr int PRM_OFF = IMG_OFF + 8 * 2048;        // two 4-KiB parameter blocks: bias[256] | colscale[256] | rowscale[256] (f32)
 constexpr int SMEM_TOTAL = PRM_OFF + 2 * 4096;
 
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 typedef int i32x8_t __attribute__((ext_vector_type(8)));
 
 struct Fp8Args {
@@ -49,8 +49,6 @@ struct Fp8Args {
     const float* amax_out;     // MODE 1: C is written as e4m3 bytes with that static scale of its own
     float* amax_next;          // MODE 1, optional: running maximum of |C| before quantisation (the NEXT call's scale: delayed scaling)
 };
-
-template <int V> struct IntC { static constexpr int value = V; };
 
 // Maximum over the wave without index registers (DPP patterns + the two permlane swaps): __shfl_xor's six bpermute indices are
 // loop invariants of the whole kernel -- hipcc hoisted them to the kernel entry and spilled all six here.
@@ -152,8 +150,7 @@ __device__ __forceinline__ void epilogue_fp8(const Fp8Args& g, f32x4_t (&acc)[8]
                 const f32x2_t b23 = {bq[j][2], bq[j][3]};
                 v01 = __builtin_elementwise_fma(v01, f32x2_t{cq[j][0], cq[j][1]}, b01);
                 v23 = __builtin_elementwise_fma(v23, f32x2_t{cq[j][2], cq[j][3]}, b23);
-                if (EPI == OV_EPI_BIAS_GELU_ERF) gelu_erf_f2x2(v01, v23);
-                if (EPI == OV_EPI_BIAS_GELU_TANH) { v01 = gelu_tanh_f2(v01); v23 = gelu_tanh_f2(v23); }
+                OV_GEMM_ACTIVATE(EPI, v01, v23);
                 if (MODE == 1) {
                     // 4 consecutive n -> 4 e4m3 bytes; image rows are 64 B (16 dwords), chunk ^= (row >> 1) & 3
                     float tmax = fmaxf(fmaxf(lmax, fabsf(v01[0])), fabsf(v01[1]));     // two v_max3_f32 with |x| source modifiers
@@ -166,8 +163,7 @@ __device__ __forceinline__ void epilogue_fp8(const Fp8Args& g, f32x4_t (&acc)[8]
                     pk8 = __builtin_amdgcn_cvt_pk_fp8_f32(__builtin_amdgcn_fmed3f(v23[0], -448.f, 448.f), __builtin_amdgcn_fmed3f(v23[1], -448.f, 448.f), pk8, true);
                     *(int*)(img + fr * 64 + ((j ^ ((fr >> 1) & 3)) << 4) + fq * 4) = pk8;
                 } else {
-                    const u32x2_t pk = {pack_bf16x2(v01[0], v01[1]), pack_bf16x2(v23[0], v23[1])};
-                    *(u32x2_t*)(wr + (((j * 2 + (fq >> 1)) ^ wsw) << 4)) = pk;
+                    *(u32x2_t*)(wr + (((j * 2 + (fq >> 1)) ^ wsw) << 4)) = OV_GEMM_PACK_QUAD(v01, v23);
                 }
             }
         }
@@ -205,9 +201,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_fp8_persist(const Fp8Args g)
     const int nwg = g.tiles_m * g.tiles_n;
     const int G = gridDim.x, bid = blockIdx.x;
     const int xcd = bid & 7, li = bid >> 3;
-    const int q8 = nwg >> 3, r8 = nwg & 7;
-    const int xstart = xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8;
-    const int xcnt = q8 + (xcd < r8 ? 1 : 0);
+    const int xstart = xcd_run(nwg, xcd).start, xcnt = xcd_run(nwg, xcd).count;
     const int nper = (G - xcd + 7) >> 3;
     int tcur = li;
     if (tcur >= xcnt) return;
@@ -300,9 +294,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_fp8_persist(const Fp8Args g)
     for (int p = 0; p < 4; ++p) stage_piece(cur, STAGE, p);
     advance(cur);                                                    // invariant at tile start: `cur` points at K-tile 2
     stage_params(0, m0, n0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    if (wm == 1) __builtin_amdgcn_s_barrier();                       // stagger the lower wave group by one interval
+    prologue_sync(wm);
 
     int cb = 0, pslot = 0, titer = 0;
     bool strict = true, has_next = false;
@@ -311,8 +303,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_fp8_persist(const Fp8Args g)
     auto frag = [](const char* p, int ca, int cb2) {                 // 32 operand bytes = two 16-byte chunks of the row
         return __builtin_bit_cast(i32x8_t, __builtin_shufflevector(*(const u32x4_t*)(p + ca), *(const u32x4_t*)(p + cb2), 0, 1, 2, 3, 4, 5, 6, 7));
     };
-    // KIND: 0 = K-tile 0 of a tile (nothing staged; K-tile 1 + parameters are older than the previous epilogue's 16 stores),
-    // 1 = K-tile 1 (stages K-tile 2; K-tile 1 has landed as a whole), 2 = steady state, 3 = last (stages the next tile's K-tile 0)
+    // One K-tile = four phases (m-half, n-half) (0,0) (0,1) (1,1) (1,0); KIND 0-3 and the schedule they select: gemm_tile.h.  Piece j of
+    // the next K-tile is issued in phase j and first read in phase 0 (j = 0, 1), 1 (j = 2), 2 (j = 3).
     auto ktile = [&](auto kind) {
         constexpr int KIND = decltype(kind)::value;
         const char* s = smem + cb;
@@ -330,38 +322,16 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_fp8_persist(const Fp8Args g)
 #pragma unroll
                 for (int j = 0; j < 2; ++j) wf[j] = frag(wp + j * 2048, c0, c1);
             }
-            if (KIND == 1 || KIND == 2) stage_piece(cur, nb, p);
-            if (KIND == 3) { if (has_next) stage_piece(nxt, nb, p); }
-            // piece j of the next K-tile is issued in phase j and first read in phase 0 (j = 0, 1), 1 (j = 2), 2 (j = 3)
-            if (KIND == 0) {
-                if (p == 3) {
-                    if (strict) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    else if (MODE == 1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");      // byte output: 8 stores per wave and tile
-                    else asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-                }
-            } else if (KIND == 1) {
-                if (p == 3) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-            } else if (KIND == 2) {
-                if (p != 2) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-            } else {
-                if (has_next) { if (p != 2) asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); }
-                else if (p == 0) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-                else if (p == 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_setprio(1);
+            OV_GEMM_KTILE_STAGE_WAIT(KtileFp8<MODE == 1>, KIND, p, strict, has_next, cur, nxt, nb, stage_piece);
+            phase_fence();
+            compute_segment([&] {
 #pragma unroll
-            for (int i = 0; i < 4; ++i)
+                for (int i = 0; i < 4; ++i)
 #pragma unroll
-                for (int j = 0; j < 2; ++j)
-                    acc[mh * 4 + i][nh * 2 + j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
-                        wf[j], af[i], acc[mh * 4 + i][nh * 2 + j], 0, 0, 0, 127, 0, 127);
-            __builtin_amdgcn_s_setprio(0);
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_sched_barrier(0);
+                    for (int j = 0; j < 2; ++j)
+                        acc[mh * 4 + i][nh * 2 + j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
+                            wf[j], af[i], acc[mh * 4 + i][nh * 2 + j], 0, 0, 0, 127, 0, 127);
+            });
         }
     };
     for (;;) {
@@ -370,10 +340,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_fp8_persist(const Fp8Args g)
         if (has_next) set_tile(tnext, nxt, nm0, nn0);
         ++titer;
         frag_consts();
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+        OV_GEMM_CLEAR_ACC(acc);
 
         ktile(IntC<0>{});
         cb ^= STAGE;
@@ -386,28 +353,16 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_fp8_persist(const Fp8Args g)
             advance(cur);
         }
         ktile(IntC<3>{});
-        if (wm == 0) __builtin_amdgcn_s_barrier();                   // re-align: every wave is past its last COMPUTE segment
-        if (has_next) {
-            advance(nxt);
-#pragma unroll
-            for (int p = 0; p < 4; ++p) stage_piece(nxt, cb, p);
-            advance(nxt);
-            asm volatile("s_waitcnt vmcnt(8)" ::: "memory");         // the next tile's K-tile 0 (issued a K-tile ago) has landed
-            stage_params(pslot ^ 1, nm0, nn0);
-        }
+        OV_GEMM_REALIGN(wm);
+        if (has_next) OV_GEMM_HANDOVER_STAGE(nxt, cb, advance, stage_piece, stage_params(pslot ^ 1, nm0, nn0));
         __builtin_amdgcn_sched_barrier(0);
         const bool edge = (m0 + BM > g.M) || (n0 + BN > g.N);
         epilogue_fp8<EPI, MODE>(g, acc, smem + IMG_OFF + wave * 2048, smem + PRM_OFF + pslot * 4096, m0, n0, wave, lane, edge, rs_const,
                                 inv_out, next_thr);
         if (!has_next) break;
-        strict = edge;
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        if (wm == 1) __builtin_amdgcn_s_barrier();
-        cb ^= STAGE;
-        pslot ^= 1;
-        cur = nxt;
-        m0 = nm0; n0 = nn0;
+        handover_barrier(edge, strict);
+        OV_GEMM_STAGGER(wm);
+        OV_GEMM_HANDOVER_SWAP(cb, STAGE, pslot, cur, nxt, m0, nm0, n0, nn0);
         tcur = tnext;
     }
 }

@@ -458,6 +458,28 @@ int ov_clip_loss_multi_backward(const float* img, const float* txt, const float*
                                 float* d_all_txt, int64_t ldg, int64_t gset_stride, float* d_scale, void* workspace,
                                 size_t workspace_bytes, ov_stream_t stream);
 
+/* Gradient accumulation for the InfoNCE.  Gradient of the loss over a fixed bank of N rows (C caption sets) with respect to the rows
+ * of one window [w0, w0 + b): the exact gradient of
+ *     1 / (2 C norm_rows) sum_c sum_{i < N} [ lse(A_c[i, :]) - A_c[i, i] + lse(B_c[i, :]) - B_c[i, i] ]
+ * restricted to the window's rows, which appear both as rows of their own strips and as columns of every other row's.
+ *   all_img / all_txt, ld, set_stride : the bank, laid out as the gathered operands of the C-set forward above (packed
+ *              [N, (1 + C) E] in place, or separate arrays)
+ *   terms    : [4 C, N], what that forward wrote for b = N, label_offset = 0 (per set lse_img, diag_img, lse_txt, diag_txt)
+ *   norm_rows: the number of rows the mean runs over (N in a world of one; a rank's own rows under data parallelism)
+ *   d_img [b, E], d_txt [C b, E] (set c in rows c b ...): always written
+ *   d_scale  : this window's share (device scalar), taken from the image-side strips only, so that disjoint windows covering the
+ *              bank sum to the full gradient; NULL = skip
+ * coef = grad_loss * logit_scale / (2 C norm_rows), both DEVICE scalars (grad_loss NULL = 1).  One pass over the window's b x N strips
+ * with both normalisers per logit; logits are never materialised; deterministic (no atomics, the d_scale partials, one per 32-row
+ * tile, are summed in a fixed order).  E % 32 == 0, E <= 1152, 1 <= C <= 4 (OV_ERR_UNSUPPORTED otherwise); NULL operands, w0 < 0,
+ * b <= 0, w0 + b > N, norm_rows <= 0, ld < E, ld or set_stride not a multiple of 4 floats, a base pointer off 16 bytes:
+ * OV_ERR_INVALID; a short workspace: OV_ERR_WORKSPACE; all before any launch. */
+size_t ov_clip_loss_window_backward_workspace_bytes(int b, int N, int C);
+int ov_clip_loss_window_backward(const float* all_img, const float* all_txt, int64_t ld, int64_t set_stride, int N, int E, int C,
+                                 const float* logit_scale, const float* terms, const float* grad_loss, int w0, int b, int norm_rows,
+                                 float* d_img, float* d_txt, float* d_scale, void* workspace, size_t workspace_bytes,
+                                 ov_stream_t stream);
+
 /* Distillation from a frozen teacher (DistillClipLoss, loss.py:180-216): the student's InfoNCE and, per direction, the cross
  * entropy of the student's log-softmax under the teacher's softmax, in one forward and one backward.
  *   img, txt        : the student's local embeddings [b, E] fp32, contiguous

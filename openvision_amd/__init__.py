@@ -4,7 +4,7 @@ Python surface mirrors the reference's ``open_clip.model.CLIP`` and ``open_clip.
 in hand-written HIP kernels behind the C ABI of ``libovhip.so`` (see include/ovhip.h).  No CPU fallback."""
 from .config import preset, openvision_model_cfg, load_config_dir, PRESETS  # noqa: F401
 
-__all__ = ["CLIP", "ClipLoss", "MultiCaptionClipLoss", "DistillClipLoss", "gather_features", "create_model", "preset", "openvision_model_cfg", "load_config_dir",
+__all__ = ["CLIP", "ClipLoss", "MultiCaptionClipLoss", "DistillClipLoss", "ContrastiveAccumulator", "gather_features", "create_model", "preset", "openvision_model_cfg", "load_config_dir",
            "WordPieceTokenizer"]
 
 
@@ -16,6 +16,9 @@ def __getattr__(name):   # lazy: importing the package must not require torch.cu
     if name in ("ClipLoss", "MultiCaptionClipLoss", "DistillClipLoss", "gather_features"):
         from . import loss
         return getattr(loss, name)
+    if name == "ContrastiveAccumulator":
+        from . import accumulate
+        return accumulate.ContrastiveAccumulator
     if name == "WordPieceTokenizer":
         from . import tokenizer
         return tokenizer.WordPieceTokenizer

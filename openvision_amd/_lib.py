@@ -153,6 +153,9 @@ SIGNATURES = {
     "ov_clip_loss_multi_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_int, c_void_p,
                                             c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p,
                                             c_void_p, c_size_t, c_void_p]),
+    "ov_clip_loss_window_backward_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "ov_clip_loss_window_backward": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                                             c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "ov_distill_loss_workspace_bytes": (c_size_t, [c_int, c_int]),
     "ov_distill_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int,
                                 c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,

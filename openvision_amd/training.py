@@ -539,15 +539,16 @@ def caption_sets(image: torch.Tensor, text: torch.Tensor) -> int:
     return nt // nb
 
 
-def clip_forward(model, image: torch.Tensor, text: torch.Tensor) -> Tuple[torch.Tensor, ...]:
+def clip_forward(model, image: torch.Tensor, text: torch.Tensor, keep: torch.Tensor = None) -> Tuple[torch.Tensor, ...]:
     """CLIP.forward (model.py:295-315) with gradients: (image_features, text_features, logit_scale.exp()), and ``logit_bias`` (the
     parameter itself, so its gradient flows) as a fourth element when the model has one (SigLIP).  Patch dropout as in
-    ``encode_image`` (drawn when the vision tower is in training mode with p > 0).
+    ``encode_image`` (drawn when the vision tower is in training mode with p > 0; ``keep`` overrides the draw, as there).
 
     ``text`` may stack C caption sets per image as [C B, T]: the text tower runs once on all rows and ``text_features`` is [C B, E],
     the input of ``MultiCaptionClipLoss(num_captions=C)``."""
     caption_sets(image, text)
-    out = (encode_image(model, image, True), encode_text(model, text, True), model.logit_scale.exp())
+    kw = {} if keep is None else {"keep": keep}
+    out = (encode_image(model, image, True, **kw), encode_text(model, text, True), model.logit_scale.exp())
     if getattr(model, "logit_bias", None) is not None:
         return out + (model.logit_bias,)
     return out
@@ -571,7 +572,7 @@ def decode(decoder, image_tokens: torch.Tensor, text_tokens: torch.Tensor) -> to
     return _LinearFn.apply(y.reshape(bsz * n, w), decoder.head.weight, None).view(bsz, n, -1)
 
 
-def coca_forward(model, decoder, image: torch.Tensor, text: torch.Tensor):
+def coca_forward(model, decoder, image: torch.Tensor, text: torch.Tensor, keep: torch.Tensor = None):
     """The reference trainer's 'coca' forward (src/main_clip.py:448-465): both towers once, their features for the contrastive loss
     and their tokens through the caption decoder -> (image_features, text_features, logit_scale.exp(), caption_logits).
 
@@ -585,13 +586,68 @@ def coca_forward(model, decoder, image: torch.Tensor, text: torch.Tensor):
     With one caption per image ([B, T] tokens) it is
 
         img_f, txt_f, scale, cap = training.coca_forward(model, decoder, images, tokens)
-        loss = ClipLoss()(img_f, txt_f, scale) + 2 * CaptionLoss()(cap, labels, mask)"""
+        loss = ClipLoss()(img_f, txt_f, scale) + 2 * CaptionLoss()(cap, labels, mask)
+
+    ``keep`` overrides the patch-dropout draw, as in ``encode_image``."""
     sets = caption_sets(image, text)
-    img_f, img_tok = encode_image(model, image, True, output_tokens=True)
+    kw = {} if keep is None else {"keep": keep}
+    img_f, img_tok = encode_image(model, image, True, output_tokens=True, **kw)
     txt_f, txt_tok = encode_text(model, text, True, output_tokens=True)
     if sets > 1:
         txt_tok = txt_tok[:image.shape[0]]
     return img_f, txt_f, model.logit_scale.exp(), decode(decoder, img_tok, txt_tok)
+
+
+def accumulated_step(model, batches, loss, decoder=None, caption_targets=None, caption_weight: float = 2.0,
+                     check: bool = False) -> torch.Tensor:
+    """Forward and backward of ONE training step over A micro-batches whose contrastive loss is the full-batch InfoNCE of all A b
+    pairs (times the world size), exactly (``accumulate.ContrastiveAccumulator``): the parameters' ``.grad`` receive the gradient the
+    one-batch step would give, at a micro-batch's activation memory.  ``batches``: a sequence of ``(image, text)`` micro-batches of one
+    size, text stacked [C b, T]; ``loss``: a ``ClipLoss`` or ``MultiCaptionClipLoss`` (``gather_with_grad=True`` under data
+    parallelism).  Returns the step's loss (device scalar, no grad).
+
+      pass 1  every micro-batch through ``clip_forward`` under ``torch.no_grad()``: the tower nodes see no requested gradient and run
+              the training path's own operators while keeping nothing, so the features are bitwise those of pass 2;
+      close   one forward over the bank of features (one all-gather of the packed rows under data parallelism);
+      pass 2  per micro-batch: forward with gradients, the window's loss, ``.backward()``; each graph is freed before the next
+              forward.
+
+    ``decoder`` (a ``caption.TextDecoder``): pass 2 runs ``coca_forward`` and adds ``caption_weight * CaptionLoss()(logits, labels_j,
+    mask_j) / A`` to window j's loss, ``caption_targets[j] = (labels, mask)``.  Patch dropout: one draw per micro-batch, made before
+    pass 1 and used by both passes.  Recomputation, frozen parameters and ``lock_image_tower`` work as in a one-batch step.
+    ``check=True`` verifies that pass 2 recomputed pass 1's features bitwise (one host synchronisation per micro-batch).
+
+    The optimiser is not touched: call ``FusedAdamW.zero_grad(windows=A)`` before and ``all_reduce_gradients`` / ``step`` after."""
+    from .accumulate import ContrastiveAccumulator
+    batches = list(batches)
+    if not batches:
+        raise ValueError("accumulated_step: no micro-batch")
+    if decoder is not None and (caption_targets is None or len(caption_targets) != len(batches)):
+        raise ValueError("accumulated_step: with a decoder, caption_targets holds one (labels, mask) pair per micro-batch")
+    acc = ContrastiveAccumulator(loss)
+    v = model.visual
+    keeps = [v.patch_dropout.sample(image.shape[0], v.num_patches) if v.dropout_active() else None for image, _ in batches]
+    with torch.no_grad():
+        for (image, text), keep in zip(batches, keeps):
+            img_f, txt_f = clip_forward(model, image, text, keep=keep)[:2]
+            acc.add(img_f, txt_f)
+        total = acc.close(model.logit_scale.exp()).clone()
+    if decoder is not None:
+        from .caption import CaptionLoss
+        cap_loss = CaptionLoss()
+    for j, ((image, text), keep) in enumerate(zip(batches, keeps)):
+        if decoder is None:
+            img_f, txt_f, scale = clip_forward(model, image, text, keep=keep)[:3]
+            part = acc.window_loss(j, img_f, txt_f, scale, check=check)
+        else:
+            img_f, txt_f, scale, cap = coca_forward(model, decoder, image, text, keep=keep)
+            labels, mask = caption_targets[j]
+            cpart = caption_weight * cap_loss(cap, labels, mask) / len(batches)
+            total += cpart.detach()
+            part = acc.window_loss(j, img_f, txt_f, scale, check=check) + cpart
+        part.backward()
+        del part, img_f, txt_f, scale
+    return total
 
 
 # --------------------------------------------------------------------------------------------------------------------------
@@ -673,15 +729,22 @@ class FusedAdamW:
             g["nu"].copy_(s["nu"].to(g["nu"].device, torch.float32))
         self.t = int(sd["t"])
 
-    def zero_grad(self) -> None:
-        """Zero the flat gradient buffers; ``.grad`` stays a view of them (set_to_none would detach the views)."""
+    def zero_grad(self, windows: int = 1) -> None:
+        """Zero the flat gradient buffers; ``.grad`` stays a view of them (set_to_none would detach the views).
+
+        ``windows``: the number of backward passes that accumulate into the buffers before the exchange (gradient accumulation:
+        ``accumulated_step`` over A micro-batches runs A backwards, so call ``zero_grad(windows=A)`` before it).  After
+        ``overlap_gradient_exchange`` each bucket then waits for its parameters' gradients of every window and starts with the last
+        window's, instead of sending the first window's partial sums.  1 is one backward per step, as before."""
+        if int(windows) < 1:
+            raise ValueError("windows must be at least 1")
         for g in self.groups:
             g["grad"].zero_()
             for (_, p), o in zip(g["params"], g["offs"]):
                 want = g["grad"][o:o + p.numel()]
                 if p.grad is None or p.grad.data_ptr() != want.data_ptr():
                     p.grad = want.view(p.shape)
-        self._rearm()
+        self._rearm(int(windows))
 
     def _collect(self) -> None:
         """A ``.grad`` that autograd replaced instead of accumulating in place is copied back into its flat slot; the slot of a
@@ -730,11 +793,11 @@ class FusedAdamW:
                 self._ov_hooks.append(p.register_post_accumulate_grad_hook(self._make_hook(gi, pi, o, mine)))
         self._rearm()
 
-    def _rearm(self) -> None:
+    def _rearm(self, windows: int = 1) -> None:
         ov = getattr(self, "_ov", None)
         if ov is not None:
             ov["works"], ov["launched"] = [], [False] * len(self._ov_buckets)
-            ov["pending"] = [len(m) for m in self._ov_members]
+            ov["pending"] = [len(m) * windows for m in self._ov_members]      # every member's gradient lands once per window
 
     def _launch_bucket(self, bi: int) -> None:
         import torch.distributed as dist

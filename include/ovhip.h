@@ -717,6 +717,36 @@ int       ov_tower_set_fp8_mask(ov_tower* t, const unsigned char* mask, int n);
  * OV_ERR_INVALID; a tower in fp8 / fp8-mixed precision with a prefix set returns OV_ERR_UNSUPPORTED from ov_tower_forward (no fp8
  * under a mask).  prefix < -1 is OV_ERR_INVALID.  The sizes ov_tower_saved_bytes* / *_workspace_bytes report hold for either state. */
 int       ov_tower_set_prefix(ov_tower* t, int prefix);
+/* Stochastic depth ("drop path", the reference's DropPath: src/models/common.py:659-675) on the training walks.  A table says, for
+ * every block i of the tower and each of its two residual branches j (0 = attention, 1 = MLP), which of the B samples the branch
+ * keeps; a kept sample's branch output is multiplied by scale[i] = 1 / keep_i, a dropped sample's branch is zero and is not computed:
+ *   idx    device int32 [layers][2][B]   the kept samples' numbers first (ascending or not), then the dropped ones'
+ *   slot   device int32 [layers][2][B]   the inverse: slot[b] = j where idx[j] == b and j < count, -1 for a dropped sample
+ *   count  host   int   [layers][2]      kept samples of the branch, 0 .. B           (copied by the call)
+ *   scale  host   float [layers]         > 0                                          (copied by the call)
+ * The device arrays and `scratch` (ov_tower_drop_path_workspace_bytes(t, B, L) bytes for the walks' L, 16-byte aligned) are
+ * borrowed until the table is cleared with idx == NULL.  While a table is set, ov_tower_forward_saving[_from], the checkpointed
+ * pair and ov_tower_backward[_partial / _input] must be called with the table's B (OV_ERR_INVALID otherwise; OV_ERR_WORKSPACE for a
+ * short scratch), and a branch whose count < B or whose scale != 1 runs
+ *   ov_sample_gather -> LayerNorm -> GEMM(s) / attention on count L rows -> product with its bias -> ov_sample_scatter_axpy
+ * and the mirror image in the backward (weight and bias gradients see the kept rows; count == 0: zeros); a dropped sample's rows of
+ * the branch's output and input gradient are the residual's, bitwise.  A branch with count == B and scale == 1, and every walk with
+ * no table, issue exactly the launches they issue without this call.  The saved slots keep their layout: a compact branch uses the
+ * leading count L rows of its regions.  ov_tower_forward (inference) returns OV_ERR_UNSUPPORTED while a table is set. */
+int       ov_tower_set_drop_path(ov_tower* t, const int* idx, const int* slot, const int* count, const float* scale, int B,
+                                 void* scratch, size_t scratch_bytes);
+size_t    ov_tower_drop_path_workspace_bytes(const ov_tower* t, int B, int L);
+/* The two glue passes of a compact branch (droppath.hip).  The L rows of a sample are contiguous, L rows of D bf16, D % 8 == 0;
+ * pointers 16-byte aligned; B <= 65535.
+ *   ov_sample_gather        dst[j L + t, :] = bf16(scale * src[idx[j] L + t, :]) for j < k; scale == 1.0f is a bitwise copy; k == 0
+ *                           launches nothing.  idx: device int32, values in [0, B) (others move nothing).
+ *   ov_sample_scatter_axpy  for every b < B: out[b] = bf16(res[b] + scale * y[slot[b]]) where 0 <= slot[b] < k, else out[b] = res[b]
+ *                           bitwise (nothing is written where out == res).  slot: device int32 [B].  out may alias res, not y.
+ * The backward uses this adding form too: the compact LayerNorm backward runs without its residual input, and the scatter adds the
+ * incoming gradient as `res`. */
+int       ov_sample_gather(const ov_bf16* src, const int* idx, ov_bf16* dst, int B, int k, int L, int D, float scale, ov_stream_t stream);
+int       ov_sample_scatter_axpy(const ov_bf16* res, const ov_bf16* y, const int* slot, ov_bf16* out, int B, int k, int L, int D, float scale,
+                                 ov_stream_t stream);
 size_t    ov_tower_workspace_bytes(const ov_tower* t, int B, int L);
 /* x[B*L, D] bf16 is updated in place through all `layers` blocks. */
 int       ov_tower_forward(const ov_tower* t, ov_bf16* x, int B, int L, void* workspace,

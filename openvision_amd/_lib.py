@@ -111,6 +111,10 @@ SIGNATURES = {
     "ov_softmax_xent_backward": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int,
                                          c_void_p, c_size_t, c_void_p]),
     "ov_tower_set_prefix": (c_int, [c_void_p, c_int]),
+    "ov_tower_set_drop_path": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t]),
+    "ov_tower_drop_path_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "ov_sample_gather": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p]),
+    "ov_sample_scatter_axpy": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p]),
     "ov_block_backward_prefix": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
                                          c_size_t, c_void_p]),
     "ov_im2col_patches": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),

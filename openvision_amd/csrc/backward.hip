@@ -615,7 +615,8 @@ int chain_linear(const BlockBufs& b, int64_t M, ov_stream_t stream, const ov_bf1
 // s.fc_act == NULL (the activation was not kept): dh = dy Wproj, then one element-wise pass turns it into da and leaves gelu(a) in b.a
 // for the c_proj dW; otherwise the GELU derivative at s.fc_pre rides on the epilogue of dy Wproj.
 int chain_mlp(const ov_tower_cfg* cfg, const ov_block_weights* w, const ov_block_saved& s, const ov_bf16* dy, const ov_block_grads* g,
-              int pairs, bool need_dx1, const BlockBufs& b, int64_t M, ov_stream_t stream) {
+              int pairs, bool need_dx1, const BlockBufs& b, int64_t M, ov_stream_t stream, bool residual = true) {
+    const ov_bf16* dres = residual ? dy : nullptr;        // false (a compact drop-path branch): b.dx1 = the branch's input gradient alone
     const bool p_ln2 = pairs & 8, p_fc = pairs & 16, p_proj = pairs & 32;
     const bool need_dln2 = p_ln2 || need_dx1;             // d ln_2 out (c_fc dX)
     const bool need_dh = p_fc || need_dln2;               // d c_fc pre-activation (c_proj dX with the GELU derivative)
@@ -635,9 +636,9 @@ int chain_mlp(const ov_tower_cfg* cfg, const ov_block_weights* w, const ov_block
         OV_TRY(chain_linear(b, M, stream, b.dh, s.ln2_out, w->fc_w, F, D, need_dln2 ? b.t1 : nullptr, p_fc ? g->fc_w : nullptr,
                             p_fc ? g->fc_b : nullptr));
     if (p_ln2 && need_dx1)                                                                                              // dx1 = dy + ...
-        OV_TRY(ov_layernorm_backward(s.x1, D, w->ln2_w, b.t1, D, dy, D, b.dx1, D, g->ln2_w, g->ln2_b, M, D, cfg->ln_eps, b.ln, b.ln_bytes, stream));
+        OV_TRY(ov_layernorm_backward(s.x1, D, w->ln2_w, b.t1, D, dres, D, b.dx1, D, g->ln2_w, g->ln2_b, M, D, cfg->ln_eps, b.ln, b.ln_bytes, stream));
     else if (p_ln2 || need_dx1)
-        OV_TRY(layernorm_backward(s.x1, D, w->ln2_w, b.t1, D, dy, D, need_dx1 ? b.dx1 : nullptr, D, p_ln2 ? g->ln2_w : nullptr,
+        OV_TRY(layernorm_backward(s.x1, D, w->ln2_w, b.t1, D, dres, D, need_dx1 ? b.dx1 : nullptr, D, p_ln2 ? g->ln2_w : nullptr,
                                   p_ln2 ? g->ln2_b : nullptr, M, D, cfg->ln_eps, b.ln, stream));
     return OV_OK;
 }
@@ -645,7 +646,8 @@ int chain_mlp(const ov_tower_cfg* cfg, const ov_block_weights* w, const ov_block
 // Attention half, x1 = x + out_proj(attn(qkv)): the pairs ln_1, in_proj, out_proj of `g` and, when dx != NULL, dx = dx1 + the branch's
 // input gradient (dx may alias dx1).  Reads s.ln1_out only for the in_proj dW.
 int chain_attn(const ov_tower_cfg* cfg, const ov_block_weights* w, const ov_bf16* x, const ov_block_saved& s, const ov_bf16* dx1, ov_bf16* dx,
-               const ov_block_grads* g, int pairs, int prefix, const BlockBufs& b, int B, int L, ov_stream_t stream) {
+               const ov_block_grads* g, int pairs, int prefix, const BlockBufs& b, int B, int L, ov_stream_t stream, bool residual = true) {
+    const ov_bf16* dres = residual ? dx1 : nullptr;       // false (a compact drop-path branch): dx = the branch's input gradient alone
     const bool p_ln1 = pairs & 1, p_qkv = pairs & 2, p_out = pairs & 4;
     const bool need_dln1 = p_ln1 || dx;                   // d ln_1 out (QKV dX)
     const bool need_dqkv = p_qkv || need_dln1;            // attention backward (reads d attention out: out_proj dX)
@@ -662,10 +664,90 @@ int chain_attn(const ov_tower_cfg* cfg, const ov_block_weights* w, const ov_bf16
         OV_TRY(chain_linear(b, M, stream, b.dqkv, s.ln1_out, w->qkv_w, 3 * D, D, need_dln1 ? b.t1 : nullptr, p_qkv ? g->qkv_w : nullptr,
                             p_qkv ? g->qkv_b : nullptr));
     if (p_ln1 && dx)
-        OV_TRY(ov_layernorm_backward(x, D, w->ln1_w, b.t1, D, dx1, D, dx, D, g->ln1_w, g->ln1_b, M, D, cfg->ln_eps, b.ln, b.ln_bytes, stream));
+        OV_TRY(ov_layernorm_backward(x, D, w->ln1_w, b.t1, D, dres, D, dx, D, g->ln1_w, g->ln1_b, M, D, cfg->ln_eps, b.ln, b.ln_bytes, stream));
     else if (p_ln1 || dx)
-        OV_TRY(layernorm_backward(x, D, w->ln1_w, b.t1, D, dx1, D, dx, D, p_ln1 ? g->ln1_w : nullptr, p_ln1 ? g->ln1_b : nullptr, M, D,
+        OV_TRY(layernorm_backward(x, D, w->ln1_w, b.t1, D, dres, D, dx, D, p_ln1 ? g->ln1_w : nullptr, p_ln1 ? g->ln1_b : nullptr, M, D,
                                   cfg->ln_eps, b.ln, stream));
+    return OV_OK;
+}
+
+// ---- drop path (ov_tower_set_drop_path): a half whose branch kept `count` of the B samples runs on those samples' rows ------------
+// The chain's buffers for a compact half: the staging areas come from the drop scratch (sized for any count <= B), dx1 = where the
+// compact MLP half leaves its input gradient.
+inline BlockBufs compact_bufs(const BlockBufs& b, const ov_block_drop& d) {
+    BlockBufs c = b;
+    c.dx1 = d.g2;
+    c.lin = d.lin; c.lin_bytes = d.lin_bytes;
+    c.ln = d.ln;   c.ln_bytes = d.ln_bytes;
+    c.att = d.att; c.att_bytes = d.att_bytes;
+    return c;
+}
+// a branch nobody kept: its requested parameter gradients are zeros
+int zero_pair(ov_bf16* w, float* bias, size_t wn, size_t bn, hipStream_t st) {
+    hipError_t e = hipMemsetAsync(w, 0, wn * sizeof(ov_bf16), st);
+    if (e == hipSuccess) e = hipMemsetAsync(bias, 0, bn * sizeof(float), st);
+    return ov_hip(e);
+}
+int zero_ln_pair(float* gw, float* gb, int D, hipStream_t st) {
+    hipError_t e = hipMemsetAsync(gw, 0, (size_t)D * sizeof(float), st);
+    if (e == hipSuccess) e = hipMemsetAsync(gb, 0, (size_t)D * sizeof(float), st);
+    return ov_hip(e);
+}
+
+// chain_mlp for a compact branch: gather dy (times the branch's scale: the branch's output gradient) and x1 of the kept samples, run
+// the half on count L rows without the LayerNorm backward's residual input, then b.dx1[b] = dy[b] + d(branch input)[slot[b]] for the
+// kept samples and dy[b] bitwise for the others.
+int chain_mlp_drop(const ov_tower_cfg* cfg, const ov_block_weights* w, const ov_block_saved& s, const ov_bf16* dy, const ov_block_grads* g,
+                   int pairs, bool need_dx1, const BlockBufs& b, int B, int L, ov_stream_t stream, const ov_block_drop& d) {
+    const ov_drop_branch& br = d.mlp;
+    const int D = cfg->width, F = cfg->mlp_pad, k = br.count;
+    const int64_t M = (int64_t)B * L;
+    hipStream_t st = (hipStream_t)stream;
+    int rc;
+    if (k == 0) {
+        if (pairs & 8) OV_TRY(zero_ln_pair(g->ln2_w, g->ln2_b, D, st));
+        if (pairs & 16) OV_TRY(zero_pair(g->fc_w, g->fc_b, (size_t)F * D, F, st));
+        if (pairs & 32) OV_TRY(zero_pair(g->proj_w, g->proj_b, (size_t)D * F, D, st));
+        if (need_dx1) OV_TRY(ov_hip(hipMemcpyAsync(b.dx1, dy, (size_t)M * D * sizeof(ov_bf16), hipMemcpyDeviceToDevice, st)));
+        return OV_OK;
+    }
+    if (!(pairs & 56) && !need_dx1) return OV_OK;
+    OV_TRY(ov_sample_gather(dy, br.idx, d.g0, B, k, L, D, br.scale, stream));
+    ov_block_saved sc = s;
+    if ((pairs & 8) || need_dx1) {
+        OV_TRY(ov_sample_gather(s.x1, br.idx, d.g1, B, k, L, D, 1.0f, stream));
+        sc.x1 = d.g1;
+    }
+    OV_TRY(chain_mlp(cfg, w, sc, d.g0, g, pairs, need_dx1, compact_bufs(b, d), (int64_t)k * L, stream, false));
+    if (need_dx1) OV_TRY(ov_sample_scatter_axpy(dy, d.g2, br.slot, b.dx1, B, k, L, D, 1.0f, stream));
+    return OV_OK;
+}
+
+// chain_attn for a compact branch, on the same terms: dx[b] = dx1[b] + d(branch input)[slot[b]], dx1[b] bitwise for a dropped sample
+int chain_attn_drop(const ov_tower_cfg* cfg, const ov_block_weights* w, const ov_bf16* x, const ov_block_saved& s, const ov_bf16* dx1,
+                    ov_bf16* dx, const ov_block_grads* g, int pairs, int prefix, const BlockBufs& b, int B, int L, ov_stream_t stream,
+                    const ov_block_drop& d) {
+    const ov_drop_branch& br = d.attn;
+    const int D = cfg->width, k = br.count;
+    const int64_t M = (int64_t)B * L;
+    hipStream_t st = (hipStream_t)stream;
+    int rc;
+    if (k == 0) {
+        if (pairs & 1) OV_TRY(zero_ln_pair(g->ln1_w, g->ln1_b, D, st));
+        if (pairs & 2) OV_TRY(zero_pair(g->qkv_w, g->qkv_b, (size_t)3 * D * D, (size_t)3 * D, st));
+        if (pairs & 4) OV_TRY(zero_pair(g->out_w, g->out_b, (size_t)D * D, D, st));
+        if (dx && dx != dx1) OV_TRY(ov_hip(hipMemcpyAsync(dx, dx1, (size_t)M * D * sizeof(ov_bf16), hipMemcpyDeviceToDevice, st)));
+        return OV_OK;
+    }
+    if (!(pairs & 7) && !dx) return OV_OK;
+    OV_TRY(ov_sample_gather(dx1, br.idx, d.g0, B, k, L, D, br.scale, stream));
+    const ov_bf16* xc = x;
+    if ((pairs & 1) || dx) {
+        OV_TRY(ov_sample_gather(x, br.idx, d.g1, B, k, L, D, 1.0f, stream));
+        xc = d.g1;
+    }
+    OV_TRY(chain_attn(cfg, w, xc, s, d.g0, dx ? d.g2 : nullptr, g, pairs, prefix, compact_bufs(b, d), k, L, stream, false));
+    if (dx) OV_TRY(ov_sample_scatter_axpy(dx1, d.g2, br.slot, dx, B, k, L, D, 1.0f, stream));
     return OV_OK;
 }
 #undef OV_TRY
@@ -674,11 +756,47 @@ int chain_attn(const ov_tower_cfg* cfg, const ov_block_weights* w, const ov_bf16
 // over the block's intermediates `s` (every field set but fc_act and attn_lse, which may be NULL), for the requested pairs of `g` and,
 // when dx != NULL, the block input's gradient (dx may alias dy).  d x1 is needed by everything in the attention half.
 int block_backward_chain(const ov_tower_cfg* cfg, const ov_block_weights* w, const ov_bf16* x, const ov_block_saved& s, const ov_bf16* dy,
-                         ov_bf16* dx, const ov_block_grads* g, int pairs, int prefix, const BlockBufs& b, int B, int L, ov_stream_t stream) {
-    const int rc = chain_mlp(cfg, w, s, dy, g, pairs, (pairs & 7) || dx, b, (int64_t)B * L, stream);
-    return rc ? rc : chain_attn(cfg, w, x, s, b.dx1, dx, g, pairs, prefix, b, B, L, stream);
+                         ov_bf16* dx, const ov_block_grads* g, int pairs, int prefix, const BlockBufs& b, int B, int L, ov_stream_t stream,
+                         const ov_block_drop* drop = nullptr) {
+    // drop path: each half on its own branch's kept samples; a branch that kept everyone at scale 1 is the plain half
+    const bool need_dx1 = (pairs & 7) || dx;
+    const int rc = drop && ov_branch_compact(drop->mlp, B) ? chain_mlp_drop(cfg, w, s, dy, g, pairs, need_dx1, b, B, L, stream, *drop)
+                                                           : chain_mlp(cfg, w, s, dy, g, pairs, need_dx1, b, (int64_t)B * L, stream);
+    if (rc) return rc;
+    return drop && ov_branch_compact(drop->attn, B) ? chain_attn_drop(cfg, w, x, s, b.dx1, dx, g, pairs, prefix, b, B, L, stream, *drop)
+                                                    : chain_attn(cfg, w, x, s, b.dx1, dx, g, pairs, prefix, b, B, L, stream);
 }
 }  // namespace
+
+// The drop scratch (common.h: ov_block_drop): three [B L, D] buffers and the chain's staging areas at the largest size any count <= B
+// asks for (the split-K plan of a dW product, and with it its staging, is not monotonic in the row count).  The sizes of the last
+// shape asked about are remembered: the walks and the size query ask again for every call.
+size_t block_drop_plan(const ov_tower_cfg* cfg, int B, int L, char* base, ov_block_drop* out) {
+    if (!block_cfg_ok(cfg) || B <= 0 || L <= 0) return 0;
+    struct Memo { int width, heads, mlp_pad, B, L, ncu; size_t lin, ln, att; };
+    static thread_local Memo memo = {};
+    const int ncu = ov_num_cus();
+    if (!(memo.width == cfg->width && memo.heads == cfg->heads && memo.mlp_pad == cfg->mlp_pad && memo.B == B && memo.L == L && memo.ncu == ncu)) {
+        Memo m = {cfg->width, cfg->heads, cfg->mlp_pad, B, L, ncu, 0, 0, 0};
+        for (int k = 1; k <= B; ++k) {
+            const BlockBufs b = plan_block(cfg, k, L, PLAN_FULL, nullptr);
+            if (b.lin_bytes > m.lin) m.lin = b.lin_bytes;
+            if (b.ln_bytes > m.ln) m.ln = b.ln_bytes;
+            if (b.att_bytes > m.att) m.att = b.att_bytes;
+        }
+        memo = m;
+    }
+    const size_t rows = align256((size_t)B * L * cfg->width * sizeof(ov_bf16));
+    size_t off = 0;
+    auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += align256(bytes); return p; };
+    ov_block_drop d = {};
+    d.g0 = (ov_bf16*)take(rows); d.g1 = (ov_bf16*)take(rows); d.g2 = (ov_bf16*)take(rows);
+    d.lin = take(memo.lin); d.lin_bytes = memo.lin;
+    d.ln = take(memo.ln);   d.ln_bytes = memo.ln;
+    d.att = take(memo.att + 256); d.att_bytes = memo.att;
+    if (out) *out = d;
+    return off;
+}
 
 extern "C" size_t ov_block_backward_workspace_bytes(const ov_tower_cfg* cfg, int B, int L) { return plan_bytes(cfg, B, L, PLAN_FULL); }
 
@@ -759,8 +877,8 @@ extern "C" int ov_block_attn_backward_input(const ov_tower_cfg* cfg, const ov_bl
 // Every field of `s` is set (ov_tower_forward_saving's slot).  block_backward_input: dx alone, in the smaller input-only workspace.
 size_t block_backward_input_workspace_bytes(const ov_tower_cfg* cfg, int B, int L) { return plan_bytes(cfg, B, L, PLAN_MLP); }
 int block_backward_input(const ov_tower_cfg* cfg, const ov_block_weights* w, const ov_bf16* x, const ov_block_saved* s, const ov_bf16* dy,
-                         ov_bf16* dx, int prefix, int B, int L, void* workspace, ov_stream_t stream) {
-    return block_backward_chain(cfg, w, x, *s, dy, dx, nullptr, 0, prefix, plan_block(cfg, B, L, PLAN_MLP, (char*)workspace), B, L, stream);
+                         ov_bf16* dx, int prefix, int B, int L, void* workspace, ov_stream_t stream, const ov_block_drop* drop) {
+    return block_backward_chain(cfg, w, x, *s, dy, dx, nullptr, 0, prefix, plan_block(cfg, B, L, PLAN_MLP, (char*)workspace), B, L, stream, drop);
 }
 
 // The requested pairs of `g`: 0 for g == NULL, -1 when a pair has exactly one NULL pointer or a pointer is not 16-byte aligned (the
@@ -781,10 +899,10 @@ int block_grad_pairs(const ov_block_grads* g) {
 // input's gradient (dx may alias dy).  Workspace: ov_block_backward_workspace_bytes.
 int block_backward_partial(const ov_tower_cfg* cfg, const ov_block_weights* w, const ov_bf16* x, const ov_block_saved* s,
                            const ov_bf16* dy, ov_bf16* dx, const ov_block_grads* g, int prefix, int B, int L, void* workspace,
-                           size_t workspace_bytes, ov_stream_t stream) {
+                           size_t workspace_bytes, ov_stream_t stream, const ov_block_drop* drop) {
     const int pairs = block_grad_pairs(g);
     if (pairs < 0) return OV_ERR_INVALID;
     const BlockBufs b = plan_block(cfg, B, L, PLAN_FULL, (char*)workspace);
     if (workspace_bytes < b.total) return OV_ERR_WORKSPACE;
-    return block_backward_chain(cfg, w, x, *s, dy, dx, g, pairs, prefix, b, B, L, stream);
+    return block_backward_chain(cfg, w, x, *s, dy, dx, g, pairs, prefix, b, B, L, stream, drop);
 }

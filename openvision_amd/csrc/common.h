@@ -31,13 +31,26 @@ static inline bool ov_attn_bwd_resident(int hd, int L) { return hd == 64 && L <=
 // backward.hip, one block over its kept activations (arguments checked by the caller), both the block's one backward chain:
 // block_backward_partial with the requested pairs of g (block_grad_pairs: bit k = pair k, -1 for a half-NULL or misaligned pair) and
 // dx unless NULL; block_backward_input with no pair, dx alone, in a smaller workspace.
+// Drop path (ov_tower_set_drop_path) of one block: per residual branch the kept samples (device idx / slot of this layer and branch,
+// their count, the branch's scale), and the scratch of a compact branch carved by block_drop_plan once per walk: g0 / g1 / g2 hold
+// B L rows of D bf16 each (gathered rows, compact product or gradient), lin / ln / att replace the chain's staging areas, sized for the
+// largest need of any count <= B.  `drop` == NULL, or a branch with count == B and scale == 1, is today's path.
+struct ov_drop_branch { const int *idx, *slot; int count; float scale; };
+struct ov_block_drop {
+    ov_drop_branch attn, mlp;
+    ov_bf16 *g0, *g1, *g2;
+    char *lin, *ln, *att;
+    size_t lin_bytes, ln_bytes, att_bytes;
+};
+static inline bool ov_branch_compact(const ov_drop_branch& b, int B) { return b.count != B || b.scale != 1.0f; }
+size_t block_drop_plan(const ov_tower_cfg* cfg, int B, int L, char* base, ov_block_drop* out);     // returns the scratch's size
 int block_grad_pairs(const ov_block_grads* g);
 int block_backward_partial(const ov_tower_cfg* cfg, const ov_block_weights* w, const ov_bf16* x, const ov_block_saved* s, const ov_bf16* dy,
                            ov_bf16* dx, const ov_block_grads* g, int prefix, int B, int L, void* workspace, size_t workspace_bytes,
-                           ov_stream_t stream);
+                           ov_stream_t stream, const ov_block_drop* drop = nullptr);
 size_t block_backward_input_workspace_bytes(const ov_tower_cfg* cfg, int B, int L);
 int block_backward_input(const ov_tower_cfg* cfg, const ov_block_weights* w, const ov_bf16* x, const ov_block_saved* s, const ov_bf16* dy,
-                         ov_bf16* dx, int prefix, int B, int L, void* workspace, ov_stream_t stream);
+                         ov_bf16* dx, int prefix, int B, int L, void* workspace, ov_stream_t stream, const ov_block_drop* drop = nullptr);
 // embed.hip: ov_im2col_patches_keep with the kept rows' positional-embedding rows gathered into posk in the same launch
 int ov_im2col_patches_keep_pos(const void* image, int img_dtype, const int* keep, ov_bf16* out, int B, int S, int P, int K, int Kpad,
                                const ov_bf16* pos, ov_bf16* posk, int D, int* err_flag, ov_stream_t stream);

@@ -46,6 +46,14 @@ struct ov_tower {
     int h_mode;
     unsigned char* mask8;         // fp8 path: per layer, which of the four GEMMs take e4m3 operands (OV_FP8_QKV | _OUT | _FC | _PROJ)
     int prefix;                   // attention mask of every block: -1 = none, >= 0 = ov_attention_prefix's prefix (ov_tower_set_prefix)
+    // drop path (ov_tower_set_drop_path): device idx / slot [layers][2][drop_B] and the scratch are borrowed, count [layers][2] and
+    // scale [layers] are the tower's own copies; drop_idx == NULL = no table
+    const int *drop_idx, *drop_slot;
+    int* drop_count;
+    float* drop_scale;
+    int drop_B;
+    char* drop_ws;
+    size_t drop_ws_bytes;
 };
 
 // Row pitch (elements) of the workspace's `big` region (qkv / MLP hidden).  max(3 D, mlp_pad) is a power-of-two number of bytes for
@@ -191,12 +199,18 @@ extern "C" ov_tower* ov_tower_create(const ov_tower_cfg* cfg) {
     t->h_amax = nullptr;
     t->h_mode = 0;
     t->prefix = -1;
+    t->drop_idx = t->drop_slot = nullptr;
+    t->drop_B = 0;
+    t->drop_ws = nullptr;
+    t->drop_ws_bytes = 0;
+    t->drop_count = new (std::nothrow) int[2 * cfg->layers]();
+    t->drop_scale = new (std::nothrow) float[cfg->layers]();
     t->blocks = new (std::nothrow) ov_block_weights[cfg->layers]();
     t->set = new (std::nothrow) unsigned char[cfg->layers]();
     t->fp8 = new (std::nothrow) ov_block_fp8[cfg->layers]();
     t->set8 = new (std::nothrow) unsigned char[cfg->layers]();
     t->mask8 = new (std::nothrow) unsigned char[cfg->layers];
-    if (!t->blocks || !t->set || !t->fp8 || !t->set8 || !t->mask8) { ov_tower_destroy(t); return nullptr; }
+    if (!t->blocks || !t->set || !t->fp8 || !t->set8 || !t->mask8 || !t->drop_count || !t->drop_scale) { ov_tower_destroy(t); return nullptr; }
     for (int i = 0; i < cfg->layers; ++i) t->mask8[i] = OV_FP8_ALL;
     return t;
 }
@@ -213,6 +227,8 @@ extern "C" void ov_tower_destroy(ov_tower* t) {
     delete[] t->fp8;
     delete[] t->mask8;
     delete[] t->set8;
+    delete[] t->drop_count;
+    delete[] t->drop_scale;
     delete t;
 }
 
@@ -271,6 +287,41 @@ extern "C" int ov_tower_set_prefix(ov_tower* t, int prefix) {
     if (!t || prefix < -1) return OV_ERR_INVALID;
     t->prefix = prefix;
     return OV_OK;
+}
+
+extern "C" int ov_tower_set_drop_path(ov_tower* t, const int* idx, const int* slot, const int* count, const float* scale, int B,
+                                      void* scratch, size_t scratch_bytes) {
+    if (!t) return OV_ERR_INVALID;
+    if (!idx) {                                                   // NULL clears: back to today's launches
+        t->drop_idx = t->drop_slot = nullptr;
+        t->drop_B = 0;
+        t->drop_ws = nullptr;
+        t->drop_ws_bytes = 0;
+        return OV_OK;
+    }
+    if (!slot || !count || !scale || !scratch || B <= 0) return OV_ERR_INVALID;
+    if (B > 65535) return OV_ERR_UNSUPPORTED;                     // the sample is the glue kernels' grid.y
+    if ((((uintptr_t)idx | (uintptr_t)slot) & 3) || ((uintptr_t)scratch & 15)) return OV_ERR_INVALID;
+    for (int i = 0; i < t->cfg.layers; ++i) {
+        if (!(scale[i] > 0.0f) || !(scale[i] <= 3.0e38f)) return OV_ERR_INVALID;
+        if (count[2 * i] < 0 || count[2 * i] > B || count[2 * i + 1] < 0 || count[2 * i + 1] > B) return OV_ERR_INVALID;
+    }
+    for (int i = 0; i < t->cfg.layers; ++i) {
+        t->drop_count[2 * i] = count[2 * i];
+        t->drop_count[2 * i + 1] = count[2 * i + 1];
+        t->drop_scale[i] = scale[i];
+    }
+    t->drop_idx = idx;
+    t->drop_slot = slot;
+    t->drop_B = B;
+    t->drop_ws = (char*)scratch;
+    t->drop_ws_bytes = scratch_bytes;
+    return OV_OK;
+}
+
+extern "C" size_t ov_tower_drop_path_workspace_bytes(const ov_tower* t, int B, int L) {
+    if (!t || B <= 0 || L <= 0) return 0;
+    return block_drop_plan(&t->cfg, B, L, nullptr, nullptr);
 }
 
 namespace {
@@ -506,6 +557,7 @@ int tail_images(int B, int L) {
 static int tower_walk(const ov_tower* t, ov_bf16* x, int B, int L, void* workspace, size_t workspace_bytes, ov_stream_t stream,
                       int last_to) {
     if (!t || !x || !workspace || B <= 0 || L <= 0) return OV_ERR_INVALID;
+    if (t->drop_idx) return OV_ERR_UNSUPPORTED;                    // drop path is the training walks' (ov_tower_set_drop_path)
     const TowerWs w = tower_ws(t, B, L);
     if (workspace_bytes < w.total) return OV_ERR_WORKSPACE;
     if (((uintptr_t)x | (uintptr_t)workspace) & 15) return OV_ERR_INVALID;
@@ -621,25 +673,78 @@ inline Slot layer_slot(const ov_tower_cfg& c, const Layout& ly, int k, int64_t M
 // One block of the saving forward: the same operator sequence as run_block, with qkv / attention output / x1 / ... written where the
 // backward will read them, the input read from s.x and the output written to y (y may be s.x: nothing reads the input after out_proj).
 // y = NULL: the slot only (the backward's recompute), c_proj is not run.
+// drop (ov_tower_set_drop_path; NULL = none): a branch that does not keep every sample at scale 1 runs compact -- its kept samples' rows
+// gathered into drop->g0, the same operators on count L rows into the LEADING rows of the slot's regions, the product with its bias
+// into drop->g1 (OV_EPI_BIAS: no fused residual), then res + scale * product scattered over all B samples (a dropped sample's rows are
+// the residual's, bitwise).  count == 0: the branch's output is a copy of its input.
 int forward_saving_layer(const ov_tower_cfg& c, const ov_block_weights& w, const Slot& s, ov_bf16* y, int B, int L, ov_stream_t stream,
-                         int prefix) {
+                         int prefix, const ov_block_drop* drop = nullptr) {
     const int D = c.width, H = c.heads, hd = D / H;
     const int64_t M = (int64_t)B * L;
     const float scale = 1.0f / sqrtf((float)hd);
     const int gelu = c.gelu_tanh ? OV_EPI_BIAS_GELU_TANH : OV_EPI_BIAS_GELU_ERF;
+    const ov_drop_branch* da = drop && ov_branch_compact(drop->attn, B) ? &drop->attn : nullptr;
+    const ov_drop_branch* dm = drop && ov_branch_compact(drop->mlp, B) ? &drop->mlp : nullptr;
+    const int Ba = da ? da->count : B, Bm = dm ? dm->count : B;      // samples each branch runs on
+    const int64_t Ma = (int64_t)Ba * L, Mm = (int64_t)Bm * L;
+    const size_t stream_bytes = (size_t)M * D * sizeof(ov_bf16);
     int rc;
-    if ((rc = ov_layernorm(s.x, OV_BF16, D, w.ln1_w, w.ln1_b, s.n1, OV_BF16, D, M, D, c.ln_eps, stream))) return rc;
-    if ((rc = ov_gemm(s.n1, D, w.qkv_w, D, w.qkv_b, s.qkv, 3 * D, M, 3 * D, D, OV_EPI_BIAS, nullptr, 0, 0, 0, 0, stream))) return rc;
-    if (prefix >= 0) rc = ov_attention_prefix(s.qkv, 3 * D, s.o, D, B, L, H, hd, scale, prefix, stream);
-    else
-        rc = ov_attn_bwd_resident(hd, L) ? ov_attention_lse(s.qkv, 3 * D, s.o, D, s.lse, B, L, H, hd, scale, stream)
-                                         : ov_attention(s.qkv, 3 * D, s.o, D, B, L, H, hd, scale, stream);
-    if (rc) return rc;
-    if ((rc = ov_gemm(s.o, D, w.out_w, D, w.out_b, s.x1, D, M, D, D, OV_EPI_BIAS_RESIDUAL, s.x, D, 0, 0, 0, stream))) return rc;
-    if ((rc = ov_layernorm(s.x1, OV_BF16, D, w.ln2_w, w.ln2_b, s.n2, OV_BF16, D, M, D, c.ln_eps, stream))) return rc;
-    if ((rc = ov_gemm_keep(s.n2, D, w.fc_w, D, w.fc_b, s.act, c.mlp_pad, s.pre, c.mlp_pad, M, c.mlp_pad, D, gelu, stream))) return rc;
+    // ---- attention half ----
+    const ov_bf16* xa = s.x;
+    if (da && Ba > 0) {
+        if ((rc = ov_sample_gather(s.x, da->idx, drop->g0, B, Ba, L, D, 1.0f, stream))) return rc;
+        xa = drop->g0;
+    }
+    if (Ba > 0) {
+        if ((rc = ov_layernorm(xa, OV_BF16, D, w.ln1_w, w.ln1_b, s.n1, OV_BF16, D, Ma, D, c.ln_eps, stream))) return rc;
+        if ((rc = ov_gemm(s.n1, D, w.qkv_w, D, w.qkv_b, s.qkv, 3 * D, Ma, 3 * D, D, OV_EPI_BIAS, nullptr, 0, 0, 0, 0, stream))) return rc;
+        if (prefix >= 0) rc = ov_attention_prefix(s.qkv, 3 * D, s.o, D, Ba, L, H, hd, scale, prefix, stream);
+        else
+            rc = ov_attn_bwd_resident(hd, L) ? ov_attention_lse(s.qkv, 3 * D, s.o, D, s.lse, Ba, L, H, hd, scale, stream)
+                                             : ov_attention(s.qkv, 3 * D, s.o, D, Ba, L, H, hd, scale, stream);
+        if (rc) return rc;
+    }
+    if (!da) {
+        if ((rc = ov_gemm(s.o, D, w.out_w, D, w.out_b, s.x1, D, M, D, D, OV_EPI_BIAS_RESIDUAL, s.x, D, 0, 0, 0, stream))) return rc;
+    } else if (Ba > 0) {
+        if ((rc = ov_gemm(s.o, D, w.out_w, D, w.out_b, drop->g1, D, Ma, D, D, OV_EPI_BIAS, nullptr, 0, 0, 0, 0, stream))) return rc;
+        if ((rc = ov_sample_scatter_axpy(s.x, drop->g1, da->slot, s.x1, B, Ba, L, D, da->scale, stream))) return rc;
+    } else if ((rc = ov_hip(hipMemcpyAsync(s.x1, s.x, stream_bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream)))) {
+        return rc;
+    }
+    // ---- MLP half ----
+    const ov_bf16* xm = s.x1;
+    if (dm && Bm > 0) {
+        if ((rc = ov_sample_gather(s.x1, dm->idx, drop->g0, B, Bm, L, D, 1.0f, stream))) return rc;
+        xm = drop->g0;
+    }
+    if (Bm > 0) {
+        if ((rc = ov_layernorm(xm, OV_BF16, D, w.ln2_w, w.ln2_b, s.n2, OV_BF16, D, Mm, D, c.ln_eps, stream))) return rc;
+        if ((rc = ov_gemm_keep(s.n2, D, w.fc_w, D, w.fc_b, s.act, c.mlp_pad, s.pre, c.mlp_pad, Mm, c.mlp_pad, D, gelu, stream))) return rc;
+    }
     if (!y) return OV_OK;
-    return ov_gemm(s.act, c.mlp_pad, w.proj_w, c.mlp_pad, w.proj_b, y, D, M, D, c.mlp_pad, OV_EPI_BIAS_RESIDUAL, s.x1, D, 0, 0, 0, stream);
+    if (!dm) return ov_gemm(s.act, c.mlp_pad, w.proj_w, c.mlp_pad, w.proj_b, y, D, M, D, c.mlp_pad, OV_EPI_BIAS_RESIDUAL, s.x1, D, 0, 0, 0, stream);
+    if (Bm == 0) return ov_hip(hipMemcpyAsync(y, s.x1, stream_bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    if ((rc = ov_gemm(s.act, c.mlp_pad, w.proj_w, c.mlp_pad, w.proj_b, drop->g1, D, Mm, D, c.mlp_pad, OV_EPI_BIAS, nullptr, 0, 0, 0, 0, stream)))
+        return rc;
+    return ov_sample_scatter_axpy(s.x1, drop->g1, dm->slot, y, B, Bm, L, D, dm->scale, stream);
+}
+
+// The table's part for layer i of a walk over B samples, in `d` (whose scratch fields block_drop_plan filled); NULL = no table
+const ov_block_drop* layer_drop(const ov_tower* t, int i, ov_block_drop& d) {
+    if (!t->drop_idx) return nullptr;
+    const size_t B = (size_t)t->drop_B;
+    d.attn = {t->drop_idx + (2 * (size_t)i) * B, t->drop_slot + (2 * (size_t)i) * B, t->drop_count[2 * i], t->drop_scale[i]};
+    d.mlp = {t->drop_idx + (2 * (size_t)i + 1) * B, t->drop_slot + (2 * (size_t)i + 1) * B, t->drop_count[2 * i + 1], t->drop_scale[i]};
+    return &d;
+}
+// A walk under a table: its B is the table's and the scratch holds the plan for (B, L); `d` gets the carved scratch.  No table: OV_OK
+int drop_walk_check(const ov_tower* t, int B, int L, ov_block_drop& d) {
+    if (!t->drop_idx) return OV_OK;
+    if (B != t->drop_B) return OV_ERR_INVALID;
+    const size_t need = block_drop_plan(&t->cfg, B, L, t->drop_ws, &d);
+    if (need == 0) return OV_ERR_UNSUPPORTED;
+    return t->drop_ws_bytes >= need ? OV_OK : OV_ERR_WORKSPACE;
 }
 
 // The training forward: layers [0, first) run in place on x with their intermediates in `scratch` (the same operators on the same
@@ -649,8 +754,10 @@ int forward_walk(const ov_tower* t, int first, ov_bf16* x, ov_bf16* scratch, con
     const ov_tower_cfg& c = t->cfg;
     const int64_t M = (int64_t)B * L;
     if (t->prefix > L) return OV_ERR_INVALID;
+    ov_block_drop dp = {};
+    if (const int rc = drop_walk_check(t, B, L, dp)) return rc;
     for (int i = 0; i < first; ++i) {
-        const int rc = forward_saving_layer(c, t->blocks[i], slot_at(c, x, scratch, M), x, B, L, stream, t->prefix);
+        const int rc = forward_saving_layer(c, t->blocks[i], slot_at(c, x, scratch, M), x, B, L, stream, t->prefix, layer_drop(t, i, dp));
         if (rc) return rc;
     }
     if (first == c.layers) return OV_OK;
@@ -658,7 +765,8 @@ int forward_walk(const ov_tower* t, int first, ov_bf16* x, ov_bf16* scratch, con
     if (e != hipSuccess) return OV_ERR_HIP - (int)e;
     for (int i = first; i < c.layers; ++i) {
         const Slot s = layer_slot(c, ly, i - first, M);
-        const int rc = forward_saving_layer(c, t->blocks[i], s, i + 1 < c.layers ? s.x + ly.x_stride : x, B, L, stream, t->prefix);
+        const int rc = forward_saving_layer(c, t->blocks[i], s, i + 1 < c.layers ? s.x + ly.x_stride : x, B, L, stream, t->prefix,
+                                            layer_drop(t, i, dp));
         if (rc) return rc;
     }
     return OV_OK;
@@ -685,15 +793,18 @@ int backward_walk(const ov_tower* t, int first, int lo, const Layout& ly, bool r
     const ov_tower_cfg& c = t->cfg;
     const int64_t M = (int64_t)B * L;
     if (t->prefix > L) return OV_ERR_INVALID;
+    ov_block_drop dp = {};
+    if (const int rc = drop_walk_check(t, B, L, dp)) return rc;
     for (int i = c.layers - 1; i >= lo; --i) {
         const Slot s = layer_slot(c, ly, i - first, M);
+        const ov_block_drop* drop = layer_drop(t, i, dp);
         int rc;
-        if (rebuild && !(top_kept && i == c.layers - 1) && (rc = forward_saving_layer(c, t->blocks[i], s, nullptr, B, L, stream, t->prefix)))
+        if (rebuild && !(top_kept && i == c.layers - 1) && (rc = forward_saving_layer(c, t->blocks[i], s, nullptr, B, L, stream, t->prefix, drop)))
             return rc;
         const ov_block_saved sv = block_saved_of(c, s, L, t->prefix);
         rc = grads ? block_backward_partial(&c, &t->blocks[i], s.x, &sv, dx, (i > lo || want_dx) ? dx : nullptr, &grads[i - first], t->prefix,
-                                            B, L, workspace, workspace_bytes, stream)
-                   : block_backward_input(&c, &t->blocks[i], s.x, &sv, dx, dx, t->prefix, B, L, workspace, stream);
+                                            B, L, workspace, workspace_bytes, stream, drop)
+                   : block_backward_input(&c, &t->blocks[i], s.x, &sv, dx, dx, t->prefix, B, L, workspace, stream, drop);
         if (rc) return rc;
     }
     return OV_OK;

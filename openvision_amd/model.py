@@ -555,6 +555,16 @@ class Transformer(nn.Module):
         self._ws = _Workspace()
         self.causal_prefix: Optional[int] = None      # None = unmasked; see set_causal_prefix
         self._causal_mask = None                      # see adopt_causal_mask
+        self.drop_path: float = 0.0                   # stochastic depth rate of the training path; see set_drop_path
+
+    def set_drop_path(self, rate: float = 0.0) -> None:
+        """Stochastic depth of the training path (the reference's ``drop_path``, vit.py:358 / text_transformer.py:533-536): block i of
+        n drops each of its two residual branches per sample with probability ``linspace(0, rate, n)[i]``.  ``rate`` in [0, 1).  Only
+        ``openvision_amd.training`` reads it, and only in training mode; every inference path ignores it."""
+        rate = float(rate)
+        if not 0.0 <= rate < 1.0:
+            raise ValueError(f"drop_path rate {rate} outside [0, 1)")
+        self.drop_path = rate
 
     def set_causal_prefix(self, prefix: Optional[int]) -> None:
         """Attention mask of every block: None (default) = unmasked; an int P >= 0 = prefix-causal, key j is visible to query i iff
@@ -1085,6 +1095,16 @@ class CLIP(nn.Module):
         table; build the stage's optimiser afterwards).  The text tower is untouched."""
         self.visual.set_input_size(image_size)
         self.vision_cfg = dataclasses.replace(self.vision_cfg, image_size=int(image_size))
+
+    def set_drop_path(self, image: float = 0.0, text: float = 0.0) -> None:
+        """Stochastic depth rates of the two towers on the training path (``Transformer.set_drop_path``; the reference's
+        ``drop_path`` of vit.py:358 and text_transformer.py:533-536), each in [0, 1).  The inference entry points ignore them, and so
+        does the training path of a tower in eval mode."""
+        for rate in (image, text):
+            if not 0.0 <= float(rate) < 1.0:
+                raise ValueError(f"drop_path rate {rate} outside [0, 1)")
+        self.visual.transformer.set_drop_path(image)
+        self.transformer.set_drop_path(text)
 
     def set_grad_checkpointing(self, enable=True):
         """Activation recomputation on the training path (model.py:261-263 of the reference; its trainer's remat='full' per block):

@@ -23,9 +23,12 @@ width that is not a multiple of 64 (So400m) is zero-padded.
 """
 from __future__ import annotations
 
+import contextlib
+import ctypes
 import os
-from typing import List, Tuple
+from typing import List, Optional, Tuple
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -97,6 +100,132 @@ def _pool(transformer) -> _Pool:
     return pool
 
 
+def drop_path_rates(rate: float, layers: int) -> np.ndarray:
+    """The per-block drop rates of a tower of ``layers`` blocks: ``np.linspace(0, rate, layers)`` (vit.py:358,
+    text_transformer.py:533-536) -- block 0 never drops, the top block drops with ``rate``."""
+    rate = float(rate)
+    if not 0.0 <= rate < 1.0:
+        raise ValueError(f"drop_path rate {rate} outside [0, 1)")
+    return np.linspace(0, rate, int(layers))
+
+
+class DropPathTable:
+    """Which samples each residual branch of each block keeps in ONE training forward and its backward: ``keep`` bool [layers, 2, B]
+    on the host (branch 0 = attention, 1 = MLP) and ``scale`` fp32 [layers] = 1 / (1 - r_i), the factor of a kept sample's branch
+    (DropPath, common.py:659-675).  ``counts[i][j]`` kept samples; ``device_tables(device)`` -> int32 ``idx`` / ``slot`` [layers, 2, B]
+    on the device (``ov_tower_set_drop_path``'s layout: the kept samples' numbers first in ascending order, then the dropped ones';
+    ``slot`` the inverse, -1 for a dropped sample), made on first use from a pinned staging copy by an asynchronous upload: no host
+    synchronisation.  ``slice(lo, hi)``: the table of blocks [lo, hi), sharing the device arrays."""
+
+    def __init__(self, keep: torch.Tensor, scale: torch.Tensor):
+        if not isinstance(keep, torch.Tensor) or keep.dtype != torch.bool:
+            raise TypeError("keep must be a torch.bool tensor [layers, 2, batch]")
+        if keep.dim() != 3 or keep.shape[1] != 2 or keep.shape[0] < 1 or keep.shape[2] < 1:
+            raise ValueError(f"keep must be [layers, 2, batch], got {tuple(keep.shape)}")
+        scale = torch.as_tensor(scale, dtype=torch.float32).detach().cpu().reshape(-1)
+        if scale.shape[0] != keep.shape[0] or not bool(torch.isfinite(scale).all()) or not bool((scale > 0).all()):
+            raise ValueError("scale must hold one finite positive factor per layer")
+        self.keep = keep.detach().cpu().contiguous()
+        self.scale = scale.contiguous()
+        self.layers, _, self.batch = self.keep.shape
+        self.counts = self.keep.sum(dim=-1).tolist()
+        self._host = None
+        self._dev = {}
+        self._parent = None
+
+    def host_tables(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(idx, slot), int32 [layers, 2, B] on the host."""
+        if self._host is None:
+            idx = torch.argsort((~self.keep).to(torch.uint8), dim=-1, stable=True)
+            rank = torch.empty_like(idx).scatter_(-1, idx, torch.arange(self.batch).expand_as(idx).contiguous())
+            slot = torch.where(self.keep, rank, torch.full_like(rank, -1))
+            self._host = torch.stack([idx.to(torch.int32), slot.to(torch.int32)]).contiguous()
+        return self._host[0], self._host[1]
+
+    def device_tables(self, device) -> Tuple[torch.Tensor, torch.Tensor]:
+        device = torch.device(device)
+        if self._parent is not None:                          # a slice: rows [lo, hi) of the parent's arrays (contiguous views)
+            parent, lo, hi = self._parent
+            idx, slot = parent.device_tables(device)
+            return idx[lo:hi], slot[lo:hi]
+        dev = self._dev.get(device)
+        if dev is None:
+            self.host_tables()
+            if device.type == "cuda" and not self._host.is_pinned():
+                self._host = self._host.pin_memory()          # kept alive here: the copy below may still be reading it
+            dev = self._dev[device] = self._host.to(device, non_blocking=True)
+        return dev[0], dev[1]
+
+    def slice(self, lo: int, hi: int) -> "DropPathTable":
+        if lo == 0 and hi == self.layers:
+            return self
+        sub = DropPathTable(self.keep[lo:hi], self.scale[lo:hi])
+        sub._parent = (self, lo, hi)
+        return sub
+
+
+def drop_path_table(transformer, batch: int, generator: Optional[torch.Generator] = None, keep: Optional[torch.Tensor] = None,
+                    scale=None) -> Optional[DropPathTable]:
+    """The drop-path table of one forward of ``transformer`` over ``batch`` samples.  Without ``keep`` it is drawn as the reference
+    draws it (common.py:673-674): per block, branch and sample ``floor(keep_i + U)`` with ``U = torch.rand`` on the CPU (``generator``,
+    or the default one), ``keep_i = 1 - linspace(0, transformer.drop_path, layers)[i]``; a rate of 0 makes no table (None).  ``keep``
+    (bool [layers, 2, batch]) replaces the draw; ``scale`` ([layers], default 1 / keep_i) replaces the factors.  The masks are not
+    seed-compatible with the JAX reference's generator."""
+    layers = len(transformer.resblocks)
+    batch = int(batch)
+    if batch < 1:
+        raise ValueError("batch must be positive")
+    rates = drop_path_rates(getattr(transformer, "drop_path", 0.0), layers)
+    keep_p = torch.from_numpy(1.0 - rates).to(torch.float32)
+    if keep is None:
+        if rates[-1] == 0.0:
+            return None
+        u = torch.rand(layers, 2, batch, generator=generator)
+        keep = torch.floor(keep_p[:, None, None] + u) >= 1.0
+    else:
+        if not isinstance(keep, torch.Tensor) or keep.dtype != torch.bool:
+            raise TypeError("keep must be a torch.bool tensor [layers, 2, batch]")
+        if tuple(keep.shape) != (layers, 2, batch):
+            raise ValueError(f"keep must be [{layers}, 2, {batch}], got {tuple(keep.shape)}")
+    return DropPathTable(keep, 1.0 / keep_p if scale is None else scale)
+
+
+def _own_drop(transformer, batch: int, drop: Optional[DropPathTable]) -> Optional[DropPathTable]:
+    """The table a forward of ``transformer`` runs under: the caller's whatever the mode, else one drawn when the transformer is in
+    training mode with ``drop_path`` > 0, else none."""
+    if drop is not None:
+        if not isinstance(drop, DropPathTable):
+            raise TypeError("drop must be a training.DropPathTable (training.drop_path_table)")
+        if drop.layers != len(transformer.resblocks) or drop.batch != int(batch):
+            raise ValueError(f"drop table is [{drop.layers}, 2, {drop.batch}], the forward needs [{len(transformer.resblocks)}, 2, {batch}]")
+        return drop
+    if transformer.training and getattr(transformer, "drop_path", 0.0) > 0:
+        return drop_path_table(transformer, batch)
+    return None
+
+
+@contextlib.contextmanager
+def _drop_scope(lib, handle, drop: Optional[DropPathTable], bsz: int, seq: int, pool, device):
+    """The handle carries ``drop`` (``ov_tower_set_drop_path``, with its scratch from the pool) for the native calls made inside, and
+    no table again afterwards, on success and on error alike: the cached handle is shared with whoever runs this tower next."""
+    if drop is None:
+        yield
+        return
+    nbytes = lib.ov_tower_drop_path_workspace_bytes(handle, bsz, seq)
+    ws = pool.take(nbytes, device, "drop")
+    try:
+        idx, slot = drop.device_tables(device)
+        counts = (ctypes.c_int * (2 * drop.layers))(*[int(c) for row in drop.counts for c in row])
+        scales = (ctypes.c_float * drop.layers)(*drop.scale.tolist())
+        check(lib.ov_tower_set_drop_path(handle, ptr(idx), ptr(slot), counts, scales, bsz, ptr(ws), nbytes), "ov_tower_set_drop_path")
+        try:
+            yield
+        finally:
+            lib.ov_tower_set_drop_path(handle, None, None, None, None, 0, None, 0)
+    finally:
+        pool.give(ws)
+
+
 class _TowerFn(torch.autograd.Function):
     """Transformer.forward (transformer.py:355-366) as one autograd node over the blocks [lo, hi) (all of them by default; several
     consecutive nodes when ``tower_forward`` is asked for chunks, so that parameter gradients become available chunk by chunk).
@@ -124,8 +253,13 @@ class _TowerFn(torch.autograd.Function):
         return None, args[0], args[1:]
 
     @classmethod
+    def _drop(cls, args):
+        return None
+
+    @classmethod
     def forward(cls, ctx, transformer, lo, hi, *args):
         prefix, x, params = cls._split(args)
+        drop = cls._drop(args)
         ctx.nargs = cls.NARGS
         blocks = list(transformer.resblocks)[lo:hi]
         b0 = blocks[0]
@@ -156,12 +290,13 @@ class _TowerFn(torch.autograd.Function):
                 saved = pool.take(nsaved, x.device, "saved")
             if nslot:
                 slot = pool.take(nslot, x.device, kind)
-            if remat:
-                check(lib.ov_tower_forward_checkpointed(handle, first, ptr(xb), ptr(saved), ptr(slot), nslot, bsz, seq, stream_ptr()),
-                      "ov_tower_forward_checkpointed")
-            else:
-                check(lib.ov_tower_forward_saving_from(handle, first, ptr(xb), ptr(saved), bsz, seq, ptr(slot), nslot, stream_ptr()),
-                      "ov_tower_forward_saving_from")
+            with _drop_scope(lib, handle, drop, bsz, seq, pool, x.device):
+                if remat:
+                    check(lib.ov_tower_forward_checkpointed(handle, first, ptr(xb), ptr(saved), ptr(slot), nslot, bsz, seq, stream_ptr()),
+                          "ov_tower_forward_checkpointed")
+                else:
+                    check(lib.ov_tower_forward_saving_from(handle, first, ptr(xb), ptr(saved), bsz, seq, ptr(slot), nslot, stream_ptr()),
+                          "ov_tower_forward_saving_from")
         except BaseException:
             for t in (saved, slot):
                 if t is not None:
@@ -174,6 +309,7 @@ class _TowerFn(torch.autograd.Function):
         ctx.first, ctx.pairs, ctx.need = first, pairs, (need_x, need_p)                    # its weights and its mask
         ctx.saved_gen = saved._ovhip_gen if saved is not None else None
         ctx.remat, ctx.slot = remat, slot
+        ctx.drop = drop                       # the backward and its recompute run under the forward's table
         ctx.x_dtype, ctx.p_dtypes = x.dtype, [p.dtype for p in params]
         return xb.to(x.dtype)
 
@@ -202,12 +338,14 @@ class _TowerFn(torch.autograd.Function):
                 nslot = lib.ov_tower_slot_bytes(handle, bsz, seq)
                 if slot is None:
                     slot = pool.take(nslot, dx.device, "slot")
-                check(lib.ov_tower_backward_checkpointed(handle, first, ptr(ctx.saved), ptr(slot), nslot, int(holds), ptr(dx), garr,
-                                                         int(need_x), bsz, seq, ptr(ws), nbytes, stream_ptr()),
-                      "ov_tower_backward_checkpointed")
-            else:
-                check(lib.ov_tower_backward_partial(handle, first, ptr(ctx.saved), ptr(dx), garr, int(need_x), bsz, seq, ptr(ws), nbytes,
-                                                    stream_ptr()), "ov_tower_backward_partial")
+            with _drop_scope(lib, handle, ctx.drop, bsz, seq, pool, dx.device):
+                if ctx.remat:
+                    check(lib.ov_tower_backward_checkpointed(handle, first, ptr(ctx.saved), ptr(slot), nslot, int(holds), ptr(dx), garr,
+                                                             int(need_x), bsz, seq, ptr(ws), nbytes, stream_ptr()),
+                          "ov_tower_backward_checkpointed")
+                else:
+                    check(lib.ov_tower_backward_partial(handle, first, ptr(ctx.saved), ptr(dx), garr, int(need_x), bsz, seq, ptr(ws),
+                                                        nbytes, stream_ptr()), "ov_tower_backward_partial")
         finally:                              # on success and on error alike; ordered on the stream: the next forward's writes come
             for t in (slot, ws, ctx.saved):   # after this backward's reads
                 if t is not None:
@@ -232,6 +370,22 @@ class _PrefixTowerFn(_TowerFn):
     @classmethod
     def _split(cls, args):
         return int(args[0]), args[1], args[2:]
+
+
+class _DropTowerFn(_TowerFn):
+    """``_TowerFn`` under a drop-path table (and a prefix-causal mask, or None): apply(transformer, lo, hi, prefix, table, x, *params).
+    The table (``DropPathTable`` of the node's blocks) stays on the ctx: the backward, and under recomputation the rebuild of each
+    block's intermediates, run the forward's masks."""
+
+    NARGS = 5
+
+    @classmethod
+    def _split(cls, args):
+        return (None if args[0] is None else int(args[0])), args[2], args[3:]
+
+    @classmethod
+    def _drop(cls, args):
+        return args[1]
 
 
 class _LinearFn(torch.autograd.Function):
@@ -425,24 +579,32 @@ def set_backward_chunk_layers(n: int) -> None:
 _OWN = object()
 
 
-def tower_forward(transformer, x: torch.Tensor, prefix=_OWN) -> torch.Tensor:
+def tower_forward(transformer, x: torch.Tensor, prefix=_OWN, drop: Optional[DropPathTable] = None) -> torch.Tensor:
     """``transformer(x)`` with gradients: x [B, L, D] on the device -> same shape; d x and every block parameter receive grad.
     ``prefix``: the attention mask of every block -- by default the transformer's own ``causal_prefix``; None = unmasked; an int P =
-    key j visible to query i iff j < P or j <= i.  It is kept on the autograd node, so the backward uses the forward's value."""
+    key j visible to query i iff j < P or j <= i.  It is kept on the autograd node, so the backward uses the forward's value.
+
+    ``drop``: the drop-path table of this forward (``drop_path_table``), used whatever the mode; by default one is drawn when the
+    transformer is in training mode with ``drop_path`` > 0.  Each branch of each block then runs on its kept samples only."""
     if prefix is _OWN:
         prefix = getattr(transformer, "causal_prefix", None)
     if not x.is_cuda:
         raise _lib.OvhipError("training path: tensors must live on an MI355X device (no CPU fallback)")
     blocks = list(transformer.resblocks)
+    drop = _own_drop(transformer, x.shape[0], drop)
     step = CHUNK_LAYERS[0] if CHUNK_LAYERS[0] > 0 else len(blocks)
     for lo in range(0, len(blocks), step):
         hi = min(len(blocks), lo + step)
         params = [p for blk in blocks[lo:hi] for p in _block_tensors(blk)]
-        x = _TowerFn.apply(transformer, lo, hi, x, *params) if prefix is None else _PrefixTowerFn.apply(transformer, lo, hi, prefix, x, *params)
+        if drop is not None:
+            x = _DropTowerFn.apply(transformer, lo, hi, prefix, drop.slice(lo, hi), x, *params)
+        else:
+            x = _TowerFn.apply(transformer, lo, hi, x, *params) if prefix is None else _PrefixTowerFn.apply(transformer, lo, hi, prefix, x, *params)
     return x
 
 
-def encode_image(model, image: torch.Tensor, normalize: bool = True, keep: torch.Tensor = None, output_tokens: bool = False):
+def encode_image(model, image: torch.Tensor, normalize: bool = True, keep: torch.Tensor = None, output_tokens: bool = False,
+                 drop: Optional[DropPathTable] = None):
     """CLIP.encode_image (model.py:265-267) with gradients.  VisionTransformer.forward, transformer.py:609-651: the OpenVision
     configuration (no ln_pre, pool -> ln_post -> proj) and the stock one (ln_pre, ln_post -> 'tok' pool -> proj).
 
@@ -452,7 +614,9 @@ def encode_image(model, image: torch.Tensor, normalize: bool = True, keep: torch
     a table is checked on the device and the flag read back (one host synchronisation), a bad one raises IndexError.
 
     ``output_tokens``: also return what the reference hands to the caption decoder (vit.py:753,786): the block stack's output without
-    the CLS token and BEFORE ln_post, [B, L - 1, width] (the kept patches under patch dropout), with gradients into the tower."""
+    the CLS token and BEFORE ln_post, [B, L - 1, width] (the kept patches under patch dropout), with gradients into the tower.
+
+    ``drop``: the image tower's drop-path table (``tower_forward``)."""
     v = model.visual
     p = v.patch_size[0]
     w = v.conv1.weight
@@ -478,7 +642,7 @@ def encode_image(model, image: torch.Tensor, normalize: bool = True, keep: torch
         x = _patch_tokens_eager(image, p, w, v.class_embedding, v.positional_embedding)
     if not isinstance(v.ln_pre, torch.nn.Identity):                # :620, after the patch dropout: on the kept tokens only
         x = _LayerNormFn.apply(x, v.ln_pre.weight, v.ln_pre.bias, v.ln_pre.eps)
-    x = tower_forward(v.transformer, x)
+    x = tower_forward(v.transformer, x, drop=drop)
     tokens = x[:, 1:]
     if v.final_ln_after_pool:
         pooled = x[:, 1:].mean(dim=1) if v.pool_type == "avg" else x[:, 0]
@@ -491,12 +655,14 @@ def encode_image(model, image: torch.Tensor, normalize: bool = True, keep: torch
     return (out, tokens) if output_tokens else out
 
 
-def encode_text_embeddings(model, x: torch.Tensor, normalize: bool = True, pool_index=None, output_tokens: bool = False):
+def encode_text_embeddings(model, x: torch.Tensor, normalize: bool = True, pool_index=None, output_tokens: bool = False,
+                           drop: Optional[DropPathTable] = None):
     """The text tower from token EMBEDDINGS x [B, T, width] (before the positional embedding), with gradients to x: the entry of
     ov-gradient-ascent.py:102-127, which feeds `soft_one_hot @ token_embedding.weight` instead of token ids.  `pool_index` (int64 [B])
-    selects the pooled position for text_pool_type 'argmax' (ids are not available here)."""
+    selects the pooled position for text_pool_type 'argmax' (ids are not available here).  ``drop``: the text tower's drop-path table
+    (``tower_forward``)."""
     x = x.float() + model.positional_embedding.float()[: x.shape[1]]
-    x = tower_forward(model.transformer, x)
+    x = tower_forward(model.transformer, x, drop=drop)
     tokens = x[:, :-1]             # output_tokens: the stack's output without its last position, before ln_final (text_transformer.py:676-682)
     x = _LayerNormFn.apply(x, model.ln_final.weight, model.ln_final.bias, model.ln_final.eps)
     pool = getattr(model, "text_pool_type", "last")
@@ -515,19 +681,20 @@ def encode_text_embeddings(model, x: torch.Tensor, normalize: bool = True, pool_
     return (out, tokens) if output_tokens else out
 
 
-def encode_text(model, text: torch.Tensor, normalize: bool = True, output_tokens: bool = False):
+def encode_text(model, text: torch.Tensor, normalize: bool = True, output_tokens: bool = False, drop: Optional[DropPathTable] = None):
     """CLIP.encode_text (model.py:269-284) with gradients: the tower's own mask (none for OpenVision; causal for a stock open_clip
     config, whose ``CLIP`` sets ``transformer.causal_prefix = 0``), ln_final on all tokens, pool per text_pool_type ('argmax': the row
     of each caption's largest id, ``text.argmax(-1)``, the first of equals as on the inference path).  `text`: int64
     token ids [B, T], or a float [B, T, vocab] matrix of (soft) one-hot rows (ov-gradient-ascent.py:105: `text @ token_embedding.weight`,
-    gradients flow to the rows)."""
+    gradients flow to the rows).  ``drop``: the text tower's drop-path table (``tower_forward``); with C caption sets stacked its batch
+    is C B."""
     if text.is_floating_point():
         if text.dim() != 3 or text.shape[-1] != model.token_embedding.weight.shape[0]:
             raise ValueError("soft tokens must be [B, T, vocab_size]")
         return encode_text_embeddings(model, text.float() @ model.token_embedding.weight.float(), normalize,
-                                      text.argmax(dim=-1).argmax(dim=-1), output_tokens)
+                                      text.argmax(dim=-1).argmax(dim=-1), output_tokens, drop=drop)
     x = F.embedding(text, model.token_embedding.weight.float())
-    return encode_text_embeddings(model, x, normalize, text.argmax(dim=-1), output_tokens)
+    return encode_text_embeddings(model, x, normalize, text.argmax(dim=-1), output_tokens, drop=drop)
 
 
 def caption_sets(image: torch.Tensor, text: torch.Tensor) -> int:
@@ -539,26 +706,47 @@ def caption_sets(image: torch.Tensor, text: torch.Tensor) -> int:
     return nt // nb
 
 
-def clip_forward(model, image: torch.Tensor, text: torch.Tensor, keep: torch.Tensor = None) -> Tuple[torch.Tensor, ...]:
+def _drop_pair(drop, n: int = 2):
+    """``drop`` of the model-level entry points: None, or one table (or None) per tower."""
+    if drop is None:
+        return (None,) * n
+    drop = tuple(drop)
+    if not 2 <= len(drop) <= n:
+        raise ValueError(f"drop must be a pair (image_table, text_table){' or a triple with the decoder table' if n > 2 else ''}")
+    return drop + (None,) * (n - len(drop))
+
+
+def _drop_kw(table) -> dict:
+    """The ``drop=`` keyword of a tower-level entry point, passed only when there is a table (as ``keep`` is)."""
+    return {} if table is None else {"drop": table}
+
+
+def clip_forward(model, image: torch.Tensor, text: torch.Tensor, keep: torch.Tensor = None, drop=None) -> Tuple[torch.Tensor, ...]:
     """CLIP.forward (model.py:295-315) with gradients: (image_features, text_features, logit_scale.exp()), and ``logit_bias`` (the
     parameter itself, so its gradient flows) as a fourth element when the model has one (SigLIP).  Patch dropout as in
     ``encode_image`` (drawn when the vision tower is in training mode with p > 0; ``keep`` overrides the draw, as there).
 
     ``text`` may stack C caption sets per image as [C B, T]: the text tower runs once on all rows and ``text_features`` is [C B, E],
-    the input of ``MultiCaptionClipLoss(num_captions=C)``."""
+    the input of ``MultiCaptionClipLoss(num_captions=C)``.
+
+    ``drop``: a pair ``(image_table, text_table)`` of drop-path tables (``drop_path_table``; either may be None), used whatever the
+    mode; by default each tower in training mode with ``drop_path`` > 0 draws its own (``CLIP.set_drop_path``)."""
     caption_sets(image, text)
     kw = {} if keep is None else {"keep": keep}
-    out = (encode_image(model, image, True, **kw), encode_text(model, text, True), model.logit_scale.exp())
+    drop_i, drop_t = _drop_pair(drop)
+    out = (encode_image(model, image, True, **kw, **_drop_kw(drop_i)), encode_text(model, text, True, **_drop_kw(drop_t)),
+           model.logit_scale.exp())
     if getattr(model, "logit_bias", None) is not None:
         return out + (model.logit_bias,)
     return out
 
 
-def decode(decoder, image_tokens: torch.Tensor, text_tokens: torch.Tensor) -> torch.Tensor:
+def decode(decoder, image_tokens: torch.Tensor, text_tokens: torch.Tensor, drop: Optional[DropPathTable] = None) -> torch.Tensor:
     """``caption.TextDecoder.forward`` with gradients (text_decoder.py:436-576, concat fusion): bias-free projections of both token
     sets (``_LinearFn``), ``[image | text | learnable]`` through the decoder's blocks under the prefix-LM mask with prefix =
     L_image + L_text (``tower_forward``), the last T_out positions through ``decoder_norm`` (``_LayerNormFn``) and the bias-free
-    vocabulary head (``_LinearFn``) -> fp32 logits [B, T_out, vocab].  Gradients reach the decoder's parameters and both inputs."""
+    vocabulary head (``_LinearFn``) -> fp32 logits [B, T_out, vocab].  Gradients reach the decoder's parameters and both inputs.
+    ``drop``: the decoder stack's drop-path table (``tower_forward``)."""
     bsz, li, _ = image_tokens.shape
     lt = text_tokens.shape[1]
     w = decoder.width
@@ -566,13 +754,13 @@ def decode(decoder, image_tokens: torch.Tensor, text_tokens: torch.Tensor) -> to
     xt = _LinearFn.apply(text_tokens.reshape(bsz * lt, -1), decoder.text_projection.weight, None).view(bsz, lt, w)
     lr = decoder.learnable_tokens.float().unsqueeze(0).expand(bsz, -1, -1)
     x = torch.cat([xi, xt, lr], dim=1)
-    x = tower_forward(decoder.transformer, x, prefix=li + lt)
+    x = tower_forward(decoder.transformer, x, prefix=li + lt, drop=drop)
     n = decoder.num_learnable_tokens
     y = _LayerNormFn.apply(x[:, -n:].contiguous(), decoder.decoder_norm.weight, decoder.decoder_norm.bias, decoder.decoder_norm.eps)
     return _LinearFn.apply(y.reshape(bsz * n, w), decoder.head.weight, None).view(bsz, n, -1)
 
 
-def coca_forward(model, decoder, image: torch.Tensor, text: torch.Tensor, keep: torch.Tensor = None):
+def coca_forward(model, decoder, image: torch.Tensor, text: torch.Tensor, keep: torch.Tensor = None, drop=None):
     """The reference trainer's 'coca' forward (src/main_clip.py:448-465): both towers once, their features for the contrastive loss
     and their tokens through the caption decoder -> (image_features, text_features, logit_scale.exp(), caption_logits).
 
@@ -588,14 +776,16 @@ def coca_forward(model, decoder, image: torch.Tensor, text: torch.Tensor, keep: 
         img_f, txt_f, scale, cap = training.coca_forward(model, decoder, images, tokens)
         loss = ClipLoss()(img_f, txt_f, scale) + 2 * CaptionLoss()(cap, labels, mask)
 
-    ``keep`` overrides the patch-dropout draw, as in ``encode_image``."""
+    ``keep`` overrides the patch-dropout draw, as in ``encode_image``.  ``drop``: ``(image_table, text_table)`` or ``(image_table,
+    text_table, decoder_table)`` of drop-path tables, as in ``clip_forward``."""
     sets = caption_sets(image, text)
     kw = {} if keep is None else {"keep": keep}
-    img_f, img_tok = encode_image(model, image, True, output_tokens=True, **kw)
-    txt_f, txt_tok = encode_text(model, text, True, output_tokens=True)
+    drop_i, drop_t, drop_d = _drop_pair(drop, 3)
+    img_f, img_tok = encode_image(model, image, True, output_tokens=True, **kw, **_drop_kw(drop_i))
+    txt_f, txt_tok = encode_text(model, text, True, output_tokens=True, **_drop_kw(drop_t))
     if sets > 1:
         txt_tok = txt_tok[:image.shape[0]]
-    return img_f, txt_f, model.logit_scale.exp(), decode(decoder, img_tok, txt_tok)
+    return img_f, txt_f, model.logit_scale.exp(), decode(decoder, img_tok, txt_tok, **_drop_kw(drop_d))
 
 
 def accumulated_step(model, batches, loss, decoder=None, caption_targets=None, caption_weight: float = 2.0,
@@ -613,8 +803,8 @@ def accumulated_step(model, batches, loss, decoder=None, caption_targets=None, c
               forward.
 
     ``decoder`` (a ``caption.TextDecoder``): pass 2 runs ``coca_forward`` and adds ``caption_weight * CaptionLoss()(logits, labels_j,
-    mask_j) / A`` to window j's loss, ``caption_targets[j] = (labels, mask)``.  Patch dropout: one draw per micro-batch, made before
-    pass 1 and used by both passes.  Recomputation, frozen parameters and ``lock_image_tower`` work as in a one-batch step.
+    mask_j) / A`` to window j's loss, ``caption_targets[j] = (labels, mask)``.  Patch dropout and drop path: one draw per micro-batch
+    (and tower), made before pass 1 and used by both passes.  Recomputation, frozen parameters and ``lock_image_tower`` work as in a one-batch step.
     ``check=True`` verifies that pass 2 recomputed pass 1's features bitwise (one host synchronisation per micro-batch).
 
     The optimiser is not touched: call ``FusedAdamW.zero_grad(windows=A)`` before and ``all_reduce_gradients`` / ``step`` after."""
@@ -627,20 +817,21 @@ def accumulated_step(model, batches, loss, decoder=None, caption_targets=None, c
     acc = ContrastiveAccumulator(loss)
     v = model.visual
     keeps = [v.patch_dropout.sample(image.shape[0], v.num_patches) if v.dropout_active() else None for image, _ in batches]
+    drops = [(_own_drop(v.transformer, image.shape[0], None), _own_drop(model.transformer, text.shape[0], None)) for image, text in batches]
     with torch.no_grad():
-        for (image, text), keep in zip(batches, keeps):
-            img_f, txt_f = clip_forward(model, image, text, keep=keep)[:2]
+        for (image, text), keep, drop in zip(batches, keeps, drops):
+            img_f, txt_f = clip_forward(model, image, text, keep=keep, drop=drop)[:2]
             acc.add(img_f, txt_f)
         total = acc.close(model.logit_scale.exp()).clone()
     if decoder is not None:
         from .caption import CaptionLoss
         cap_loss = CaptionLoss()
-    for j, ((image, text), keep) in enumerate(zip(batches, keeps)):
+    for j, ((image, text), keep, drop) in enumerate(zip(batches, keeps, drops)):
         if decoder is None:
-            img_f, txt_f, scale = clip_forward(model, image, text, keep=keep)[:3]
+            img_f, txt_f, scale = clip_forward(model, image, text, keep=keep, drop=drop)[:3]
             part = acc.window_loss(j, img_f, txt_f, scale, check=check)
         else:
-            img_f, txt_f, scale, cap = coca_forward(model, decoder, image, text, keep=keep)
+            img_f, txt_f, scale, cap = coca_forward(model, decoder, image, text, keep=keep, drop=drop)
             labels, mask = caption_targets[j]
             cpart = caption_weight * cap_loss(cap, labels, mask) / len(batches)
             total += cpart.detach()

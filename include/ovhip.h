@@ -616,6 +616,29 @@ int ov_attention_prefix_backward(const ov_bf16* qkv, int64_t ld_qkv, const ov_bf
                                  int64_t ld_dout, ov_bf16* dqkv, int64_t ld_dqkv, int B, int L, int H, int hd, float scale, int prefix,
                                  void* workspace, size_t workspace_bytes, ov_stream_t stream);
 
+/* ---- attentional pooling (attn_pool.hip): cross-attention from n_q projected queries, shared by every image, to the L keys of each
+ * image: out[b] = softmax(scale q k_b^T) v_b.  q [n_q, H*hd] has no batch stride; kv [B*L, 2*H*hd] holds the k | v column blocks with
+ * heads contiguous inside each (the K/V projection GEMM's output); out [B*n_q, H*hd] has heads merged (the out-proj GEMM's operand).
+ * lse (or NULL): [B*H][n_q rounded up to 32] fp32 row log-sum-exp in log2 units, entries [0, n_q) of each row written, for the
+ * backward.  Same arithmetic as ov_attention (fp32 scores in log2 units, online softmax with the lazy rescale, P rounded to bf16).
+ * hd % 8 == 0 and hd <= 96 (zero-padded in LDS), 1 <= n_q <= 256: OV_ERR_UNSUPPORTED otherwise.  B, L, H >= 1, every row pitch a
+ * multiple of 8 and at least as wide as its row, every bf16 pointer 16-byte aligned, lse 4-byte: OV_ERR_INVALID otherwise.  Nothing
+ * is launched on an error. */
+int ov_attn_pool(const ov_bf16* q, int64_t ld_q, const ov_bf16* kv, int64_t ld_kv, ov_bf16* out, int64_t ld_out, float* lse, int B, int L,
+                 int n_q, int H, int hd, float scale, ov_stream_t stream);
+/* Backward of ov_attn_pool: from q, kv, the forward's out and lse (required) and the upstream dout [B*n_q, H*hd] it writes
+ * dkv [B*L, 2*H*hd] = (dK | dV) in bf16 and dq [n_q, H*hd] in fp32 = the sum over the B images.  Three launches: the dQ pass (a
+ * workgroup walks a fixed chunk of images in order and keeps their sum in its accumulators; it also writes delta), the dK / dV pass,
+ * and the sum of the chunks' partials in chunk order.  No atomics; the chunk (ov_attn_pool_backward_chunk) depends on n_q alone, so
+ * the result depends on the shape only and repeats bitwise.  workspace: ov_attn_pool_backward_workspace_bytes bytes (delta and the
+ * partials), 16-byte aligned; OV_ERR_WORKSPACE if short.  ld_dq a multiple of 4 floats, dq 16-byte aligned.  Otherwise the checks of
+ * ov_attn_pool. */
+size_t ov_attn_pool_backward_workspace_bytes(int B, int L, int n_q, int H, int hd);
+int ov_attn_pool_backward_chunk(int n_q);     /* images per dQ partial */
+int ov_attn_pool_backward(const ov_bf16* q, int64_t ld_q, const ov_bf16* kv, int64_t ld_kv, const ov_bf16* out, int64_t ld_out,
+                          const ov_bf16* dout, int64_t ld_dout, const float* lse, float* dq, int64_t ld_dq, ov_bf16* dkv, int64_t ld_dkv,
+                          int B, int L, int n_q, int H, int hd, float scale, void* workspace, size_t workspace_bytes, ov_stream_t stream);
+
 /* da = dh * gelu'(a) on the pre-activation a [rows, N] (tanh_form = 0: exact erf GELU, vision; 1: tanh form, text).  N % 8 == 0.
  * h_out (optional) receives gelu(a).  da may alias dh and h_out may alias a (element-wise, in place). */
 int ov_gelu_backward(const ov_bf16* a, int64_t lda, const ov_bf16* dh, int64_t lddh, ov_bf16* da, int64_t ldda, ov_bf16* h_out,

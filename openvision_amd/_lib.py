@@ -184,6 +184,12 @@ SIGNATURES = {
     "ov_attention_backward_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "ov_attention_backward": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_int,
                                       c_float, c_void_p, c_size_t, c_void_p]),
+    "ov_attn_pool": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float,
+                             c_void_p]),
+    "ov_attn_pool_backward_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "ov_attn_pool_backward_chunk": (c_int, [c_int]),
+    "ov_attn_pool_backward": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
+                                      c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_size_t, c_void_p]),
     "ov_transpose_bf16": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_int64, c_void_p]),
     "ov_linear_backward_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
     "ov_linear_backward_plan": (c_int, [c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p]),

@@ -4,9 +4,10 @@ Mirrors the dataclasses the reference builds its towers from
 (``src/convert_upload/open_clip/model.py:27-84`` ``CLIPVisionCfg`` / ``CLIPTextCfg``) and the
 size tables of the JAX->HF converter (``src/convert_upload/transfer_jax2hf.py:76-92``).
 Only the fields the encode-and-contrast path reads are kept: the OpenVision towers and the stock
-open_clip ones (causal text with 'argmax' pooling, ln_pre, 'tok' pooling).  Anything that would
-select a different architecture (attentional pooling, timm/HF towers, quick_gelu, layer-scale,
-embed_cls, proj_bias) is rejected loudly instead of being silently ignored.
+open_clip ones (causal text with 'argmax' pooling, ln_pre, 'tok' pooling).  ``vision_cfg.attentional_pool=True``
+(the open_clip CoCa image pooler, with ``attn_pooler_queries`` / ``attn_pooler_heads``) is built; its string forms are not.  Anything
+that would select a different architecture (timm/HF towers, quick_gelu, layer-scale, embed_cls, proj_bias) is rejected loudly instead
+of being silently ignored.
 
 ``vision_cfg.pos_embed_type`` selects the image position table (``openvision_amd.posembed``):
 
@@ -38,6 +39,8 @@ class CLIPVisionCfg:
     ls_init_value: Optional[float] = None
     patch_dropout: float = 0.0
     attentional_pool: bool = False
+    attn_pooler_queries: int = 256
+    attn_pooler_heads: int = 8
     no_ln_pre: bool = False
     pos_embed_type: str = "learnable"
     final_ln_after_pool: bool = False
@@ -88,11 +91,39 @@ def _from_dict(cls, d: Union[dict, Any]):
     return cls(**{k: v for k, v in d.items() if k in known})
 
 
-def vision_cfg_from(d) -> CLIPVisionCfg:
+def attn_pool_head_dim(embed_dim: int, heads: int) -> int:
+    """Head dim of the attentional pooler (AttentionalPooler(d_model=embed_dim, n_head=heads), transformer.py:187-207), checked
+    against what ``ov_attn_pool`` takes: a multiple of 8, at most 96."""
+    if heads <= 0 or embed_dim % heads:
+        raise ValueError(f"attentional pool: embed_dim {embed_dim} must be a multiple of attn_pooler_heads {heads}")
+    hd = embed_dim // heads
+    if hd % 8 or hd > 96:
+        raise ValueError(f"attentional pool: head dim {hd} (embed_dim {embed_dim} / attn_pooler_heads {heads}) must be a multiple "
+                         f"of 8 and at most 96")
+    return hd
+
+
+def vision_cfg_from(d, embed_dim: Optional[int] = None) -> CLIPVisionCfg:
+    """``embed_dim`` (the model's, when the caller knows it) lets the pooler's head dim be checked here."""
     c = _from_dict(CLIPVisionCfg, d)
-    if c.timm_model_name or c.attentional_pool or c.ls_init_value is not None:
-        raise ValueError("vision_cfg selects a tower outside the OpenVision ViT path "
-                         "(timm / attentional pool / layer-scale)")
+    if c.timm_model_name or c.ls_init_value is not None:
+        raise ValueError("vision_cfg selects a tower outside the OpenVision ViT path (timm / layer-scale)")
+    if c.attentional_pool:
+        if c.attentional_pool is not True:
+            # the reference's 'parallel' / 'cascade' string forms: "untested, WIP" there (transformer.py:626-634)
+            raise ValueError(f"vision attentional_pool={c.attentional_pool!r}: only the bool form (the open_clip CoCa pooler) is built")
+        if c.final_ln_after_pool:
+            # the reference does not consult the flag on the pooled branch (transformer.py:636-640: ln_post always runs on the pooler's
+            # rows, before 'tok' / 'avg'); a config that asks for both would be silently given something else, so it is refused.  No
+            # open_clip coca_* config sets it; an OpenVision preset (final_ln_after_pool=true) needs it switched off with the pooler
+            raise ValueError("vision attentional_pool=true with final_ln_after_pool=true: the pooled branch applies ln_post to the "
+                             "pooler's rows before pooling, whatever the flag says; set final_ln_after_pool=false")
+        if not 1 <= int(c.attn_pooler_queries) <= 256:
+            raise ValueError(f"vision attn_pooler_queries must lie in [1, 256], got {c.attn_pooler_queries!r}")
+        if int(c.attn_pooler_heads) < 1:
+            raise ValueError(f"vision attn_pooler_heads must be positive, got {c.attn_pooler_heads!r}")
+        if embed_dim is not None:
+            attn_pool_head_dim(int(embed_dim), int(c.attn_pooler_heads))
     if not 0 <= float(c.patch_dropout) < 1:                      # PatchDropout's own assertion (transformer.py:56)
         raise ValueError(f"vision patch_dropout must lie in [0, 1), got {c.patch_dropout!r}")
     if c.pool_type not in ("avg", "tok"):

@@ -33,7 +33,7 @@ from . import _lib
 from ._lib import OV_BF16, OV_F32, EPI_BIAS, EPI_GELU_ERF, EPI_GELU_TANH, EPI_RESIDUAL, ptr, stream_ptr, check
 from . import posembed
 from .config import (CLIPVisionCfg, CLIPTextCfg, POS_EMBED_TYPES, vision_cfg_from, text_cfg_from, gelu_is_tanh, ln_eps,
-                     mlp_width)
+                     mlp_width, attn_pool_head_dim)
 
 MAX_MICRO_BATCH = 1024          # encode_* split larger batches so the workspace stays bounded
 
@@ -253,6 +253,116 @@ class MultiheadAttention(nn.Module):
         return self._pk.get((self.in_proj_weight, self.in_proj_bias),
                             lambda: (_pack_matrix(self.in_proj_weight, 3 * d, _round_up(d, 64)),
                                      _pack_vec(self.in_proj_bias, 3 * d, self.in_proj_weight.device)))
+
+
+class PoolAttention(nn.Module):
+    """Parameter layout of ``nn.MultiheadAttention(embed_dim, num_heads, kdim=kdim, vdim=kdim, batch_first=True)``: the packed
+    ``in_proj_weight`` [3E, E] when kdim == embed_dim, else ``q_proj_weight`` [E, E], ``k_proj_weight`` and ``v_proj_weight`` [E, kdim];
+    ``in_proj_bias`` [3E] and ``out_proj`` in both.  The layout not in use is registered as None, as torch does."""
+
+    def __init__(self, embed_dim: int, num_heads: int, kdim: int):
+        super().__init__()
+        self.embed_dim, self.num_heads, self.head_dim, self.kdim = embed_dim, num_heads, embed_dim // num_heads, kdim
+        self.batch_first = True
+        self._qkv_same_embed_dim = kdim == embed_dim
+        if self._qkv_same_embed_dim:
+            self.in_proj_weight = nn.Parameter(torch.empty(3 * embed_dim, embed_dim))
+            nn.init.normal_(self.in_proj_weight, std=embed_dim ** -0.5)
+            for n in ("q_proj_weight", "k_proj_weight", "v_proj_weight"):
+                self.register_parameter(n, None)
+        else:
+            self.q_proj_weight = nn.Parameter(torch.empty(embed_dim, embed_dim))
+            self.k_proj_weight = nn.Parameter(torch.empty(embed_dim, kdim))
+            self.v_proj_weight = nn.Parameter(torch.empty(embed_dim, kdim))
+            for w in (self.q_proj_weight, self.k_proj_weight, self.v_proj_weight):
+                nn.init.normal_(w, std=w.shape[1] ** -0.5)
+            self.register_parameter("in_proj_weight", None)
+        self.in_proj_bias = nn.Parameter(torch.zeros(3 * embed_dim))
+        self.out_proj = Linear(embed_dim, embed_dim, bias=True)
+
+    def weight_params(self):
+        return (self.in_proj_weight,) if self._qkv_same_embed_dim else (self.q_proj_weight, self.k_proj_weight, self.v_proj_weight)
+
+    def q_weight(self) -> torch.Tensor:
+        """[E, E]: the query projection (a view of the packed matrix in that layout)."""
+        return self.in_proj_weight[: self.embed_dim] if self._qkv_same_embed_dim else self.q_proj_weight
+
+    def kv_weight(self) -> torch.Tensor:
+        """[2E, kdim]: the key rows above the value rows, the K | V column blocks ``ov_attn_pool`` reads."""
+        if self._qkv_same_embed_dim:
+            return self.in_proj_weight[self.embed_dim:]
+        return torch.cat([self.k_proj_weight, self.v_proj_weight], dim=0)
+
+
+class AttentionalPooler(nn.Module):
+    """transformer.py:187-207: ``n_queries`` learned queries, shared by every image, attend to the tokens of each image:
+    ``MultiheadAttention(d_model, n_head, kdim=context_dim)(ln_q(query) expanded over B, ln_k(x), ln_k(x))`` -> [B, n_queries, d_model].
+    Both LayerNorms have the class default eps 1e-5, whatever the tower's ``norm_kwargs`` say (the reference passes them none).
+
+    The parameters and their state-dict names are the reference's, in both layouts of ``nn.MultiheadAttention`` (``PoolAttention``).
+    On the HIP path: ln_k and the K | V projection GEMM over all tokens, ``ov_attn_pool``, the out_proj GEMM.  The projected queries
+    ``ln_q(query) Wq^T + bq`` do not depend on the input: they are computed once and cached with the packed weights (``_Packed``)."""
+
+    def __init__(self, d_model: int, context_dim: int, n_head: int = 8, n_queries: int = 256):
+        super().__init__()
+        attn_pool_head_dim(d_model, n_head)
+        if not 1 <= n_queries <= 256:
+            raise ValueError(f"attentional pool: n_queries {n_queries} outside [1, 256]")
+        if context_dim % 64:
+            raise ValueError(f"attentional pool: context width {context_dim} must be a multiple of 64")
+        self.query = nn.Parameter(torch.randn(n_queries, d_model))
+        self.attn = PoolAttention(d_model, n_head, context_dim)
+        self.ln_q = LayerNorm(d_model, eps=1e-5)
+        self.ln_k = LayerNorm(context_dim, eps=1e-5)
+        self._pk = _Packed()
+        self._ws = _Workspace()
+
+    def packed(self):
+        """(projected queries [n_q, E] bf16, K | V weight [2E, context] bf16, K | V bias [2E] fp32, out_proj weight [E, E padded to 64]
+        bf16, out_proj bias fp32)."""
+        a = self.attn
+        e, nq = a.embed_dim, self.query.shape[0]
+        kp = _round_up(e, 64)
+
+        def build():
+            lib, st, dev = _lib.load(), stream_ptr(), self.query.device
+            g, b = self.ln_q.packed()
+            qsrc = self.query.detach().float().contiguous()
+            qn = torch.zeros(nq, kp, dtype=torch.bfloat16, device=dev)
+            check(lib.ov_layernorm(ptr(qsrc), OV_F32, e, ptr(g), ptr(b), ptr(qn), OV_BF16, kp, nq, e, float(self.ln_q.eps), st), "ov_layernorm(ln_q)")
+            bias = a.in_proj_bias.detach().float()
+            wq = _pack_matrix(a.q_weight(), e, kp)
+            qp = torch.empty(nq, e, dtype=torch.bfloat16, device=dev)
+            _gemm_bias(ptr(qn), kp, ptr(wq), kp, ptr(bias[:e].contiguous()), ptr(qp), e, nq, e, kp, st, "ov_gemm(pool q)")
+            wkv = _pack_matrix(a.kv_weight(), 2 * e, a.kdim)
+            wo, bo = a.out_proj.packed(e, kp)
+            return qp, wkv, bias[e:].contiguous(), wo, bo
+        return self._pk.get((self.query, self.ln_q.weight, self.ln_q.bias, *a.weight_params(), a.in_proj_bias, a.out_proj.weight,
+                             a.out_proj.bias), build)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        """x [B, L, context_dim] (any L >= 1) -> [B, n_queries, d_model] bf16."""
+        _require_cuda(x, "AttentionalPooler")
+        a = self.attn
+        if x.dim() != 3 or x.shape[2] != a.kdim:
+            raise ValueError(f"expected [batch, tokens, {a.kdim}], got {tuple(x.shape)}")
+        lib, st = _lib.load(), stream_ptr()
+        bsz, seq, d = x.shape
+        e, nq, kp = a.embed_dim, self.query.shape[0], _round_up(a.embed_dim, 64)
+        qp, wkv, bkv, wo, bo = self.packed()
+        xb = x.detach().to(torch.bfloat16).contiguous().view(bsz * seq, d)
+        g, b = self.ln_k.packed()
+        xk = torch.empty_like(xb)
+        check(lib.ov_layernorm(ptr(xb), OV_BF16, d, ptr(g), ptr(b), ptr(xk), OV_BF16, d, bsz * seq, d, float(self.ln_k.eps), st), "ov_layernorm(ln_k)")
+        kv = torch.empty(bsz * seq, 2 * e, dtype=torch.bfloat16, device=x.device)
+        _gemm_bias(ptr(xk), d, ptr(wkv), d, ptr(bkv), ptr(kv), 2 * e, bsz * seq, 2 * e, d, st, "ov_gemm(pool kv)")
+        # the out_proj GEMM reads rows padded to its 64-column granule: ov_attn_pool writes into the wider pitch
+        o = torch.zeros(bsz * nq, kp, dtype=torch.bfloat16, device=x.device) if kp != e else torch.empty(bsz * nq, e, dtype=torch.bfloat16, device=x.device)
+        check(lib.ov_attn_pool(ptr(qp), e, ptr(kv), 2 * e, ptr(o), kp, None, bsz, seq, nq, a.num_heads, a.head_dim, a.head_dim ** -0.5, st),
+              "ov_attn_pool")
+        y = torch.empty(bsz * nq, e, dtype=torch.bfloat16, device=x.device)
+        _gemm_bias(ptr(o), kp, ptr(wo), kp, ptr(bo), ptr(y), e, bsz * nq, e, kp, st, "ov_gemm(pool out_proj)")
+        return y.view(bsz, nq, e)
 
 
 class PatchConv(nn.Module):
@@ -676,12 +786,16 @@ def keep_to_device(keep: torch.Tensor, device) -> torch.Tensor:
 
 
 class VisionTransformer(nn.Module):
-    """transformer.py:434-651 restricted to what OpenVision instantiates (no attentional pool)."""
+    """transformer.py:434-651 restricted to what OpenVision and the stock open_clip towers instantiate, the bool form of
+    ``attentional_pool`` (the open_clip CoCa pooler) included: then ``attn_pool`` is an ``AttentionalPooler`` over all tokens of the
+    block stack, ``ln_post`` and ``proj`` have ``output_dim`` rows, and ``final_ln_after_pool`` is not consulted (:636-640;
+    ``config.vision_cfg_from`` refuses the pooler together with ``final_ln_after_pool=true``)."""
 
     def __init__(self, image_size: int, patch_size: int, width: int, layers: int, heads: int, mlp_ratio: float,
                  output_dim: int, pool_type: str = "avg", final_ln_after_pool: bool = True, no_ln_pre: bool = True,
                  act_kwargs: Optional[dict] = None, eps: float = 1e-6, output_tokens: bool = False,
-                 patch_dropout: float = 0.0, pos_embed_type: str = "learnable"):
+                 patch_dropout: float = 0.0, pos_embed_type: str = "learnable", attentional_pool: bool = False,
+                 attn_pooler_queries: int = 256, attn_pooler_heads: int = 8):
         super().__init__()
         if pos_embed_type not in POS_EMBED_TYPES:
             raise ValueError(f"pos_embed_type {pos_embed_type!r}: expected one of {POS_EMBED_TYPES}")
@@ -706,11 +820,15 @@ class VisionTransformer(nn.Module):
         self.patch_dropout = PatchDropout(patch_dropout) if patch_dropout > 0. else nn.Identity()
         self.ln_pre = nn.Identity() if no_ln_pre else LayerNorm(width, eps=eps)
         self.transformer = Transformer(width, layers, heads, mlp_ratio, act_kwargs, eps)
-        self.attn_pool = None
+        if attentional_pool not in (False, True, None):
+            raise ValueError(f"attentional_pool={attentional_pool!r}: only the bool form is built")
+        self.attn_pool = AttentionalPooler(output_dim, width, n_head=attn_pooler_heads, n_queries=attn_pooler_queries) if attentional_pool else None
+        pool_dim = output_dim if attentional_pool else width
         self.pool_type = pool_type
-        self.ln_post = LayerNorm(width, eps=eps)
-        self.proj = nn.Parameter(scale * torch.randn(width, output_dim))
+        self.ln_post = LayerNorm(pool_dim, eps=eps)
+        self.proj = nn.Parameter(scale * torch.randn(pool_dim, output_dim))
         self._pk = _Packed()
+        self._pool_pk = _Packed()
         self._ws = _Workspace()
 
     # -- packed head -----------------------------------------------------------------------------------
@@ -738,7 +856,10 @@ class VisionTransformer(nn.Module):
     def lock(self, unlocked_groups: int = 0, freeze_bn_stats: bool = False) -> None:
         """LiT locking (transformer.py:542-572): freeze the whole tower, then train again the last ``unlocked_groups`` of its
         parameter groups (``_lock_groups``).  ``freeze_bn_stats`` is accepted and has no effect, as in the reference (there is no
-        BatchNorm).  Frozen parameters get no gradient from ``openvision_amd.training``, which then skips their work."""
+        BatchNorm).  Frozen parameters get no gradient from ``openvision_amd.training``, which then skips their work.
+
+        The reference names no parameter of the attentional pooler in any group (transformer.py:542-573): ``lock`` freezes the
+        pooler and no ``unlocked_groups`` value trains it again.  That is mirrored here."""
         self.requires_grad_(False)
         if unlocked_groups:
             for group in self._lock_groups()[-unlocked_groups:]:
@@ -819,7 +940,11 @@ class VisionTransformer(nn.Module):
         for b0 in range(0, bsz, MAX_MICRO_BATCH):
             nb = min(MAX_MICRO_BATCH, bsz - b0)
             kb = None if keep is None else keep[b0:b0 + nb]
-            if not isinstance(self.ln_pre, nn.Identity):
+            if self.attn_pool is not None:
+                # the pooler reads every token of the full stack: no last-block shortcut, no fused head
+                tok = self.transformer(self.ln_pre(self._embed_tokens(img[b0:b0 + nb], kb)))
+                out[b0:b0 + nb] = self._pooled_head(tok, normalize)[0]
+            elif not isinstance(self.ln_pre, nn.Identity):
                 tok = self._embed_tokens(img[b0:b0 + nb], kb)
                 tok = self.transformer(self.ln_pre(tok))
                 out[b0:b0 + nb] = self._head_forward(tok, normalize)
@@ -867,7 +992,37 @@ class VisionTransformer(nn.Module):
                                                 nbytes, stream_ptr()), "ov_vision_head_forward_tokens")
         return out
 
+    def _pooled_head(self, tok: torch.Tensor, normalize: bool):
+        """The attentional-pool tail (transformer.py:636-646): attn_pool over all tokens -> ln_post -> 'tok' / 'avg' -> proj [-> L2].
+        tok [B, L, width] -> (features [B, output_dim] fp32, tokens = ln_post(pool(x))[:, 1:] [B, n_q - 1, output_dim] fp32)."""
+        lib, st = _lib.load(), stream_ptr()
+        y = self.attn_pool(tok)                                    # [B, n_q, E] bf16
+        bsz, nq, e = y.shape
+        g, b = self.ln_post.packed()
+        z = torch.empty(bsz, nq, e, dtype=torch.float32, device=tok.device)
+        check(lib.ov_layernorm(ptr(y), OV_BF16, e, ptr(g), ptr(b), ptr(z), OV_F32, e, bsz * nq, e, float(self.ln_post.eps), st), "ov_layernorm(ln_post)")
+        kp = _round_up(e, 64)
+        pooled = torch.zeros(bsz, kp, dtype=torch.bfloat16, device=tok.device)
+        if self.pool_type == "avg":
+            if nq < 2:
+                raise ValueError("attentional pool with pool_type 'avg' needs at least two queries (the mean runs over queries 1..)")
+            pooled[:, :e] = z[:, 1:].mean(dim=1)
+        else:
+            pooled[:, :e] = z[:, 0]
+        wp = self._pool_pk.get((self.proj,), lambda: _pack_matrix(self.proj.detach().t(), _round_up(self.output_dim, 8), kp))
+        n = wp.shape[0]
+        outb = torch.empty(bsz, n, dtype=torch.bfloat16, device=tok.device)
+        _gemm_bias(ptr(pooled), kp, ptr(wp), kp, None, ptr(outb), n, bsz, n, kp, st, "ov_gemm(proj)")
+        feats = outb[:, : self.output_dim].float()
+        return (l2_normalize(feats) if normalize else feats), z[:, 1:]
+
     def forward(self, x: torch.Tensor):
+        if self.output_tokens and self.attn_pool is not None:
+            self._check_image(x)
+            keep = self._draw_keep(x.shape[0], x.device) if self.dropout_active() else None
+            tok = self.transformer(self.ln_pre(self._embed_tokens(_kernel_input(x.detach()), keep)))
+            pooled, tokens = self._pooled_head(tok, False)
+            return pooled, tokens.to(x.dtype)
         if self.output_tokens:
             self._check_image(x)
             keep = self._draw_keep(x.shape[0], x.device) if self.dropout_active() else None
@@ -899,7 +1054,7 @@ class CLIP(nn.Module):
                                       "GEMM epilogues carry erf and tanh GELU only.  Stock open_clip models trained with nn.GELU "
                                       "(the LAION / DataComp checkpoints) load with quick_gelu=False")
         self.output_dict = output_dict
-        v = vision_cfg_from(vision_cfg)
+        v = vision_cfg_from(vision_cfg, embed_dim)
         t = text_cfg_from(text_cfg)
         self.vision_cfg, self.text_cfg, self.embed_dim = v, t, embed_dim
         self.visual = VisionTransformer(
@@ -907,7 +1062,8 @@ class CLIP(nn.Module):
             heads=v.width // v.head_width, mlp_ratio=v.mlp_ratio, output_dim=embed_dim, pool_type=v.pool_type,
             final_ln_after_pool=v.final_ln_after_pool, no_ln_pre=v.no_ln_pre, act_kwargs=v.act_kwargs,
             eps=ln_eps(v.norm_kwargs), output_tokens=v.output_tokens, patch_dropout=float(v.patch_dropout),
-            pos_embed_type=v.pos_embed_type)
+            pos_embed_type=v.pos_embed_type, attentional_pool=bool(v.attentional_pool),
+            attn_pooler_queries=int(v.attn_pooler_queries), attn_pooler_heads=int(v.attn_pooler_heads))
         # text tower parts are adopted at the top level, as the reference does (model.py:239-248)
         self.transformer = Transformer(t.width, t.layers, t.heads, t.mlp_ratio, t.act_kwargs, ln_eps(t.norm_kwargs))
         self.context_length = t.context_length

@@ -62,6 +62,26 @@ def _block(sd: Dict[str, torch.Tensor], prefix: str, d: int, mlp: int, seed: int
     n("mlp.c_proj.bias", (d,), 0.1)
 
 
+def _attn_pool(sd: Dict[str, torch.Tensor], prefix: str, e: int, d: int, n_queries: int, seed: int) -> None:
+    """AttentionalPooler(d_model=e, context_dim=d) (transformer.py:187-207).  nn.MultiheadAttention packs its three projections as
+    in_proj_weight [3e, e] when kdim == vdim == embed_dim and keeps q / k / v_proj_weight apart otherwise."""
+    n = lambda k, shape, std, mean=0.0: sd.__setitem__(prefix + k, _normal(prefix + k, shape, std, seed, mean))
+    n("query", (n_queries, e), 1.0)
+    if d == e:
+        n("attn.in_proj_weight", (3 * e, e), 1.0 / math.sqrt(e))
+    else:
+        n("attn.q_proj_weight", (e, e), 1.0 / math.sqrt(e))
+        n("attn.k_proj_weight", (e, d), 1.0 / math.sqrt(d))
+        n("attn.v_proj_weight", (e, d), 1.0 / math.sqrt(d))
+    n("attn.in_proj_bias", (3 * e,), 0.1)
+    n("attn.out_proj.weight", (e, e), 0.5 / math.sqrt(e))
+    n("attn.out_proj.bias", (e,), 0.1)
+    n("ln_q.weight", (e,), 0.1, 1.0)
+    n("ln_q.bias", (e,), 0.1)
+    n("ln_k.weight", (d,), 0.1, 1.0)
+    n("ln_k.bias", (d,), 0.1)
+
+
 def make_state_dict(model_cfg: Dict[str, Any], seed: int = 0, variant: str = "v1") -> Dict[str, torch.Tensor]:
     """fp32 state dict for ``CLIP(**model_cfg)`` (reference key names and shapes).
 
@@ -106,7 +126,8 @@ def _make_v1(model_cfg: Dict[str, Any], seed: int = 0) -> Dict[str, torch.Tensor
     d = v.width
     sd["visual.class_embedding"] = _normal("visual.class_embedding", (d,), 0.5, seed)
     sd["visual.positional_embedding"] = posemb_sincos_2d(g, g, d)
-    sd["visual.proj"] = _normal("visual.proj", (d, e), 1.0 / math.sqrt(d), seed)
+    pd = e if v.attentional_pool else d       # the pooler hands ln_post and proj rows of embed_dim (transformer.py:528-535)
+    sd["visual.proj"] = _normal("visual.proj", (pd, e), 1.0 / math.sqrt(pd), seed)
     sd["visual.conv1.weight"] = _normal("visual.conv1.weight", (d, 3, v.patch_size, v.patch_size),
                                         1.0 / math.sqrt(3 * v.patch_size ** 2), seed)
     if not v.no_ln_pre:                       # the stock open_clip image tower (transformer.py:491); OpenVision has none
@@ -114,8 +135,10 @@ def _make_v1(model_cfg: Dict[str, Any], seed: int = 0) -> Dict[str, torch.Tensor
         sd["visual.ln_pre.bias"] = _normal("visual.ln_pre.bias", (d,), 0.1, seed)
     for i in range(v.layers):
         _block(sd, f"visual.transformer.resblocks.{i}.", d, mlp_width(d, v.mlp_ratio), seed)
-    sd["visual.ln_post.weight"] = _normal("visual.ln_post.weight", (d,), 0.1, seed, 1.0)
-    sd["visual.ln_post.bias"] = _normal("visual.ln_post.bias", (d,), 0.1, seed)
+    if v.attentional_pool:
+        _attn_pool(sd, "visual.attn_pool.", e, d, int(v.attn_pooler_queries), seed)
+    sd["visual.ln_post.weight"] = _normal("visual.ln_post.weight", (pd,), 0.1, seed, 1.0)
+    sd["visual.ln_post.bias"] = _normal("visual.ln_post.bias", (pd,), 0.1, seed)
 
     dt = t.width
     sd["token_embedding.weight"] = _normal("token_embedding.weight", (t.vocab_size, dt), 0.5, seed)

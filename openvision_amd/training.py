@@ -427,6 +427,56 @@ class _LinearFn(torch.autograd.Function):
         return (dx[:, :k].to(xd) if need_x else None, dw[:n, :k].to(wd) if need_w else None, db[:n].to(bd) if has_b else None)
 
 
+class _AttnPoolFn(torch.autograd.Function):
+    """The pooler's cross-attention core with gradients: out [B n_q, E] = softmax(scale q k_b^T) v_b on ``ov_attn_pool`` (which keeps the
+    row log-sum-exp), backward on ``ov_attn_pool_backward``.  q [n_q, E]: the projected queries, shared by every image, so d q is the
+    sum over the batch (fixed order, no atomics: bitwise repeatable); kv [B L, 2E]: the K | V projection of the tokens."""
+
+    @staticmethod
+    def forward(ctx, q, kv, bsz, seq, heads):
+        lib = _lib.load()
+        nq, e = q.shape
+        hd = e // heads
+        qb = q.detach().to(torch.bfloat16).contiguous()
+        kvb = kv.detach().to(torch.bfloat16).contiguous()
+        out = torch.empty(bsz * nq, e, dtype=torch.bfloat16, device=q.device)
+        lse = torch.empty(bsz * heads, _round_up(nq, 32), dtype=torch.float32, device=q.device)
+        check(lib.ov_attn_pool(ptr(qb), e, ptr(kvb), 2 * e, ptr(out), e, ptr(lse), bsz, seq, nq, heads, hd, hd ** -0.5, stream_ptr()),
+              "ov_attn_pool")
+        ctx.save_for_backward(qb, kvb, out, lse)
+        ctx.dims = (bsz, seq, nq, heads, hd, q.dtype, kv.dtype)
+        return out.float()
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib = _lib.load()
+        qb, kvb, out, lse = ctx.saved_tensors
+        bsz, seq, nq, heads, hd, qd, kvd = ctx.dims
+        e = heads * hd
+        dob = dout.detach().to(torch.bfloat16).contiguous()
+        dq = torch.empty(nq, e, dtype=torch.float32, device=dout.device)
+        dkv = torch.empty(bsz * seq, 2 * e, dtype=torch.bfloat16, device=dout.device)
+        nb = lib.ov_attn_pool_backward_workspace_bytes(bsz, seq, nq, heads, hd)
+        ws = torch.empty(nb + 256, dtype=torch.uint8, device=dout.device)
+        check(lib.ov_attn_pool_backward(ptr(qb), e, ptr(kvb), 2 * e, ptr(out), e, ptr(dob), e, ptr(lse), ptr(dq), e, ptr(dkv), 2 * e, bsz, seq,
+                                        nq, heads, hd, hd ** -0.5, ptr(ws), nb, stream_ptr()), "ov_attn_pool_backward")
+        return (dq.to(qd) if ctx.needs_input_grad[0] else None, dkv.to(kvd) if ctx.needs_input_grad[1] else None, None, None, None)
+
+
+def attn_pool_forward(pool, x: torch.Tensor) -> torch.Tensor:
+    """``model.AttentionalPooler`` with gradients (transformer.py:201-207): x [B, L, context] -> [B, n_queries, d_model] fp32.  ln_k
+    and ln_q on ``_LayerNormFn``, the three projections and out_proj on ``_LinearFn``, the attention on ``_AttnPoolFn``."""
+    a = pool.attn
+    bsz, seq, d = x.shape
+    e, nq = a.embed_dim, pool.query.shape[0]
+    xk = _LayerNormFn.apply(x, pool.ln_k.weight, pool.ln_k.bias, pool.ln_k.eps)
+    qn = _LayerNormFn.apply(pool.query, pool.ln_q.weight, pool.ln_q.bias, pool.ln_q.eps)
+    qp = _LinearFn.apply(qn, a.q_weight(), a.in_proj_bias[:e])
+    kv = _LinearFn.apply(xk.reshape(bsz * seq, d), a.kv_weight(), a.in_proj_bias[e:])
+    o = _AttnPoolFn.apply(qp, kv, bsz, seq, a.num_heads)
+    return _LinearFn.apply(o, a.out_proj.weight, a.out_proj.bias).view(bsz, nq, e)
+
+
 class _LayerNormFn(torch.autograd.Function):
     """LayerNorm (transformer.py:15-30: fp32 statistics) on ov_layernorm / ov_layernorm_backward: ln_post on the pooled rows, ln_final
     on the text tokens."""
@@ -616,6 +666,10 @@ def encode_image(model, image: torch.Tensor, normalize: bool = True, keep: torch
     ``output_tokens``: also return what the reference hands to the caption decoder (vit.py:753,786): the block stack's output without
     the CLS token and BEFORE ln_post, [B, L - 1, width] (the kept patches under patch dropout), with gradients into the tower.
 
+    A tower with ``attentional_pool`` (transformer.py:636-640) pools all 1 + K tokens with ``attn_pool_forward``, applies ln_post to
+    the n_q pooled rows and takes 'tok' / 'avg' over them; its ``output_tokens`` are the reference's for that branch,
+    ``ln_post(pool(x))[:, 1:]`` [B, n_q - 1, embed_dim].
+
     ``drop``: the image tower's drop-path table (``tower_forward``)."""
     v = model.visual
     p = v.patch_size[0]
@@ -644,7 +698,10 @@ def encode_image(model, image: torch.Tensor, normalize: bool = True, keep: torch
         x = _LayerNormFn.apply(x, v.ln_pre.weight, v.ln_pre.bias, v.ln_pre.eps)
     x = tower_forward(v.transformer, x, drop=drop)
     tokens = x[:, 1:]
-    if v.final_ln_after_pool:
+    if v.attn_pool is not None:                                    # :636-640: pool all tokens, ln_post, then 'tok' / 'avg' over the queries
+        xx = _LayerNormFn.apply(attn_pool_forward(v.attn_pool, x), v.ln_post.weight, v.ln_post.bias, v.ln_post.eps)
+        pooled, tokens = (xx[:, 1:].mean(dim=1) if v.pool_type == "avg" else xx[:, 0]), xx[:, 1:]
+    elif v.final_ln_after_pool:
         pooled = x[:, 1:].mean(dim=1) if v.pool_type == "avg" else x[:, 0]
         pooled = _LayerNormFn.apply(pooled, v.ln_post.weight, v.ln_post.bias, v.ln_post.eps)
     else:
@@ -750,6 +807,10 @@ def decode(decoder, image_tokens: torch.Tensor, text_tokens: torch.Tensor, drop:
     bsz, li, _ = image_tokens.shape
     lt = text_tokens.shape[1]
     w = decoder.width
+    if image_tokens.shape[-1] != decoder.image_projection.in_features:
+        raise ValueError(f"decode: image tokens of width {image_tokens.shape[-1]}, but the decoder was built with image_width="
+                         f"{decoder.image_projection.in_features} (a tower with attentional_pool hands over its pooler's tokens, of "
+                         f"width embed_dim)")
     xi = _LinearFn.apply(image_tokens.reshape(bsz * li, -1), decoder.image_projection.weight, None).view(bsz, li, w)
     xt = _LinearFn.apply(text_tokens.reshape(bsz * lt, -1), decoder.text_projection.weight, None).view(bsz, lt, w)
     lr = decoder.learnable_tokens.float().unsqueeze(0).expand(bsz, -1, -1)
@@ -846,9 +907,10 @@ def accumulated_step(model, batches, loss, decoder=None, caption_targets=None, c
 # --------------------------------------------------------------------------------------------------------------------------
 def default_decay_filter(name: str, p: torch.Tensor) -> bool:
     """The reference decays '.*/kernel$' only (build_optax.py:259: Dense / Conv kernels): here the 2-D (and conv) weight matrices;
-    biases, LayerNorm parameters, class / positional / token embeddings, the logit scale and the logit bias are not decayed."""
+    biases, LayerNorm parameters, class / positional / token embeddings, the attentional pooler's ``query`` (no kernel in that rule; its projection matrices are decayed), the logit scale and the
+    logit bias are not decayed."""
     if (name.endswith("token_embedding.weight") or "positional_embedding" in name or name.endswith("class_embedding")
-            or name.endswith("learnable_tokens")):
+            or name.endswith("learnable_tokens") or name.endswith("attn_pool.query")):
         return False
     return p.dim() >= 2
 
